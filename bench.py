@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- read-pairs/s of the FEDRANN hot path (embed -> normalise -> all-pairs cosine k-NN).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--dim D] [--knn k]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--dim D] [--knn k] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one pass of the hot path over the whole synthetic read set: every rank embeds and
@@ -67,7 +67,13 @@ def parse_args():
     p.add_argument("--host-steps", type=int, default=0,
                    help="steps of the host-to-host pass over the full CSR (0 = --steps, like the device-resident run); the "
                         "compacted-CSR variant runs min(3, that)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (k-NN indices and distances, the "
+                        "embedding) as DIR/<name>.npy: all rows if they fit in 64 MB, else a fixed seeded sample of rows")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def cpu_budget():
@@ -207,6 +213,46 @@ def cpu_baseline(s, P, d, k, target_seconds, gpu_result=None):
                    "%d rows (%.2fs+%.2fs), k-NN of %d of %d query rows vs all targets in %.2fs, "
                    "extrapolated x%.1f in queries" % (n, t_embed, t_norm, nq, n, t_knn, n / nq)),
     }
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: the most all files together may hold (npy headers included)
+DUMP_SEED = 7919         # --dump-outputs: the row sample (fixed: two builds of the project dump the same rows)
+
+
+def dump_outputs(path, out, lo, n, k, d, world, rank):
+    """--dump-outputs: the last timed step's results as DIR/<name>.npy.  rows.npy (float64) = the global row numbers
+    dumped, ascending; indices.npy (float64, exact for int32) and distances.npy (float32) = their k-NN lists;
+    embedding.npy (float32) = their rows of E.  Every row when the files fit in DUMP_BYTES, else a sample of rows drawn
+    with DUMP_SEED from [0, n): the same rows whatever the build or the number of ranks.  Collective when world > 1;
+    rank 0 writes."""
+    import numpy as np
+    import torch
+    idx, dst, E = out
+    per_row = 8 + 8 * k + 4 * k + 4 * d
+    m = min(n, (DUMP_BYTES - 4 * 4096) // per_row)  # (4 KB per file covers an npy header)
+    rows = np.arange(n) if m == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=m, replace=False))
+    mine = rows[(rows >= lo) & (rows < lo + idx.shape[0])]
+    sel = torch.from_numpy(mine - lo).to(idx.device)
+    parts = [(mine, idx.index_select(0, sel).cpu().numpy(), dst.index_select(0, sel).cpu().numpy(),
+              E.index_select(0, sel).cpu().numpy())]
+    if world > 1:
+        import torch.distributed as dist
+        gathered = [None] * world
+        dist.all_gather_object(gathered, parts[0])
+        parts = gathered
+    if rank != 0:
+        return
+    got = np.concatenate([p[0] for p in parts])
+    assert np.array_equal(got, rows), "dump: the ranks' rows do not cover the sample"
+    os.makedirs(path, exist_ok=True)
+    arrays = {"rows": rows.astype(np.float64),
+              "indices": np.concatenate([p[1] for p in parts]).astype(np.float64),
+              "distances": np.concatenate([p[2] for p in parts]).astype(np.float32),
+              "embedding": np.concatenate([p[3] for p in parts]).astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print("bench.py: dumped %d of %d rows (%s) to %s" % (m, n, ", ".join("%s %s" % (nm, a.shape) for nm, a in arrays.items()),
+                                                         path), file=sys.stderr)
 
 
 def main():
@@ -351,6 +397,8 @@ def main():
         return dt, kms, kcnt, res
 
     elapsed, kernel_ms, kernel_cnt, out = timed_run(args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, pipe.lo, n, k, d, world, rank)
     uncertified = ctx.last_uncertified()
     uniq_t, uniq_q = ctx.last_unique()  # rows actually searched (duplicate-row classes)
     pass_launches, pass_queues = ctx.last_prefilter_launches()
