@@ -21,7 +21,7 @@ SYMBOLS = (
     "fdr_overlaps_write", "fdr_last_prefilter_launches", "fdr_knn_classes_dev", "fdr_knn_unique_dev",
     "fdr_knn_expand_dev", "fdr_kmer_output_scan_range", "fdr_kmer_output_load_range",
     "fdr_kmer_count_begin", "fdr_kmer_count_add", "fdr_kmer_count_finish", "fdr_reads_scan", "fdr_reads_parse",
-    "fdr_kmer_output_append", "fdr_last_query_paths",
+    "fdr_kmer_output_append", "fdr_last_query_paths", "fdr_last_knn_trace",
 )
 FDR_MAX_K = 128
 KERNELS = ("embed_csr", "normalize_rows", "knn_tile", "knn_merge", "knn_prefilter", "knn_rerank",
@@ -29,6 +29,20 @@ KERNELS = ("embed_csr", "normalize_rows", "knn_tile", "knn_merge", "knn_prefilte
 FDR_MAX_DIM = 2048
 # fdr_last_query_paths codes (include/fedrann_hip.h: FDR_PATH_*)
 PATH_CERTIFIED, PATH_RANGE, PATH_EXACT, PATH_ZERO, PATH_RANGE_OVERFLOW, PATH_GENERIC, PATH_CLASS_MEMBER = 1, 2, 3, 4, 5, 6, 0x80
+# fdr_last_knn_trace (include/fedrann_hip.h: FDR_TRACE_*, FDR_FALLBACK_*)
+TRACE_KINDS = ("none", "exact", "prefilter", "generic")
+FALLBACKS = ("none", "chunked", "whole")
+
+
+class KnnTrace(ctypes.Structure):
+    """struct fdr_knn_trace (include/fedrann_hip.h), field for field."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("kind", "dp", "k", "kp")] + \
+        [(n, ctypes.c_int64) for n in ("queries", "targets")] + \
+        [(n, ctypes.c_int32) for n in (
+            "pass_waves", "pass_wps", "pass_units", "pass_list_keys", "pass_pingpong", "pass_launches", "pass_queues",
+            "pass_segments", "uncertified", "zero_queries", "range_queries", "range_chunks", "range_pp_chunks",
+            "range_w8_chunks", "range_overflow", "exact_fallback", "exact_calls", "exact_queries", "exact_waves",
+            "exact_qsets", "generic")]
 
 
 class FedrannHipError(RuntimeError):
@@ -90,6 +104,7 @@ def load_library():
     L.fdr_knn_expand_dev.argtypes = [vp, i64, i64, i64, vp, vp, i64, vp, vp, vp]
     L.fdr_last_uncertified.argtypes = [vp]
     L.fdr_last_query_paths.argtypes = [vp, vp, i64]
+    L.fdr_last_knn_trace.argtypes = [vp, ctypes.POINTER(KnnTrace)]
     L.fdr_set_knn_mode.argtypes = [vp, ctypes.c_int]
     L.fdr_set_dedup_mode.argtypes = [vp, ctypes.c_int]
     L.fdr_last_unique.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
@@ -420,6 +435,16 @@ class Context:
         member of a duplicate-row class of several rows): fdr_last_query_paths.  Diagnostics; the tests' strata."""
         out = np.empty(int(n_queries), dtype=np.uint8)
         self._check(self._L.fdr_last_query_paths(self._h, _ptr(out), int(n_queries)), "fdr_last_query_paths")
+        return out
+
+    def last_knn_trace(self):
+        """dict of fdr_last_knn_trace: which kernels the last k-NN call ran ("kind" and "exact_fallback" as names).
+        Diagnostics; the tests assert the variant they meant to run with it."""
+        t = KnnTrace()
+        self._check(self._L.fdr_last_knn_trace(self._h, ctypes.byref(t)), "fdr_last_knn_trace")
+        out = {name: int(getattr(t, name)) for name, _ in KnnTrace._fields_}
+        out["kind"] = TRACE_KINDS[out["kind"]]
+        out["exact_fallback"] = FALLBACKS[out["exact_fallback"]]
         return out
 
     def timing(self, enable):

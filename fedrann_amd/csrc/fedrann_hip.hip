@@ -484,6 +484,7 @@ struct fdr_ctx {
         uint8_t all = 0;
         hipStream_t stream = nullptr;
     } paths;
+    fdr_knn_trace trace = {};  // fdr_last_knn_trace: the kernels the last k-NN call ran
     // duplicate-row classes built by fdr_knn_classes_dev for the calls that follow it (fdr_knn_unique_dev /
     // fdr_knn_expand_dev): the tables live in the caller's workspace
     struct {
@@ -628,6 +629,20 @@ FDR_EXPORT int fdr_last_prefilter_launches(fdr_ctx *ctx, int *launches, int *que
     *launches = ctx->last_pass_launches;
     *queues = ctx->last_pass_queues;
     return FDR_OK;
+}
+
+FDR_EXPORT int fdr_last_knn_trace(fdr_ctx *ctx, fdr_knn_trace *out) {
+    if (!ctx || !out) return fail(FDR_E_ARG, "bad argument");
+    *out = ctx->trace;
+    return FDR_OK;
+}
+
+// Every k-NN entry point starts here, before its argument checks: no earlier call's trace or path codes survive it.
+static void knn_call_begin(fdr_ctx *ctx) {
+    ctx->trace = fdr_knn_trace{};
+    ctx->paths.dev = nullptr;
+    ctx->paths.n = 0;
+    ctx->paths.all = FDR_PATH_NONE;
 }
 
 FDR_EXPORT int fdr_set_knn_mode(fdr_ctx *ctx, int mode) {
@@ -903,6 +918,10 @@ static int launch_knn_exact(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_
     const KnnShape &sh = kShapes[p.shape];
     const size_t lds = knn_lds_bytes(sh, k);
     if (lds > 160 * 1024) return fail(FDR_E_ARG, "knn: k=%d, d=%d needs %zu B of LDS (> 160 KiB)", k, d, lds);
+    ctx->trace.exact_calls++;
+    ctx->trace.exact_queries += (int32_t)nq;
+    ctx->trace.exact_waves = sh.nw;
+    ctx->trace.exact_qsets = sh.nq;
     const int dbg = dev_knobs().debug;  // (development builds only; 0 in the release library)
     (void)dbg;
     // the nqb * nseg work items in one launch, or (p.cohort > 0: knn_plan_compute) in synchronised rounds dealt to
@@ -1107,6 +1126,18 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     const int pshape = prefilter_shape(dp, kp, nq, ctx->num_cus, nt);
     const KnnPlan p = knn_plan(ctx->num_cus, nq, nt, d, kp, pshape);
     const KnnShape &sh = kShapes[pshape];
+    fdr_knn_trace &tr = ctx->trace;
+    tr.kind = FDR_TRACE_PREFILTER;
+    tr.dp = dp;
+    tr.k = k;
+    tr.kp = kp;
+    tr.queries = nq;
+    tr.targets = nt;
+    tr.pass_waves = sh.nw;
+    tr.pass_wps = sh.wps;
+    tr.pass_units = sh.tps;
+    tr.pass_list_keys = kp <= 32 ? 16 : 32;
+    tr.pass_segments = p.nseg;
     unsigned *d_bits = reinterpret_cast<unsigned *>(ws);
     unsigned *d_shared = reinterpret_cast<unsigned *>(ws + p.bits_bytes);
     u64 *d_partial = reinterpret_cast<u64 *>(ws + p.bits_bytes + p.shared_bytes);
@@ -1219,6 +1250,7 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
         } else if (dp == 128) FDR_SHAPE_CASE(2, FDR_LAUNCH_PRE(128, 1, 4, 4, 2));
         else if (sh.nw == 8 && sh.wps == 2 && (sh.tps == 16 || (dp == 512 && sh.tps == 8)) && dev_knobs().pp != 0) {
             // the ping-pong kernel (knn_prefilter_pp.inc)
+            tr.pass_pingpong = 1;
             if (dp == 256) {
                 if (kp <= 32) FDR_SHAPE_CASE(3, FDR_LH_CASE(16, FDR_LAUNCH_PRE3((knn_prefilter_pp_kernel<256, 8, 16>), 512)));
                 else FDR_SHAPE_CASE(3, FDR_LH_CASE(32, FDR_LAUNCH_PRE3((knn_prefilter_pp_kernel<256, 8, 32>), 512)));
@@ -1249,6 +1281,8 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     if ((lrc = launch_items(0, n_items))) return lrc;
     ctx->last_pass_launches = li;
     ctx->last_pass_queues = nqueues;
+    tr.pass_launches = li;
+    tr.pass_queues = nqueues;
     if ((lrc = join())) return lrc;  // the merge below (on `st`) needs the other queues' launches too
     if (nqueues > 1 && (trc = timing_end(ctx, FDR_KERNEL_KNN_PREFILTER, st))) return trc;
 #ifdef FDR_STAMPS
@@ -1315,6 +1349,9 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     int count = counts[0];
     const int zcount = counts[1], rcount = counts[2];
     ctx->last_flagged = count + rcount;
+    tr.uncertified = count;
+    tr.zero_queries = zcount;
+    tr.range_queries = rcount;
     if (rcount > 0) {  // plateau queries: collect {d~ <= theta} with a second fp16 pass, rank it exactly
         if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
         _Float16 *d_hqc = reinterpret_cast<_Float16 *>(ws + L.off_hqc);
@@ -1359,6 +1396,9 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
 #undef FDR_LAUNCH_RANGE
 #undef FDR_LAUNCH_RANGE_PP
             HIP_TRY(hipGetLastError());
+            tr.range_chunks++;
+            tr.range_pp_chunks += use_pp ? 1 : 0;
+            tr.range_w8_chunks += wide ? 1 : 0;
             hipLaunchKernelGGL(knn_rerank_long_kernel, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st,
                                (const int *)(d_rlist + first), c, (const int *)d_cnt, (const int *)d_rcand, k,
                                d_Qhat, d_That, dp, (int)t_base, d_idx, d_dist, d_counter, d_flagged, d_path);
@@ -1368,12 +1408,19 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
         // ranges that overflowed were appended to the exact list: read its final length
         HIP_TRY(hipMemcpyAsync(counts, d_counter, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
+        tr.range_overflow = counts[0] - count;
         count = counts[0];
     }
     if (count <= 0) return FDR_OK;
-    if ((int64_t)count * 2 > nq - zcount)  // the prefilter did not help on this input: exact pass for everyone
+    if ((int64_t)count * 2 > nq - zcount) {  // the prefilter did not help on this input: exact pass for everyone
+        tr.exact_fallback = FDR_FALLBACK_WHOLE;
+        // every row, the all-zero ones too, is recomputed by the exact kernel: its code, as in exact mode
+        ctx->paths.dev = nullptr;
+        ctx->paths.all = FDR_PATH_EXACT;
         return launch_knn_exact(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist,
                                 d_ws, L.knn_bytes, st);
+    }
+    tr.exact_fallback = FDR_FALLBACK_CHUNKED;
     for (int first = 0; first < count; first += L.chunk) {
         const int c = std::min(L.chunk, count - first);
         hipLaunchKernelGGL(gather_queries_kernel, dim3((unsigned)c), dim3(256), 0, st, d_Qhat, d_qzero,
@@ -1408,6 +1455,11 @@ static int launch_knn_mode(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_q
     ctx->paths.dev = nullptr;
     ctx->paths.n = nq;
     ctx->paths.all = FDR_PATH_EXACT;
+    ctx->trace.kind = FDR_TRACE_EXACT;
+    ctx->trace.dp = dp;
+    ctx->trace.k = k;
+    ctx->trace.queries = nq;
+    ctx->trace.targets = nt;
     return launch_knn_exact(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist,
                             d_ws, ws_bytes, st);
 }
@@ -1485,6 +1537,12 @@ static int launch_knn(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero,
         ctx->paths.dev = nullptr;
         ctx->paths.n = nq;
         ctx->paths.all = FDR_PATH_GENERIC;
+        ctx->trace.kind = FDR_TRACE_GENERIC;
+        ctx->trace.dp = dp;
+        ctx->trace.k = k;
+        ctx->trace.queries = nq;
+        ctx->trace.targets = nt;
+        ctx->trace.generic = 1;
         int trc = timing_begin(ctx, FDR_KERNEL_KNN_TILE, st);
         if (trc) return trc;
         hipLaunchKernelGGL(knn_generic_kernel, dim3((unsigned)((nq + GEN_QPB - 1) / GEN_QPB)), dim3(256),
@@ -1631,6 +1689,7 @@ FDR_EXPORT int fdr_knn_classes_dev(fdr_ctx *ctx, const float *d_That, const uint
                                    int32_t *n_unique_out) {
     int rc = use_device(ctx);
     if (rc) return rc;
+    knn_call_begin(ctx);
     hipStream_t st = (hipStream_t)stream;
     ctx->cls.valid = false;
     if (!n_unique_out) return fail(FDR_E_ARG, "knn_classes: n_unique_out is null");
@@ -1703,6 +1762,7 @@ FDR_EXPORT int fdr_knn_unique_dev(fdr_ctx *ctx, int64_t u_lo, int64_t u_hi, int3
                                   void *stream) {
     int rc = use_device(ctx);
     if (rc) return rc;
+    knn_call_begin(ctx);
     if (!ctx->cls.valid) return fail(FDR_E_STATE, "knn_unique: no classes (call fdr_knn_classes_dev first)");
     if (u_lo < 0 || u_hi < u_lo || u_hi > ctx->cls.nu || u_hi - u_lo > ctx->cls.nq_max)
         return fail(FDR_E_ARG, "knn_unique: bad range [%lld, %lld) of %d unique rows (at most %lld per call)",
@@ -1729,6 +1789,7 @@ FDR_EXPORT int fdr_knn_expand_dev(fdr_ctx *ctx, int64_t q0, int64_t nq, int64_t 
                                   void *stream) {
     int rc = use_device(ctx);
     if (rc) return rc;
+    knn_call_begin(ctx);
     if (!ctx->cls.valid) return fail(FDR_E_STATE, "knn_expand: no classes (call fdr_knn_classes_dev first)");
     if (q0 < 0 || nq < 0 || q0 + nq > ctx->cls.nt) return fail(FDR_E_ARG, "knn_expand: bad row range");
     if (nq == 0) return FDR_OK;
@@ -1775,6 +1836,7 @@ FDR_EXPORT int fdr_knn_dev(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_q
                            size_t workspace_bytes, void *stream) {
     int rc = use_device(ctx);
     if (rc) return rc;
+    knn_call_begin(ctx);
     if (d_workspace == ctx->cls.ws) ctx->cls.valid = false;  // (this call overwrites the tables fdr_knn_classes_dev left there)
     return launch_knn(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist,
                       d_workspace, workspace_bytes, (hipStream_t)stream);
@@ -2014,6 +2076,7 @@ FDR_EXPORT int fdr_knn(fdr_ctx *ctx, const float *E, int64_t n, int32_t d, int32
                        int32_t *idx_out, float *dist_out) {
     int rc = use_device(ctx);
     if (rc) return rc;
+    knn_call_begin(ctx);
     if (!E || n <= 0) return fail(FDR_E_ARG, "knn: empty input");
     if (fdr_padded_dim(d) < 0) return fail(FDR_E_ARG, "knn: dimension %d unsupported (1..%d)", d, FDR_MAX_DIM);
     if ((rc = ctx->E.reserve((size_t)n * d * 4))) return rc;
@@ -2026,6 +2089,7 @@ FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indp
                              float *E_out) {
     int rc = use_device(ctx);
     if (rc) return rc;
+    knn_call_begin(ctx);
     if ((rc = check_csr(n_rows, a_indptr, a_indices))) return rc;
     if (ctx->n_features <= 0) return fail(FDR_E_STATE, "embed: no projection loaded");
     if (n_rows <= 0) return fail(FDR_E_ARG, "embed_knn: empty input");

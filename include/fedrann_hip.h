@@ -196,6 +196,43 @@ int fdr_last_unique(fdr_ctx *ctx, int *unique_targets, int *unique_queries);
  * of kernel launches and of queues they were dealt to (with two queues two launches are in flight at any
  * time and FDR_KERNEL_KNN_PREFILTER is ONE timed span over the whole pass; 0 / 0 after an exact-mode call). */
 int fdr_last_prefilter_launches(fdr_ctx *ctx, int *launches, int *queues);
+/* Diagnostics (test support; nothing in the product reads it): which kernels the most recent k-NN call ran.  With
+ * the duplicate-row layer active it describes the inner search of the unique rows.  Every k-NN entry point
+ * (fdr_knn_dev, fdr_knn, fdr_embed_knn, fdr_knn_classes_dev, fdr_knn_unique_dev, fdr_knn_expand_dev) clears it, and
+ * the per-query path codes, before it checks its arguments. */
+#define FDR_TRACE_NONE 0       /* no k-NN search ran (a cleared trace, or a call that failed or found nothing to do) */
+#define FDR_TRACE_EXACT 1      /* exact mode: the fp32 kernel for every query */
+#define FDR_TRACE_PREFILTER 2  /* fp16 candidate pass + certificate (+ range pass, + exact fallback) */
+#define FDR_TRACE_GENERIC 3    /* d > 512 or k > 64: the generic kernel */
+#define FDR_FALLBACK_NONE 0
+#define FDR_FALLBACK_CHUNKED 1 /* the uncertified queries gathered and searched by the exact kernel, in chunks */
+#define FDR_FALLBACK_WHOLE 2   /* more than half the non-zero queries uncertified: the exact kernel for every query */
+typedef struct fdr_knn_trace {
+    int32_t kind;              /* FDR_TRACE_* */
+    int32_t dp, k, kp;         /* padded dimension, neighbours, candidates per query of the pass (prefilter only) */
+    int64_t queries, targets;  /* rows of the search described (the unique rows with the duplicate-row layer) */
+    /* candidate pass (prefilter only) */
+    int32_t pass_waves;        /* waves per workgroup: 4 or 8 */
+    int32_t pass_wps;          /* waves per SIMD of the shape: 4 (128 VGPRs), 3 (168), 2 (256) */
+    int32_t pass_units;        /* one-tile stage units of the LDS ring */
+    int32_t pass_list_keys;    /* keys per register list: 16 (K' <= 32) or 32 */
+    int32_t pass_pingpong;     /* 1: knn_prefilter_pp_kernel */
+    int32_t pass_launches, pass_queues, pass_segments;
+    /* certificate outcome (read back by the host) and range pass */
+    int32_t uncertified, zero_queries;  /* rows sent to the exact list by the certificate; all-zero queries */
+    int32_t range_queries;     /* plateau queries of the range pass */
+    int32_t range_chunks;      /* its launches (at most 32768 queries each) ... */
+    int32_t range_pp_chunks;   /* ... of them on knn_range_pp_kernel (>= 4096 queries in the chunk) */
+    int32_t range_w8_chunks;   /* ... of them on the eight-wave d <= 128 range kernel */
+    int32_t range_overflow;    /* exact-list entries added by the range pass (sets above its capacity) */
+    /* exact fp32 kernel */
+    int32_t exact_fallback;    /* FDR_FALLBACK_* (prefilter only) */
+    int32_t exact_calls;       /* searches on the exact kernel (whole call = 1; chunked fallback = its chunks) */
+    int32_t exact_queries;     /* queries they searched */
+    int32_t exact_waves, exact_qsets;  /* shape of the last one: waves per workgroup, query sets per wave (0: none) */
+    int32_t generic;           /* 1: the generic kernel ran */
+} fdr_knn_trace;
+int fdr_last_knn_trace(fdr_ctx *ctx, fdr_knn_trace *out);
 /* Prefilter mode only: number of query rows of the most recent k-NN call whose candidate set could
  * not be certified and that were therefore searched by the exact kernel. */
 int fdr_last_uncertified(fdr_ctx *ctx);

@@ -134,6 +134,7 @@ def run_rank_share(ctx, oracle, R, d, k, doubling, ranks=8, rank=0, sample=64, p
                 prefilter_pflops_on_unique_rows=(2.0 * ut * uq * d / (info["kernels_ms"]["knn_prefilter"] * 1e-3) / 1e15
                                                  if info["kernels_ms"].get("knn_prefilter") else None))
     paths = ctx.last_query_paths(nq)  # (before the workspace is used again)
+    info["knn_trace"] = ctx.last_knn_trace()
     idx_keep, dst_keep = idx.clone(), dst.clone()
     # rows of the block that share their normalised row, bit for bit, with another row of the matrix -- counted
     # independently of the library (a 64-bit hash of the row's bits, torch on the device)
@@ -229,3 +230,22 @@ def assert_rank_share(info):
     for name in c:
         assert t[name] == min(c[name], info["path_sample_per_stratum"]), (name, c, t)
     assert c["certified"] > 0 and c["range"] >= 64 and c["zero"] > 0 and c["class_member"] >= 64, c
+    assert_trace_strata(info["knn_trace"], c)
+
+
+def assert_trace_strata(tr, c):
+    """Every way the trace of the call says some rows took shows up as a non-empty stratum of the path codes (and so
+    gave the oracle its rows)."""
+    assert tr["kind"] == "prefilter", tr
+    if tr["exact_fallback"] == "whole":
+        assert c["exact"] == sum(c[s] for s in ("certified", "range", "exact", "zero")), (tr, c)
+        return
+    if tr["uncertified"] + tr["range_overflow"] > 0:
+        assert c["exact"] > 0, (tr, c)
+    if tr["range_overflow"] > 0:
+        assert c["overflow"] > 0, (tr, c)
+    if tr["range_queries"] > tr["range_overflow"]:
+        assert c["range"] > 0, (tr, c)
+    if tr["zero_queries"] > 0:
+        assert c["zero"] > 0, (tr, c)
+    assert c["certified"] > 0, (tr, c)

@@ -9,7 +9,7 @@ import numpy as np
 
 from fedrann_amd import _lib
 
-STRATA = ("certified", "range", "exact", "zero", "class_member", "range_in_class", "edges")
+STRATA = ("certified", "range", "exact", "overflow", "zero", "class_member", "range_in_class", "edges")
 
 
 def strata_masks(paths):
@@ -22,6 +22,7 @@ def strata_masks(paths):
         "certified": code == _lib.PATH_CERTIFIED,
         "range": code == _lib.PATH_RANGE,
         "exact": (code == _lib.PATH_EXACT) | (code == _lib.PATH_RANGE_OVERFLOW) | (code == _lib.PATH_GENERIC),
+        "overflow": code == _lib.PATH_RANGE_OVERFLOW,  # (a part of "exact": the range pass's set exceeded its capacity)
         "zero": code == _lib.PATH_ZERO,
         "class_member": member,
         "range_in_class": member & (code == _lib.PATH_RANGE),  # (a plateau query whose result was expanded from its class)

@@ -13,6 +13,9 @@ for bit, + whole-result properties."""
 import numpy as np
 import pytest
 
+from _rank_share import assert_trace_strata
+from _strata import stratified_rows
+
 pytestmark = pytest.mark.gpu
 
 
@@ -56,20 +59,27 @@ def _check_rank_share(ctx, oracle, E, nq, k, sample=256):
     idx, dst = eng.knn(Ehat[:nq], zero[:nq], nq, Ehat, zero, n, d, k)
     torch.cuda.synchronize(dev)
     ut, uq = ctx.last_unique()
+    paths, trace = ctx.last_query_paths(nq), ctx.last_knn_trace()
     idx, dst = idx.cpu().numpy(), dst.cpu().numpy()
     # whole-result properties: keys strictly ascending per row, indices in range, distances in [0, 1]
     key = dst.view(np.uint32).astype(np.uint64) << np.uint64(32) | idx.astype(np.uint64)
     assert np.all(key[:, 1:] > key[:, :-1])
     assert idx.min() >= 0 and idx.max() < n and dst.min() >= 0 and dst.max() <= 1
-    # sampled exact oracle over ALL targets (incl. all-zero query rows and the block's first / last rows)
+    # exact oracle over ALL targets for rows drawn per execution path (tests/_strata.py: every stratum the path codes
+    # report, the block's first / last rows) -- a uniform sample meets the range, overflow and exact rows by chance only
+    rows, counts, _ = stratified_rows(paths, per=max(32, sample // 4), seed=1)
+    if trace["kind"] == "prefilter":
+        assert_trace_strata(trace, counts)
     Eh_host, _, z_host = oracle.normalize(E.cpu().numpy())
-    rng = np.random.default_rng(1)
-    zr = np.flatnonzero(z_host[:nq])[:16]
-    rows = np.unique(np.concatenate([rng.choice(nq, size=sample, replace=False), zr, [0, 1, nq - 2, nq - 1]]))
     wi, wd = oracle.knn_normalized(Eh_host[rows], z_host[rows], Eh_host, z_host, k)
     assert np.array_equal(idx[rows], wi)
     assert np.array_equal(dst[rows].view(np.uint32), wd.view(np.uint32))
-    return ut, uq
+    return ut, uq, trace
+
+
+def _pass(trace):
+    """The candidate pass's instantiation from the trace: (DP, waves per workgroup, stage units, list keys, ping-pong)."""
+    return (trace["dp"], trace["pass_waves"], trace["pass_units"], trace["pass_list_keys"], trace["pass_pingpong"])
 
 
 def _real_rank_share(ctx, oracle, tag, **kw):
@@ -122,8 +132,12 @@ def test_reference_default_dimension_500_in_rounds(ctx, oracle):
     ctx.set_knn_mode("auto")
     ctx.set_dedup_mode("auto")
     E = _device_embeddings(600_000, 500, nnz=8, loci=250_000, seed=6)
-    _check_rank_share(ctx, oracle, E, 150_000, 50, sample=128)
-    assert ctx.last_prefilter_launches()[1] == 2
+    _, uq, tr = _check_rank_share(ctx, oracle, E, 150_000, 50, sample=128)
+    # K' = 62 at DP = 512: the four-wave four-unit shape below 512 blocks of 256 unique queries per CU, the ping-pong
+    # kernel <512, 4, 32> (four-unit stages) from there; either way in rounds on two queues
+    pp = uq > 2 * 256 * ctx.device_info()["cus"] - 256
+    assert _pass(tr) == ((512, 8, 8, 32, 1) if pp else (512, 4, 8, 32, 0)), (uq, tr)
+    assert tr["pass_launches"] > 1 and tr["pass_queues"] == 2, tr
 
 
 def test_ping_pong_kernel_short_lists_d256_and_d500(ctx, oracle):
@@ -134,12 +148,14 @@ def test_ping_pong_kernel_short_lists_d256_and_d500(ctx, oracle):
     ctx.set_knn_mode("auto")
     ctx.set_dedup_mode("auto")
     E = _device_embeddings(400_000, 256, nnz=8, loci=150_000, seed=8, doubling=True)
-    _check_rank_share(ctx, oracle, E[:200_000].contiguous(), 200_000, 20, sample=128)
-    assert ctx.last_prefilter_launches()[1] == 2  # (launches of one workgroup per CU on two queues)
+    _, uq, tr = _check_rank_share(ctx, oracle, E[:200_000].contiguous(), 200_000, 20, sample=128)
+    assert _pass(tr) == (256, 8, 16, 16, 1), (uq, tr)  # knn_prefilter_pp_kernel<256, 8, 16>
+    assert tr["pass_queues"] == 2  # (launches of one workgroup per CU on two queues)
     del E
     E = _device_embeddings(600_000, 500, nnz=8, loci=250_000, seed=9)
-    _check_rank_share(ctx, oracle, E, 150_000, 20, sample=128)
-    assert ctx.last_prefilter_launches()[1] == 2
+    _, uq, tr = _check_rank_share(ctx, oracle, E, 150_000, 20, sample=128)
+    assert _pass(tr) == (512, 8, 16, 16, 1), (uq, tr)  # knn_prefilter_pp_kernel<512, 8, 16>
+    assert tr["pass_queues"] == 2
 
 
 def test_rank_slice_of_one_million_rows_d128_in_one_launch(ctx, oracle):
@@ -150,9 +166,10 @@ def test_rank_slice_of_one_million_rows_d128_in_one_launch(ctx, oracle):
     ctx.set_knn_mode("auto")
     ctx.set_dedup_mode("auto")
     E = _device_embeddings(1_000_000, 128, nnz=8, loci=400_000, seed=11)
-    ut, uq = _check_rank_share(ctx, oracle, E, 110_000, 20, sample=192)  # (a ninth: 430 query blocks of 256)
+    ut, uq, tr = _check_rank_share(ctx, oracle, E, 110_000, 20, sample=192)  # (a ninth: 430 query blocks of 256)
     assert 65_536 <= uq <= 117_900 and ut >= 4 * uq  # (256 .. 460 blocks of 256 unique queries on 256 CUs)
-    assert ctx.last_prefilter_launches() == (1, 1)
+    assert _pass(tr) == (128, 8, 8, 16, 0) and tr["pass_wps"] == 4, tr  # eight waves, four-unit stages (W8U4)
+    assert ctx.last_prefilter_launches() == (1, 1) and (tr["pass_launches"], tr["pass_queues"]) == (1, 1)
 
 
 def test_per_rank_workspace_of_configs_4_and_5_fits_hbm(ctx):
