@@ -11,10 +11,11 @@ projection matrix -> embeddings -> k-NN -> overlaps.tsv.  Entry points:
     --feature-matrix feature_matrix.npz --kmer-counts counts.npy [--read-names names.txt]
         (scipy.sparse.save_npz binary CSR of the rows to search; see feature_extraction.py).
 
---devices 0,1,...: the rows are sharded over several GPUs of the node.  The parent process starts one
-child per GPU BEFORE it touches a GPU itself; every child embeds its row block, the blocks are
-all-gathered (RCCL), every child searches its rows against all rows and writes its part of overlaps.tsv;
-the parent concatenates the parts in rank order (byte-identical to the single-GPU file).
+--devices 0,1,...: every stage is sharded over several GPUs of the node.  The parent process starts one
+child per GPU BEFORE it touches a GPU itself; from reads, every child counts and searches its byte range of
+the file (stage1_sharded.py), then embeds its row block, the blocks are all-gathered (RCCL), every child
+searches its rows against all rows and writes its part of overlaps.tsv; the parent concatenates the parts in
+rank order (byte-identical to the single-GPU file).
 """
 import argparse
 import logging
@@ -94,7 +95,7 @@ def build_parser():
                    help="With --devices: nccl (= RCCL over xGMI; one GPU per process) or gloo (processes may "
                         "share a GPU: one-GPU rehearsal of the sharded path).")
     g.add_argument("--rank-worker", action="store_true", default=False, help=argparse.SUPPRESS)
-    g.add_argument("--stage1-worker", action="store_true", default=False, help=argparse.SUPPRESS)
+    g.add_argument("--stage1-cuts", type=str, default=None, help=argparse.SUPPRESS)
     return p
 
 
@@ -313,9 +314,10 @@ def load_rank_inputs(args, output_dir, rank, world):
 
 def run_rank_worker(args, output_dir, temp_dir):
     """One rank of `--devices`: RANK / WORLD_SIZE / FEDRANN_DEVICE / FEDRANN_RENDEZVOUS come from the parent, and
-    so does stage 1's output (the parent runs it in a child of its own before it starts the ranks).  A rank
-    loads ITS rows of the feature matrix, embeds them, the normalised blocks are all-gathered, it searches its
-    rows against all rows (distributed.ShardedPipeline) and writes temp/overlaps.rank<r>.tsv."""
+    so do the byte-range cuts of the reads (--stage1-cuts) when the run starts from reads: the rank then runs its
+    share of stage 1 (stage1_sharded.run_stage1_rank), which leaves temp/kmer_searcher/output.bin and the library
+    for all ranks.  A rank loads ITS rows of the feature matrix, embeds them, the normalised blocks are all-gathered,
+    it searches its rows against all rows (distributed.ShardedPipeline) and writes temp/overlaps.rank<r>.tsv."""
     import datetime
     import torch
     import torch.distributed as dist
@@ -327,19 +329,28 @@ def run_rank_worker(args, output_dir, temp_dir):
     torch.cuda.set_device(device)
     # rendezvous through a file in temp/ (no port to lose to another process); the host stages between two
     # collectives (loading a rank's rows of a 10 M-read matrix, writing its part of overlaps.tsv) may take long
-    # (FEDRANN_COLLECTIVE_TIMEOUT_S: how long a rank waits inside one collective, default 2 h -- the only long host stage
-    # between two collectives is the load below, and a barrier right after it takes that wait; a rank that hangs without
-    # dying no longer holds its siblings for half a day)
+    # (FEDRANN_COLLECTIVE_TIMEOUT_S: how long a rank waits inside one collective, default 2 h -- the long host stages
+    # between two collectives are a rank's share of stage 1, bounded by its byte range, and the load below, and a
+    # barrier right after each takes that wait; a rank that hangs without dying no longer holds its siblings for half a
+    # day)
     kw = dict(init_method="file://" + os.environ["FEDRANN_RENDEZVOUS"], rank=rank, world_size=world,
               timeout=datetime.timedelta(seconds=float(os.environ.get("FEDRANN_COLLECTIVE_TIMEOUT_S", "7200"))))
     if args.dist_backend == "nccl":
         dist.init_process_group("nccl", device_id=device, **kw)
     else:
         dist.init_process_group("gloo", **kw)
+    ctx = _lib.Context(device.index)
+    if args.stage1_cuts:
+        from .stage1_sharded import parse_cuts, run_stage1_rank
+        is_fastq, cuts = parse_cuts(args.stage1_cuts)
+        if rank == 0:
+            logger.info("--- 1. k-mer %s over %d GPUs ---", "search" if args.kmer_library else "counting and search",
+                        world)
+        args.kmer_searcher_output, args.kmer_library = run_stage1_rank(args, temp_dir, ctx, device, args.dist_backend,
+                                                                       cuts, is_fastq, args.input)
     n, lo, hi, ip, ix, n_features, P, name_off, names, strands = load_rank_inputs(args, output_dir, rank, world)
     dist.barrier()  # every rank has its rows: what follows is GPU work and short collectives
     k = args.nndescent_n_neighbors
-    ctx = _lib.Context(device.index)
     Pc = _projection_csr(P)
     ctx.projection_load(Pc.indptr, Pc.indices, Pc.data, n_features, args.embedding_dimension)
     pipe = ShardedPipeline(HipEngine(ctx, device), n, args.embedding_dimension, k, rank=rank, world_size=world,
@@ -361,33 +372,27 @@ def run_rank_worker(args, output_dir, temp_dir):
     ctx.close()
 
 
-def run_stage1_worker(args, temp_dir):
-    """Stage 1 of a `--devices` run (k-mer counting / sampling / search on the first GPU), as a child of its own
-    that has exited before the ranks start: no rank waits inside a collective while it runs."""
-    if args.kmer_library:
-        logger.info("--- 1b. k-mer search on the GPU ---")
-        _gpu_kmer_search(args.input, args.kmer_library, args.kmer_size, temp_dir)
-    else:
-        from .count_kmers import run_kmer_searcher
-        logger.info("--- 1. Counter kmers (GPU) ---")
-        run_kmer_searcher(input_path=args.input, k=args.kmer_size, sample_fraction=args.kmer_sample_fraction,
-                          min_multiplicity=args.kmer_min_multiplicity)
-
-
 def launch_rank_workers(argv, args, devices, output_dir, temp_dir, keep_intermediates):
     """The parent of `--devices`: no GPU call here (a process that has initialised the GPU must not start
-    others on this pool, and the children own the devices).  Children = this module with --stage1-worker
-    (once, when reads were given) and --rank-worker (one per device)."""
+    others on this pool, and the children own the devices).  Children = this module with --rank-worker (one per
+    device).  From reads, the parent decompresses a .gz input into temp/ and cuts the plain file into one byte range
+    per rank (stage1_sharded.cut_ranges, a few KiB read around each cut); the ranks run stage 1 between them."""
     import time
     argv = list(argv)
     if args.input and not args.kmer_searcher_output and not args.feature_matrix:
-        env = dict(os.environ, FEDRANN_DEVICE=str(devices[0]))
-        rc = subprocess.call([sys.executable, "-m", "fedrann_amd"] + argv + ["--stage1-worker"], env=env)
-        if rc:
-            raise SystemExit("stage 1 failed: exit code %d" % rc)
-        argv += ["--kmer-searcher-output", join(temp_dir, "kmer_searcher", "output.bin")]
-        if not args.kmer_library:
-            argv += ["--kmer-library", join(temp_dir, "fwd_kmer_library.fasta")]
+        from .stage1_sharded import cut_ranges, format_cuts
+        reads = args.input
+        if reads.endswith(".gz"):
+            import gzip
+            plain = join(temp_dir, os.path.basename(reads[:-3]))
+            with gzip.open(reads, "rb") as src, open(plain, "wb") as dst:
+                copyfileobj(src, dst, 1 << 24)
+            reads = plain
+        if not args.kmer_library and not reads.endswith((".fasta", ".fa", ".fastq", ".fq")):
+            raise ValueError("Unsupported file format. Please provide a FASTA or FASTQ file.")  # (as run_kmer_searcher)
+        is_fastq, cuts = cut_ranges(reads, len(devices))
+        logger.debug("stage 1 byte ranges: %s", cuts)
+        argv += ["-i", abspath(reads), "--stage1-cuts", format_cuts(is_fastq, cuts)]
     rendezvous = join(temp_dir, "rendezvous.%d" % os.getpid())
     if os.path.exists(rendezvous):
         os.remove(rendezvous)
@@ -447,12 +452,12 @@ def _gpu_kmer_search(reads_path, fwd_library, k, temp_dir):
     library is the reverse complement of every forward k-mer, in the same order (`seqkit seq -r -p`,
     count_kmers.py:127); both are passed in the reference's order: forward, then reverse."""
     from .kmer_search import kmer_searcher
-    comp = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
+    from .stage1_sharded import reverse_library_text
     with open(fwd_library, "rb") as f:
-        lines = f.read().split(b"\n")
+        rev_text = reverse_library_text(f.read())
     rev_path = join(temp_dir, "rev_kmer_library.fasta")
     with open(rev_path, "wb") as f:
-        f.write(b"\n".join(l if l.startswith(b">") else l.translate(comp)[::-1] for l in lines))
+        f.write(rev_text)
     if reads_path.endswith(".gz"):
         import gzip
         plain = join(temp_dir, os.path.basename(reads_path[:-3]))
@@ -473,7 +478,7 @@ def main(argv=None):
     global_variables.seed = args.seed
     check_limits(args.embedding_dimension, args.nndescent_n_neighbors)  # before any work (the library would
     # only refuse them after stages 1-3)
-    if args.device is not None and not (args.rank_worker or args.stage1_worker):
+    if args.device is not None and not args.rank_worker:
         os.environ["FEDRANN_DEVICE"] = str(args.device)
     output_dir = abspath(args.output_dir)
     os.makedirs(output_dir, exist_ok=True)
@@ -484,8 +489,6 @@ def main(argv=None):
     global_variables.temp_dir = temp_dir
     have_ks = bool(args.kmer_searcher_output)
     have_fm = bool(args.feature_matrix)
-    if args.rank_worker and have_ks:
-        args.input = None  # (stage 1 has run: the parent passes its output next to the user's arguments)
     if sum((bool(args.input), have_ks, have_fm)) != 1:
         raise SystemExit(
             "give exactly one of -i reads, -i reads + --kmer-library, --kmer-searcher-output + --kmer-library, "
@@ -496,8 +499,6 @@ def main(argv=None):
         raise SystemExit("--feature-matrix needs --kmer-counts")
     if args.rank_worker:
         return run_rank_worker(args, output_dir, temp_dir)
-    if args.stage1_worker:
-        return run_stage1_worker(args, temp_dir)
     logger.info("FEDRANN (MI355X hot path) version: %s", __version__)
     logger.debug("Parameters: %s", args)
     if args.devices:

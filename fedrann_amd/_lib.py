@@ -21,7 +21,8 @@ SYMBOLS = (
     "fdr_overlaps_write", "fdr_last_prefilter_launches", "fdr_knn_classes_dev", "fdr_knn_unique_dev",
     "fdr_knn_expand_dev", "fdr_kmer_output_scan_range", "fdr_kmer_output_load_range",
     "fdr_kmer_count_begin", "fdr_kmer_count_add", "fdr_kmer_count_finish", "fdr_reads_scan", "fdr_reads_parse",
-    "fdr_kmer_output_append", "fdr_last_query_paths", "fdr_last_knn_trace",
+    "fdr_kmer_output_append", "fdr_last_query_paths", "fdr_last_knn_trace", "fdr_kmer_count_export_dev",
+    "fdr_kmer_count_merge_dev", "fdr_kmer_count_merge",
 )
 FDR_MAX_K = 128
 KERNELS = ("embed_csr", "normalize_rows", "knn_tile", "knn_merge", "knn_prefilter", "knn_rerank",
@@ -130,6 +131,9 @@ def load_library():
     L.fdr_kmer_count_finish.argtypes = [vp, i64, p64]
     L.fdr_set_kmer_count_block.argtypes = [vp, ctypes.c_int64]
     L.fdr_last_kmer_count_blocks.argtypes = [vp]
+    L.fdr_kmer_count_export_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.fdr_kmer_count_merge_dev.argtypes = [vp, i32, vp, vp, vp, i64, p64, vp]
+    L.fdr_kmer_count_merge.argtypes = [vp, i32, vp, vp, vp, i64, p64]
     L.fdr_timing.argtypes = [vp, ctypes.c_int]
     L.fdr_timing_read.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                   ctypes.POINTER(ctypes.c_float)]
@@ -237,6 +241,17 @@ def reads_parse(buf, n, is_fastq, fastq_ids_as_fasta, eof, seq_buf=None):
     sp = span.tolist()
     ids = [bytes(view[sp[2 * r]:sp[2 * r + 1]]) for r in range(R.value)]
     return used.value, ids, seqs, off
+
+
+def reads_consumed(buf, n, is_fastq, fastq_ids_as_fasta, eof):
+    """Bytes of buf[:n] that hold whole records only (fdr_reads_scan without the parse; host only)."""
+    L = load_library()
+    used, R, nb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    rc = L.fdr_reads_scan(buf.ctypes.data if n else None, int(n), int(bool(is_fastq)), int(bool(fastq_ids_as_fasta)),
+                          int(bool(eof)), ctypes.byref(used), ctypes.byref(R), ctypes.byref(nb))
+    if rc != 0:
+        raise FedrannHipError("fdr_reads_scan failed (%d): %s" % (rc, L.fdr_last_error().decode()))
+    return used.value
 
 
 def kmer_output_append(path, ids, indptr, indices):
@@ -408,6 +423,45 @@ class Context:
     def set_kmer_count_block(self, chars):
         """Characters per block of kmer_count (0 = default 2^31); small blocks exercise the merge in tests."""
         self._check(self._L.fdr_set_kmer_count_block(self._h, int(chars)), "fdr_set_kmer_count_block")
+
+    def kmer_count_export_dev(self, d_splitters, n_parts, d_codes_out=None, d_counts_out=None, stream=None):
+        """The accumulated, unthresholded table cut at n_parts - 1 splitter codes (device pointers, e.g. torch's
+        data_ptr()): returns the part offsets int64 [n_parts + 1]; with d_codes_out / d_counts_out (device, at least
+        part_off[-1] entries each) the table is copied there too."""
+        part_off = np.empty(int(n_parts) + 1, dtype=np.int64)
+        self._check(self._L.fdr_kmer_count_export_dev(self._h, d_splitters or None, int(n_parts), d_codes_out or None,
+                                                      d_counts_out or None, part_off.ctypes.data, stream or None),
+                    "fdr_kmer_count_export_dev")
+        return part_off
+
+    def kmer_count_merge_dev(self, run_off, d_codes, d_counts, min_count=1, stream=None):
+        """Merge the runs (run_off int64 [W + 1]) of device arrays d_codes / d_counts: (codes, counts) ascending, the
+        summed counts >= min_count."""
+        run_off = np.ascontiguousarray(run_off, dtype=np.int64)
+        n = ctypes.c_int64()
+        self._check(self._L.fdr_kmer_count_merge_dev(self._h, run_off.size - 1, run_off.ctypes.data, d_codes or None,
+                                                     d_counts or None, int(min_count), ctypes.byref(n), stream or None),
+                    "fdr_kmer_count_merge_dev")
+        return self._kmer_count_fetch(n.value)
+
+    def kmer_count_merge(self, run_off, codes, counts, min_count=1):
+        """kmer_count_merge_dev from host arrays."""
+        run_off = np.ascontiguousarray(run_off, dtype=np.int64)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        if codes.size != counts.size or (run_off.size and codes.size < int(run_off[-1])):
+            raise ValueError("run_off does not describe codes / counts")
+        n = ctypes.c_int64()
+        self._check(self._L.fdr_kmer_count_merge(self._h, run_off.size - 1, run_off.ctypes.data, codes.ctypes.data,
+                                                 counts.ctypes.data, int(min_count), ctypes.byref(n)),
+                    "fdr_kmer_count_merge")
+        return self._kmer_count_fetch(n.value)
+
+    def _kmer_count_fetch(self, n):
+        codes = np.empty(n, dtype=np.uint64)
+        counts = np.empty(n, dtype=np.uint64)
+        self._check(self._L.fdr_kmer_count_fetch(self._h, codes.ctypes.data, counts.ctypes.data), "fdr_kmer_count_fetch")
+        return codes, counts
 
     def last_kmer_count_blocks(self):
         """Non-empty blocks the last kmer_count call counted."""

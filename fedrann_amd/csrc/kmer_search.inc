@@ -827,3 +827,280 @@ FDR_EXPORT int fdr_kmer_count_fetch(fdr_ctx *ctx, uint64_t *codes_out, uint64_t 
     ctx->kc_n = 0;
     return FDR_OK;
 }
+
+// ---- counting over several ranks: export by code range, W-way merge of the received runs -------------------------
+// A rank of a sharded stage 1 counts its byte range of the reads (fdr_kmer_count_begin / _add), exports its
+// unthresholded table cut at W - 1 splitter codes (fdr_kmer_count_export_dev), the parts are exchanged (rank p gets
+// every rank's part p), and fdr_kmer_count_merge_dev folds the W received runs into one table with the threshold
+// applied; fdr_kmer_count_fetch returns it as after fdr_kmer_count_finish.
+//
+// The merge is one pass over the runs (no chain of pairwise merges re-streaming the growing table):
+//   1. every KM_STRIDE-th code of every run is a sample; the sorted samples are the tile boundaries, so a tile holds
+//      about KM_STRIDE elements of all runs together (at most W x KM_STRIDE);
+//   2. km_bounds_kernel binary-searches every run for every boundary: tile t's slice of run r;
+//   3. km_tile_kernel, one workgroup per tile: the tile's slices go to LDS (when they fit; else the searches below
+//      read them from global memory), and every element's place in the merged sequence is its index in its own
+//      run plus its lower bound in every other run (+1 in a run before its own that holds the same code: ties go
+//      by run number).  A code's copy in the lowest run holding it owns the code: it sums the counts of all copies
+//      (at most W: every run is unique) and flags the total if it reaches min_count;
+//   4. an inclusive scan of the flags compacts the owners' (code, total) in ascending code order.
+#define KM_STRIDE 1024
+#define KM_CACHE 4096  // codes of a tile held in LDS (32 KiB)
+#define KM_MAX_RUNS 256
+
+__device__ __forceinline__ long long km_lower_bound(const u64 *a, long long n, u64 c) {
+    long long lo = 0;
+    while (n > 0) {
+        const long long h = n >> 1;
+        if (a[lo + h] < c) {
+            lo += h + 1;
+            n -= h + 1;
+        } else {
+            n = h;
+        }
+    }
+    return lo;
+}
+
+// samples: code KM_STRIDE * (q + 1) of run r for q < samp_pre[r + 1] - samp_pre[r]
+__global__ __launch_bounds__(256) void km_sample_kernel(const u64 *__restrict__ codes, const long long *__restrict__ roff,
+                                                        const long long *__restrict__ samp_pre, int n_runs, long long n_s,
+                                                        u64 *__restrict__ samples) {
+    const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= n_s) return;
+    int r = 0;
+    while (samp_pre[r + 1] <= s) ++r;  // (n_runs <= KM_MAX_RUNS)
+    samples[s] = codes[roff[r] + (s - samp_pre[r] + 1) * KM_STRIDE];
+}
+
+// slice[t * W + r] = index in run r of tile t's first element, t = 0 .. T (row T = the run's length)
+__global__ __launch_bounds__(256) void km_bounds_kernel(const u64 *__restrict__ codes, const long long *__restrict__ roff,
+                                                        const u64 *__restrict__ bounds, long long n_tiles, int n_runs,
+                                                        long long *__restrict__ slice) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (n_tiles + 1) * n_runs) return;
+    const long long t = i / n_runs;
+    const int r = (int)(i - t * n_runs);
+    const long long len = roff[r + 1] - roff[r];
+    slice[i] = t == 0 ? 0 : t == n_tiles ? len : km_lower_bound(codes + roff[r], len, bounds[t - 1]);
+}
+
+__global__ __launch_bounds__(256) void km_tile_kernel(const u64 *__restrict__ codes, const u64 *__restrict__ counts,
+                                                      const long long *__restrict__ roff, const long long *__restrict__ slice,
+                                                      int n_runs, u64 min_count, u64 *__restrict__ m_codes,
+                                                      u64 *__restrict__ m_tot, int *__restrict__ keep) {
+    __shared__ long long s_lo[KM_MAX_RUNS], s_base[KM_MAX_RUNS], s_pre[KM_MAX_RUNS + 1];
+    __shared__ u64 s_cache[KM_CACHE];
+    const long long t = blockIdx.x;
+    const int tid = threadIdx.x;
+    for (int r = tid; r < n_runs; r += 256) {
+        s_lo[r] = slice[t * n_runs + r];
+        s_base[r] = roff[r];
+    }
+    __syncthreads();
+    if (tid == 0) {  // (n_runs <= KM_MAX_RUNS: a short serial prefix)
+        long long acc = 0;
+        for (int r = 0; r < n_runs; ++r) {
+            s_pre[r] = acc;
+            acc += max(0ll, slice[(t + 1) * n_runs + r] - s_lo[r]);  // (> 0 for ascending runs; a bad run reads nothing out of bounds)
+        }
+        s_pre[n_runs] = acc;
+    }
+    __syncthreads();
+    const long long tot = s_pre[n_runs];
+    const bool in_lds = tot <= KM_CACHE;
+    auto run_of = [&](long long q) {  // the run of the tile's q-th element (upper bound in s_pre, minus one)
+        int lo = 0, n = n_runs;
+        while (n > 0) {
+            const int h = n >> 1;
+            if (s_pre[lo + h + 1] <= q) {
+                lo += h + 1;
+                n -= h + 1;
+            } else {
+                n = h;
+            }
+        }
+        return lo;
+    };
+    if (in_lds) {
+        for (long long q = tid; q < tot; q += 256) {
+            const int r = run_of(q);
+            s_cache[q] = codes[s_base[r] + s_lo[r] + (q - s_pre[r])];
+        }
+        __syncthreads();
+    }
+    for (long long q = tid; q < tot; q += 256) {
+        const int j = run_of(q);
+        const long long gi = s_lo[j] + (q - s_pre[j]);  // index in run j
+        const u64 c = in_lds ? s_cache[q] : codes[s_base[j] + gi];
+        u64 total = counts[s_base[j] + gi];
+        long long pos = gi;
+        bool owner = true;
+        for (int r = 0; r < n_runs; ++r) {
+            if (r == j) continue;
+            const long long n = s_pre[r + 1] - s_pre[r];
+            const u64 *a = in_lds ? s_cache + s_pre[r] : codes + s_base[r] + s_lo[r];
+            const long long lb = km_lower_bound(a, n, c);
+            pos += s_lo[r] + lb;
+            if (lb < n && a[lb] == c) {
+                if (r < j) {
+                    owner = false;
+                    ++pos;
+                } else if (owner) {
+                    total += counts[s_base[r] + s_lo[r] + lb];
+                }
+            }
+        }
+        keep[pos] = owner && total >= min_count ? 1 : 0;
+        if (owner) {
+            m_codes[pos] = c;
+            m_tot[pos] = total;
+        }
+    }
+}
+
+// part_off[p] = first index of the table with code >= splitters[p - 1] (p = 1 .. n_parts - 1)
+__global__ __launch_bounds__(256) void km_parts_kernel(const u64 *__restrict__ table, long long n,
+                                                       const u64 *__restrict__ splitters, int n_parts,
+                                                       long long *__restrict__ part_off) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p > n_parts) return;
+    part_off[p] = p == 0 ? 0 : p == n_parts ? n : km_lower_bound(table, n, splitters[p - 1]);
+}
+
+FDR_EXPORT int fdr_kmer_count_export_dev(fdr_ctx *ctx, const uint64_t *d_splitters, int32_t n_parts,
+                                         uint64_t *d_codes_out, uint64_t *d_counts_out, int64_t *part_off_out,
+                                         void *stream) {
+    if (int rc = use_device(ctx)) return rc;
+    if (ctx->kc_k <= 0) return fail(FDR_E_STATE, "fdr_kmer_count_export_dev: call fdr_kmer_count_begin first");
+    if (n_parts < 1 || !part_off_out || (n_parts > 1 && !d_splitters) || (!d_codes_out != !d_counts_out))
+        return fail(FDR_E_ARG, "fdr_kmer_count_export_dev: bad argument");
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    const u64 *d_codes = (const u64 *)(ctx->kc_acc ? ctx->kc_a1.p : ctx->kc_a0.p);
+    const u64 *d_counts = (const u64 *)(ctx->kc_acc ? ctx->kc_c1.p : ctx->kc_c0.p);
+    long long n = ctx->kc_na;
+    if (n > 0) {  // the "no k-mer here" marker ~0 sorts last and is no k-mer: not exported
+        u64 last = 0;
+        HIP_TRY(hipMemcpyAsync(&last, d_codes + (n - 1), 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (last == ~0ull) --n;
+    }
+    if (int rc = ctx->ks_indptr.reserve((size_t)(n_parts + 1) * 8)) return rc;
+    hipLaunchKernelGGL(km_parts_kernel, dim3((unsigned)((n_parts + 256) / 256)), dim3(256), 0, st, d_codes, n,
+                       (const u64 *)d_splitters, (int)n_parts, (long long *)ctx->ks_indptr.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(part_off_out, ctx->ks_indptr.p, (size_t)(n_parts + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (d_codes_out && n > 0) {
+        HIP_TRY(hipMemcpyAsync(d_codes_out, d_codes, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_counts_out, d_counts, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return FDR_OK;
+}
+
+// the merge of n_runs runs already on the device (d_codes / d_counts at run_off[r] .. run_off[r + 1])
+static int km_merge(fdr_ctx *ctx, int32_t n_runs, const int64_t *run_off, const u64 *d_codes, const u64 *d_counts,
+                    int64_t min_count, int64_t *n_out, hipStream_t st) {
+    const long long M = run_off[n_runs];
+    ctx->kc_k = 0;
+    ctx->kc_n = 0;
+    *n_out = 0;
+    if (M == 0) return FDR_OK;
+    if (M >= 0x7fffffffll) return fail(FDR_E_ARG, "fdr_kmer_count_merge: %lld entries (limit 2^31)", M);
+    const u64 minc = (u64)std::max<int64_t>(1, min_count);
+    std::vector<long long> samp_pre((size_t)n_runs + 1, 0);
+    for (int r = 0; r < n_runs; ++r) {
+        const long long len = run_off[r + 1] - run_off[r];
+        samp_pre[(size_t)r + 1] = samp_pre[(size_t)r] + (len > 0 ? (len - 1) / KM_STRIDE : 0);
+    }
+    const long long n_s = samp_pre[(size_t)n_runs], n_tiles = n_s + 1;
+    size_t t_sort = 0, t_scan = 0;
+    (void)rocprim::radix_sort_keys(nullptr, t_sort, (u64 *)nullptr, (u64 *)nullptr, (size_t)std::max(n_s, 1ll), 0, 64,
+                                   (hipStream_t) nullptr);
+    (void)rocprim::inclusive_scan(nullptr, t_scan, (int *)nullptr, (int *)nullptr, (size_t)M, rocprim::plus<int>(),
+                                  (hipStream_t) nullptr);
+    if (int rc = ctx->ks_tmp.reserve(std::max(t_sort, t_scan))) return rc;
+    if (int rc = ctx->ks_off.reserve((size_t)(2 * n_runs + 2) * 8)) return rc;  // run offsets, sample prefix
+    if (int rc = ctx->ks_codes.reserve((size_t)std::max(n_s, 1ll) * 8)) return rc;  // samples
+    if (int rc = ctx->ks_keys.reserve((size_t)std::max(n_s, 1ll) * 8)) return rc;   // sorted samples = boundaries
+    if (int rc = ctx->ks_idx.reserve((size_t)(n_tiles + 1) * n_runs * 8)) return rc;  // slices
+    if (int rc = ctx->kc_mk.reserve((size_t)M * 8)) return rc;   // owners' codes at their merged place
+    if (int rc = ctx->kc_mv.reserve((size_t)M * 8)) return rc;   // ... their totals
+    if (int rc = ctx->ks_pos.reserve((size_t)M * 4)) return rc;  // keep flags
+    if (int rc = ctx->ks_rows.reserve((size_t)M * 4)) return rc; // their inclusive scan
+    long long *d_roff = (long long *)ctx->ks_off.p, *d_spre = d_roff + n_runs + 1;
+    HIP_TRY(hipMemcpyAsync(d_roff, run_off, (size_t)(n_runs + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_spre, samp_pre.data(), (size_t)(n_runs + 1) * 8, hipMemcpyHostToDevice, st));
+    int trc = timing_begin(ctx, FDR_KERNEL_KMER_COMPACT, st);
+    if (trc) return trc;
+    if (n_s > 0) {
+        hipLaunchKernelGGL(km_sample_kernel, dim3((unsigned)((n_s + 255) / 256)), dim3(256), 0, st, d_codes,
+                           (const long long *)d_roff, (const long long *)d_spre, (int)n_runs, n_s, (u64 *)ctx->ks_codes.p);
+        HIP_TRY(hipGetLastError());
+        size_t tb = ctx->ks_tmp.cap;
+        HIP_TRY(rocprim::radix_sort_keys(ctx->ks_tmp.p, tb, (u64 *)ctx->ks_codes.p, (u64 *)ctx->ks_keys.p, (size_t)n_s,
+                                         0, 64, st));
+    }
+    const long long nb = (n_tiles + 1) * n_runs;
+    hipLaunchKernelGGL(km_bounds_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, d_codes,
+                       (const long long *)d_roff, (const u64 *)ctx->ks_keys.p, n_tiles, (int)n_runs,
+                       (long long *)ctx->ks_idx.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(km_tile_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, d_codes, d_counts,
+                       (const long long *)d_roff, (const long long *)ctx->ks_idx.p, (int)n_runs, minc,
+                       (u64 *)ctx->kc_mk.p, (u64 *)ctx->kc_mv.p, (int *)ctx->ks_pos.p);
+    HIP_TRY(hipGetLastError());
+    size_t tb = ctx->ks_tmp.cap;
+    HIP_TRY(rocprim::inclusive_scan(ctx->ks_tmp.p, tb, (int *)ctx->ks_pos.p, (int *)ctx->ks_rows.p, (size_t)M,
+                                    rocprim::plus<int>(), st));
+    int kept = 0;
+    HIP_TRY(hipMemcpyAsync(&kept, static_cast<int *>(ctx->ks_rows.p) + (M - 1), 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (kept > 0) {
+        if (int rc = ctx->ks_pairs2.reserve((size_t)kept * 8)) return rc;
+        if (int rc = ctx->kc_counts.reserve((size_t)kept * 8)) return rc;
+        hipLaunchKernelGGL(kc_compact64_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st,
+                           (const u64 *)ctx->kc_mk.p, (const u64 *)ctx->kc_mv.p, M, (const int *)ctx->ks_pos.p,
+                           (const int *)ctx->ks_rows.p, (u64 *)ctx->ks_pairs2.p, (u64 *)ctx->kc_counts.p);
+        HIP_TRY(hipGetLastError());
+    }
+    if ((trc = timing_end(ctx, FDR_KERNEL_KMER_COMPACT, st))) return trc;
+    HIP_TRY(hipStreamSynchronize(st));
+    ctx->kc_n = kept;
+    *n_out = kept;
+    return FDR_OK;
+}
+
+static int km_check_runs(int32_t n_runs, const int64_t *run_off, int64_t *n_out) {
+    if (!n_out || !run_off || n_runs < 1 || n_runs > KM_MAX_RUNS)
+        return fail(FDR_E_ARG, "fdr_kmer_count_merge: bad argument (1 .. %d runs)", KM_MAX_RUNS);
+    if (run_off[0] != 0) return fail(FDR_E_ARG, "fdr_kmer_count_merge: run_off[0] must be 0");
+    for (int r = 0; r < n_runs; ++r)
+        if (run_off[r + 1] < run_off[r]) return fail(FDR_E_ARG, "fdr_kmer_count_merge: run_off is not monotone");
+    return FDR_OK;
+}
+
+FDR_EXPORT int fdr_kmer_count_merge_dev(fdr_ctx *ctx, int32_t n_runs, const int64_t *run_off, const uint64_t *d_codes,
+                                        const uint64_t *d_counts, int64_t min_count, int64_t *n_out, void *stream) {
+    if (int rc = use_device(ctx)) return rc;
+    if (int rc = km_check_runs(n_runs, run_off, n_out)) return rc;
+    if (run_off[n_runs] > 0 && (!d_codes || !d_counts)) return fail(FDR_E_ARG, "fdr_kmer_count_merge_dev: null input");
+    return km_merge(ctx, n_runs, run_off, (const u64 *)d_codes, (const u64 *)d_counts, min_count, n_out,
+                    stream ? (hipStream_t)stream : ctx->stream);
+}
+
+FDR_EXPORT int fdr_kmer_count_merge(fdr_ctx *ctx, int32_t n_runs, const int64_t *run_off, const uint64_t *codes,
+                                    const uint64_t *counts, int64_t min_count, int64_t *n_out) {
+    if (int rc = use_device(ctx)) return rc;
+    if (int rc = km_check_runs(n_runs, run_off, n_out)) return rc;
+    const int64_t M = run_off[n_runs];
+    if (M > 0 && (!codes || !counts)) return fail(FDR_E_ARG, "fdr_kmer_count_merge: null input");
+    hipStream_t st = ctx->stream;
+    if (M > 0) {  // (the accumulated-table buffers hold the inputs: the merge replaces that table anyway)
+        if (int rc = ctx->kc_a0.reserve((size_t)M * 8)) return rc;
+        if (int rc = ctx->kc_c0.reserve((size_t)M * 8)) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->kc_a0.p, codes, (size_t)M * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->kc_c0.p, counts, (size_t)M * 8, hipMemcpyHostToDevice, st));
+    }
+    return km_merge(ctx, n_runs, run_off, (const u64 *)ctx->kc_a0.p, (const u64 *)ctx->kc_c0.p, min_count, n_out, st);
+}

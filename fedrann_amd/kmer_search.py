@@ -153,7 +153,14 @@ def _complete_prefix(raw, is_fastq, eof):
     return int(nl[-1]) + 1 if i == n else int(starts[min(i, n - 1)])
 
 
-def iter_sequence_blocks(path, fastq_ids_as_fasta=False, chunk_bytes=1 << 28, reuse_buffers=False):
+def file_is_fastq(path):
+    """The format of a reads file, from its first byte (FASTQ iff it is '@'; an empty file is FASTA)."""
+    with open(path, "rb") as f:
+        return f.read(1) == b"@"
+
+
+def iter_sequence_blocks(path, fastq_ids_as_fasta=False, chunk_bytes=1 << 28, reuse_buffers=False, start=None,
+                         end=None, is_fastq=None, status=None):
     """The records of a FASTA / FASTQ file in file order, a piece of the file at a time: yields (ids, seqs uint8,
     seq_off int64) for consecutive groups of whole records.  The reference streams its reads through pipes
     (count_kmers.py:131-139, kmer_searcher.cpp:284-292); this keeps the host at about chunk_bytes + one record
@@ -161,24 +168,57 @@ def iter_sequence_blocks(path, fastq_ids_as_fasta=False, chunk_bytes=1 << 28, re
     into one reused buffer and cut into records by the library's native reader (fdr_reads_scan / fdr_reads_parse);
     the unconsumed tail of a piece moves to the front of the buffer, which grows only for a record longer than it.
     reuse_buffers: the yielded seqs are views of ONE buffer, valid until the next piece is asked for (what the
-    pipeline wants: no fresh pages per piece); default: every piece owns its arrays."""
+    pipeline wants: no fresh pages per piece); default: every piece owns its arrays.
+    Byte-range form (one rank's share of a sharded stage 1): the bytes [start, end) only, `end` taken for the end
+    of the input, in the format is_fastq of the WHOLE file (file_is_fastq; never decided from the range's first
+    byte).  status: a dict that receives "aligned": whether the reader's walk reached `end` as a record boundary
+    (FASTQ: no record of four lines was cut short by `end`; always true for FASTA, whose cuts sit at '>' lines)."""
     chunk_bytes = max(int(chunk_bytes), 1)
+    ranged = start is not None or end is not None
+    if status is not None:
+        status["aligned"] = True
     with open(path, "rb", buffering=0) as f:
+        if ranged:
+            start = int(start or 0)
+            end = os.fstat(f.fileno()).st_size if end is None else int(end)
+            if is_fastq is None:
+                raise ValueError("the byte-range form needs the file's format (is_fastq)")
+            f.seek(start)
+            left = max(end - start, 0)
+        else:
+            left = None
         buf = np.empty(chunk_bytes, dtype=np.uint8)
-        have = f.readinto(memoryview(buf)) or 0
+
+        def fill(view):
+            nonlocal left
+            if left is not None:
+                view = view[:left]
+                if len(view) == 0:
+                    return 0
+            got = f.readinto(view) or 0
+            if left is not None:
+                left -= got
+            return got
+
+        have = fill(memoryview(buf))
         if have == 0:
             return
-        is_fastq = buf[0] == ord("@")  # (a first line that is just '\n' is empty: FASTA)
+        if not ranged:
+            is_fastq = buf[0] == ord("@")  # (a first line that is just '\n' is empty: FASTA)
         eof = False
         seq_buf = None
         while True:
             if not eof and have == buf.size:  # (a record longer than the buffer is waiting for its end)
                 buf = np.concatenate((buf, np.empty(max(chunk_bytes, buf.size), dtype=np.uint8)))
             while not eof and have < buf.size:
-                got = f.readinto(memoryview(buf)[have:]) or 0
+                got = fill(memoryview(buf)[have:])
                 if got == 0:
                     eof = True
                 have += got
+            if eof and status is not None and is_fastq:
+                # the walk over the whole file would reach `end` as a loop position iff, read as if more followed,
+                # this last piece holds whole records (and skipped lines) only
+                status["aligned"] = _lib.reads_consumed(buf, have, True, fastq_ids_as_fasta, False) == have
             if reuse_buffers and (seq_buf is None or seq_buf.size < have):
                 seq_buf = np.empty(buf.size, dtype=np.uint8)
             used, ids, seqs, off = _lib.reads_parse(buf, have, is_fastq, fastq_ids_as_fasta, eof, seq_buf)
@@ -257,6 +297,47 @@ def write_kmer_frequency_bin(path, indices, n_lib):
     out.tofile(path)
 
 
+def read_library_files(kmer_lib, k):
+    """The library codes of a path or a list of paths, as `cat fwd rev | grep -v '^>' | kmer_searcher` reads them."""
+    paths = [kmer_lib] if isinstance(kmer_lib, (str, bytes, os.PathLike)) else list(kmer_lib)
+    texts = []
+    for p in paths:
+        with open(p, "rb") as f:
+            t = f.read()
+        texts.append(b"\n".join(l for l in t.split(b"\n") if not l.startswith(b">")) + b"\n")
+    return load_kmer_library(texts, k)
+
+
+def write_frequency_counts(path, freq):
+    """kmer_frequency.bin from the per-index read counts freq [n_lib] (see write_kmer_frequency_bin)."""
+    freq = np.asarray(freq)
+    nz = np.flatnonzero(freq)
+    out = np.empty((nz.size, 2), dtype="<u8")
+    out[:, 0] = nz
+    out[:, 1] = freq[nz]
+    out.tofile(path)
+
+
+def search_append(out_bin, blocks, codes, k, freq, context=None, collected=None):
+    """Search the (ids, seqs, seq_off) pieces of `blocks` against the library `codes` and append their output.bin
+    records to out_bin (natively: fdr_kmer_output_append, no per-record Python); freq [n_lib] += the reads per
+    library index.  collected: (ids, indptr parts, indices parts) lists that receive the records.  Returns
+    (reads, hits)."""
+    n_reads = nnz = 0
+    for ids, seqs, off in blocks:
+        indptr, indices = search(seqs, off, codes, k, context=context)
+        _lib.kmer_output_append(out_bin, ids, indptr, indices)
+        if indices.size:
+            freq += np.bincount(indices, minlength=freq.size)
+        if collected is not None:
+            collected[0].extend(ids)
+            collected[1].append(indptr[1:] + nnz)
+            collected[2].append(indices)
+        n_reads += len(ids)
+        nnz += int(indices.size)
+    return n_reads, nnz
+
+
 def kmer_searcher(kmer_lib, input_reads, output_dir, k, threads=None, context=None, fastq_ids_as_fasta=False,
                   collect=True, chunk_bytes=1 << 28, lib_codes=None):
     """Drop-in for the command line `kmer_searcher <kmer_lib> <input> <output_dir> <k> <threads>`
@@ -275,16 +356,10 @@ def kmer_searcher(kmer_lib, input_reads, output_dir, k, threads=None, context=No
             raise ValueError("Invalid k value: %r" % (k,))
         codes = np.ascontiguousarray(lib_codes, dtype=np.uint64)
     else:
-        paths = [kmer_lib] if isinstance(kmer_lib, (str, bytes, os.PathLike)) else list(kmer_lib)
-        texts = []
-        for p in paths:
-            with open(p, "rb") as f:
-                t = f.read()
-            texts.append(b"\n".join(l for l in t.split(b"\n") if not l.startswith(b">")) + b"\n")
-        codes = load_kmer_library(texts, k)
+        codes = read_library_files(kmer_lib, k)
     os.makedirs(output_dir, exist_ok=True)
     freq = np.zeros(int(codes.size), dtype=np.int64)
-    all_ids, ptr_parts, idx_parts, n_reads, nnz = [], [np.zeros(1, dtype=np.int64)], [], 0, 0
+    all_ids, ptr_parts, idx_parts = [], [np.zeros(1, dtype=np.int64)], []
     # The records go to output.bin.tmp, which becomes output.bin once the header holds the record count: a piece that
     # fails (an id fdr_kmer_output_append refuses, a GPU error) leaves no output.bin with a VALID header saying "0
     # records" behind for a later --kmer-searcher-output run to take for an empty read set.
@@ -295,18 +370,10 @@ def kmer_searcher(kmer_lib, input_reads, output_dir, k, threads=None, context=No
     try:
         with open(out_bin, "wb") as f:
             f.write(struct.pack("<4sB3sQ", b"KMER", 1, b"\0\0\0", 0))
-        for ids, seqs, off in iter_sequence_blocks(input_reads, fastq_ids_as_fasta=fastq_ids_as_fasta,
-                                                   chunk_bytes=chunk_bytes, reuse_buffers=True):
-            indptr, indices = search(seqs, off, codes, k, context=context)
-            _lib.kmer_output_append(out_bin, ids, indptr, indices)  # (native: no per-record Python)
-            if indices.size:
-                freq += np.bincount(indices, minlength=freq.size)
-            if collect:
-                all_ids += ids
-                ptr_parts.append(indptr[1:] + nnz)
-                idx_parts.append(indices)
-            n_reads += len(ids)
-            nnz += int(indices.size)
+        blocks = iter_sequence_blocks(input_reads, fastq_ids_as_fasta=fastq_ids_as_fasta, chunk_bytes=chunk_bytes,
+                                      reuse_buffers=True)
+        n_reads, nnz = search_append(out_bin, blocks, codes, k, freq, context=context,
+                                     collected=(all_ids, ptr_parts, idx_parts) if collect else None)
         with open(out_bin, "r+b") as f:  # the record count, known now
             f.seek(8)
             f.write(struct.pack("<Q", n_reads))
@@ -315,11 +382,7 @@ def kmer_searcher(kmer_lib, input_reads, output_dir, k, threads=None, context=No
         if os.path.exists(out_bin):
             os.remove(out_bin)
         raise
-    nz = np.flatnonzero(freq)
-    out = np.empty((nz.size, 2), dtype="<u8")
-    out[:, 0] = nz
-    out[:, 1] = freq[nz]
-    out.tofile(os.path.join(output_dir, "kmer_frequency.bin"))
+    write_frequency_counts(os.path.join(output_dir, "kmer_frequency.bin"), freq)
     if not collect:
         return n_reads, None, nnz, int(codes.size)
     indices = np.concatenate(idx_parts) if idx_parts else np.empty(0, dtype=np.int32)

@@ -292,6 +292,27 @@ int fdr_kmer_count_add(fdr_ctx *ctx, const uint8_t *seqs, const int64_t *seq_off
 int fdr_kmer_count_finish(fdr_ctx *ctx, int64_t min_count, int64_t *n_out);
 int fdr_set_kmer_count_block(fdr_ctx *ctx, int64_t chars);
 int fdr_last_kmer_count_blocks(fdr_ctx *ctx);
+/* Counting over the ranks of a sharded run: each rank counts its share of the reads (begin / add, no threshold), exports
+ * its table cut at n_parts - 1 ascending splitter codes, part p goes to rank p, and each rank merges the runs it received.
+ *   fdr_kmer_count_export_dev: d_splitters uint64 [n_parts - 1] on the device; copies the accumulated, unthresholded
+ *                              table (ascending codes) to d_codes_out / d_counts_out uint64 (device, or both NULL for
+ *                              the offsets only) and writes the host offsets part_off_out int64 [n_parts + 1]: part p =
+ *                              codes in [splitters[p - 1], splitters[p]) at part_off_out[p] .. part_off_out[p + 1].
+ *                              The table stays as it is.
+ *   fdr_kmer_count_merge_dev:  n_runs (1 .. 256) runs at run_off[r] .. run_off[r + 1] (host int64 [n_runs + 1],
+ *                              run_off[0] = 0) of d_codes / d_counts uint64 (device), each strictly ascending in code;
+ *                              sums the counts of equal codes, keeps totals >= min_count and leaves them in the
+ *                              context: *n_out = their number, then fdr_kmer_count_fetch (ascending code order).  One
+ *                              pass (tile boundaries from samples of every run, every element placed by its bounds in
+ *                              the other runs), not a chain of pairwise merges.  Fewer than 2^31 entries in all.
+ *   fdr_kmer_count_merge:      the same from host arrays (replaces the context's accumulated table).
+ * stream: a hipStream_t (NULL = the context's). */
+int fdr_kmer_count_export_dev(fdr_ctx *ctx, const uint64_t *d_splitters, int32_t n_parts, uint64_t *d_codes_out,
+                              uint64_t *d_counts_out, int64_t *part_off_out, void *stream);
+int fdr_kmer_count_merge_dev(fdr_ctx *ctx, int32_t n_runs, const int64_t *run_off, const uint64_t *d_codes,
+                             const uint64_t *d_counts, int64_t min_count, int64_t *n_out, void *stream);
+int fdr_kmer_count_merge(fdr_ctx *ctx, int32_t n_runs, const int64_t *run_off, const uint64_t *codes,
+                         const uint64_t *counts, int64_t min_count, int64_t *n_out);
 
 /* ---- FASTA / FASTQ reader of the k-mer stage (host only: no context, no GPU) -------------------------
  * Replaces read_sequences of kmer_searcher/kmer_searcher.cpp:153-200 (FASTQ iff the first line starts with '@';
