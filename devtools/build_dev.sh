@@ -1,7 +1,7 @@
 #!/bin/bash
 # development build of the library: -DFDR_DEV keeps the FDR_KNN_* knobs (never shipped, never tested against)
 # usage: bash devtools/build_dev.sh NAME [extra hipcc flags]  -> devtools/ab/libNAME.so  (FEDRANN_HIP_LIB=... to use it)
-# (-DFDR_SHAPE_MASK=bits -DFDR_LH_MASK=16|32|48: compile only some prefilter shapes -- fedrann_hip.hip: FDR_SHAPE_CASE;
+# (-DFDR_SHAPE_MASK=bits -DFDR_LH_MASK=16|32|48: compile only some candidate-pass shapes -- bit i = kShapes[i], knn_plan.inc;
 #  the sources are snapshot first: hipcc reads them twice, minutes apart, and an edit in between would split the build)
 name=${1:-dev}; shift
 mkdir -p devtools/ab

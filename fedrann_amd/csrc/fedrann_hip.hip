@@ -892,6 +892,120 @@ FDR_EXPORT size_t fdr_knn_workspace_bytes(fdr_ctx *ctx, int64_t nq, int64_t nt, 
     return knn_workspace_bytes_impl(ctx, nq, nt, d, k);
 }
 
+// ---- the kernels of kShapes (knn_plan.inc) ---------------------------------------------------------------------------
+// Built for the entries with `release` set (a development build: every entry); -DFDR_SHAPE_MASK=<bits of KnnShapeId>
+// and -DFDR_LH_MASK=<16 | 32 | 48> narrow the candidate pass's kernels further (hipcc takes minutes per kernel).  An
+// entry that is not compiled is a null pointer.
+#ifndef FDR_SHAPE_MASK
+#define FDR_SHAPE_MASK (~0ull)
+#endif
+#ifndef FDR_LH_MASK
+#define FDR_LH_MASK 48
+#endif
+typedef void (*TileKernel)(const float *, const unsigned char *, int, const float *, const unsigned *, int, int, SegBounds,
+                           int, int, u64 *, unsigned *, int, int, int FDR_DBG_PARAM);
+typedef void (*PassKernel)(const _Float16 *, int, const _Float16 *, int, int, SegBounds, int, int, u64 *, unsigned *, int,
+                           int, int, OrderArgs FDR_DBG_PARAM);
+typedef void (*RangeKernel)(const _Float16 *, const float *, int, const _Float16 *, int, int, SegBounds, int *, int *);
+static_assert(kShapes[FDR_R128].tps == RANGE_STAGES && kShapes[FDR_R256].tps == RANGE_STAGES &&
+              kShapes[FDR_R512].tps == RANGE_STAGES, "the range kernel's ring");
+
+template <int S>
+static constexpr bool shape_compiled() {
+    constexpr KnnShape e = kShapes[S];
+#ifdef FDR_DEV
+    constexpr bool built = true;
+#else
+    constexpr bool built = e.release;
+#endif
+    constexpr bool pass = e.family == FDR_FAM_PREFILTER || e.family == FDR_FAM_PINGPONG;
+    return built && (!pass || (((unsigned long long)(FDR_SHAPE_MASK) >> S) & 1));
+}
+template <int S>
+static constexpr TileKernel tile_kernel() {
+    constexpr KnnShape e = kShapes[S];
+    if constexpr (e.family == FDR_FAM_TILE && shape_compiled<S>()) return knn_tile_kernel<e.dp, e.nq, e.nw, e.wps>;
+    else return nullptr;
+}
+template <int S, int LH>
+static constexpr PassKernel pass_kernel() {
+    constexpr KnnShape e = kShapes[S];
+    if constexpr (!shape_compiled<S>() || !(e.lists & LH & FDR_LH_MASK)) return nullptr;
+    else if constexpr (e.family == FDR_FAM_PREFILTER)
+        return knn_prefilter_kernel<e.dp, e.nq, e.nw, e.wps, e.units(), LH, e.paired && LH == 16>;
+    else if constexpr (e.family == FDR_FAM_PINGPONG) return knn_prefilter_pp_kernel<e.dp, e.units(), LH>;
+    else return nullptr;
+}
+template <int S>
+static constexpr RangeKernel range_kernel() {
+    constexpr KnnShape e = kShapes[S];
+    if constexpr (!shape_compiled<S>()) return nullptr;
+    else if constexpr (e.family == FDR_FAM_RANGE) return knn_range_kernel<e.dp, e.nw, e.dp == 128 ? e.wps : 2>;  // (kShapes: R256)
+    else if constexpr (e.family == FDR_FAM_RANGE_PP) return knn_range_pp_kernel<e.dp, e.units()>;
+    else return nullptr;
+}
+template <size_t... S>
+struct KnnKernelTable {
+    static constexpr TileKernel tile[] = {tile_kernel<S>()...};
+    static constexpr PassKernel pass[][2] = {{pass_kernel<S, 16>(), pass_kernel<S, 32>()}...};  // [shape][K' > 32]
+    static constexpr RangeKernel range[] = {range_kernel<S>()...};
+};
+template <size_t... S>
+static KnnKernelTable<S...> knn_kernel_table(std::index_sequence<S...>);
+typedef decltype(knn_kernel_table(std::make_index_sequence<FDR_NUM_SHAPES>())) KnnKernels;
+
+static int no_kernel(int shape) {
+    return fail(FDR_E_STATE, "this development build was compiled without the kernel shape this call needs (kShapes[%d])",
+                shape);
+}
+
+// Launches a plan's nqb * nseg work items: in one launch, or (p.cohort > 0: knn_plan_compute) in synchronised rounds of
+// p.cohort workgroups dealt round-robin to at most max_queues queues -- the caller's stream and ctx->aux_stream[] -- so
+// that the workgroups of a later launch take the slots the stragglers of an earlier one have freed (one queue: every
+// launch ends with its slowest workgroup while the rest of the chip idles).  launch(stream, workgroups, first item)
+// queues one launch.  Timed as one `kind` span over all launches when they overlap on several queues (their own spans
+// would count the same time twice), else a span per launch (span_each) or one around them all.
+struct Rounds {
+    int launches = 0, queues = 0;
+};
+template <class Launch>
+static int launch_rounds(fdr_ctx *ctx, const KnnPlan &p, int max_queues, int kind, bool span_each, hipStream_t st,
+                         Rounds &r, Launch launch) {
+    const long long n_items = (long long)p.nqb * p.nseg;
+    const long long per_launch = p.cohort > 0 ? p.cohort : n_items;
+    const int nqueues = p.cohort > 0 && n_items > per_launch ? std::max(1, std::min(p.queues, max_queues)) : 1;
+    hipStream_t qs[4] = {st, st, st, st};
+    if (nqueues > 1) {
+        if (!ctx->aux_ev[0]) {
+            for (hipStream_t &a : ctx->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&a, hipStreamNonBlocking));
+            for (hipEvent_t &e : ctx->aux_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        for (int q = 1; q < nqueues; ++q) qs[q] = ctx->aux_stream[q - 1];
+    }
+    const bool one_span = nqueues > 1 || !span_each;
+    int trc;
+    if (one_span && (trc = timing_begin(ctx, kind, st))) return trc;
+    if (nqueues > 1) {  // what `st` has queued so far is visible to the other queues' launches
+        HIP_TRY(hipEventRecord(ctx->aux_ev[0], st));
+        for (int q = 1; q < nqueues; ++q) HIP_TRY(hipStreamWaitEvent(qs[q], ctx->aux_ev[0], 0));
+    }
+    int li = 0;  // launch li goes to queue li % nqueues
+    for (long long base = 0; base < n_items; base += per_launch, ++li) {
+        const hipStream_t ls = qs[li % nqueues];
+        if (!one_span && (trc = timing_begin(ctx, kind, ls))) return trc;
+        launch(ls, (unsigned)std::min(per_launch, n_items - base), (int)base);
+        if (!one_span && (trc = timing_end(ctx, kind, ls))) return trc;
+    }
+    HIP_TRY(hipGetLastError());
+    r.launches = li;
+    r.queues = nqueues;
+    for (int q = 1; q < nqueues; ++q) {  // `st` waits for everything the other queues have been given
+        HIP_TRY(hipEventRecord(ctx->aux_ev[q], qs[q]));
+        HIP_TRY(hipStreamWaitEvent(st, ctx->aux_ev[q], 0));
+    }
+    return one_span ? timing_end(ctx, kind, st) : FDR_OK;
+}
+
 static int launch_knn_exact(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero, int64_t nq,
                       const float *d_That, const uint8_t *d_tzero, int64_t nt, int64_t t_base,
                       int d, int k, int32_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes,
@@ -909,6 +1023,8 @@ static int launch_knn_exact(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_
     const KnnPlan p = knn_plan(ctx->num_cus, nq, nt, d, k);
     if (ws_bytes < p.total_bytes)
         return fail(FDR_E_ARG, "knn: workspace %zu < required %zu bytes", ws_bytes, p.total_bytes);
+    const TileKernel kern = KnnKernels::tile[p.shape];
+    if (!kern) return no_kernel(p.shape);
     unsigned *d_bits = reinterpret_cast<unsigned *>(d_ws);
     unsigned *d_shared = reinterpret_cast<unsigned *>(static_cast<char *>(d_ws) + p.bits_bytes);
     u64 *d_partial = reinterpret_cast<u64 *>(static_cast<char *>(d_ws) + p.bits_bytes + p.shared_bytes);
@@ -924,50 +1040,14 @@ static int launch_knn_exact(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_
     ctx->trace.exact_qsets = sh.nq;
     const int dbg = dev_knobs().debug;  // (development builds only; 0 in the release library)
     (void)dbg;
-    // the nqb * nseg work items in one launch, or (p.cohort > 0: knn_plan_compute) in synchronised rounds dealt to
-    // p.queues queues, like the prefilter pass
-    const long long n_items = (long long)p.nqb * p.nseg;
-    const long long per_launch = p.cohort > 0 ? p.cohort : n_items;
-    const int nqueues = p.cohort > 0 && n_items > per_launch ? std::max(1, std::min(p.queues, 2)) : 1;
-    hipStream_t qs[2] = {st, st};
-    if (nqueues > 1) {
-        if (!ctx->aux_ev[0]) {
-            for (hipStream_t &a : ctx->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&a, hipStreamNonBlocking));
-            for (hipEvent_t &e : ctx->aux_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        qs[1] = ctx->aux_stream[0];
-    }
-    int trc = timing_begin(ctx, FDR_KERNEL_KNN_TILE, st);
+    const int qcap = knn_qcap(sh, k);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    Rounds r;  // (rounds on at most two queues, like the prefilter pass)
+    int trc = launch_rounds(ctx, p, 2, FDR_KERNEL_KNN_TILE, false, st, r, [&](hipStream_t s, unsigned grid, int base) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh.nw), lds, s, d_Qhat, d_qzero, (int)nq, d_That, d_bits, (int)nt,
+                           (int)t_base, p.segs, k, p.nq_pad, d_partial, d_shared, qcap, base, p.nqb FDR_DBG_ARG(dbg));
+    });
     if (trc) return trc;
-    if (nqueues > 1) {
-        HIP_TRY(hipEventRecord(ctx->aux_ev[0], st));
-        HIP_TRY(hipStreamWaitEvent(qs[1], ctx->aux_ev[0], 0));
-    }
-#define FDR_LAUNCH_KNN(DP_, NQ_, NW_, WPS_)                                                          \
-    do {                                                                                             \
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_tile_kernel<DP_, NQ_, NW_, WPS_>), \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));          \
-        int li_ = 0;                                                                                 \
-        for (long long base_ = 0; base_ < n_items; base_ += per_launch, ++li_)                       \
-            hipLaunchKernelGGL((knn_tile_kernel<DP_, NQ_, NW_, WPS_>),                               \
-                               dim3((unsigned)std::min(per_launch, n_items - base_)), dim3(64 * NW_), lds, \
-                               qs[li_ % nqueues], d_Qhat, d_qzero, (int)nq, d_That, d_bits, (int)nt, (int)t_base, \
-                               p.segs, k, p.nq_pad, d_partial, d_shared, knn_qcap(sh, k), (int)base_, p.nqb \
-                               FDR_DBG_ARG(dbg));                                                    \
-    } while (0)
-    switch (p.shape) {
-        case 0: FDR_LAUNCH_KNN(128, 1, 4, 3); break;
-        case 1: FDR_LAUNCH_KNN(128, 1, 8, 4); break;
-        case 2: FDR_LAUNCH_KNN(128, 2, 4, 2); break;
-        case 3: FDR_LAUNCH_KNN(256, 1, 8, 2); break;
-        default: FDR_LAUNCH_KNN(512, 1, 4, 1); break;
-    }
-#undef FDR_LAUNCH_KNN
-    HIP_TRY(hipGetLastError());
-    if (nqueues > 1) {
-        HIP_TRY(hipEventRecord(ctx->aux_ev[1], qs[1]));
-        HIP_TRY(hipStreamWaitEvent(st, ctx->aux_ev[1], 0));
-    }
 #ifdef FDR_DEBUG_COUNTERS
     if (dbg & 2) {
         unsigned long long c[8];
@@ -979,7 +1059,6 @@ static int launch_knn_exact(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_
         HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_counters), z, sizeof(z)));
     }
 #endif
-    if ((trc = timing_end(ctx, FDR_KERNEL_KNN_TILE, st))) return trc;
     if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_MERGE, st))) return trc;
     hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st,
                        (const u64 *)d_partial, p.nseg, (int)nq, p.nq_pad, k, d_idx, d_dist);
@@ -987,115 +1066,6 @@ static int launch_knn_exact(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_
     return timing_end(ctx, FDR_KERNEL_KNN_MERGE, st);
 }
 
-// Which of the prefilter pass's shapes are compiled (-DFDR_SHAPE_MASK=<bits of the FDR_SHAPE_CASE numbers below>,
-// -DFDR_LH_MASK=<16 | 32 | 48>): the release library holds the shapes prefilter_shape() chooses by itself, a development
-// build all of them (the round-3 shapes the knobs D256 / PP can put back), or a subset to save minutes of hipcc.
-#ifndef FDR_SHAPE_MASK
-#ifdef FDR_DEV
-#define FDR_SHAPE_MASK 0xffff
-#else
-#define FDR_SHAPE_MASK 0xA4CE  // the shapes prefilter_shape() can choose without a development knob: cases 1-3, 6, 7, 10, 13, 15
-#endif
-#endif
-#ifndef FDR_LH_MASK
-#define FDR_LH_MASK 48
-#endif
-#define FDR_SEL_1(...) __VA_ARGS__
-#define FDR_SEL_0(...) return fail(FDR_E_STATE, "this development build was compiled without the kernel shape this call needs")
-#define FDR_CAT2(a, b) a##b
-#define FDR_CAT(a, b) FDR_CAT2(a, b)
-#if (FDR_SHAPE_MASK >> 0) & 1
-#define FDR_SHAPE_ON_0 1
-#else
-#define FDR_SHAPE_ON_0 0
-#endif
-#if (FDR_SHAPE_MASK >> 1) & 1
-#define FDR_SHAPE_ON_1 1
-#else
-#define FDR_SHAPE_ON_1 0
-#endif
-#if (FDR_SHAPE_MASK >> 2) & 1
-#define FDR_SHAPE_ON_2 1
-#else
-#define FDR_SHAPE_ON_2 0
-#endif
-#if (FDR_SHAPE_MASK >> 3) & 1
-#define FDR_SHAPE_ON_3 1
-#else
-#define FDR_SHAPE_ON_3 0
-#endif
-#if (FDR_SHAPE_MASK >> 4) & 1
-#define FDR_SHAPE_ON_4 1
-#else
-#define FDR_SHAPE_ON_4 0
-#endif
-#if (FDR_SHAPE_MASK >> 5) & 1
-#define FDR_SHAPE_ON_5 1
-#else
-#define FDR_SHAPE_ON_5 0
-#endif
-#if (FDR_SHAPE_MASK >> 6) & 1
-#define FDR_SHAPE_ON_6 1
-#else
-#define FDR_SHAPE_ON_6 0
-#endif
-#if (FDR_SHAPE_MASK >> 7) & 1
-#define FDR_SHAPE_ON_7 1
-#else
-#define FDR_SHAPE_ON_7 0
-#endif
-#if (FDR_SHAPE_MASK >> 8) & 1
-#define FDR_SHAPE_ON_8 1
-#else
-#define FDR_SHAPE_ON_8 0
-#endif
-#if (FDR_SHAPE_MASK >> 9) & 1
-#define FDR_SHAPE_ON_9 1
-#else
-#define FDR_SHAPE_ON_9 0
-#endif
-#if (FDR_SHAPE_MASK >> 10) & 1
-#define FDR_SHAPE_ON_10 1
-#else
-#define FDR_SHAPE_ON_10 0
-#endif
-#if (FDR_SHAPE_MASK >> 11) & 1
-#define FDR_SHAPE_ON_11 1
-#else
-#define FDR_SHAPE_ON_11 0
-#endif
-#if (FDR_SHAPE_MASK >> 12) & 1
-#define FDR_SHAPE_ON_12 1
-#else
-#define FDR_SHAPE_ON_12 0
-#endif
-#if (FDR_SHAPE_MASK >> 13) & 1
-#define FDR_SHAPE_ON_13 1
-#else
-#define FDR_SHAPE_ON_13 0
-#endif
-#if (FDR_SHAPE_MASK >> 14) & 1
-#define FDR_SHAPE_ON_14 1
-#else
-#define FDR_SHAPE_ON_14 0
-#endif
-#if (FDR_SHAPE_MASK >> 15) & 1
-#define FDR_SHAPE_ON_15 1
-#else
-#define FDR_SHAPE_ON_15 0
-#endif
-#if FDR_LH_MASK & 16
-#define FDR_LH_ON_16 1
-#else
-#define FDR_LH_ON_16 0
-#endif
-#if FDR_LH_MASK & 32
-#define FDR_LH_ON_32 1
-#else
-#define FDR_LH_ON_32 0
-#endif
-#define FDR_SHAPE_CASE(n, ...) FDR_CAT(FDR_SEL_, FDR_SHAPE_ON_##n)(__VA_ARGS__)
-#define FDR_LH_CASE(n, ...) FDR_CAT(FDR_SEL_, FDR_LH_ON_##n)(__VA_ARGS__)
 // ---- prefilter mode: fp16 pass -> certificate + exact re-rank -> exact pass for the rest -------
 static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero, int64_t nq,
                                 const float *d_That, const uint8_t *d_tzero, int64_t nt, int64_t t_base,
@@ -1137,7 +1107,10 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     tr.pass_wps = sh.wps;
     tr.pass_units = sh.tps;
     tr.pass_list_keys = kp <= 32 ? 16 : 32;
+    tr.pass_pingpong = sh.family == FDR_FAM_PINGPONG;
     tr.pass_segments = p.nseg;
+    const PassKernel kern = KnnKernels::pass[pshape][kp > 32];
+    if (!kern) return no_kernel(pshape);
     unsigned *d_bits = reinterpret_cast<unsigned *>(ws);
     unsigned *d_shared = reinterpret_cast<unsigned *>(ws + p.bits_bytes);
     u64 *d_partial = reinterpret_cast<u64 *>(ws + p.bits_bytes + p.shared_bytes);
@@ -1188,108 +1161,22 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     if ((trc = timing_end(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
     const int pdbg = dev_knobs().debug;
     (void)pdbg;
-    // the nqb * nseg work items in launches of p.cohort workgroups (0: one launch): see knn_plan_compute
-    const long long n_items = (long long)p.nqb * p.nseg;
-    const long long per_launch = p.cohort > 0 ? p.cohort : n_items;
-    // Several queues: with the launches of the synchronised rounds dealt round-robin to the caller's stream and
-    // further ones, the workgroups of a later launch take the slots the stragglers of an earlier one have
-    // freed (one queue: every launch ends with its slowest workgroup while the rest of the chip idles).
-    const int nqueues = p.cohort > 0 && n_items > per_launch ? std::max(1, std::min(p.queues, 4)) : 1;
-    // one timed span for the whole pass when launches overlap (their own spans would count the same time twice)
-    if (nqueues > 1 && (trc = timing_begin(ctx, FDR_KERNEL_KNN_PREFILTER, st))) return trc;
-    hipStream_t qs[4] = {st, st, st, st};
-    if (nqueues > 1) {
-        if (!ctx->aux_ev[0]) {
-            for (hipStream_t &a : ctx->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&a, hipStreamNonBlocking));
-            for (hipEvent_t &e : ctx->aux_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        for (int q = 1; q < nqueues; ++q) qs[q] = ctx->aux_stream[q - 1];
-    }
-    auto fork = [&]() -> int {  // what `st` has queued so far is visible to the other queues' next launches
-        if (nqueues > 1) {
-            HIP_TRY(hipEventRecord(ctx->aux_ev[0], st));
-            for (int q = 1; q < nqueues; ++q) HIP_TRY(hipStreamWaitEvent(qs[q], ctx->aux_ev[0], 0));
-        }
-        return FDR_OK;
-    };
-    auto join = [&]() -> int {  // `st` waits for everything the other queues have been given
-        for (int q = 1; q < nqueues; ++q) {
-            HIP_TRY(hipEventRecord(ctx->aux_ev[q], qs[q]));
-            HIP_TRY(hipStreamWaitEvent(st, ctx->aux_ev[q], 0));
-        }
-        return FDR_OK;
-    };
-    int li = 0;  // launches so far (launch li goes to queue li % nqueues)
-    auto launch_items = [&](long long it_lo, long long it_hi) -> int {
-#define FDR_LAUNCH_PRE3(KERNEL_, THREADS_)                                                              \
-    do {                                                                                                \
-        for (long long base_ = it_lo; base_ < it_hi; base_ += per_launch, ++li) { /* (one queue: every launch its own timed span) */ \
-            hipStream_t ls_ = qs[li % nqueues];                                                         \
-            if (lds > 32768) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            if (nqueues == 1 && (trc = timing_begin(ctx, FDR_KERNEL_KNN_PREFILTER, ls_))) return trc;   \
-            hipLaunchKernelGGL(KERNEL_, dim3((unsigned)std::min(per_launch, it_hi - base_)), dim3(THREADS_), lds, \
-                               ls_, p1_q, (int)nq, p1_t, (int)nt, (int)t_base, p.segs, kp, p.nq_pad, d_partial, \
-                               d_shared, ib, (int)base_, p.nqb, ord FDR_DBG_ARG(pdbg));             \
-            if (nqueues == 1 && (trc = timing_end(ctx, FDR_KERNEL_KNN_PREFILTER, ls_))) return trc;     \
-        }                                                                                               \
-    } while (0)
-#define FDR_LAUNCH_PRE2(DP_, NQ_, NW_, WPS_, U_, LH_) \
-    FDR_LAUNCH_PRE3((knn_prefilter_kernel<DP_, NQ_, NW_, WPS_, U_, LH_>), 64 * NW_)
-#define FDR_LAUNCH_PRE(DP_, NQ_, NW_, WPS_, U_)                                                         \
-    do {                                                                                                \
-        if (kp <= 32) FDR_LH_CASE(16, FDR_LAUNCH_PRE2(DP_, NQ_, NW_, WPS_, U_, 16));                    \
-        else FDR_LH_CASE(32, FDR_LAUNCH_PRE2(DP_, NQ_, NW_, WPS_, U_, 32));                             \
-    } while (0)
-        // (FDR_SHAPE_CASE: a development build may compile a subset of the shapes, -DFDR_SHAPE_MASK=bits: 10 minutes of hipcc otherwise)
-        if (dp == 128 && kp <= 32) {
-            // d <= 128, K' <= 32: the stage's two tiles as two interleaved MFMA chains (1-4 % faster; still
-            // <= 128 VGPRs)
-            if (sh.nw == 8 && sh.tps == 8) FDR_SHAPE_CASE(15, FDR_LAUNCH_PRE3((knn_prefilter_kernel<128, 1, 8, 4, 4, 16, true>), 512));
-            else if (sh.nw == 8) FDR_SHAPE_CASE(0, FDR_LAUNCH_PRE3((knn_prefilter_kernel<128, 1, 8, 4, 2, 16, true>), 512));
-            else FDR_SHAPE_CASE(1, FDR_LAUNCH_PRE3((knn_prefilter_kernel<128, 1, 4, 4, 2, 16, true>), 256));
-        } else if (dp == 128) FDR_SHAPE_CASE(2, FDR_LAUNCH_PRE(128, 1, 4, 4, 2));
-        else if (sh.nw == 8 && sh.wps == 2 && (sh.tps == 16 || (dp == 512 && sh.tps == 8)) && dev_knobs().pp != 0) {
-            // the ping-pong kernel (knn_prefilter_pp.inc)
-            tr.pass_pingpong = 1;
-            if (dp == 256) {
-                if (kp <= 32) FDR_SHAPE_CASE(3, FDR_LH_CASE(16, FDR_LAUNCH_PRE3((knn_prefilter_pp_kernel<256, 8, 16>), 512)));
-                else FDR_SHAPE_CASE(3, FDR_LH_CASE(32, FDR_LAUNCH_PRE3((knn_prefilter_pp_kernel<256, 8, 32>), 512)));
-            } else if (dp == 512 && sh.tps == 16 && kp <= 32) {
-                FDR_SHAPE_CASE(13, FDR_LH_CASE(16, FDR_LAUNCH_PRE3((knn_prefilter_pp_kernel<512, 8, 16>), 512)));
-            } else if (dp == 512 && sh.tps == 8 && kp > 32) {
-                FDR_SHAPE_CASE(13, FDR_LH_CASE(32, FDR_LAUNCH_PRE3((knn_prefilter_pp_kernel<512, 4, 32>), 512)));
-            } else {
-                return fail(FDR_E_STATE, "knn prefilter: no ping-pong kernel for d = %d, K' = %d, ring of %d units", d, kp, sh.tps);
-            }
-        } else if (dp == 256 && sh.tps == 16 && sh.nw == 8) FDR_SHAPE_CASE(14, FDR_LAUNCH_PRE(256, 1, 8, 2, 8));
-        else if (dp == 256 && sh.tps == 8 && sh.nw == 8) FDR_SHAPE_CASE(4, FDR_LAUNCH_PRE(256, 1, 8, 2, 4));
-        else if (dp == 512 && sh.tps == 8 && sh.nw == 8) FDR_SHAPE_CASE(5, FDR_LAUNCH_PRE(512, 1, 8, 2, 4));
-        else if (dp == 256 && sh.tps == 8) FDR_SHAPE_CASE(6, FDR_LAUNCH_PRE(256, 1, 4, 2, 4));
-        else if (dp == 512 && sh.tps == 8) FDR_SHAPE_CASE(7, FDR_LAUNCH_PRE(512, 1, 4, 2, 4));
-        else if (dp == 256 && sh.wps == 2 && sh.nw == 8) FDR_SHAPE_CASE(8, FDR_LAUNCH_PRE(256, 1, 8, 2, 2));
-        else if (dp == 256 && sh.wps == 2) FDR_SHAPE_CASE(9, FDR_LAUNCH_PRE(256, 1, 4, 2, 2));
-        else if (dp == 256) FDR_SHAPE_CASE(10, FDR_LAUNCH_PRE(256, 1, 4, 3, 2));
-        else FDR_SHAPE_CASE(11, FDR_LAUNCH_PRE(512, 1, 4, 2, 2));
-#undef FDR_LAUNCH_PRE3
-#undef FDR_LAUNCH_PRE2
-#undef FDR_LAUNCH_PRE
-        HIP_TRY(hipGetLastError());
-        return FDR_OK;
-    };
-    int lrc;
-    if ((lrc = fork())) return lrc;
-    if ((lrc = launch_items(0, n_items))) return lrc;
-    ctx->last_pass_launches = li;
-    ctx->last_pass_queues = nqueues;
-    tr.pass_launches = li;
-    tr.pass_queues = nqueues;
-    if ((lrc = join())) return lrc;  // the merge below (on `st`) needs the other queues' launches too
-    if (nqueues > 1 && (trc = timing_end(ctx, FDR_KERNEL_KNN_PREFILTER, st))) return trc;
+    if (lds > 32768)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    Rounds r;  // (rounds on up to four queues; one queue: every launch its own timed span)
+    const int lrc = launch_rounds(ctx, p, 4, FDR_KERNEL_KNN_PREFILTER, true, st, r, [&](hipStream_t s, unsigned grid, int base) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh.nw), lds, s, p1_q, (int)nq, p1_t, (int)nt, (int)t_base, p.segs, kp,
+                           p.nq_pad, d_partial, d_shared, ib, base, p.nqb, ord FDR_DBG_ARG(pdbg));
+    });
+    ctx->last_pass_launches = r.launches;
+    ctx->last_pass_queues = r.queues;
+    tr.pass_launches = r.launches;
+    tr.pass_queues = r.queues;
+    if (lrc) return lrc;
 #ifdef FDR_STAMPS
     {
         unsigned long long c[16][8];
-        HIP_TRY(hipStreamSynchronize(st));
-        for (int q = 1; q < nqueues; ++q) HIP_TRY(hipStreamSynchronize(qs[q]));
+        HIP_TRY(hipStreamSynchronize(st));  // (the other queues' launches too: `st` has joined them)
         HIP_TRY(hipMemcpyFromSymbol(c, HIP_SYMBOL(g_stamps), sizeof(c)));
         for (int w = 0; w < sh.nw; ++w) {
             const double st_n = (double)std::max<unsigned long long>(1, c[w][5]);
@@ -1364,41 +1251,20 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
                                (const _Float16 *)d_hq, (const float *)d_theta, (const int *)d_rlist, first, c,
                                dp, d_hqc, d_thetac, d_cnt);
             HIP_TRY(hipGetLastError());
-            // From 4096 plateau queries (16 blocks of 256, times the plan's segments) the pass runs on the ping-pong
-            // skeleton (knn_range_pp_kernel: eight waves, one workgroup per CU, eight-unit stages); a handful of them (1 M
-            // rows: 1100) keeps round 3's kernel with its many short segments.
-            // (d <= 128, many plateau queries: round 3's eight-wave form, development knob RANGE8 with RANGEPP = 0)
-            const int r8 = dev_knobs().range8, rpp = dev_knobs().rangepp;
-            const bool use_pp = rpp == 1 || (rpp < 0 && c >= 4096);
-            const bool wide = !use_pp && dp == 128 && (r8 == 1 || (r8 < 0 && rcount >= 65536));
-            const KnnPlan rp = knn_plan(ctx->num_cus, c, nt, d, 1, use_pp ? FDR_SHAPE_PP256 : wide ? FDR_SHAPE_PREFILTER_W8 : range_shape(dp));  // (k = 1: ring-only LDS)
-            const size_t rlds = use_pp ? (size_t)16 * 32 * 256 + (size_t)RANGE_LANE_BUF * 512 * 4
-                                       : (size_t)RANGE_STAGES * 32 * 256 + (size_t)RANGE_LANE_BUF * (wide ? 512 : 256) * 4;  // ring + lane buffers
-#define FDR_LAUNCH_RANGE(DP_, NW_, WPS_)                                                                \
-    hipLaunchKernelGGL((knn_range_kernel<DP_, NW_, WPS_>), dim3((unsigned)rp.nqb, (unsigned)rp.nseg),      \
-                       dim3(64 * NW_), rlds, st, (const _Float16 *)d_hqc, (const float *)d_thetac, c,     \
-                       (const _Float16 *)d_ht, (int)nt, (int)t_base, rp.segs, d_cnt, d_rcand)
-#define FDR_LAUNCH_RANGE_PP(DP_)                                                                        \
-    do {                                                                                                \
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_range_pp_kernel<DP_, 8>),         \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));            \
-        hipLaunchKernelGGL((knn_range_pp_kernel<DP_, 8>), dim3((unsigned)rp.nqb, (unsigned)rp.nseg), dim3(512), rlds, \
-                           st, (const _Float16 *)d_hqc, (const float *)d_thetac, c, (const _Float16 *)d_ht, (int)nt,  \
-                           (int)t_base, rp.segs, d_cnt, d_rcand);                                       \
-    } while (0)
-            if (use_pp && dp == 128) FDR_LAUNCH_RANGE_PP(128);
-            else if (use_pp && dp == 256) FDR_LAUNCH_RANGE_PP(256);
-            else if (use_pp) FDR_LAUNCH_RANGE_PP(512);
-            else if (wide) FDR_LAUNCH_RANGE(128, 8, 4);
-            else if (dp == 128) FDR_LAUNCH_RANGE(128, 4, 4);
-            else if (dp == 256) FDR_LAUNCH_RANGE(256, 4, 2);
-            else FDR_LAUNCH_RANGE(512, 4, 2);
-#undef FDR_LAUNCH_RANGE
-#undef FDR_LAUNCH_RANGE_PP
+            const int rs = range_shape(dp, c, rcount);
+            const KnnShape &rsh = kShapes[rs];
+            const RangeKernel rk = KnnKernels::range[rs];
+            if (!rk) return no_kernel(rs);
+            const KnnPlan rp = knn_plan(ctx->num_cus, c, nt, d, 1, rs);  // (k = 1: ring-only LDS)
+            const size_t rlds = knn_lds_bytes(rsh, 1) + (size_t)RANGE_LANE_BUF * 64 * rsh.nw * 4;  // ring + lane buffers
+            if (rsh.family == FDR_FAM_RANGE_PP)
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(rk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
+            hipLaunchKernelGGL(rk, dim3((unsigned)rp.nqb, (unsigned)rp.nseg), dim3(64 * rsh.nw), rlds, st, (const _Float16 *)d_hqc,
+                               (const float *)d_thetac, c, (const _Float16 *)d_ht, (int)nt, (int)t_base, rp.segs, d_cnt, d_rcand);
             HIP_TRY(hipGetLastError());
             tr.range_chunks++;
-            tr.range_pp_chunks += use_pp ? 1 : 0;
-            tr.range_w8_chunks += wide ? 1 : 0;
+            tr.range_pp_chunks += rsh.family == FDR_FAM_RANGE_PP;
+            tr.range_w8_chunks += rs == FDR_R128_W8;
             hipLaunchKernelGGL(knn_rerank_long_kernel, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st,
                                (const int *)(d_rlist + first), c, (const int *)d_cnt, (const int *)d_rcand, k,
                                d_Qhat, d_That, dp, (int)t_base, d_idx, d_dist, d_counter, d_flagged, d_path);

@@ -52,53 +52,82 @@ static int prefilter_extra(int k) {
     return k + 12 <= width ? 12 : FDR_PREFILTER_EXTRA;
 }
 
-// Kernel shapes.  queries/workgroup QW = 32*NQ*NW; slots = workgroups resident per CU (LDS- and
-// register-limited).  Shape choice: see knn_choose_shape().
+// Kernel shapes: one entry per kernel a pass can launch (the candidate pass: per list width), so that an index names
+// the kernel.  queries/workgroup QW = 32*NQ*NW; slots = workgroups resident per CU (LDS- and register-limited).  The
+// passes choose among them with knn_choose_shape() (exact), prefilter_shape() (candidates) and range_shape() (range).
+enum KnnFamily {
+    FDR_FAM_TILE,       // knn_tile_kernel<DP, NQ, NW, WPS> (knn_exact.inc): the exact fp32 pass
+    FDR_FAM_PREFILTER,  // knn_prefilter_kernel<DP, NQ, NW, WPS, U, LH, PAIRED> (knn_prefilter.inc): fp16 candidates
+    FDR_FAM_PINGPONG,   // knn_prefilter_pp_kernel<DP, U, LH> (knn_prefilter_pp.inc): eight waves, 256 registers
+    FDR_FAM_RANGE,      // knn_range_kernel<DP, NW, WPS> (knn_prefilter.inc): the range pass over plateau queries
+    FDR_FAM_RANGE_PP,   // knn_range_pp_kernel<DP, U> (knn_prefilter_pp.inc): the range pass, ping-pong skeleton
+};
 struct KnnShape {
-    int dp, nq, nw, wps;
-    int tps;  // > 0: fp16 prefilter shape whose LDS ring holds tps one-tile (8 KB) stages
+    int family, dp, nq, nw, wps;
+    int tps;       // fp16 passes: the LDS ring's one-tile (8 KB) units, two stages of units() each; 0: the fp32 tile kernel
+    bool paired;   // candidate pass, 16-key lists: the stage's two tiles as two interleaved MFMA chains (d <= 128: 1-4 %)
+    int lists;     // candidate pass: the list widths (16 / 32 keys a lane, K' <= 32 / > 32) it is compiled for, or'ed
+    bool release;  // chosen with the default knobs: compiled into the release library (a development build: every entry)
+    constexpr int units() const { return tps / 2; }  // the stage's units U
 };
-static const KnnShape kShapes[] = {
-    {128, 1, 4, 3, 0},  // 128 queries/WG, <=168 VGPRs, up to 3 WG/CU
-    {128, 1, 8, 4, 0},  // 256 queries/WG, <=128 VGPRs, up to 2 WG/CU
-    {128, 2, 4, 2, 0},  // 256 queries/WG, <=256 VGPRs, up to 2 WG/CU
-    {256, 1, 8, 2, 0},  // 256 queries/WG, <=256 VGPRs, 1 WG/CU
-    {512, 1, 4, 1, 0},  // 128 queries/WG, one wave per SIMD: 512 registers per lane (256 of them queries)
-    // fp16 prefilter (LDS = the ring only): 128 queries/WG, two-unit stages (32 KB ring).  One-unit
-    // stages (a barrier per 8 MFMAs) cost +25 % at d <= 128, three / four-unit stages lose workgroups per
-    // CU, two query sets per wave (NQ = 2, 192 VGPRs) lost 10-25 % to the lower occupancy.
-    {128, 1, 4, 4, 4},  // d <= 128: <= 128 VGPRs, 4 WG/CU
-    {256, 1, 4, 3, 4},  // d <= 256: <= 168 VGPRs, one tile per stage
-    {512, 1, 4, 2, 4},  // d <= 512: 128 VGPRs of queries, half a tile per stage
+enum KnnShapeId {
+    FDR_X128, FDR_X128_W8, FDR_X128_Q2, FDR_X256, FDR_X512,
+    FDR_P128, FDR_P128_W8, FDR_P128_W8U4, FDR_P256, FDR_P256_V2, FDR_P256_W8, FDR_P256_U4, FDR_P256_W8U4, FDR_P256_W8U8,
+    FDR_P512, FDR_P512_U4, FDR_P512_W8U4,
+    FDR_PP256, FDR_PP512_U8, FDR_PP512_U4,
+    FDR_R128, FDR_R128_W8, FDR_R256, FDR_R512, FDR_RPP128, FDR_RPP256, FDR_RPP512,
+    FDR_NUM_SHAPES
+};
+static constexpr KnnShape kShapes[] = {
+    // the exact tile kernel
+    {FDR_FAM_TILE, 128, 1, 4, 3, 0, false, 0, true},   // X128: 128 queries/WG, <=168 VGPRs, up to 3 WG/CU
+    {FDR_FAM_TILE, 128, 1, 8, 4, 0, false, 0, false},  // X128_W8: 256 queries/WG, <=128 VGPRs, up to 2 WG/CU (knob SHAPE)
+    {FDR_FAM_TILE, 128, 2, 4, 2, 0, false, 0, true},   // X128_Q2: 256 queries/WG, <=256 VGPRs, up to 2 WG/CU
+    {FDR_FAM_TILE, 256, 1, 8, 2, 0, false, 0, true},   // X256: 256 queries/WG, <=256 VGPRs, 1 WG/CU
+    {FDR_FAM_TILE, 512, 1, 4, 1, 0, false, 0, true},   // X512: 128 queries/WG, one wave per SIMD: 512 registers per lane
+                                                       // (256 of them queries)
+    // fp16 candidate pass (LDS = the ring only): 128 queries/WG, two-unit stages (32 KB ring).  One-unit stages (a barrier
+    // per 8 MFMAs) cost +25 % at d <= 128, three / four-unit stages lose workgroups per CU, two query sets per wave
+    // (NQ = 2, 192 VGPRs) lost 10-25 % to the lower occupancy.
+    {FDR_FAM_PREFILTER, 128, 1, 4, 4, 4, true, 48, true},  // P128: d <= 128, <= 128 VGPRs, 4 WG/CU
     // eight waves per workgroup (256 queries, 2 WG/CU): every staged tile serves twice the queries, half the L2 -> LDS
-    // traffic and LDS-DMA instructions per flop (devtools/mfma_shape_bench.hip: 0.67 -> 0.76 of the peak for the bare loop)
-    {128, 1, 8, 4, 4},
+    // traffic and LDS-DMA instructions per flop (devtools/mfma_shape_bench.hip: 0.67 -> 0.76 of the peak for the bare loop);
+    // W8U4: FOUR-unit stages (two pairs of tiles per barrier, 64 KB ring, 2 WG/CU)
+    {FDR_FAM_PREFILTER, 128, 1, 8, 4, 4, true, 16, false},  // P128_W8 (knob W8 = 2)
+    {FDR_FAM_PREFILTER, 128, 1, 8, 4, 8, true, 16, true},   // P128_W8U4
+    {FDR_FAM_PREFILTER, 256, 1, 4, 3, 4, false, 48, true},  // P256: d <= 256, <= 168 VGPRs, one tile per stage
     // d <= 256 at 256 VGPRs: all eight fragments of a unit in flight (the d <= 512 kernel's inner loop), two workgroups per
-    // CU on two queues; and the same with eight waves (256 queries, one workgroup per CU)
-    {256, 1, 4, 2, 4},
-    {256, 1, 8, 2, 4},
+    // CU on two queues; and the same with eight waves (256 queries, one workgroup per CU)  (knob D256 = 1 / 2)
+    {FDR_FAM_PREFILTER, 256, 1, 4, 2, 4, false, 48, false},  // P256_V2
+    {FDR_FAM_PREFILTER, 256, 1, 8, 2, 4, false, 48, false},  // P256_W8
     // the 256-VGPR shapes with four-unit stages: a 64 KB ring, still two workgroups per CU (d <= 256 with K' > 32, d <= 512)
-    {256, 1, 4, 2, 8},
-    {512, 1, 4, 2, 8},
-    // the same with eight waves -- 256 queries per staged tile, one workgroup per CU (d <= 256 with K' > 32 and enough query
-    // blocks; d <= 512: development only, measured slower)
-    {256, 1, 8, 2, 8},
-    {512, 1, 8, 2, 8},
-    {256, 1, 8, 2, 16},  // ... with eight-unit stages, a 128 KB ring (d <= 256 with K' > 32 from 131 k queries)
-    {512, 1, 8, 2, 16},  // the same for d <= 512 (two tiles per stage)
-    {128, 1, 8, 2, 16},  // (unused: the ping-pong shape at d <= 128 measured 0.745 against 0.90 without the cold path and was dropped)
-    {128, 1, 8, 4, 8},   // d <= 128, eight waves, FOUR-unit stages (two pairs of tiles per barrier, 64 KB ring, 2 WG/CU)
+    {FDR_FAM_PREFILTER, 256, 1, 4, 2, 8, false, 32, true},  // P256_U4
+    // the same with eight waves -- 256 queries per staged tile, one workgroup per CU (d <= 256 with K' > 32; knob D256 = 4),
+    // and with eight-unit stages, a 128 KB ring (D256 = 5, or the ping-pong sizes with PP = 0)
+    {FDR_FAM_PREFILTER, 256, 1, 8, 2, 8, false, 32, false},   // P256_W8U4
+    {FDR_FAM_PREFILTER, 256, 1, 8, 2, 16, false, 32, false},  // P256_W8U8
+    {FDR_FAM_PREFILTER, 512, 1, 4, 2, 4, false, 48, false},   // P512: d <= 512, 128 VGPRs of queries, half a tile per stage
+    {FDR_FAM_PREFILTER, 512, 1, 4, 2, 8, false, 48, true},    // P512_U4
+    {FDR_FAM_PREFILTER, 512, 1, 8, 2, 8, false, 48, false},   // P512_W8U4: development only, measured slower (D256 = 4)
+    // The ping-pong kernel (eight waves, 256 registers, one workgroup per CU): d <= 256 with eight-unit stages; d <= 512
+    // with eight-unit stages for K' <= 32 and four-unit ones for K' > 32 (128 query + 33 list registers leave room for one
+    // tile's accumulators).  (d <= 128 measured 0.745 against 0.90 without the cold path and was dropped.)
+    {FDR_FAM_PINGPONG, 256, 1, 8, 2, 16, false, 48, true},  // PP256
+    {FDR_FAM_PINGPONG, 512, 1, 8, 2, 16, false, 16, true},  // PP512_U8
+    {FDR_FAM_PINGPONG, 512, 1, 8, 2, 8, false, 32, true},   // PP512_U4
+    // the range pass: the candidate pass's geometry, RANGE_STAGES one-unit stages (d > 128: compiled for 256 VGPRs; at
+    // d <= 256 it takes 148, so the three workgroups per CU of wps = 3 fit); from 4096 plateau queries the ping-pong
+    // skeleton with eight-unit stages
+    {FDR_FAM_RANGE, 128, 1, 4, 4, 4, false, 0, true},      // R128
+    {FDR_FAM_RANGE, 128, 1, 8, 4, 4, false, 0, true},      // R128_W8
+    {FDR_FAM_RANGE, 256, 1, 4, 3, 4, false, 0, true},      // R256
+    {FDR_FAM_RANGE, 512, 1, 4, 2, 4, false, 0, true},      // R512
+    {FDR_FAM_RANGE_PP, 128, 1, 8, 2, 16, false, 0, true},  // RPP128
+    {FDR_FAM_RANGE_PP, 256, 1, 8, 2, 16, false, 0, true},  // RPP256
+    {FDR_FAM_RANGE_PP, 512, 1, 8, 2, 16, false, 0, true},  // RPP512
 };
-// The ping-pong kernel (knn_prefilter_pp.inc: eight waves, 256 registers, one workgroup per CU): d <= 256 with eight-unit
-// stages; d <= 512 with eight-unit stages for K' <= 32 and four-unit ones for K' > 32 (128 query + 33 list registers leave
-// room for one tile's accumulators).
-#define FDR_SHAPE_PP256 15
-#define FDR_SHAPE_PP512_16 16
-#define FDR_SHAPE_PP512_32 14
-#define FDR_SHAPE_W8U4 18
-#define FDR_SHAPE_PREFILTER 5  // + 0 / 1 / 2 for d <= 128 / 256 / 512
-static int range_shape(int dp) { return FDR_SHAPE_PREFILTER + (dp == 128 ? 0 : dp == 256 ? 1 : 2); }
-#define FDR_SHAPE_PREFILTER_W8 8
+static_assert(sizeof(kShapes) / sizeof(kShapes[0]) == FDR_NUM_SHAPES, "one kShapes entry per KnnShapeId");
+
 static int prefilter_shape(int dp, int kp, int64_t nq, int num_cus, int64_t nt = 0) {  // kp = K' = candidates per query of the pass
     // d <= 128: eight waves per workgroup once the 256-query blocks fill (nearly) a round of two workgroups per CU --
     // 100.1 -> 97.7 ms at 1 M rows, 15.1 -> 14.6 ms for a rank's eighth of them; 100 k rows (391 blocks): 2.7 -> 3.0 ms,
@@ -113,7 +142,7 @@ static int prefilter_shape(int dp, int kp, int64_t nq, int num_cus, int64_t nt =
     const int64_t blocks = (nq + 255) / 256;
     const bool fills = blocks * 10 >= (int64_t)num_cus * 2 * 9 || (blocks >= num_cus && nt >= 4 * nq);
     if (dp == 128 && kp <= 32 && (w8 == 3 || ((w8 == 1 || w8 == 2) && fills)))
-        return w8 == 2 ? FDR_SHAPE_PREFILTER_W8 : FDR_SHAPE_W8U4;
+        return w8 == 2 ? FDR_P128_W8 : FDR_P128_W8U4;
     // d > 128: the ping-pong kernel once its 256-query blocks fill two launches of one workgroup per CU (round 4; same box,
     // round 3's shapes -> ping-pong): d = 256 / k = 50 at 1 M doubled rows 330 -> 323 ms, at 4 M 4.00 -> 3.40 s (0.67 -> 0.79 of
     // the fp16 peak), a rank of config 5 10.9 -> 8.8 s (0.68 -> 0.84); d = 256 / k = 20 at 1 M doubled rows 324 -> 290 ms;
@@ -122,8 +151,8 @@ static int prefilter_shape(int dp, int kp, int64_t nq, int num_cus, int64_t nt =
     // (development knob PP: 0 = never, 1 = at every size)
     const int pp = dev_knobs().pp;
     const bool pp_fills = (nq + 255) / 256 >= (int64_t)num_cus * 2;
-    if (dp == 256 && (pp == 1 || (pp < 0 && pp_fills))) return FDR_SHAPE_PP256;
-    if (dp == 512 && (pp == 1 || (pp < 0 && pp_fills))) return kp <= 32 ? FDR_SHAPE_PP512_16 : FDR_SHAPE_PP512_32;
+    if (dp == 256 && (pp == 1 || (pp < 0 && pp_fills))) return FDR_PP256;
+    if (dp == 512 && (pp == 1 || (pp < 0 && pp_fills))) return kp <= 32 ? FDR_PP512_U8 : FDR_PP512_U4;
     // Round 3's shapes.  d <= 256 with K' > 32 (the 2 x 32-key register lists): 64 fragment + 33 list + 16 accumulator
     // registers do not fit the 168-VGPR shape without spills -- at 256 VGPRs, two workgroups per CU on two queues, all
     // eight fragments of a unit in flight and four-unit stages: 575 -> 372 ms at 1 M doubled rows, k = 50 (K' <= 32 keeps the
@@ -131,14 +160,25 @@ static int prefilter_shape(int dp, int kp, int64_t nq, int num_cus, int64_t nt =
     // (knob D256: 1 / 2 = two-unit stages / eight waves and one workgroup per CU, 4 / 5 = the eight-wave shape with four- /
     // eight-unit stages: development, with PP = 0)
     const int v256 = dev_knobs().d256;
-    if (dp == 256 && v256 == 1) return FDR_SHAPE_PREFILTER_W8 + 1;
-    if (dp == 256 && v256 == 2) return FDR_SHAPE_PREFILTER_W8 + 2;
-    if (dp == 256 && kp > 32 && v256 == 4) return FDR_SHAPE_PREFILTER_W8 + 5;
-    if (dp == 256 && kp > 32 && (v256 == 5 || (v256 == 3 && pp == 0 && pp_fills))) return FDR_SHAPE_PREFILTER_W8 + 7;
-    if (dp == 256 && v256 == 3 && kp > 32) return FDR_SHAPE_PREFILTER_W8 + 3;
-    if (dp == 512 && v256 == 4) return FDR_SHAPE_PREFILTER_W8 + 6;
-    if (dp == 512 && v256 == 3) return FDR_SHAPE_PREFILTER_W8 + 4;
-    return range_shape(dp);
+    if (dp == 256 && v256 == 1) return FDR_P256_V2;
+    if (dp == 256 && v256 == 2) return FDR_P256_W8;
+    if (dp == 256 && kp > 32 && v256 == 4) return FDR_P256_W8U4;
+    if (dp == 256 && kp > 32 && (v256 == 5 || (v256 == 3 && pp == 0 && pp_fills))) return FDR_P256_W8U8;
+    if (dp == 256 && v256 == 3 && kp > 32) return FDR_P256_U4;
+    if (dp == 512 && v256 == 4) return FDR_P512_W8U4;
+    if (dp == 512 && v256 == 3) return FDR_P512_U4;
+    return dp == 128 ? FDR_P128 : dp == 256 ? FDR_P256 : FDR_P512;
+}
+
+// The range pass over `chunk` of its `plateau` queries.  From 4096 queries (16 blocks of 256, times the plan's segments)
+// it runs on the ping-pong skeleton (eight waves, one workgroup per CU, eight-unit stages); a handful of them (1 M rows:
+// 1100) keeps round 3's kernel with its many short segments.  (d <= 128, many plateau queries: round 3's eight-wave form,
+// development knob RANGE8 with RANGEPP = 0)
+static int range_shape(int dp, int chunk = 0, int plateau = 0) {  // (dp alone: the four-wave kernel of a few queries)
+    const int r8 = dev_knobs().range8, rpp = dev_knobs().rangepp;
+    if (rpp == 1 || (rpp < 0 && chunk >= 4096)) return dp == 128 ? FDR_RPP128 : dp == 256 ? FDR_RPP256 : FDR_RPP512;
+    if (dp == 128 && (r8 == 1 || (r8 < 0 && plateau >= 65536))) return FDR_R128_W8;
+    return dp == 128 ? FDR_R128 : dp == 256 ? FDR_R256 : FDR_R512;
 }
 
 static size_t knn_lds_bytes_q(const KnnShape &sh, int k, int qcap) {
@@ -167,15 +207,15 @@ static int knn_wg_per_cu(const KnnShape &sh, int k) {
 
 static int knn_choose_shape(int dp, int k) {
     const int forced = dev_knobs().shape;
-    if (forced >= 0 && forced < (int)(sizeof(kShapes) / sizeof(kShapes[0])) && kShapes[forced].dp == dp &&
+    if (forced >= 0 && forced < FDR_NUM_SHAPES && kShapes[forced].family == FDR_FAM_TILE && kShapes[forced].dp == dp &&
         knn_wg_per_cu(kShapes[forced], k) > 0)
         return forced;
-    if (dp == 256) return 3;
-    if (dp == 512) return 4;
+    if (dp == 256) return FDR_X256;
+    if (dp == 512) return FDR_X512;
     // d <= 128: the 4-wave / 128-query shape (no spills at 168 VGPRs, finest work granularity) while
     // at least two workgroups fit in LDS; for larger k the 2-chain 256-VGPR shape
-    if (knn_wg_per_cu(kShapes[0], k) >= 2) return 0;
-    return 2;
+    if (knn_wg_per_cu(kShapes[FDR_X128], k) >= 2) return FDR_X128;
+    return FDR_X128_Q2;
 }
 
 struct KnnPlan {

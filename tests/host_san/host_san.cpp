@@ -257,7 +257,8 @@ static int cmd_tables(unsigned seed, long long F, int d) {
     return 0;
 }
 
-static int check_plan(int cus, int64_t nq, int64_t nt, int d, int k, int shape) {
+// pass: the family of the pass that runs the plan (FDR_FAM_TILE, _PREFILTER or _RANGE; the ping-pong forms count as theirs)
+static int check_plan(int cus, int64_t nq, int64_t nt, int d, int k, int shape, int pass) {
     const KnnPlan p = knn_plan(cus, nq, nt, d, k, shape);
     const KnnShape &sh = kShapes[p.shape];
     const int T = (int)((nt + 31) / 32);
@@ -272,6 +273,11 @@ static int check_plan(int cus, int64_t nq, int64_t nt, int d, int k, int shape) 
     ok = ok && p.cohort >= 0 && (p.cohort == 0 || (p.cohort <= cus * 4 && sh.tps > 0)) &&
          p.total_bytes == p.bits_bytes + p.shared_bytes + p.partial_bytes &&
          p.partial_bytes == (size_t)p.nseg * p.nq_pad * (size_t)k * 8;
+    // a shape the default knobs choose is compiled into the release library, as a kernel of the pass's family (the
+    // candidate pass: for the list width K' = k needs)
+    const bool family = sh.family == pass || (pass == FDR_FAM_PREFILTER && sh.family == FDR_FAM_PINGPONG) ||
+                        (pass == FDR_FAM_RANGE && sh.family == FDR_FAM_RANGE_PP);
+    ok = ok && sh.release && family && (pass != FDR_FAM_PREFILTER || (sh.lists & (k <= 32 ? 16 : 32)));
     if (!ok) printf("FAIL plan cus=%d nq=%lld nt=%lld d=%d k=%d shape=%d nseg=%d\n", cus, (long long)nq, (long long)nt, d, k, shape, p.nseg);
     return ok ? 0 : 1;
 }
@@ -287,13 +293,19 @@ static int cmd_plan() {
                     if (nt < k) continue;
                     const int dp = padded_dim(d);
                     for (int64_t nq : {nt, (nt + 7) / 8, (int64_t)1}) {
-                        bad += check_plan(cus, nq, nt, d, k, -1);  // exact shapes
+                        bad += check_plan(cus, nq, nt, d, k, -1, FDR_FAM_TILE);  // exact shapes
                         ++n;
                         const int kp = (k + prefilter_extra(k) + 1) & ~1;
                         if (kp <= FDR_FAST_MAX_K && nt >= kp) {
-                            bad += check_plan(cus, nq, nt, d, kp, prefilter_shape(dp, kp, nq, cus));
-                            bad += check_plan(cus, nq, nt, d, 1, range_shape(dp));
-                            n += 2;
+                            bad += check_plan(cus, nq, nt, d, kp, prefilter_shape(dp, kp, nq, cus), FDR_FAM_PREFILTER);
+                            bad += check_plan(cus, nq, nt, d, kp, prefilter_shape(dp, kp, nq, cus, nt), FDR_FAM_PREFILTER);
+                            bad += check_plan(cus, nq, nt, d, 1, range_shape(dp), FDR_FAM_RANGE);
+                            // the range pass's chunks: a few plateau queries, or all of them
+                            for (const int64_t plateau : {std::min<int64_t>(nq, 4095), nq}) {
+                                const int c = (int)std::min<int64_t>(plateau, 32768);
+                                bad += check_plan(cus, c, nt, d, 1, range_shape(dp, c, (int)plateau), FDR_FAM_RANGE);
+                            }
+                            n += 5;
                         }
                     }
                 }
