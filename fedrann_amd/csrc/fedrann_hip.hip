@@ -410,11 +410,12 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float *__rest
 #include "csr_compact.inc"        // dead-feature filter (plain C++)
 #include "host_upload.inc"        // host CSR -> device in chunks: raw over PCIe and compacted on the host at once
 #include "knn_exact.inc"      // K3 / K4: fp32 MFMA tile kernel with LDS top-k lists, merge
+#include "knn_exact_wide.inc"  // K3s: K3 for 512 < d <= 1024, the components split over two waves
 #include "knn_prefilter.inc"  // P1 / P2: fp16 MFMA candidate pass, merges, certificate + re-rank, range pass
 #include "knn_prefilter_pp.inc"  // P1 for the 256-register shapes: the two waves of a SIMD take turns at the matrix pipe
 #include "knn_order.inc"      // P1: scan order by chunk mask (sort keys, ordered fp16 copy)
 #include "dedup_classes.inc"  // duplicate-row classes: hash, tables, gathers, expansion
-#include "knn_generic.inc"    // d > 512 or k > 64: every pair on the vector ALU
+#include "knn_generic.inc"    // d > 1024, or k > 64 / d > 512 below 8192 targets: every pair on the vector ALU
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -803,7 +804,6 @@ static int launch_normalize(fdr_ctx *ctx, const float *d_E, int64_t n_rows, int 
 }
 
 static size_t knn_workspace_bytes_impl(const fdr_ctx *ctx, int64_t nq, int64_t nt, int d, int k);
-static bool knn_generic_wanted(int dp, int k) { return dp > FDR_FAST_MAX_DIM || k > FDR_FAST_MAX_K; }
 
 // ---- prefilter mode: workspace layout -------------------------------------------------------
 // mode: FDR_MODE_AUTO uses the fp16 prefilter whenever it applies (d <= 128, k + 8 <= 64) and the
@@ -888,7 +888,9 @@ static PrefilterLayout prefilter_layout(const fdr_ctx *ctx, int64_t nq, int64_t 
 FDR_EXPORT size_t fdr_knn_workspace_bytes(fdr_ctx *ctx, int64_t nq, int64_t nt, int32_t d,
                                           int32_t k) {
     if (!ctx || nq <= 0 || nt <= 0 || k <= 0 || k > FDR_MAX_K || fdr_padded_dim(d) < 0) return 0;
-    if (knn_generic_wanted(fdr_padded_dim(d), k)) return 256;  // (the generic kernel needs no scratch)
+    const int route = knn_route(fdr_padded_dim(d), k, nt);
+    if (route == FDR_ROUTE_GENERIC) return 256;  // (the generic kernel needs no scratch)
+    if (route == FDR_ROUTE_WIDE) return knn_plan(ctx->num_cus, nq, nt, d, k).total_bytes;  // (the exact pass alone)
     return knn_workspace_bytes_impl(ctx, nq, nt, d, k);
 }
 
@@ -925,6 +927,7 @@ template <int S>
 static constexpr TileKernel tile_kernel() {
     constexpr KnnShape e = kShapes[S];
     if constexpr (e.family == FDR_FAM_TILE && shape_compiled<S>()) return knn_tile_kernel<e.dp, e.nq, e.nw, e.wps>;
+    else if constexpr (e.family == FDR_FAM_TILE_SPLIT && shape_compiled<S>()) return knn_tile_split_kernel<e.dp>;
     else return nullptr;
 }
 template <int S, int LH>
@@ -1012,7 +1015,7 @@ static int launch_knn_exact(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_
                       hipStream_t st) {
     const int dp = fdr_padded_dim(d);
     if (dp < 0) return fail(FDR_E_ARG, "knn: dimension %d unsupported (1..%d)", d, FDR_MAX_DIM);
-    if (k < 1 || k > FDR_FAST_MAX_K || dp > FDR_FAST_MAX_DIM)
+    if (k < 1 || k > FDR_EXACT_MAX_K || dp > FDR_EXACT_MAX_DIM)
         return fail(FDR_E_ARG, "knn: k=%d, d=%d outside the MFMA kernels' shapes", k, d);
     if (nq < 0 || nt < k) return fail(FDR_E_ARG, "knn: need n_targets (%lld) >= k (%d)", (long long)nt, k);
     if (nt + t_base > 0x7fffffffll || nq > 0x7fffffffll)
@@ -1060,8 +1063,12 @@ static int launch_knn_exact(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_
     }
 #endif
     if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_MERGE, st))) return trc;
-    hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st,
-                       (const u64 *)d_partial, p.nseg, (int)nq, p.nq_pad, k, d_idx, d_dist);
+    if (k <= FDR_FAST_MAX_K)
+        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st,
+                           (const u64 *)d_partial, p.nseg, (int)nq, p.nq_pad, k, d_idx, d_dist);
+    else
+        hipLaunchKernelGGL(knn_merge_wide_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st,
+                           (const u64 *)d_partial, p.nseg, (int)nq, p.nq_pad, k, d_idx, d_dist);
     HIP_TRY(hipGetLastError());
     return timing_end(ctx, FDR_KERNEL_KNN_MERGE, st);
 }
@@ -1312,7 +1319,7 @@ static int launch_knn_mode(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_q
                            const float *d_That, const uint8_t *d_tzero, int64_t nt, int64_t t_base, int d,
                            int k, int32_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes, hipStream_t st) {
     const int dp = fdr_padded_dim(d);
-    if (dp > 0 && k >= 1 && k <= FDR_FAST_MAX_K && nq > 0 && nt >= k && knn_prefilter_wanted(ctx, dp, nt, k) &&
+    if (dp > 0 && k >= 1 && knn_route(dp, k, nt) == FDR_ROUTE_FAST && nq > 0 && nt >= k && knn_prefilter_wanted(ctx, dp, nt, k) &&
         d_Qhat && d_qzero && d_That && d_tzero && d_idx && d_dist && d_ws)
         return launch_knn_prefilter(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx,
                                     d_dist, d_ws, ws_bytes, st);
@@ -1391,7 +1398,8 @@ static int launch_knn(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero,
                       const float *d_That, const uint8_t *d_tzero, int64_t nt, int64_t t_base, int d,
                       int k, int32_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes, hipStream_t st) {
     const int dp = fdr_padded_dim(d);
-    if (dp > 0 && k >= 1 && k <= FDR_MAX_K && knn_generic_wanted(dp, k)) {  // beyond the MFMA kernels' shapes
+    const int route = dp > 0 ? knn_route(dp, k, nt) : FDR_ROUTE_GENERIC;
+    if (dp > 0 && k >= 1 && k <= FDR_MAX_K && route == FDR_ROUTE_GENERIC) {  // beyond the MFMA kernels' shapes
         if (nq < 0 || nt < k) return fail(FDR_E_ARG, "knn: need n_targets (%lld) >= k (%d)", (long long)nt, k);
         if (nt + t_base > 0x7fffffffll || nq > 0x7fffffffll) return fail(FDR_E_ARG, "knn: row numbers exceed int32");
         if (nq == 0) return FDR_OK;
@@ -1421,7 +1429,8 @@ static int launch_knn(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero,
     const bool q_in_t = d_Qhat && d_That && dp > 0 && d_Qhat >= d_That &&
                         d_Qhat + (size_t)nq * dp <= d_That + (size_t)nt * dp &&
                         ((d_Qhat - d_That) % dp) == 0;
-    if (!(dp > 0 && k >= 1 && k <= FDR_FAST_MAX_K && nq > 0 && nt >= k && q_in_t && knn_dedup_wanted(ctx, nq, nt) &&
+    // (FDR_ROUTE_WIDE: the exact pass of launch_knn_mode, never the duplicate-row classes)
+    if (!(dp > 0 && k >= 1 && route == FDR_ROUTE_FAST && nq > 0 && nt >= k && q_in_t && knn_dedup_wanted(ctx, nq, nt) &&
           d_qzero && d_tzero && d_idx && d_dist && d_ws)) {
         ctx->last_unique_targets = (int)nt;
         ctx->last_unique_queries = (int)nq;
@@ -1564,7 +1573,7 @@ FDR_EXPORT int fdr_knn_classes_dev(fdr_ctx *ctx, const float *d_That, const uint
     if (dp < 0 || k < 1 || k > FDR_MAX_K || nt < k || nq_max <= 0 || nq_max > nt || !d_That || !d_tzero || !d_ws ||
         nt > 0x7fffffffll)
         return fail(FDR_E_ARG, "knn_classes: bad argument");
-    if (knn_generic_wanted(dp, k)) return FDR_OK;  // (no classes beyond the MFMA kernels' shapes: the callers use fdr_knn_dev)
+    if (knn_route(dp, k, nt) != FDR_ROUTE_FAST) return FDR_OK;  // (no classes beyond k <= 64, d <= 512: the callers use fdr_knn_dev)
     if (!knn_dedup_wanted(ctx, nq_max, nt)) return FDR_OK;  // (small sets: the callers use fdr_knn_dev)
     const DedupLayout L = dedup_layout(ctx, nq_max, nt, d, k);
     if (ws_bytes < L.total) return fail(FDR_E_ARG, "knn_classes: workspace %zu < required %zu bytes", ws_bytes, L.total);

@@ -409,17 +409,13 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_tile_kernel(
 // ------------------------------------------------------------------------------------------
 #define MERGE_CAP 512  // keys per query staged in LDS; longer candidate sets are re-read from global
 
-__global__ __launch_bounds__(256) void knn_merge_kernel(const u64 *__restrict__ partial, int nseg,
-                                                        int nq, int nq_pad, int K,
-                                                        int *__restrict__ idx_out,
-                                                        float *__restrict__ dist_out) {
-    __shared__ u64 stage[4][MERGE_CAP];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int q = blockIdx.x * 4 + wave;
-    if (q >= nq) return;
+// PICKS: picks per lane (K <= 64 * PICKS); stage: this wave's CAP keys of LDS
+template <int PICKS, int CAP>
+__device__ __forceinline__ void knn_merge_query(const u64 *__restrict__ partial, int nseg, int q, int nq_pad, int K,
+                                                u64 *mine_lds, int *__restrict__ idx_out, float *__restrict__ dist_out) {
+    const int lane = threadIdx.x & 63;
     const int M = nseg * K;
-    const bool staged = M <= MERGE_CAP;
-    u64 *mine_lds = stage[wave];
+    const bool staged = M <= CAP;
     if (staged) {  // one pass over global memory; the k selection rounds then run out of LDS
         for (int m = lane; m < M; m += 64) {
             const int seg = m / K, e = m - seg * K;
@@ -427,7 +423,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const u64 *__restrict__ 
         }
     }
     u64 prev1 = 0;  // previous pick + 1 (0 = none yet)
-    u64 mine = 0;
+    u64 mine = 0, mine1 = 0;  // picks lane and (PICKS = 2) lane + 64
     for (int r = 0; r < K; ++r) {
         u64 best = ~0ull;
         for (int m = lane; m < M; m += 64) {
@@ -447,10 +443,38 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const u64 *__restrict__ 
         }
         prev1 = best + 1;
         if (lane == r) mine = best;
+        if (PICKS > 1 && lane + 64 == r) mine1 = best;
     }
     if (lane < K) {
         idx_out[(size_t)q * K + lane] = (int)(unsigned)(mine & 0xffffffffull);
         dist_out[(size_t)q * K + lane] = __uint_as_float((unsigned)(mine >> 32));
     }
+    if (PICKS > 1 && lane + 64 < K) {
+        idx_out[(size_t)q * K + lane + 64] = (int)(unsigned)(mine1 & 0xffffffffull);
+        dist_out[(size_t)q * K + lane + 64] = __uint_as_float((unsigned)(mine1 >> 32));
+    }
 }
 
+__global__ __launch_bounds__(256) void knn_merge_kernel(const u64 *__restrict__ partial, int nseg,
+                                                        int nq, int nq_pad, int K,
+                                                        int *__restrict__ idx_out,
+                                                        float *__restrict__ dist_out) {
+    __shared__ u64 stage[4][MERGE_CAP];
+    const int wave = threadIdx.x >> 6;
+    const int q = blockIdx.x * 4 + wave;
+    if (q >= nq) return;
+    knn_merge_query<1, MERGE_CAP>(partial, nseg, q, nq_pad, K, stage[wave], idx_out, dist_out);
+}
+
+// K4w  merge for 64 < K <= FDR_EXACT_MAX_K: two picks per lane (lane l keeps picks l and l + 64); the planner keeps
+// nseg * K <= FDR_MERGE_WIDE_CAP (knn_plan_compute), so every query's keys are staged in LDS.
+__global__ __launch_bounds__(256) void knn_merge_wide_kernel(const u64 *__restrict__ partial, int nseg,
+                                                             int nq, int nq_pad, int K,
+                                                             int *__restrict__ idx_out,
+                                                             float *__restrict__ dist_out) {
+    __shared__ u64 stage[4][FDR_MERGE_WIDE_CAP];
+    const int wave = threadIdx.x >> 6;
+    const int q = blockIdx.x * 4 + wave;
+    if (q >= nq) return;
+    knn_merge_query<2, FDR_MERGE_WIDE_CAP>(partial, nseg, q, nq_pad, K, stage[wave], idx_out, dist_out);
+}

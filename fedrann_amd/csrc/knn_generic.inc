@@ -1,6 +1,7 @@
 // Part of libfedrann_hip.so: included by fedrann_hip.hip (one translation unit), not compiled on its own.
 // ------------------------------------------------------------------------------------------
-// Exact cosine k-NN for sizes outside the MFMA kernels' shapes: d > 512 or k > 64.
+// Exact cosine k-NN for sizes outside the MFMA kernels' shapes: d > 1024, or k > 64 / d > 512 below 8192 targets
+// (knn_route).
 //
 // The reference accepts any -n / --nndescent-n-neighbors (fedrann/__main__.py:128-146); its defaults (500, 50)
 // and BASELINE.json's configurations run on the MFMA kernels (knn_exact.inc, knn_prefilter.inc).  This kernel

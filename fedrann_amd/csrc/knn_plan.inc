@@ -3,9 +3,15 @@
 // targets into segments.  Plain C++, no HIP.
 #define QCAP 4  // default entries per lane append queue (the kernels take the actual value, 2 or 4)
 #define FDR_MAX_SEG 96
-// what the MFMA kernels cover (FDR_MAX_K / FDR_MAX_DIM of the header are the generic kernel's limits, knn_generic.inc)
+// what the MFMA kernels cover (FDR_MAX_K / FDR_MAX_DIM of the header are the generic kernel's limits, knn_generic.inc):
+// every pass (fp16 prefilter, exact, duplicate-row classes) up to FDR_FAST_MAX_K / _DIM; the exact pass alone up to
+// FDR_EXACT_MAX_K neighbours from FDR_WIDE_MIN_TARGETS targets (knn_route)
 #define FDR_FAST_MAX_K 64
 #define FDR_FAST_MAX_DIM 512
+#define FDR_EXACT_MAX_K 128
+#define FDR_EXACT_MAX_DIM 1024   // (d > 512: the split-K tile kernel, knn_exact_wide.inc)
+#define FDR_MERGE_WIDE_CAP 1024  // keys per query the k > 64 merge stages in LDS (knn_merge_wide_kernel)
+#define FDR_WIDE_MIN_TARGETS 8192  // (AUTO's prefilter threshold; a function of nt alone: every rank decides alike)
 
 // Target segment boundaries (in rows, multiples of 32 except the last): segment s = [b[s], b[s+1]).
 struct SegBounds {
@@ -18,7 +24,7 @@ static int padded_dim(int d) {  // row length (floats) of the normalised-embeddi
     if (d <= 128) return 128;
     if (d <= 256) return 256;
     if (d <= 512) return 512;
-    if (d <= 1024) return 1024;  // (beyond the MFMA kernels' shapes: the generic kernel, knn_generic.inc)
+    if (d <= 1024) return 1024;  // (the split-K tile kernel, knn_exact_wide.inc; below 8192 targets the generic kernel)
     if (d <= FDR_MAX_DIM) return 2048;
     return FDR_E_ARG;
 }
@@ -61,6 +67,7 @@ enum KnnFamily {
     FDR_FAM_PINGPONG,   // knn_prefilter_pp_kernel<DP, U, LH> (knn_prefilter_pp.inc): eight waves, 256 registers
     FDR_FAM_RANGE,      // knn_range_kernel<DP, NW, WPS> (knn_prefilter.inc): the range pass over plateau queries
     FDR_FAM_RANGE_PP,   // knn_range_pp_kernel<DP, U> (knn_prefilter_pp.inc): the range pass, ping-pong skeleton
+    FDR_FAM_TILE_SPLIT, // knn_tile_split_kernel<DP> (knn_exact_wide.inc): the exact fp32 pass, K split over two waves
 };
 struct KnnShape {
     int family, dp, nq, nw, wps;
@@ -68,7 +75,9 @@ struct KnnShape {
     bool paired;   // candidate pass, 16-key lists: the stage's two tiles as two interleaved MFMA chains (d <= 128: 1-4 %)
     int lists;     // candidate pass: the list widths (16 / 32 keys a lane, K' <= 32 / > 32) it is compiled for, or'ed
     bool release;  // chosen with the default knobs: compiled into the release library (a development build: every entry)
+    int split = 1; // waves that share one 32-query set, each holding a part of its components (FDR_FAM_TILE_SPLIT: 2)
     constexpr int units() const { return tps / 2; }  // the stage's units U
+    constexpr int qw() const { return 32 * nq * nw / split; }  // queries per workgroup
 };
 enum KnnShapeId {
     FDR_X128, FDR_X128_W8, FDR_X128_Q2, FDR_X256, FDR_X512,
@@ -76,6 +85,7 @@ enum KnnShapeId {
     FDR_P512, FDR_P512_U4, FDR_P512_W8U4,
     FDR_PP256, FDR_PP512_U8, FDR_PP512_U4,
     FDR_R128, FDR_R128_W8, FDR_R256, FDR_R512, FDR_RPP128, FDR_RPP256, FDR_RPP512,
+    FDR_X256_W4, FDR_X1024,
     FDR_NUM_SHAPES
 };
 static constexpr KnnShape kShapes[] = {
@@ -125,6 +135,13 @@ static constexpr KnnShape kShapes[] = {
     {FDR_FAM_RANGE_PP, 128, 1, 8, 2, 16, false, 0, true},  // RPP128
     {FDR_FAM_RANGE_PP, 256, 1, 8, 2, 16, false, 0, true},  // RPP256
     {FDR_FAM_RANGE_PP, 512, 1, 8, 2, 16, false, 0, true},  // RPP512
+    // the exact tile kernel for 64 < k <= 128 (knn_choose_shape): lists of k x 128 queries x 8 bytes (up to 128 KiB)
+    // leave room for one workgroup per CU, so 128 queries per workgroup, one wave per SIMD; d <= 128 and d <= 512
+    // take X128 and X512, d <= 256 this one (X256's 256 queries would not fit above k = 70)
+    {FDR_FAM_TILE, 256, 1, 4, 2, 0, false, 0, true},  // X256_W4: 128 queries/WG, <=256 VGPRs
+    // d <= 1024 (k <= 128): a wave holds 512 of a query's components (256 registers, X512's budget), so two waves -- one
+    // per SIMD -- share a 32-query set: 64 queries/WG, one WG/CU
+    {FDR_FAM_TILE_SPLIT, 1024, 1, 4, 1, 0, false, 0, true, 2},  // X1024
 };
 static_assert(sizeof(kShapes) / sizeof(kShapes[0]) == FDR_NUM_SHAPES, "one kShapes entry per KnnShapeId");
 
@@ -182,10 +199,11 @@ static int range_shape(int dp, int chunk = 0, int plateau = 0) {  // (dp alone: 
 }
 
 static size_t knn_lds_bytes_q(const KnnShape &sh, int k, int qcap) {
-    const size_t qw = (size_t)32 * sh.nq * sh.nw, nt = (size_t)64 * sh.nw;
+    const size_t qw = (size_t)sh.qw(), nt = (size_t)64 * sh.nw;
     if (sh.tps > 0) return (size_t)sh.tps * 32 * 256;  // fp16 prefilter: the ring only (lists in registers)
-    const size_t ring = (size_t)2 * 32 * 64 * 4;
-    return ring + (size_t)k * qw * 8 + (size_t)qcap * sh.nq * nt * 8;
+    // split K: a ring stage holds one 64-component chunk per part, and each pair hands 32 x 32 partial sums over
+    const size_t ring = (size_t)2 * 32 * 64 * 4 * sh.split, handoff = sh.split > 1 ? (size_t)(sh.nw / sh.split) * 4096 : 0;
+    return ring + handoff + (size_t)k * qw * 8 + (size_t)qcap * sh.nq * nt * 8;
 }
 
 // Entries per lane append queue: 4, or 2 when that lets one more workgroup share the CU's LDS
@@ -210,12 +228,28 @@ static int knn_choose_shape(int dp, int k) {
     if (forced >= 0 && forced < FDR_NUM_SHAPES && kShapes[forced].family == FDR_FAM_TILE && kShapes[forced].dp == dp &&
         knn_wg_per_cu(kShapes[forced], k) > 0)
         return forced;
+    if (dp == 1024) return FDR_X1024;
+    if (k > FDR_FAST_MAX_K) return dp == 128 ? FDR_X128 : dp == 256 ? FDR_X256_W4 : FDR_X512;  // (128 queries/WG)
     if (dp == 256) return FDR_X256;
     if (dp == 512) return FDR_X512;
     // d <= 128: the 4-wave / 128-query shape (no spills at 168 VGPRs, finest work granularity) while
     // at least two workgroups fit in LDS; for larger k the 2-chain 256-VGPR shape
     if (knn_wg_per_cu(kShapes[FDR_X128], k) >= 2) return FDR_X128;
     return FDR_X128_Q2;
+}
+
+// Which kernels a k-NN call of padded dimension dp, k neighbours and nt targets runs on.  Every entry point (the
+// workspace size, the class layer, the search) takes its decision from here.
+enum KnnRoute {
+    FDR_ROUTE_FAST,     // k <= 64, d <= 512: exact or fp16-prefilter MFMA passes, duplicate-row classes
+    FDR_ROUTE_WIDE,     // 64 < k <= 128 at d <= 512, or k <= 128 at 512 < d <= 1024, nt >= 8192: the exact MFMA pass
+                        // alone (no prefilter, no classes)
+    FDR_ROUTE_GENERIC,  // the rest: knn_generic_kernel (knn_generic.inc)
+};
+static int knn_route(int dp, int k, int64_t nt) {
+    if (dp <= FDR_FAST_MAX_DIM && k <= FDR_FAST_MAX_K) return FDR_ROUTE_FAST;
+    if (dp <= FDR_EXACT_MAX_DIM && k <= FDR_EXACT_MAX_K && nt >= FDR_WIDE_MIN_TARGETS) return FDR_ROUTE_WIDE;
+    return FDR_ROUTE_GENERIC;
 }
 
 struct KnnPlan {
@@ -321,7 +355,7 @@ static KnnPlan knn_plan_compute(int num_cus, int64_t nq, int64_t nt, int d, int 
     KnnPlan p;
     p.shape = shape >= 0 ? shape : knn_choose_shape(padded_dim(d), k);
     const KnnShape &sh = kShapes[p.shape];
-    p.qw = 32 * sh.nq * sh.nw;
+    p.qw = sh.qw();
     p.nqb = (int)((nq + p.qw - 1) / p.qw);
     p.nq_pad = p.nqb * p.qw;
     // Work split.  The grid is nqb query blocks x nseg target segments; workgroups are dispatched
@@ -369,6 +403,8 @@ static KnnPlan knn_plan_compute(int num_cus, int64_t nq, int64_t nt, int d, int 
                     left -= t;
                 }
                 if ((int)segs.size() > FDR_MAX_SEG) continue;
+                // (k > 64: the merge stages every query's nseg * k keys in LDS)
+                if (k > FDR_FAST_MAX_K && (int)segs.size() * k > FDR_MERGE_WIDE_CAP) continue;
                 // (k > 1: the candidate pass, whose partial lists the workspace bound covers; the range pass, k = 1,
                 // keeps no lists and wants many short segments when only a few query blocks are left)
                 if (sh.tps > 0 && k > 1 && (int)segs.size() > (T + cap_tiles - 1) / cap_tiles + FDR_PLAN_EXTRA_SEG) continue;

@@ -43,9 +43,11 @@ extern "C" {
 #define FDR_E_STATE (-5)   /* call order (e.g. embed before a projection was loaded) */
 #define FDR_E_IO (-6)      /* a file could not be opened / mapped */
 
-#define FDR_MAX_K 128      /* neighbours per row (self included); up to 64 on the MFMA kernels, beyond on a generic one */
-#define FDR_MAX_DIM 2048   /* embedding dimension; up to 512 (reference default: 500) on the MFMA kernels, beyond on a
-                              generic vector-ALU kernel (same results, far slower: DESIGN.md) */
+#define FDR_MAX_K 128      /* neighbours per row (self included); up to 64 on every MFMA pass, 65..128 on the exact MFMA
+                              pass from 8192 targets (d <= 1024), else on a generic kernel */
+#define FDR_MAX_DIM 2048   /* embedding dimension; up to 512 (reference default: 500) on every MFMA pass, up to 1024 on
+                              the exact MFMA pass from 8192 targets, beyond on a generic vector-ALU kernel (same results,
+                              far slower: DESIGN.md) */
 
 typedef struct fdr_ctx fdr_ctx;
 
@@ -98,8 +100,9 @@ int fdr_embed(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indptr, const int32
  * ascending by (distance, index); self is a candidate like any other row.  Canonical arithmetic
  * (DESIGN.md section 4): rows are scaled by (float)(1/sqrt((double)chain(x,x))), the
  * similarity is the fp32 fma chain over components 0..d-1, dist = clamp(1 - c, 0, 1), two
- * all-zero rows are at distance 0.  Requires n >= k, 1 <= k <= FDR_MAX_K, d <= FDR_MAX_DIM (k > 64 or d > 512: the
- * generic kernel, every pair on the vector ALU). */
+ * all-zero rows are at distance 0.  Requires n >= k, 1 <= k <= FDR_MAX_K, d <= FDR_MAX_DIM (from 8192 targets,
+ * 64 < k <= 128 at d <= 512 and any k at 512 < d <= 1024: the exact MFMA pass alone, no prefilter, no duplicate-row
+ * classes; d > 1024, or beyond k <= 64, d <= 512 below 8192 targets: the generic kernel, every pair on the vector ALU). */
 int fdr_knn(fdr_ctx *ctx, const float *E, int64_t n, int32_t d, int32_t k, int32_t *idx_out,
             float *dist_out);
 
@@ -203,7 +206,7 @@ int fdr_last_prefilter_launches(fdr_ctx *ctx, int *launches, int *queues);
 #define FDR_TRACE_NONE 0       /* no k-NN search ran (a cleared trace, or a call that failed or found nothing to do) */
 #define FDR_TRACE_EXACT 1      /* exact mode: the fp32 kernel for every query */
 #define FDR_TRACE_PREFILTER 2  /* fp16 candidate pass + certificate (+ range pass, + exact fallback) */
-#define FDR_TRACE_GENERIC 3    /* d > 512 or k > 64: the generic kernel */
+#define FDR_TRACE_GENERIC 3    /* d > 1024, or k > 64 / d > 512 below 8192 targets: the generic kernel */
 #define FDR_FALLBACK_NONE 0
 #define FDR_FALLBACK_CHUNKED 1 /* the uncertified queries gathered and searched by the exact kernel, in chunks */
 #define FDR_FALLBACK_WHOLE 2   /* more than half the non-zero queries uncertified: the exact kernel for every query */
@@ -249,7 +252,7 @@ int fdr_last_uncertified(fdr_ctx *ctx);
 #define FDR_PATH_EXACT 3           /* the exact fp32 kernel (exact mode; uncertifiable queries of the prefilter mode) */
 #define FDR_PATH_ZERO 4            /* all-zero query row: closed-form answer */
 #define FDR_PATH_RANGE_OVERFLOW 5  /* the range pass collected more than its capacity: the exact kernel */
-#define FDR_PATH_GENERIC 6         /* d > 512 or k > 64: the generic kernel */
+#define FDR_PATH_GENERIC 6         /* d > 1024, or k > 64 / d > 512 below 8192 targets: the generic kernel */
 #define FDR_PATH_CLASS_MEMBER 0x80
 int fdr_last_query_paths(fdr_ctx *ctx, uint8_t *paths, int64_t n_queries);
 
