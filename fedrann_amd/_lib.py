@@ -43,7 +43,7 @@ class KnnTrace(ctypes.Structure):
             "pass_waves", "pass_wps", "pass_units", "pass_list_keys", "pass_pingpong", "pass_launches", "pass_queues",
             "pass_segments", "uncertified", "zero_queries", "range_queries", "range_chunks", "range_pp_chunks",
             "range_w8_chunks", "range_overflow", "exact_fallback", "exact_calls", "exact_queries", "exact_waves",
-            "exact_qsets", "generic")]
+            "exact_qsets", "generic", "exact_segments")]
 
 
 class FedrannHipError(RuntimeError):

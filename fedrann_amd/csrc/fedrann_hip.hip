@@ -1041,6 +1041,7 @@ static int launch_knn_exact(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_
     ctx->trace.exact_queries += (int32_t)nq;
     ctx->trace.exact_waves = sh.nw;
     ctx->trace.exact_qsets = sh.nq;
+    ctx->trace.exact_segments = p.nseg;
     const int dbg = dev_knobs().debug;  // (development builds only; 0 in the release library)
     (void)dbg;
     const int qcap = knn_qcap(sh, k);

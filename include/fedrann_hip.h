@@ -234,6 +234,7 @@ typedef struct fdr_knn_trace {
     int32_t exact_queries;     /* queries they searched */
     int32_t exact_waves, exact_qsets;  /* shape of the last one: waves per workgroup, query sets per wave (0: none) */
     int32_t generic;           /* 1: the generic kernel ran */
+    int32_t exact_segments;    /* target segments of the last exact-kernel search (0: none) */
 } fdr_knn_trace;
 int fdr_last_knn_trace(fdr_ctx *ctx, fdr_knn_trace *out);
 /* Prefilter mode only: number of query rows of the most recent k-NN call whose candidate set could

@@ -19,6 +19,11 @@ What is produced (data only: inputs + expected outputs, no reference source):
   precompute_big.json      sha256 of P (CSR by feature) for L=1_000_000, d=256
   embed_tiny.npz           E for 5 hand-written reads through get_feature_matrix
   embed_mid.npz            E for 1500 synthetic reads (3000 rows), d=128
+  embed_wide.npz           inputs + sha256 of E for 300 synthetic reads (600 rows) at
+                           d=1000 and d=2048 (E itself, 7 MB of incompressible floats,
+                           is not stored; the projection is recomputed from its counts)
+
+Only the wide embeddings:  /opt/conda/bin/python3.9 -B tests/golden/make_golden.py embed_wide
   metadata_tiny.json       get_metadata() names / strands for the tiny reads
   overlaps_edge.{npz,tsv}  get_output_dataframe + to_csv on hand-written edge cases
   overlaps_rand.{npz,tsv}  the same on a random 400-row x 12 neighbour table
@@ -140,7 +145,39 @@ def p_to_csr_arrays(P):
             c.data.view(np.uint32).copy())
 
 
-def main():
+def make_embed_wide(pre, fe, tmp):
+    """get_feature_matrix at d = 1000 and 2048 (the k-NN kernels' DP = 1024 and 2048): 300 reads over a library of
+    L = 4000 k-mers, read lengths 1 .. 6000 ids (rows longer than the 256 ids the embed kernel keeps in flight) and
+    a few at the edges of its 64-id chunks."""
+    import numpy as np
+    rng = np.random.default_rng(2048)
+    L = 4000
+    counts = rng.integers(2, 61, size=L).astype(np.int64)
+    lens = [1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 6000]
+    lens += [int(x) for x in rng.integers(1, 700, size=300 - len(lens))]
+    reads = [rng.choice(2 * L, size=n, replace=False).astype(np.int64) for n in lens]
+    names = ["wide_%d/%d" % (i, n) for i, n in enumerate(lens)]
+    ob = os.path.join(tmp, "wide.bin")
+    write_output_bin(ob, names, reads)
+    out = {"L": L, "counts": counts, "read_lens": np.array(lens, np.int64), "read_idx": np.concatenate(reads)}
+    for d in (1000, 2048):
+        fa = os.path.join(tmp, "lib_wide_%d.fasta" % d)
+        write_counts_fasta(fa, counts)
+        P, F = pre.get_precompute_matrix(n_components=d, counter_file=fa, n_features=2 * L)
+        ip, ix, bits = p_to_csr_arrays(P)
+        h = hashlib.sha256()
+        for a in (ip, ix, bits):
+            h.update(np.ascontiguousarray(a).tobytes())
+        out["P_sha256_%d" % d] = np.array(h.hexdigest())
+        E = fe.get_feature_matrix(ks_file=ob, precompute_matrix=P, kmer_count=2 * L,
+                                  read_count=len(reads), chunk_size=128)
+        assert E.dtype == np.float32 and E.shape == (2 * len(reads), d)
+        out["E_sha256_%d" % d] = np.array(hashlib.sha256(np.ascontiguousarray(E).view(np.uint32).tobytes()).hexdigest())
+        out["E_head_bits_%d" % d] = E[:8].view(np.uint32).copy()  # (a readable diff when the digest differs)
+    np.savez_compressed(os.path.join(HERE, "embed_wide.npz"), **out)
+
+
+def main(only=None):
     import numpy as np
     import scipy
     import pandas as pd
@@ -152,6 +189,10 @@ def main():
     print("versions", versions)
     assert np.__version__.startswith("1.26"), "run under the pinned numpy 1.26.x"
     tmp = tempfile.mkdtemp(prefix="golden_")
+    if only == "embed_wide":
+        make_embed_wide(pre, fe, tmp)
+        print("embed_wide.npz written to", HERE)
+        return
 
     # ---- precompute -------------------------------------------------------
     def run_pre(counts, d):
@@ -258,10 +299,12 @@ def main():
         names += ["read/%d_x" % i] * 2
     run_tsv("overlaps_rand", idx, dist, names, [0, 1] * (n // 2))
 
+    make_embed_wide(pre, fe, tmp)
+
     with open(os.path.join(HERE, "VERSIONS.json"), "w") as f:
         json.dump(versions, f, indent=1)
     print("golden vectors written to", HERE)
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1] if len(sys.argv) > 1 else None)

@@ -154,3 +154,38 @@ def test_nndescent_restatement_approximates_the_exact_search(oracle):
         assert np.all((idx[nz] == np.arange(6000)[nz, None]).any(1) | (dist[nz, -1] == 0))  # self, unless k exact duplicates precede it
         recall = float((dist <= wd[:, k - 1:k]).mean())
         assert recall >= floor, (trees, leaf, recall)
+
+
+def wide_golden_case(oracle, d):
+    """Inputs of tests/golden/embed_wide.npz at dimension d (1000 or 2048) as (indptr, indices, P, F), the projection
+    recomputed from the stored counts and checked against the reference's digest."""
+    g = np.load(golden("embed_wide.npz"))
+    L = int(g["L"])
+    P = oracle.precompute_matrix(g["counts"], d)
+    h = hashlib.sha256()
+    for a in (P[0], P[1], P[2].view(np.uint32)):
+        h.update(np.ascontiguousarray(a).tobytes())
+    assert h.hexdigest() == str(g["P_sha256_%d" % d])
+    rows, o = [], 0
+    for n in g["read_lens"]:
+        r = g["read_idx"][o:o + n]
+        o += n
+        rows.append(np.sort(r))
+        rows.append(np.sort(np.where(r < L, r + L, r - L)))
+    indptr, indices = oracle.rows_to_csr(rows)
+    return indptr, indices, P, 2 * L
+
+
+def assert_wide_golden(E, d):
+    g = np.load(golden("embed_wide.npz"))
+    bits = np.ascontiguousarray(E).view(np.uint32)
+    assert np.array_equal(bits[:8], g["E_head_bits_%d" % d])
+    assert hashlib.sha256(bits.tobytes()).hexdigest() == str(g["E_sha256_%d" % d])
+
+
+@pytest.mark.parametrize("d", [1000, 2048])
+def test_embed_wide_matches_reference(oracle, d):
+    """get_feature_matrix at d = 1000 and 2048 (DP = 1024 and 2048): reads up to 6000 ids, the oracle's E bit for bit."""
+    indptr, indices, P, F = wide_golden_case(oracle, d)
+    assert np.diff(indptr).max() > 256
+    assert_wide_golden(oracle.embed(indptr, indices, P, F, d), d)
