@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- read-pairs/s of the FEDRANN hot path (embed -> normalise -> all-pairs cosine k-NN).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--dim D] [--knn k] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--dim D] [--knn k] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what `value` needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints
+its line (with the per-kernel times and the roofline of those same steps).  `--full` adds the figures that take runs
+of their own: the other k-NN mode's pass (`other_mode`), the host-to-host passes, `cpu_baseline` and `recall`, and
+`roofline.traffic` from the stored profiles.
 
 A step = one pass of the hot path over the whole synthetic read set: every rank embeds and
 normalises its row block, the normalised embeddings are all-gathered (N > 1), and every rank
@@ -18,9 +23,9 @@ fdr_embed_knn, i.e. with the PCIe copies inside the timed region -- once with th
 delivers it and once with the dead features dropped on the host first (fdr_csr_compact; not timed,
 it belongs to the loader).
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel of the timed mode (the fp16 MFMA
-prefilter pass by default, the fp32 MFMA tile kernel in exact mode), priced on the unique rows it
-actually searched; `cpu_baseline` times this repo's CPU oracle (a port of the path, not the reference's
+Rank 0 prints ONE JSON line (`full` says which kind of run made it).  `roofline` is for the dominant
+kernel of the timed mode (the fp16 MFMA prefilter pass by default, the fp32 MFMA tile kernel in exact
+mode), priced on the unique rows it actually searched; `cpu_baseline` times this repo's CPU oracle (a port of the path, not the reference's
 pynndescent, which is not installed) on a bounded sample of the same workload; `recall` compares the
 timed run's rows with the oracle's (tie-aware recall@k) and, when it imports, with pynndescent called
 as the reference calls it.
@@ -50,20 +55,24 @@ def parse_args():
     p.add_argument("--dim", type=int, default=128)
     p.add_argument("--knn", type=int, default=20)
     p.add_argument("--seed", type=int, default=602)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: the pass in the other k-NN mode, the "
+                        "host-to-host passes, the CPU baselines and recall, and the HBM traffic from the stored profiles; "
+                        "without it a run sets up, warms up, times its steps, dumps (--dump-outputs) and prints its line")
     p.add_argument("--cpu-baseline-seconds", type=float, default=15.0,
-                   help="target CPU time of the cpu_baseline sample (0 = skip)")
+                   help="target CPU time of the cpu_baseline sample (0 = skip; with --full)")
     p.add_argument("--doubling", action="store_true", help="fwd/rev row doubling (2 rows per read)")
     p.add_argument("--mode", choices=["auto", "exact", "prefilter"], default="auto",
                    help="k-NN mode of the timed run (same results in every mode); auto = the library's "
                         "default: fp16 prefilter + certificate + exact re-rank when it applies")
     p.add_argument("--no-compare", action="store_true",
-                   help="skip the extra (separately timed) pass in the other k-NN mode")
+                   help="with --full: skip the extra (separately timed) pass in the other k-NN mode")
     p.add_argument("--compare-steps", type=int, default=2, help="steps of the other-mode pass")
-    p.add_argument("--no-host-span", action="store_true", help="skip the host-to-host (PCIe-inclusive) passes")
+    p.add_argument("--no-host-span", action="store_true", help="with --full: skip the host-to-host (PCIe-inclusive) passes")
     p.add_argument("--nndescent-full", action="store_true",
-                   help="also run the restated reference algorithm (oracle/nndescent.c: RP forest + NN-descent with the "
-                        "reference's arguments) on ALL rows of the workload -- minutes of host time, outside every timed region; "
-                        "its recall is scored against the GPU run's (exact) result")
+                   help="with --full: also run the restated reference algorithm (oracle/nndescent.c: RP forest + NN-descent "
+                        "with the reference's arguments) on ALL rows of the workload -- minutes of host time, outside every "
+                        "timed region; its recall is scored against the GPU run's (exact) result")
     p.add_argument("--host-steps", type=int, default=0,
                    help="steps of the host-to-host pass over the full CSR (0 = --steps, like the device-resident run); the "
                         "compacted-CSR variant runs min(3, that)")
@@ -73,6 +82,8 @@ def parse_args():
     args = p.parse_args()
     if args.steps < 1 or args.warmup < 0:
         p.error("--steps must be >= 1 and --warmup >= 0")
+    if args.nndescent_full and not args.full:
+        p.error("--nndescent-full is part of the CPU baseline: it needs --full")
     return args
 
 
@@ -307,7 +318,10 @@ def main():
     # python -m fedrann_amd -- is the CSR without the ids P has no entry for: >= 90 % of them, density 1 / sqrt(F); same
     # E bit for bit, tests); the full CSR is kept too while it is small enough to be the host-to-host pass's and the CPU
     # baseline's input (10 M reads: 6.8 GB of ids per copy -- the pieces are dropped and those two legs are skipped).
-    keep_full = (r_hi - g_lo) <= 2_000_000
+    # Those two legs run with --full only.
+    host_span_on = args.full and world == 1 and not args.no_host_span
+    cpu_base_on = args.full and world == 1 and args.cpu_baseline_seconds > 0
+    keep_full = (host_span_on or cpu_base_on) and (r_hi - g_lo) <= 2_000_000
     piece = 1_000_000
     gen_threads = cpu_budget()  # (a 100 k-read chunk of the generator holds ~2 GB of temporaries: as many at once as fit)
     try:
@@ -406,7 +420,7 @@ def main():
 
     # the same workload in the other mode, separately timed (never part of `value`)
     other = None
-    if not args.no_compare and (used_prefilter or args.mode != "exact"):
+    if args.full and not args.no_compare and (used_prefilter or args.mode != "exact"):
         other_mode = "exact" if used_prefilter else "prefilter"
         ctx.set_knn_mode(other_mode)
         o_steps = max(1, min(args.steps, args.compare_steps))
@@ -423,9 +437,9 @@ def main():
     # fused host-pointer call (H2D, embed, normalise, k-NN, D2H).  Never `value` (the contract times the
     # device-resident path); same results, checked.
     host_span = None
-    if world == 1 and not args.no_host_span and not keep_full:
+    if host_span_on and not keep_full:
         host_span = {"skipped": "the full CSR of %d reads is not held on the host (see keep_full)" % R}
-    elif world == 1 and not args.no_host_span:
+    elif host_span_on:
         h_idx = np.empty((n, k), dtype=np.int32)
         h_dst = np.empty((n, k), dtype=np.float32)
         hsteps = args.host_steps if args.host_steps > 0 else args.steps
@@ -493,33 +507,34 @@ def main():
         nnz_loc = int(ix.size)
         embed_bytes = 4.0 * nnz_loc + 8.0 * nloc + 4.0 * nloc * d
         # HBM bytes per launch from the committed rocprofv3 --pmc passes (FETCH_SIZE doubled as the
-        # gfx950 guide prescribes + WRITE_SIZE); only valid for the workload the profile was collected on
+        # gfx950 guide prescribes + WRITE_SIZE); only valid for the workload the profile was collected on (--full)
         traffic, traffic_src = None, None
-        try:
-            import glob
-            import re
-            summaries = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_summary.json")),
-                               key=lambda f: int(re.search(r"r(\d+)", os.path.basename(f)).group(1)), reverse=True)
-            for path in summaries:  # the newest round's profile of THIS workload
-                with open(path) as f:
-                    prof = json.load(f)
-                if prof.get("bench_args") == {"reads": R, "dim": d, "knn": k, "gpus": world, "doubling": args.doubling}:
-                    pmc = prof["pmc_per_launch_avg"]
-                    kname = ("knn_prefilter_pp_kernel" if "knn_prefilter_pp_kernel" in pmc else "knn_prefilter_kernel") \
-                        if used_prefilter else "knn_tile_kernel"
-                    traffic = pmc[kname]["hbm_bytes_per_launch"]
-                    traffic_src = ("profiles/%s (rocprofv3 --pmc FETCH_SIZE x2 (gfx950 correction) + WRITE_SIZE, bytes "
-                                   "per launch, same workload)" % os.path.basename(path))
-                    break
-        except Exception:
-            traffic = None
+        if args.full:
+            try:
+                import glob
+                import re
+                summaries = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_summary.json")),
+                                   key=lambda f: int(re.search(r"r(\d+)", os.path.basename(f)).group(1)), reverse=True)
+                for path in summaries:  # the newest round's profile of THIS workload
+                    with open(path) as f:
+                        prof = json.load(f)
+                    if prof.get("bench_args") == {"reads": R, "dim": d, "knn": k, "gpus": world, "doubling": args.doubling}:
+                        pmc = prof["pmc_per_launch_avg"]
+                        kname = ("knn_prefilter_pp_kernel" if "knn_prefilter_pp_kernel" in pmc else "knn_prefilter_kernel") \
+                            if used_prefilter else "knn_tile_kernel"
+                        traffic = pmc[kname]["hbm_bytes_per_launch"]
+                        traffic_src = ("profiles/%s (rocprofv3 --pmc FETCH_SIZE x2 (gfx950 correction) + WRITE_SIZE, bytes "
+                                       "per launch, same workload)" % os.path.basename(path))
+                        break
+            except Exception:
+                traffic = None
         result = {
             "metric": "read-pairs/sec (overlap candidates)", "value": value, "unit": "read-pairs/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32 (canonical fp32 results; fp16 MFMA candidate prefilter + exact fp32 re-rank)"
                      if used_prefilter else "f32",
-            "data": "synthetic",
+            "data": "synthetic", "full": bool(args.full),
             "config": {"workload": "%d synthetic ONT reads (%d rows%s), %d-dim projection, k-NN=%d, "
                                    "row-sharded over %d GPU(s)" % (R, n, ", fwd/rev doubled" if args.doubling else "",
                                                                   d, k, world),
@@ -549,7 +564,7 @@ def main():
             other["roofline"] = mfma_roofline(other["kernels_ms"], other["kernel_launches"], other["mode"] == "prefilter",
                                               timed_mode=False)
             result["other_mode"] = other
-        if world == 1 and args.cpu_baseline_seconds > 0 and keep_full:
+        if cpu_base_on and keep_full:
             m = min(nloc, 1 << 17)
             base = cpu_baseline(s, P, d, k, args.cpu_baseline_seconds,
                                 gpu_result=(out[0][:m].cpu().numpy(), out[1][:m].cpu().numpy()))

@@ -8,6 +8,7 @@ extra="$@"   # extra bench.py arguments (e.g. --reads 1000000 --no-compare)
 out=$GRAFT_REPO_ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 B="python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 2 --cpu-baseline-seconds 0 $extra"
+B="$B --full"   # the trace run also times the other k-NN mode and the host-to-host passes (profiles/README.md)
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$tag -o trace -- $B > $out/prof_$tag.bench.json 2> $out/prof_$tag.err || exit 1
 # (the counter passes time nothing: no host-to-host passes, no other-mode pass -- every per-kernel figure of the summary
 # then belongs to the timed workload's own launches)
