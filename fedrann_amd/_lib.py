@@ -22,7 +22,8 @@ SYMBOLS = (
     "fdr_knn_expand_dev", "fdr_kmer_output_scan_range", "fdr_kmer_output_load_range",
     "fdr_kmer_count_begin", "fdr_kmer_count_add", "fdr_kmer_count_finish", "fdr_reads_scan", "fdr_reads_parse",
     "fdr_kmer_output_append", "fdr_last_query_paths", "fdr_last_knn_trace", "fdr_kmer_count_export_dev",
-    "fdr_kmer_count_merge_dev", "fdr_kmer_count_merge",
+    "fdr_kmer_count_merge_dev", "fdr_kmer_count_merge", "fdr_set_knn_capture", "fdr_last_candidates",
+    "fdr_last_range_sets",
 )
 FDR_MAX_K = 128
 KERNELS = ("embed_csr", "normalize_rows", "knn_tile", "knn_merge", "knn_prefilter", "knn_rerank",
@@ -33,6 +34,9 @@ PATH_CERTIFIED, PATH_RANGE, PATH_EXACT, PATH_ZERO, PATH_RANGE_OVERFLOW, PATH_GEN
 # fdr_last_knn_trace (include/fedrann_hip.h: FDR_TRACE_*, FDR_FALLBACK_*)
 TRACE_KINDS = ("none", "exact", "prefilter", "generic")
 FALLBACKS = ("none", "chunked", "whole")
+# fdr_set_knn_capture (include/fedrann_hip.h: FDR_CAPTURE_*, FDR_RANGE_CAP)
+CAPTURE_CANDIDATES, CAPTURE_RANGE = 1, 2
+RANGE_CAP = 1024
 
 
 class KnnTrace(ctypes.Structure):
@@ -107,6 +111,9 @@ def load_library():
     L.fdr_last_query_paths.argtypes = [vp, vp, i64]
     L.fdr_last_knn_trace.argtypes = [vp, ctypes.POINTER(KnnTrace)]
     L.fdr_set_knn_mode.argtypes = [vp, ctypes.c_int]
+    L.fdr_set_knn_capture.argtypes = [vp, ctypes.c_int]
+    L.fdr_last_candidates.argtypes = [vp, vp, i64, i32, ctypes.POINTER(i32)]
+    L.fdr_last_range_sets.argtypes = [vp, i64, vp, vp, vp, vp]
     L.fdr_set_dedup_mode.argtypes = [vp, ctypes.c_int]
     L.fdr_last_unique.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     L.fdr_last_prefilter_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
@@ -500,6 +507,29 @@ class Context:
         out["kind"] = TRACE_KINDS[out["kind"]]
         out["exact_fallback"] = FALLBACKS[out["exact_fallback"]]
         return out
+
+    def set_knn_capture(self, what):
+        """Or of CAPTURE_CANDIDATES / CAPTURE_RANGE (0: off): fdr_set_knn_capture.  Test support."""
+        self._check(self._L.fdr_set_knn_capture(self._h, int(what)), "fdr_set_knn_capture")
+
+    def last_candidates(self, n_queries, kp):
+        """(uint64 keys [n_queries, kp], qbits) of the last prefilter-mode call: fdr_last_candidates.  key = fp32 bits of
+        d~ << 32 | global target row; unused slots all ones."""
+        keys = np.empty((int(n_queries), int(kp)), dtype=np.uint64)
+        qbits = ctypes.c_int32(0)
+        self._check(self._L.fdr_last_candidates(self._h, _ptr(keys), int(n_queries), int(kp), ctypes.byref(qbits)),
+                    "fdr_last_candidates")
+        return keys, int(qbits.value)
+
+    def last_range_sets(self, n_range):
+        """(queries, theta, counts, rows [n_range, RANGE_CAP]) of the last call's range pass: fdr_last_range_sets.
+        Rows are global target rows, -1 past min(count, RANGE_CAP)."""
+        n = int(n_range)
+        q, th, cnt = np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.int32)
+        rows = np.empty((n, RANGE_CAP), np.int32)
+        self._check(self._L.fdr_last_range_sets(self._h, n, _ptr(q), _ptr(th), _ptr(cnt), _ptr(rows)),
+                    "fdr_last_range_sets")
+        return q, th, cnt, rows
 
     def timing(self, enable):
         self._check(self._L.fdr_timing(self._h, 1 if enable else 0), "fdr_timing")

@@ -486,6 +486,15 @@ struct fdr_ctx {
         hipStream_t stream = nullptr;
     } paths;
     fdr_knn_trace trace = {};  // fdr_last_knn_trace: the kernels the last k-NN call ran
+    // fdr_set_knn_capture / fdr_last_candidates / fdr_last_range_sets: the prefilter pass's intermediate results
+    struct {
+        int what = 0;                    // FDR_CAPTURE_* of fdr_set_knn_capture
+        bool cand_valid = false, range_valid = false;  // (cleared by every k-NN entry point)
+        int64_t nq = 0, n_range = 0;
+        int kp = 0, qbits = 0;
+        DevBuf cand, rq, rtheta, rcnt, rrows;  // ctx-owned copies: [nq, kp] keys; per range query id, theta, count, rows
+        hipStream_t stream = nullptr;
+    } cap;
     // duplicate-row classes built by fdr_knn_classes_dev for the calls that follow it (fdr_knn_unique_dev /
     // fdr_knn_expand_dev): the tables live in the caller's workspace
     struct {
@@ -570,7 +579,8 @@ FDR_EXPORT int fdr_destroy(fdr_ctx *ctx) {
                       &ctx->ks_seq, &ctx->ks_off, &ctx->ks_codes, &ctx->ks_keys, &ctx->ks_vals, &ctx->ks_bloom,
                       &ctx->ks_counter, &ctx->ks_pairs, &ctx->ks_pairs2, &ctx->ks_flag, &ctx->ks_pos,
                       &ctx->ks_idx, &ctx->ks_rows, &ctx->ks_indptr, &ctx->ks_tmp, &ctx->kc_counts,
-                      &ctx->kc_a0, &ctx->kc_a1, &ctx->kc_c0, &ctx->kc_c1, &ctx->kc_mk, &ctx->kc_mv, &ctx->kc_rc};
+                      &ctx->kc_a0, &ctx->kc_a1, &ctx->kc_c0, &ctx->kc_c1, &ctx->kc_mk, &ctx->kc_mv, &ctx->kc_rc,
+                      &ctx->cap.cand, &ctx->cap.rq, &ctx->cap.rtheta, &ctx->cap.rcnt, &ctx->cap.rrows};
     for (DevBuf *b : bufs) b->release();
     ctx->up_pool.stop();
     ctx->c_indptr.release();
@@ -638,9 +648,51 @@ FDR_EXPORT int fdr_last_knn_trace(fdr_ctx *ctx, fdr_knn_trace *out) {
     return FDR_OK;
 }
 
+FDR_EXPORT int fdr_set_knn_capture(fdr_ctx *ctx, int what) {
+    if (!ctx || what < 0 || what > (FDR_CAPTURE_CANDIDATES | FDR_CAPTURE_RANGE)) return fail(FDR_E_ARG, "bad capture flags");
+    ctx->cap.what = what;
+    return FDR_OK;
+}
+
+FDR_EXPORT int fdr_last_candidates(fdr_ctx *ctx, uint64_t *keys, int64_t n_queries, int32_t kp, int32_t *qbits_out) {
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    if (!keys || n_queries <= 0 || kp <= 0) return fail(FDR_E_ARG, "last_candidates: bad argument");
+    if (!ctx->cap.cand_valid) return fail(FDR_E_STATE, "last_candidates: the last k-NN call captured no candidates");
+    if (ctx->cap.nq != n_queries || ctx->cap.kp != kp)
+        return fail(FDR_E_STATE, "last_candidates: the last k-NN call captured %lld x %d keys, not %lld x %d",
+                    (long long)ctx->cap.nq, ctx->cap.kp, (long long)n_queries, kp);
+    HIP_TRY(hipMemcpyAsync(keys, ctx->cap.cand.p, (size_t)n_queries * kp * 8, hipMemcpyDeviceToHost, ctx->cap.stream));
+    HIP_TRY(hipStreamSynchronize(ctx->cap.stream));
+    if (qbits_out) *qbits_out = ctx->cap.qbits;
+    return FDR_OK;
+}
+
+FDR_EXPORT int fdr_last_range_sets(fdr_ctx *ctx, int64_t n_range, int32_t *queries, float *theta, int32_t *counts,
+                                   int32_t *rows) {
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    if (!queries || !theta || !counts || !rows || n_range <= 0) return fail(FDR_E_ARG, "last_range_sets: bad argument");
+    if (!ctx->cap.range_valid) return fail(FDR_E_STATE, "last_range_sets: the last k-NN call captured no range pass");
+    if (ctx->cap.n_range != n_range)
+        return fail(FDR_E_STATE, "last_range_sets: the last k-NN call captured %lld range queries, not %lld",
+                    (long long)ctx->cap.n_range, (long long)n_range);
+    const hipStream_t st = ctx->cap.stream;
+    HIP_TRY(hipMemcpyAsync(queries, ctx->cap.rq.p, (size_t)n_range * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(theta, ctx->cap.rtheta.p, (size_t)n_range * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(counts, ctx->cap.rcnt.p, (size_t)n_range * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(rows, ctx->cap.rrows.p, (size_t)n_range * RANGE_CAP * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int64_t i = 0; i < n_range; ++i)  // (the slots the pass did not fill hold whatever the workspace held)
+        for (int m = std::max(0, std::min(counts[i], RANGE_CAP)); m < RANGE_CAP; ++m) rows[i * RANGE_CAP + m] = -1;
+    return FDR_OK;
+}
+
 // Every k-NN entry point starts here, before its argument checks: no earlier call's trace or path codes survive it.
 static void knn_call_begin(fdr_ctx *ctx) {
     ctx->trace = fdr_knn_trace{};
+    ctx->cap.cand_valid = ctx->cap.range_valid = false;
+    ctx->cap.nq = ctx->cap.n_range = 0;
     ctx->paths.dev = nullptr;
     ctx->paths.n = 0;
     ctx->paths.all = FDR_PATH_NONE;
@@ -1215,6 +1267,15 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     hipLaunchKernelGGL(knn_merge_keys_kernel, dim3((unsigned)((nq + mq - 1) / mq)), dim3(256), 0, st,
                        (const u64 *)d_partial, p.nseg, (int)nq, p.nq_pad, kp, d_cand);
     HIP_TRY(hipGetLastError());
+    if (ctx->cap.what & FDR_CAPTURE_CANDIDATES) {  // (test support: fdr_last_candidates)
+        if ((trc = ctx->cap.cand.reserve((size_t)nq * kp * 8))) return trc;
+        HIP_TRY(hipMemcpyAsync(ctx->cap.cand.p, d_cand, (size_t)nq * kp * 8, hipMemcpyDeviceToDevice, st));
+        ctx->cap.nq = nq;
+        ctx->cap.kp = kp;
+        ctx->cap.qbits = std::min(20, 32 - ib);
+        ctx->cap.stream = st;
+        ctx->cap.cand_valid = true;
+    }
     HIP_TRY(hipMemsetAsync(d_counter, 0, 16, st));
     int *d_rlist = reinterpret_cast<int *>(ws + L.off_rlist);
     float *d_theta = reinterpret_cast<float *>(ws + L.off_theta);
@@ -1253,6 +1314,13 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
         float *d_thetac = reinterpret_cast<float *>(ws + L.off_thetac);
         int *d_cnt = reinterpret_cast<int *>(ws + L.off_cnt);
         int *d_rcand = reinterpret_cast<int *>(ws + L.off_rcand);
+        const bool rcap = ctx->cap.what & FDR_CAPTURE_RANGE;  // (test support: fdr_last_range_sets)
+        if (rcap) {
+            if ((trc = ctx->cap.rq.reserve((size_t)rcount * 4)) || (trc = ctx->cap.rtheta.reserve((size_t)rcount * 4)) ||
+                (trc = ctx->cap.rcnt.reserve((size_t)rcount * 4)) || (trc = ctx->cap.rrows.reserve((size_t)rcount * RANGE_CAP * 4)))
+                return trc;
+            ctx->cap.stream = st;
+        }
         for (int first = 0; first < rcount; first += L.rchunk) {
             const int c = std::min(L.rchunk, rcount - first);
             hipLaunchKernelGGL(gather_half_queries_kernel, dim3((unsigned)c), dim3(256), 0, st,
@@ -1273,10 +1341,23 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
             tr.range_chunks++;
             tr.range_pp_chunks += rsh.family == FDR_FAM_RANGE_PP;
             tr.range_w8_chunks += rs == FDR_R128_W8;
+            if (rcap) {
+                char *cq = static_cast<char *>(ctx->cap.rq.p), *cth = static_cast<char *>(ctx->cap.rtheta.p);
+                char *cc = static_cast<char *>(ctx->cap.rcnt.p), *cr = static_cast<char *>(ctx->cap.rrows.p);
+                HIP_TRY(hipMemcpyAsync(cq + (size_t)first * 4, d_rlist + first, (size_t)c * 4, hipMemcpyDeviceToDevice, st));
+                HIP_TRY(hipMemcpyAsync(cth + (size_t)first * 4, d_thetac, (size_t)c * 4, hipMemcpyDeviceToDevice, st));
+                HIP_TRY(hipMemcpyAsync(cc + (size_t)first * 4, d_cnt, (size_t)c * 4, hipMemcpyDeviceToDevice, st));
+                HIP_TRY(hipMemcpyAsync(cr + (size_t)first * RANGE_CAP * 4, d_rcand, (size_t)c * RANGE_CAP * 4,
+                                       hipMemcpyDeviceToDevice, st));
+            }
             hipLaunchKernelGGL(knn_rerank_long_kernel, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st,
                                (const int *)(d_rlist + first), c, (const int *)d_cnt, (const int *)d_rcand, k,
                                d_Qhat, d_That, dp, (int)t_base, d_idx, d_dist, d_counter, d_flagged, d_path);
             HIP_TRY(hipGetLastError());
+        }
+        if (rcap) {
+            ctx->cap.n_range = rcount;
+            ctx->cap.range_valid = true;
         }
         if ((trc = timing_end(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
         // ranges that overflowed were appended to the exact list: read its final length
@@ -1321,9 +1402,12 @@ static int launch_knn_mode(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_q
                            int k, int32_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes, hipStream_t st) {
     const int dp = fdr_padded_dim(d);
     if (dp > 0 && k >= 1 && knn_route(dp, k, nt) == FDR_ROUTE_FAST && nq > 0 && nt >= k && knn_prefilter_wanted(ctx, dp, nt, k) &&
-        d_Qhat && d_qzero && d_That && d_tzero && d_idx && d_dist && d_ws)
-        return launch_knn_prefilter(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx,
-                                    d_dist, d_ws, ws_bytes, st);
+        d_Qhat && d_qzero && d_That && d_tzero && d_idx && d_dist && d_ws) {
+        const int rc = launch_knn_prefilter(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx,
+                                            d_dist, d_ws, ws_bytes, st);
+        if (rc) ctx->cap.cand_valid = ctx->cap.range_valid = false;  // (a failed call leaves no capture)
+        return rc;
+    }
     ctx->last_flagged = 0;  // (exact mode certifies nothing)
     ctx->last_pass_launches = ctx->last_pass_queues = 0;
     ctx->paths.dev = nullptr;

@@ -29,6 +29,8 @@ static int padded_dim(int d) {  // row length (floats) of the normalised-embeddi
     return FDR_E_ARG;
 }
 
+// (bounds |fp16 pass distance - canonical distance| with the grid term of prefilter_eps(); the device's own candidate
+// lists are checked against it on adversarial rows in tests/test_gpu_candidates.py, test_candidates_on_adversarial_rows)
 #define FDR_PREFILTER_EPS 0.00105f
 #define FDR_PREFILTER_EXTRA 8
 

@@ -256,6 +256,30 @@ int fdr_last_uncertified(fdr_ctx *ctx);
 #define FDR_PATH_GENERIC 6         /* d > 1024, or k > 64 / d > 512 below 8192 targets: the generic kernel */
 #define FDR_PATH_CLASS_MEMBER 0x80
 int fdr_last_query_paths(fdr_ctx *ctx, uint8_t *paths, int64_t n_queries);
+/* Diagnostics (test support; nothing in the product reads it): a copy of the prefilter mode's intermediate results,
+ * so that the tests can check the fp16 candidate pass and the range pass against a plain model.  `what` or's the
+ * FDR_CAPTURE_* flags (default 0: nothing is captured, and the only cost is one host-side branch).  While a flag is
+ * set, every prefilter-mode search copies, in stream order, into buffers the context owns (the caller's workspace may
+ * be freed as soon as the call returns):
+ *   FDR_CAPTURE_CANDIDATES  the merged candidate lists, n_queries x K' keys (fdr_last_candidates);
+ *   FDR_CAPTURE_RANGE       per range-pass query: its query row, the bound theta, the count of targets the pass
+ *                           found with d~ <= theta and the first min(count, 1024) of them (fdr_last_range_sets).
+ * With the duplicate-row layer active the capture describes the inner search of the unique rows.  Every k-NN entry
+ * point clears the capture; asking after an exact-mode, generic, failed or non-capturing call is FDR_E_STATE. */
+#define FDR_CAPTURE_CANDIDATES 1
+#define FDR_CAPTURE_RANGE 2
+#define FDR_RANGE_CAP 1024  /* row slots per range query of fdr_last_range_sets */
+int fdr_set_knn_capture(fdr_ctx *ctx, int what);
+/* The candidate lists of the last call: keys [n_queries, kp] (n_queries and kp = K' as in fdr_last_knn_trace), one
+ * ascending list per query.  key = (fp32 bits of d~) << 32 | target row, with d~ = qd / QM1 the approximate
+ * distance on the pass's grid of QM1 = 2^qbits - 2 steps and the target row a GLOBAL index (t_base + local row);
+ * unused slots are all ones.  *qbits_out (may be null) receives qbits. */
+int fdr_last_candidates(fdr_ctx *ctx, uint64_t *keys, int64_t n_queries, int32_t kp, int32_t *qbits_out);
+/* The range-pass queries of the last call (n_range = range_queries of fdr_last_knn_trace), in the order the pass took
+ * them: queries [n_range] (local query rows), theta [n_range] (the pass admitted d~ <= theta, d~ = 1 - clamp(s~, 0, 1)
+ * in fp32), counts [n_range] (targets found: may exceed FDR_RANGE_CAP) and rows [n_range, FDR_RANGE_CAP]: the first
+ * min(count, FDR_RANGE_CAP) entries of a query's row are the GLOBAL target rows collected, in no order; the rest -1. */
+int fdr_last_range_sets(fdr_ctx *ctx, int64_t n_range, int32_t *queries, float *theta, int32_t *counts, int32_t *rows);
 
 /* ---- k-mer search on the GPU: reads x k-mer library -> per-read set of library indices -----------
  * Replaces the reference's native tool kmer_searcher (kmer_searcher/kmer_searcher.cpp:232-375; called
