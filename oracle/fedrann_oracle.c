@@ -246,9 +246,10 @@ ORC_API int orc_num_threads(void) {
 /* ------------------------------------------------------------------------------------------
  * kmer_searcher (the step upstream of the hot path).
  *
- * PARITY UNPINNED: kmer_searcher/kmer_searcher.cpp is the reference's only native file; it needs the
- * un-vendored robin_hood.h submodule (unbuildable here, see oracle/Makefile) and its own test data pin
- * an obsolete text format.  What follows restates its algorithm line by line, quirks included.
+ * PINNED: kmer_searcher/kmer_searcher.cpp is the reference's only native file.  oracle/Makefile compiles it
+ * unchanged into oracle/_ref/ against ref_shim/robin_hood.h (a stand-in for the un-vendored robin-hood
+ * hashing header), and tests/test_kmer_reference.py holds this restatement against it (1 thread, indices
+ * sorted per record).  What follows restates its algorithm line by line, quirks included.
  *
  *  - kmer_to_int (kmer_searcher.cpp:138-151): 2 bits per base, A=0 C=1 G=2 T=3, either case; any other
  *    character makes the k-mer invalid.

@@ -14,8 +14,14 @@ Pinned against the reference's own outputs (tests/golden/, made by tests/golden/
     nndescent          <- the same call, as the ALGORITHM pynndescent runs (nndescent.c: RP forest + NN-descent
                           restated from its published description): CPU baseline and recall figure only
     read_sequences / kmer_library / kmer_search
-                       <- kmer_searcher/kmer_searcher.cpp   PARITY UNPINNED (needs the un-vendored
-                          robin_hood.h; its own test data pin an obsolete format)
+                       <- kmer_searcher/kmer_searcher.cpp   PINNED against the reference program itself:
+                          oracle/Makefile compiles kmer_searcher.cpp unchanged into oracle/_ref/ against
+                          ref_shim/robin_hood.h (std::unordered_map / _set for the un-vendored robin-hood
+                          hashing); run_kmer_searcher runs it with 1 thread (records in file order), and the
+                          tests compare ids, index SETS (sorted per record; the hash order is unspecified)
+                          and kmer_frequency.bin bytes (tests/test_kmer_reference.py, the fixtures
+                          tests/golden/kmer_*; on the GPU tests/test_gpu_kmer_reference.py)
+    kmer_count         <- jellyfish count -C / dump -L      PARITY UNPINNED (third-party binary absent)
 """
 import ctypes
 import io
@@ -31,7 +37,8 @@ _LIB = None
 
 
 def build():
-    """Compile oracle/libfedrann_oracle.so (gcc, a second or two)."""
+    """Compile oracle/libfedrann_oracle.so (gcc, a second or two) and, where the reference checkout is present,
+    its kmer_searcher.cpp into oracle/_ref/kmer_searcher (see oracle/Makefile)."""
     subprocess.run(["make", "-s", "-C", _HERE], check=True)
 
 
@@ -272,8 +279,60 @@ def overlaps_tsv(indices, distances, read_names, strands):
 
 
 # --------------------------------------------------------------------------------------------
-# kmer_searcher (kmer_searcher/kmer_searcher.cpp) -- PARITY UNPINNED, see fedrann_oracle.c
+# kmer_searcher (kmer_searcher/kmer_searcher.cpp) -- pinned by the reference program, see below
 # --------------------------------------------------------------------------------------------
+def kmer_searcher_binary():
+    """Path of the reference's kmer_searcher built by build() (oracle/Makefile); an error if it is missing."""
+    path = os.path.join(_HERE, "_ref", "kmer_searcher")
+    if not os.access(path, os.X_OK):
+        raise FileNotFoundError("%s is missing: run build() (python __graft_entry__.py) in a checkout that has the "
+                                "reference source (oracle/Makefile, REF=...)" % path)
+    return path
+
+
+def read_kmer_output(path):
+    """output.bin (kmer_searcher.cpp:98-130) -> (ids list of bytes, list of index arrays, each SORTED: the reference
+    writes a record's indices in its hash set's order, which is unspecified)."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    magic, version, _, total = struct.unpack_from("<4sB3sQ", raw, 0)
+    if magic != b"KMER" or version != 1:
+        raise ValueError("%s: not an output.bin" % path)
+    ids, rows, o = [], [], 16
+    for _ in range(total):
+        (n,) = struct.unpack_from("<H", raw, o)
+        ids.append(raw[o + 2:o + 2 + n])
+        o += 2 + n
+        (c,) = struct.unpack_from("<I", raw, o)
+        rows.append(np.sort(np.frombuffer(raw, dtype="<u8", count=c, offset=o + 4)))
+        o += 4 + 8 * c
+    if o != len(raw):
+        raise ValueError("%s: %d trailing bytes" % (path, len(raw) - o))
+    return ids, rows
+
+
+def run_kmer_searcher(kmer_lib, reads, out_dir, k, expect_records=None):
+    """Run the reference program `kmer_searcher kmer_lib reads out_dir k 1` (one consumer thread: records in file
+    order).  Returns (ids, sorted index arrays, kmer_frequency.bin bytes).
+    The program's consumer loop can exit just before the producer's last push (kmer_searcher.cpp:300-305 against
+    :291), dropping the final records; so the record count is held against expect_records (default: the count
+    read_sequences gives) and a short file is run once more, then refused."""
+    exe = kmer_searcher_binary()
+    if expect_records is None:
+        expect_records = len(read_sequences(reads)[0])
+    for _ in range(2):
+        subprocess.run([exe, str(kmer_lib), str(reads), str(out_dir), str(int(k)), "1"], check=True,
+                       stdout=subprocess.DEVNULL)
+        ids, rows = read_kmer_output(os.path.join(str(out_dir), "output.bin"))
+        if len(ids) == expect_records:
+            with open(os.path.join(str(out_dir), "kmer_frequency.bin"), "rb") as f:
+                return ids, rows, f.read()
+        if len(ids) > expect_records:
+            raise RuntimeError("kmer_searcher wrote %d records for %s, expected %d" % (len(ids), reads, expect_records))
+    raise RuntimeError("kmer_searcher wrote %d records for %s, expected %d, in two runs (its consumer loop can exit "
+                       "before the last records are queued)" % (len(ids), reads, expect_records))
+
+
 def read_sequences(path):
     """kmer_searcher.cpp:153-200, line by line.  FASTA unless the first line starts with '@'.
     FASTA: id = header up to the first space/tab, sequence = the following lines concatenated (only the
