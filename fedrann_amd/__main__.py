@@ -11,6 +11,9 @@ projection matrix -> embeddings -> k-NN -> overlaps.tsv.  Entry points:
     --feature-matrix feature_matrix.npz --kmer-counts counts.npy [--read-names names.txt]
         (scipy.sparse.save_npz binary CSR of the rows to search; see feature_extraction.py).
 
+--no-projection: stages 2-3 build the IDF-weighted feature rows (value of feature f = idf[f]) instead of the
+projection and the embeddings, and stage 4 searches them exactly (fdr_knn_sparse); -n is ignored.  One GPU.
+
 --devices 0,1,...: every stage is sharded over several GPUs of the node.  The parent process starts one
 child per GPU BEFORE it touches a GPU itself; from reads, every child counts and searches its byte range of
 the file (stage1_sharded.py), then embeds its row block, the blocks are all-gathered (RCCL), every child
@@ -34,7 +37,7 @@ from . import global_variables
 from .feature_extraction import (build_feature_csr, embed_csr, get_feature_matrix, get_metadata,
                                  load_feature_matrix_npz, save_feature_matrix_npz)
 from .nearest_neighbors import NNDescent_ava
-from .precompute import build_precompute_matrix, get_precompute_matrix
+from .precompute import build_precompute_matrix, get_precompute_matrix, idf_weights
 
 LOG_FORMAT = "%(asctime)s - %(levelname)s - %(message)s"  # custom_logging.py:8
 logger = logging.getLogger("fedrann_amd")
@@ -88,6 +91,9 @@ def build_parser():
                         "fwd_kmer_library.fasta.")
     g.add_argument("--read-names", type=str, default=None,
                    help="With --feature-matrix: text file, one 'name<TAB>strand' (or just name) per row.")
+    g.add_argument("--no-projection", action="store_true", default=False,
+                   help="Search the IDF-weighted feature rows themselves (exact cosine k-NN, no random projection: "
+                        "the ground truth the projection approximates); -n is ignored.  One GPU only.")
     g.add_argument("--device", type=int, default=None, help="GPU ordinal (default $LOCAL_RANK or 0).")
     g.add_argument("--devices", type=str, default=None,
                    help="Comma-separated GPU ordinals: shard the rows over these GPUs (one process each).")
@@ -188,22 +194,32 @@ def check_limits(embedding_dimension, nndescent_n_neighbors):
 
 
 def load_inputs(*, output_dir, embedding_dimension, save_feature_matrix, kmer_searcher_output=None,
-                kmer_library=None, feature_matrix=None, kmer_counts=None, read_names_path=None, save=True):
+                kmer_library=None, feature_matrix=None, kmer_counts=None, read_names_path=None, save=True,
+                no_projection=False):
     """Stages 2-3a of the reference pipeline on the host (__main__.py:329-345): the projection matrix and
-    the read x feature CSR.  Returns (indptr, indices, n_features, P, read_names, strands)."""
+    the read x feature CSR.  Returns (indptr, indices, n_features, P, read_names, strands); with no_projection the
+    IDF weights of the features (float32 [n_features]) take P's place."""
     if kmer_searcher_output:
         from .precompute import read_kmer_counts
         n_features = 2 * int(read_kmer_counts(kmer_library).size)  # (count_kmers.py:148)
-        logger.info("--- 2. Generate dimension reduction and IDF matrix ---")
-        P, n_features = get_precompute_matrix(n_components=embedding_dimension, counter_file=kmer_library,
-                                              n_features=n_features)
+        if no_projection:
+            logger.info("--- 2. Generate IDF weights (no projection) ---")
+            P = idf_weights(read_kmer_counts(kmer_library), n_features)
+        else:
+            logger.info("--- 2. Generate dimension reduction and IDF matrix ---")
+            P, n_features = get_precompute_matrix(n_components=embedding_dimension, counter_file=kmer_library,
+                                                  n_features=n_features)
         logger.info("--- 3. Generate feature matrix ---")
         indptr, indices, read_names, strands = build_feature_csr(kmer_searcher_output, n_features)
     else:
         indptr, indices, n_features = load_feature_matrix_npz(feature_matrix)
         counts = _load_counts(kmer_counts)
-        logger.info("--- 2. Generate dimension reduction and IDF matrix ---")
-        P = build_precompute_matrix(counts, embedding_dimension, n_features=n_features)
+        if no_projection:
+            logger.info("--- 2. Generate IDF weights (no projection) ---")
+            P = idf_weights(counts, n_features)
+        else:
+            logger.info("--- 2. Generate dimension reduction and IDF matrix ---")
+            P = build_precompute_matrix(counts, embedding_dimension, n_features=n_features)
         logger.info("--- 3. Generate feature matrix ---")
         read_names, strands = _load_names(read_names_path, indptr.size - 1)
     if save_feature_matrix and save:
@@ -214,10 +230,11 @@ def load_inputs(*, output_dir, embedding_dimension, save_feature_matrix, kmer_se
 def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                          nndescent_n_neighbors, save_feature_matrix, keep_intermediates, chunk_size,
                          kmer_searcher_output=None, kmer_library=None, feature_matrix=None,
-                         kmer_counts=None, read_names_path=None):
+                         kmer_counts=None, read_names_path=None, no_projection=False):
     """Stages 2-4 of the reference pipeline (__main__.py:329-391) on one GPU.  The embeddings never leave
     HBM between the projection and the search (fdr_embed_knn), and only the features P has entries for
-    cross PCIe (fdr_csr_compact; the saved feature_matrix.npz is the full matrix)."""
+    cross PCIe (fdr_csr_compact; the saved feature_matrix.npz is the full matrix).  no_projection: stage 4
+    searches the IDF-weighted feature rows themselves (value of feature f = idf[f]; fdr_knn_sparse)."""
     from . import _lib
     from .feature_extraction import _projection_csr
     if kmer_searcher_output:
@@ -227,8 +244,15 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     indptr, indices, n_features, P, read_names, strands = load_inputs(
         output_dir=output_dir, embedding_dimension=embedding_dimension, save_feature_matrix=save_feature_matrix,
         kmer_searcher_output=kmer_searcher_output, kmer_library=kmer_library, feature_matrix=feature_matrix,
-        kmer_counts=kmer_counts, read_names_path=read_names_path)
+        kmer_counts=kmer_counts, read_names_path=read_names_path, no_projection=no_projection)
     ctx = _lib.default_context()
+    if no_projection:
+        logger.info("--- 4. Nearest Neighbors Search (exact, on the IDF-weighted feature rows) ---")
+        logger.info("--no-projection: -n/--embedding-dimension (%d) is ignored; %d rows x %d features, %d stored "
+                    "entries", embedding_dimension, indptr.size - 1, n_features, indices.size)
+        neighbor_matrix, distances = ctx.knn_sparse(indptr, indices, P[indices], n_features, nndescent_n_neighbors)
+        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates)
+        return
     Pc = _projection_csr(P)
     ctx.projection_load(Pc.indptr, Pc.indices, Pc.data, n_features, embedding_dimension)
     cip, cix = ctx.csr_compact(indptr, indices)
@@ -238,6 +262,10 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     logger.info("Using exact GPU k-NN in place of NNDescent (n_trees = %s, leaf_size = %s are inert)",
                 nndescent_n_trees, 200)
     neighbor_matrix, distances = ctx.embed_knn(cip, cix, nndescent_n_neighbors)
+    _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates)
+
+
+def _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates):
     nbr_output_file = join(output_dir, "overlaps.tsv")
     logger.debug("Saving overlap table to %s", nbr_output_file)
     rows = write_overlaps(nbr_output_file, neighbor_matrix, distances, read_names, strands)
@@ -476,8 +504,11 @@ def main(argv=None):
     args = parse_command_line_arguments(argv)
     global_variables.threads = args.threads
     global_variables.seed = args.seed
-    check_limits(args.embedding_dimension, args.nndescent_n_neighbors)  # before any work (the library would
-    # only refuse them after stages 1-3)
+    check_limits(1 if args.no_projection else args.embedding_dimension,  # (-n is not used without the projection)
+                 args.nndescent_n_neighbors)  # before any work (the library would only refuse them after stages 1-3)
+    if args.no_projection and args.devices and len([x for x in args.devices.split(",") if x.strip()]) > 1:
+        raise SystemExit("--no-projection runs on one GPU: it cannot be combined with --devices over several GPUs "
+                         "(sharding the sparse search is not implemented)")
     if args.device is not None and not args.rank_worker:
         os.environ["FEDRANN_DEVICE"] = str(args.device)
     output_dir = abspath(args.output_dir)
@@ -530,7 +561,7 @@ def main(argv=None):
         save_feature_matrix=args.save_feature_matrix, keep_intermediates=args.keep_intermediates,
         chunk_size=args.chunk_size, kmer_searcher_output=args.kmer_searcher_output,
         kmer_library=args.kmer_library, feature_matrix=args.feature_matrix,
-        kmer_counts=args.kmer_counts, read_names_path=args.read_names)
+        kmer_counts=args.kmer_counts, read_names_path=args.read_names, no_projection=args.no_projection)
 
 
 if __name__ == "__main__":

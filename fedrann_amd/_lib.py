@@ -23,7 +23,7 @@ SYMBOLS = (
     "fdr_kmer_count_begin", "fdr_kmer_count_add", "fdr_kmer_count_finish", "fdr_reads_scan", "fdr_reads_parse",
     "fdr_kmer_output_append", "fdr_last_query_paths", "fdr_last_knn_trace", "fdr_kmer_count_export_dev",
     "fdr_kmer_count_merge_dev", "fdr_kmer_count_merge", "fdr_set_knn_capture", "fdr_last_candidates",
-    "fdr_last_range_sets",
+    "fdr_last_range_sets", "fdr_knn_sparse",
 )
 FDR_MAX_K = 128
 KERNELS = ("embed_csr", "normalize_rows", "knn_tile", "knn_merge", "knn_prefilter", "knn_rerank",
@@ -32,7 +32,7 @@ FDR_MAX_DIM = 2048
 # fdr_last_query_paths codes (include/fedrann_hip.h: FDR_PATH_*)
 PATH_CERTIFIED, PATH_RANGE, PATH_EXACT, PATH_ZERO, PATH_RANGE_OVERFLOW, PATH_GENERIC, PATH_CLASS_MEMBER = 1, 2, 3, 4, 5, 6, 0x80
 # fdr_last_knn_trace (include/fedrann_hip.h: FDR_TRACE_*, FDR_FALLBACK_*)
-TRACE_KINDS = ("none", "exact", "prefilter", "generic")
+TRACE_KINDS = ("none", "exact", "prefilter", "generic", "sparse")
 FALLBACKS = ("none", "chunked", "whole")
 # fdr_set_knn_capture (include/fedrann_hip.h: FDR_CAPTURE_*, FDR_RANGE_CAP)
 CAPTURE_CANDIDATES, CAPTURE_RANGE = 1, 2
@@ -99,6 +99,7 @@ def load_library():
     L.fdr_embed.argtypes = [vp, i64, vp, vp, vp]
     L.fdr_knn.argtypes = [vp, vp, i64, i32, i32, vp, vp]
     L.fdr_embed_knn.argtypes = [vp, i64, vp, vp, i32, vp, vp, vp]
+    L.fdr_knn_sparse.argtypes = [vp, i64, i64, vp, vp, vp, i32, vp, vp]
     L.fdr_embed_dev.argtypes = [vp, i64, vp, vp, vp, vp]
     L.fdr_normalize_dev.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     L.fdr_knn_workspace_bytes.argtypes = [vp, i64, i64, i32, i32]
@@ -314,6 +315,38 @@ def overlaps_write(path, idx, dist, name_off, names, strands, row0=0, append=Fal
     if rc != 0:
         raise FedrannHipError("fdr_overlaps_write failed (%d): %s" % (rc, L.fdr_last_error().decode()))
     return int(lines.value)
+
+
+def check_sparse_rows(indptr, indices, values, n_features, k):
+    """The argument checks of Context.knn_sparse (fdr_knn_sparse repeats them on the device); needs no GPU.
+    Returns (n, k, n_features)."""
+    for name, a, dt in (("indptr", indptr, np.int64), ("indices", indices, np.int32), ("values", values, np.float32)):
+        if a is None and name == "values":
+            continue
+        if not isinstance(a, np.ndarray) or a.dtype != dt:
+            raise TypeError("%s must be a numpy %s array" % (name, np.dtype(dt)))
+        if a.ndim != 1 or not a.flags.c_contiguous:
+            raise ValueError("%s must be a C-contiguous 1-D array" % name)
+    if indptr.size < 1 or indptr[0] != 0 or indptr[-1] != indices.size or np.any(np.diff(indptr) < 0):
+        raise ValueError("indptr is not a CSR row pointer of the indices")
+    if values is not None and values.size != indices.size:
+        raise ValueError("values and indices differ in length")
+    n, k, F = indptr.size - 1, int(k), int(n_features)
+    if not 1 <= F <= np.iinfo(np.int32).max:
+        raise ValueError("n_features must be in [1, 2^31)")
+    if not 1 <= k <= FDR_MAX_K or k > n:
+        raise ValueError("need 1 <= k <= min(%d, n = %d), got k = %d" % (FDR_MAX_K, n, k))
+    if indices.size:
+        if int(indices.min()) < 0 or int(indices.max()) >= F:
+            raise ValueError("a feature index is outside [0, %d)" % F)
+        ascending = np.diff(indices) > 0
+        starts = indptr[1:-1]
+        ascending[starts[(starts > 0) & (starts < indices.size)] - 1] = True  # (a row's first id follows another row)
+        if not np.all(ascending):
+            raise ValueError("feature indices must be strictly ascending inside each row (sorted, no duplicates)")
+    if values is not None and not np.all(np.isfinite(values)):
+        raise ValueError("values must be finite")
+    return n, k, F
 
 
 class Context:
@@ -592,6 +625,18 @@ class Context:
         dist = np.empty((n, k), dtype=np.float32)
         self._check(self._L.fdr_knn(self._h, _ptr(E), n, d, int(k), _ptr(idx), _ptr(dist)),
                     "fdr_knn")
+        return idx, dist
+
+    def knn_sparse(self, indptr, indices, values, n_features, k):
+        """Exact cosine k-NN of the rows of a CSR (fdr_knn_sparse): the bits of knn() on the densified matrix,
+        without densifying it.  indptr int64 [n + 1], indices int32 strictly ascending inside each row and in
+        [0, n_features), values float32 (finite) or None (every stored entry 1).  Returns (idx int32 [n, k],
+        dist float32 [n, k])."""
+        n, k, F = check_sparse_rows(indptr, indices, values, n_features, k)
+        idx = np.empty((n, k), dtype=np.int32)
+        dist = np.empty((n, k), dtype=np.float32)
+        self._check(self._L.fdr_knn_sparse(self._h, n, F, _ptr(indptr), _ptr(indices), _ptr(values), k, _ptr(idx),
+                                           _ptr(dist)), "fdr_knn_sparse")
         return idx, dist
 
     def embed_knn(self, a_indptr, a_indices, k, return_embedding=False, out=None):

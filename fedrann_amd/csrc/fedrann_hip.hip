@@ -4,6 +4,7 @@
 //   K2 normalize_rows_kernel E -> Ehat          (done inside pynndescent in the reference)
 //   K3 knn_tile_kernel       exact cosine top-k (nearest_neighbors.py:39-55 -> pynndescent)
 //   K4 knn_merge_kernel      merge of per-segment top-k lists
+//   S1-S4 (knn_sparse.inc)   exact cosine top-k on the sparse feature rows themselves (no projection)
 //
 // Written for wave64 / MFMA / 160 KB LDS directly; there is no other backend.
 // ABI: include/fedrann_hip.h.  Design notes and rooflines: DESIGN.md.
@@ -466,6 +467,9 @@ struct fdr_ctx {
     DevBuf ks_seq, ks_off, ks_codes, ks_keys, ks_vals, ks_bloom, ks_counter, ks_pairs, ks_pairs2, ks_flag, ks_pos,
         ks_idx, ks_rows, ks_indptr, ks_tmp, kc_counts;
     DevBuf kc_a0, kc_a1, kc_c0, kc_c1, kc_mk, kc_mv, kc_rc;  // counting in blocks: accumulated table (ping / pong), merge buffers
+    // sparse k-NN (knn_sparse.inc)
+    DevBuf sp_ip, sp_ix, sp_val, sp_xhat, sp_keys, sp_keys2, sp_pos, sp_pos2, sp_efeat, sp_pval, sp_runptr, sp_heavy,
+        sp_cnt, sp_tmp;
     long long ks_nnz = 0, kc_n = 0;
     int64_t kc_block_chars = 0;  // fdr_set_kmer_count_block
     int kc_blocks = 0;           // blocks of the last fdr_kmer_count
@@ -580,7 +584,10 @@ FDR_EXPORT int fdr_destroy(fdr_ctx *ctx) {
                       &ctx->ks_counter, &ctx->ks_pairs, &ctx->ks_pairs2, &ctx->ks_flag, &ctx->ks_pos,
                       &ctx->ks_idx, &ctx->ks_rows, &ctx->ks_indptr, &ctx->ks_tmp, &ctx->kc_counts,
                       &ctx->kc_a0, &ctx->kc_a1, &ctx->kc_c0, &ctx->kc_c1, &ctx->kc_mk, &ctx->kc_mv, &ctx->kc_rc,
-                      &ctx->cap.cand, &ctx->cap.rq, &ctx->cap.rtheta, &ctx->cap.rcnt, &ctx->cap.rrows};
+                      &ctx->cap.cand, &ctx->cap.rq, &ctx->cap.rtheta, &ctx->cap.rcnt, &ctx->cap.rrows,
+                      &ctx->sp_ip, &ctx->sp_ix, &ctx->sp_val, &ctx->sp_xhat, &ctx->sp_keys, &ctx->sp_keys2,
+                      &ctx->sp_pos, &ctx->sp_pos2, &ctx->sp_efeat, &ctx->sp_pval, &ctx->sp_runptr, &ctx->sp_heavy,
+                      &ctx->sp_cnt, &ctx->sp_tmp};
     for (DevBuf *b : bufs) b->release();
     ctx->up_pool.stop();
     ctx->c_indptr.release();
@@ -2060,6 +2067,7 @@ FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indp
     return knn_from_device_E(ctx, (const float *)ctx->E.p, n_rows, ctx->d, k, idx_out, dist_out);
 }
 
+#include "knn_sparse.inc"  // S1 .. S4: exact cosine k-NN on sparse feature rows (fdr_knn_sparse)
 #include "kmer_search.inc"
 #include "kmer_output_loader.inc"
 #include "reads_parser.inc"

@@ -1,0 +1,460 @@
+// Part of libfedrann_hip.so: included by fedrann_hip.hip (one translation unit), not compiled on its own.
+// ------------------------------------------------------------------------------------------
+// S1 .. S4  exact cosine k-NN on sparse feature rows (fdr_knn_sparse), without the projection.
+//
+// The canonical similarity (DESIGN.md section 4) is the fp32 fma chain over the components in ascending order,
+// starting at +0.  A term with a zero factor leaves the accumulator's value unchanged, so the chain over the
+// features two rows SHARE, in ascending feature order, is the chain over all components of the densified rows
+// (up to the sign of a zero accumulator, which 1 - c cannot see).  The same holds for the norm chain of a row
+// over its stored values.  The kernels below therefore give the bits of fdr_knn on the densified matrix:
+//   S1 sp_rows_kernel      per row: norm chain over the stored values, rinv, zero flag, xhat = x * rinv; argument
+//                          checks (ids in [0, F), strictly ascending; finite values); one posting key per stored
+//                          entry whose xhat is not +-0 (an entry with xhat = +-0 cannot change an accumulator)
+//   (rocprim radix sort of (feature << 32 | row) keys: the postings, ascending by row inside a feature)
+//   S2 sp_postings_kernel  per-feature runs: run offsets (int64), posting rows / values, each entry's run id
+//   S3 knn_sparse_kernel   one wave per query: walk the query's features in ascending order; the lanes take the
+//                          feature's posting entries and update an LDS hash table keyed by target row that holds the
+//                          fp32 accumulator.  A target occurs once per feature, so one lane writes a slot per feature
+//                          step and the steps are ordered (no float atomics; the key insert is a compare-and-swap).
+//                          Then the keys (dist_bits << 32 | row) with dist < 1 are sorted together with the query's
+//                          list, and the list is filled with distance-1 rows in index order (every row outside the
+//                          table is at distance exactly 1).  A query whose table would pass SP_LIMIT distinct targets
+//                          is handed to ...
+//   S3r knn_sparse_kernel<true>  the same over ranges of SP_W consecutive target rows (a range holds at most SP_W
+//                          distinct targets, so the table never overflows at any posting length, a feature present
+//                          in every row included); each feature's slice of a range is found by binary search in its
+//                          ascending posting list, and each range's candidates are merged into the list by
+//                          (dist, idx).
+//   S4 sp_zero_row_kernel  the closed-form answer of an all-zero query: the first k zero rows (distance 0), then the
+//                          first rows that are not zero (distance 1).
+// Cost model: the pair updates are sum over features f of df_f^2 (df_f = posting length); each reads an 8-byte
+// posting entry (row, value), so the search moves ~8 * sum df_f^2 bytes, mostly from L2.  A range-split query
+// costs ceil(n / SP_W) binary searches per stored entry on top.
+// ------------------------------------------------------------------------------------------
+#define SP_CAP 1024    // hash-table slots per query (key int32 | fp32 accumulator: 8 KiB of LDS)
+#define SP_LOG2CAP 10
+#define SP_LIMIT 512   // more distinct targets than this before a chunk of 64 postings: the range-split kernel
+#define SP_W 512       // target rows per range of the range-split kernel (<= SP_CAP: the table cannot fill)
+#define SP_LIST 128    // the query's list (FDR_MAX_K keys) ahead of the table in the same LDS array
+#define SP_EMPTY (-1)
+static_assert(SP_LIST >= FDR_MAX_K, "the list holds k keys");
+static_assert(SP_LIST + SP_LIMIT + 64 <= SP_LIST + SP_CAP && SP_LIST + SP_W <= SP_LIST + SP_CAP,
+              "list + candidates of one range fit the sort buffer");
+static_assert((1 << SP_LOG2CAP) == SP_CAP, "SP_CAP is a power of two");
+
+// counters of one call (u64 each)
+#define SP_CNT_ERR 0      // or of SP_ERR_* bits
+#define SP_CNT_DROPPED 1  // stored entries without a posting (xhat = +-0)
+#define SP_CNT_ZERO 2     // zero rows
+#define SP_CNT_HEAVY 3    // queries handed to the range-split kernel
+#define SP_ERR_RANGE 1u
+#define SP_ERR_ORDER 2u
+#define SP_ERR_VALUE 4u
+
+// S1: one thread per row
+__global__ __launch_bounds__(256) void sp_rows_kernel(long long n, long long F, const long long *__restrict__ indptr,
+                                                      const int *__restrict__ indices, const float *__restrict__ vals,
+                                                      float *__restrict__ xhat, u64 *__restrict__ keys,
+                                                      unsigned *__restrict__ pos, int *__restrict__ efeat,
+                                                      unsigned char *__restrict__ zero, u64 *__restrict__ cnt) {
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    const long long b = indptr[q], e = indptr[q + 1];
+    float nn = 0.0f;  // the canonical norm chain over the stored values in order (zeros between them add nothing)
+    for (long long j = b; j < e; ++j) {
+        const float v = vals ? vals[j] : 1.0f;
+        nn = __builtin_fmaf(v, v, nn);
+    }
+    float ri = 0.0f;
+    if (nn > 0.0f) ri = (float)(1.0 / sqrt((double)nn));
+    zero[q] = nn > 0.0f ? 0 : 1;
+    if (!(nn > 0.0f)) atomicAdd(&cnt[SP_CNT_ZERO], 1ull);
+    unsigned err = 0;
+    long long prev = -1;
+    u64 dropped = 0;
+    for (long long j = b; j < e; ++j) {
+        const long long f = indices[j];
+        const float v = vals ? vals[j] : 1.0f;
+        if (f < 0 || f >= F) err |= SP_ERR_RANGE;
+        else if (f <= prev) err |= SP_ERR_ORDER;
+        prev = f;
+        if (!isfinite(v)) err |= SP_ERR_VALUE;
+        const float x = v * ri;
+        const bool keep = x != 0.0f && err == 0u;
+        xhat[j] = x;
+        keys[j] = keep ? (((u64)f << 32) | (u64)q) : ((u64)F << 32);  // (F << 32: after every posting)
+        pos[j] = (unsigned)j;
+        efeat[j] = -1;
+        dropped += keep ? 0 : 1;
+    }
+    if (err) atomicOr(&cnt[SP_CNT_ERR], (u64)err);
+    if (dropped) atomicAdd(&cnt[SP_CNT_DROPPED], dropped);
+}
+
+__global__ __launch_bounds__(256) void sp_run_flags_kernel(long long m, const u64 *__restrict__ keys,
+                                                           int *__restrict__ flag) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < m) flag[i] = (i == 0 || (keys[i] >> 32) != (keys[i - 1] >> 32)) ? 1 : 0;
+}
+
+// S2: sorted postings -> run offsets, rows, values, and each stored entry's run id (features renumbered densely in
+// ascending order, so no array is as long as F)
+__global__ __launch_bounds__(256) void sp_postings_kernel(long long m, const u64 *__restrict__ keys,
+                                                          const unsigned *__restrict__ pos,
+                                                          const int *__restrict__ run_incl,
+                                                          const float *__restrict__ xhat, int *__restrict__ efeat,
+                                                          int *__restrict__ prow, float *__restrict__ pval,
+                                                          long long *__restrict__ runptr) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const int c = run_incl[i] - 1;
+    const unsigned p = pos[i];
+    efeat[p] = c;
+    prow[i] = (int)(unsigned)keys[i];
+    pval[i] = xhat[p];
+    if (i == 0 || run_incl[i - 1] != run_incl[i]) runptr[c] = i;
+    if (i == m - 1) runptr[c + 1] = m;
+}
+
+// S4: one wave, sixteen rows per lane and turn; stops once it has k of each kind
+__global__ __launch_bounds__(64) void sp_zero_row_kernel(long long n, const unsigned char *__restrict__ zero, int k,
+                                                         int *__restrict__ zidx, float *__restrict__ zdist) {
+    __shared__ int zr[FDR_MAX_K], nr[FDR_MAX_K];
+    const int lane = threadIdx.x;
+    int nz = 0, nv = 0;  // zero / non-zero rows found so far (wave-uniform)
+    for (long long base = 0; base < n && (nz < k || nv < k); base += 64 * 16) {
+        unsigned zm = 0, vm = 0;
+        for (int b = 0; b < 16; ++b) {
+            const long long r = base + lane * 16 + b;
+            if (r < n) {
+                if (zero[r]) zm |= 1u << b;
+                else vm |= 1u << b;
+            }
+        }
+        int iz = __popc(zm), iv = __popc(vm);
+        for (int off = 1; off < 64; off <<= 1) {
+            const int a = __shfl_up(iz, off), c = __shfl_up(iv, off);
+            if (lane >= off) {
+                iz += a;
+                iv += c;
+            }
+        }
+        int sz = nz + iz - __popc(zm), sv = nv + iv - __popc(vm);
+        for (int b = 0; b < 16; ++b) {
+            const int r = (int)(base + lane * 16 + b);
+            if ((zm >> b) & 1u) {
+                if (sz < k) zr[sz] = r;
+                ++sz;
+            }
+            if ((vm >> b) & 1u) {
+                if (sv < k) nr[sv] = r;
+                ++sv;
+            }
+        }
+        nz += __shfl(iz, 63);
+        nv += __shfl(iv, 63);
+    }
+    __syncthreads();
+    const int zk = min(nz, k);
+    for (int i = lane; i < k; i += 64) {  // (n >= k: nv >= k - zk)
+        zidx[i] = i < zk ? zr[i] : nr[i - zk];
+        zdist[i] = i < zk ? 0.0f : 1.0f;
+    }
+}
+
+// the slot of target row t (inserted if new); the caller keeps the distinct keys below SP_CAP, so a free slot exists
+__device__ __forceinline__ int sp_insert(int *tab, int t, bool &isnew) {
+    unsigned s = ((unsigned)t * 0x9E3779B1u) >> (32 - SP_LOG2CAP);
+    for (int probe = 0; probe < SP_CAP; ++probe) {
+        const int cur = __hip_atomic_load(&tab[2 * s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        if (cur == t) return (int)s;
+        if (cur == SP_EMPTY) {
+            const int old = atomicCAS(&tab[2 * s], SP_EMPTY, t);
+            if (old == SP_EMPTY) {
+                isnew = true;
+                return (int)s;
+            }
+            if (old == t) return (int)s;
+        }
+        s = (s + 1) & (SP_CAP - 1);
+    }
+    return -1;  // (unreachable: fewer than SP_CAP distinct keys)
+}
+
+__device__ __forceinline__ long long sp_lower_bound(const int *__restrict__ a, long long lo, long long hi, int v) {
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (a[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// S3 / S3r: one wave (one workgroup) per query
+template <bool RANGE>
+__global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, const long long *__restrict__ indptr,
+                                                        const int *__restrict__ efeat, const float *__restrict__ xhat,
+                                                        const long long *__restrict__ runptr,
+                                                        const int *__restrict__ prow, const float *__restrict__ pval,
+                                                        const unsigned char *__restrict__ zero, int k,
+                                                        const int *__restrict__ zidx, const float *__restrict__ zdist,
+                                                        int *__restrict__ heavy, u64 *__restrict__ cnt,
+                                                        int *__restrict__ idx_out, float *__restrict__ dist_out) {
+    __shared__ u64 buf[SP_LIST + SP_CAP];  // [0, k): the query's list; [SP_LIST, ...): the table, then the sort buffer
+    int *tab = reinterpret_cast<int *>(buf + SP_LIST);  // slot s: tab[2 s] = target row (SP_EMPTY), tab[2 s + 1] = acc
+    const int lane = threadIdx.x;
+    const long long q = RANGE ? (long long)heavy[blockIdx.x] : (long long)blockIdx.x;
+    int *out_i = idx_out + q * k;
+    float *out_d = dist_out + q * k;
+    if (!RANGE && zero[q]) {
+        for (int i = lane; i < k; i += 64) {
+            out_i[i] = zidx[i];
+            out_d[i] = zdist[i];
+        }
+        return;
+    }
+    const long long qb = indptr[q], qe = indptr[q + 1];
+    for (int i = lane; i < SP_LIST; i += 64) buf[i] = KEY_INF;
+    const long long nranges = RANGE ? (n + SP_W - 1) / SP_W : 1;
+    const u64 lt = (1ull << lane) - 1ull;
+    for (long long r = 0; r < nranges; ++r) {
+        const int lo = RANGE ? (int)(r * SP_W) : 0;
+        const int hi = RANGE ? (int)min(n, (long long)lo + SP_W) : (int)n;
+        for (int i = lane; i < SP_CAP; i += 64) buf[SP_LIST + i] = 0x00000000FFFFFFFFull;  // key SP_EMPTY, acc +0
+        __syncthreads();
+        int count = 0;  // distinct targets in the table (wave-uniform)
+        bool overflow = false;
+        for (long long j0 = qb; j0 < qe && !overflow; j0 += 64) {
+            // lane l holds the query's stored entry j0 + l: its value and its feature's posting slice
+            const long long j = j0 + lane;
+            int c = -1;
+            float qv = 0.0f;
+            long long ps = 0, pe = 0;
+            if (j < qe) {
+                c = efeat[j];
+                if (c >= 0) {
+                    qv = xhat[j];
+                    ps = runptr[c];
+                    pe = runptr[c + 1];
+                    if (RANGE) {
+                        ps = sp_lower_bound(prow, ps, pe, lo);
+                        pe = sp_lower_bound(prow, ps, pe, hi);
+                    }
+                }
+            }
+            u64 live = __ballot(c >= 0 && pe > ps);
+            while (live) {  // the features in ascending order (wave-uniform)
+                const int src = __builtin_ctzll(live);
+                live &= live - 1;
+                const float v = __shfl(qv, src);
+                const long long s0 = __shfl(ps, src), s1 = __shfl(pe, src);
+                for (long long base = s0; base < s1; base += 64) {
+                    if (!RANGE && count > SP_LIMIT) {
+                        overflow = true;
+                        break;
+                    }
+                    const long long e = base + lane;
+                    bool isnew = false;
+                    if (e < s1) {
+                        const int s = sp_insert(tab, prow[e], isnew);
+                        if (s >= 0) {
+                            float *a = reinterpret_cast<float *>(&tab[2 * s + 1]);
+                            *a = __builtin_fmaf(v, pval[e], isnew ? 0.0f : *a);
+                        }
+                    }
+                    count += __popcll(__ballot(isnew));
+                    __syncthreads();  // (one wave: orders this step's table writes before the next step's reads)
+                }
+                if (overflow) break;
+            }
+        }
+        if (overflow) {
+            if (lane == 0) heavy[atomicAdd(&cnt[SP_CNT_HEAVY], 1ull)] = (int)q;
+            return;
+        }
+        // the table's keys with dist < 1, appended to the list, sorted by (dist, idx)
+        u64 cand[SP_CAP / 64];
+#pragma unroll
+        for (int i = 0; i < SP_CAP / 64; ++i) {
+            const u64 w = buf[SP_LIST + lane + 64 * i];
+            const int t = (int)(unsigned)w;
+            u64 key = KEY_INF;
+            if (t != SP_EMPTY) {
+                const float d = dist_from_sim(__uint_as_float((unsigned)(w >> 32)));
+                if (d < 1.0f) key = ((u64)__float_as_uint(d) << 32) | (unsigned)t;
+            }
+            cand[i] = key;
+        }
+        __syncthreads();
+        int m = k;
+#pragma unroll
+        for (int i = 0; i < SP_CAP / 64; ++i) {
+            const bool h = cand[i] != KEY_INF;
+            const u64 bal = __ballot(h);
+            if (h) buf[m + __popcll(bal & lt)] = cand[i];
+            m += __popcll(bal);
+        }
+        int P = 64;
+        while (P < m) P <<= 1;
+        for (int i = m + lane; i < P; i += 64) buf[i] = KEY_INF;
+        __syncthreads();
+        for (int k2 = 2; k2 <= P; k2 <<= 1)
+            for (int jj = k2 >> 1; jj > 0; jj >>= 1) {
+                for (int p = lane; p < P / 2; p += 64) {
+                    const int i = ((p & ~(jj - 1)) << 1) | (p & (jj - 1)), ixj = i + jj;
+                    const u64 a = buf[i], b = buf[ixj];
+                    if ((a > b) == ((i & k2) == 0)) {
+                        buf[i] = b;
+                        buf[ixj] = a;
+                    }
+                }
+                __syncthreads();
+            }
+    }
+    // the list's keys (all at dist < 1), then the smallest rows outside it at distance 1
+    int have = 0;
+    for (int i0 = 0; i0 < k; i0 += 64) have += __popcll(__ballot(i0 + lane < k && buf[i0 + lane] != KEY_INF));
+    for (int i = lane; i < have; i += 64) {
+        const u64 key = buf[i];
+        out_i[i] = (int)(unsigned)key;
+        out_d[i] = __uint_as_float((unsigned)(key >> 32));
+    }
+    int filled = have;
+    for (long long base = 0; filled < k; base += 64) {  // (n >= k: ends)
+        const long long rr = base + lane;
+        bool take = rr < n;
+        for (int i = 0; i < have && take; ++i) take = (unsigned)buf[i] != (unsigned)rr;
+        const u64 bal = __ballot(take);
+        const int at = filled + __popcll(bal & lt);
+        if (take && at < k) {
+            out_i[at] = (int)rr;
+            out_d[at] = 1.0f;
+        }
+        filled += __popcll(bal);
+    }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------
+FDR_EXPORT int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const int64_t *indptr,
+                              const int32_t *indices, const float *values, int32_t k, int32_t *idx_out,
+                              float *dist_out) {
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    knn_call_begin(ctx);
+    if (!indptr || !idx_out || !dist_out) return fail(FDR_E_ARG, "knn_sparse: null pointer");
+    if (k < 1 || k > FDR_MAX_K) return fail(FDR_E_ARG, "knn_sparse: k=%d unsupported (1..%d)", k, FDR_MAX_K);
+    if (n < k) return fail(FDR_E_ARG, "knn_sparse: need n (%lld) >= k (%d)", (long long)n, k);
+    if (n > INT32_MAX) return fail(FDR_E_ARG, "knn_sparse: n (%lld) must be below 2^31 rows", (long long)n);
+    if (n_features < 1 || n_features > INT32_MAX)
+        return fail(FDR_E_ARG, "knn_sparse: n_features (%lld) must be in [1, 2^31)", (long long)n_features);
+    if (indptr[0] != 0) return fail(FDR_E_ARG, "knn_sparse: indptr[0] must be 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (indptr[i + 1] < indptr[i]) return fail(FDR_E_ARG, "knn_sparse: indptr not monotone at row %lld", (long long)i);
+    const int64_t nnz = indptr[n];
+    if (nnz > INT32_MAX)
+        return fail(FDR_E_ARG, "knn_sparse: %lld stored entries (at most 2^31 - 1)", (long long)nnz);
+    if (nnz > 0 && !indices) return fail(FDR_E_ARG, "knn_sparse: indices is null");
+    const hipStream_t st = ctx->stream;
+    const size_t m1 = (size_t)std::max<int64_t>(nnz, 1);
+    if ((rc = ctx->sp_ip.reserve((size_t)(n + 1) * 8))) return rc;
+    if ((rc = ctx->sp_ix.reserve(m1 * 4))) return rc;
+    if (values && (rc = ctx->sp_val.reserve(m1 * 4))) return rc;
+    if ((rc = ctx->sp_xhat.reserve(m1 * 4))) return rc;
+    if ((rc = ctx->sp_keys.reserve(m1 * 8))) return rc;
+    if ((rc = ctx->sp_keys2.reserve(m1 * 8))) return rc;
+    if ((rc = ctx->sp_pos.reserve(m1 * 4))) return rc;
+    if ((rc = ctx->sp_pos2.reserve(m1 * 4))) return rc;
+    if ((rc = ctx->sp_efeat.reserve(m1 * 4))) return rc;
+    if ((rc = ctx->sp_pval.reserve(m1 * 4))) return rc;
+    if ((rc = ctx->sp_runptr.reserve((m1 + 1) * 8))) return rc;
+    if ((rc = ctx->sp_heavy.reserve((size_t)n * 4))) return rc;
+    if ((rc = ctx->sp_cnt.reserve(64 + (size_t)FDR_MAX_K * 8))) return rc;
+    if ((rc = ctx->zero.reserve((size_t)n))) return rc;
+    if ((rc = ctx->idx.reserve((size_t)n * k * 4))) return rc;
+    if ((rc = ctx->dist.reserve((size_t)n * k * 4))) return rc;
+    u64 *cnt = (u64 *)ctx->sp_cnt.p;
+    int *zidx = (int *)((char *)ctx->sp_cnt.p + 64);
+    float *zdist = (float *)((char *)ctx->sp_cnt.p + 64 + FDR_MAX_K * 4);
+    HIP_TRY(hipMemcpyAsync(ctx->sp_ip.p, indptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+    if (nnz > 0) {
+        HIP_TRY(hipMemcpyAsync(ctx->sp_ix.p, indices, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+        if (values) HIP_TRY(hipMemcpyAsync(ctx->sp_val.p, values, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipMemsetAsync(cnt, 0, 64, st));
+    hipLaunchKernelGGL(sp_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n,
+                       (long long)n_features, (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_ix.p,
+                       values ? (const float *)ctx->sp_val.p : nullptr, (float *)ctx->sp_xhat.p, (u64 *)ctx->sp_keys.p,
+                       (unsigned *)ctx->sp_pos.p, (int *)ctx->sp_efeat.p, (unsigned char *)ctx->zero.p, cnt);
+    HIP_TRY(hipGetLastError());
+    u64 h_cnt[4];
+    HIP_TRY(hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_cnt[SP_CNT_ERR] & SP_ERR_RANGE)
+        return fail(FDR_E_ARG, "knn_sparse: a feature index is outside [0, %lld)", (long long)n_features);
+    if (h_cnt[SP_CNT_ERR] & SP_ERR_ORDER)
+        return fail(FDR_E_ARG, "knn_sparse: feature indices must be strictly ascending inside a row");
+    if (h_cnt[SP_CNT_ERR] & SP_ERR_VALUE) return fail(FDR_E_ARG, "knn_sparse: non-finite value");
+    const long long kept = (long long)nnz - (long long)h_cnt[SP_CNT_DROPPED];
+    const long long nzero = (long long)h_cnt[SP_CNT_ZERO];
+    if (kept > 0) {
+        int end_bit = 32;
+        while (end_bit < 64 && ((u64)n_features >> (end_bit - 32)) != 0) ++end_bit;  // (the sentinel F << 32 too)
+        size_t t_sort = 0, t_scan = 0;
+        (void)rocprim::radix_sort_pairs(nullptr, t_sort, (u64 *)nullptr, (u64 *)nullptr, (unsigned *)nullptr,
+                                        (unsigned *)nullptr, (size_t)nnz, 0, end_bit, (hipStream_t) nullptr);
+        (void)rocprim::inclusive_scan(nullptr, t_scan, (int *)nullptr, (int *)nullptr, (size_t)kept,
+                                      rocprim::plus<int>(), (hipStream_t) nullptr);
+        if ((rc = ctx->sp_tmp.reserve(std::max(t_sort, t_scan)))) return rc;
+        size_t tb = ctx->sp_tmp.cap;
+        HIP_TRY(rocprim::radix_sort_pairs(ctx->sp_tmp.p, tb, (u64 *)ctx->sp_keys.p, (u64 *)ctx->sp_keys2.p,
+                                          (unsigned *)ctx->sp_pos.p, (unsigned *)ctx->sp_pos2.p, (size_t)nnz, 0,
+                                          end_bit, st));
+        // the unsorted keys are free now: run-start flags and inclusive run numbers (two int32 per entry fit)
+        int *flag = (int *)ctx->sp_keys.p, *run_incl = flag + kept;
+        const unsigned g = (unsigned)((kept + 255) / 256);
+        hipLaunchKernelGGL(sp_run_flags_kernel, dim3(g), dim3(256), 0, st, kept, (const u64 *)ctx->sp_keys2.p, flag);
+        HIP_TRY(hipGetLastError());
+        tb = ctx->sp_tmp.cap;
+        HIP_TRY(rocprim::inclusive_scan(ctx->sp_tmp.p, tb, flag, run_incl, (size_t)kept, rocprim::plus<int>(), st));
+        // posting rows go where the unsorted positions were
+        hipLaunchKernelGGL(sp_postings_kernel, dim3(g), dim3(256), 0, st, kept, (const u64 *)ctx->sp_keys2.p,
+                           (const unsigned *)ctx->sp_pos2.p, (const int *)run_incl, (const float *)ctx->sp_xhat.p,
+                           (int *)ctx->sp_efeat.p, (int *)ctx->sp_pos.p, (float *)ctx->sp_pval.p,
+                           (long long *)ctx->sp_runptr.p);
+        HIP_TRY(hipGetLastError());
+    }
+    if (nzero > 0) {
+        hipLaunchKernelGGL(sp_zero_row_kernel, dim3(1), dim3(64), 0, st, (long long)n, (const unsigned char *)ctx->zero.p,
+                           (int)k, zidx, zdist);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(knn_sparse_kernel<false>, dim3((unsigned)n), dim3(64), 0, st, (long long)n,
+                       (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_efeat.p, (const float *)ctx->sp_xhat.p,
+                       (const long long *)ctx->sp_runptr.p, (const int *)ctx->sp_pos.p, (const float *)ctx->sp_pval.p,
+                       (const unsigned char *)ctx->zero.p, (int)k, (const int *)zidx, (const float *)zdist,
+                       (int *)ctx->sp_heavy.p, cnt, (int *)ctx->idx.p, (float *)ctx->dist.p);
+    HIP_TRY(hipGetLastError());
+    u64 h_heavy = 0;
+    HIP_TRY(hipMemcpyAsync(&h_heavy, cnt + SP_CNT_HEAVY, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_heavy > 0) {
+        hipLaunchKernelGGL(knn_sparse_kernel<true>, dim3((unsigned)h_heavy), dim3(64), 0, st, (long long)n,
+                           (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_efeat.p, (const float *)ctx->sp_xhat.p,
+                           (const long long *)ctx->sp_runptr.p, (const int *)ctx->sp_pos.p,
+                           (const float *)ctx->sp_pval.p, (const unsigned char *)ctx->zero.p, (int)k,
+                           (const int *)zidx, (const float *)zdist, (int *)ctx->sp_heavy.p, cnt, (int *)ctx->idx.p,
+                           (float *)ctx->dist.p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(idx_out, ctx->idx.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(dist_out, ctx->dist.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    fdr_knn_trace &t = ctx->trace;
+    t.kind = FDR_TRACE_SPARSE;
+    t.k = k;
+    t.queries = t.targets = n;
+    t.zero_queries = (int32_t)std::min<long long>(nzero, INT32_MAX);
+    t.range_queries = (int32_t)h_heavy;
+    t.range_chunks = h_heavy ? (int32_t)((n + SP_W - 1) / SP_W) : 0;
+    return FDR_OK;
+}

@@ -3,7 +3,8 @@
 Mirror of the reference's fedrann/nearest_neighbors.py (NNDescent_ava.get_neighbors :22-55), which
 wraps pynndescent.NNDescent(...).neighbor_graph.  NN-descent approximates the exact k-NN graph;
 this class returns the exact graph (tiled MFMA distance kernel + top-k, see
-csrc/fedrann_hip.hip), so the forest / descent hyper-parameters are accepted and ignored.
+csrc/fedrann_hip.hip), so the forest / descent hyper-parameters are accepted and ignored.  A sparse matrix
+wider than FDR_MAX_DIM columns is searched as it is (csrc/knn_sparse.inc) instead of densified.
 Rows come back ascending by (distance, index); a row's self match is a neighbour like any other,
 as in `index.neighbor_graph`.
 """
@@ -29,6 +30,11 @@ class NNDescent_ava(_NearestNeighbors):
         if metric != "cosine":
             raise ValueError("only metric='cosine' is implemented (the reference's only call, "
                              "__main__.py:186)")
+        ctx = context or _lib.default_context()
+        if sp.issparse(data) and data.ndim == 2 and data.shape[1] > _lib.FDR_MAX_DIM:
+            # too wide to densify (F = 2 x sampled k-mers: 1.3 M columns at 100 k reads): the exact search of the
+            # sparse rows themselves, same canonical result as the dense route on the densified matrix
+            return self._sparse_neighbors(data, int(index_n_neighbors), ctx, verbose)
         if sp.issparse(data):
             data = data.toarray()
         data = np.ascontiguousarray(data, dtype=np.float32)  # pynndescent also casts to float32
@@ -38,10 +44,23 @@ class NNDescent_ava(_NearestNeighbors):
         k = int(index_n_neighbors)
         if n < k:
             raise ValueError("n_neighbors (%d) must not exceed the number of rows (%d)" % (k, n))
-        ctx = context or _lib.default_context()
         if verbose:
             logger.info("exact cosine k-NN on %s: %d rows x %d dims, k = %d (n_trees / leaf_size / "
                         "n_iters are NN-descent parameters and do not apply)",
                         ctx.device_info()["name"], n, d, k)
         nbr_indices, distances = ctx.knn(data, k)
         return nbr_indices, distances
+
+    @staticmethod
+    def _sparse_neighbors(data, k, ctx, verbose):
+        A = data.tocsr(copy=True)  # (the caller's matrix is left as it is)
+        A.sum_duplicates()  # canonical: summed duplicates, ascending columns per row
+        A.sort_indices()
+        n, F = A.shape
+        if n < k:
+            raise ValueError("n_neighbors (%d) must not exceed the number of rows (%d)" % (k, n))
+        if verbose:
+            logger.info("exact cosine k-NN on %s over the sparse rows: %d rows x %d features, %d stored entries, "
+                        "k = %d", ctx.device_info()["name"], n, F, A.nnz, k)
+        return ctx.knn_sparse(A.indptr.astype(np.int64), A.indices.astype(np.int32),
+                              np.ascontiguousarray(A.data, dtype=np.float32), F, k)

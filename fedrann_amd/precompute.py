@@ -71,6 +71,24 @@ def kmer_count_generator(filename, kmer_count):
         yield i + kmer_count, int(c)
 
 
+def idf_weights(counts, n_features=None):
+    """float32 [F] IDF weight of every feature, as build_precompute_matrix uses it (precompute.py:68-77):
+    count[i] = count[i + F/2] = counts[i] (features without a line stay 0), idf = float32(ln(F / (count + 1e-12)))."""
+    counts = np.asarray(counts, dtype=np.int64)
+    L = int(counts.size)
+    F = 2 * L if n_features is None else int(n_features)
+    half = int(F / 2)  # the reference passes int(n_features / 2) as kmer_count
+    if L > half:
+        raise IndexError("counter file has %d k-mers but n_features/2 = %d" % (L, half))
+    if F <= 0:
+        raise ValueError("n_features must be positive")
+    cnt = np.zeros(F, dtype=np.uint64)
+    cnt[:L] = counts
+    cnt[half:half + L] = counts
+    with np.errstate(divide="ignore"):
+        return np.log(F / (cnt + 1e-12)).astype(np.float32)
+
+
 def build_precompute_matrix(counts, n_components, n_features=None, density="auto",
                             seed=DEFAULT_SEED):
     """P from the forward-library counts.  Returns scipy CSR (F x d, float32, sorted indices).
@@ -84,19 +102,8 @@ def build_precompute_matrix(counts, n_components, n_features=None, density="auto
       :107    scale = float32(sqrt(1/density) / sqrt(d))     (value-based casting of numpy 1.x)
       :113    P[f, c] = (scale * sign) * idf[f]                (two float32 multiplies)
     """
-    counts = np.asarray(counts, dtype=np.int64)
-    L = int(counts.size)
-    F = 2 * L if n_features is None else int(n_features)
-    half = int(F / 2)  # the reference passes int(n_features / 2) as kmer_count
-    if L > half:
-        raise IndexError("counter file has %d k-mers but n_features/2 = %d" % (L, half))
-    if F <= 0:
-        raise ValueError("n_features must be positive")
-    cnt = np.zeros(F, dtype=np.uint64)
-    cnt[:L] = counts
-    cnt[half:half + L] = counts
-    with np.errstate(divide="ignore"):
-        idf = np.log(F / (cnt + 1e-12)).astype(np.float32)
+    idf = idf_weights(counts, n_features)
+    F = int(idf.size)
     logger.debug("idf.shape=%s", idf.shape)
     if density == "auto":
         _density = 1 / math.sqrt(F)

@@ -111,6 +111,21 @@ int fdr_knn(fdr_ctx *ctx, const float *E, int64_t n, int32_t d, int32_t k, int32
 int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indptr, const int32_t *a_indices,
                   int32_t k, int32_t *idx_out, float *dist_out, float *E_out);
 
+/* ---- exact cosine k-NN on sparse feature rows, without the projection  (replaces
+ *      NNDescent_ava().get_neighbors(csr, metric="cosine", index_n_neighbors=k, ...).neighbor_graph for a
+ *      csr_matrix argument, nearest_neighbors.py:39-55; pynndescent searches sparse cosine data natively) -----------
+ * The rows are a CSR with n rows and n_features columns: indptr int64 [n + 1], indices int32 [indptr[n]] strictly
+ * ascending inside each row and in [0, n_features), values float32 [indptr[n]] finite (NULL: every stored entry is
+ * 1).  Host pointers; the call synchronises.  idx_out int32 [n, k], dist_out float32 [n, k]: the result of fdr_knn on
+ * the densified matrix, bit for bit: the norm chain over a row's stored values in order, the
+ * similarity chain over the features two rows share in ascending order, dist = clamp(1 - c, 0, 1), two zero rows at
+ * distance 0, (distance, index) order, self a candidate; every row that shares no feature with a non-zero query is
+ * at distance exactly 1, so such a list ends in the smallest row indices not already in it.  Limits (FDR_E_ARG):
+ * 1 <= k <= FDR_MAX_K, k <= n < 2^31, 1 <= n_features < 2^31, fewer than 2^31 stored entries.  Cost: ~8 bytes per
+ * row-pair update, sum over the features of df^2 (df = rows holding the feature); DESIGN.md section 5. */
+int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const int64_t *indptr, const int32_t *indices,
+                   const float *values, int32_t k, int32_t *idx_out, float *dist_out);
+
 /* ---- device-resident API (multi-GPU host, bench.py) ----------------------------------------
  * All pointers are device pointers; work is enqueued on `stream` (a hipStream_t). */
 int fdr_embed_dev(fdr_ctx *ctx, int64_t n_rows, const int64_t *d_indptr, const int32_t *d_indices,
@@ -201,12 +216,16 @@ int fdr_last_unique(fdr_ctx *ctx, int *unique_targets, int *unique_queries);
 int fdr_last_prefilter_launches(fdr_ctx *ctx, int *launches, int *queues);
 /* Diagnostics (test support; nothing in the product reads it): which kernels the most recent k-NN call ran.  With
  * the duplicate-row layer active it describes the inner search of the unique rows.  Every k-NN entry point
- * (fdr_knn_dev, fdr_knn, fdr_embed_knn, fdr_knn_classes_dev, fdr_knn_unique_dev, fdr_knn_expand_dev) clears it, and
+ * (fdr_knn_dev, fdr_knn, fdr_embed_knn, fdr_knn_classes_dev, fdr_knn_unique_dev, fdr_knn_expand_dev, fdr_knn_sparse)
+ * clears it, and
  * the per-query path codes, before it checks its arguments. */
 #define FDR_TRACE_NONE 0       /* no k-NN search ran (a cleared trace, or a call that failed or found nothing to do) */
 #define FDR_TRACE_EXACT 1      /* exact mode: the fp32 kernel for every query */
 #define FDR_TRACE_PREFILTER 2  /* fp16 candidate pass + certificate (+ range pass, + exact fallback) */
 #define FDR_TRACE_GENERIC 3    /* d > 1024, or k > 64 / d > 512 below 8192 targets: the generic kernel */
+#define FDR_TRACE_SPARSE 4     /* fdr_knn_sparse: zero_queries = zero rows; range_queries = queries whose targets
+                                  overflowed the table and were searched over row ranges, range_chunks = the ranges
+                                  of each */
 #define FDR_FALLBACK_NONE 0
 #define FDR_FALLBACK_CHUNKED 1 /* the uncertified queries gathered and searched by the exact kernel, in chunks */
 #define FDR_FALLBACK_WHOLE 2   /* more than half the non-zero queries uncertified: the exact kernel for every query */
