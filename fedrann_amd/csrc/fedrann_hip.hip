@@ -9,9 +9,6 @@
 // Written for wave64 / MFMA / 160 KB LDS directly; there is no other backend.
 // ABI: include/fedrann_hip.h.  Design notes and rooflines: DESIGN.md.
 #include <hip/hip_runtime.h>
-#include <cstring>
-#include <type_traits>
-#include <utility>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_run_length_encode.hpp>
@@ -19,20 +16,22 @@
 #include <rocprim/device/device_reduce_by_key.hpp>
 
 #include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <condition_variable>
 #include <cstdarg>
-#include <limits>
-#include <string>
 #include <cstdint>
 #include <cstdio>
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <new>
-#include <atomic>
-#include <condition_variable>
 #include <functional>
+#include <limits>
 #include <mutex>
+#include <new>
+#include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/fedrann_hip.h"
@@ -407,6 +406,7 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float *__rest
 }
 
 #include "knn_plan.inc"           // shapes, LDS budgets, target segments (plain C++)
+#include "knn_workspace.inc"      // the workspace of a k-NN call: its regions, once (plain C++)
 #include "projection_tables.inc"  // the embed kernel's lookup tables (plain C++)
 #include "csr_compact.inc"        // dead-feature filter (plain C++)
 #include "host_upload.inc"        // host CSR -> device in chunks: raw over PCIe and compacted on the host at once
@@ -442,6 +442,27 @@ struct DevBuf {
         p = nullptr;
         cap = 0;
     }
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }  // (fdr_destroy has made the context's device current)
+};
+
+// What the last k-NN call did, for the fdr_last_* getters.
+struct KnnCallRecord {
+    struct {
+        int flagged = 0;               // queries that took the exact path (exact mode certifies nothing: 0)
+        int launches = 0, queues = 0;  // of the candidate pass
+    } pass;
+    int unique_targets = 0, unique_queries = 0;  // duplicate-row classes
+    // fdr_last_query_paths: per-query path codes (in that call's workspace), or one code for all rows
+    struct {
+        const uint8_t *dev = nullptr;
+        int64_t n = 0;  // 0: nothing recorded
+        uint8_t all = FDR_PATH_NONE;
+        hipStream_t stream = nullptr;
+    } paths;
+    fdr_knn_trace trace = {};  // fdr_last_knn_trace: the kernels the call ran
 };
 
 struct fdr_ctx {
@@ -479,17 +500,7 @@ struct fdr_ctx {
     // stream; fdr_timing_read() sums the elapsed times of all launches since the last read
     int knn_mode = FDR_MODE_AUTO;
     int dedup_mode = FDR_DEDUP_AUTO;
-    int last_flagged = 0;  // prefilter mode: queries of the last call that took the exact path
-    int last_unique_targets = 0, last_unique_queries = 0;  // duplicate-row classes of the last call
-    int last_pass_launches = 0, last_pass_queues = 0;      // prefilter pass of the last call
-    // fdr_last_query_paths: the last call's per-query path codes (in that call's workspace), or one code for all rows
-    struct {
-        const uint8_t *dev = nullptr;
-        int64_t n = 0;  // 0: nothing recorded
-        uint8_t all = 0;
-        hipStream_t stream = nullptr;
-    } paths;
-    fdr_knn_trace trace = {};  // fdr_last_knn_trace: the kernels the last k-NN call ran
+    KnnCallRecord last;  // what the fdr_last_* getters report
     // fdr_set_knn_capture / fdr_last_candidates / fdr_last_range_sets: the prefilter pass's intermediate results
     struct {
         int what = 0;                    // FDR_CAPTURE_* of fdr_set_knn_capture
@@ -514,6 +525,31 @@ struct fdr_ctx {
     std::vector<hipEvent_t> ev_pool[FDR_NUM_KERNELS];  // start, stop, start, stop, ...
     size_t ev_used[FDR_NUM_KERNELS] = {};
 };
+
+// Every k-NN entry point starts here, before its argument checks: no earlier call's trace, path codes or capture
+// survive it.  `pass` and the unique counts do: fdr_last_uncertified / fdr_last_prefilter_launches / fdr_last_unique
+// report the last SEARCH, also after an fdr_knn_expand_dev or a call that failed its checks.
+static void knn_call_begin(fdr_ctx *ctx) {
+    ctx->last.trace = fdr_knn_trace{};
+    ctx->last.paths = {};
+    ctx->cap.cand_valid = ctx->cap.range_valid = false;
+    ctx->cap.nq = ctx->cap.n_range = 0;
+}
+
+// the trace's header: a call of `kind` on (dp, k, nq, nt)
+static void knn_call_header(fdr_ctx *ctx, int kind, int dp, int k, int64_t nq, int64_t nt) {
+    ctx->last.trace.kind = kind;
+    ctx->last.trace.dp = dp;
+    ctx->last.trace.k = k;
+    ctx->last.trace.queries = nq;
+    ctx->last.trace.targets = nt;
+}
+// "this whole call took `path`": one code for all nq rows, no candidate pass, nothing left uncertified
+static void knn_call_whole(fdr_ctx *ctx, uint8_t path, int kind, int dp, int k, int64_t nq, int64_t nt) {
+    knn_call_header(ctx, kind, dp, k, nq, nt);
+    ctx->last.paths = {nullptr, nq, path, nullptr};
+    ctx->last.pass = {};
+}
 
 static int timing_begin(fdr_ctx *ctx, int kind, hipStream_t st) {
     if (!ctx->timing) return FDR_OK;
@@ -578,22 +614,7 @@ FDR_EXPORT int fdr_destroy(fdr_ctx *ctx) {
     if (!ctx) return FDR_OK;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    DevBuf *bufs[] = {&ctx->ftab, &ctx->crow, &ctx->ent, &ctx->a_indptr, &ctx->a_indices, &ctx->E,
-                      &ctx->Ehat, &ctx->zero, &ctx->idx, &ctx->dist, &ctx->ws,
-                      &ctx->ks_seq, &ctx->ks_off, &ctx->ks_codes, &ctx->ks_keys, &ctx->ks_vals, &ctx->ks_bloom,
-                      &ctx->ks_counter, &ctx->ks_pairs, &ctx->ks_pairs2, &ctx->ks_flag, &ctx->ks_pos,
-                      &ctx->ks_idx, &ctx->ks_rows, &ctx->ks_indptr, &ctx->ks_tmp, &ctx->kc_counts,
-                      &ctx->kc_a0, &ctx->kc_a1, &ctx->kc_c0, &ctx->kc_c1, &ctx->kc_mk, &ctx->kc_mv, &ctx->kc_rc,
-                      &ctx->cap.cand, &ctx->cap.rq, &ctx->cap.rtheta, &ctx->cap.rcnt, &ctx->cap.rrows,
-                      &ctx->sp_ip, &ctx->sp_ix, &ctx->sp_val, &ctx->sp_xhat, &ctx->sp_keys, &ctx->sp_keys2,
-                      &ctx->sp_pos, &ctx->sp_pos2, &ctx->sp_efeat, &ctx->sp_pval, &ctx->sp_runptr, &ctx->sp_heavy,
-                      &ctx->sp_cnt, &ctx->sp_tmp};
-    for (DevBuf *b : bufs) b->release();
     ctx->up_pool.stop();
-    ctx->c_indptr.release();
-    ctx->c_indices.release();
-    ctx->stage_ids.release();
-    ctx->stage_ptr.release();
     for (hipEvent_t e : ctx->up_ev)
         if (e) (void)hipEventDestroy(e);
     for (int i = 0; i < FDR_NUM_KERNELS; ++i)
@@ -617,41 +638,42 @@ FDR_EXPORT int fdr_device_info(fdr_ctx *ctx, char *buf, int buflen) {
     return FDR_OK;
 }
 
-FDR_EXPORT int fdr_last_uncertified(fdr_ctx *ctx) { return ctx ? ctx->last_flagged : 0; }
+FDR_EXPORT int fdr_last_uncertified(fdr_ctx *ctx) { return ctx ? ctx->last.pass.flagged : 0; }
 
 FDR_EXPORT int fdr_last_query_paths(fdr_ctx *ctx, uint8_t *paths, int64_t n_queries) {
     int rc = use_device(ctx);
     if (rc) return rc;
     if (!paths || n_queries <= 0) return fail(FDR_E_ARG, "last_query_paths: bad argument");
-    if (ctx->paths.n != n_queries)
+    const auto &rec = ctx->last.paths;
+    if (rec.n != n_queries)
         return fail(FDR_E_STATE, "last_query_paths: the last k-NN call recorded codes for %lld query rows, not %lld",
-                    (long long)ctx->paths.n, (long long)n_queries);
-    if (!ctx->paths.dev) {
-        memset(paths, ctx->paths.all, (size_t)n_queries);
+                    (long long)rec.n, (long long)n_queries);
+    if (!rec.dev) {
+        memset(paths, rec.all, (size_t)n_queries);
         return FDR_OK;
     }
-    HIP_TRY(hipMemcpyAsync(paths, ctx->paths.dev, (size_t)n_queries, hipMemcpyDeviceToHost, ctx->paths.stream));
-    HIP_TRY(hipStreamSynchronize(ctx->paths.stream));
+    HIP_TRY(hipMemcpyAsync(paths, rec.dev, (size_t)n_queries, hipMemcpyDeviceToHost, rec.stream));
+    HIP_TRY(hipStreamSynchronize(rec.stream));
     return FDR_OK;
 }
 
 FDR_EXPORT int fdr_last_unique(fdr_ctx *ctx, int *unique_targets, int *unique_queries) {
     if (!ctx || !unique_targets || !unique_queries) return fail(FDR_E_ARG, "bad argument");
-    *unique_targets = ctx->last_unique_targets;
-    *unique_queries = ctx->last_unique_queries;
+    *unique_targets = ctx->last.unique_targets;
+    *unique_queries = ctx->last.unique_queries;
     return FDR_OK;
 }
 
 FDR_EXPORT int fdr_last_prefilter_launches(fdr_ctx *ctx, int *launches, int *queues) {
     if (!ctx || !launches || !queues) return fail(FDR_E_ARG, "bad argument");
-    *launches = ctx->last_pass_launches;
-    *queues = ctx->last_pass_queues;
+    *launches = ctx->last.pass.launches;
+    *queues = ctx->last.pass.queues;
     return FDR_OK;
 }
 
 FDR_EXPORT int fdr_last_knn_trace(fdr_ctx *ctx, fdr_knn_trace *out) {
     if (!ctx || !out) return fail(FDR_E_ARG, "bad argument");
-    *out = ctx->trace;
+    *out = ctx->last.trace;
     return FDR_OK;
 }
 
@@ -693,16 +715,6 @@ FDR_EXPORT int fdr_last_range_sets(fdr_ctx *ctx, int64_t n_range, int32_t *queri
     for (int64_t i = 0; i < n_range; ++i)  // (the slots the pass did not fill hold whatever the workspace held)
         for (int m = std::max(0, std::min(counts[i], RANGE_CAP)); m < RANGE_CAP; ++m) rows[i * RANGE_CAP + m] = -1;
     return FDR_OK;
-}
-
-// Every k-NN entry point starts here, before its argument checks: no earlier call's trace or path codes survive it.
-static void knn_call_begin(fdr_ctx *ctx) {
-    ctx->trace = fdr_knn_trace{};
-    ctx->cap.cand_valid = ctx->cap.range_valid = false;
-    ctx->cap.nq = ctx->cap.n_range = 0;
-    ctx->paths.dev = nullptr;
-    ctx->paths.n = 0;
-    ctx->paths.all = FDR_PATH_NONE;
 }
 
 FDR_EXPORT int fdr_set_knn_mode(fdr_ctx *ctx, int mode) {
@@ -862,95 +874,29 @@ static int launch_normalize(fdr_ctx *ctx, const float *d_E, int64_t n_rows, int 
     return timing_end(ctx, FDR_KERNEL_NORMALIZE, st);
 }
 
-static size_t knn_workspace_bytes_impl(const fdr_ctx *ctx, int64_t nq, int64_t nt, int d, int k);
-
-// ---- prefilter mode: workspace layout -------------------------------------------------------
-// mode: FDR_MODE_AUTO uses the fp16 prefilter whenever it applies (d <= 128, k + 8 <= 64) and the
-// target set is large enough to pay for it; FDR_KNN_MODE=exact|prefilter|auto overrides the context.
-static bool knn_prefilter_wanted(const fdr_ctx *ctx, int dp, int64_t nt, int k) {
-    const int mode = ctx->knn_mode;
-    if (mode == FDR_MODE_EXACT) return false;
-    const int kp = (k + prefilter_extra(k) + 1) & ~1;
-    if (!(kp <= FDR_FAST_MAX_K && nt >= kp)) return false;
-    if (nt > (int64_t)FDR_MAX_SEG << FDR_PREFILTER_MAX_IB) return false;  // segments too long for the keys
-    return mode == FDR_MODE_PREFILTER || nt >= 8192;
+// ---- k-NN workspaces (knn_workspace.inc): what rocprim asks for, the context's view ---------------------------------
+static size_t order_sort_tmp_bytes(size_t rows) {
+    size_t t = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, t, (u64 *)nullptr, (u64 *)nullptr, (int *)nullptr, (int *)nullptr, rows, 0, 40,
+                                    (hipStream_t) nullptr);
+    return t;
 }
-
-struct PrefilterLayout {
-    int kp, chunk;
-    size_t knn_bytes;  // region shared (in stream order) by the prefilter pass and the exact passes
-    size_t off_ht, off_hq, off_cand, off_counter, off_flagged, off_qc, off_qzc, off_idxc, off_distc;
-    size_t off_rlist, off_theta, off_hqc, off_thetac, off_cnt, off_rcand, total;  // range pass
-    size_t off_path;  // per-query path codes (fdr_last_query_paths)
-    int rchunk;
-    int ordered;  // ordered scan possible: sort keys, order tables, ordered fp16 copies
-    size_t off_okeys, off_okeys_s, off_ovals, off_perm_t, off_perm_q, off_ho_t, off_ho_q, off_otmp, otmp_bytes;
-};
-
-static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
-static PrefilterLayout prefilter_layout(const fdr_ctx *ctx, int64_t nq, int64_t nt, int d, int k) {
-    PrefilterLayout L;
-    L.kp = (k + prefilter_extra(k) + 1) & ~1;
-    L.chunk = (int)std::min<int64_t>(nq, 16384);
-    const size_t exact_all = knn_plan(ctx->num_cus, nq, nt, d, k).total_bytes;
-    const int dp = fdr_padded_dim(d);
-    const KnnPlan pp = knn_plan(ctx->num_cus, nq, nt, d, L.kp, prefilter_shape(dp, L.kp, nq, ctx->num_cus, nt));
-    // (a later call on fewer unique rows may plan more, shorter segments: room for the largest such plan)
-    // (the bound words and the lists padded for the widest query block: a later call may choose the other shape)
-    const size_t pre = std::max(pp.total_bytes, pp.bits_bytes + align256((size_t)(nq + 512) * 4) +
-                                                    prefilter_partial_bound(nq, nt, L.kp, pp.qw));
-    // any exact plan for <= chunk queries: bits + bound words + at most FDR_MAX_SEG segments of lists
-    const size_t chunk_bound = align256((size_t)((nt + 31) / 32) * 4) + align256((size_t)(L.chunk + 128) * 4) +
-                               (size_t)FDR_MAX_SEG * (L.chunk + 128) * (size_t)k * 8;
-    L.knn_bytes = align256(std::max(exact_all, std::max(pre, chunk_bound)));
-    size_t o = L.knn_bytes;
-    L.off_ht = o;       o += align256((size_t)nt * dp * 2);
-    L.off_hq = o;       o += align256((size_t)nq * dp * 2);
-    L.off_cand = o;     o += align256((size_t)nq * L.kp * 8);
-    L.off_counter = o;  o += 1024;  // [0] exact list, [1] all-zero queries, [2] range list; zero answer at +256 / +512
-    L.off_flagged = o;  o += align256((size_t)nq * 4);
-    L.off_qc = o;       o += align256((size_t)L.chunk * dp * 4);
-    L.off_qzc = o;      o += align256((size_t)L.chunk);
-    L.off_idxc = o;     o += align256((size_t)L.chunk * k * 4);
-    L.off_distc = o;    o += align256((size_t)L.chunk * k * 4);
-    L.rchunk = (int)std::min<int64_t>(nq, 32768);  // range pass: queries per launch
-    L.off_rlist = o;    o += align256((size_t)nq * 4);
-    L.off_theta = o;    o += align256((size_t)nq * 4);
-    L.off_hqc = o;      o += align256((size_t)L.rchunk * dp * 2);
-    L.off_thetac = o;   o += align256((size_t)L.rchunk * 4);
-    L.off_cnt = o;      o += align256((size_t)L.rchunk * 4);
-    L.off_rcand = o;    o += align256((size_t)L.rchunk * RANGE_CAP * 4);
-    L.off_path = o;     o += align256((size_t)nq);
-    L.ordered = pp.cohort > 0 || dev_knobs().ordered != 0;  // (the sizes at which the pass runs in synchronised rounds)
-    L.off_okeys = L.off_okeys_s = L.off_ovals = L.off_perm_t = L.off_perm_q = L.off_ho_t = L.off_ho_q = 0;
-    L.off_otmp = L.otmp_bytes = 0;
-    if (L.ordered) {
-        const size_t nmax = (size_t)std::max(nq, nt);  // (the keys / sort scratch serve the targets, then the queries)
-        L.off_okeys = o;    o += align256(nmax * 8);
-        L.off_okeys_s = o;  o += align256(nmax * 8);
-        L.off_ovals = o;    o += align256(nmax * 4);
-        L.off_perm_t = o;   o += align256((size_t)nt * 4);
-        L.off_perm_q = o;   o += align256((size_t)nq * 4);
-        L.off_ho_t = o;     o += align256((size_t)nt * dp * 2);
-        L.off_ho_q = o;     o += align256((size_t)nq * dp * 2);
-        size_t t_sort = 0;
-        (void)rocprim::radix_sort_pairs(nullptr, t_sort, (u64 *)nullptr, (u64 *)nullptr, (int *)nullptr, (int *)nullptr,
-                                        nmax, 0, 40, (hipStream_t) nullptr);
-        L.otmp_bytes = align256(t_sort);
-        L.off_otmp = o;     o += L.otmp_bytes;
-    }
-    L.total = o;
-    return L;
+static size_t class_tables_tmp_bytes(size_t rows) {
+    size_t t_sort = 0, t_scan = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, t_sort, (u64 *)nullptr, (u64 *)nullptr, (int *)nullptr, (int *)nullptr, rows, 0,
+                                    64, (hipStream_t) nullptr);
+    (void)rocprim::inclusive_scan(nullptr, t_scan, (int *)nullptr, (int *)nullptr, rows, rocprim::plus<int>(),
+                                  (hipStream_t) nullptr);
+    return std::max(t_sort, t_scan);
+}
+static WsEnv ws_env(const fdr_ctx *ctx) {
+    return {ctx->num_cus, ctx->knn_mode, ctx->dedup_mode, order_sort_tmp_bytes, class_tables_tmp_bytes};
 }
 
 FDR_EXPORT size_t fdr_knn_workspace_bytes(fdr_ctx *ctx, int64_t nq, int64_t nt, int32_t d,
                                           int32_t k) {
     if (!ctx || nq <= 0 || nt <= 0 || k <= 0 || k > FDR_MAX_K || fdr_padded_dim(d) < 0) return 0;
-    const int route = knn_route(fdr_padded_dim(d), k, nt);
-    if (route == FDR_ROUTE_GENERIC) return 256;  // (the generic kernel needs no scratch)
-    if (route == FDR_ROUTE_WIDE) return knn_plan(ctx->num_cus, nq, nt, d, k).total_bytes;  // (the exact pass alone)
-    return knn_workspace_bytes_impl(ctx, nq, nt, d, k);
+    return knn_workspace_bytes(ws_env(ctx), nq, nt, d, k);
 }
 
 // ---- the kernels of kShapes (knn_plan.inc) ---------------------------------------------------------------------------
@@ -1068,20 +1014,29 @@ static int launch_rounds(fdr_ctx *ctx, const KnnPlan &p, int max_queues, int kin
     return one_span ? timing_end(ctx, kind, st) : FDR_OK;
 }
 
+// The argument checks of a k-NN call, before anything is routed or recorded.  (The workspace's SIZE is checked by the
+// path that lays it out.)  Returns FDR_OK for nq == 0 whatever the pointers: the callers launch nothing then.
+static int check_knn_args(const float *d_Qhat, const uint8_t *d_qzero, int64_t nq, const float *d_That,
+                          const uint8_t *d_tzero, int64_t nt, int64_t t_base, int d, int k, const int32_t *d_idx,
+                          const float *d_dist, const void *d_ws) {
+    const int dp = fdr_padded_dim(d);
+    if (dp < 0) return fail(FDR_E_ARG, "knn: dimension %d unsupported (1..%d)", d, FDR_MAX_DIM);
+    if (k < 1 || k > FDR_MAX_K) return fail(FDR_E_ARG, "knn: k=%d, d=%d outside the MFMA kernels' shapes", k, d);
+    if (nq < 0 || nt < k) return fail(FDR_E_ARG, "knn: need n_targets (%lld) >= k (%d)", (long long)nt, k);
+    if (nt + t_base > 0x7fffffffll || nq > 0x7fffffffll) return fail(FDR_E_ARG, "knn: row numbers exceed int32");
+    if (nq == 0) return FDR_OK;
+    const bool need_ws = knn_route(dp, k, nt) != FDR_ROUTE_GENERIC;  // (the generic kernel needs no scratch)
+    if (!d_Qhat || !d_qzero || !d_That || !d_tzero || !d_idx || !d_dist || (need_ws && !d_ws))
+        return fail(FDR_E_ARG, "knn: null device pointer");
+    return FDR_OK;
+}
+static_assert(FDR_MAX_K == FDR_EXACT_MAX_K, "every k the generic kernel takes, the exact MFMA pass takes from 8192 targets");
+
 static int launch_knn_exact(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero, int64_t nq,
                       const float *d_That, const uint8_t *d_tzero, int64_t nt, int64_t t_base,
                       int d, int k, int32_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes,
                       hipStream_t st) {
-    const int dp = fdr_padded_dim(d);
-    if (dp < 0) return fail(FDR_E_ARG, "knn: dimension %d unsupported (1..%d)", d, FDR_MAX_DIM);
-    if (k < 1 || k > FDR_EXACT_MAX_K || dp > FDR_EXACT_MAX_DIM)
-        return fail(FDR_E_ARG, "knn: k=%d, d=%d outside the MFMA kernels' shapes", k, d);
-    if (nq < 0 || nt < k) return fail(FDR_E_ARG, "knn: need n_targets (%lld) >= k (%d)", (long long)nt, k);
-    if (nt + t_base > 0x7fffffffll || nq > 0x7fffffffll)
-        return fail(FDR_E_ARG, "knn: row numbers exceed int32");
-    if (nq == 0) return FDR_OK;
-    if (!d_Qhat || !d_qzero || !d_That || !d_tzero || !d_idx || !d_dist || !d_ws)
-        return fail(FDR_E_ARG, "knn: null device pointer");
+    if (nq == 0) return FDR_OK;  // (an empty call is recorded as an exact one and launches nothing)
     const KnnPlan p = knn_plan(ctx->num_cus, nq, nt, d, k);
     if (ws_bytes < p.total_bytes)
         return fail(FDR_E_ARG, "knn: workspace %zu < required %zu bytes", ws_bytes, p.total_bytes);
@@ -1096,11 +1051,11 @@ static int launch_knn_exact(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_
     const KnnShape &sh = kShapes[p.shape];
     const size_t lds = knn_lds_bytes(sh, k);
     if (lds > 160 * 1024) return fail(FDR_E_ARG, "knn: k=%d, d=%d needs %zu B of LDS (> 160 KiB)", k, d, lds);
-    ctx->trace.exact_calls++;
-    ctx->trace.exact_queries += (int32_t)nq;
-    ctx->trace.exact_waves = sh.nw;
-    ctx->trace.exact_qsets = sh.nq;
-    ctx->trace.exact_segments = p.nseg;
+    ctx->last.trace.exact_calls++;
+    ctx->last.trace.exact_queries += (int32_t)nq;
+    ctx->last.trace.exact_waves = sh.nw;
+    ctx->last.trace.exact_qsets = sh.nq;
+    ctx->last.trace.exact_segments = p.nseg;
     const int dbg = dev_knobs().debug;  // (development builds only; 0 in the release library)
     (void)dbg;
     const int qcap = knn_qcap(sh, k);
@@ -1140,36 +1095,20 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
                                 hipStream_t st) {
     // the queries ARE the targets (row i of one is row i of the other): one fp16 copy serves both sides
     const bool self = d_Qhat == d_That && d_qzero == d_tzero && nq == nt;
-    const PrefilterLayout L = prefilter_layout(ctx, nq, nt, d, k);
+    const PrefilterWs L = prefilter_ws(ws_env(ctx), d_ws, nq, nt, d, k);
     if (ws_bytes < L.total)
         return fail(FDR_E_ARG, "knn: workspace %zu < required %zu bytes", ws_bytes, L.total);
-    char *ws = static_cast<char *>(d_ws);
-    _Float16 *d_ht = reinterpret_cast<_Float16 *>(ws + L.off_ht);
-    _Float16 *d_hq = self ? d_ht : reinterpret_cast<_Float16 *>(ws + L.off_hq);
-    u64 *d_cand = reinterpret_cast<u64 *>(ws + L.off_cand);
-    int *d_counter = reinterpret_cast<int *>(ws + L.off_counter);
-    int *d_flagged = reinterpret_cast<int *>(ws + L.off_flagged);
-    float *d_qc = reinterpret_cast<float *>(ws + L.off_qc);
-    uint8_t *d_qzc = reinterpret_cast<uint8_t *>(ws + L.off_qzc);
-    int32_t *d_idxc = reinterpret_cast<int32_t *>(ws + L.off_idxc);
-    float *d_distc = reinterpret_cast<float *>(ws + L.off_distc);
+    _Float16 *const d_ht = L.ht, *const d_hq = self ? L.ht : L.hq;
     const int kp = L.kp;
-    uint8_t *d_path = reinterpret_cast<uint8_t *>(ws + L.off_path);
-    ctx->paths.dev = d_path;
-    ctx->paths.n = nq;
-    ctx->paths.stream = st;
-
     const int dp = fdr_padded_dim(d);
+    knn_call_header(ctx, FDR_TRACE_PREFILTER, dp, k, nq, nt);
+    ctx->last.paths = {L.path, nq, FDR_PATH_NONE, st};  // (per query: the re-rank kernels write the codes)
+
     const int pshape = prefilter_shape(dp, kp, nq, ctx->num_cus, nt);
     const KnnPlan p = knn_plan(ctx->num_cus, nq, nt, d, kp, pshape);
     const KnnShape &sh = kShapes[pshape];
-    fdr_knn_trace &tr = ctx->trace;
-    tr.kind = FDR_TRACE_PREFILTER;
-    tr.dp = dp;
-    tr.k = k;
+    fdr_knn_trace &tr = ctx->last.trace;
     tr.kp = kp;
-    tr.queries = nq;
-    tr.targets = nt;
     tr.pass_waves = sh.nw;
     tr.pass_wps = sh.wps;
     tr.pass_units = sh.tps;
@@ -1178,9 +1117,9 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     tr.pass_segments = p.nseg;
     const PassKernel kern = KnnKernels::pass[pshape][kp > 32];
     if (!kern) return no_kernel(pshape);
-    unsigned *d_bits = reinterpret_cast<unsigned *>(ws);
-    unsigned *d_shared = reinterpret_cast<unsigned *>(ws + p.bits_bytes);
-    u64 *d_partial = reinterpret_cast<u64 *>(ws + p.bits_bytes + p.shared_bytes);
+    unsigned *d_bits = reinterpret_cast<unsigned *>(L.knn);  // (the plan's regions, as in launch_knn_exact)
+    unsigned *d_shared = reinterpret_cast<unsigned *>(L.knn + p.bits_bytes);
+    u64 *d_partial = reinterpret_cast<u64 *>(L.knn + p.bits_bytes + p.shared_bytes);
 
     int trc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, st);  // conversion + set-up count as "rerank"
     if (trc) return trc;
@@ -1196,16 +1135,13 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     OrderArgs ord = {nullptr, nullptr};
     const _Float16 *p1_q = d_hq, *p1_t = d_ht;  // what the candidate pass streams
     if (L.ordered) {
-        u64 *okeys = reinterpret_cast<u64 *>(ws + L.off_okeys), *okeys_s = reinterpret_cast<u64 *>(ws + L.off_okeys_s);
-        int *ovals = reinterpret_cast<int *>(ws + L.off_ovals);
-        int *perm_t = reinterpret_cast<int *>(ws + L.off_perm_t), *perm_q = reinterpret_cast<int *>(ws + L.off_perm_q);
-        _Float16 *ho_t = reinterpret_cast<_Float16 *>(ws + L.off_ho_t);
-        _Float16 *ho_q = self ? ho_t : reinterpret_cast<_Float16 *>(ws + L.off_ho_q);
+        _Float16 *const ho_t = L.ho_t, *const ho_q = self ? L.ho_t : L.ho_q;
+        int *const perm_t = L.perm_t, *const perm_q = L.perm_q;
         auto order = [&](const float *X, int64_t n, int *perm, _Float16 *out) -> int {
             hipLaunchKernelGGL(row_chunk_keys_kernel, dim3((unsigned)(((size_t)n * 16 + 255) / 256)), dim3(256), 0, st, X,
-                               (int)n, dp, okeys, ovals);
+                               (int)n, dp, L.okeys, L.ovals);
             size_t tb = L.otmp_bytes;
-            HIP_TRY(rocprim::radix_sort_pairs(ws + L.off_otmp, tb, okeys, okeys_s, ovals, perm, (size_t)n, 0, 40, st));
+            HIP_TRY(rocprim::radix_sort_pairs(L.otmp, tb, L.okeys, L.okeys_s, L.ovals, perm, (size_t)n, 0, 40, st));
             const long long groups = (long long)n * (dp / 8);
             hipLaunchKernelGGL(to_half_ordered_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, X,
                                (const int *)perm, groups, dp / 8, out);
@@ -1235,8 +1171,8 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
         hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh.nw), lds, s, p1_q, (int)nq, p1_t, (int)nt, (int)t_base, p.segs, kp,
                            p.nq_pad, d_partial, d_shared, ib, base, p.nqb, ord FDR_DBG_ARG(pdbg));
     });
-    ctx->last_pass_launches = r.launches;
-    ctx->last_pass_queues = r.queues;
+    ctx->last.pass.launches = r.launches;
+    ctx->last.pass.queues = r.queues;
     tr.pass_launches = r.launches;
     tr.pass_queues = r.queues;
     if (lrc) return lrc;
@@ -1272,55 +1208,46 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
     const int64_t mq = p.nseg * kp <= 64 ? 4 * MERGE_QPW : 4;  // queries per workgroup of knn_merge_keys_kernel
     hipLaunchKernelGGL(knn_merge_keys_kernel, dim3((unsigned)((nq + mq - 1) / mq)), dim3(256), 0, st,
-                       (const u64 *)d_partial, p.nseg, (int)nq, p.nq_pad, kp, d_cand);
+                       (const u64 *)d_partial, p.nseg, (int)nq, p.nq_pad, kp, L.cand);
     HIP_TRY(hipGetLastError());
     if (ctx->cap.what & FDR_CAPTURE_CANDIDATES) {  // (test support: fdr_last_candidates)
         if ((trc = ctx->cap.cand.reserve((size_t)nq * kp * 8))) return trc;
-        HIP_TRY(hipMemcpyAsync(ctx->cap.cand.p, d_cand, (size_t)nq * kp * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->cap.cand.p, L.cand, (size_t)nq * kp * 8, hipMemcpyDeviceToDevice, st));
         ctx->cap.nq = nq;
         ctx->cap.kp = kp;
         ctx->cap.qbits = std::min(20, 32 - ib);
         ctx->cap.stream = st;
         ctx->cap.cand_valid = true;
     }
-    HIP_TRY(hipMemsetAsync(d_counter, 0, 16, st));
-    int *d_rlist = reinterpret_cast<int *>(ws + L.off_rlist);
-    float *d_theta = reinterpret_cast<float *>(ws + L.off_theta);
+    HIP_TRY(hipMemsetAsync(L.counter, 0, 16, st));
     const float margin = 2.0f * prefilter_eps(ib) + 4.0e-7f;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_rerank_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, RERANK_LDS_BYTES));
     hipLaunchKernelGGL(knn_rerank_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), RERANK_LDS_BYTES, st,
-                       (const u64 *)d_cand, kp, k, d_Qhat, d_qzero, d_That, (int)nq, dp, (int)t_base, margin,
-                       d_idx, d_dist, d_counter, d_flagged, d_rlist, d_theta, d_path);
-    {   // all-zero queries share one closed-form answer (their number is only known on the device yet)
-        int *d_zidx = d_counter + 64;
-        float *d_zdist = reinterpret_cast<float *>(d_counter + 128);
-        hipLaunchKernelGGL(zero_answer_kernel, dim3(1), dim3(1024), 0, st, (const unsigned *)d_bits, (int)nt,
-                           (int)t_base, k, d_zidx, d_zdist);
-        hipLaunchKernelGGL(scatter_zero_answer_kernel, dim3((unsigned)(((int64_t)nq * k + 255) / 256)),
-                           dim3(256), 0, st, (const int *)d_zidx, (const float *)d_zdist,
-                           (const int *)d_flagged, (int)nq, (const int *)d_counter, k, d_idx, d_dist);
-    }
+                       (const u64 *)L.cand, kp, k, d_Qhat, d_qzero, d_That, (int)nq, dp, (int)t_base, margin,
+                       d_idx, d_dist, L.counter, L.flagged, L.rlist, L.theta, L.path);
+    // all-zero queries share one closed-form answer (their number is only known on the device yet)
+    hipLaunchKernelGGL(zero_answer_kernel, dim3(1), dim3(1024), 0, st, (const unsigned *)d_bits, (int)nt,
+                       (int)t_base, k, L.zidx, L.zdist);
+    hipLaunchKernelGGL(scatter_zero_answer_kernel, dim3((unsigned)(((int64_t)nq * k + 255) / 256)),
+                       dim3(256), 0, st, (const int *)L.zidx, (const float *)L.zdist,
+                       (const int *)L.flagged, (int)nq, (const int *)L.counter, k, d_idx, d_dist);
     HIP_TRY(hipGetLastError());
     if ((trc = timing_end(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
 
     // how many queries could not be certified / are all-zero / need a range pass?  (one 12-byte
     // read-back; the passes below are sized from it)
     int counts[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(counts, d_counter, 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(counts, L.counter, 12, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     int count = counts[0];
     const int zcount = counts[1], rcount = counts[2];
-    ctx->last_flagged = count + rcount;
+    ctx->last.pass.flagged = count + rcount;
     tr.uncertified = count;
     tr.zero_queries = zcount;
     tr.range_queries = rcount;
     if (rcount > 0) {  // plateau queries: collect {d~ <= theta} with a second fp16 pass, rank it exactly
         if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
-        _Float16 *d_hqc = reinterpret_cast<_Float16 *>(ws + L.off_hqc);
-        float *d_thetac = reinterpret_cast<float *>(ws + L.off_thetac);
-        int *d_cnt = reinterpret_cast<int *>(ws + L.off_cnt);
-        int *d_rcand = reinterpret_cast<int *>(ws + L.off_rcand);
         const bool rcap = ctx->cap.what & FDR_CAPTURE_RANGE;  // (test support: fdr_last_range_sets)
         if (rcap) {
             if ((trc = ctx->cap.rq.reserve((size_t)rcount * 4)) || (trc = ctx->cap.rtheta.reserve((size_t)rcount * 4)) ||
@@ -1331,8 +1258,8 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
         for (int first = 0; first < rcount; first += L.rchunk) {
             const int c = std::min(L.rchunk, rcount - first);
             hipLaunchKernelGGL(gather_half_queries_kernel, dim3((unsigned)c), dim3(256), 0, st,
-                               (const _Float16 *)d_hq, (const float *)d_theta, (const int *)d_rlist, first, c,
-                               dp, d_hqc, d_thetac, d_cnt);
+                               (const _Float16 *)d_hq, (const float *)L.theta, (const int *)L.rlist, first, c,
+                               dp, L.hqc, L.thetac, L.cnt);
             HIP_TRY(hipGetLastError());
             const int rs = range_shape(dp, c, rcount);
             const KnnShape &rsh = kShapes[rs];
@@ -1342,8 +1269,8 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
             const size_t rlds = knn_lds_bytes(rsh, 1) + (size_t)RANGE_LANE_BUF * 64 * rsh.nw * 4;  // ring + lane buffers
             if (rsh.family == FDR_FAM_RANGE_PP)
                 HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(rk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
-            hipLaunchKernelGGL(rk, dim3((unsigned)rp.nqb, (unsigned)rp.nseg), dim3(64 * rsh.nw), rlds, st, (const _Float16 *)d_hqc,
-                               (const float *)d_thetac, c, (const _Float16 *)d_ht, (int)nt, (int)t_base, rp.segs, d_cnt, d_rcand);
+            hipLaunchKernelGGL(rk, dim3((unsigned)rp.nqb, (unsigned)rp.nseg), dim3(64 * rsh.nw), rlds, st, (const _Float16 *)L.hqc,
+                               (const float *)L.thetac, c, (const _Float16 *)d_ht, (int)nt, (int)t_base, rp.segs, L.cnt, L.rcand);
             HIP_TRY(hipGetLastError());
             tr.range_chunks++;
             tr.range_pp_chunks += rsh.family == FDR_FAM_RANGE_PP;
@@ -1351,15 +1278,15 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
             if (rcap) {
                 char *cq = static_cast<char *>(ctx->cap.rq.p), *cth = static_cast<char *>(ctx->cap.rtheta.p);
                 char *cc = static_cast<char *>(ctx->cap.rcnt.p), *cr = static_cast<char *>(ctx->cap.rrows.p);
-                HIP_TRY(hipMemcpyAsync(cq + (size_t)first * 4, d_rlist + first, (size_t)c * 4, hipMemcpyDeviceToDevice, st));
-                HIP_TRY(hipMemcpyAsync(cth + (size_t)first * 4, d_thetac, (size_t)c * 4, hipMemcpyDeviceToDevice, st));
-                HIP_TRY(hipMemcpyAsync(cc + (size_t)first * 4, d_cnt, (size_t)c * 4, hipMemcpyDeviceToDevice, st));
-                HIP_TRY(hipMemcpyAsync(cr + (size_t)first * RANGE_CAP * 4, d_rcand, (size_t)c * RANGE_CAP * 4,
+                HIP_TRY(hipMemcpyAsync(cq + (size_t)first * 4, L.rlist + first, (size_t)c * 4, hipMemcpyDeviceToDevice, st));
+                HIP_TRY(hipMemcpyAsync(cth + (size_t)first * 4, L.thetac, (size_t)c * 4, hipMemcpyDeviceToDevice, st));
+                HIP_TRY(hipMemcpyAsync(cc + (size_t)first * 4, L.cnt, (size_t)c * 4, hipMemcpyDeviceToDevice, st));
+                HIP_TRY(hipMemcpyAsync(cr + (size_t)first * RANGE_CAP * 4, L.rcand, (size_t)c * RANGE_CAP * 4,
                                        hipMemcpyDeviceToDevice, st));
             }
             hipLaunchKernelGGL(knn_rerank_long_kernel, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st,
-                               (const int *)(d_rlist + first), c, (const int *)d_cnt, (const int *)d_rcand, k,
-                               d_Qhat, d_That, dp, (int)t_base, d_idx, d_dist, d_counter, d_flagged, d_path);
+                               (const int *)(L.rlist + first), c, (const int *)L.cnt, (const int *)L.rcand, k,
+                               d_Qhat, d_That, dp, (int)t_base, d_idx, d_dist, L.counter, L.flagged, L.path);
             HIP_TRY(hipGetLastError());
         }
         if (rcap) {
@@ -1368,7 +1295,7 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
         }
         if ((trc = timing_end(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
         // ranges that overflowed were appended to the exact list: read its final length
-        HIP_TRY(hipMemcpyAsync(counts, d_counter, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(counts, L.counter, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         tr.range_overflow = counts[0] - count;
         count = counts[0];
@@ -1377,8 +1304,8 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     if ((int64_t)count * 2 > nq - zcount) {  // the prefilter did not help on this input: exact pass for everyone
         tr.exact_fallback = FDR_FALLBACK_WHOLE;
         // every row, the all-zero ones too, is recomputed by the exact kernel: its code, as in exact mode
-        ctx->paths.dev = nullptr;
-        ctx->paths.all = FDR_PATH_EXACT;
+        // (the trace stays a prefilter trace, and the pass's launches and uncertified count stand)
+        ctx->last.paths = {nullptr, nq, FDR_PATH_EXACT, nullptr};
         return launch_knn_exact(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist,
                                 d_ws, L.knn_bytes, st);
     }
@@ -1386,129 +1313,93 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     for (int first = 0; first < count; first += L.chunk) {
         const int c = std::min(L.chunk, count - first);
         hipLaunchKernelGGL(gather_queries_kernel, dim3((unsigned)c), dim3(256), 0, st, d_Qhat, d_qzero,
-                           (const int *)d_flagged, first, c, dp, d_qc, d_qzc);
+                           (const int *)L.flagged, first, c, dp, L.qc, L.qzc);
         HIP_TRY(hipGetLastError());
-        int rc = launch_knn_exact(ctx, d_qc, d_qzc, c, d_That, d_tzero, nt, t_base, d, k, d_idxc, d_distc,
+        int rc = launch_knn_exact(ctx, L.qc, L.qzc, c, d_That, d_tzero, nt, t_base, d, k, L.idxc, L.distc,
                                   d_ws, L.knn_bytes, st);
         if (rc) return rc;
         hipLaunchKernelGGL(scatter_results_kernel, dim3((unsigned)(((int64_t)c * k + 255) / 256)), dim3(256),
-                           0, st, (const int *)d_idxc, (const float *)d_distc, (const int *)d_flagged, first,
+                           0, st, (const int *)L.idxc, (const float *)L.distc, (const int *)L.flagged, first,
                            c, k, d_idx, d_dist);
         HIP_TRY(hipGetLastError());
     }
     return FDR_OK;
 }
 
-static size_t knn_mode_workspace_bytes(const fdr_ctx *ctx, int64_t nq, int64_t nt, int d, int k) {
-    if (knn_prefilter_wanted(ctx, fdr_padded_dim(d), nt, k)) return prefilter_layout(ctx, nq, nt, d, k).total;
-    return knn_plan(ctx->num_cus, nq, nt, d, k).total_bytes;
-}
-
 static int launch_knn_mode(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero, int64_t nq,
                            const float *d_That, const uint8_t *d_tzero, int64_t nt, int64_t t_base, int d,
                            int k, int32_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes, hipStream_t st) {
     const int dp = fdr_padded_dim(d);
-    if (dp > 0 && k >= 1 && knn_route(dp, k, nt) == FDR_ROUTE_FAST && nq > 0 && nt >= k && knn_prefilter_wanted(ctx, dp, nt, k) &&
-        d_Qhat && d_qzero && d_That && d_tzero && d_idx && d_dist && d_ws) {
+    if (knn_route(dp, k, nt) == FDR_ROUTE_FAST && nq > 0 && knn_prefilter_wanted(ctx->knn_mode, nt, k)) {
         const int rc = launch_knn_prefilter(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx,
                                             d_dist, d_ws, ws_bytes, st);
         if (rc) ctx->cap.cand_valid = ctx->cap.range_valid = false;  // (a failed call leaves no capture)
         return rc;
     }
-    ctx->last_flagged = 0;  // (exact mode certifies nothing)
-    ctx->last_pass_launches = ctx->last_pass_queues = 0;
-    ctx->paths.dev = nullptr;
-    ctx->paths.n = nq;
-    ctx->paths.all = FDR_PATH_EXACT;
-    ctx->trace.kind = FDR_TRACE_EXACT;
-    ctx->trace.dp = dp;
-    ctx->trace.k = k;
-    ctx->trace.queries = nq;
-    ctx->trace.targets = nt;
+    knn_call_whole(ctx, FDR_PATH_EXACT, FDR_TRACE_EXACT, dp, k, nq, nt);
     return launch_knn_exact(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist,
                             d_ws, ws_bytes, st);
 }
 
 // ---- duplicate-row classes: search unique queries x unique targets, expand --------------------
-struct DedupLayout {
-    size_t inner_bytes;  // workspace of the inner k-NN call (sized for the un-deduplicated problem)
-    size_t off_hash, off_hash_s, off_idx, off_idx_s, off_flag, off_cid, off_cls, off_cstart, off_isrep,
-        off_upos, off_uofc, off_cofu, off_uqflag, off_uqpos, off_U, off_uzero, off_Uq, off_uqz, off_idxu,
-        off_distu, off_rowpath, off_tmp, tmp_bytes, total;
-};
-
-#define FDR_DEDUP_PROBE_BELOW (1 << 18)
-static bool knn_dedup_wanted(const fdr_ctx *ctx, int64_t nq, int64_t nt) {
-    if (ctx->dedup_mode != FDR_DEDUP_AUTO) return ctx->dedup_mode != FDR_DEDUP_OFF;
-    return nt >= 8192 && nq >= 1024;  // (from the size at which the prefilter mode engages)
+// Queues the class tables of the n target rows that hash_rows_kernel has hashed into W.hash / W.idx: sort -> class
+// starts -> scan -> class tables -> scan -> unique tables.  No synchronise; W.cid[n - 1] is then the number of classes.
+// The one builder: the ranks of a row-sharded run (fdr_knn_classes_dev) and a plain call get the same tables from the
+// same rows.
+static int queue_class_tables(const DedupWs &W, const float *d_That, int n, int dp, hipStream_t st) {
+    const unsigned g1 = (unsigned)((n + 255) / 256);
+    size_t tb = W.tmp_bytes;
+    HIP_TRY(rocprim::radix_sort_pairs(W.tmp, tb, W.hash, W.hash_s, W.idx, W.idx_s, (size_t)n, 0, 64, st));
+    hipLaunchKernelGGL(mark_class_starts_kernel, dim3(g1), dim3(256), 0, st, d_That, n, dp, (const u64 *)W.hash_s,
+                       (const int *)W.idx_s, W.flag);
+    tb = W.tmp_bytes;
+    HIP_TRY(rocprim::inclusive_scan(W.tmp, tb, W.flag, W.cid, (size_t)n, rocprim::plus<int>(), st));
+    hipLaunchKernelGGL(class_tables_kernel, dim3(g1), dim3(256), 0, st, n, (const int *)W.flag, (const int *)W.cid,
+                       (const int *)W.idx_s, W.cls, W.cstart, W.isrep);
+    tb = W.tmp_bytes;
+    HIP_TRY(rocprim::inclusive_scan(W.tmp, tb, W.isrep, W.upos, (size_t)n, rocprim::plus<int>(), st));
+    hipLaunchKernelGGL(unique_tables_kernel, dim3(g1), dim3(256), 0, st, n, (const int *)W.isrep, (const int *)W.upos,
+                       (const int *)W.cls, (const int *)W.cstart, W.uofc, W.cofu, W.rep_m);
+    HIP_TRY(hipGetLastError());
+    return FDR_OK;
 }
 
-static DedupLayout dedup_layout(const fdr_ctx *ctx, int64_t nq, int64_t nt, int d, int k) {
-    DedupLayout L;
-    const int dp = fdr_padded_dim(d);
-    L.inner_bytes = align256(knn_mode_workspace_bytes(ctx, nq, nt, d, k));
-    size_t o = L.inner_bytes;
-    auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
-    // (one block: the sorted hashes follow the unsorted ones, and the (representative, size, start) table of
-    // expand_classes_kernel, 16 bytes per unique row, takes the place of both once the classes are marked)
-    L.off_hash = take(align256((size_t)nt * 8) + (size_t)nt * 8);
-    L.off_hash_s = L.off_hash + align256((size_t)nt * 8);
-    L.off_idx = take((size_t)nt * 4);
-    L.off_idx_s = take((size_t)nt * 4);
-    L.off_flag = take((size_t)nt * 4);
-    L.off_cid = take((size_t)nt * 4);
-    L.off_cls = take((size_t)nt * 4);
-    L.off_cstart = take((size_t)(nt + 1) * 4);
-    L.off_isrep = take((size_t)nt * 4);
-    L.off_upos = take((size_t)nt * 4);
-    L.off_uofc = take((size_t)nt * 4);
-    L.off_cofu = take((size_t)nt * 4);
-    L.off_uqflag = take((size_t)nt * 4);
-    L.off_uqpos = take((size_t)nt * 4);
-    L.off_U = take((size_t)nt * dp * 4);
-    L.off_uzero = take((size_t)nt);
-    L.off_Uq = take((size_t)nq * dp * 4);
-    L.off_uqz = take((size_t)nq);
-    L.off_idxu = take((size_t)nq * k * 4);
-    L.off_distu = take((size_t)nq * k * 4);
-    L.off_rowpath = take((size_t)nq);  // path codes of the original rows (fdr_last_query_paths)
-    size_t t_sort = 0, t_scan = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, t_sort, (u64 *)nullptr, (u64 *)nullptr, (int *)nullptr,
-                                    (int *)nullptr, (size_t)nt, 0, 64, (hipStream_t) nullptr);
-    (void)rocprim::inclusive_scan(nullptr, t_scan, (int *)nullptr, (int *)nullptr, (size_t)nt,
-                                  rocprim::plus<int>(), (hipStream_t) nullptr);
-    L.tmp_bytes = align256(std::max(t_sort, t_scan));
-    L.off_tmp = take(L.tmp_bytes);
-    L.total = o;
-    return L;
+// Is searching nu unique targets for nuq unique queries worth the gathers and the expansion?  Never with fewer unique
+// rows than neighbours asked for; else when forced (tests), or when the pairs to score fall to 90 %.
+static bool dedup_worth(int nu, int nuq, int64_t nt, int64_t nq, int k, int dedup_mode) {
+    if (nu < k) return false;
+    return dedup_mode == FDR_DEDUP_FORCE || (double)nu * nuq <= 0.9 * (double)nt * (double)nq;
 }
 
-// queries (waves) per workgroup of expand_classes_kernel: four while their K * K keys stay within 32 KiB of LDS
-static int expand_waves_per_block(int k) { return (size_t)4 * k * k * 8 <= 32768 ? 4 : (size_t)2 * k * k * 8 <= 32768 ? 2 : 1; }
+// expand_classes_kernel: the unique rows' results (idx_u / dist_u, u_stride elements apart; found through uqpos where
+// only some unique rows were queries) -> the results of rows [q0, q0 + nq) of the classes in W
+static int launch_expand(const DedupWs &W, int64_t q0, int64_t nq, int k, int64_t t_base, const int *uqpos,
+                         const int32_t *idx_u, const float *dist_u, int64_t u_stride, int32_t *d_idx, float *d_dist,
+                         const uint8_t *upath, uint8_t path_all, uint8_t *rowpath, hipStream_t st) {
+    // queries (waves) per workgroup: four while their K * K keys stay within 32 KiB of LDS  (k <= FDR_FAST_MAX_K = 64)
+    const int xw = (size_t)4 * k * k * 8 <= 32768 ? 4 : (size_t)2 * k * k * 8 <= 32768 ? 2 : 1;
+    const int xq = xw * (64 / k) * EXPAND_UNROLL;
+    hipLaunchKernelGGL(expand_classes_kernel, dim3((unsigned)((nq + xq - 1) / xq)), dim3(64 * xw), (size_t)xw * k * k * 8,
+                       st, (int)q0, (int)nq, k, 64 / k, (int)t_base, (const int *)W.cls, (const int *)W.uofc, uqpos,
+                       (const int *)idx_u, dist_u, (const int *)W.idx_s, (const int4 *)W.rep_m, d_idx, d_dist,
+                       (int)u_stride, upath, path_all, rowpath);
+    HIP_TRY(hipGetLastError());
+    return FDR_OK;
+}
 
 static int launch_knn(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero, int64_t nq,
                       const float *d_That, const uint8_t *d_tzero, int64_t nt, int64_t t_base, int d,
                       int k, int32_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes, hipStream_t st) {
+    int rc = check_knn_args(d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist, d_ws);
+    if (rc) return rc;
     const int dp = fdr_padded_dim(d);
-    const int route = dp > 0 ? knn_route(dp, k, nt) : FDR_ROUTE_GENERIC;
-    if (dp > 0 && k >= 1 && k <= FDR_MAX_K && route == FDR_ROUTE_GENERIC) {  // beyond the MFMA kernels' shapes
-        if (nq < 0 || nt < k) return fail(FDR_E_ARG, "knn: need n_targets (%lld) >= k (%d)", (long long)nt, k);
-        if (nt + t_base > 0x7fffffffll || nq > 0x7fffffffll) return fail(FDR_E_ARG, "knn: row numbers exceed int32");
+    const int route = knn_route(dp, k, nt);
+    if (route == FDR_ROUTE_GENERIC) {  // beyond the MFMA kernels' shapes
         if (nq == 0) return FDR_OK;
-        if (!d_Qhat || !d_qzero || !d_That || !d_tzero || !d_idx || !d_dist) return fail(FDR_E_ARG, "knn: null device pointer");
-        ctx->last_unique_targets = (int)nt;
-        ctx->last_unique_queries = (int)nq;
-        ctx->last_flagged = 0;
-        ctx->last_pass_launches = ctx->last_pass_queues = 0;
-        ctx->paths.dev = nullptr;
-        ctx->paths.n = nq;
-        ctx->paths.all = FDR_PATH_GENERIC;
-        ctx->trace.kind = FDR_TRACE_GENERIC;
-        ctx->trace.dp = dp;
-        ctx->trace.k = k;
-        ctx->trace.queries = nq;
-        ctx->trace.targets = nt;
-        ctx->trace.generic = 1;
+        ctx->last.unique_targets = (int)nt;
+        ctx->last.unique_queries = (int)nq;
+        knn_call_whole(ctx, FDR_PATH_GENERIC, FDR_TRACE_GENERIC, dp, k, nq, nt);
+        ctx->last.trace.generic = 1;
         int trc = timing_begin(ctx, FDR_KERNEL_KNN_TILE, st);
         if (trc) return trc;
         hipLaunchKernelGGL(knn_generic_kernel, dim3((unsigned)((nq + GEN_QPB - 1) / GEN_QPB)), dim3(256),
@@ -1517,106 +1408,68 @@ static int launch_knn(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero,
         HIP_TRY(hipGetLastError());
         return timing_end(ctx, FDR_KERNEL_KNN_TILE, st);
     }
+    // the plain search, every row a class of its own, in the first `bytes` of the workspace
+    auto plain = [&](size_t bytes) {
+        ctx->last.unique_targets = (int)nt;
+        ctx->last.unique_queries = (int)nq;
+        return launch_knn_mode(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist, d_ws, bytes, st);
+    };
     // the queries must be a block of the target rows (they are in every caller of this library)
-    const bool q_in_t = d_Qhat && d_That && dp > 0 && d_Qhat >= d_That &&
-                        d_Qhat + (size_t)nq * dp <= d_That + (size_t)nt * dp &&
+    const bool q_in_t = nq > 0 && d_Qhat >= d_That && d_Qhat + (size_t)nq * dp <= d_That + (size_t)nt * dp &&
                         ((d_Qhat - d_That) % dp) == 0;
     // (FDR_ROUTE_WIDE: the exact pass of launch_knn_mode, never the duplicate-row classes)
-    if (!(dp > 0 && k >= 1 && route == FDR_ROUTE_FAST && nq > 0 && nt >= k && q_in_t && knn_dedup_wanted(ctx, nq, nt) &&
-          d_qzero && d_tzero && d_idx && d_dist && d_ws)) {
-        ctx->last_unique_targets = (int)nt;
-        ctx->last_unique_queries = (int)nq;
-        return launch_knn_mode(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist,
-                               d_ws, ws_bytes, st);
-    }
-    const DedupLayout L = dedup_layout(ctx, nq, nt, d, k);
-    if (ws_bytes < L.total) return fail(FDR_E_ARG, "knn: workspace %zu < required %zu bytes", ws_bytes, L.total);
-    char *ws = static_cast<char *>(d_ws);
-    u64 *hash = (u64 *)(ws + L.off_hash), *hash_s = (u64 *)(ws + L.off_hash_s);
-    int *idx = (int *)(ws + L.off_idx), *idx_s = (int *)(ws + L.off_idx_s), *flag = (int *)(ws + L.off_flag);
-    int *cid = (int *)(ws + L.off_cid), *cls = (int *)(ws + L.off_cls), *cstart = (int *)(ws + L.off_cstart);
-    int *isrep = (int *)(ws + L.off_isrep), *upos = (int *)(ws + L.off_upos), *uofc = (int *)(ws + L.off_uofc);
-    int *cofu = (int *)(ws + L.off_cofu), *uqflag = (int *)(ws + L.off_uqflag), *uqpos = (int *)(ws + L.off_uqpos);
-    float *U = (float *)(ws + L.off_U), *Uq = (float *)(ws + L.off_Uq);
-    uint8_t *uzero = (uint8_t *)(ws + L.off_uzero), *uqz = (uint8_t *)(ws + L.off_uqz);
-    int32_t *idx_u = (int32_t *)(ws + L.off_idxu);
-    float *dist_u = (float *)(ws + L.off_distu);
-    void *tmp = ws + L.off_tmp;
+    if (!(route == FDR_ROUTE_FAST && q_in_t && knn_dedup_wanted(ctx->dedup_mode, nq, nt))) return plain(ws_bytes);
+    const WsEnv env = ws_env(ctx);
+    const DedupWs W = dedup_ws(env, d_ws, nq, nt, d, k);
+    if (ws_bytes < W.total) return fail(FDR_E_ARG, "knn: workspace %zu < required %zu bytes", ws_bytes, W.total);
     const int n = (int)nt;
     const int q0 = (int)((d_Qhat - d_That) / dp);
     const unsigned g16 = (unsigned)(((size_t)n * 16 + 255) / 256), g1 = (unsigned)((n + 255) / 256);
 
     int trc = timing_begin(ctx, FDR_KERNEL_KNN_DEDUP, st);
     if (trc) return trc;
-    hipLaunchKernelGGL(hash_rows_kernel, dim3(g16), dim3(256), 0, st, d_That, n, dp, hash, idx);
+    hipLaunchKernelGGL(hash_rows_kernel, dim3(g16), dim3(256), 0, st, d_That, n, dp, W.hash, W.idx);
     HIP_TRY(hipGetLastError());
-    const bool always = ctx->dedup_mode == FDR_DEDUP_FORCE;  // expand even without duplicates (tests)
     // From 2^18 targets the sort and the tables (< 1 ms at 1 M rows) are noise next to the search (~ n^2): no probe,
-    // no read-back for it; the decision falls on the exact unique counts below.
-    if (!always && nt < FDR_DEDUP_PROBE_BELOW) {
-        // a hash-table probe (~15 us) tells whether enough rows repeat to pay for the sort and the tables;
-        // the table borrows the (still unused) unique-row buffer
-        unsigned tsize = 1024;
-        while (tsize < 2u * (unsigned)n && tsize < (1u << 30)) tsize <<= 1;
-        if ((size_t)tsize * 8 + 256 <= (size_t)nt * dp * 4) {
-            u64 *table = reinterpret_cast<u64 *>(U);
-            int *d_cnt = reinterpret_cast<int *>(table + tsize);
-            HIP_TRY(hipMemsetAsync(table, 0, (size_t)tsize * 8 + 4, st));
-            hipLaunchKernelGGL(dedup_probe_kernel, dim3(g1), dim3(256), 0, st, (const u64 *)hash, n, table,
-                               tsize - 1, d_cnt);
-            HIP_TRY(hipGetLastError());
-            int dups = 0;
-            HIP_TRY(hipMemcpyAsync(&dups, d_cnt, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if ((double)dups < 0.05 * (double)n) {  // (unique share)^2 > 0.9: not worth it
-                if ((trc = timing_end(ctx, FDR_KERNEL_KNN_DEDUP, st))) return trc;
-                ctx->last_unique_targets = (int)nt;
-                ctx->last_unique_queries = (int)nq;
-                return launch_knn_mode(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx,
-                                       d_dist, d_ws, L.inner_bytes, st);
-            }
+    // no read-back for it; the decision falls on the exact unique counts below.  Below: a hash-table probe (~15 us)
+    // tells whether enough rows repeat to pay for the sort and the tables.
+    if (ctx->dedup_mode != FDR_DEDUP_FORCE && W.probe_slots) {
+        HIP_TRY(hipMemsetAsync(W.probe_table, 0, (size_t)W.probe_slots * 8 + 4, st));
+        hipLaunchKernelGGL(dedup_probe_kernel, dim3(g1), dim3(256), 0, st, (const u64 *)W.hash, n, W.probe_table,
+                           W.probe_slots - 1, W.probe_count);
+        HIP_TRY(hipGetLastError());
+        int dups = 0;
+        HIP_TRY(hipMemcpyAsync(&dups, W.probe_count, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if ((double)dups < 0.05 * (double)n) {  // (unique share)^2 > 0.9: not worth it
+            if ((trc = timing_end(ctx, FDR_KERNEL_KNN_DEDUP, st))) return trc;
+            return plain(W.inner_bytes);
         }
     }
-    size_t tb = L.tmp_bytes;
-    HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, hash, hash_s, idx, idx_s, (size_t)n, 0, 64, st));
-    hipLaunchKernelGGL(mark_class_starts_kernel, dim3(g1), dim3(256), 0, st, d_That, n, dp,
-                       (const u64 *)hash_s, (const int *)idx_s, flag);
-    tb = L.tmp_bytes;
-    HIP_TRY(rocprim::inclusive_scan(tmp, tb, flag, cid, (size_t)n, rocprim::plus<int>(), st));
-    hipLaunchKernelGGL(class_tables_kernel, dim3(g1), dim3(256), 0, st, n, (const int *)flag,
-                       (const int *)cid, (const int *)idx_s, cls, cstart, isrep);
-    tb = L.tmp_bytes;
-    HIP_TRY(rocprim::inclusive_scan(tmp, tb, isrep, upos, (size_t)n, rocprim::plus<int>(), st));
-    // (rep_m takes the hashes' place: nothing reads them once the classes are marked)
-    hipLaunchKernelGGL(unique_tables_kernel, dim3(g1), dim3(256), 0, st, n, (const int *)isrep,
-                       (const int *)upos, (const int *)cls, (const int *)cstart, uofc, cofu, (int4 *)hash);
-    HIP_TRY(hipMemsetAsync(uqflag, 0, (size_t)n * 4, st));
+    if ((rc = queue_class_tables(W, d_That, n, dp, st))) return rc;
+    HIP_TRY(hipMemsetAsync(W.uqflag, 0, (size_t)n * 4, st));
     hipLaunchKernelGGL(mark_query_classes_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, q0,
-                       (int)nq, (const int *)cls, (const int *)uofc, uqflag);
-    tb = L.tmp_bytes;
-    HIP_TRY(rocprim::inclusive_scan(tmp, tb, uqflag, uqpos, (size_t)n, rocprim::plus<int>(), st));
+                       (int)nq, (const int *)W.cls, (const int *)W.uofc, W.uqflag);
+    size_t tb = W.tmp_bytes;
+    HIP_TRY(rocprim::inclusive_scan(W.tmp, tb, W.uqflag, W.uqpos, (size_t)n, rocprim::plus<int>(), st));
     HIP_TRY(hipGetLastError());
     int nu = 0, nuq = 0;
-    HIP_TRY(hipMemcpyAsync(&nu, cid + (n - 1), 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&nuq, uqpos + (n - 1), 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&nu, W.cid + (n - 1), 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&nuq, W.uqpos + (n - 1), 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    ctx->last_unique_targets = nu;
-    ctx->last_unique_queries = nuq;
-    const bool worth = nu >= k && (always || (double)nu * nuq <= 0.9 * (double)nt * (double)nq);
-    size_t inner_need = worth ? knn_mode_workspace_bytes(ctx, nuq, nu, d, k) : 0;
-    if (!worth || inner_need > L.inner_bytes) {  // few duplicates (or, never seen, no room): plain search
+    // few duplicates (or, never seen, no room for the inner call): plain search
+    if (!dedup_worth(nu, nuq, nt, nq, k, ctx->dedup_mode) || knn_mode_workspace_bytes(env, nuq, nu, d, k) > W.inner_bytes) {
         if ((trc = timing_end(ctx, FDR_KERNEL_KNN_DEDUP, st))) return trc;
-        ctx->last_unique_targets = (int)nt;
-        ctx->last_unique_queries = (int)nq;
-        return launch_knn_mode(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist,
-                               d_ws, L.inner_bytes, st);
+        return plain(W.inner_bytes);
     }
+    ctx->last.unique_targets = nu;
+    ctx->last.unique_queries = nuq;
     hipLaunchKernelGGL(gather_unique_rows_kernel, dim3(g16), dim3(256), 0, st, d_That, d_tzero, n, dp,
-                       (const int *)isrep, (const int *)upos, U, uzero);
+                       (const int *)W.isrep, (const int *)W.upos, W.U, W.uzero);
     if (nuq != nu)  // (else the unique queries are the unique rows: no copy, see below)
         hipLaunchKernelGGL(gather_unique_queries_kernel, dim3((unsigned)(((size_t)nu * 16 + 255) / 256)), dim3(256),
-                           0, st, (const float *)U, (const unsigned char *)uzero, nu, dp, (const int *)uqflag,
-                           (const int *)uqpos, Uq, uqz);
+                           0, st, (const float *)W.U, (const unsigned char *)W.uzero, nu, dp, (const int *)W.uqflag,
+                           (const int *)W.uqpos, W.Uq, W.uqz);
     HIP_TRY(hipGetLastError());
     if ((trc = timing_end(ctx, FDR_KERNEL_KNN_DEDUP, st))) return trc;
     // unique rows are stored in ascending representative order, and the unique queries are a subsequence
@@ -1624,25 +1477,16 @@ static int launch_knn(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero,
     // (every unique row is a query: Uq would be a copy of U -- the same pointers let the prefilter mode see that
     // the queries are the targets)
     const bool all_q = nuq == nu;
-    int rc = launch_knn_mode(ctx, all_q ? U : Uq, all_q ? uzero : uqz, nuq, U, uzero, nu, 0, d, k, idx_u, dist_u, d_ws,
-                             L.inner_bytes, st);
+    rc = launch_knn_mode(ctx, all_q ? W.U : W.Uq, all_q ? W.uzero : W.uqz, nuq, W.U, W.uzero, nu, 0, d, k, W.idx_u,
+                         W.dist_u, d_ws, W.inner_bytes, st);
     if (rc) return rc;
     if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_DEDUP, st))) return trc;
-    const int xw = expand_waves_per_block(k), xq = xw * (64 / k) * EXPAND_UNROLL;  // (k <= FDR_FAST_MAX_K = 64 here)
-    hipLaunchKernelGGL(expand_classes_kernel, dim3((unsigned)((nq + xq - 1) / xq)), dim3(64 * xw), (size_t)xw * k * k * 8, st, q0, (int)nq, k, 64 / k,
-                       (int)t_base, (const int *)cls, (const int *)uofc, (const int *)uqpos, (const int *)idx_u,
-                       (const float *)dist_u, (const int *)idx_s, (const int4 *)hash, d_idx, d_dist, k,
-                       ctx->paths.n == nuq ? ctx->paths.dev : nullptr, ctx->paths.all, (uint8_t *)(ws + L.off_rowpath));
-    HIP_TRY(hipGetLastError());
-    ctx->paths.dev = (const uint8_t *)(ws + L.off_rowpath);  // (the unique rows' codes, carried to the rows of their classes)
-    ctx->paths.n = nq;
-    ctx->paths.stream = st;
+    const auto &inner = ctx->last.paths;  // the unique rows' codes, carried to the rows of their classes
+    if ((rc = launch_expand(W, q0, nq, k, t_base, W.uqpos, W.idx_u, W.dist_u, k, d_idx, d_dist,
+                            inner.n == nuq ? inner.dev : nullptr, inner.all, W.rowpath, st)))
+        return rc;
+    ctx->last.paths = {W.rowpath, nq, FDR_PATH_NONE, st};
     return timing_end(ctx, FDR_KERNEL_KNN_DEDUP, st);
-}
-
-static size_t knn_workspace_bytes_impl(const fdr_ctx *ctx, int64_t nq, int64_t nt, int d, int k) {
-    if (knn_dedup_wanted(ctx, nq, nt)) return dedup_layout(ctx, nq, nt, d, k).total;
-    return knn_mode_workspace_bytes(ctx, nq, nt, d, k);
 }
 
 // ---- duplicate-row classes across ranks ---------------------------------------------------------
@@ -1666,48 +1510,26 @@ FDR_EXPORT int fdr_knn_classes_dev(fdr_ctx *ctx, const float *d_That, const uint
         nt > 0x7fffffffll)
         return fail(FDR_E_ARG, "knn_classes: bad argument");
     if (knn_route(dp, k, nt) != FDR_ROUTE_FAST) return FDR_OK;  // (no classes beyond k <= 64, d <= 512: the callers use fdr_knn_dev)
-    if (!knn_dedup_wanted(ctx, nq_max, nt)) return FDR_OK;  // (small sets: the callers use fdr_knn_dev)
-    const DedupLayout L = dedup_layout(ctx, nq_max, nt, d, k);
-    if (ws_bytes < L.total) return fail(FDR_E_ARG, "knn_classes: workspace %zu < required %zu bytes", ws_bytes, L.total);
-    char *ws = static_cast<char *>(d_ws);
-    u64 *hash = (u64 *)(ws + L.off_hash), *hash_s = (u64 *)(ws + L.off_hash_s);
-    int *idx = (int *)(ws + L.off_idx), *idx_s = (int *)(ws + L.off_idx_s), *flag = (int *)(ws + L.off_flag);
-    int *cid = (int *)(ws + L.off_cid), *cls = (int *)(ws + L.off_cls), *cstart = (int *)(ws + L.off_cstart);
-    int *isrep = (int *)(ws + L.off_isrep), *upos = (int *)(ws + L.off_upos), *uofc = (int *)(ws + L.off_uofc);
-    int *cofu = (int *)(ws + L.off_cofu);
-    float *U = (float *)(ws + L.off_U);
-    uint8_t *uzero = (uint8_t *)(ws + L.off_uzero);
-    void *tmp = ws + L.off_tmp;
+    if (!knn_dedup_wanted(ctx->dedup_mode, nq_max, nt)) return FDR_OK;  // (small sets: the callers use fdr_knn_dev)
+    const DedupWs W = dedup_ws(ws_env(ctx), d_ws, nq_max, nt, d, k);
+    if (ws_bytes < W.total) return fail(FDR_E_ARG, "knn_classes: workspace %zu < required %zu bytes", ws_bytes, W.total);
     const int n = (int)nt;
-    const unsigned g16 = (unsigned)(((size_t)n * 16 + 255) / 256), g1 = (unsigned)((n + 255) / 256);
+    const unsigned g16 = (unsigned)(((size_t)n * 16 + 255) / 256);
     int trc = timing_begin(ctx, FDR_KERNEL_KNN_DEDUP, st);
     if (trc) return trc;
-    hipLaunchKernelGGL(hash_rows_kernel, dim3(g16), dim3(256), 0, st, d_That, n, dp, hash, idx);
+    hipLaunchKernelGGL(hash_rows_kernel, dim3(g16), dim3(256), 0, st, d_That, n, dp, W.hash, W.idx);
     HIP_TRY(hipGetLastError());
     // No hash-table probe here (launch_knn's shortcut for small sets): its count depends on the order in which
     // the table fills, and every rank of a row-sharded run must take the SAME decision from the same gathered
     // rows or their collectives no longer match.  The exact unique count after the sort is deterministic.
-    size_t tb = L.tmp_bytes;
-    HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, hash, hash_s, idx, idx_s, (size_t)n, 0, 64, st));
-    hipLaunchKernelGGL(mark_class_starts_kernel, dim3(g1), dim3(256), 0, st, d_That, n, dp, (const u64 *)hash_s,
-                       (const int *)idx_s, flag);
-    tb = L.tmp_bytes;
-    HIP_TRY(rocprim::inclusive_scan(tmp, tb, flag, cid, (size_t)n, rocprim::plus<int>(), st));
-    hipLaunchKernelGGL(class_tables_kernel, dim3(g1), dim3(256), 0, st, n, (const int *)flag, (const int *)cid,
-                       (const int *)idx_s, cls, cstart, isrep);
-    tb = L.tmp_bytes;
-    HIP_TRY(rocprim::inclusive_scan(tmp, tb, isrep, upos, (size_t)n, rocprim::plus<int>(), st));
-    hipLaunchKernelGGL(unique_tables_kernel, dim3(g1), dim3(256), 0, st, n, (const int *)isrep, (const int *)upos,
-                       (const int *)cls, (const int *)cstart, uofc, cofu, (int4 *)hash);  // (rep_m over the hashes)
-    HIP_TRY(hipGetLastError());
+    if ((rc = queue_class_tables(W, d_That, n, dp, st))) return rc;
     int nu = 0;
-    HIP_TRY(hipMemcpyAsync(&nu, cid + (n - 1), 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&nu, W.cid + (n - 1), 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    // (fewer unique rows than neighbours asked for; or too few repeats to pay: the rule of launch_knn, on exact counts)
-    if (nu < k || (ctx->dedup_mode != FDR_DEDUP_FORCE && (double)nu * (double)nu > 0.9 * (double)nt * (double)nt))
-        return timing_end(ctx, FDR_KERNEL_KNN_DEDUP, st);
+    // (every unique row may be a query of some rank: launch_knn's rule with nuq = nu, nq = nt)
+    if (!dedup_worth(nu, nu, nt, nt, k, ctx->dedup_mode)) return timing_end(ctx, FDR_KERNEL_KNN_DEDUP, st);
     hipLaunchKernelGGL(gather_unique_rows_kernel, dim3(g16), dim3(256), 0, st, d_That, d_tzero, n, dp,
-                       (const int *)isrep, (const int *)upos, U, uzero);
+                       (const int *)W.isrep, (const int *)W.upos, W.U, W.uzero);
     HIP_TRY(hipGetLastError());
     if ((trc = timing_end(ctx, FDR_KERNEL_KNN_DEDUP, st))) return trc;
     ctx->cls.valid = true;
@@ -1720,9 +1542,14 @@ FDR_EXPORT int fdr_knn_classes_dev(fdr_ctx *ctx, const float *d_That, const uint
     ctx->cls.nu = nu;
     ctx->cls.ws = d_ws;
     ctx->cls.ws_bytes = ws_bytes;
-    ctx->last_unique_targets = nu;
+    ctx->last.unique_targets = nu;
     *n_unique_out = nu;
     return FDR_OK;
+}
+
+// the tables fdr_knn_classes_dev left in the caller's workspace: the same layout, from what it recorded
+static DedupWs classes_ws(const fdr_ctx *ctx) {
+    return dedup_ws(ws_env(ctx), ctx->cls.ws, ctx->cls.nq_max, ctx->cls.nt, ctx->cls.d, ctx->cls.k);
 }
 
 FDR_EXPORT int fdr_knn_unique_dev(fdr_ctx *ctx, int64_t u_lo, int64_t u_hi, int32_t *d_idx_u, float *d_dist_u,
@@ -1737,18 +1564,13 @@ FDR_EXPORT int fdr_knn_unique_dev(fdr_ctx *ctx, int64_t u_lo, int64_t u_hi, int3
     if (u_hi == u_lo) return FDR_OK;
     if (!d_idx_u || !d_dist_u) return fail(FDR_E_ARG, "knn_unique: null output");
     const int dp = fdr_padded_dim(ctx->cls.d);
-    const DedupLayout L = dedup_layout(ctx, ctx->cls.nq_max, ctx->cls.nt, ctx->cls.d, ctx->cls.k);
-    char *ws = static_cast<char *>(ctx->cls.ws);
-    const float *U = (const float *)(ws + L.off_U);
-    const uint8_t *uzero = (const uint8_t *)(ws + L.off_uzero);
-    ctx->last_unique_queries = (int)(u_hi - u_lo);
-    struct NoPaths {  // (fdr_last_query_paths covers whole calls; a share of the unique rows is not one)
-        fdr_ctx *c;
-        ~NoPaths() { c->paths.n = 0; }
-    } no_paths{ctx};
+    const DedupWs W = classes_ws(ctx);
+    ctx->last.unique_queries = (int)(u_hi - u_lo);
     // the unique rows are stored in ascending representative order; a share of them is a block of U
-    return launch_knn_mode(ctx, U + (size_t)u_lo * dp, uzero + u_lo, u_hi - u_lo, U, uzero, ctx->cls.nu, 0, ctx->cls.d,
-                           ctx->cls.k, d_idx_u, d_dist_u, ctx->cls.ws, L.inner_bytes, (hipStream_t)stream);
+    rc = launch_knn_mode(ctx, W.U + (size_t)u_lo * dp, W.uzero + u_lo, u_hi - u_lo, W.U, W.uzero, ctx->cls.nu, 0,
+                         ctx->cls.d, ctx->cls.k, d_idx_u, d_dist_u, ctx->cls.ws, W.inner_bytes, (hipStream_t)stream);
+    ctx->last.paths = {};  // (fdr_last_query_paths covers whole calls; a share of the unique rows is not one)
+    return rc;
 }
 
 FDR_EXPORT int fdr_knn_expand_dev(fdr_ctx *ctx, int64_t q0, int64_t nq, int64_t t_base, const int32_t *d_idx_u_all,
@@ -1756,7 +1578,7 @@ FDR_EXPORT int fdr_knn_expand_dev(fdr_ctx *ctx, int64_t q0, int64_t nq, int64_t 
                                   void *stream) {
     int rc = use_device(ctx);
     if (rc) return rc;
-    knn_call_begin(ctx);
+    knn_call_begin(ctx);  // (no path codes: the unique rows were searched by several ranks)
     if (!ctx->cls.valid) return fail(FDR_E_STATE, "knn_expand: no classes (call fdr_knn_classes_dev first)");
     if (q0 < 0 || nq < 0 || q0 + nq > ctx->cls.nt) return fail(FDR_E_ARG, "knn_expand: bad row range");
     if (nq == 0) return FDR_OK;
@@ -1765,18 +1587,11 @@ FDR_EXPORT int fdr_knn_expand_dev(fdr_ctx *ctx, int64_t q0, int64_t nq, int64_t 
     const int k = ctx->cls.k;
     if (u_row_stride == 0) u_row_stride = k;
     if (u_row_stride < k || u_row_stride > 0x7fffffffll) return fail(FDR_E_ARG, "knn_expand: bad row stride");
-    const DedupLayout L = dedup_layout(ctx, ctx->cls.nq_max, ctx->cls.nt, ctx->cls.d, k);
-    char *ws = static_cast<char *>(ctx->cls.ws);
     int trc = timing_begin(ctx, FDR_KERNEL_KNN_DEDUP, st);
     if (trc) return trc;
-    const int xw = expand_waves_per_block(k), xq = xw * (64 / k) * EXPAND_UNROLL;
-    hipLaunchKernelGGL(expand_classes_kernel, dim3((unsigned)((nq + xq - 1) / xq)), dim3(64 * xw), (size_t)xw * k * k * 8, st, (int)q0, (int)nq, k,
-                       64 / k, (int)t_base, (const int *)(ws + L.off_cls), (const int *)(ws + L.off_uofc), (const int *)nullptr,
-                       (const int *)d_idx_u_all, d_dist_u_all, (const int *)(ws + L.off_idx_s),
-                       (const int4 *)(ws + L.off_hash), d_idx, d_dist, (int)u_row_stride, (const uint8_t *)nullptr,
-                       (uint8_t)0, (uint8_t *)nullptr);
-    HIP_TRY(hipGetLastError());
-    ctx->paths.n = 0;  // (the unique rows were searched by several ranks: no codes)
+    if ((rc = launch_expand(classes_ws(ctx), q0, nq, k, t_base, nullptr, d_idx_u_all, d_dist_u_all, u_row_stride, d_idx,
+                            d_dist, nullptr, 0, nullptr, st)))
+        return rc;
     return timing_end(ctx, FDR_KERNEL_KNN_DEDUP, st);
 }
 

@@ -40,10 +40,11 @@ struct PinnedBuf {
         cap = bytes;
         return FDR_OK;
     }
-    void release() {
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() {
         if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
     }
 };
 

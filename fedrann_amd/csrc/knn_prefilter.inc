@@ -1082,9 +1082,7 @@ __global__ __launch_bounds__(256) void knn_rerank_kernel(
 // certificate, which does not need the K' list to be complete), as long as theta < 1.  This pass
 // re-streams the fp16 targets for those queries only and collects that set (no top-k state at all, so
 // it runs at the MFMA / staging rate); knn_rerank_long_kernel then ranks it with the canonical fp32
-// chain.  Queries whose set exceeds RANGE_CAP fall back to the exact kernel.
-#define RANGE_CAP 1024
-static_assert(RANGE_CAP == FDR_RANGE_CAP, "fdr_last_range_sets's row length (include/fedrann_hip.h)");
+// chain.  Queries whose set exceeds RANGE_CAP (knn_workspace.inc) fall back to the exact kernel.
 #define RANGE_STAGES 4  // LDS ring of the range pass: one-unit (8 KB) stages, RANGE_STAGES - 1 in flight
 #define RANGE_LANE_BUF 8  // candidates a lane gathers in LDS before it claims their places with one atomic
 

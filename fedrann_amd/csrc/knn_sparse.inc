@@ -449,7 +449,7 @@ FDR_EXPORT int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const
     HIP_TRY(hipMemcpyAsync(idx_out, ctx->idx.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(dist_out, ctx->dist.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    fdr_knn_trace &t = ctx->trace;
+    fdr_knn_trace &t = ctx->last.trace;
     t.kind = FDR_TRACE_SPARSE;
     t.k = k;
     t.queries = t.targets = n;

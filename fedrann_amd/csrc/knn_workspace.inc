@@ -1,0 +1,231 @@
+// Part of libfedrann_hip.so (included by fedrann_hip.hip after knn_plan.inc) and of the host-only sanitizer build
+// (tests/host_san/host_san.cpp): the ONE description of the workspace of a k-NN call -- which regions it holds, of
+// which element type and length, in which order, and which regions deliberately reuse another.  Plain C++, no HIP.
+//
+// A layout function walks an arena and fills a struct whose members are the typed pointers; with a null base the same
+// walk only counts, and its `total` is what fdr_knn_workspace_bytes reports.
+#ifdef __HIPCC__
+typedef _Float16 ws_half;
+typedef int4 ws_int4;
+#else  // (the host-only build: stand-ins of the same size)
+typedef uint16_t ws_half;
+struct ws_int4 {
+    int x, y, z, w;
+};
+#endif
+
+#define RANGE_CAP 1024  // targets the range pass collects per query (knn_prefilter.inc); beyond it: the exact kernel
+static_assert(RANGE_CAP == FDR_RANGE_CAP, "fdr_last_range_sets's row length (include/fedrann_hip.h)");
+#define FDR_DEDUP_PROBE_BELOW (1 << 18)  // targets from which launch_knn skips the duplicate probe
+
+static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+
+struct WsRegion {
+    size_t off, bytes;
+};
+struct WsArena {
+    char *base;                              // null: count only
+    std::vector<WsRegion> *log = nullptr;    // (the layout test: every region taken)
+    size_t at = 0;
+    template <class T>
+    T *take(size_t count) {  // `count` elements of T at the current offset; the next region starts 256-byte aligned
+        const size_t off = at;
+        at += align256(count * sizeof(T));
+        if (log) log->push_back({off, count * sizeof(T)});
+        return base ? reinterpret_cast<T *>(base + off) : nullptr;
+    }
+};
+// element n of a region, as the start of an alias inside it (null in a counting walk)
+template <class T>
+static T *ws_at(T *region, size_t n) { return region ? region + n : nullptr; }
+
+// what a layout depends on besides the problem's size: the device, the context's modes, and the temporary storage
+// rocprim asks for (fedrann_hip.hip: order_sort_tmp_bytes, class_tables_tmp_bytes; the layout test: stand-ins)
+struct WsEnv {
+    int num_cus, knn_mode, dedup_mode;
+    size_t (*order_sort_tmp)(size_t rows);    // radix sort of `rows` (u64, int) pairs over 40 key bits
+    size_t (*class_tables_tmp)(size_t rows);  // the larger of: radix sort of `rows` pairs over 64 bits, inclusive int scan
+};
+
+// mode: FDR_MODE_AUTO uses the fp16 prefilter whenever it applies (d <= 512, k + 8 <= 64) and the target set is large
+// enough to pay for it; fdr_set_knn_mode / FDR_KNN_MODE=exact|prefilter override it.
+static bool knn_prefilter_wanted(int knn_mode, int64_t nt, int k) {
+    if (knn_mode == FDR_MODE_EXACT) return false;
+    const int kp = (k + prefilter_extra(k) + 1) & ~1;
+    if (!(kp <= FDR_FAST_MAX_K && nt >= kp)) return false;
+    if (nt > (int64_t)FDR_MAX_SEG << FDR_PREFILTER_MAX_IB) return false;  // segments too long for the keys
+    return knn_mode == FDR_MODE_PREFILTER || nt >= 8192;
+}
+
+static bool knn_dedup_wanted(int dedup_mode, int64_t nq, int64_t nt) {
+    if (dedup_mode != FDR_DEDUP_AUTO) return dedup_mode != FDR_DEDUP_OFF;
+    return nt >= 8192 && nq >= 1024;  // (from the size at which the prefilter mode engages)
+}
+
+// ---- prefilter mode: fp16 pass -> certificate + exact re-rank -> exact pass for the rest ------------------------------
+struct PrefilterWs {
+    int kp, chunk, rchunk;
+    int ordered;  // ordered scan possible: sort keys, order tables, ordered fp16 copies
+    size_t knn_bytes, otmp_bytes, total;
+    char *knn;  // knn_bytes shared (in stream order) by the candidate pass and the exact passes: a KnnPlan's regions
+    ws_half *ht, *hq;  // fp16 targets, queries
+    u64 *cand;         // [nq, kp] merged candidate keys
+    int *counter;      // 1024 bytes: [0] exact list, [1] all-zero queries, [2] range list; inside it, the all-zero
+    int *zidx;         // ... queries' one answer: k indices at + 256 bytes
+    float *zdist;      // ... and k distances at + 512 bytes  (k <= FDR_FAST_MAX_K = 64)
+    int *flagged;      // the exact list
+    float *qc;         // chunked exact fall-back: the chunk's queries, zero flags, results
+    uint8_t *qzc;
+    int32_t *idxc;
+    float *distc;
+    int *rlist;  // range pass: its queries, their thresholds; per launch of rchunk queries: fp16 rows, thresholds,
+    float *theta;  // counts, rows found
+    ws_half *hqc;
+    float *thetac;
+    int *cnt, *rcand;
+    uint8_t *path;  // per-query path codes (fdr_last_query_paths)
+    // ordered only (else null); keys, values and sort scratch serve the targets, then the queries
+    u64 *okeys, *okeys_s;
+    int *ovals, *perm_t, *perm_q;
+    ws_half *ho_t, *ho_q;
+    char *otmp;
+};
+
+static PrefilterWs prefilter_ws(const WsEnv &env, void *base, int64_t nq, int64_t nt, int d, int k,
+                                std::vector<WsRegion> *log = nullptr) {
+    PrefilterWs L = {};
+    WsArena A{static_cast<char *>(base), log};
+    L.kp = (k + prefilter_extra(k) + 1) & ~1;
+    L.chunk = (int)std::min<int64_t>(nq, 16384);
+    L.rchunk = (int)std::min<int64_t>(nq, 32768);  // range pass: queries per launch
+    const size_t exact_all = knn_plan(env.num_cus, nq, nt, d, k).total_bytes;
+    const int dp = padded_dim(d);
+    const KnnPlan pp = knn_plan(env.num_cus, nq, nt, d, L.kp, prefilter_shape(dp, L.kp, nq, env.num_cus, nt));
+    // (a later call on fewer unique rows may plan more, shorter segments: room for the largest such plan)
+    // (the bound words and the lists padded for the widest query block: a later call may choose the other shape)
+    const size_t pre = std::max(pp.total_bytes, pp.bits_bytes + align256((size_t)(nq + 512) * 4) +
+                                                    prefilter_partial_bound(nq, nt, L.kp, pp.qw));
+    // any exact plan for <= chunk queries: bits + bound words + at most FDR_MAX_SEG segments of lists
+    const size_t chunk_bound = align256((size_t)((nt + 31) / 32) * 4) + align256((size_t)(L.chunk + 128) * 4) +
+                               (size_t)FDR_MAX_SEG * (L.chunk + 128) * (size_t)k * 8;
+    L.knn_bytes = align256(std::max(exact_all, std::max(pre, chunk_bound)));
+    L.knn = A.take<char>(L.knn_bytes);
+    L.ht = A.take<ws_half>((size_t)nt * dp);
+    L.hq = A.take<ws_half>((size_t)nq * dp);
+    L.cand = A.take<u64>((size_t)nq * L.kp);
+    L.counter = A.take<int>(256);
+    L.zidx = ws_at(L.counter, 64);
+    L.zdist = reinterpret_cast<float *>(ws_at(L.counter, 128));
+    L.flagged = A.take<int>((size_t)nq);
+    L.qc = A.take<float>((size_t)L.chunk * dp);
+    L.qzc = A.take<uint8_t>((size_t)L.chunk);
+    L.idxc = A.take<int32_t>((size_t)L.chunk * k);
+    L.distc = A.take<float>((size_t)L.chunk * k);
+    L.rlist = A.take<int>((size_t)nq);
+    L.theta = A.take<float>((size_t)nq);
+    L.hqc = A.take<ws_half>((size_t)L.rchunk * dp);
+    L.thetac = A.take<float>((size_t)L.rchunk);
+    L.cnt = A.take<int>((size_t)L.rchunk);
+    L.rcand = A.take<int>((size_t)L.rchunk * RANGE_CAP);
+    L.path = A.take<uint8_t>((size_t)nq);
+    L.ordered = pp.cohort > 0 || dev_knobs().ordered != 0;  // (the sizes at which the pass runs in synchronised rounds)
+    if (L.ordered) {
+        const size_t nmax = (size_t)std::max(nq, nt);
+        L.okeys = A.take<u64>(nmax);
+        L.okeys_s = A.take<u64>(nmax);
+        L.ovals = A.take<int>(nmax);
+        L.perm_t = A.take<int>((size_t)nt);
+        L.perm_q = A.take<int>((size_t)nq);
+        L.ho_t = A.take<ws_half>((size_t)nt * dp);
+        L.ho_q = A.take<ws_half>((size_t)nq * dp);
+        L.otmp_bytes = align256(env.order_sort_tmp(nmax));
+        L.otmp = A.take<char>(L.otmp_bytes);
+    }
+    L.total = A.at;
+    return L;
+}
+
+// the workspace of launch_knn_mode: the prefilter mode's, or the exact pass's plan alone
+static size_t knn_mode_workspace_bytes(const WsEnv &env, int64_t nq, int64_t nt, int d, int k) {
+    if (knn_prefilter_wanted(env.knn_mode, nt, k)) return prefilter_ws(env, nullptr, nq, nt, d, k).total;
+    return knn_plan(env.num_cus, nq, nt, d, k).total_bytes;
+}
+
+// ---- duplicate-row classes: search unique queries x unique targets, expand --------------------------------------------
+struct DedupWs {
+    size_t inner_bytes, tmp_bytes, total;
+    char *inner;  // inner_bytes: workspace of the inner k-NN call (sized for the un-deduplicated problem)
+    // One block: the sorted hashes follow the unsorted ones, and rep_m -- the (representative, size, start) table of
+    // expand_classes_kernel, 16 bytes per unique row -- takes the place of both once the classes are marked (nothing
+    // reads the hashes after that).
+    u64 *hash, *hash_s;
+    ws_int4 *rep_m;
+    int *idx, *idx_s, *flag, *cid, *cls, *cstart, *isrep, *upos, *uofc, *cofu, *uqflag, *uqpos;
+    float *U;  // the unique rows
+    // Below FDR_DEDUP_PROBE_BELOW targets, and while U is still unused: a hash table of probe_slots (a power of two,
+    // >= 2 nt) words and its duplicate counter behind it.  probe_slots = 0: U has no room for them, no probe.
+    unsigned probe_slots;
+    u64 *probe_table;
+    int *probe_count;
+    uint8_t *uzero;
+    float *Uq;  // the unique queries (where they are not all the unique rows)
+    uint8_t *uqz;
+    int32_t *idx_u;  // the inner call's results
+    float *dist_u;
+    uint8_t *rowpath;  // path codes of the original rows (fdr_last_query_paths)
+    char *tmp;         // tmp_bytes of rocprim scratch
+};
+
+static DedupWs dedup_ws(const WsEnv &env, void *base, int64_t nq, int64_t nt, int d, int k,
+                        std::vector<WsRegion> *log = nullptr) {
+    DedupWs L = {};
+    WsArena A{static_cast<char *>(base), log};
+    const int dp = padded_dim(d);
+    const size_t n = (size_t)nt, hash_words = align256(n * 8) / 8;
+    L.inner_bytes = align256(knn_mode_workspace_bytes(env, nq, nt, d, k));
+    L.inner = A.take<char>(L.inner_bytes);
+    L.hash = A.take<u64>(hash_words + n);
+    L.hash_s = ws_at(L.hash, hash_words);
+    L.rep_m = reinterpret_cast<ws_int4 *>(L.hash);  // (n x 16 bytes <= the block's)
+    L.idx = A.take<int>(n);
+    L.idx_s = A.take<int>(n);
+    L.flag = A.take<int>(n);
+    L.cid = A.take<int>(n);
+    L.cls = A.take<int>(n);
+    L.cstart = A.take<int>(n + 1);
+    L.isrep = A.take<int>(n);
+    L.upos = A.take<int>(n);
+    L.uofc = A.take<int>(n);
+    L.cofu = A.take<int>(n);
+    L.uqflag = A.take<int>(n);
+    L.uqpos = A.take<int>(n);
+    L.U = A.take<float>(n * dp);
+    if (nt < FDR_DEDUP_PROBE_BELOW) {
+        unsigned tsize = 1024;
+        while (tsize < 2u * (unsigned)n) tsize <<= 1;
+        if ((size_t)tsize * 8 + 256 <= n * dp * 4) {
+            L.probe_slots = tsize;
+            L.probe_table = reinterpret_cast<u64 *>(L.U);
+            L.probe_count = reinterpret_cast<int *>(ws_at(L.probe_table, tsize));
+        }
+    }
+    L.uzero = A.take<uint8_t>(n);
+    L.Uq = A.take<float>((size_t)nq * dp);
+    L.uqz = A.take<uint8_t>((size_t)nq);
+    L.idx_u = A.take<int32_t>((size_t)nq * k);
+    L.dist_u = A.take<float>((size_t)nq * k);
+    L.rowpath = A.take<uint8_t>((size_t)nq);
+    L.tmp_bytes = align256(env.class_tables_tmp(n));
+    L.tmp = A.take<char>(L.tmp_bytes);
+    L.total = A.at;
+    return L;
+}
+
+// fdr_knn_workspace_bytes for valid sizes
+static size_t knn_workspace_bytes(const WsEnv &env, int64_t nq, int64_t nt, int d, int k) {
+    const int route = knn_route(padded_dim(d), k, nt);
+    if (route == FDR_ROUTE_GENERIC) return 256;  // (the generic kernel needs no scratch)
+    if (route == FDR_ROUTE_WIDE) return knn_plan(env.num_cus, nq, nt, d, k).total_bytes;  // (the exact pass alone)
+    if (knn_dedup_wanted(env.dedup_mode, nq, nt)) return dedup_ws(env, nullptr, nq, nt, d, k).total;
+    return knn_mode_workspace_bytes(env, nq, nt, d, k);
+}

@@ -1,6 +1,7 @@
 // Host-only build of the library's plain-C++ parts under AddressSanitizer + UBSan (never the GPU build):
 //   kmer_output_loader.inc (output.bin -> CSR), projection_tables.inc (the embed kernel's lookup tables),
-//   csr_compact.inc (dead-feature filter), knn_plan.inc (launch planner), overlaps_writer.inc (overlaps.tsv).
+//   csr_compact.inc (dead-feature filter), knn_plan.inc (launch planner), knn_workspace.inc (the workspace of a k-NN
+//   call), overlaps_writer.inc (overlaps.tsv).
 // tests/test_host_san.py builds this with g++ -fsanitize=address,undefined and drives it; each command
 // prints a result line that the test compares with what libfedrann_hip.so returns for the same input.
 //
@@ -11,6 +12,7 @@
 //   host_san overlaps OUT THREADS                 -> writes a random neighbour graph (whole, and as two appended blocks)
 //   host_san plan-print NQ NT D K SHAPE           -> one plan (devtools)
 //   host_san plan                                 -> sweeps the planner over edge sizes, checks invariants
+//   host_san layout                               -> sweeps the k-NN workspace layouts over the same sizes, checks them
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -29,6 +31,7 @@
 #include "../../include/fedrann_hip.h"
 #include "../../fedrann_amd/csrc/host_common.inc"
 #include "../../fedrann_amd/csrc/knn_plan.inc"
+#include "../../fedrann_amd/csrc/knn_workspace.inc"
 #include "../../fedrann_amd/csrc/projection_tables.inc"
 #include "../../fedrann_amd/csrc/csr_compact.inc"
 #include "../../fedrann_amd/csrc/kmer_output_loader.inc"
@@ -316,6 +319,106 @@ static int cmd_plan() {
     return bad ? 1 : 0;
 }
 
+// ---- the k-NN workspace layouts (knn_workspace.inc) on a fake base: nothing is read or written through the pointers
+struct LayoutCheck {
+    const char *base;
+    size_t total;
+    const std::vector<WsRegion> &log;
+    bool ok = true;
+    // every region 256-byte aligned, inside [base, base + total), and disjoint from every other
+    void regions() {
+        std::vector<WsRegion> r = log;
+        std::sort(r.begin(), r.end(), [](const WsRegion &a, const WsRegion &b) { return a.off < b.off; });
+        for (size_t i = 0; i < r.size(); ++i) {
+            ok = ok && r[i].off % 256 == 0 && r[i].off + r[i].bytes <= total;
+            ok = ok && (i == 0 || r[i - 1].off + r[i - 1].bytes <= r[i].off);
+        }
+    }
+    // `region` is one of the regions taken, and `alias` [bytes] lies inside it, from `from` bytes into it onwards
+    void inside(const void *alias, size_t bytes, const void *region, size_t from = 0) {
+        const size_t ro = (size_t)((const char *)region - base), ao = (size_t)((const char *)alias - base);
+        bool found = false;
+        for (const WsRegion &r : log)
+            if (r.off == ro) found = ao >= ro + from && ao + bytes <= ro + r.bytes;
+        ok = ok && alias && region && found;
+    }
+};
+
+static size_t g_tmp_bytes;  // what the stand-ins for rocprim's temporary-storage queries answer
+static size_t tmp_standin(size_t) { return g_tmp_bytes; }
+
+static int check_layouts(const WsEnv &env, int64_t nq, int64_t nt, int d, int k) {
+    char *const base = reinterpret_cast<char *>((uintptr_t)1 << 40);
+    const int dp = padded_dim(d);
+    bool ok = true;
+    size_t want = knn_plan(env.num_cus, nq, nt, d, k).total_bytes;  // what fdr_knn_workspace_bytes must say
+    if (knn_prefilter_wanted(env.knn_mode, nt, k)) {
+        std::vector<WsRegion> log;
+        const PrefilterWs L = prefilter_ws(env, base, nq, nt, d, k, &log);
+        LayoutCheck c{base, L.total, log};
+        c.regions();
+        c.inside(L.zidx, (size_t)k * 4, L.counter, 16);  // (the three counters come first)
+        c.inside(L.zdist, (size_t)k * 4, L.counter, 16);
+        ok = c.ok && (const char *)L.zidx + (size_t)k * 4 <= (const char *)L.zdist && L.knn == base;
+        ok = ok && prefilter_ws(env, nullptr, nq, nt, d, k).total == L.total && L.knn_bytes <= L.total;
+        ok = ok && L.chunk >= 1 && L.chunk <= nq && L.rchunk >= 1 && L.rchunk <= nq && L.kp >= k && (L.ordered != 0) == (L.otmp != nullptr);
+        // the regions of every plan that runs in the shared head: the candidate pass, the whole exact fall-back, and the
+        // chunked one for any c <= chunk queries
+        ok = ok && L.knn_bytes >= knn_plan(env.num_cus, nq, nt, d, k).total_bytes &&
+             L.knn_bytes >= knn_plan(env.num_cus, nq, nt, d, L.kp, prefilter_shape(dp, L.kp, nq, env.num_cus, nt)).total_bytes;
+        for (const int64_t cq : {(int64_t)1, (int64_t)127, (int64_t)129, (int64_t)L.chunk / 2, (int64_t)L.chunk - 1, (int64_t)L.chunk})
+            if (cq >= 1 && cq <= L.chunk) ok = ok && L.knn_bytes >= knn_plan(env.num_cus, cq, nt, d, k).total_bytes;
+        want = L.total;
+    }
+    ok = ok && knn_mode_workspace_bytes(env, nq, nt, d, k) == want;
+    if (knn_dedup_wanted(env.dedup_mode, nq, nt)) {
+        std::vector<WsRegion> log;
+        const DedupWs W = dedup_ws(env, base, nq, nt, d, k, &log);
+        LayoutCheck c{base, W.total, log};
+        c.regions();
+        const size_t n = (size_t)nt;
+        c.inside(W.hash_s, n * 8, W.hash, n * 8);  // (behind the unsorted hashes: the sort reads one and writes the other)
+        c.inside(W.rep_m, n * 16, W.hash);
+        if (W.probe_slots) {
+            c.inside(W.probe_table, (size_t)W.probe_slots * 8, W.U);
+            c.inside(W.probe_count, 4, W.U, (size_t)W.probe_slots * 8);
+            ok = ok && W.probe_slots >= 2 * n && (W.probe_slots & (W.probe_slots - 1)) == 0 && nt < FDR_DEDUP_PROBE_BELOW;
+        }
+        ok = ok && c.ok && W.inner == base && dedup_ws(env, nullptr, nq, nt, d, k).total == W.total;
+        ok = ok && W.inner_bytes >= want && W.tmp_bytes >= g_tmp_bytes;  // (the inner call on the full problem)
+        want = W.total;
+    }
+    ok = ok && knn_workspace_bytes(env, nq, nt, d, k) == want;
+    if (!ok)
+        printf("FAIL layout cus=%d mode=%d dedup=%d tmp=%zu nq=%lld nt=%lld d=%d k=%d\n", env.num_cus, env.knn_mode,
+               env.dedup_mode, g_tmp_bytes, (long long)nq, (long long)nt, d, k);
+    return ok ? 0 : 1;
+}
+
+// the sizes of cmd_plan on the route that has these workspaces (FDR_ROUTE_FAST), every k-NN mode x duplicate-row mode
+static int cmd_layout() {
+    int bad = 0, n = 0;
+    const int64_t sizes[] = {20, 64, 8191, 8192, 8193, 100000, (1 << 19) - 1, 1 << 19, (1 << 19) + 1, 1000000,
+                             1250000, 2500000, 10000000, 20000000, ((int64_t)FDR_MAX_SEG << FDR_PREFILTER_MAX_IB)};
+    for (const size_t tmp : {(size_t)0, (size_t)1, (size_t)3 << 20}) {
+        g_tmp_bytes = tmp;
+        for (int cus : {256, 304, 64})
+            for (int64_t nt : sizes)
+                for (int d : {16, 128, 256, 500})
+                    for (int k : {1, 20, 50, 64}) {
+                        if (nt < k || knn_route(padded_dim(d), k, nt) != FDR_ROUTE_FAST) continue;
+                        for (int64_t nq : {nt, (nt + 7) / 8, (int64_t)1})
+                            for (int mode : {FDR_MODE_AUTO, FDR_MODE_EXACT, FDR_MODE_PREFILTER})
+                                for (int dedup : {FDR_DEDUP_AUTO, FDR_DEDUP_OFF, FDR_DEDUP_FORCE}) {
+                                    bad += check_layouts(WsEnv{cus, mode, dedup, tmp_standin, tmp_standin}, nq, nt, d, k);
+                                    ++n;
+                                }
+                    }
+    }
+    printf("rc=%d layouts=%d\n", bad ? 1 : 0, n);
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
     const std::string cmd = argc > 1 ? argv[1] : "";
     if (cmd == "loader" && argc == 5) return cmd_loader(argv[2], atoll(argv[3]), atoi(argv[4]), false);
@@ -325,6 +428,7 @@ int main(int argc, char **argv) {
     if (cmd == "reads" && argc == 6) return cmd_reads(argv[2], atoll(argv[3]), atoi(argv[4]), argv[5]);
     if (cmd == "tables" && argc == 5) return cmd_tables((unsigned)atoi(argv[2]), atoll(argv[3]), atoi(argv[4]));
     if (cmd == "plan") return cmd_plan();
+    if (cmd == "layout") return cmd_layout();
     if (cmd == "floats" && argc == 3) {  // host_san floats N: float32 bit patterns (one hex word per line on stdin) -> text
         char line[64], out[64];
         long long n = atoll(argv[2]);
@@ -385,6 +489,6 @@ int main(int argc, char **argv) {
         printf(" bytes=%zu\n", p.total_bytes);
         return 0;
     }
-    fprintf(stderr, "usage: host_san loader|loader-stale|tables|plan ...\n");
+    fprintf(stderr, "usage: host_san loader|loader-stale|tables|plan|layout ...\n");
     return 2;
 }

@@ -1,5 +1,5 @@
 """The library's plain-C++ parts (output.bin loader, projection table builder, dead-feature filter, launch
-planner) built HOST-ONLY with AddressSanitizer + UBSan and driven through tests/host_san/host_san.cpp.
+planner, k-NN workspace layouts) built HOST-ONLY with AddressSanitizer + UBSan and driven through tests/host_san/host_san.cpp.
 CPU only: sanitizers never run on the GPU build.  Each harness result is compared with what the regular
 libfedrann_hip.so returns for the same input (same code, built by hipcc)."""
 import ctypes
@@ -66,6 +66,18 @@ def test_planner_sweep_under_sanitizers(san):
     f = _fields(san("plan"))
     assert f["rc"] == "0" and int(f["plans"]) > 9000
     assert 1 <= int(f["config4_nseg"]) <= 48 and 1 <= int(f["config5_nseg"]) <= 48
+
+
+def test_workspace_layouts_under_sanitizers(san):
+    """knn_workspace.inc over the planner sweep's sizes on the route that has these workspaces, x k-NN mode {auto, exact,
+    prefilter} x duplicate-row mode {auto, off, force} x stand-in rocprim temp sizes {0, 1, 3 MiB}, each layout built on
+    a fake base: every region 256-byte aligned, inside [base, base + total) and disjoint from the others; every declared
+    alias (the sorted hashes behind the unsorted ones, rep_m over both, the probe table and its counter in U, the zero
+    answer in the counter block) inside the region it reuses; the counting walk returns the same total; the dedup
+    layout's inner region holds the inner call's workspace for the full problem; the prefilter layout's shared head
+    holds the candidate pass's plan and the exact plan of any chunk of the fall-back."""
+    f = _fields(san("layout"))
+    assert f["rc"] == "0" and int(f["layouts"]) > 50000
 
 
 @pytest.mark.parametrize("seed,F,d", [(3, 200_000, 128), (4, 5000, 16), (5, 1_000_003, 500), (6, 64, 4)])
