@@ -409,7 +409,7 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float *__rest
 #include "knn_workspace.inc"      // the workspace of a k-NN call: its regions, once (plain C++)
 #include "projection_tables.inc"  // the embed kernel's lookup tables (plain C++)
 #include "csr_compact.inc"        // dead-feature filter (plain C++)
-#include "host_upload.inc"        // host CSR -> device in chunks: raw over PCIe and compacted on the host at once
+#include "host_upload.inc"        // host CSR -> device in chunks, raw over PCIe and compacted on the host at once: the scheduler (plain C++)
 #include "knn_exact.inc"      // K3 / K4: fp32 MFMA tile kernel with LDS top-k lists, merge
 #include "knn_exact_wide.inc"  // K3s: K3 for 512 < d <= 1024, the components split over two waves
 #include "knn_prefilter.inc"  // P1 / P2: fp16 MFMA candidate pass, merges, certificate + re-rank, range pass
@@ -448,6 +448,31 @@ struct DevBuf {
     ~DevBuf() { release(); }  // (fdr_destroy has made the context's device current)
 };
 
+// its pinned twin on the host
+struct PinnedBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    int reserve(size_t bytes) {
+        if (bytes <= cap) return FDR_OK;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        hipError_t e = hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return fail(FDR_E_NOMEM, "hipHostMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        }
+        cap = bytes;
+        return FDR_OK;
+    }
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() {
+        if (p) (void)hipHostFree(p);
+    }
+};
+
 // What the last k-NN call did, for the fdr_last_* getters.
 struct KnnCallRecord {
     struct {
@@ -481,8 +506,8 @@ struct fdr_ctx {
     // scratch for the host-pointer API
     DevBuf a_indptr, a_indices, E, Ehat, zero, idx, dist, ws;
     DevBuf c_indptr, c_indices;             // ... the chunks the host compacted (upload_embed_pipelined)
-    hup::PinnedBuf stage_ids, stage_ptr;    // ... their pinned staging
-    hipEvent_t up_ev[2] = {nullptr, nullptr};  // ... the two raw runs in flight
+    PinnedBuf stage_ids, stage_ptr;         // ... their pinned staging
+    hipEvent_t up_ev[3] = {nullptr, nullptr, nullptr};  // ... the two raw runs in flight; [2] behind the last copy out of the staging
     hup::WorkerPool up_pool;                // ... the helpers
     // k-mer search (kmer_search.inc)
     DevBuf ks_seq, ks_off, ks_codes, ks_keys, ks_vals, ks_bloom, ks_counter, ks_pairs, ks_pairs2, ks_flag, ks_pos,
@@ -1644,171 +1669,73 @@ static int upload_csr(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indptr,
     return FDR_OK;
 }
 
+// How the upload's scheduler (host_upload.inc) reaches the device: its three operations on ctx->stream.
+struct UploadLink {
+    fdr_ctx *ctx;
+    int64_t n_rows;
+    const int64_t *a_indptr;
+    const int32_t *a_indices;
+    float *d_E;
+    int64_t stage_cap;
+    // rows [r0, r1) as they are, the embed kernel behind them
+    int send_raw(int64_t r0, int64_t r1, int slot) {
+        hipStream_t st = ctx->stream;
+        const int64_t o = a_indptr[r0], len = a_indptr[r1] - o;
+        if (len > 0)
+            HIP_TRY(hipMemcpyAsync((int32_t *)ctx->a_indices.p + o, a_indices + o, (size_t)len * 4, hipMemcpyHostToDevice, st));
+        int erc = launch_embed(ctx, r1 - r0, (const int64_t *)ctx->a_indptr.p + r0, (const int32_t *)ctx->a_indices.p,
+                               d_E + (size_t)r0 * ctx->d, st);
+        if (erc) return erc;
+        if (slot >= 0) HIP_TRY(hipEventRecord(ctx->up_ev[slot], st));
+        return FDR_OK;
+    }
+    int wait_slot(int slot) {
+        HIP_TRY(hipEventSynchronize(ctx->up_ev[slot]));
+        return FDR_OK;
+    }
+    // what the helpers staged, rows [rb, n_rows): two copies and one launch
+    int send_staged(int64_t rb, int64_t used) {
+        hipStream_t st = ctx->stream;
+        const int32_t *stage_ids = (const int32_t *)ctx->stage_ids.p;
+        const int64_t *stage_ptr = (const int64_t *)ctx->stage_ptr.p;
+        if (used > 0)
+            HIP_TRY(hipMemcpyAsync((int32_t *)ctx->c_indices.p + (stage_cap - used), stage_ids + (stage_cap - used),
+                                   (size_t)used * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync((int64_t *)ctx->c_indptr.p + rb, stage_ptr + rb, (size_t)(n_rows - rb + 1) * 8,
+                               hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(ctx->up_ev[2], st));  // (the next call's helpers write the staging again: it waits for this)
+        return launch_embed(ctx, n_rows - rb, (const int64_t *)ctx->c_indptr.p + rb, (const int32_t *)ctx->c_indices.p,
+                            d_E + (size_t)rb * ctx->d, st);
+    }
+};
+
 // Host CSR -> E (device, [n_rows, d]) on ctx->stream: see host_upload.inc.  Small inputs take the plain path.
 static int upload_embed_pipelined(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indptr, const int32_t *a_indices,
                                   float *d_E) {
     int rc;
     const int64_t nnz = a_indptr[n_rows];
-    const int d = ctx->d;
-    const int64_t min_ids = 1 << 20;  // below 4 MB of ids there is nothing to overlap
-    const int nthr = std::max(1, std::min(host_cpu_budget() - 1, 31));  // (the calling thread drives the link)
-    if (nnz < min_ids || ctx->h_bits.empty()) {
+    const hup::Tuning tune;
+    if (nnz < tune.min_ids || ctx->h_bits.empty()) {
         if ((rc = upload_csr(ctx, n_rows, a_indptr, a_indices))) return rc;
         return launch_embed(ctx, n_rows, (const int64_t *)ctx->a_indptr.p, (const int32_t *)ctx->a_indices.p, d_E, ctx->stream);
     }
-    // chunks of ~T ids, cut at row boundaries by bisection of the (monotone) row pointers
-    const int64_t T = 1 << 18;  // (1 MB of ids: ~0.25 ms for a helper, 18 us on the link; helpers' chunks cost no launch each)
-    const int RUN = 8;          // chunks the link takes at once
-    std::vector<hup::Chunk> chunks;
-    for (int64_t r = 0; r < n_rows;) {
-        const int64_t want = a_indptr[r] + T;
-        int64_t r1 = std::upper_bound(a_indptr + r + 1, a_indptr + n_rows + 1, want) - a_indptr;  // first row END beyond `want`
-        r1 = std::min(n_rows, std::max(r + 1, r1 - 1 > r ? r1 - 1 : r + 1));
-        hup::Chunk c;
-        c.r0 = r;
-        c.r1 = r1;
-        chunks.push_back(c);
-        r = r1;
-    }
-    const int64_t nch = (int64_t)chunks.size();
-    for (const hup::Chunk &c : chunks)
-        if (a_indptr[c.r0] < 0 || a_indptr[c.r1] < a_indptr[c.r0] || a_indptr[c.r1] > nnz)
-            return fail(FDR_E_ARG, "embed: indptr not monotone near row %lld", (long long)c.r0);
-    const int64_t stage_cap = std::max<int64_t>(1 << 20, nnz / 6);  // ids of pinned staging (P keeps ~5 % of them)
-    if ((rc = ctx->a_indptr.reserve((size_t)(n_rows + 1) * 8))) return rc;
-    if ((rc = ctx->a_indices.reserve((size_t)nnz * 4))) return rc;
-    if ((rc = ctx->c_indptr.reserve((size_t)(n_rows + nch + 1) * 8))) return rc;
-    if ((rc = ctx->c_indices.reserve((size_t)stage_cap * 4))) return rc;
-    if ((rc = ctx->stage_ids.reserve((size_t)stage_cap * 4))) return rc;
-    if ((rc = ctx->stage_ptr.reserve((size_t)(n_rows + nch + 1) * 8))) return rc;
     for (hipEvent_t &e : ctx->up_ev)
         if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    int32_t *stage_ids = (int32_t *)ctx->stage_ids.p;
-    int64_t *stage_ptr = (int64_t *)ctx->stage_ptr.p;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(ctx->a_indptr.p, a_indptr, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, st));
-
-    // the two fronts: chunks [front, back) are unclaimed
-    std::atomic<uint64_t> ends{(uint64_t)nch};  // front << 32 | back
-    auto claim = [&](bool from_back, int want, int &got) -> int64_t {  // up to `want` chunks from one end; returns the first
-        uint64_t v = ends.load();
-        for (;;) {
-            const uint64_t f = v >> 32, b = v & 0xffffffffull;
-            if (f >= b) return -1;
-            const uint64_t m = std::min<uint64_t>((uint64_t)want, b - f);
-            const uint64_t nv = from_back ? (f << 32 | (b - m)) : ((f + m) << 32 | b);
-            if (ends.compare_exchange_weak(v, nv)) {
-                got = (int)m;
-                return (int64_t)(from_back ? b - m : f);
-            }
-        }
-    };
-    // The helpers' chunks end up in ROW ORDER at the END of the staging buffer, without gaps -- chunk ci right below
-    // chunk ci + 1 -- so that what they produced is one copy of ids, one of row pointers and ONE embed launch, however
-    // small the chunks.  A helper that has compacted chunk ci (into a buffer of its own) waits for cum[ci + 1], the ids
-    // of all chunks above it (a chained scan: that chunk was claimed just before this one and takes as long), publishes
-    // cum[ci] and copies its ids to stage_ids + stage_cap - cum[ci]; its rows' pointers are absolute positions there.
-    std::vector<std::atomic<int64_t>> cum((size_t)nch + 1);
-    for (auto &c : cum) c.store(-1, std::memory_order_relaxed);
-    cum[(size_t)nch].store(0);
-    std::atomic<bool> overflow{false};
-    std::atomic<int64_t> bad_row{-1};
-    const uint32_t *bw = ctx->h_bits.data();
-    const uint64_t F = (uint64_t)ctx->n_features;
-    auto worker = [&]() {
-        std::vector<int32_t> scratch;
-        std::vector<int64_t> lptr;
-        for (;;) {
-            int got = 0;
-            const int64_t ci = claim(true, 1, got);
-            if (ci < 0) break;
-            hup::Chunk &c = chunks[(size_t)ci];
-            const int64_t raw = a_indptr[c.r1] - a_indptr[c.r0], rows = c.r1 - c.r0;
-            int64_t n = 0;
-            bool ok = !overflow.load() && bad_row.load() < 0;
-            for (int64_t r = c.r0; ok && r < c.r1; ++r)
-                if (a_indptr[r + 1] < a_indptr[r]) {
-                    int64_t exp = -1;
-                    bad_row.compare_exchange_strong(exp, r);
-                    ok = false;
-                }
-            if (ok) {
-                if ((int64_t)scratch.size() < raw + 16) scratch.resize((size_t)raw + 16);  // (+ 16: the vector loop stores whole registers)
-                if ((int64_t)lptr.size() < rows + 1) lptr.resize((size_t)rows + 1);
-                n = csrc::compact_chunk(bw, F, a_indptr, a_indices, c.r0, c.r1, scratch.data(), raw, lptr.data());
-            }
-            int64_t above;  // (every claimed chunk publishes, whatever happened to it: the chain must not break)
-            while ((above = cum[(size_t)ci + 1].load(std::memory_order_acquire)) < 0) std::this_thread::yield();
-            const int64_t mine = above + (ok ? n : 0);
-            if (ok && mine > stage_cap) {  // (P keeps far more ids than expected: the helpers' chunks go raw after all)
-                overflow.store(true);
-                ok = false;
-            }
-            cum[(size_t)ci].store(ok ? mine : above, std::memory_order_release);
-            if (!ok) {
-                c.staged_off = -2;
-                continue;
-            }
-            const int64_t base = stage_cap - mine;
-            memcpy(stage_ids + base, scratch.data(), (size_t)n * 4);
-            for (int64_t r = 0; r < rows; ++r) stage_ptr[c.r0 + r] = base + lptr[(size_t)r];
-            c.staged_off = base;
-            c.staged_n = n;
-        }
-    };
-    ctx->up_pool.ensure(nthr);  // (fewer helpers than hoped: the link carries more)
-    ctx->up_pool.start(worker);
-    auto send_raw = [&](int64_t r0, int64_t r1, int slot) -> int {  // rows [r0, r1) as they are, the embed kernel behind them
-        const int64_t o = a_indptr[r0], len = a_indptr[r1] - o;
-        if (len > 0)
-            HIP_TRY(hipMemcpyAsync((int32_t *)ctx->a_indices.p + o, a_indices + o, (size_t)len * 4, hipMemcpyHostToDevice, st));
-        int erc = launch_embed(ctx, r1 - r0, (const int64_t *)ctx->a_indptr.p + r0, (const int32_t *)ctx->a_indices.p,
-                               d_E + (size_t)r0 * d, st);
-        if (erc) return erc;
-        if (slot >= 0) HIP_TRY(hipEventRecord(ctx->up_ev[slot], st));
-        return FDR_OK;
-    };
-    int urc = FDR_OK;
-    int64_t sent = 0;
-    for (; urc == FDR_OK; ++sent) {
-        if (sent >= 2) {  // two runs in flight: the next is claimed when the link has taken the one before the last
-            hipError_t e = hipEventSynchronize(ctx->up_ev[sent & 1]);
-            if (e != hipSuccess) {
-                urc = fail(FDR_E_HIP, "hipEventSynchronize failed: %s", hipGetErrorString(e));
-                break;
-            }
-        }
-        int got = 0;
-        const int64_t ci = claim(false, RUN, got);
-        if (ci < 0) break;
-        urc = send_raw(chunks[(size_t)ci].r0, chunks[(size_t)(ci + got - 1)].r1, (int)(sent & 1));
-    }
-    ctx->up_pool.wait();
-    if (urc) return urc;
-    if (bad_row.load() >= 0) return fail(FDR_E_ARG, "embed: indptr not monotone at row %lld", (long long)bad_row.load());
-    // what the helpers left: chunks [first, nch), in row order at the end of the staging buffer -- two copies and one
-    // launch; if the staging buffer overflowed (a dense P) or a chunk was dropped, their rows go raw after all
-    const int64_t first = (int64_t)(ends.load() & 0xffffffffull);  // (the helpers claimed downwards from nch)
-    if (first < nch) {
-        bool all_staged = !overflow.load();
-        for (int64_t ci = first; ci < nch && all_staged; ++ci) all_staged = chunks[(size_t)ci].staged_off >= 0;
-        const int64_t rb = chunks[(size_t)first].r0;
-        if (!all_staged) {
-            if ((rc = send_raw(rb, n_rows, -1))) return rc;
-        } else {
-            const int64_t used = cum[(size_t)first].load();
-            stage_ptr[n_rows] = stage_cap;
-            if (used > 0)
-                HIP_TRY(hipMemcpyAsync((int32_t *)ctx->c_indices.p + (stage_cap - used), stage_ids + (stage_cap - used),
-                                       (size_t)used * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync((int64_t *)ctx->c_indptr.p + rb, stage_ptr + rb, (size_t)(n_rows - rb + 1) * 8,
-                                   hipMemcpyHostToDevice, st));
-            if ((rc = launch_embed(ctx, n_rows - rb, (const int64_t *)ctx->c_indptr.p + rb, (const int32_t *)ctx->c_indices.p,
-                                   d_E + (size_t)rb * d, st)))
-                return rc;
-        }
-    }
-    return FDR_OK;
+    // the staging is not touched (grown, or written by this call's helpers) under a copy the last call left in flight
+    HIP_TRY(hipEventSynchronize(ctx->up_ev[2]));
+    const int64_t stage_cap = hup::Tuning::stage_cap(nnz);
+    if ((rc = ctx->a_indptr.reserve((size_t)(n_rows + 1) * 8))) return rc;
+    if ((rc = ctx->a_indices.reserve((size_t)nnz * 4))) return rc;
+    if ((rc = ctx->c_indptr.reserve((size_t)(n_rows + 1) * 8))) return rc;
+    if ((rc = ctx->c_indices.reserve((size_t)stage_cap * 4))) return rc;
+    if ((rc = ctx->stage_ids.reserve((size_t)stage_cap * 4))) return rc;
+    if ((rc = ctx->stage_ptr.reserve((size_t)(n_rows + 1) * 8))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->a_indptr.p, a_indptr, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    UploadLink link{ctx, n_rows, a_indptr, a_indices, d_E, stage_cap};
+    return hup::upload(tune, n_rows, a_indptr, a_indices, ctx->h_bits.data(), (uint64_t)ctx->n_features,
+                       (int32_t *)ctx->stage_ids.p, (int64_t *)ctx->stage_ptr.p, stage_cap, ctx->up_pool,
+                       hup::Tuning::helpers(host_cpu_budget()), link)
+        .rc;
 }
 
 FDR_EXPORT int fdr_embed(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indptr,

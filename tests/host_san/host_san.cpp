@@ -1,9 +1,10 @@
 // Host-only build of the library's plain-C++ parts under AddressSanitizer + UBSan (never the GPU build):
 //   kmer_output_loader.inc (output.bin -> CSR), projection_tables.inc (the embed kernel's lookup tables),
-//   csr_compact.inc (dead-feature filter), knn_plan.inc (launch planner), knn_workspace.inc (the workspace of a k-NN
-//   call), overlaps_writer.inc (overlaps.tsv).
+//   csr_compact.inc (dead-feature filter), host_upload.inc (the pipelined upload's scheduler), knn_plan.inc (launch
+//   planner), knn_workspace.inc (the workspace of a k-NN call), overlaps_writer.inc (overlaps.tsv).
 // tests/test_host_san.py builds this with g++ -fsanitize=address,undefined and drives it; each command
-// prints a result line that the test compares with what libfedrann_hip.so returns for the same input.
+// prints a result line that the test compares with what libfedrann_hip.so returns for the same input.  It builds it a
+// second time with -fsanitize=thread and runs `upload`, the one case with threads that share state without a lock.
 //
 //   host_san loader PATH N_FEATURES THREADS       -> "rc=<code> R=.. nnz=.. sums=<4 weighted sums>" | "rc=<code> err=<msg>"
 //   host_san loader-stale PATH N_FEATURES         -> load with capacities that no longer match: must fail cleanly
@@ -13,15 +14,21 @@
 //   host_san plan-print NQ NT D K SHAPE           -> one plan (devtools)
 //   host_san plan                                 -> sweeps the planner over edge sizes, checks invariants
 //   host_san layout                               -> sweeps the k-NN workspace layouts over the same sizes, checks them
+//   host_san upload                               -> sweeps the upload's scheduler over inputs x helper counts x links
+//                                                    on a link that records what it is handed, checks the record
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cmath>
+#include <condition_variable>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
+#include <mutex>
 #include <random>
 #include <string>
 #include <thread>
@@ -34,6 +41,7 @@
 #include "../../fedrann_amd/csrc/knn_workspace.inc"
 #include "../../fedrann_amd/csrc/projection_tables.inc"
 #include "../../fedrann_amd/csrc/csr_compact.inc"
+#include "../../fedrann_amd/csrc/host_upload.inc"
 #include "../../fedrann_amd/csrc/kmer_output_loader.inc"
 #include "../../fedrann_amd/csrc/reads_parser.inc"
 #include "../../fedrann_amd/csrc/overlaps_writer.inc"
@@ -419,8 +427,227 @@ static int cmd_layout() {
     return bad ? 1 : 0;
 }
 
+// ---- the pipelined upload's scheduler (host_upload.inc) on a stand-in link that records what it is handed
+struct UploadInput {
+    const char *name;
+    std::vector<int64_t> ip;
+    std::vector<int32_t> ix;
+    std::vector<uint32_t> bits;
+    int64_t F;
+    int64_t n_rows() const { return (int64_t)ip.size() - 1; }
+};
+
+// rows of len(r) ascending ids below F (a few beyond it); every `alive_of`-th feature has a P row
+template <typename LenFn>
+static UploadInput upload_input(const char *name, std::mt19937_64 &rng, int64_t n_rows, int64_t F, int alive_of, LenFn &&len) {
+    UploadInput in{name, std::vector<int64_t>((size_t)n_rows + 1, 0), {}, std::vector<uint32_t>((size_t)(F + 31) / 32, 0), F};
+    for (int64_t f = 0; f < F; f += alive_of) in.bits[(size_t)(f >> 5)] |= 1u << (f & 31);
+    for (int64_t r = 0; r < n_rows; ++r) {
+        std::vector<int32_t> row((size_t)len(r));
+        for (int32_t &f : row) f = (int32_t)(rng() % (uint64_t)(F + (r % 101 == 0 ? 7 : 0)));
+        std::sort(row.begin(), row.end());
+        in.ix.insert(in.ix.end(), row.begin(), row.end());
+        in.ip[(size_t)r + 1] = (int64_t)in.ix.size();
+    }
+    return in;
+}
+
+struct RecordingLink {
+    struct Raw {
+        int64_t r0, r1;
+        int slot;
+    };
+    const std::vector<int32_t> &stage_ids;
+    const std::vector<int64_t> &stage_ptr;
+    int sleep_us;  // what every send takes
+    int stall_at;  // the raw send (by its number) that takes a tenth of a second on top, -1: none
+    std::vector<Raw> raws;
+    bool pending[2] = {false, false};
+    bool slots_ok = true;  // a slot is waited for before it is used again: never more than two runs in flight
+    int staged_sends = 0, ops = 0, staged_at = -1;
+    int64_t first_row = -1, used = 0;
+    std::vector<int32_t> ids;  // what the staged send took: the last `used` ids ...
+    std::vector<int64_t> ptr;  // ... and stage_ptr[first_row .. n_rows]
+
+    void take_time() const {
+        if (sleep_us) std::this_thread::sleep_for(std::chrono::microseconds(sleep_us));
+    }
+    int send_raw(int64_t r0, int64_t r1, int slot) {
+        if (slot >= 0) {
+            slots_ok = slots_ok && slot < 2 && !pending[slot];
+            pending[slot] = true;
+        }
+        if ((int)raws.size() == stall_at) std::this_thread::sleep_for(std::chrono::milliseconds(100));
+        raws.push_back({r0, r1, slot});
+        ++ops;
+        take_time();
+        return FDR_OK;
+    }
+    int wait_slot(int slot) {
+        slots_ok = slots_ok && slot >= 0 && slot < 2 && pending[slot];
+        pending[slot] = false;
+        return FDR_OK;
+    }
+    int send_staged(int64_t first, int64_t n_used) {
+        ++staged_sends;
+        staged_at = ops++;
+        first_row = first;
+        used = n_used;
+        if (n_used < 0 || n_used > (int64_t)stage_ids.size() || first < 0 || first >= (int64_t)stage_ptr.size()) return FDR_OK;  // (reported by the caller's checks)
+        ids.assign(stage_ids.end() - n_used, stage_ids.end());
+        ptr.assign(stage_ptr.begin() + first, stage_ptr.end());
+        take_time();
+        return FDR_OK;
+    }
+};
+
+struct UploadTally {
+    int combos = 0, staged = 0, overflow = 0, refused = 0;
+    int met[3] = {0, 0, 0};  // runs of input "sparse" whose fronts met in the first, the middle, the last third of the rows
+};
+
+// one upload of `in` (malformed: some row breaks 0 <= indptr[r] <= indptr[r + 1] <= nnz and the call must refuse it) with
+// `helpers` threads and a link that takes sleep_us per send and stalls once, after stall_share percent of the runs the
+// input has (-1: never); every array sized EXACTLY (an overrun is an ASan report)
+static int upload_once(const UploadInput &in, const hup::Tuning &tune, int helpers, int sleep_us, int stall_share, bool malformed,
+                       UploadTally &tally) {
+    const int64_t n_rows = in.n_rows(), nnz = in.ip[(size_t)n_rows], cap = std::max<int64_t>(64, nnz / 6);  // (staging as small as the chunks)
+    std::vector<int32_t> stage_ids((size_t)cap, -1);
+    std::vector<int64_t> stage_ptr((size_t)n_rows + 1, -7);
+    const int64_t runs = ((int64_t)hup::cut_chunks(in.ip.data(), n_rows, tune.ids_per_chunk).size() + tune.run - 1) / tune.run;
+    RecordingLink link{stage_ids, stage_ptr, sleep_us, stall_share < 0 ? -1 : (int)(runs * stall_share / 100)};
+    hup::Outcome o;
+    {
+        hup::WorkerPool pool;  // (a pool of its own: helpers = 0 is "no thread could be started")
+        o = hup::upload(tune, n_rows, in.ip.data(), in.ix.data(), in.bits.data(), (uint64_t)in.F, stage_ids.data(), stage_ptr.data(),
+                        cap, pool, helpers, link);
+    }
+    auto failed = [&](const char *what) {
+        printf("FAIL upload %s: %s (helpers=%d sleep=%d rc=%d bad_row=%lld)\n", in.name, what, helpers, sleep_us, o.rc, (long long)o.bad_row);
+        return 1;
+    };
+    ++tally.combos;
+    if (!link.slots_ok) return failed("a slot reused before it was waited for");
+    if (malformed) {  // refused at a row that is malformed, whichever thread met it, and nobody was handed such a row's ids
+        auto bad = [&](int64_t r) { return in.ip[(size_t)r] < 0 || in.ip[(size_t)r + 1] < in.ip[(size_t)r] || in.ip[(size_t)r + 1] > nnz; };
+        if (o.rc != FDR_E_ARG || o.bad_row < 0 || o.bad_row >= n_rows || !bad(o.bad_row)) return failed("malformed indptr not refused at such a row");
+        if (link.staged_sends) return failed("staged send of a refused input");
+        for (const RecordingLink::Raw &s : link.raws)
+            for (int64_t r = s.r0; r < s.r1; ++r)
+                if (bad(r)) return failed("malformed row sent");
+        ++tally.refused;
+        return 0;
+    }
+    if (o.rc != FDR_OK || o.bad_row >= 0) return failed("valid input refused");
+    // the link's view: raw runs of whole chunks from row 0 upwards, at most `run` chunks each, on alternating slots; then
+    // at most one of: the staged send, one raw send (slot -1) of the rest
+    const std::vector<hup::Chunk> chunks = hup::cut_chunks(in.ip.data(), n_rows, tune.ids_per_chunk);
+    std::vector<int64_t> chunk_at((size_t)n_rows + 1, -1);  // row -> the chunk that starts there
+    for (size_t c = 0; c < chunks.size(); ++c) chunk_at[(size_t)chunks[c].r0] = (int64_t)c;
+    chunk_at[(size_t)n_rows] = (int64_t)chunks.size();
+    int64_t next = 0;
+    for (size_t i = 0; i < link.raws.size(); ++i) {
+        const RecordingLink::Raw &s = link.raws[i];
+        if (s.r0 != next || s.r1 <= s.r0 || s.r1 > n_rows) return failed("raw sends not contiguous");
+        const int64_t c0 = chunk_at[(size_t)s.r0], c1 = chunk_at[(size_t)s.r1];
+        if (c0 < 0 || c1 < 0) return failed("raw send not of whole chunks");
+        if (s.slot >= 0 ? (s.slot != (int)(i & 1) || c1 - c0 > tune.run) : (i + 1 != link.raws.size() || s.r1 != n_rows || link.staged_sends))
+            return failed("raw run too long, on the wrong slot, or a rest that is not last");
+        next = s.r1;
+    }
+    if (link.staged_sends > 1 || (link.staged_sends == 1 && (link.first_row != next || link.staged_at != link.ops - 1)))
+        return failed("staged send not once, last, from where the raw runs ended");
+    if (link.staged_sends == 0 && next != n_rows) return failed("rows not covered");
+    if (o.raw_rows != next || o.staged_rows != n_rows - next) return failed("outcome's row counts");
+    // staged row pointers: ascending inside [cap - used, cap], from the first staged id to the end of the buffer
+    if (link.staged_sends) {
+        if (link.used < 0 || link.used > cap || (int64_t)link.ptr.size() != n_rows - next + 1) return failed("staged sizes");
+        if (link.ptr.front() != cap - link.used || link.ptr.back() != cap) return failed("staged pointers' ends");
+        for (size_t r = 0; r + 1 < link.ptr.size(); ++r)
+            if (link.ptr[r] > link.ptr[r + 1]) return failed("staged pointers not ascending");
+    }
+    // per row, the ids the embed kernel meets (raw rows: filtered by the bitmap, as the kernel does) == csrc::compact
+    std::vector<int64_t> want_ip((size_t)n_rows + 1);
+    std::vector<int32_t> want_ix((size_t)nnz);
+    if (csrc::compact(in.bits, in.F, n_rows, in.ip.data(), in.ix.data(), want_ip.data(), want_ix.data(), nnz, 1)) return failed("compact");
+    for (int64_t r = 0; r < n_rows; ++r) {
+        std::vector<int32_t> got;
+        if (r < next) {
+            for (int64_t q = in.ip[(size_t)r]; q < in.ip[(size_t)r + 1]; ++q) {
+                const uint32_t f = (uint32_t)in.ix[(size_t)q];
+                if ((int64_t)f < in.F && ((in.bits[f >> 5] >> (f & 31)) & 1u)) got.push_back((int32_t)f);
+            }
+        } else {
+            const int64_t base = cap - link.used;
+            got.assign(link.ids.begin() + (link.ptr[(size_t)(r - next)] - base), link.ids.begin() + (link.ptr[(size_t)(r - next) + 1] - base));
+        }
+        if (got != std::vector<int32_t>(want_ix.begin() + want_ip[(size_t)r], want_ix.begin() + want_ip[(size_t)r + 1]))
+            return failed("a row's ids differ from csrc::compact");
+    }
+    tally.staged += link.staged_sends;
+    tally.overflow += o.overflow ? 1 : 0;
+    if (!strcmp(in.name, "sparse")) ++tally.met[std::min<int64_t>(2, 3 * next / n_rows)];
+    return 0;
+}
+
+static int cmd_upload() {
+    std::mt19937_64 rng(11);
+    hup::Tuning tune;  // small chunks and staging, so that a few thousand rows are hundreds of chunks
+    tune.ids_per_chunk = 96;
+    auto some = [&](int64_t) { return (int)(rng() % 40); };
+    std::vector<UploadInput> inputs;
+    inputs.push_back(upload_input("sparse", rng, 4000, 5000, 20, some));  // the helpers' chunks fit the staging buffer
+    inputs.push_back(upload_input("full", rng, 9000, 5000, 1, some));     // every id survives: staging overflows, the rest goes raw
+    inputs.push_back(upload_input("empty-rows", rng, 6000, 5000, 10, [&](int64_t r) { return r < 50 || r % 1000 > 300 || r > 5900 ? 0 : (int)(rng() % 60); }));
+    inputs.push_back(upload_input("long-row", rng, 3000, 5000, 10, [&](int64_t r) { return r % 700 == 350 ? 500 : (int)(rng() % 20); }));
+    inputs.push_back(upload_input("one-row", rng, 1, 5000, 3, [](int64_t) { return 300; }));
+    inputs.push_back(upload_input("few-rows", rng, 3, 5000, 3, [](int64_t r) { return r == 1 ? 0 : 150; }));
+    const size_t n_valid = inputs.size();
+    // a dip in indptr: at a chunk boundary, inside a chunk the link takes first, inside one of the helpers' end; and the two
+    // other ways an entry can be wrong: negative, beyond the ids (a little, and by so much that adding to it overflows)
+    const std::vector<hup::Chunk> cut = hup::cut_chunks(inputs[0].ip.data(), inputs[0].n_rows(), tune.ids_per_chunk);
+    auto inside = [&](size_t c) {  // an indptr entry strictly inside a chunk at or after c
+        while (cut[c].r1 - cut[c].r0 < 2) ++c;
+        return (cut[c].r0 + cut[c].r1) / 2;
+    };
+    struct Dip {
+        const char *name;
+        int64_t entry, below_prev;  // indptr[entry] = indptr[entry - 1] - below_prev, or (below_prev = 0) a fixed value
+        int64_t value;
+    };
+    const int64_t nnz0 = inputs[0].ip.back();
+    const Dip dips[] = {{"dip-boundary", cut[cut.size() / 2].r0, 1, 0}, {"dip-front", inside(1), 1, 0}, {"dip-back", inside(cut.size() - 8), 1, 0},
+                        {"negative", inside(cut.size() / 3), 0, -3}, {"beyond", inside(2 * cut.size() / 3), 0, nnz0 + 9},
+                        {"huge", cut[cut.size() / 4].r0, 0, std::numeric_limits<int64_t>::max() - 5}};
+    for (const Dip &d : dips) {
+        UploadInput in = inputs[0];
+        in.name = d.name;
+        if (in.ip[(size_t)d.entry - 1] < 1) return printf("FAIL upload: no room for a dip\n"), 1;
+        in.ip[(size_t)d.entry] = d.below_prev ? in.ip[(size_t)d.entry - 1] - d.below_prev : d.value;
+        inputs.push_back(in);
+    }
+    UploadTally tally;
+    // The links: an instant one; two that sleep per send (us), about as fast as the helpers and much slower; and two
+    // instant ones that stall ONCE for a tenth of a second, before their first run and after half of the runs.  Where the
+    // fronts meet is up to the scheduler (on an idle machine the woken helpers may take every chunk before the calling
+    // thread's first claim), except at the ends: without helpers the link carries all rows (the back), and behind the stall
+    // before the first run the helpers take all that is left (the front).
+    const struct {
+        int sleep_us, stall_share;
+    } links[5] = {{0, -1}, {30, -1}, {1000, -1}, {0, 50}, {0, 0}};
+    int bad = 0;
+    for (size_t i = 0; i < inputs.size(); ++i)
+        for (int helpers : {0, 1, 5, 15})
+            for (int l = 0; l < 5; ++l)
+                bad += upload_once(inputs[i], tune, helpers, links[l].sleep_us, links[l].stall_share, i >= n_valid, tally);
+    printf("rc=%d combos=%d staged=%d overflow=%d refused=%d met=%d,%d,%d\n", bad ? 1 : 0, tally.combos, tally.staged, tally.overflow,
+           tally.refused, tally.met[0], tally.met[1], tally.met[2]);
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
     const std::string cmd = argc > 1 ? argv[1] : "";
+    if (cmd == "upload") return cmd_upload();
     if (cmd == "loader" && argc == 5) return cmd_loader(argv[2], atoll(argv[3]), atoi(argv[4]), false);
     if (cmd == "loader-stale" && argc == 4) return cmd_loader(argv[2], atoll(argv[3]), 2, true);
     if (cmd == "loader-range" && argc == 8)
@@ -489,6 +716,6 @@ int main(int argc, char **argv) {
         printf(" bytes=%zu\n", p.total_bytes);
         return 0;
     }
-    fprintf(stderr, "usage: host_san loader|loader-stale|tables|plan|layout ...\n");
+    fprintf(stderr, "usage: host_san loader|loader-stale|tables|plan|layout|upload ...\n");
     return 2;
 }

@@ -1,5 +1,7 @@
 """The library's plain-C++ parts (output.bin loader, projection table builder, dead-feature filter, launch
-planner, k-NN workspace layouts) built HOST-ONLY with AddressSanitizer + UBSan and driven through tests/host_san/host_san.cpp.
+planner, k-NN workspace layouts, the pipelined upload's scheduler) built HOST-ONLY with AddressSanitizer + UBSan and
+driven through tests/host_san/host_san.cpp; the upload's scheduler, whose threads share state without a lock, also
+under ThreadSanitizer (a second build of the same file).
 CPU only: sanitizers never run on the GPU build.  Each harness result is compared with what the regular
 libfedrann_hip.so returns for the same input (same code, built by hipcc)."""
 import ctypes
@@ -16,27 +18,53 @@ from fedrann_amd import _lib
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "host_san", "host_san.cpp")
 BIN = os.path.join(HERE, "host_san", "host_san")
-FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-         "-fno-sanitize-recover=undefined", "-Wall", "-Wno-unused-function", "-pthread"]
+BIN_TSAN = BIN + "_tsan"
+COMMON = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Wall", "-Wno-unused-function", "-pthread"]
+FLAGS = COMMON + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+FLAGS_TSAN = COMMON + ["-fsanitize=thread"]
+REPORTS = ("ERROR: AddressSanitizer", "runtime error", "WARNING: ThreadSanitizer")
 
 
-@pytest.fixture(scope="module")
-def san():
+def _harness(binary, flags):
+    """Build tests/host_san/host_san.cpp with `flags` (when it is older than its sources) and return a function
+    that runs it and fails on any sanitizer report."""
     gxx = shutil.which("g++")
     if gxx is None:
         pytest.skip("g++ not available")
     csrc = os.path.join(os.path.dirname(HERE), "fedrann_amd", "csrc")
     deps = [SRC] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".inc")]
-    if not os.path.exists(BIN) or any(os.path.getmtime(d) > os.path.getmtime(BIN) for d in deps):
-        subprocess.run([gxx] + FLAGS + [SRC, "-o", BIN], check=True)
+    if not os.path.exists(binary) or any(os.path.getmtime(d) > os.path.getmtime(binary) for d in deps):
+        subprocess.run([gxx] + flags + [SRC, "-o", binary], check=True)
 
     def run(*args, ok_codes=(0,)):
         env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-        r = subprocess.run([BIN] + [str(a) for a in args], capture_output=True, text=True, timeout=900, env=env)
-        assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+        r = subprocess.run([binary] + [str(a) for a in args], capture_output=True, text=True, timeout=900, env=env)
+        assert not any(w in r.stderr for w in REPORTS), r.stderr[-3000:]
         assert r.returncode in ok_codes, (r.returncode, r.stdout, r.stderr[-2000:])
         return r.stdout.strip()
     return run
+
+
+@pytest.fixture(scope="module")
+def san():
+    return _harness(BIN, FLAGS)
+
+
+@pytest.fixture(scope="module")
+def tsan(tmp_path_factory):
+    """The harness under ThreadSanitizer.  Skips only where the TSan runtime cannot start at all in this
+    environment (it gives up on the process's memory layout before main), judged from an empty program."""
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("g++ not available")
+    d = tmp_path_factory.mktemp("tsan_probe")
+    (d / "probe.cpp").write_text("int main() { return 0; }\n")
+    subprocess.run([gxx, "-fsanitize=thread", str(d / "probe.cpp"), "-o", str(d / "probe")], check=True)
+    r = subprocess.run([str(d / "probe")], capture_output=True, text=True, timeout=60)
+    if r.returncode != 0 and "unexpected memory mapping" in r.stderr:
+        pytest.skip("the ThreadSanitizer runtime cannot start here: " + r.stderr.strip().splitlines()[0])
+    assert r.returncode == 0, r.stderr[-2000:]
+    return _harness(BIN_TSAN, FLAGS_TSAN)
 
 
 def _fields(line):
@@ -78,6 +106,40 @@ def test_workspace_layouts_under_sanitizers(san):
     holds the candidate pass's plan and the exact plan of any chunk of the fall-back."""
     f = _fields(san("layout"))
     assert f["rc"] == "0" and int(f["layouts"]) > 50000
+
+
+def _check_upload_sweep(line):
+    f = _fields(line)
+    # 12 inputs (6 valid, 6 with a bad indptr entry) x 4 helper counts x 5 links
+    assert f["rc"] == "0" and int(f["combos"]) == 240 and int(f["refused"]) == 120
+    # both ends of the sweep were reached: the helpers' chunks went out staged, and staging overflowed
+    assert int(f["staged"]) > 0 and int(f["overflow"]) > 0
+    # the 20 runs of input "sparse" by the third of the rows in which the fronts met.  Two ends hold whatever the
+    # scheduler does: without helpers the link carries all rows (4 links that end in the last third; the fifth stalls in
+    # the middle), and behind a link that stalls for 0.1 s before its first run the helpers, who need milliseconds for
+    # the whole input, take all that is left (3 helper counts).  The middle third is reported, not asserted.
+    front, _, back = (int(x) for x in f["met"].split(","))
+    assert front >= 3 and back >= 4, f["met"]
+
+
+def test_upload_scheduler_under_sanitizers(san):
+    """host_upload.inc's two-front schedule on a link that records what it is handed, small chunks: inputs {sparse
+    bitmap, full bitmap (staging overflows, the rest goes raw), empty rows, a row longer than a chunk, 1 row, 3 rows} x
+    helpers {0, 1, 5, 15} x link {instant, as fast as the helpers, slow, stalling once in the middle, stalling at the
+    front}, arrays sized exactly.  Every row reaches the
+    link exactly once; the ids the embed kernel would meet per row equal csrc::compact of the whole CSR; staged row
+    pointers ascend inside [stage_cap - used, stage_cap] and end at stage_cap; raw runs are whole chunks, at most RUN
+    of them, never more than two slots not waited for.  A dip in indptr at a chunk boundary, inside a chunk of the
+    front and inside one of the back, a negative entry, one beyond the ids and one near
+    INT64_MAX are refused with FDR_E_ARG at a malformed
+    row, and no such row is ever sent."""
+    _check_upload_sweep(san("upload"))
+
+
+def test_upload_scheduler_under_thread_sanitizer(tsan):
+    """The same sweep under ThreadSanitizer: the claim word, the chained scan over cum[] and the flags the helpers and
+    the link share draw no report."""
+    _check_upload_sweep(tsan("upload"))
 
 
 @pytest.mark.parametrize("seed,F,d", [(3, 200_000, 128), (4, 5000, 16), (5, 1_000_003, 500), (6, 64, 4)])
