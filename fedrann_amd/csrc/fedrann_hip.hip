@@ -412,8 +412,8 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float *__rest
 #include "host_upload.inc"        // host CSR -> device in chunks, raw over PCIe and compacted on the host at once: the scheduler (plain C++)
 #include "knn_exact.inc"      // K3 / K4: fp32 MFMA tile kernel with LDS top-k lists, merge
 #include "knn_exact_wide.inc"  // K3s: K3 for 512 < d <= 1024, the components split over two waves
-#include "knn_prefilter.inc"  // P1 / P2: fp16 MFMA candidate pass, merges, certificate + re-rank, range pass
-#include "knn_prefilter_pp.inc"  // P1 for the 256-register shapes: the two waves of a SIMD take turns at the matrix pipe
+#include "knn_prefilter.inc"  // P1 / P2: fp16 MFMA candidate pass, merges, certificate + re-rank, range pass; fragment_addresses, RangeHits
+#include "knn_prefilter_pp.inc"  // P1 and the range pass for the 256-register shapes: the two waves of a SIMD take turns at the matrix pipe
 #include "knn_order.inc"      // P1: scan order by chunk mask (sort keys, ordered fp16 copy)
 #include "dedup_classes.inc"  // duplicate-row classes: hash, tables, gathers, expansion
 #include "knn_generic.inc"    // d > 1024, or k > 64 / d > 512 below 8192 targets: every pair on the vector ALU
@@ -1187,14 +1187,12 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     const int ib = prefilter_index_bits(max_seg);
     if (ib > FDR_PREFILTER_MAX_IB) return fail(FDR_E_ARG, "knn prefilter: segment of %d rows", max_seg);
     if ((trc = timing_end(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
-    const int pdbg = dev_knobs().debug;
-    (void)pdbg;
     if (lds > 32768)
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     Rounds r;  // (rounds on up to four queues; one queue: every launch its own timed span)
     const int lrc = launch_rounds(ctx, p, 4, FDR_KERNEL_KNN_PREFILTER, true, st, r, [&](hipStream_t s, unsigned grid, int base) {
         hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh.nw), lds, s, p1_q, (int)nq, p1_t, (int)nt, (int)t_base, p.segs, kp,
-                           p.nq_pad, d_partial, d_shared, ib, base, p.nqb, ord FDR_DBG_ARG(pdbg));
+                           p.nq_pad, d_partial, d_shared, ib, base, p.nqb, ord FDR_DBG_ARG(dev_knobs().debug));
     });
     ctx->last.pass.launches = r.launches;
     ctx->last.pass.queues = r.queues;
@@ -1219,7 +1217,7 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     }
 #endif
 #ifdef FDR_DEBUG_COUNTERS
-    if (pdbg & 2) {
+    if (dev_knobs().debug & 2) {
         unsigned long long c[8];
         HIP_TRY(hipStreamSynchronize(st));
         HIP_TRY(hipMemcpyFromSymbol(c, HIP_SYMBOL(g_dbg_counters), sizeof(c)));

@@ -99,23 +99,22 @@ __device__ unsigned long long g_stamps[16][8];  // [wave][phase]
 #define STAMP(v) do { } while (0)
 #define STAMP_ADD(ph, a, b) do { } while (0)
 #endif
-#ifndef FDR_SHARE_EVERY
-#define FDR_SHARE_EVERY 63  // the lists are flushed and the bounds exchanged every (this + 1) stages (a power of two - 1):
-                            // 16 / 32 / 64 / 128 stages = 96.3 / 95.0 / 94.4 / 94.1 ms at 1 M rows, 8 stages 99.1; flat at 100 k rows
-#endif
-#ifndef FDR_STAGGER
-#define FDR_STAGGER 1  // 1: the eight-wave shape's second half scores a stage late (see STAGGER in knn_prefilter_kernel)
-#endif
-#ifndef FDR_DEEP_PIPELINE
-#define FDR_DEEP_PIPELINE 4  // k-steps the 256-VGPR shapes read their LDS fragments ahead (0: eight reads, then eight MFMAs, per unit)
-#endif
-#ifndef FDR_LATE_PRIO
-#define FDR_LATE_PRIO 0
-#endif
-#ifndef FDR_OFFER_BATCHED
-#define FDR_OFFER_BATCHED 0  // 1: the cold path's "any lane passes" masks in batches (measured: -1 % at 1 M rows, +3 % at 100 k)
-#endif
+// the lists are flushed and the bounds exchanged every (FDR_SHARE_EVERY + 1) stages (a power of two - 1):
+// 16 / 32 / 64 / 128 stages = 96.3 / 95.0 / 94.4 / 94.1 ms at 1 M rows, 8 stages 99.1; flat at 100 k rows
+constexpr int FDR_SHARE_EVERY = 63;
 
+
+// A lane's eight fragment addresses inside a unit of 32 rows x 128 fp16 components: k-step s reads the 16-byte slot
+// (2 s + h) ^ (j & 15) of row j (the slots are XOR-swizzled with the row when the LDS-DMA writes them).  They are LDS
+// addresses, ring base included, so that a read is `ds_read_b128 v, fa[s] offset:stage/unit`.
+__device__ __forceinline__ void fragment_addresses(unsigned (&fa)[8], const unsigned char *ring_base, int j, int h) {
+    const unsigned ring = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char *)ring_base;
+#pragma unroll
+    for (int s8 = 0; s8 < 8; ++s8) {
+        fa[s8] = ring + (unsigned)(j * 256 + (((2 * s8 + h) ^ (j & 15)) * 16));
+        asm volatile("" : "+v"(fa[s8]));  // (opaque: otherwise hipcc re-derives it with a v_add per read)
+    }
+}
 
 __device__ __forceinline__ unsigned partner32(unsigned x, int h) {  // value held by lane ^ 32
     const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
@@ -195,7 +194,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_prefilter_kernel(
 #pragma unroll
         for (int i = 0; i < NCH * 8; ++i) b[n][i] = qp[2 * i + h];
     }
-    // quantisation grid and the lists
+    // quantisation grid and the lists (knn_prefilter_pp_kernel carries a COPY of this list code -- share, rethreshold,
+    // flush, offer, the write-out: a fix here must be made there too; why it is not one struct: docs/experiments.md A-21)
     const int qbits = min(20, 32 - ib);
     const unsigned QM1 = (1u << qbits) - 2u;
     const float qscale = (float)QM1, qinv = 1.0f / qscale;
@@ -327,51 +327,6 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_prefilter_kernel(
         }
     };
     // the rows of one finished tile against query set n's list (cold: most tiles have no candidate)
-#if FDR_OFFER_BATCHED
-    // The "does any lane pass" masks come in batches -- the four groups' first, then the four rows' of a group that
-    // has a candidate -- so that the compares issue back to back and the wave pays the vector -> scalar round
-    // trip (compare, then a branch on its result) three times per cold tile instead of once per group and row.
-    auto offer = [&](const f32x16 &a, const int (&g)[4], RegList<LH> &Ln, unsigned &a0, unsigned &a1,
-                     const unsigned fl, const int th, int lrow, int nvalid) {
-        const bool dbgc = (dbg & 2) != 0;
-        DBG_COUNT(1);
-        u64 gm[4];
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) gm[q4] = __ballot(g[q4] >= th);
-        asm volatile("" : "+s"(gm[0]), "+s"(gm[1]), "+s"(gm[2]), "+s"(gm[3]));
-        const int vlim = nvalid - 4 * h;  // this lane's tile rows below vlim exist (only a segment's last tile has fewer than 32)
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-            if (gm[q4] == 0ull) continue;
-            DBG_COUNT(2);
-            bool ps[4];
-            u64 rm[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = 4 * q4 + i, roff = (r & 3) + 8 * (r >> 2);
-                ps[i] = __float_as_int(a[r]) >= th && roff < vlim;
-                rm[i] = __ballot(ps[i]);
-            }
-            asm volatile("" : "+s"(rm[0]), "+s"(rm[1]), "+s"(rm[2]), "+s"(rm[3]));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (rm[i] == 0ull) continue;
-                const int r = 4 * q4 + i, roff = (r & 3) + 8 * (r >> 2);
-                unsigned cand = PK_EMPTY;
-                if (ps[i]) {
-                    const float sc = fminf(fmaxf(a[r], 0.0f), 1.0f);
-                    const unsigned qd = QM1 - (unsigned)__builtin_rintf(sc * qscale);
-                    if (qd <= fl) cand = (qd << ib) | (unsigned)(lrow + roff);
-                }
-                DBG_COUNT(3);
-                if (__any(cand != PK_EMPTY && a1 != PK_EMPTY)) flush(Ln, a0, a1);  // some lane's queue is full
-                a1 = (a0 != PK_EMPTY && a1 == PK_EMPTY) ? cand : a1;
-                a0 = a0 == PK_EMPTY ? cand : a0;
-            }
-        }
-    };
-
-#else
     auto offer = [&](const f32x16 &a, const int (&g)[4], RegList<LH> &Ln, unsigned &a0, unsigned &a1,
                      const unsigned fl, const int th, int lrow, int nvalid) {
         const bool dbgc = (dbg & 2) != 0;
@@ -398,18 +353,9 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_prefilter_kernel(
             }
         }
     };
-
-#endif
-    // this lane's eight fragment addresses inside a unit (k-step s reads slot (2s + h) ^ (j & 15) of row j)
-    // (as LDS addresses, ring base included, so that a read is `ds_read_b128 v, fa offset:stage/unit`)
     typedef const f16x8 __attribute__((address_space(3))) lds_f16x8;
-    const unsigned ring = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem;
     unsigned fa[8];
-#pragma unroll
-    for (int s8 = 0; s8 < 8; ++s8) {
-        fa[s8] = ring + (unsigned)(j * 256 + (((2 * s8 + h) ^ (j & 15)) * 16));
-        asm volatile("" : "+v"(fa[s8]));  // (opaque: otherwise hipcc re-derives it with a v_add per read)
-    }
+    fragment_addresses(fa, smem, j, h);
 
     f32x16 acc[NQ];
 #pragma unroll
@@ -440,7 +386,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_prefilter_kernel(
     };
     constexpr bool PAIR = PAIRED && NCH == 1 && (U == 2 || U == 4) && NQ == 1;  // a stage's tiles pairwise as two MFMA chains
     constexpr int NP = U / 2;  // ... pairs per stage (U = 4: half the barriers per tile)
-    constexpr bool STAGGER = PAIR && NW == 8 && FDR_STAGGER;
+    constexpr bool STAGGER = PAIR && NW == 8;  // the eight-wave shape's second half scores a stage late (below)
     const bool late = STAGGER && wave >= NW / 2;  // (wave-uniform)
     f32x16 accB;  // PAIR: the second tile's accumulators
 #pragma unroll
@@ -517,14 +463,14 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_prefilter_kernel(
         } else {
         // (also the 168-VGPR d <= 256 shape with 16-key lists, two k-steps deep: 322 -> 315 ms at 1 M doubled rows, k = 20;
         // d <= 128 with 32-key lists at 128 VGPRs spills: 42 -> 204 ms)
-        constexpr bool DEEP = FDR_DEEP_PIPELINE && (WPS <= 2 || (WPS == 3 && DP == 256 && LH == 16));
+        constexpr bool DEEP = WPS <= 2 || (WPS == 3 && DP == 256 && LH == 16);
         if (DEEP && U * (it + 1) <= nunits) {  // (a full stage; a segment's last, partial one: below)
             // 256-register shapes (two waves per SIMD: little else hides an LDS latency): ONE continuous pipeline over the
             // stage's 8 U k-steps -- the fragment of k-step s + D is requested before the MFMA of k-step s issues, and a
             // k-step waits only for ITS read (counted lgkmcnt: LDS reads return in order), across unit and tile
             // boundaries.  D + 1 fragment registers instead of eight, no bubble per unit.
             if constexpr (DEEP) {
-                constexpr int KS = 8 * U, D = WPS <= 2 ? FDR_DEEP_PIPELINE : 2, R = D + 1;
+                constexpr int KS = 8 * U, D = WPS <= 2 ? 4 : 2, R = D + 1;  // D: k-steps the fragments are read ahead
                 f16x8 fr[R];
                 // (a ring beyond 64 KB: the odd stage's base no longer fits the 16-bit immediate; its addresses are made once
                 // per stage)
@@ -561,8 +507,6 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_prefilter_kernel(
         } else {
 #pragma unroll
         for (int uu = 0; uu < U; ++uu) {
-            constexpr int dummy = 0;
-            (void)dummy;
             const int c = NCH <= U ? uu % NCH : (U * par + uu) % NCH;  // static chunk number
             const int unit = U * it + uu;
             if (unit < nunits) {  // wave-uniform
@@ -628,9 +572,6 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_prefilter_kernel(
         __syncthreads();  // stage it+1 is complete (all waves' pieces) before anyone reads it
 #endif
     };
-#if FDR_LATE_PRIO  // (development: static priority for the later-dispatched half of an eight-wave workgroup)
-    if (NW == 8 && wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
-#endif
     const int niter = nstages + (STAGGER ? 1 : 0);
     for (int it0 = 0; it0 < niter; it0 += 2) {
         stage_body(std::integral_constant<int, 0>{}, it0);
@@ -1086,6 +1027,41 @@ __global__ __launch_bounds__(256) void knn_rerank_kernel(
 #define RANGE_STAGES 4  // LDS ring of the range pass: one-unit (8 KB) stages, RANGE_STAGES - 1 in flight
 #define RANGE_LANE_BUF 8  // candidates a lane gathers in LDS before it claims their places with one atomic
 
+// A lane's hits wait in its own RANGE_LANE_BUF-entry LDS buffer (behind the ring) and leave with ONE returning atomic per
+// batch: a plateau query collects hundreds of rows, and a wave that waits ~2 us for every single `atomicAdd(cnt + q, 1)`
+// spent most of a short scan doing so (1100 queries at 1 M rows / 8: 387 us).
+template <int NT>  // threads per workgroup = the buffer's stride
+struct RangeHits {
+    int *lbuf;    // [RANGE_LANE_BUF][NT]; this lane's entries are lbuf[i * NT + tid]
+    int *cnt;     // per-query hit counters
+    int *cand;    // [nq][RANGE_CAP]
+    int qg, tid;  // this lane's query and thread number
+    int lcount;
+    __device__ __forceinline__ void flush() {
+        const int pos = atomicAdd(cnt + qg, lcount);
+        for (int i = 0; i < lcount; ++i)
+            if (pos + i < RANGE_CAP) cand[(size_t)qg * RANGE_CAP + pos + i] = lbuf[i * NT + tid];
+        lcount = 0;
+    }
+    __device__ __forceinline__ void add(int row) {
+        lbuf[lcount * NT + tid] = row;
+        if (++lcount == RANGE_LANE_BUF) flush();
+    }
+    // the hits of one finished tile some lane of which is above its floor: acc[r] is the similarity with row
+    // row0 + (r & 3) + 8 * (r >> 2); sfloor is the conservative similarity form of d~ <= th
+    __device__ __forceinline__ void collect(const f32x16 &acc, int row0, float sfloor, float th, int t_end, int t_base) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            if (acc[r] > sfloor) {
+                float a1 = acc[r];
+                asm volatile("" : "+v"(a1));
+                const int row = row0 + (r & 3) + 8 * (r >> 2);
+                if (dist_from_sim(a1) <= th && row < t_end) add(t_base + row);
+            }
+        }
+    }
+};
+
 template <int DP, int NW, int WPS>
 __global__ __launch_bounds__(64 * NW, WPS) void knn_range_kernel(
     const _Float16 *__restrict__ Qh, const float *__restrict__ theta, int nq,
@@ -1095,7 +1071,6 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_range_kernel(
     constexpr int QW = 32 * NW;
     constexpr int NCH = DP / 128;
     constexpr int UNIT_BYTES = 32 * 256;
-    constexpr int SLOTS = 16;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
@@ -1138,17 +1113,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_range_kernel(
                                              16, 0, 0);
         }
     };
-    // A lane's candidates wait in its own RANGE_LANE_BUF-entry LDS buffer (behind the ring) and leave with ONE returning
-    // atomic per batch: a plateau query collects hundreds of rows, and a wave that waits ~2 us for every single
-    // `atomicAdd(cnt + q, 1)` spent most of a short scan doing so (1100 queries at 1 M rows / 8: 387 us).
-    int *lbuf = reinterpret_cast<int *>(smem + RANGE_STAGES * UNIT_BYTES);  // [RANGE_LANE_BUF][64 * NW]
-    int lcount = 0;
-    auto flush_lane = [&]() {
-        const int pos = atomicAdd(cnt + qg, lcount);
-        for (int i = 0; i < lcount; ++i)
-            if (pos + i < RANGE_CAP) cand[(size_t)qg * RANGE_CAP + pos + i] = lbuf[i * (64 * NW) + tid];
-        lcount = 0;
-    };
+    RangeHits<64 * NW> hits{reinterpret_cast<int *>(smem + RANGE_STAGES * UNIT_BYTES), cnt, cand, qg, tid, 0};
 #pragma unroll
     for (int i = 0; i < RANGE_STAGES - 1; ++i)
         if (i < nunits) issue_stage(i);
@@ -1159,14 +1124,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_range_kernel(
     // (the unit loop is unrolled over the ring), so the eight reads of a unit are ds_read_b128 with immediate offsets
     // awaited one by one with counted lgkmcnt: the first MFMA starts when the first fragment is there, not the last.
     unsigned foff[8];
-    {
-        const unsigned fbase = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem + (unsigned)(j * SLOTS * 16);
-#pragma unroll
-        for (int s2 = 0; s2 < 8; ++s2) {
-            foff[s2] = fbase + (unsigned)((((2 * s2 + h) ^ (j & 15))) * 16);
-            asm volatile("" : "+v"(foff[s2]));  // (opaque: otherwise hipcc re-derives it with a v_add per read)
-        }
-    }
+    fragment_addresses(foff, smem, j, h);
     static_assert(RANGE_STAGES % NCH == 0, "the ring holds whole tiles");
     auto unit = [&](auto slotc, const int it) {
         constexpr int slot = decltype(slotc)::value;
@@ -1197,19 +1155,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_range_kernel(
             for (int r = 1; r < 16; ++r) mx = fmaxf(mx, acc[r]);
             if (__any(mx > sfloor)) {
                 const int t = it / NCH;
-                const int row0 = t_begin + 32 * t + 4 * h;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    if (acc[r] > sfloor) {
-                        float a1 = acc[r];
-                        asm volatile("" : "+v"(a1));
-                        const int row = row0 + (r & 3) + 8 * (r >> 2);
-                        if (dist_from_sim(a1) <= th && row < t_end) {
-                            lbuf[lcount * (64 * NW) + tid] = t_base + row;
-                            if (++lcount == RANGE_LANE_BUF) flush_lane();
-                        }
-                    }
-                }
+                hits.collect(acc, t_begin + 32 * t + 4 * h, sfloor, th, t_end, t_base);
             }
         }
     };
@@ -1218,7 +1164,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_range_kernel(
             if (it0 + decltype(sc)::value < nunits) unit(sc, it0 + decltype(sc)::value);
         });
     }
-    if (lcount > 0) flush_lane();
+    if (hits.lcount > 0) hits.flush();
 }
 
 // exact ranking of a collected range: one wave per query, keys staged in LDS

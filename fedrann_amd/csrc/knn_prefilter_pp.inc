@@ -60,6 +60,9 @@ __global__ __launch_bounds__(512, 2) void knn_prefilter_pp_kernel(
         for (int i = 0; i < NCH * 8; ++i) b[i] = qp[2 * i + h];
     }
     // quantisation grid and the list (see knn_prefilter_kernel: the same state, one query set per wave)
+    // (A COPY of that kernel's list code, on purpose: as one struct used by both kernels it cost the one-stream shapes
+    // registers and scratch -- docs/experiments.md A-21.  A fix to share / rethreshold / flush / offer / the write-out
+    // here must be made there too.)
     const int qbits = min(20, 32 - ib);
     const unsigned QM1 = (1u << qbits) - 2u;
     const float qscale = (float)QM1, qinv = 1.0f / qscale;
@@ -173,14 +176,8 @@ __global__ __launch_bounds__(512, 2) void knn_prefilter_pp_kernel(
                         __float_as_int(av[4 * q4 + 3]));
     };
 
-    // this lane's eight fragment addresses inside a unit (k-step s reads slot (2s + h) ^ (j & 15) of row j)
-    const unsigned ring = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem;
     unsigned fa[8];
-#pragma unroll
-    for (int s8 = 0; s8 < 8; ++s8) {
-        fa[s8] = ring + (unsigned)(j * 256 + (((2 * s8 + h) ^ (j & 15)) * 16));
-        asm volatile("" : "+v"(fa[s8]));  // (opaque: otherwise hipcc re-derives it with a v_add per read)
-    }
+    fragment_addresses(fa, smem, j, h);
     f32x16 acc[TPS];
 #pragma unroll
     for (int t = 0; t < TPS; ++t)
@@ -364,6 +361,10 @@ __global__ __launch_bounds__(512, 2) void knn_prefilter_pp_kernel(
 // 0.66 of the fp16 peak with one-unit stages and a barrier per eight MFMAs), a rank of config 5 12 k (58 ms).  Here a
 // stage is eight units, a wave's turn at the pipe 64 MFMAs, and the other turn tests the stage's tiles against the
 // query's similarity floor (one max tree per tile) and gathers the rare hits in the lane's LDS buffer.
+// (The skeleton -- descriptor, issue_stage, rd / prime / mfma_turn, next_slot, the two groups' loops -- is a copy of
+// knn_prefilter_pp_kernel's with another score_turn: one function template for both changed both kernels' registers and
+// scratch, docs/experiments.md A-21.  This copy clamps an empty segment's descriptor and last row; the candidate pass's
+// work items are the plan's segments, which each hold at least one row.)
 // Grid: x = query block (256 queries), y = target segment.
 template <int DP, int U>
 __global__ __launch_bounds__(512, 2) void knn_range_pp_kernel(
@@ -419,22 +420,9 @@ __global__ __launch_bounds__(512, 2) void knn_range_pp_kernel(
                 (int)vo, (u % NCH) * 256, 0, 0);
         });
     };
-    // a lane's hits wait in its own RANGE_LANE_BUF-entry LDS buffer (behind the ring) and leave with ONE returning atomic
-    int *lbuf = reinterpret_cast<int *>(smem + 2 * STAGE_BYTES);  // [RANGE_LANE_BUF][512]
-    int lcount = 0;
-    auto flush_lane = [&]() {
-        const int pos = atomicAdd(cnt + qg, lcount);
-        for (int i = 0; i < lcount; ++i)
-            if (pos + i < RANGE_CAP) cand[(size_t)qg * RANGE_CAP + pos + i] = lbuf[i * 512 + tid];
-        lcount = 0;
-    };
-    const unsigned ring = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem;
+    RangeHits<512> hits{reinterpret_cast<int *>(smem + 2 * STAGE_BYTES), cnt, cand, qg, tid, 0};  // (behind the ring)
     unsigned fa[8];
-#pragma unroll
-    for (int s8 = 0; s8 < 8; ++s8) {
-        fa[s8] = ring + (unsigned)(j * 256 + (((2 * s8 + h) ^ (j & 15)) * 16));
-        asm volatile("" : "+v"(fa[s8]));
-    }
+    fragment_addresses(fa, smem, j, h);
     f32x16 acc[TPS];
 #pragma unroll
     for (int t = 0; t < TPS; ++t)
@@ -476,19 +464,7 @@ __global__ __launch_bounds__(512, 2) void knn_range_pp_kernel(
             static_for(std::make_integer_sequence<int, TPS>{}, [&](auto t_c) {
                 if (tl == decltype(t_c)::value) cur = acc[decltype(t_c)::value];
             });
-            const int row0 = t_begin + 32 * (it * TPS + tl) + 4 * h;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if (cur[r] > sfloor) {
-                    float a1 = cur[r];
-                    asm volatile("" : "+v"(a1));
-                    const int row = row0 + (r & 3) + 8 * (r >> 2);
-                    if (dist_from_sim(a1) <= th && row < t_end) {
-                        lbuf[lcount * 512 + tid] = t_base + row;
-                        if (++lcount == RANGE_LANE_BUF) flush_lane();
-                    }
-                }
-            }
+            hits.collect(cur, t_begin + 32 * (it * TPS + tl) + 4 * h, sfloor, th, t_end, t_base);
         }
     };
     auto next_slot = [&](const int par) __attribute__((always_inline)) {
@@ -527,5 +503,5 @@ __global__ __launch_bounds__(512, 2) void knn_range_pp_kernel(
         }
         if (nstages > 0) score_turn(nstages - 1);
     }
-    if (live && lcount > 0) flush_lane();
+    if (live && hits.lcount > 0) hits.flush();
 }
