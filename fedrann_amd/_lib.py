@@ -23,7 +23,7 @@ SYMBOLS = (
     "fdr_kmer_count_begin", "fdr_kmer_count_add", "fdr_kmer_count_finish", "fdr_reads_scan", "fdr_reads_parse",
     "fdr_kmer_output_append", "fdr_last_query_paths", "fdr_last_knn_trace", "fdr_kmer_count_export_dev",
     "fdr_kmer_count_merge_dev", "fdr_kmer_count_merge", "fdr_set_knn_capture", "fdr_last_candidates",
-    "fdr_last_range_sets", "fdr_knn_sparse",
+    "fdr_last_range_sets", "fdr_knn_sparse", "fdr_set_live_chunks",
 )
 FDR_MAX_K = 128
 KERNELS = ("embed_csr", "normalize_rows", "knn_tile", "knn_merge", "knn_prefilter", "knn_rerank",
@@ -47,7 +47,8 @@ class KnnTrace(ctypes.Structure):
             "pass_waves", "pass_wps", "pass_units", "pass_list_keys", "pass_pingpong", "pass_launches", "pass_queues",
             "pass_segments", "uncertified", "zero_queries", "range_queries", "range_chunks", "range_pp_chunks",
             "range_w8_chunks", "range_overflow", "exact_fallback", "exact_calls", "exact_queries", "exact_waves",
-            "exact_qsets", "generic", "exact_segments")]
+            "exact_qsets", "generic", "exact_segments", "pass_live", "pass_live_items_2", "pass_live_items_3",
+            "pass_live_items_4", "pass_live_items_5", "pass_live_items_6", "pass_live_dense_items")]
 
 
 class FedrannHipError(RuntimeError):
@@ -116,6 +117,7 @@ def load_library():
     L.fdr_last_candidates.argtypes = [vp, vp, i64, i32, ctypes.POINTER(i32)]
     L.fdr_last_range_sets.argtypes = [vp, i64, vp, vp, vp, vp]
     L.fdr_set_dedup_mode.argtypes = [vp, ctypes.c_int]
+    L.fdr_set_live_chunks.argtypes = [vp, ctypes.c_int]
     L.fdr_last_unique.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     L.fdr_last_prefilter_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     p64 = ctypes.POINTER(ctypes.c_int64)
@@ -410,6 +412,12 @@ class Context:
         tests) -- same results, see include/fedrann_hip.h."""
         code = {"auto": 0, "off": 1, "on": 2, "force": 3}[mode]
         self._check(self._L.fdr_set_dedup_mode(self._h, code), "fdr_set_dedup_mode")
+
+    def set_live_chunks(self, mode):
+        """Live-chunk candidate pass at d <= 128: "auto" (default), "off" or "force" (at every size; tests) -- same
+        results, see include/fedrann_hip.h."""
+        code = {"auto": 0, "off": 1, "force": 2}[mode]
+        self._check(self._L.fdr_set_live_chunks(self._h, code), "fdr_set_live_chunks")
 
     def kmer_search(self, seqs, seq_off, lib_codes, k):
         """Per-read ascending unique library indices: (indptr int64 [R+1], indices int32 [nnz])."""

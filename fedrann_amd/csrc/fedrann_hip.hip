@@ -415,6 +415,7 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float *__rest
 #include "knn_prefilter.inc"  // P1 / P2: fp16 MFMA candidate pass, merges, certificate + re-rank, range pass; fragment_addresses, RangeHits
 #include "knn_prefilter_pp.inc"  // P1 and the range pass for the 256-register shapes: the two waves of a SIMD take turns at the matrix pipe
 #include "knn_order.inc"      // P1: scan order by chunk mask (sort keys, ordered fp16 copy)
+#include "knn_prefilter_live.inc"  // P1 at d <= 128: only the query block's non-empty chunks (block masks, blocked copy)
 #include "dedup_classes.inc"  // duplicate-row classes: hash, tables, gathers, expansion
 #include "knn_generic.inc"    // d > 1024, or k > 64 / d > 512 below 8192 targets: every pair on the vector ALU
 
@@ -525,6 +526,8 @@ struct fdr_ctx {
     // stream; fdr_timing_read() sums the elapsed times of all launches since the last read
     int knn_mode = FDR_MODE_AUTO;
     int dedup_mode = FDR_DEDUP_AUTO;
+    int live_mode = FDR_LIVE_AUTO;  // fdr_set_live_chunks
+    std::vector<unsigned> live_host;  // the live-chunk plan's read-back and upload (block masks; order + ids)
     KnnCallRecord last;  // what the fdr_last_* getters report
     // fdr_set_knn_capture / fdr_last_candidates / fdr_last_range_sets: the prefilter pass's intermediate results
     struct {
@@ -754,6 +757,12 @@ FDR_EXPORT int fdr_set_dedup_mode(fdr_ctx *ctx, int mode) {
     return FDR_OK;
 }
 
+FDR_EXPORT int fdr_set_live_chunks(fdr_ctx *ctx, int mode) {
+    if (!ctx || mode < FDR_LIVE_AUTO || mode > FDR_LIVE_FORCE) return fail(FDR_E_ARG, "bad live-chunk mode");
+    ctx->live_mode = mode;
+    return FDR_OK;
+}
+
 FDR_EXPORT int fdr_timing(fdr_ctx *ctx, int enable) {
     if (!ctx) return fail(FDR_E_ARG, "null context");
     ctx->timing = enable != 0;
@@ -915,7 +924,7 @@ static size_t class_tables_tmp_bytes(size_t rows) {
     return std::max(t_sort, t_scan);
 }
 static WsEnv ws_env(const fdr_ctx *ctx) {
-    return {ctx->num_cus, ctx->knn_mode, ctx->dedup_mode, order_sort_tmp_bytes, class_tables_tmp_bytes};
+    return {ctx->num_cus, ctx->knn_mode, ctx->dedup_mode, order_sort_tmp_bytes, class_tables_tmp_bytes, ctx->live_mode};
 }
 
 FDR_EXPORT size_t fdr_knn_workspace_bytes(fdr_ctx *ctx, int64_t nq, int64_t nt, int32_t d,
@@ -1129,7 +1138,7 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     knn_call_header(ctx, FDR_TRACE_PREFILTER, dp, k, nq, nt);
     ctx->last.paths = {L.path, nq, FDR_PATH_NONE, st};  // (per query: the re-rank kernels write the codes)
 
-    const int pshape = prefilter_shape(dp, kp, nq, ctx->num_cus, nt);
+    const int pshape = prefilter_shape_live(ctx->live_mode, dp, kp, nq, ctx->num_cus, nt);
     const KnnPlan p = knn_plan(ctx->num_cus, nq, nt, d, kp, pshape);
     const KnnShape &sh = kShapes[pshape];
     fdr_knn_trace &tr = ctx->last.trace;
@@ -1180,6 +1189,14 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
         p1_t = ho_t;
         ord.perm_q = self ? perm_t : perm_q;
         p1_q = ho_q;
+        if (L.live) {  // the targets once more in blocks of (tile, chunk); the query blocks' masks (the sorted keys are the queries')
+            const long long bgroups = (long long)((nt + 31) / 32 + 4) * 32 * 16;
+            hipLaunchKernelGGL(to_half_blocked_kernel, dim3((unsigned)((bgroups + 255) / 256)), dim3(256), 0, st, d_That,
+                               (const int *)perm_t, (int)nt, bgroups, L.hb_t);
+            hipLaunchKernelGGL(live_block_masks_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(64), 0, st,
+                               (const u64 *)L.okeys_s, (int)nq, L.live_masks);
+            HIP_TRY(hipGetLastError());
+        }
     }
     const size_t lds = knn_lds_bytes(sh, kp);
     int max_seg = 1;
@@ -1190,10 +1207,90 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     if (lds > 32768)
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     Rounds r;  // (rounds on up to four queues; one queue: every launch its own timed span)
-    const int lrc = launch_rounds(ctx, p, 4, FDR_KERNEL_KNN_PREFILTER, true, st, r, [&](hipStream_t s, unsigned grid, int base) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh.nw), lds, s, p1_q, (int)nq, p1_t, (int)nt, (int)t_base, p.segs, kp,
-                           p.nq_pad, d_partial, d_shared, ib, base, p.nqb, ord FDR_DBG_ARG(dev_knobs().debug));
-    });
+    int lrc;
+    if (L.live) {
+        // Live-chunk pass: the blocks' masks come back (nqb words, one synchronisation), live_plan groups the blocks by
+        // live chunks, and every group runs in synchronised rounds of its own, segment-major -- the NL groups on their
+        // knn_prefilter_live_kernel<NL>, ascending, then the dense group on `kern`.  The shipped kernel takes a block
+        // RANGE and the dense blocks lie scattered over the order (wherever 256 rows straddle two masks), so their
+        // queries, order-table entries and bound words are gathered side by side first (live_gather_dense_kernel); one
+        // launch per contiguous run instead cost a whole scan's time per stray block: 147 ms a step at 1 M reads.
+        const int nqb = p.nqb;
+        std::vector<unsigned> &hb = ctx->live_host;
+        hb.resize((size_t)3 * nqb);
+        HIP_TRY(hipMemcpyAsync(hb.data(), L.live_masks, (size_t)nqb * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const long long per_launch = p.cohort > 0 ? p.cohort : 0;
+        const LivePlan lp = live_plan(hb.data(), nqb, p.nseg, ctx->live_mode == FDR_LIVE_FORCE ? 0 : per_launch);
+        std::copy(lp.ids.begin(), lp.ids.end(), hb.begin() + nqb);
+        for (int i = 0; i < nqb; ++i) hb[(size_t)2 * nqb + i] = (unsigned)lp.order[(size_t)i];
+        HIP_TRY(hipMemcpyAsync(L.live_ids, hb.data() + nqb, (size_t)nqb * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(L.live_order, hb.data() + 2 * (size_t)nqb, (size_t)nqb * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));  // (pageable source: the vector may be reused by the next call)
+        tr.pass_live = 1;
+        int dense_nq = 0;  // queries of the gathered dense group
+        for (const LiveGroup &g : lp.groups) {
+            if (g.nl != FDR_LIVE_DENSE) {
+                tr.pass_live_items[g.nl - FDR_LIVE_MIN_NL] = g.count * p.nseg;
+                continue;
+            }
+            tr.pass_live_dense_items = g.count * p.nseg;
+            const int last = lp.order[(size_t)(g.first + g.count - 1)];  // (ascending: only the last one can be short)
+            dense_nq = (g.count - 1) * 256 + (int)std::min<int64_t>(256, nq - (int64_t)last * 256);
+            hipLaunchKernelGGL(live_gather_dense_kernel, dim3((unsigned)g.count), dim3(256), 0, st, p1_q, ord.perm_q,
+                               (const unsigned *)d_shared, (int)nq, (const int *)(L.live_order + g.first), L.live_hq,
+                               L.live_perm, L.live_tau);
+        }
+        for (int nl = FDR_LIVE_MIN_NL; nl <= FDR_LIVE_MAX_NL; ++nl)
+            if (live_lds_bytes(nl) > 32768)
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kLiveKernels[nl - FDR_LIVE_MIN_NL]),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)live_lds_bytes(nl)));
+        const int nqueues = p.cohort > 0 ? std::max(1, std::min(p.queues, 4)) : 1;
+        hipStream_t qs[4] = {st, st, st, st};
+        if (nqueues > 1) {
+            if (!ctx->aux_ev[0]) {
+                for (hipStream_t &a : ctx->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&a, hipStreamNonBlocking));
+                for (hipEvent_t &e : ctx->aux_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            }
+            for (int q = 1; q < nqueues; ++q) qs[q] = ctx->aux_stream[q - 1];
+        }
+        if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_PREFILTER, st))) return trc;
+        if (nqueues > 1) {
+            HIP_TRY(hipEventRecord(ctx->aux_ev[0], st));
+            for (int q = 1; q < nqueues; ++q) HIP_TRY(hipStreamWaitEvent(qs[q], ctx->aux_ev[0], 0));
+        }
+        int li = 0;  // launch li goes to queue li % nqueues
+        for (const LiveGroup &g : lp.groups) {
+            const long long n_items = (long long)g.count * p.nseg;
+            const long long per = per_launch > 0 ? per_launch : n_items;
+            for (long long base = 0; base < n_items; base += per, ++li) {
+                const hipStream_t ls = qs[li % nqueues];
+                const unsigned grid = (unsigned)std::min(per, n_items - base);
+                if (g.nl == FDR_LIVE_DENSE)
+                    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh.nw), lds, ls, (const _Float16 *)L.live_hq, dense_nq, p1_t,
+                                       (int)nt, (int)t_base, p.segs, kp, p.nq_pad, d_partial, L.live_tau, ib, (int)base, g.count,
+                                       OrderArgs{ord.perm_t, (const int *)L.live_perm} FDR_DBG_ARG(dev_knobs().debug));
+                else
+                    hipLaunchKernelGGL(kLiveKernels[g.nl - FDR_LIVE_MIN_NL], dim3(grid), dim3(512), live_lds_bytes(g.nl), ls,
+                                       p1_q, (int)nq, (const _Float16 *)L.hb_t, (int)nt, (int)t_base, p.segs, kp, p.nq_pad,
+                                       d_partial, d_shared, ib, (int)base, g.count, (const int *)(L.live_order + g.first),
+                                       (const unsigned *)L.live_ids, ord);
+            }
+        }
+        HIP_TRY(hipGetLastError());
+        r.launches = li;
+        r.queues = nqueues;
+        for (int q = 1; q < nqueues; ++q) {
+            HIP_TRY(hipEventRecord(ctx->aux_ev[q], qs[q]));
+            HIP_TRY(hipStreamWaitEvent(st, ctx->aux_ev[q], 0));
+        }
+        lrc = timing_end(ctx, FDR_KERNEL_KNN_PREFILTER, st);
+    } else {
+        lrc = launch_rounds(ctx, p, 4, FDR_KERNEL_KNN_PREFILTER, true, st, r, [&](hipStream_t s, unsigned grid, int base) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh.nw), lds, s, p1_q, (int)nq, p1_t, (int)nt, (int)t_base, p.segs, kp,
+                               p.nq_pad, d_partial, d_shared, ib, base, p.nqb, ord FDR_DBG_ARG(dev_knobs().debug));
+        });
+    }
     ctx->last.pass.launches = r.launches;
     ctx->last.pass.queues = r.queues;
     tr.pass_launches = r.launches;

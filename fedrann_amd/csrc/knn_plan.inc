@@ -498,3 +498,64 @@ static KnnPlan knn_plan_compute(int num_cus, int64_t nq, int64_t nt, int d, int 
     return p;
 }
 
+
+// ---- live-chunk groups of the d <= 128 candidate pass (knn_prefilter_live.inc) ---------------------------------------
+// A 256-query block whose queries are all zero outside NL of the eight 16-component chunks runs on
+// knn_prefilter_live_kernel<NL> (NL = 2 .. 6; a block with fewer live chunks is padded to 2); blocks with seven or eight
+// live chunks keep the dense kernel.  The blocks of one instance form a group; a group's work items are (segment, block
+// of the group), segment-major, and run in synchronised rounds of their own.  A group with fewer work items than
+// `min_items` (one launch) joins the next larger NL -- the last live group joins the dense one -- and its blocks' ids are
+// padded with chunks that are empty in the block, which is harmless: the kernel adds their true products, +0.
+#define FDR_LIVE_MIN_NL 2
+#define FDR_LIVE_MAX_NL 6
+#define FDR_LIVE_DENSE 8  // LiveGroup::nl of the dense group
+struct LiveGroup {
+    int nl;            // chunks per tile the group's kernel multiplies (FDR_LIVE_DENSE: the dense kernel)
+    int first, count;  // its blocks: order[first .. first + count), ascending
+};
+struct LivePlan {
+    std::vector<int> order;       // every query block once, group by group
+    std::vector<unsigned> ids;    // [block]: its group's nl chunk ids, ascending, four bits each (dense group: 0x76543210)
+    std::vector<LiveGroup> groups;  // ascending nl; the dense group last
+};
+static int live_popcount8(unsigned m) {
+    int c = 0;
+    for (int b = 0; b < 8; ++b) c += (m >> b) & 1;
+    return c;
+}
+// masks[b]: bit c set <=> chunk c is non-empty in some query of block b
+static LivePlan live_plan(const unsigned *masks, int nqb, int nseg, long long min_items) {
+    LivePlan P;
+    P.order.reserve((size_t)nqb);
+    P.ids.assign((size_t)nqb, 0x76543210u);
+    std::vector<int> of_nl[FDR_LIVE_DENSE + 1];
+    for (int b = 0; b < nqb; ++b) {
+        const int pc = live_popcount8(masks[b] & 0xffu);
+        of_nl[pc > FDR_LIVE_MAX_NL ? FDR_LIVE_DENSE : std::max(pc, FDR_LIVE_MIN_NL)].push_back(b);
+    }
+    for (int nl = FDR_LIVE_MIN_NL; nl <= FDR_LIVE_MAX_NL; ++nl) {  // small groups move up
+        std::vector<int> &g = of_nl[nl];
+        if (g.empty() || (long long)g.size() * nseg >= min_items) continue;
+        std::vector<int> &up = of_nl[nl < FDR_LIVE_MAX_NL ? nl + 1 : FDR_LIVE_DENSE];
+        std::vector<int> merged(g.size() + up.size());
+        std::merge(g.begin(), g.end(), up.begin(), up.end(), merged.begin());
+        up.swap(merged);
+        g.clear();
+    }
+    for (int nl = FDR_LIVE_MIN_NL; nl <= FDR_LIVE_DENSE; ++nl) {
+        const std::vector<int> &g = of_nl[nl];
+        if (g.empty()) continue;
+        P.groups.push_back(LiveGroup{nl, (int)P.order.size(), (int)g.size()});
+        for (int b : g) {
+            P.order.push_back(b);
+            if (nl == FDR_LIVE_DENSE) continue;
+            unsigned m = masks[b] & 0xffu;
+            for (int c = 0; c < 8 && live_popcount8(m) < nl; ++c) m |= 1u << c;  // pad with the lowest empty chunks
+            unsigned packed = 0;
+            for (int c = 0, i = 0; c < 8; ++c)
+                if ((m >> c) & 1) packed |= (unsigned)c << (4 * i++);
+            P.ids[(size_t)b] = packed;
+        }
+    }
+    return P;
+}

@@ -45,7 +45,23 @@ struct WsEnv {
     int num_cus, knn_mode, dedup_mode;
     size_t (*order_sort_tmp)(size_t rows);    // radix sort of `rows` (u64, int) pairs over 40 key bits
     size_t (*class_tables_tmp)(size_t rows);  // the larger of: radix sort of `rows` pairs over 64 bits, inclusive int scan
+    int live_mode = FDR_LIVE_AUTO;            // fdr_set_live_chunks
 };
+
+// The live-chunk candidate pass (knn_prefilter_live.inc).  FDR_LIVE_AUTO_ON: whether AUTO takes it where it applies --
+// decided by measurement, docs/experiments.md A-22: 96.5 -> 70.9 ms per step at 1 M reads, so it does.
+#define FDR_LIVE_AUTO_ON 1
+// the candidate pass's shape: FORCE puts every d <= 128, K' <= 32 call on the eight-wave four-unit shape
+static int prefilter_shape_live(int live_mode, int dp, int kp, int64_t nq, int num_cus, int64_t nt) {
+    if (live_mode == FDR_LIVE_FORCE && dp == 128 && kp <= 32) return FDR_P128_W8U4;
+    return prefilter_shape(dp, kp, nq, num_cus, nt);
+}
+// ... and whether a call of that shape and plan groups its query blocks by live chunks: only where the shipped
+// eight-wave shape runs in synchronised rounds on two queues (FORCE: wherever the shape was forced)
+static bool live_chunks_wanted(int live_mode, int shape, const KnnPlan &pp) {
+    if (live_mode == FDR_LIVE_OFF || shape != FDR_P128_W8U4) return false;
+    return live_mode == FDR_LIVE_FORCE || (FDR_LIVE_AUTO_ON && pp.cohort > 0 && pp.queues == 2);
+}
 
 // mode: FDR_MODE_AUTO uses the fp16 prefilter whenever it applies (d <= 512, k + 8 <= 64) and the target set is large
 // enough to pay for it; fdr_set_knn_mode / FDR_KNN_MODE=exact|prefilter override it.
@@ -89,6 +105,16 @@ struct PrefilterWs {
     int *ovals, *perm_t, *perm_q;
     ws_half *ho_t, *ho_q;
     char *otmp;
+    // live-chunk pass only (else null): the ordered fp16 targets in blocks of (tile, chunk), the query blocks' chunk
+    // masks, and the plan made from them (live_plan: blocks group by group, chunk ids per block)
+    int live;
+    ws_half *hb_t;
+    unsigned *live_masks, *live_ids;
+    int *live_order;
+    // ... and the dense group's queries side by side (the shipped kernel takes a block RANGE): rows, order table, bounds
+    ws_half *live_hq;
+    int *live_perm;
+    unsigned *live_tau;
 };
 
 static PrefilterWs prefilter_ws(const WsEnv &env, void *base, int64_t nq, int64_t nt, int d, int k,
@@ -100,7 +126,8 @@ static PrefilterWs prefilter_ws(const WsEnv &env, void *base, int64_t nq, int64_
     L.rchunk = (int)std::min<int64_t>(nq, 32768);  // range pass: queries per launch
     const size_t exact_all = knn_plan(env.num_cus, nq, nt, d, k).total_bytes;
     const int dp = padded_dim(d);
-    const KnnPlan pp = knn_plan(env.num_cus, nq, nt, d, L.kp, prefilter_shape(dp, L.kp, nq, env.num_cus, nt));
+    const int pshape = prefilter_shape_live(env.live_mode, dp, L.kp, nq, env.num_cus, nt);
+    const KnnPlan pp = knn_plan(env.num_cus, nq, nt, d, L.kp, pshape);
     // (a later call on fewer unique rows may plan more, shorter segments: room for the largest such plan)
     // (the bound words and the lists padded for the widest query block: a later call may choose the other shape)
     const size_t pre = std::max(pp.total_bytes, pp.bits_bytes + align256((size_t)(nq + 512) * 4) +
@@ -128,7 +155,9 @@ static PrefilterWs prefilter_ws(const WsEnv &env, void *base, int64_t nq, int64_
     L.cnt = A.take<int>((size_t)L.rchunk);
     L.rcand = A.take<int>((size_t)L.rchunk * RANGE_CAP);
     L.path = A.take<uint8_t>((size_t)nq);
-    L.ordered = pp.cohort > 0 || dev_knobs().ordered != 0;  // (the sizes at which the pass runs in synchronised rounds)
+    L.live = live_chunks_wanted(env.live_mode, pshape, pp);
+    // (the sizes at which the pass runs in synchronised rounds; the live-chunk pass needs the order)
+    L.ordered = pp.cohort > 0 || dev_knobs().ordered != 0 || L.live;
     if (L.ordered) {
         const size_t nmax = (size_t)std::max(nq, nt);
         L.okeys = A.take<u64>(nmax);
@@ -140,6 +169,17 @@ static PrefilterWs prefilter_ws(const WsEnv &env, void *base, int64_t nq, int64_
         L.ho_q = A.take<ws_half>((size_t)nq * dp);
         L.otmp_bytes = align256(env.order_sort_tmp(nmax));
         L.otmp = A.take<char>(L.otmp_bytes);
+    }
+    if (L.live) {
+        // whole tiles of 32 rows, and four tiles more: a segment's last stage fetches up to three tiles past its end
+        L.hb_t = A.take<ws_half>(((size_t)(nt + 31) / 32 + 4) * 32 * dp);
+        const size_t nqb = (size_t)(nq + 255) / 256;
+        L.live_masks = A.take<unsigned>(nqb);
+        L.live_ids = A.take<unsigned>(nqb);
+        L.live_order = A.take<int>(nqb);
+        L.live_hq = A.take<ws_half>(nqb * 256 * dp);
+        L.live_perm = A.take<int>(nqb * 256);
+        L.live_tau = A.take<unsigned>(nqb * 256);
     }
     L.total = A.at;
     return L;

@@ -207,6 +207,15 @@ int fdr_set_knn_mode(fdr_ctx *ctx, int mode);
 #define FDR_DEDUP_ON 2
 #define FDR_DEDUP_FORCE 3
 int fdr_set_dedup_mode(fdr_ctx *ctx, int mode);
+/* Live-chunk candidate pass: at d <= 128 and K' <= 32 the fp16 pass of a 256-query block skips
+ * the 16-component chunks that are empty in every query of the block (knn_prefilter_live_kernel<NL>; blocks with
+ * seven or eight live chunks keep the dense kernel) -- the same bits either way.  AUTO (default): where the
+ * eight-wave shape runs in synchronised rounds.  OFF: never.  FORCE: at every size, on the eight-wave shape (the
+ * parity tests). */
+#define FDR_LIVE_AUTO 0
+#define FDR_LIVE_OFF 1
+#define FDR_LIVE_FORCE 2
+int fdr_set_live_chunks(fdr_ctx *ctx, int mode);
 /* Unique target / query rows the most recent k-NN call
  * actually searched (= the row counts when the call found too few duplicates to bother). */
 int fdr_last_unique(fdr_ctx *ctx, int *unique_targets, int *unique_queries);
@@ -254,6 +263,10 @@ typedef struct fdr_knn_trace {
     int32_t exact_waves, exact_qsets;  /* shape of the last one: waves per workgroup, query sets per wave (0: none) */
     int32_t generic;           /* 1: the generic kernel ran */
     int32_t exact_segments;    /* target segments of the last exact-kernel search (0: none) */
+    /* live-chunk candidate pass (prefilter only) */
+    int32_t pass_live;         /* 1: the pass ran grouped by live chunks (knn_prefilter_live_kernel<NL> + the dense kernel) */
+    int32_t pass_live_items[5];    /* its work items (query block x segment) on the NL = 2, 3, 4, 5, 6 instances */
+    int32_t pass_live_dense_items; /* ... and on the dense kernel (blocks with seven or eight live chunks) */
 } fdr_knn_trace;
 int fdr_last_knn_trace(fdr_ctx *ctx, fdr_knn_trace *out);
 /* Prefilter mode only: number of query rows of the most recent k-NN call whose candidate set could
