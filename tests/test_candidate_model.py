@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import _candidate_model as M
+import _live_rows as L
 from test_gpu_parity import _adversarial_rows
 
 KINDS = ("fp16_midpoints", "fp16_subnormals", "dense")
@@ -149,6 +150,108 @@ def test_range_checker(mid_set):
     big = np.full(12, 2000, np.int32)  # (more than the model's sets hold: |B| < count)
     with pytest.raises(AssertionError, match="outside"):
         M.check_ranges(model, qs, theta, big, rows, 20)
+
+
+# ---- the live-chunk pass (knn_prefilter_live_kernel<NL>): the GPU tests' inputs can see its faults -------------------
+LIVE_FAULTS = ("drop", "swap", "neighbour")
+
+
+def _emulate_live_pass(model, ids, kp, qbits, fault=None, nl=None):
+    """The live-chunk pass over the model's fp16 rows [n, 128], every row a query: the rows in scan order, blocks of 256
+    queries, block b multiplying only the chunks ids[b] (ascending ids; float64 sums), the kp targets of smallest
+    d = 1 - clamp(s, 0, 1) keyed on the device's grid.  `fault`, applied to every block that runs as instance `nl`:
+      "drop"       one chunk that is non-empty in the block is left out of its ids;
+      "swap"       the two 8-component halves of one such chunk change places in the block's query fragments;
+      "neighbour"  the block reads the next block's packed id word (the last block: the one before), nl nibbles of it
+                   -- ids past the neighbour's own read as chunk 0, as the zero nibbles of the word would."""
+    H = model.H.astype(np.float64)
+    n = H.shape[0]
+    order = L.scan_order(model.X)
+    masks = L.block_masks(model.X)
+    assert len(ids) == len(masks)
+    keys = np.empty((n, kp), np.uint64)
+    q = M.qm1(qbits)
+    for b, own in enumerate(ids):
+        rows = order[256 * b:256 * b + 256]
+        Q, use = H[rows], list(own)
+        if fault is not None and len(own) == nl:
+            live = [c for c in own if (int(masks[b]) >> c) & 1]
+            if fault == "drop":
+                use.remove(live[0])
+            elif fault == "swap":
+                c = live[0]
+                Q = Q.copy()
+                Q[:, 16 * c:16 * c + 8], Q[:, 16 * c + 8:16 * c + 16] = H[rows, 16 * c + 8:16 * c + 16], H[rows, 16 * c:16 * c + 8]
+            elif fault == "neighbour":
+                other = ids[b + 1] if b + 1 < len(ids) else ids[b - 1]
+                use = (list(other) + [0] * 8)[:nl]
+            else:
+                raise ValueError(fault)
+        s = np.zeros((len(rows), n))
+        for c in use:
+            s += Q[:, 16 * c:16 * c + 16] @ H[:, 16 * c:16 * c + 16].T
+        d = 1.0 - np.clip(s, 0.0, 1.0)
+        top = np.argsort(d, axis=1, kind="stable")[:, :kp]
+        dq = (np.float32(q) - np.rint((1 - np.take_along_axis(d, top, 1)) * q).astype(np.float32)) / np.float32(q)
+        keys[rows] = (dq.astype(np.float32).view(np.uint32).astype(np.uint64) << np.uint64(32)) | \
+            (top + model.t_base).astype(np.uint64)
+    return keys
+
+
+def _live_model(oracle, E, d):
+    Eh, _, zero = oracle.normalize(E)
+    X = np.zeros((E.shape[0], 128), np.float32)
+    X[:, :Eh.shape[1]] = Eh
+    return M.Model(X, zero, d)
+
+
+def _faults_are_seen(model, ids, nls, faults, tag):
+    n = model.nt
+    keys = _emulate_live_pass(model, ids, 32, 20)
+    rep = M.check_lists(model, keys, 20, np.arange(n), complete=np.arange(n))
+    assert rep["lists"] == n - int(model.zero.sum()) and rep["completeness_min_gap"] >= 0, (tag, rep)
+    for nl in nls:
+        assert any(len(b) == nl for b in ids), (tag, nl, [len(b) for b in ids])
+        for fault in faults:
+            bad = _emulate_live_pass(model, ids, 32, 20, fault=fault, nl=nl)
+            with pytest.raises(AssertionError):
+                M.check_lists(model, bad, 20, np.arange(n), complete=np.arange(n))
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("d", [16, 32, 48, 64, 80, 96, 40, 100])
+def test_live_chunk_faults_are_visible_on_dense_signed_rows(oracle, kind, d):
+    """Set 1 of tests/test_gpu_live_chunks.py at 1 200 rows: every block holds all ceil(d / 16) chunks (one chunk: run
+    as two, with a padded id; seven: the dense kernel, no live instance).  The fault-free emulation passes every check;
+    a dropped chunk and swapped halves fail them.  Where every block carries the same ids, reading a neighbour's changes
+    nothing (asserted: the emulation returns the same keys) -- that fault is set 2's to show."""
+    rng = np.random.default_rng(d + 7 * len(kind))
+    model = _live_model(oracle, _adversarial_rows(kind, 1200, d, rng), d)
+    ids = L.block_ids(model.X)
+    nch = -(-d // 16)
+    want = list(range(8)) if nch >= 7 else list(range(max(nch, 2)))
+    # (the sparse kinds' first block, the rows of fewest chunks, may lack a chunk where the last one is half full)
+    assert ids[-1] == want and (kind != "dense" or all(b == want for b in ids)), (ids, want)
+    if nch >= 7:
+        _faults_are_seen(model, ids, (), (), "%s-%d" % (kind, d))
+        return
+    _faults_are_seen(model, ids, (len(want),), ("drop", "swap"), "%s-%d" % (kind, d))
+    if all(b == want for b in ids):
+        same = _emulate_live_pass(model, ids, 32, 20, fault="neighbour", nl=len(want))
+        assert np.array_equal(same, _emulate_live_pass(model, ids, 32, 20))
+
+
+def test_live_chunk_faults_are_visible_on_signed_mask_classes(oracle):
+    """Set 2 at 2 000 rows, the class sizes chosen so that its eight blocks run as 3, 2, 3, 5, 4, 5, dense and 6 (the
+    first holds the zero rows, the lonely rows and the start of the two-chunk class; two straddle a class boundary):
+    every instance NL = 2 .. 6 has a block, and each of the three faults on each NL fails a check."""
+    rng = np.random.default_rng(2208)
+    E, _ = L.signed_classes(rng, sizes=(402, 300, 468, 300, 420), lonely=100, zeros=10)
+    assert E.shape[0] == 2000
+    model = _live_model(oracle, E, 128)
+    ids = L.block_ids(model.X)
+    assert [len(b) for b in ids] == [3, 2, 3, 5, 4, 5, 8, 6], ids
+    _faults_are_seen(model, ids, (2, 3, 4, 5, 6), LIVE_FAULTS, "signed classes")
 
 
 def test_rounding_helpers():
