@@ -491,6 +491,22 @@ struct KnnCallRecord {
     fdr_knn_trace trace = {};  // fdr_last_knn_trace: the kernels the call ran
 };
 
+// The arguments of a k-NN call: nq query rows against nt target rows numbered from t_base, k neighbours each.
+struct KnnArgs {
+    const float *Qhat;  // queries, normalised (normalize_rows_kernel's layout), and their all-zero flags
+    const uint8_t *qzero;
+    int64_t nq;
+    const float *That;  // targets, likewise
+    const uint8_t *tzero;
+    int64_t nt, t_base;
+    int d, k;
+    int32_t *idx;  // [nq, k] results
+    float *dist;
+    void *ws;
+    size_t ws_bytes;
+    hipStream_t st;
+};
+
 struct fdr_ctx {
     int device = 0;
     int num_cus = 256;
@@ -527,7 +543,7 @@ struct fdr_ctx {
     int knn_mode = FDR_MODE_AUTO;
     int dedup_mode = FDR_DEDUP_AUTO;
     int live_mode = FDR_LIVE_AUTO;  // fdr_set_live_chunks
-    std::vector<unsigned> live_host;  // the live-chunk plan's read-back and upload (block masks; order + ids)
+    std::vector<unsigned> live_host;  // the live-chunk plan's read-back: the query blocks' masks
     KnnCallRecord last;  // what the fdr_last_* getters report
     // fdr_set_knn_capture / fdr_last_candidates / fdr_last_range_sets: the prefilter pass's intermediate results
     struct {
@@ -1001,21 +1017,23 @@ static int no_kernel(int shape) {
                 shape);
 }
 
-// Launches a plan's nqb * nseg work items: in one launch, or (p.cohort > 0: knn_plan_compute) in synchronised rounds of
-// p.cohort workgroups dealt round-robin to at most max_queues queues -- the caller's stream and ctx->aux_stream[] -- so
-// that the workgroups of a later launch take the slots the stragglers of an earlier one have freed (one queue: every
-// launch ends with its slowest workgroup while the rest of the chip idles).  launch(stream, workgroups, first item)
-// queues one launch.  Timed as one `kind` span over all launches when they overlap on several queues (their own spans
-// would count the same time twice), else a span per launch (span_each) or one around them all.
-struct Rounds {
-    int launches = 0, queues = 0;
-};
+#include "knn_debug.inc"  // development builds: the kernels' counters and stamps after a pass
+
+// Launches a pass's work items -- `items` per group; a plain pass is one group of p.nqb * p.nseg -- group by group: each
+// in one launch, or (p.cohort > 0: knn_plan_compute) in synchronised rounds of p.cohort workgroups dealt round-robin to
+// at most max_queues queues -- the caller's stream and ctx->aux_stream[] -- so that the workgroups of a later launch
+// take the slots the stragglers of an earlier one have freed (one queue: every launch ends with its slowest workgroup
+// while the rest of the chip idles).  The launches are round_schedule's (knn_plan.inc); a single one stays on the
+// caller's stream.  launch(stream, workgroups, first item, group) queues one.  Timed as one `kind` span over all launches
+// when they overlap on several queues (their own spans would count the same time twice), else a span per launch
+// (span_each) or one around them all.
+struct Rounds { int launches = 0, queues = 0; };
 template <class Launch>
-static int launch_rounds(fdr_ctx *ctx, const KnnPlan &p, int max_queues, int kind, bool span_each, hipStream_t st,
-                         Rounds &r, Launch launch) {
-    const long long n_items = (long long)p.nqb * p.nseg;
-    const long long per_launch = p.cohort > 0 ? p.cohort : n_items;
-    const int nqueues = p.cohort > 0 && n_items > per_launch ? std::max(1, std::min(p.queues, max_queues)) : 1;
+static int launch_rounds(fdr_ctx *ctx, const KnnPlan &p, const std::vector<long long> &items, int max_queues, int kind,
+                         bool span_each, hipStream_t st, Rounds &r, Launch launch) {
+    const int dealt = p.cohort > 0 ? std::max(1, std::min(p.queues, max_queues)) : 1;
+    const std::vector<RoundLaunch> sched = round_schedule(items, p.cohort > 0 ? p.cohort : 0, dealt);
+    const int nqueues = sched.size() > 1 ? dealt : 1;
     hipStream_t qs[4] = {st, st, st, st};
     if (nqueues > 1) {
         if (!ctx->aux_ev[0]) {
@@ -1031,15 +1049,14 @@ static int launch_rounds(fdr_ctx *ctx, const KnnPlan &p, int max_queues, int kin
         HIP_TRY(hipEventRecord(ctx->aux_ev[0], st));
         for (int q = 1; q < nqueues; ++q) HIP_TRY(hipStreamWaitEvent(qs[q], ctx->aux_ev[0], 0));
     }
-    int li = 0;  // launch li goes to queue li % nqueues
-    for (long long base = 0; base < n_items; base += per_launch, ++li) {
-        const hipStream_t ls = qs[li % nqueues];
+    for (const RoundLaunch &l : sched) {
+        const hipStream_t ls = qs[l.queue];
         if (!one_span && (trc = timing_begin(ctx, kind, ls))) return trc;
-        launch(ls, (unsigned)std::min(per_launch, n_items - base), (int)base);
+        launch(ls, (unsigned)l.grid, l.base, l.group);
         if (!one_span && (trc = timing_end(ctx, kind, ls))) return trc;
     }
     HIP_TRY(hipGetLastError());
-    r.launches = li;
+    r.launches = (int)sched.size();
     r.queues = nqueues;
     for (int q = 1; q < nqueues; ++q) {  // `st` waits for everything the other queues have been given
         HIP_TRY(hipEventRecord(ctx->aux_ev[q], qs[q]));
@@ -1050,127 +1067,101 @@ static int launch_rounds(fdr_ctx *ctx, const KnnPlan &p, int max_queues, int kin
 
 // The argument checks of a k-NN call, before anything is routed or recorded.  (The workspace's SIZE is checked by the
 // path that lays it out.)  Returns FDR_OK for nq == 0 whatever the pointers: the callers launch nothing then.
-static int check_knn_args(const float *d_Qhat, const uint8_t *d_qzero, int64_t nq, const float *d_That,
-                          const uint8_t *d_tzero, int64_t nt, int64_t t_base, int d, int k, const int32_t *d_idx,
-                          const float *d_dist, const void *d_ws) {
-    const int dp = fdr_padded_dim(d);
-    if (dp < 0) return fail(FDR_E_ARG, "knn: dimension %d unsupported (1..%d)", d, FDR_MAX_DIM);
-    if (k < 1 || k > FDR_MAX_K) return fail(FDR_E_ARG, "knn: k=%d, d=%d outside the MFMA kernels' shapes", k, d);
-    if (nq < 0 || nt < k) return fail(FDR_E_ARG, "knn: need n_targets (%lld) >= k (%d)", (long long)nt, k);
-    if (nt + t_base > 0x7fffffffll || nq > 0x7fffffffll) return fail(FDR_E_ARG, "knn: row numbers exceed int32");
-    if (nq == 0) return FDR_OK;
-    const bool need_ws = knn_route(dp, k, nt) != FDR_ROUTE_GENERIC;  // (the generic kernel needs no scratch)
-    if (!d_Qhat || !d_qzero || !d_That || !d_tzero || !d_idx || !d_dist || (need_ws && !d_ws))
+static int check_knn_args(fdr_ctx *, const KnnArgs &a) {
+    const int dp = fdr_padded_dim(a.d);
+    if (dp < 0) return fail(FDR_E_ARG, "knn: dimension %d unsupported (1..%d)", a.d, FDR_MAX_DIM);
+    if (a.k < 1 || a.k > FDR_MAX_K) return fail(FDR_E_ARG, "knn: k=%d, d=%d outside the MFMA kernels' shapes", a.k, a.d);
+    if (a.nq < 0 || a.nt < a.k) return fail(FDR_E_ARG, "knn: need n_targets (%lld) >= k (%d)", (long long)a.nt, a.k);
+    if (a.nt + a.t_base > 0x7fffffffll || a.nq > 0x7fffffffll) return fail(FDR_E_ARG, "knn: row numbers exceed int32");
+    if (a.nq == 0) return FDR_OK;
+    const bool need_ws = knn_route(dp, a.k, a.nt) != FDR_ROUTE_GENERIC;  // (the generic kernel needs no scratch)
+    if (!a.Qhat || !a.qzero || !a.That || !a.tzero || !a.idx || !a.dist || (need_ws && !a.ws))
         return fail(FDR_E_ARG, "knn: null device pointer");
     return FDR_OK;
 }
 static_assert(FDR_MAX_K == FDR_EXACT_MAX_K, "every k the generic kernel takes, the exact MFMA pass takes from 8192 targets");
 
-static int launch_knn_exact(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero, int64_t nq,
-                      const float *d_That, const uint8_t *d_tzero, int64_t nt, int64_t t_base,
-                      int d, int k, int32_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes,
-                      hipStream_t st) {
-    if (nq == 0) return FDR_OK;  // (an empty call is recorded as an exact one and launches nothing)
-    const KnnPlan p = knn_plan(ctx->num_cus, nq, nt, d, k);
-    if (ws_bytes < p.total_bytes)
-        return fail(FDR_E_ARG, "knn: workspace %zu < required %zu bytes", ws_bytes, p.total_bytes);
+static int launch_knn_exact(fdr_ctx *ctx, const KnnArgs &a) {
+    if (a.nq == 0) return FDR_OK;  // (an empty call is recorded as an exact one and launches nothing)
+    const hipStream_t st = a.st;
+    const int k = a.k;
+    const KnnPlan p = knn_plan(ctx->num_cus, a.nq, a.nt, a.d, k);
+    if (a.ws_bytes < p.total_bytes) return fail(FDR_E_ARG, "knn: workspace %zu < required %zu bytes", a.ws_bytes, p.total_bytes);
     const TileKernel kern = KnnKernels::tile[p.shape];
     if (!kern) return no_kernel(p.shape);
-    unsigned *d_bits = reinterpret_cast<unsigned *>(d_ws);
-    unsigned *d_shared = reinterpret_cast<unsigned *>(static_cast<char *>(d_ws) + p.bits_bytes);
-    u64 *d_partial = reinterpret_cast<u64 *>(static_cast<char *>(d_ws) + p.bits_bytes + p.shared_bytes);
-    hipLaunchKernelGGL(pack_zero_bits_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st,
-                       d_tzero, (int)nt, d_bits, d_shared, p.nq_pad);
+    const PlanRegions R = plan_regions(a.ws, p);
+    hipLaunchKernelGGL(pack_zero_bits_kernel, dim3((unsigned)((a.nt + 255) / 256)), dim3(256), 0, st,
+                       a.tzero, (int)a.nt, R.bits, R.shared, p.nq_pad);
     HIP_TRY(hipGetLastError());
     const KnnShape &sh = kShapes[p.shape];
     const size_t lds = knn_lds_bytes(sh, k);
-    if (lds > 160 * 1024) return fail(FDR_E_ARG, "knn: k=%d, d=%d needs %zu B of LDS (> 160 KiB)", k, d, lds);
+    if (lds > 160 * 1024) return fail(FDR_E_ARG, "knn: k=%d, d=%d needs %zu B of LDS (> 160 KiB)", k, a.d, lds);
     ctx->last.trace.exact_calls++;
-    ctx->last.trace.exact_queries += (int32_t)nq;
+    ctx->last.trace.exact_queries += (int32_t)a.nq;
     ctx->last.trace.exact_waves = sh.nw;
     ctx->last.trace.exact_qsets = sh.nq;
     ctx->last.trace.exact_segments = p.nseg;
-    const int dbg = dev_knobs().debug;  // (development builds only; 0 in the release library)
-    (void)dbg;
+    [[maybe_unused]] const int dbg = dev_knobs().debug;  // (development builds only; 0 in the release library)
     const int qcap = knn_qcap(sh, k);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     Rounds r;  // (rounds on at most two queues, like the prefilter pass)
-    int trc = launch_rounds(ctx, p, 2, FDR_KERNEL_KNN_TILE, false, st, r, [&](hipStream_t s, unsigned grid, int base) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh.nw), lds, s, d_Qhat, d_qzero, (int)nq, d_That, d_bits, (int)nt,
-                           (int)t_base, p.segs, k, p.nq_pad, d_partial, d_shared, qcap, base, p.nqb FDR_DBG_ARG(dbg));
+    int trc = launch_rounds(ctx, p, {(long long)p.nqb * p.nseg}, 2, FDR_KERNEL_KNN_TILE, false, st, r,
+                            [&](hipStream_t s, unsigned grid, int base, int) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh.nw), lds, s, a.Qhat, a.qzero, (int)a.nq, a.That, R.bits, (int)a.nt,
+                           (int)a.t_base, p.segs, k, p.nq_pad, R.partial, R.shared, qcap, base, p.nqb FDR_DBG_ARG(dbg));
     });
     if (trc) return trc;
-#ifdef FDR_DEBUG_COUNTERS
-    if (dbg & 2) {
-        unsigned long long c[8];
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpyFromSymbol(c, HIP_SYMBOL(g_dbg_counters), sizeof(c)));
-        fprintf(stderr, "[fdr debug] grid %d x %d  calls(with tile) %llu  hot-episodes... update_calls=%llu rounds=%llu flushes=%llu flush_iters=%llu rescans=%llu\n",
-                p.nqb, p.nseg, c[0], c[0], c[1], c[2], c[3], c[4]);
-        unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_counters), z, sizeof(z)));
-    }
-#endif
+    if ((trc = dump_debug_counters(st, "tile", p, "update calls, rounds, flushes, flush iterations, rescans, -"))) return trc;
     if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_MERGE, st))) return trc;
-    if (k <= FDR_FAST_MAX_K)
-        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st,
-                           (const u64 *)d_partial, p.nseg, (int)nq, p.nq_pad, k, d_idx, d_dist);
-    else
-        hipLaunchKernelGGL(knn_merge_wide_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st,
-                           (const u64 *)d_partial, p.nseg, (int)nq, p.nq_pad, k, d_idx, d_dist);
+    hipLaunchKernelGGL(k <= FDR_FAST_MAX_K ? knn_merge_kernel : knn_merge_wide_kernel, dim3((unsigned)((a.nq + 3) / 4)),
+                       dim3(256), 0, st, (const u64 *)R.partial, p.nseg, (int)a.nq, p.nq_pad, k, a.idx, a.dist);
     HIP_TRY(hipGetLastError());
     return timing_end(ctx, FDR_KERNEL_KNN_MERGE, st);
 }
 
 // ---- prefilter mode: fp16 pass -> certificate + exact re-rank -> exact pass for the rest -------
-static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero, int64_t nq,
-                                const float *d_That, const uint8_t *d_tzero, int64_t nt, int64_t t_base,
-                                int d, int k, int32_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes,
-                                hipStream_t st) {
-    // the queries ARE the targets (row i of one is row i of the other): one fp16 copy serves both sides
-    const bool self = d_Qhat == d_That && d_qzero == d_tzero && nq == nt;
-    const PrefilterWs L = prefilter_ws(ws_env(ctx), d_ws, nq, nt, d, k);
-    if (ws_bytes < L.total)
-        return fail(FDR_E_ARG, "knn: workspace %zu < required %zu bytes", ws_bytes, L.total);
-    _Float16 *const d_ht = L.ht, *const d_hq = self ? L.ht : L.hq;
-    const int kp = L.kp;
-    const int dp = fdr_padded_dim(d);
-    knn_call_header(ctx, FDR_TRACE_PREFILTER, dp, k, nq, nt);
-    ctx->last.paths = {L.path, nq, FDR_PATH_NONE, st};  // (per query: the re-rank kernels write the codes)
+struct PrefilterCounts { int exact, zero, range; };  // queries left to the exact pass / all-zero / left to the range pass
+// What the stages of one call share.
+struct PrefilterCall {
+    fdr_ctx *ctx;
+    KnnArgs a;
+    bool self;  // the queries ARE the targets (row i of one is row i of the other): one fp16 copy serves both sides
+    int dp;
+    PrefilterWs L;
+    int shape;  // of the candidate pass (kShapes), its plan, its kernel, the plan's regions in L.knn
+    KnnPlan p;
+    PassKernel kern;
+    PlanRegions R;
+    int ib;                      // index bits of the pass's keys
+    const _Float16 *p1_q, *p1_t;  // what the candidate pass streams: the fp16 copies, or the ordered ones with
+    OrderArgs ord;                // ... their order tables
+    const KnnShape &sh() const { return kShapes[shape]; }
+    size_t lds() const { return knn_lds_bytes(sh(), L.kp); }
+    _Float16 *hq() const { return self ? L.ht : L.hq; }  // the queries' fp16 copy
+    // the stages, in the order launch_knn_prefilter runs them (a call takes one of the two passes)
+    int setup(), pass_dense(Rounds &r), pass_live(Rounds &r);
+    int certify(PrefilterCounts &n), range(PrefilterCounts &n), exact_rest(const PrefilterCounts &n);
+};
 
-    const int pshape = prefilter_shape_live(ctx->live_mode, dp, kp, nq, ctx->num_cus, nt);
-    const KnnPlan p = knn_plan(ctx->num_cus, nq, nt, d, kp, pshape);
-    const KnnShape &sh = kShapes[pshape];
-    fdr_knn_trace &tr = ctx->last.trace;
-    tr.kp = kp;
-    tr.pass_waves = sh.nw;
-    tr.pass_wps = sh.wps;
-    tr.pass_units = sh.tps;
-    tr.pass_list_keys = kp <= 32 ? 16 : 32;
-    tr.pass_pingpong = sh.family == FDR_FAM_PINGPONG;
-    tr.pass_segments = p.nseg;
-    const PassKernel kern = KnnKernels::pass[pshape][kp > 32];
-    if (!kern) return no_kernel(pshape);
-    unsigned *d_bits = reinterpret_cast<unsigned *>(L.knn);  // (the plan's regions, as in launch_knn_exact)
-    unsigned *d_shared = reinterpret_cast<unsigned *>(L.knn + p.bits_bytes);
-    u64 *d_partial = reinterpret_cast<u64 *>(L.knn + p.bits_bytes + p.shared_bytes);
-
-    int trc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, st);  // conversion + set-up count as "rerank"
+// Conversion and set-up, timed as "rerank": fp16 copies, zero bits, ordered and blocked copies, the keys' index bits.
+int PrefilterCall::setup() {
+    const hipStream_t st = a.st;
+    const int64_t nq = a.nq, nt = a.nt;
+    int trc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, st);
     if (trc) return trc;
-    hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)((nt * (dp / 8) + 255) / 256)), dim3(256), 0, st, d_That,
-                       (long long)nt * (dp / 8), d_ht);
+    hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)((nt * (dp / 8) + 255) / 256)), dim3(256), 0, st, a.That,
+                       (long long)nt * (dp / 8), L.ht);
     if (!self)
-        hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)((nq * (dp / 8) + 255) / 256)), dim3(256), 0, st, d_Qhat,
-                           (long long)nq * (dp / 8), d_hq);
+        hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)((nq * (dp / 8) + 255) / 256)), dim3(256), 0, st, a.Qhat,
+                           (long long)nq * (dp / 8), L.hq);
     hipLaunchKernelGGL(pack_zero_bits_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st,
-                       d_tzero, (int)nt, d_bits, d_shared, p.nq_pad);
+                       a.tzero, (int)nt, R.bits, R.shared, p.nq_pad);
     HIP_TRY(hipGetLastError());
-    // Ordered scan (knn_order.inc): rows by chunk mask, fp16 copies in that order
-    OrderArgs ord = {nullptr, nullptr};
-    const _Float16 *p1_q = d_hq, *p1_t = d_ht;  // what the candidate pass streams
-    if (L.ordered) {
+    ord = {nullptr, nullptr};
+    p1_q = hq();
+    p1_t = L.ht;
+    if (L.ordered) {  // knn_order.inc: rows by chunk mask, fp16 copies in that order
         _Float16 *const ho_t = L.ho_t, *const ho_q = self ? L.ho_t : L.ho_q;
-        int *const perm_t = L.perm_t, *const perm_q = L.perm_q;
         auto order = [&](const float *X, int64_t n, int *perm, _Float16 *out) -> int {
             hipLaunchKernelGGL(row_chunk_keys_kernel, dim3((unsigned)(((size_t)n * 16 + 255) / 256)), dim3(256), 0, st, X,
                                (int)n, dp, L.okeys, L.ovals);
@@ -1183,152 +1174,103 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
             return FDR_OK;
         };
         int orc;
-        if ((orc = order(d_That, nt, perm_t, ho_t))) return orc;
-        if (!self && (orc = order(d_Qhat, nq, perm_q, ho_q))) return orc;
-        ord.perm_t = perm_t;
+        if ((orc = order(a.That, nt, L.perm_t, ho_t))) return orc;
+        if (!self && (orc = order(a.Qhat, nq, L.perm_q, ho_q))) return orc;
+        ord.perm_t = L.perm_t;
         p1_t = ho_t;
-        ord.perm_q = self ? perm_t : perm_q;
+        ord.perm_q = self ? L.perm_t : L.perm_q;
         p1_q = ho_q;
         if (L.live) {  // the targets once more in blocks of (tile, chunk); the query blocks' masks (the sorted keys are the queries')
             const long long bgroups = (long long)((nt + 31) / 32 + 4) * 32 * 16;
-            hipLaunchKernelGGL(to_half_blocked_kernel, dim3((unsigned)((bgroups + 255) / 256)), dim3(256), 0, st, d_That,
-                               (const int *)perm_t, (int)nt, bgroups, L.hb_t);
+            hipLaunchKernelGGL(to_half_blocked_kernel, dim3((unsigned)((bgroups + 255) / 256)), dim3(256), 0, st, a.That,
+                               (const int *)L.perm_t, (int)nt, bgroups, L.hb_t);
             hipLaunchKernelGGL(live_block_masks_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(64), 0, st,
                                (const u64 *)L.okeys_s, (int)nq, L.live_masks);
             HIP_TRY(hipGetLastError());
         }
     }
-    const size_t lds = knn_lds_bytes(sh, kp);
     int max_seg = 1;
     for (int i = 0; i < p.nseg; ++i) max_seg = std::max(max_seg, p.segs.b[i + 1] - p.segs.b[i]);
-    const int ib = prefilter_index_bits(max_seg);
+    ib = prefilter_index_bits(max_seg);
     if (ib > FDR_PREFILTER_MAX_IB) return fail(FDR_E_ARG, "knn prefilter: segment of %d rows", max_seg);
     if ((trc = timing_end(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
-    if (lds > 32768)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    Rounds r;  // (rounds on up to four queues; one queue: every launch its own timed span)
-    int lrc;
-    if (L.live) {
-        // Live-chunk pass: the blocks' masks come back (nqb words, one synchronisation), live_plan groups the blocks by
-        // live chunks, and every group runs in synchronised rounds of its own, segment-major -- the NL groups on their
-        // knn_prefilter_live_kernel<NL>, ascending, then the dense group on `kern`.  The shipped kernel takes a block
-        // RANGE and the dense blocks lie scattered over the order (wherever 256 rows straddle two masks), so their
-        // queries, order-table entries and bound words are gathered side by side first (live_gather_dense_kernel); one
-        // launch per contiguous run instead cost a whole scan's time per stray block: 147 ms a step at 1 M reads.
-        const int nqb = p.nqb;
-        std::vector<unsigned> &hb = ctx->live_host;
-        hb.resize((size_t)3 * nqb);
-        HIP_TRY(hipMemcpyAsync(hb.data(), L.live_masks, (size_t)nqb * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        const long long per_launch = p.cohort > 0 ? p.cohort : 0;
-        const LivePlan lp = live_plan(hb.data(), nqb, p.nseg, ctx->live_mode == FDR_LIVE_FORCE ? 0 : per_launch);
-        std::copy(lp.ids.begin(), lp.ids.end(), hb.begin() + nqb);
-        for (int i = 0; i < nqb; ++i) hb[(size_t)2 * nqb + i] = (unsigned)lp.order[(size_t)i];
-        HIP_TRY(hipMemcpyAsync(L.live_ids, hb.data() + nqb, (size_t)nqb * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(L.live_order, hb.data() + 2 * (size_t)nqb, (size_t)nqb * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));  // (pageable source: the vector may be reused by the next call)
-        tr.pass_live = 1;
-        int dense_nq = 0;  // queries of the gathered dense group
-        for (const LiveGroup &g : lp.groups) {
-            if (g.nl != FDR_LIVE_DENSE) {
-                tr.pass_live_items[g.nl - FDR_LIVE_MIN_NL] = g.count * p.nseg;
-                continue;
-            }
-            tr.pass_live_dense_items = g.count * p.nseg;
-            const int last = lp.order[(size_t)(g.first + g.count - 1)];  // (ascending: only the last one can be short)
-            dense_nq = (g.count - 1) * 256 + (int)std::min<int64_t>(256, nq - (int64_t)last * 256);
-            hipLaunchKernelGGL(live_gather_dense_kernel, dim3((unsigned)g.count), dim3(256), 0, st, p1_q, ord.perm_q,
-                               (const unsigned *)d_shared, (int)nq, (const int *)(L.live_order + g.first), L.live_hq,
-                               L.live_perm, L.live_tau);
-        }
-        for (int nl = FDR_LIVE_MIN_NL; nl <= FDR_LIVE_MAX_NL; ++nl)
-            if (live_lds_bytes(nl) > 32768)
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kLiveKernels[nl - FDR_LIVE_MIN_NL]),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)live_lds_bytes(nl)));
-        const int nqueues = p.cohort > 0 ? std::max(1, std::min(p.queues, 4)) : 1;
-        hipStream_t qs[4] = {st, st, st, st};
-        if (nqueues > 1) {
-            if (!ctx->aux_ev[0]) {
-                for (hipStream_t &a : ctx->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&a, hipStreamNonBlocking));
-                for (hipEvent_t &e : ctx->aux_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            }
-            for (int q = 1; q < nqueues; ++q) qs[q] = ctx->aux_stream[q - 1];
-        }
-        if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_PREFILTER, st))) return trc;
-        if (nqueues > 1) {
-            HIP_TRY(hipEventRecord(ctx->aux_ev[0], st));
-            for (int q = 1; q < nqueues; ++q) HIP_TRY(hipStreamWaitEvent(qs[q], ctx->aux_ev[0], 0));
-        }
-        int li = 0;  // launch li goes to queue li % nqueues
-        for (const LiveGroup &g : lp.groups) {
-            const long long n_items = (long long)g.count * p.nseg;
-            const long long per = per_launch > 0 ? per_launch : n_items;
-            for (long long base = 0; base < n_items; base += per, ++li) {
-                const hipStream_t ls = qs[li % nqueues];
-                const unsigned grid = (unsigned)std::min(per, n_items - base);
-                if (g.nl == FDR_LIVE_DENSE)
-                    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh.nw), lds, ls, (const _Float16 *)L.live_hq, dense_nq, p1_t,
-                                       (int)nt, (int)t_base, p.segs, kp, p.nq_pad, d_partial, L.live_tau, ib, (int)base, g.count,
-                                       OrderArgs{ord.perm_t, (const int *)L.live_perm} FDR_DBG_ARG(dev_knobs().debug));
-                else
-                    hipLaunchKernelGGL(kLiveKernels[g.nl - FDR_LIVE_MIN_NL], dim3(grid), dim3(512), live_lds_bytes(g.nl), ls,
-                                       p1_q, (int)nq, (const _Float16 *)L.hb_t, (int)nt, (int)t_base, p.segs, kp, p.nq_pad,
-                                       d_partial, d_shared, ib, (int)base, g.count, (const int *)(L.live_order + g.first),
-                                       (const unsigned *)L.live_ids, ord);
-            }
-        }
-        HIP_TRY(hipGetLastError());
-        r.launches = li;
-        r.queues = nqueues;
-        for (int q = 1; q < nqueues; ++q) {
-            HIP_TRY(hipEventRecord(ctx->aux_ev[q], qs[q]));
-            HIP_TRY(hipStreamWaitEvent(st, ctx->aux_ev[q], 0));
-        }
-        lrc = timing_end(ctx, FDR_KERNEL_KNN_PREFILTER, st);
-    } else {
-        lrc = launch_rounds(ctx, p, 4, FDR_KERNEL_KNN_PREFILTER, true, st, r, [&](hipStream_t s, unsigned grid, int base) {
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh.nw), lds, s, p1_q, (int)nq, p1_t, (int)nt, (int)t_base, p.segs, kp,
-                               p.nq_pad, d_partial, d_shared, ib, base, p.nqb, ord FDR_DBG_ARG(dev_knobs().debug));
-        });
-    }
-    ctx->last.pass.launches = r.launches;
-    ctx->last.pass.queues = r.queues;
-    tr.pass_launches = r.launches;
-    tr.pass_queues = r.queues;
-    if (lrc) return lrc;
-#ifdef FDR_STAMPS
-    {
-        unsigned long long c[16][8];
-        HIP_TRY(hipStreamSynchronize(st));  // (the other queues' launches too: `st` has joined them)
-        HIP_TRY(hipMemcpyFromSymbol(c, HIP_SYMBOL(g_stamps), sizeof(c)));
-        for (int w = 0; w < sh.nw; ++w) {
-            const double st_n = (double)std::max<unsigned long long>(1, c[w][5]);
-            // (knn_prefilter_kernel: 0 dma-issue, 1 mfma+score, 2 share, 3 vmcnt(0), 4 barrier; knn_prefilter_pp_kernel: 0 pipe
-            // turn, 1 dma-issue, 2 scoring, 3 / 4 barrier after the pipe / the other turn, 6 long other turns)
-            fprintf(stderr, "[fdr stamps] wave %d: stages %llu  per stage (s_memtime ticks): ph0 %.0f  ph1 %.0f  ph2 %.0f  ph3 %.0f  "
-                            "ph4 %.0f  long turns %llu\n", w, c[w][5], c[w][0] / st_n, c[w][1] / st_n, c[w][2] / st_n,
-                    c[w][3] / st_n, c[w][4] / st_n, c[w][6]);
-        }
-        unsigned long long z[16][8] = {};
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof(z)));
-    }
-#endif
-#ifdef FDR_DEBUG_COUNTERS
-    if (dev_knobs().debug & 2) {
-        unsigned long long c[8];
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpyFromSymbol(c, HIP_SYMBOL(g_dbg_counters), sizeof(c)));
-        fprintf(stderr, "[fdr debug] prefilter grid %d x %d  wave-tiles %llu  cold %llu  groups %llu  rounds %llu  "
-                        "second rounds %llu  candidates %llu\n", p.nqb, p.nseg, c[0], c[1], c[2], c[3], c[4], c[5]);
-        unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_counters), z, sizeof(z)));
-    }
-#endif
+    if (lds() > 32768)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds()));
+    return FDR_OK;
+}
 
+// The dense candidate pass: rounds on up to four queues (one queue: every launch its own timed span).
+int PrefilterCall::pass_dense(Rounds &r) {
+    return launch_rounds(ctx, p, {(long long)p.nqb * p.nseg}, 4, FDR_KERNEL_KNN_PREFILTER, true, a.st, r,
+                         [&](hipStream_t s, unsigned grid, int base, int) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh().nw), lds(), s, p1_q, (int)a.nq, p1_t, (int)a.nt, (int)a.t_base,
+                           p.segs, L.kp, p.nq_pad, R.partial, R.shared, ib, base, p.nqb, ord FDR_DBG_ARG(dev_knobs().debug));
+    });
+}
+
+// The live-chunk candidate pass: the blocks' masks come back (nqb words, one synchronisation), live_plan groups the
+// blocks by live chunks, and every group runs in synchronised rounds of its own, segment-major -- the NL groups on their
+// knn_prefilter_live_kernel<NL>, ascending, then the dense group on kern -- as ONE timed span.  The shipped kernel
+// takes a block RANGE and the dense blocks lie scattered over the order (wherever 256 rows straddle two masks), so their
+// queries, order-table entries and bound words are gathered side by side first (live_gather_dense_kernel); one launch
+// per contiguous run instead cost a whole scan's time per stray block: 147 ms a step at 1 M reads.
+int PrefilterCall::pass_live(Rounds &r) {
+    const hipStream_t st = a.st;
+    const int nqb = p.nqb, kp = L.kp;
+    fdr_knn_trace &tr = ctx->last.trace;
+    std::vector<unsigned> &masks = ctx->live_host;
+    masks.resize((size_t)nqb);
+    HIP_TRY(hipMemcpyAsync(masks.data(), L.live_masks, (size_t)nqb * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const LivePlan lp = live_plan(masks.data(), nqb, p.nseg, ctx->live_mode == FDR_LIVE_FORCE ? 0 : p.cohort);
+    HIP_TRY(hipMemcpyAsync(L.live_ids, lp.ids.data(), (size_t)nqb * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(L.live_order, lp.order.data(), (size_t)nqb * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));  // (pageable sources that end with this function)
+    tr.pass_live = 1;
+    int dense_nq = 0;  // queries of the gathered dense group
+    std::vector<long long> items;
+    for (const LiveGroup &g : lp.groups) {
+        items.push_back((long long)g.count * p.nseg);
+        if (g.nl != FDR_LIVE_DENSE) {
+            tr.pass_live_items[g.nl - FDR_LIVE_MIN_NL] = g.count * p.nseg;
+            continue;
+        }
+        tr.pass_live_dense_items = g.count * p.nseg;
+        const int last = lp.order[(size_t)(g.first + g.count - 1)];  // (ascending: only the last one can be short)
+        dense_nq = (g.count - 1) * 256 + (int)std::min<int64_t>(256, a.nq - (int64_t)last * 256);
+        hipLaunchKernelGGL(live_gather_dense_kernel, dim3((unsigned)g.count), dim3(256), 0, st, p1_q, ord.perm_q,
+                           (const unsigned *)R.shared, (int)a.nq, (const int *)(L.live_order + g.first), L.live_hq,
+                           L.live_perm, L.live_tau);
+    }
+    for (int nl = FDR_LIVE_MIN_NL; nl <= FDR_LIVE_MAX_NL; ++nl)
+        if (live_lds_bytes(nl) > 32768)
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kLiveKernels[nl - FDR_LIVE_MIN_NL]),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)live_lds_bytes(nl)));
+    return launch_rounds(ctx, p, items, 4, FDR_KERNEL_KNN_PREFILTER, false, st, r,
+                         [&](hipStream_t s, unsigned grid, int base, int group) {
+        const LiveGroup &g = lp.groups[(size_t)group];
+        if (g.nl == FDR_LIVE_DENSE)
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh().nw), lds(), s, (const _Float16 *)L.live_hq, dense_nq, p1_t,
+                               (int)a.nt, (int)a.t_base, p.segs, kp, p.nq_pad, R.partial, L.live_tau, ib, base, g.count,
+                               OrderArgs{ord.perm_t, (const int *)L.live_perm} FDR_DBG_ARG(dev_knobs().debug));
+        else
+            hipLaunchKernelGGL(kLiveKernels[g.nl - FDR_LIVE_MIN_NL], dim3(grid), dim3(512), live_lds_bytes(g.nl), s,
+                               p1_q, (int)a.nq, (const _Float16 *)L.hb_t, (int)a.nt, (int)a.t_base, p.segs, kp, p.nq_pad,
+                               R.partial, R.shared, ib, base, g.count, (const int *)(L.live_order + g.first),
+                               (const unsigned *)L.live_ids, ord);
+    });
+}
+
+// Key merge and capture, certificate + exact re-rank, zero answers; the 12-byte read-back that sizes the passes below.
+int PrefilterCall::certify(PrefilterCounts &n) {
+    const hipStream_t st = a.st;
+    const int kp = L.kp, k = a.k;
+    const int64_t nq = a.nq;
+    int trc;
     if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
     const int64_t mq = p.nseg * kp <= 64 ? 4 * MERGE_QPW : 4;  // queries per workgroup of knn_merge_keys_kernel
     hipLaunchKernelGGL(knn_merge_keys_kernel, dim3((unsigned)((nq + mq - 1) / mq)), dim3(256), 0, st,
-                       (const u64 *)d_partial, p.nseg, (int)nq, p.nq_pad, kp, L.cand);
+                       (const u64 *)R.partial, p.nseg, (int)nq, p.nq_pad, kp, L.cand);
     HIP_TRY(hipGetLastError());
     if (ctx->cap.what & FDR_CAPTURE_CANDIDATES) {  // (test support: fdr_last_candidates)
         if ((trc = ctx->cap.cand.reserve((size_t)nq * kp * 8))) return trc;
@@ -1344,121 +1286,171 @@ static int launch_knn_prefilter(fdr_ctx *ctx, const float *d_Qhat, const uint8_t
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_rerank_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, RERANK_LDS_BYTES));
     hipLaunchKernelGGL(knn_rerank_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), RERANK_LDS_BYTES, st,
-                       (const u64 *)L.cand, kp, k, d_Qhat, d_qzero, d_That, (int)nq, dp, (int)t_base, margin,
-                       d_idx, d_dist, L.counter, L.flagged, L.rlist, L.theta, L.path);
+                       (const u64 *)L.cand, kp, k, a.Qhat, a.qzero, a.That, (int)nq, dp, (int)a.t_base, margin,
+                       a.idx, a.dist, L.counter, L.flagged, L.rlist, L.theta, L.path);
     // all-zero queries share one closed-form answer (their number is only known on the device yet)
-    hipLaunchKernelGGL(zero_answer_kernel, dim3(1), dim3(1024), 0, st, (const unsigned *)d_bits, (int)nt,
-                       (int)t_base, k, L.zidx, L.zdist);
+    hipLaunchKernelGGL(zero_answer_kernel, dim3(1), dim3(1024), 0, st, (const unsigned *)R.bits, (int)a.nt,
+                       (int)a.t_base, k, L.zidx, L.zdist);
     hipLaunchKernelGGL(scatter_zero_answer_kernel, dim3((unsigned)(((int64_t)nq * k + 255) / 256)),
                        dim3(256), 0, st, (const int *)L.zidx, (const float *)L.zdist,
-                       (const int *)L.flagged, (int)nq, (const int *)L.counter, k, d_idx, d_dist);
+                       (const int *)L.flagged, (int)nq, (const int *)L.counter, k, a.idx, a.dist);
     HIP_TRY(hipGetLastError());
     if ((trc = timing_end(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
-
-    // how many queries could not be certified / are all-zero / need a range pass?  (one 12-byte
-    // read-back; the passes below are sized from it)
-    int counts[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(counts, L.counter, 12, hipMemcpyDeviceToHost, st));
+    n = {0, 0, 0};  // how many queries could not be certified / are all-zero / need a range pass?
+    HIP_TRY(hipMemcpyAsync(&n, L.counter, 12, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    int count = counts[0];
-    const int zcount = counts[1], rcount = counts[2];
-    ctx->last.pass.flagged = count + rcount;
-    tr.uncertified = count;
-    tr.zero_queries = zcount;
-    tr.range_queries = rcount;
-    if (rcount > 0) {  // plateau queries: collect {d~ <= theta} with a second fp16 pass, rank it exactly
-        if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
-        const bool rcap = ctx->cap.what & FDR_CAPTURE_RANGE;  // (test support: fdr_last_range_sets)
-        if (rcap) {
-            if ((trc = ctx->cap.rq.reserve((size_t)rcount * 4)) || (trc = ctx->cap.rtheta.reserve((size_t)rcount * 4)) ||
-                (trc = ctx->cap.rcnt.reserve((size_t)rcount * 4)) || (trc = ctx->cap.rrows.reserve((size_t)rcount * RANGE_CAP * 4)))
-                return trc;
-            ctx->cap.stream = st;
-        }
-        for (int first = 0; first < rcount; first += L.rchunk) {
-            const int c = std::min(L.rchunk, rcount - first);
-            hipLaunchKernelGGL(gather_half_queries_kernel, dim3((unsigned)c), dim3(256), 0, st,
-                               (const _Float16 *)d_hq, (const float *)L.theta, (const int *)L.rlist, first, c,
-                               dp, L.hqc, L.thetac, L.cnt);
-            HIP_TRY(hipGetLastError());
-            const int rs = range_shape(dp, c, rcount);
-            const KnnShape &rsh = kShapes[rs];
-            const RangeKernel rk = KnnKernels::range[rs];
-            if (!rk) return no_kernel(rs);
-            const KnnPlan rp = knn_plan(ctx->num_cus, c, nt, d, 1, rs);  // (k = 1: ring-only LDS)
-            const size_t rlds = knn_lds_bytes(rsh, 1) + (size_t)RANGE_LANE_BUF * 64 * rsh.nw * 4;  // ring + lane buffers
-            if (rsh.family == FDR_FAM_RANGE_PP)
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(rk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
-            hipLaunchKernelGGL(rk, dim3((unsigned)rp.nqb, (unsigned)rp.nseg), dim3(64 * rsh.nw), rlds, st, (const _Float16 *)L.hqc,
-                               (const float *)L.thetac, c, (const _Float16 *)d_ht, (int)nt, (int)t_base, rp.segs, L.cnt, L.rcand);
-            HIP_TRY(hipGetLastError());
-            tr.range_chunks++;
-            tr.range_pp_chunks += rsh.family == FDR_FAM_RANGE_PP;
-            tr.range_w8_chunks += rs == FDR_R128_W8;
-            if (rcap) {
-                char *cq = static_cast<char *>(ctx->cap.rq.p), *cth = static_cast<char *>(ctx->cap.rtheta.p);
-                char *cc = static_cast<char *>(ctx->cap.rcnt.p), *cr = static_cast<char *>(ctx->cap.rrows.p);
-                HIP_TRY(hipMemcpyAsync(cq + (size_t)first * 4, L.rlist + first, (size_t)c * 4, hipMemcpyDeviceToDevice, st));
-                HIP_TRY(hipMemcpyAsync(cth + (size_t)first * 4, L.thetac, (size_t)c * 4, hipMemcpyDeviceToDevice, st));
-                HIP_TRY(hipMemcpyAsync(cc + (size_t)first * 4, L.cnt, (size_t)c * 4, hipMemcpyDeviceToDevice, st));
-                HIP_TRY(hipMemcpyAsync(cr + (size_t)first * RANGE_CAP * 4, L.rcand, (size_t)c * RANGE_CAP * 4,
-                                       hipMemcpyDeviceToDevice, st));
-            }
-            hipLaunchKernelGGL(knn_rerank_long_kernel, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st,
-                               (const int *)(L.rlist + first), c, (const int *)L.cnt, (const int *)L.rcand, k,
-                               d_Qhat, d_That, dp, (int)t_base, d_idx, d_dist, L.counter, L.flagged, L.path);
-            HIP_TRY(hipGetLastError());
-        }
-        if (rcap) {
-            ctx->cap.n_range = rcount;
-            ctx->cap.range_valid = true;
-        }
-        if ((trc = timing_end(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
-        // ranges that overflowed were appended to the exact list: read its final length
-        HIP_TRY(hipMemcpyAsync(counts, L.counter, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        tr.range_overflow = counts[0] - count;
-        count = counts[0];
+    ctx->last.pass.flagged = n.exact + n.range;
+    ctx->last.trace.uncertified = n.exact;
+    ctx->last.trace.zero_queries = n.zero;
+    ctx->last.trace.range_queries = n.range;
+    return FDR_OK;
+}
+
+// Plateau queries: collect {d~ <= theta} with a second fp16 pass, rank it exactly.  Ranges that overflow are appended
+// to the exact list: n.exact becomes its final length.
+int PrefilterCall::range(PrefilterCounts &n) {
+    const hipStream_t st = a.st;
+    const int rcount = n.range;
+    fdr_knn_trace &tr = ctx->last.trace;
+    int trc;
+    if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
+    const bool rcap = ctx->cap.what & FDR_CAPTURE_RANGE;  // (test support: fdr_last_range_sets)
+    if (rcap) {
+        if ((trc = ctx->cap.rq.reserve((size_t)rcount * 4)) || (trc = ctx->cap.rtheta.reserve((size_t)rcount * 4)) ||
+            (trc = ctx->cap.rcnt.reserve((size_t)rcount * 4)) || (trc = ctx->cap.rrows.reserve((size_t)rcount * RANGE_CAP * 4)))
+            return trc;
+        ctx->cap.stream = st;
     }
-    if (count <= 0) return FDR_OK;
-    if ((int64_t)count * 2 > nq - zcount) {  // the prefilter did not help on this input: exact pass for everyone
-        tr.exact_fallback = FDR_FALLBACK_WHOLE;
+    for (int first = 0; first < rcount; first += L.rchunk) {
+        const int cq = std::min(L.rchunk, rcount - first);
+        hipLaunchKernelGGL(gather_half_queries_kernel, dim3((unsigned)cq), dim3(256), 0, st, (const _Float16 *)hq(),
+                           (const float *)L.theta, (const int *)L.rlist, first, cq, dp, L.hqc, L.thetac, L.cnt);
+        HIP_TRY(hipGetLastError());
+        const int rs = range_shape(dp, cq, rcount);
+        const KnnShape &rsh = kShapes[rs];
+        const RangeKernel rk = KnnKernels::range[rs];
+        if (!rk) return no_kernel(rs);
+        const KnnPlan rp = knn_plan(ctx->num_cus, cq, a.nt, a.d, 1, rs);  // (k = 1: ring-only LDS)
+        const size_t rlds = knn_lds_bytes(rsh, 1) + (size_t)RANGE_LANE_BUF * 64 * rsh.nw * 4;  // ring + lane buffers
+        if (rsh.family == FDR_FAM_RANGE_PP)
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(rk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
+        hipLaunchKernelGGL(rk, dim3((unsigned)rp.nqb, (unsigned)rp.nseg), dim3(64 * rsh.nw), rlds, st, (const _Float16 *)L.hqc,
+                           (const float *)L.thetac, cq, (const _Float16 *)L.ht, (int)a.nt, (int)a.t_base, rp.segs, L.cnt, L.rcand);
+        HIP_TRY(hipGetLastError());
+        tr.range_chunks++;
+        tr.range_pp_chunks += rsh.family == FDR_FAM_RANGE_PP;
+        tr.range_w8_chunks += rs == FDR_R128_W8;
+        if (rcap) {
+            auto keep = [&](const DevBuf &to, const void *from, size_t row_bytes) {  // this chunk's rows, behind the earlier ones
+                return hipMemcpyAsync(static_cast<char *>(to.p) + first * row_bytes, from, cq * row_bytes, hipMemcpyDeviceToDevice, st);
+            };
+            HIP_TRY(keep(ctx->cap.rq, L.rlist + first, 4));
+            HIP_TRY(keep(ctx->cap.rtheta, L.thetac, 4));
+            HIP_TRY(keep(ctx->cap.rcnt, L.cnt, 4));
+            HIP_TRY(keep(ctx->cap.rrows, L.rcand, (size_t)RANGE_CAP * 4));
+        }
+        hipLaunchKernelGGL(knn_rerank_long_kernel, dim3((unsigned)((cq + 3) / 4)), dim3(256), 0, st,
+                           (const int *)(L.rlist + first), cq, (const int *)L.cnt, (const int *)L.rcand, a.k,
+                           a.Qhat, a.That, dp, (int)a.t_base, a.idx, a.dist, L.counter, L.flagged, L.path);
+        HIP_TRY(hipGetLastError());
+    }
+    if (rcap) {
+        ctx->cap.n_range = rcount;
+        ctx->cap.range_valid = true;
+    }
+    if ((trc = timing_end(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
+    int count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, L.counter, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    tr.range_overflow = count - n.exact;
+    n.exact = count;
+    return FDR_OK;
+}
+
+// The exact pass for the exact list's n.exact queries, gathered in chunks -- or for everyone -- in L.knn's regions.
+int PrefilterCall::exact_rest(const PrefilterCounts &n) {
+    const hipStream_t st = a.st;
+    KnnArgs e = a;
+    e.ws_bytes = L.knn_bytes;
+    if ((int64_t)n.exact * 2 > a.nq - n.zero) {
+        ctx->last.trace.exact_fallback = FDR_FALLBACK_WHOLE;
         // every row, the all-zero ones too, is recomputed by the exact kernel: its code, as in exact mode
         // (the trace stays a prefilter trace, and the pass's launches and uncertified count stand)
-        ctx->last.paths = {nullptr, nq, FDR_PATH_EXACT, nullptr};
-        return launch_knn_exact(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist,
-                                d_ws, L.knn_bytes, st);
+        ctx->last.paths = {nullptr, a.nq, FDR_PATH_EXACT, nullptr};
+        return launch_knn_exact(ctx, e);
     }
-    tr.exact_fallback = FDR_FALLBACK_CHUNKED;
-    for (int first = 0; first < count; first += L.chunk) {
-        const int c = std::min(L.chunk, count - first);
-        hipLaunchKernelGGL(gather_queries_kernel, dim3((unsigned)c), dim3(256), 0, st, d_Qhat, d_qzero,
-                           (const int *)L.flagged, first, c, dp, L.qc, L.qzc);
+    ctx->last.trace.exact_fallback = FDR_FALLBACK_CHUNKED;
+    e.Qhat = L.qc;
+    e.qzero = L.qzc;
+    e.idx = L.idxc;
+    e.dist = L.distc;
+    for (int first = 0; first < n.exact; first += L.chunk) {
+        const int cq = std::min(L.chunk, n.exact - first);
+        hipLaunchKernelGGL(gather_queries_kernel, dim3((unsigned)cq), dim3(256), 0, st, a.Qhat, a.qzero,
+                           (const int *)L.flagged, first, cq, dp, L.qc, L.qzc);
         HIP_TRY(hipGetLastError());
-        int rc = launch_knn_exact(ctx, L.qc, L.qzc, c, d_That, d_tzero, nt, t_base, d, k, L.idxc, L.distc,
-                                  d_ws, L.knn_bytes, st);
+        e.nq = cq;
+        int rc = launch_knn_exact(ctx, e);
         if (rc) return rc;
-        hipLaunchKernelGGL(scatter_results_kernel, dim3((unsigned)(((int64_t)c * k + 255) / 256)), dim3(256),
-                           0, st, (const int *)L.idxc, (const float *)L.distc, (const int *)L.flagged, first,
-                           c, k, d_idx, d_dist);
+        hipLaunchKernelGGL(scatter_results_kernel, dim3((unsigned)(((int64_t)cq * a.k + 255) / 256)), dim3(256), 0, st,
+                           (const int *)L.idxc, (const float *)L.distc, (const int *)L.flagged, first, cq, a.k, a.idx, a.dist);
         HIP_TRY(hipGetLastError());
     }
     return FDR_OK;
 }
 
-static int launch_knn_mode(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero, int64_t nq,
-                           const float *d_That, const uint8_t *d_tzero, int64_t nt, int64_t t_base, int d,
-                           int k, int32_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes, hipStream_t st) {
-    const int dp = fdr_padded_dim(d);
-    if (knn_route(dp, k, nt) == FDR_ROUTE_FAST && nq > 0 && knn_prefilter_wanted(ctx->knn_mode, nt, k)) {
-        const int rc = launch_knn_prefilter(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx,
-                                            d_dist, d_ws, ws_bytes, st);
+static int launch_knn_prefilter(fdr_ctx *ctx, const KnnArgs &a) {
+    PrefilterCall c = {ctx, a};
+    c.self = a.Qhat == a.That && a.qzero == a.tzero && a.nq == a.nt;
+    c.dp = fdr_padded_dim(a.d);
+    c.L = prefilter_ws(ws_env(ctx), a.ws, a.nq, a.nt, a.d, a.k);
+    if (a.ws_bytes < c.L.total) return fail(FDR_E_ARG, "knn: workspace %zu < required %zu bytes", a.ws_bytes, c.L.total);
+    const int kp = c.L.kp;
+    knn_call_header(ctx, FDR_TRACE_PREFILTER, c.dp, a.k, a.nq, a.nt);
+    ctx->last.paths = {c.L.path, a.nq, FDR_PATH_NONE, a.st};  // (per query: the re-rank kernels write the codes)
+
+    c.shape = prefilter_shape_live(ctx->live_mode, c.dp, kp, a.nq, ctx->num_cus, a.nt);
+    c.p = knn_plan(ctx->num_cus, a.nq, a.nt, a.d, kp, c.shape);
+    fdr_knn_trace &tr = ctx->last.trace;
+    tr.kp = kp;
+    tr.pass_waves = c.sh().nw;
+    tr.pass_wps = c.sh().wps;
+    tr.pass_units = c.sh().tps;
+    tr.pass_list_keys = kp <= 32 ? 16 : 32;
+    tr.pass_pingpong = c.sh().family == FDR_FAM_PINGPONG;
+    tr.pass_segments = c.p.nseg;
+    c.kern = KnnKernels::pass[c.shape][kp > 32];
+    if (!c.kern) return no_kernel(c.shape);
+    c.R = plan_regions(c.L.knn, c.p);
+    int rc;
+    if ((rc = c.setup())) return rc;
+    Rounds r;
+    rc = c.L.live ? c.pass_live(r) : c.pass_dense(r);
+    ctx->last.pass.launches = r.launches;
+    ctx->last.pass.queues = r.queues;
+    tr.pass_launches = r.launches;
+    tr.pass_queues = r.queues;
+    if (rc) return rc;
+#ifdef FDR_STAMPS
+    if ((rc = dump_stamps(a.st, c.sh().nw))) return rc;
+#endif
+    if ((rc = dump_debug_counters(a.st, "prefilter", c.p, "wave-tiles, cold, groups, rounds, second rounds, candidates"))) return rc;
+    PrefilterCounts n;
+    if ((rc = c.certify(n))) return rc;
+    if (n.range > 0 && (rc = c.range(n))) return rc;
+    if (n.exact <= 0) return FDR_OK;
+    return c.exact_rest(n);
+}
+
+static int launch_knn_mode(fdr_ctx *ctx, const KnnArgs &a) {
+    const int dp = fdr_padded_dim(a.d);
+    if (knn_route(dp, a.k, a.nt) == FDR_ROUTE_FAST && a.nq > 0 && knn_prefilter_wanted(ctx->knn_mode, a.nt, a.k)) {
+        const int rc = launch_knn_prefilter(ctx, a);
         if (rc) ctx->cap.cand_valid = ctx->cap.range_valid = false;  // (a failed call leaves no capture)
         return rc;
     }
-    knn_call_whole(ctx, FDR_PATH_EXACT, FDR_TRACE_EXACT, dp, k, nq, nt);
-    return launch_knn_exact(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist,
-                            d_ws, ws_bytes, st);
+    knn_call_whole(ctx, FDR_PATH_EXACT, FDR_TRACE_EXACT, dp, a.k, a.nq, a.nt);
+    return launch_knn_exact(ctx, a);
 }
 
 // ---- duplicate-row classes: search unique queries x unique targets, expand --------------------
@@ -1484,13 +1476,6 @@ static int queue_class_tables(const DedupWs &W, const float *d_That, int n, int 
     return FDR_OK;
 }
 
-// Is searching nu unique targets for nuq unique queries worth the gathers and the expansion?  Never with fewer unique
-// rows than neighbours asked for; else when forced (tests), or when the pairs to score fall to 90 %.
-static bool dedup_worth(int nu, int nuq, int64_t nt, int64_t nq, int k, int dedup_mode) {
-    if (nu < k) return false;
-    return dedup_mode == FDR_DEDUP_FORCE || (double)nu * nuq <= 0.9 * (double)nt * (double)nq;
-}
-
 // expand_classes_kernel: the unique rows' results (idx_u / dist_u, u_stride elements apart; found through uqpos where
 // only some unique rows were queries) -> the results of rows [q0, q0 + nq) of the classes in W
 static int launch_expand(const DedupWs &W, int64_t q0, int64_t nq, int k, int64_t t_base, const int *uqpos,
@@ -1507,11 +1492,13 @@ static int launch_expand(const DedupWs &W, int64_t q0, int64_t nq, int k, int64_
     return FDR_OK;
 }
 
-static int launch_knn(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero, int64_t nq,
-                      const float *d_That, const uint8_t *d_tzero, int64_t nt, int64_t t_base, int d,
-                      int k, int32_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes, hipStream_t st) {
-    int rc = check_knn_args(d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist, d_ws);
+static int launch_knn(fdr_ctx *ctx, const KnnArgs &a) {
+    int rc = check_knn_args(ctx, a);
     if (rc) return rc;
+    const float *const d_Qhat = a.Qhat, *const d_That = a.That;
+    const int64_t nq = a.nq, nt = a.nt;
+    const int d = a.d, k = a.k;
+    const hipStream_t st = a.st;
     const int dp = fdr_padded_dim(d);
     const int route = knn_route(dp, k, nt);
     if (route == FDR_ROUTE_GENERIC) {  // beyond the MFMA kernels' shapes
@@ -1523,8 +1510,8 @@ static int launch_knn(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero,
         int trc = timing_begin(ctx, FDR_KERNEL_KNN_TILE, st);
         if (trc) return trc;
         hipLaunchKernelGGL(knn_generic_kernel, dim3((unsigned)((nq + GEN_QPB - 1) / GEN_QPB)), dim3(256),
-                           (size_t)GEN_QPB * dp * 4, st, d_Qhat, d_qzero, (int)nq, d_That, d_tzero, (int)nt, (int)t_base, dp, k,
-                           d_idx, d_dist);
+                           (size_t)GEN_QPB * dp * 4, st, d_Qhat, a.qzero, (int)nq, d_That, a.tzero, (int)nt, (int)a.t_base, dp, k,
+                           a.idx, a.dist);
         HIP_TRY(hipGetLastError());
         return timing_end(ctx, FDR_KERNEL_KNN_TILE, st);
     }
@@ -1532,16 +1519,18 @@ static int launch_knn(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero,
     auto plain = [&](size_t bytes) {
         ctx->last.unique_targets = (int)nt;
         ctx->last.unique_queries = (int)nq;
-        return launch_knn_mode(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist, d_ws, bytes, st);
+        KnnArgs b = a;
+        b.ws_bytes = bytes;
+        return launch_knn_mode(ctx, b);
     };
     // the queries must be a block of the target rows (they are in every caller of this library)
     const bool q_in_t = nq > 0 && d_Qhat >= d_That && d_Qhat + (size_t)nq * dp <= d_That + (size_t)nt * dp &&
                         ((d_Qhat - d_That) % dp) == 0;
     // (FDR_ROUTE_WIDE: the exact pass of launch_knn_mode, never the duplicate-row classes)
-    if (!(route == FDR_ROUTE_FAST && q_in_t && knn_dedup_wanted(ctx->dedup_mode, nq, nt))) return plain(ws_bytes);
+    if (!(route == FDR_ROUTE_FAST && q_in_t && knn_dedup_wanted(ctx->dedup_mode, nq, nt))) return plain(a.ws_bytes);
     const WsEnv env = ws_env(ctx);
-    const DedupWs W = dedup_ws(env, d_ws, nq, nt, d, k);
-    if (ws_bytes < W.total) return fail(FDR_E_ARG, "knn: workspace %zu < required %zu bytes", ws_bytes, W.total);
+    const DedupWs W = dedup_ws(env, a.ws, nq, nt, d, k);
+    if (a.ws_bytes < W.total) return fail(FDR_E_ARG, "knn: workspace %zu < required %zu bytes", a.ws_bytes, W.total);
     const int n = (int)nt;
     const int q0 = (int)((d_Qhat - d_That) / dp);
     const unsigned g16 = (unsigned)(((size_t)n * 16 + 255) / 256), g1 = (unsigned)((n + 255) / 256);
@@ -1584,7 +1573,7 @@ static int launch_knn(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero,
     }
     ctx->last.unique_targets = nu;
     ctx->last.unique_queries = nuq;
-    hipLaunchKernelGGL(gather_unique_rows_kernel, dim3(g16), dim3(256), 0, st, d_That, d_tzero, n, dp,
+    hipLaunchKernelGGL(gather_unique_rows_kernel, dim3(g16), dim3(256), 0, st, d_That, a.tzero, n, dp,
                        (const int *)W.isrep, (const int *)W.upos, W.U, W.uzero);
     if (nuq != nu)  // (else the unique queries are the unique rows: no copy, see below)
         hipLaunchKernelGGL(gather_unique_queries_kernel, dim3((unsigned)(((size_t)nu * 16 + 255) / 256)), dim3(256),
@@ -1597,12 +1586,21 @@ static int launch_knn(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_qzero,
     // (every unique row is a query: Uq would be a copy of U -- the same pointers let the prefilter mode see that
     // the queries are the targets)
     const bool all_q = nuq == nu;
-    rc = launch_knn_mode(ctx, all_q ? W.U : W.Uq, all_q ? W.uzero : W.uqz, nuq, W.U, W.uzero, nu, 0, d, k, W.idx_u,
-                         W.dist_u, d_ws, W.inner_bytes, st);
-    if (rc) return rc;
+    KnnArgs u = a;
+    u.Qhat = all_q ? W.U : W.Uq;
+    u.qzero = all_q ? W.uzero : W.uqz;
+    u.nq = nuq;
+    u.That = W.U;
+    u.tzero = W.uzero;
+    u.nt = nu;
+    u.t_base = 0;
+    u.idx = W.idx_u;
+    u.dist = W.dist_u;
+    u.ws_bytes = W.inner_bytes;
+    if ((rc = launch_knn_mode(ctx, u))) return rc;
     if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_DEDUP, st))) return trc;
     const auto &inner = ctx->last.paths;  // the unique rows' codes, carried to the rows of their classes
-    if ((rc = launch_expand(W, q0, nq, k, t_base, W.uqpos, W.idx_u, W.dist_u, k, d_idx, d_dist,
+    if ((rc = launch_expand(W, q0, nq, k, a.t_base, W.uqpos, W.idx_u, W.dist_u, k, a.idx, a.dist,
                             inner.n == nuq ? inner.dev : nullptr, inner.all, W.rowpath, st)))
         return rc;
     ctx->last.paths = {W.rowpath, nq, FDR_PATH_NONE, st};
@@ -1687,8 +1685,9 @@ FDR_EXPORT int fdr_knn_unique_dev(fdr_ctx *ctx, int64_t u_lo, int64_t u_hi, int3
     const DedupWs W = classes_ws(ctx);
     ctx->last.unique_queries = (int)(u_hi - u_lo);
     // the unique rows are stored in ascending representative order; a share of them is a block of U
-    rc = launch_knn_mode(ctx, W.U + (size_t)u_lo * dp, W.uzero + u_lo, u_hi - u_lo, W.U, W.uzero, ctx->cls.nu, 0,
-                         ctx->cls.d, ctx->cls.k, d_idx_u, d_dist_u, ctx->cls.ws, W.inner_bytes, (hipStream_t)stream);
+    rc = launch_knn_mode(ctx, KnnArgs{W.U + (size_t)u_lo * dp, W.uzero + u_lo, u_hi - u_lo, W.U, W.uzero, ctx->cls.nu, 0,
+                                      ctx->cls.d, ctx->cls.k, d_idx_u, d_dist_u, ctx->cls.ws, W.inner_bytes,
+                                      (hipStream_t)stream});
     ctx->last.paths = {};  // (fdr_last_query_paths covers whole calls; a share of the unique rows is not one)
     return rc;
 }
@@ -1740,8 +1739,8 @@ FDR_EXPORT int fdr_knn_dev(fdr_ctx *ctx, const float *d_Qhat, const uint8_t *d_q
     if (rc) return rc;
     knn_call_begin(ctx);
     if (d_workspace == ctx->cls.ws) ctx->cls.valid = false;  // (this call overwrites the tables fdr_knn_classes_dev left there)
-    return launch_knn(ctx, d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist,
-                      d_workspace, workspace_bytes, (hipStream_t)stream);
+    return launch_knn(ctx, KnnArgs{d_Qhat, d_qzero, nq, d_That, d_tzero, nt, t_base, d, k, d_idx, d_dist, d_workspace,
+                                   workspace_bytes, (hipStream_t)stream});
 }
 
 // ---- host-pointer API ------------------------------------------------------------------------
@@ -1866,10 +1865,10 @@ static int knn_from_device_E(fdr_ctx *ctx, const float *d_E, int64_t n, int d, i
     if ((rc = ctx->ws.reserve(wsb))) return rc;
     if ((rc = launch_normalize(ctx, d_E, n, d, (float *)ctx->Ehat.p, (uint8_t *)ctx->zero.p, ctx->stream)))
         return rc;
-    if ((rc = launch_knn(ctx, (const float *)ctx->Ehat.p, (const uint8_t *)ctx->zero.p, n,
-                         (const float *)ctx->Ehat.p, (const uint8_t *)ctx->zero.p, n, 0, d, k,
-                         (int32_t *)ctx->idx.p, (float *)ctx->dist.p, ctx->ws.p, wsb, ctx->stream)))
-        return rc;
+    const float *const Ehat = (const float *)ctx->Ehat.p;
+    const uint8_t *const zero = (const uint8_t *)ctx->zero.p;
+    const KnnArgs a = {Ehat, zero, n, Ehat, zero, n, 0, d, k, (int32_t *)ctx->idx.p, (float *)ctx->dist.p, ctx->ws.p, wsb, ctx->stream};
+    if ((rc = launch_knn(ctx, a))) return rc;
     HIP_TRY(hipMemcpyAsync(idx_out, ctx->idx.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(dist_out, ctx->dist.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

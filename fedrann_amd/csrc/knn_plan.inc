@@ -559,3 +559,22 @@ static LivePlan live_plan(const unsigned *masks, int nqb, int nseg, long long mi
     }
     return P;
 }
+
+// ---- the launches of a pass: one list for every k-NN pass (fedrann_hip.hip: launch_rounds) ---------------------------
+// A pass is one or more groups of work items -- a plain pass: one group of nqb * nseg; the live-chunk pass: a group per
+// LiveGroup, count * nseg each -- and every group runs in launches of at most `per_launch` items (0: one launch per
+// group), ascending and contiguous, only its last one short.  The launches are dealt round-robin over `queues` queues
+// in issue order, across the groups: launch i goes to queue i % queues.
+struct RoundLaunch {
+    int group, queue;
+    int base, grid;  // the group's items [base, base + grid)
+};
+static std::vector<RoundLaunch> round_schedule(const std::vector<long long> &items, long long per_launch, int queues) {
+    std::vector<RoundLaunch> S;
+    for (size_t g = 0; g < items.size(); ++g) {
+        const long long n = items[g], per = per_launch > 0 ? per_launch : n;
+        for (long long base = 0; base < n; base += per)
+            S.push_back(RoundLaunch{(int)g, (int)(S.size() % (size_t)queues), (int)base, (int)std::min(per, n - base)});
+    }
+    return S;
+}

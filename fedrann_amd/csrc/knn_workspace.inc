@@ -39,6 +39,18 @@ struct WsArena {
 template <class T>
 static T *ws_at(T *region, size_t n) { return region ? region + n : nullptr; }
 
+// The three regions of a KnnPlan's p.total_bytes at `base`: the targets' zero bits, the query blocks' shared bound
+// words, the per-segment partial lists -- for the exact pass and the candidate pass alike.
+struct PlanRegions {
+    unsigned *bits, *shared;
+    u64 *partial;
+};
+static PlanRegions plan_regions(void *base, const KnnPlan &p) {
+    char *const b = static_cast<char *>(base);
+    return {reinterpret_cast<unsigned *>(b), reinterpret_cast<unsigned *>(b + p.bits_bytes),
+            reinterpret_cast<u64 *>(b + p.bits_bytes + p.shared_bytes)};
+}
+
 // what a layout depends on besides the problem's size: the device, the context's modes, and the temporary storage
 // rocprim asks for (fedrann_hip.hip: order_sort_tmp_bytes, class_tables_tmp_bytes; the layout test: stand-ins)
 struct WsEnv {
@@ -76,6 +88,13 @@ static bool knn_prefilter_wanted(int knn_mode, int64_t nt, int k) {
 static bool knn_dedup_wanted(int dedup_mode, int64_t nq, int64_t nt) {
     if (dedup_mode != FDR_DEDUP_AUTO) return dedup_mode != FDR_DEDUP_OFF;
     return nt >= 8192 && nq >= 1024;  // (from the size at which the prefilter mode engages)
+}
+
+// Is searching nu unique targets for nuq unique queries worth the gathers and the expansion?  Never with fewer unique
+// rows than neighbours asked for; else when forced (tests), or when the pairs to score fall to 90 %.
+static bool dedup_worth(int nu, int nuq, int64_t nt, int64_t nq, int k, int dedup_mode) {
+    if (nu < k) return false;
+    return dedup_mode == FDR_DEDUP_FORCE || (double)nu * nuq <= 0.9 * (double)nt * (double)nq;
 }
 
 // ---- prefilter mode: fp16 pass -> certificate + exact re-rank -> exact pass for the rest ------------------------------

@@ -13,7 +13,7 @@
 //   host_san overlaps OUT THREADS                 -> writes a random neighbour graph (whole, and as two appended blocks)
 //   host_san plan-print NQ NT D K SHAPE           -> one plan (devtools)
 //   host_san plan                                 -> sweeps the planner over edge sizes, checks invariants
-//   host_san layout                               -> sweeps the k-NN workspace layouts over the same sizes, checks them
+//   host_san layout                               -> sweeps the k-NN workspace layouts (and plan_regions) over the same sizes, checks them
 //   host_san upload                               -> sweeps the upload's scheduler over inputs x helper counts x links
 //                                                    on a link that records what it is handed, checks the record
 #include <algorithm>
@@ -352,6 +352,19 @@ struct LayoutCheck {
     }
 };
 
+// plan_regions: a plan's three regions -- zero bits, bound words, partial lists -- lie inside p.total_bytes, 256-byte
+// aligned and disjoint
+static bool check_plan_regions(const KnnPlan &p, int64_t nt) {
+    char *const base = reinterpret_cast<char *>((uintptr_t)1 << 40);
+    const PlanRegions R = plan_regions(base, p);
+    const std::vector<WsRegion> log = {{(size_t)((char *)R.bits - base), (size_t)((nt + 31) / 32) * 4},
+                                       {(size_t)((char *)R.shared - base), (size_t)p.nq_pad * 4},
+                                       {(size_t)((char *)R.partial - base), p.partial_bytes}};
+    LayoutCheck c{base, p.total_bytes, log};
+    c.regions();
+    return c.ok && (char *)R.bits == base;
+}
+
 static size_t g_tmp_bytes;  // what the stand-ins for rocprim's temporary-storage queries answer
 static size_t tmp_standin(size_t) { return g_tmp_bytes; }
 
@@ -360,9 +373,12 @@ static int check_layouts(const WsEnv &env, int64_t nq, int64_t nt, int d, int k)
     const int dp = padded_dim(d);
     bool ok = true;
     size_t want = knn_plan(env.num_cus, nq, nt, d, k).total_bytes;  // what fdr_knn_workspace_bytes must say
+    ok = ok && check_plan_regions(knn_plan(env.num_cus, nq, nt, d, k), nt);  // (the exact pass's plan)
     if (knn_prefilter_wanted(env.knn_mode, nt, k)) {
         std::vector<WsRegion> log;
         const PrefilterWs L = prefilter_ws(env, base, nq, nt, d, k, &log);
+        // (the candidate pass's plan, as launch_knn_prefilter asks for it)
+        ok = ok && check_plan_regions(knn_plan(env.num_cus, nq, nt, d, L.kp, prefilter_shape_live(env.live_mode, dp, L.kp, nq, env.num_cus, nt)), nt);
         LayoutCheck c{base, L.total, log};
         c.regions();
         c.inside(L.zidx, (size_t)k * 4, L.counter, 16);  // (the three counters come first)

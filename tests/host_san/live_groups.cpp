@@ -1,8 +1,10 @@
 // Host-only build of the live-chunk grouping (live_plan in knn_plan.inc) under AddressSanitizer + UBSan:
 // tests/test_live_groups.py builds this with the flags of test_host_san.py and runs it.
 //
-//   live_groups  -> random and hand-made block masks, several segment counts and launch sizes; prints
-//                   "rc=<0|1> plans=<n> merged=<n>" and a FAIL line per broken invariant
+//   live_groups  -> random and hand-made block masks, several segment counts and launch sizes; for every plan, and for
+//                   a single group of all its blocks, the launches round_schedule deals (launch sizes 0, 1, 64, 512 on
+//                   1, 2 and 4 queues); prints "rc=<0|1> plans=<n> merged=<n> schedules=<n>" and a FAIL line per
+//                   broken invariant
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -30,9 +32,45 @@ static int nl_of(unsigned m) {  // the instance a block would take by itself
     return pc > FDR_LIVE_MAX_NL ? FDR_LIVE_DENSE : std::max(pc, FDR_LIVE_MIN_NL);
 }
 
+// round_schedule over groups of `items`: every group's items [0, n) exactly once by launches with ascending, contiguous
+// base; groups in the given order; no launch above the launch size and only a group's last one short; launch i on queue
+// i % queues; launch size 0: exactly one launch per non-empty group
+static int g_schedules;
+static int check_schedule(const std::vector<long long> &items, int nqb, int nseg) {
+    for (long long per : {0ll, 1ll, 64ll, 512ll})
+        for (int queues : {1, 2, 4}) {
+            const std::vector<RoundLaunch> S = round_schedule(items, per, queues);
+            ++g_schedules;
+            size_t i = 0;
+            for (size_t g = 0; g < items.size(); ++g) {
+                long long at = 0;
+                int launches = 0;
+                while (i < S.size() && S[i].group == (int)g) {
+                    const RoundLaunch &l = S[i];
+                    if (l.base != at || l.grid <= 0) return fail("schedule cover", nqb, nseg, per);
+                    if (l.queue != (int)(i % (size_t)queues)) return fail("schedule queue", nqb, nseg, per);
+                    if (per > 0 && l.grid > per) return fail("schedule launch size", nqb, nseg, per);
+                    at += l.grid;
+                    if (per > 0 && l.grid < per && at != items[g]) return fail("schedule short launch", nqb, nseg, per);
+                    ++launches;
+                    ++i;
+                }
+                if (at != items[g]) return fail("schedule group", nqb, nseg, per);  // (also: a group out of order)
+                if (per == 0 && launches != (items[g] > 0 ? 1 : 0)) return fail("schedule one launch", nqb, nseg, per);
+            }
+            if (i != S.size()) return fail("schedule order", nqb, nseg, per);
+        }
+    return 0;
+}
+
 static int check(const std::vector<unsigned> &masks, int nseg, long long min_items, int &merged) {
     const int nqb = (int)masks.size();
     const LivePlan P = live_plan(masks.data(), nqb, nseg, min_items);
+    {  // the launches of this plan's groups, and of a plain pass over the same blocks
+        std::vector<long long> items;
+        for (const LiveGroup &g : P.groups) items.push_back((long long)g.count * nseg);
+        if (check_schedule(items, nqb, nseg) || check_schedule({(long long)nqb * nseg}, nqb, nseg)) return 1;
+    }
     // every block exactly once; the groups tile `order`, ascending nl, blocks ascending inside a group (so that the work
     // items (segment, block of the group) are segment-major over an ascending block list)
     if ((int)P.order.size() != nqb || (int)P.ids.size() != nqb) return fail("sizes", nqb, nseg, min_items);
@@ -121,6 +159,17 @@ int main() {
         bad += check(masks, 1, 4, merged);
         ++plans;
     }
-    printf("rc=%d plans=%d merged=%d\n", bad ? 1 : 0, plans, merged);
+    // by hand: groups of 5, 0 and 3 items in launches of 2 on two queues -- the empty group launches nothing, and the deal
+    // goes on across the groups
+    {
+        const std::vector<RoundLaunch> S = round_schedule({5, 0, 3}, 2, 2);
+        const int want[5][4] = {{0, 0, 0, 2}, {0, 1, 2, 2}, {0, 0, 4, 1}, {2, 1, 0, 2}, {2, 0, 2, 1}};  // group, queue, base, grid
+        bool ok = S.size() == 5;
+        for (size_t i = 0; ok && i < 5; ++i)
+            ok = S[i].group == want[i][0] && S[i].queue == want[i][1] && S[i].base == want[i][2] && S[i].grid == want[i][3];
+        if (!ok) bad += fail("schedule by hand", 0, 1, 2);
+        bad += check_schedule({5, 0, 3}, 0, 1) + check_schedule({}, 0, 1);
+    }
+    printf("rc=%d plans=%d merged=%d schedules=%d\n", bad ? 1 : 0, plans, merged, g_schedules);
     return bad ? 1 : 0;
 }

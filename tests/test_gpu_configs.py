@@ -170,6 +170,25 @@ def test_rank_slice_of_one_million_rows_d128_in_one_launch(ctx, oracle):
     assert 65_536 <= uq <= 117_900 and ut >= 4 * uq  # (256 .. 460 blocks of 256 unique queries on 256 CUs)
     assert _pass(tr) == (128, 8, 8, 16, 0) and tr["pass_wps"] == 4, tr  # eight waves, four-unit stages (W8U4)
     assert ctx.last_prefilter_launches() == (1, 1) and (tr["pass_launches"], tr["pass_queues"]) == (1, 1)
+    # the same call in exact mode, timed: every span the launchers open is closed on its own kind -- the tile pass and
+    # the merge have elapsed time, the candidate pass none
+    import torch
+    from _paths_rows import _normalize
+    from fedrann_amd import _lib
+    from fedrann_amd.distributed import HipEngine
+    Ehat, zero = _normalize(ctx, E)
+    ctx.set_knn_mode("exact")
+    ctx.timing(True)
+    try:
+        HipEngine(ctx, E.device).knn(Ehat[:110_000], zero[:110_000], 110_000, Ehat, zero, E.shape[0], 128, 20)
+        torch.cuda.synchronize(E.device)
+        spans = {name: ctx.timing_read(i) for i, name in enumerate(_lib.KERNELS)}
+    finally:
+        ctx.timing(False)
+        ctx.set_knn_mode("auto")
+    assert ctx.last_knn_trace()["kind"] == "exact", ctx.last_knn_trace()
+    assert spans["knn_tile"][0] > 0 and spans["knn_tile"][1] > 0 and spans["knn_merge"][0] > 0 and spans["knn_merge"][1] > 0, spans
+    assert spans["knn_prefilter"] == (0, 0.0), spans
 
 
 def test_per_rank_workspace_of_configs_4_and_5_fits_hbm(ctx):

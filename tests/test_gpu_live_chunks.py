@@ -74,7 +74,7 @@ def same_bits(got, want):
 
 def run_forced(ctx, E, want):
     got = ctx.knn(E, K)
-    tr = ctx.last_knn_trace()
+    tr, launches = ctx.last_knn_trace(), ctx.last_prefilter_launches()
     assert tr["kind"] == "prefilter" and tr["pass_live"] == 1 and tr["pass_waves"] == 8 and tr["pass_units"] == 8, tr
     assert same_bits(got, want), "forced live-chunk pass differs from the oracle"
     ctx.set_knn_mode("exact")
@@ -85,6 +85,9 @@ def run_forced(ctx, E, want):
     assert same_bits(got, exact), "forced live-chunk pass differs from exact mode"
     items = {k: v for k, v in tr.items() if k.startswith("pass_live_") and k != "pass_live"}
     assert items == expected_items(E, tr["pass_segments"]), (items, expected_blocks(E))
+    # 36 .. 52 query blocks, far below one round: every group in ONE launch, all on the caller's stream
+    assert tr["pass_launches"] == sum(1 for v in items.values() if v != 0) and tr["pass_queues"] == 1, tr
+    assert launches == (tr["pass_launches"], tr["pass_queues"]), (launches, tr)
     return tr
 
 

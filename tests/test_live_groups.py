@@ -18,7 +18,12 @@ def test_live_chunk_groups_under_sanitizers():
     (segment, block) are segment-major; a block runs on the instance of its own live-chunk count (below two: two) or,
     where its group is smaller than one launch, on the next larger one -- never a smaller one, and never moved when
     nothing is merged; the dense group holds exactly the blocks of seven or eight live chunks (plus a last live group too
-    small for a launch); a block's ids are its group's NL chunks, ascending, and cover its mask."""
+    small for a launch); a block's ids are its group's NL chunks, ascending, and cover its mask.
+
+    And the launches round_schedule (knn_plan.inc) deals for every such plan's groups and for a single group of the same
+    blocks, launch sizes 0, 1, 64, 512 on 1, 2 and 4 queues: each group's items covered exactly once by launches with
+    ascending, contiguous base, groups in the plan's order, no launch above the launch size, only a group's last launch
+    short, launch i on queue i mod queues, launch size 0 one launch per non-empty group; one list spelled out by hand."""
     gxx = shutil.which("g++")
     if gxx is None:
         pytest.skip("g++ not available")
@@ -32,3 +37,4 @@ def test_live_chunk_groups_under_sanitizers():
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-2000:])
     f = dict(kv.split("=", 1) for kv in r.stdout.split() if "=" in kv)
     assert f["rc"] == "0" and int(f["plans"]) > 200 and int(f["merged"]) > 100
+    assert int(f["schedules"]) >= 2 * 12 * int(f["plans"])  # (every plan: its groups and the single group, 4 sizes x 3 queues)
