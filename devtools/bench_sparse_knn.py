@@ -1,12 +1,16 @@
 """Time the exact sparse k-NN (fdr_knn_sparse) on synthetic reads with IDF values, next to the projected search.
 
-    python devtools/bench_sparse_knn.py [--reads 100000 1000000] [--k 20] [--steps 3]
+    python devtools/bench_sparse_knn.py [--reads 100000 1000000] [--k 20] [--steps 3] [--metric cosine|jaccard]
+                                        [--values idf|none]
 
 Rows: synth(R, doubling=True) (2 R rows), value of feature f = idf[f] (what --no-projection searches).  For each size
 it prints one JSON line: the median wall time of the knn_sparse call (host arrays in, results out: it synchronises;
 the upload of the CSR is included), sum over features of df^2 (row-pair updates), the posting bytes 8 * sum df^2 over
 that time, and the median wall time of embed_knn at d = 128 on the same rows (the projected path of config 3; the
 compacted CSR, as the command line passes it).  Kernel times alone: run it under rocprofv3 --kernel-trace --stats.
+--metric jaccard times fdr_knn_sparse_metric on the rows' sets (values=None, 4 posting bytes per pair update);
+--values none gives cosine the same rows without values (every stored entry 1), the like-for-like comparison.
+"sparse_ms_all" lists every timed call, so the spread between repetitions is visible.
 """
 import argparse
 import json
@@ -30,7 +34,7 @@ def _median_ms(fn, steps):
         t0 = time.perf_counter()
         fn()
         t.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(t))
+    return float(np.median(t)), [round(x, 2) for x in t]
 
 
 def main():
@@ -39,26 +43,30 @@ def main():
     ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--no-projected", action="store_true", help="skip the d = 128 comparison")
+    ap.add_argument("--metric", choices=["cosine", "jaccard"], default="cosine")
+    ap.add_argument("--values", choices=["idf", "none"], default="idf", help="cosine only: IDF values, or none (ones)")
     a = ap.parse_args()
     ctx = _lib.Context(int(os.environ.get("FEDRANN_DEVICE", "0")))
     for R in a.reads:
         s = synth(R, doubling=True)
         indptr, indices, F = s["indptr"], s["indices"], s["n_features"]
-        values = idf_weights(s["counts"], F)[indices]
+        values = None if a.metric == "jaccard" or a.values == "none" else idf_weights(s["counts"], F)[indices]
+        entry_bytes = 4 if a.metric == "jaccard" else 8
         n = indptr.size - 1
         df = np.bincount(indices, minlength=F).astype(np.float64)
         sum_df2 = float(np.sum(df * df))
-        ms = _median_ms(lambda: ctx.knn_sparse(indptr, indices, values, F, a.k), a.steps)
+        ms, all_ms = _median_ms(lambda: ctx.knn_sparse(indptr, indices, values, F, a.k, metric=a.metric), a.steps)
         trace = ctx.last_knn_trace()
         out = {"reads": R, "rows": n, "n_features": F, "nnz_per_row": indices.size / n, "mean_df": float(df[df > 0].mean()),
-               "max_df": int(df.max()), "sum_df2": sum_df2, "k": a.k, "sparse_ms": round(ms, 2),
-               "posting_GBps": round(8 * sum_df2 / (ms * 1e-3) / 1e9, 1), "range_queries": trace["range_queries"],
+               "max_df": int(df.max()), "sum_df2": sum_df2, "k": a.k, "metric": a.metric,
+               "values": "none" if values is None else "idf", "sparse_ms": round(ms, 2), "sparse_ms_all": all_ms,
+               "posting_GBps": round(entry_bytes * sum_df2 / (ms * 1e-3) / 1e9, 1), "range_queries": trace["range_queries"],
                "zero_queries": trace["zero_queries"]}
         if not a.no_projected:
             P = build_precompute_matrix(s["counts"], 128, n_features=F)
             ctx.projection_load(P.indptr, P.indices, P.data, F, 128)
             cip, cix = ctx.csr_compact(indptr, indices)
-            out["projected_d128_ms"] = round(_median_ms(lambda: ctx.embed_knn(cip, cix, a.k), a.steps), 2)
+            out["projected_d128_ms"] = round(_median_ms(lambda: ctx.embed_knn(cip, cix, a.k), a.steps)[0], 2)
         print(json.dumps(out), flush=True)
 
 

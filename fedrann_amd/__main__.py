@@ -13,6 +13,8 @@ projection matrix -> embeddings -> k-NN -> overlaps.tsv.  Entry points:
 
 --no-projection: stages 2-3 build the IDF-weighted feature rows (value of feature f = idf[f]) instead of the
 projection and the embeddings, and stage 4 searches them exactly (fdr_knn_sparse); -n is ignored.  One GPU.
+--no-projection-metric jaccard (with --no-projection): stage 2 builds no weights and stage 4 searches the rows'
+k-mer sets by exact Jaccard distance (fdr_knn_sparse_metric), the quantity MinHash tools estimate.
 
 --devices 0,1,...: every stage is sharded over several GPUs of the node.  The parent process starts one
 child per GPU BEFORE it touches a GPU itself; from reads, every child counts and searches its byte range of
@@ -94,6 +96,9 @@ def build_parser():
     g.add_argument("--no-projection", action="store_true", default=False,
                    help="Search the IDF-weighted feature rows themselves (exact cosine k-NN, no random projection: "
                         "the ground truth the projection approximates); -n is ignored.  One GPU only.")
+    g.add_argument("--no-projection-metric", choices=["cosine", "jaccard"], default="cosine",
+                   help="With --no-projection: cosine on the IDF-weighted rows, or the exact Jaccard distance of the "
+                        "rows' feature sets (no weights).")
     g.add_argument("--device", type=int, default=None, help="GPU ordinal (default $LOCAL_RANK or 0).")
     g.add_argument("--devices", type=str, default=None,
                    help="Comma-separated GPU ordinals: shard the rows over these GPUs (one process each).")
@@ -195,14 +200,20 @@ def check_limits(embedding_dimension, nndescent_n_neighbors):
 
 def load_inputs(*, output_dir, embedding_dimension, save_feature_matrix, kmer_searcher_output=None,
                 kmer_library=None, feature_matrix=None, kmer_counts=None, read_names_path=None, save=True,
-                no_projection=False):
+                no_projection=False, metric="cosine"):
     """Stages 2-3a of the reference pipeline on the host (__main__.py:329-345): the projection matrix and
     the read x feature CSR.  Returns (indptr, indices, n_features, P, read_names, strands); with no_projection the
-    IDF weights of the features (float32 [n_features]) take P's place."""
+    IDF weights of the features (float32 [n_features]) take P's place, or None with metric="jaccard" (sets have
+    no weights)."""
+    jaccard = no_projection and metric == "jaccard"
+    if jaccard:
+        logger.info("--- 2. (skipped) no IDF weights: the Jaccard search takes the feature sets, values=None ---")
     if kmer_searcher_output:
         from .precompute import read_kmer_counts
         n_features = 2 * int(read_kmer_counts(kmer_library).size)  # (count_kmers.py:148)
-        if no_projection:
+        if jaccard:
+            P = None
+        elif no_projection:
             logger.info("--- 2. Generate IDF weights (no projection) ---")
             P = idf_weights(read_kmer_counts(kmer_library), n_features)
         else:
@@ -214,7 +225,9 @@ def load_inputs(*, output_dir, embedding_dimension, save_feature_matrix, kmer_se
     else:
         indptr, indices, n_features = load_feature_matrix_npz(feature_matrix)
         counts = _load_counts(kmer_counts)
-        if no_projection:
+        if jaccard:
+            P = None
+        elif no_projection:
             logger.info("--- 2. Generate IDF weights (no projection) ---")
             P = idf_weights(counts, n_features)
         else:
@@ -230,11 +243,13 @@ def load_inputs(*, output_dir, embedding_dimension, save_feature_matrix, kmer_se
 def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                          nndescent_n_neighbors, save_feature_matrix, keep_intermediates, chunk_size,
                          kmer_searcher_output=None, kmer_library=None, feature_matrix=None,
-                         kmer_counts=None, read_names_path=None, no_projection=False):
+                         kmer_counts=None, read_names_path=None, no_projection=False,
+                         no_projection_metric="cosine"):
     """Stages 2-4 of the reference pipeline (__main__.py:329-391) on one GPU.  The embeddings never leave
     HBM between the projection and the search (fdr_embed_knn), and only the features P has entries for
     cross PCIe (fdr_csr_compact; the saved feature_matrix.npz is the full matrix).  no_projection: stage 4
-    searches the IDF-weighted feature rows themselves (value of feature f = idf[f]; fdr_knn_sparse)."""
+    searches the IDF-weighted feature rows themselves (value of feature f = idf[f]; fdr_knn_sparse), or with
+    no_projection_metric="jaccard" their sets by Jaccard distance (fdr_knn_sparse_metric)."""
     from . import _lib
     from .feature_extraction import _projection_csr
     if kmer_searcher_output:
@@ -244,10 +259,19 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     indptr, indices, n_features, P, read_names, strands = load_inputs(
         output_dir=output_dir, embedding_dimension=embedding_dimension, save_feature_matrix=save_feature_matrix,
         kmer_searcher_output=kmer_searcher_output, kmer_library=kmer_library, feature_matrix=feature_matrix,
-        kmer_counts=kmer_counts, read_names_path=read_names_path, no_projection=no_projection)
+        kmer_counts=kmer_counts, read_names_path=read_names_path, no_projection=no_projection,
+        metric=no_projection_metric)
     ctx = _lib.default_context()
+    if no_projection and no_projection_metric == "jaccard":
+        logger.info("--- 4. Nearest Neighbors Search (exact, metric = jaccard, on the feature sets) ---")
+        logger.info("--no-projection: -n/--embedding-dimension (%d) is ignored; %d rows x %d features, %d stored "
+                    "entries", embedding_dimension, indptr.size - 1, n_features, indices.size)
+        neighbor_matrix, distances = ctx.knn_sparse(indptr, indices, None, n_features, nndescent_n_neighbors,
+                                                    metric="jaccard")
+        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates)
+        return
     if no_projection:
-        logger.info("--- 4. Nearest Neighbors Search (exact, on the IDF-weighted feature rows) ---")
+        logger.info("--- 4. Nearest Neighbors Search (exact, metric = cosine, on the IDF-weighted feature rows) ---")
         logger.info("--no-projection: -n/--embedding-dimension (%d) is ignored; %d rows x %d features, %d stored "
                     "entries", embedding_dimension, indptr.size - 1, n_features, indices.size)
         neighbor_matrix, distances = ctx.knn_sparse(indptr, indices, P[indices], n_features, nndescent_n_neighbors)
@@ -509,6 +533,9 @@ def main(argv=None):
     if args.no_projection and args.devices and len([x for x in args.devices.split(",") if x.strip()]) > 1:
         raise SystemExit("--no-projection runs on one GPU: it cannot be combined with --devices over several GPUs "
                          "(sharding the sparse search is not implemented)")
+    if args.no_projection_metric != "cosine" and not args.no_projection:
+        raise SystemExit("--no-projection-metric %s needs --no-projection (the projected search is cosine only)"
+                         % args.no_projection_metric)
     if args.device is not None and not args.rank_worker:
         os.environ["FEDRANN_DEVICE"] = str(args.device)
     output_dir = abspath(args.output_dir)
@@ -561,7 +588,8 @@ def main(argv=None):
         save_feature_matrix=args.save_feature_matrix, keep_intermediates=args.keep_intermediates,
         chunk_size=args.chunk_size, kmer_searcher_output=args.kmer_searcher_output,
         kmer_library=args.kmer_library, feature_matrix=args.feature_matrix,
-        kmer_counts=args.kmer_counts, read_names_path=args.read_names, no_projection=args.no_projection)
+        kmer_counts=args.kmer_counts, read_names_path=args.read_names, no_projection=args.no_projection,
+        no_projection_metric=args.no_projection_metric)
 
 
 if __name__ == "__main__":

@@ -23,7 +23,7 @@ SYMBOLS = (
     "fdr_kmer_count_begin", "fdr_kmer_count_add", "fdr_kmer_count_finish", "fdr_reads_scan", "fdr_reads_parse",
     "fdr_kmer_output_append", "fdr_last_query_paths", "fdr_last_knn_trace", "fdr_kmer_count_export_dev",
     "fdr_kmer_count_merge_dev", "fdr_kmer_count_merge", "fdr_set_knn_capture", "fdr_last_candidates",
-    "fdr_last_range_sets", "fdr_knn_sparse", "fdr_set_live_chunks",
+    "fdr_last_range_sets", "fdr_knn_sparse", "fdr_set_live_chunks", "fdr_knn_sparse_metric",
 )
 FDR_MAX_K = 128
 KERNELS = ("embed_csr", "normalize_rows", "knn_tile", "knn_merge", "knn_prefilter", "knn_rerank",
@@ -37,6 +37,9 @@ FALLBACKS = ("none", "chunked", "whole")
 # fdr_set_knn_capture (include/fedrann_hip.h: FDR_CAPTURE_*, FDR_RANGE_CAP)
 CAPTURE_CANDIDATES, CAPTURE_RANGE = 1, 2
 RANGE_CAP = 1024
+# fdr_knn_sparse_metric (include/fedrann_hip.h: FDR_METRIC_*)
+METRIC_COSINE, METRIC_JACCARD = 0, 1
+SPARSE_METRICS = {"cosine": METRIC_COSINE, "jaccard": METRIC_JACCARD}
 
 
 class KnnTrace(ctypes.Structure):
@@ -101,6 +104,7 @@ def load_library():
     L.fdr_knn.argtypes = [vp, vp, i64, i32, i32, vp, vp]
     L.fdr_embed_knn.argtypes = [vp, i64, vp, vp, i32, vp, vp, vp]
     L.fdr_knn_sparse.argtypes = [vp, i64, i64, vp, vp, vp, i32, vp, vp]
+    L.fdr_knn_sparse_metric.argtypes = [vp, i32, i64, i64, vp, vp, vp, i32, vp, vp]
     L.fdr_embed_dev.argtypes = [vp, i64, vp, vp, vp, vp]
     L.fdr_normalize_dev.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     L.fdr_knn_workspace_bytes.argtypes = [vp, i64, i64, i32, i32]
@@ -317,6 +321,13 @@ def overlaps_write(path, idx, dist, name_off, names, strands, row0=0, append=Fal
     if rc != 0:
         raise FedrannHipError("fdr_overlaps_write failed (%d): %s" % (rc, L.fdr_last_error().decode()))
     return int(lines.value)
+
+
+def sparse_metric_code(metric):
+    """FDR_METRIC_* of a metric name of Context.knn_sparse; needs no GPU."""
+    if not isinstance(metric, str) or metric not in SPARSE_METRICS:
+        raise ValueError("metric must be 'cosine' or 'jaccard', got %r" % (metric,))
+    return SPARSE_METRICS[metric]
 
 
 def check_sparse_rows(indptr, indices, values, n_features, k):
@@ -635,16 +646,25 @@ class Context:
                     "fdr_knn")
         return idx, dist
 
-    def knn_sparse(self, indptr, indices, values, n_features, k):
-        """Exact cosine k-NN of the rows of a CSR (fdr_knn_sparse): the bits of knn() on the densified matrix,
-        without densifying it.  indptr int64 [n + 1], indices int32 strictly ascending inside each row and in
-        [0, n_features), values float32 (finite) or None (every stored entry 1).  Returns (idx int32 [n, k],
-        dist float32 [n, k])."""
+    def knn_sparse(self, indptr, indices, values, n_features, k, metric="cosine"):
+        """Exact k-NN of the rows of a CSR.  indptr int64 [n + 1], indices int32 strictly ascending inside each row
+        and in [0, n_features), values float32 (finite) or None (every stored entry 1).  Returns (idx int32 [n, k],
+        dist float32 [n, k]).
+        metric="cosine" (fdr_knn_sparse): the bits of knn() on the densified matrix, without densifying it.
+        metric="jaccard" (fdr_knn_sparse_metric): the Jaccard distance of the rows' sets, a row's set being its stored
+        entries with a value other than 0: (float32)((u - c) / u) in float64 for c shared features and a union of u,
+        0 for two empty rows; ascending by (distance, index)."""
+        code = sparse_metric_code(metric)
         n, k, F = check_sparse_rows(indptr, indices, values, n_features, k)
         idx = np.empty((n, k), dtype=np.int32)
         dist = np.empty((n, k), dtype=np.float32)
-        self._check(self._L.fdr_knn_sparse(self._h, n, F, _ptr(indptr), _ptr(indices), _ptr(values), k, _ptr(idx),
-                                           _ptr(dist)), "fdr_knn_sparse")
+        if code == METRIC_COSINE:
+            self._check(self._L.fdr_knn_sparse(self._h, n, F, _ptr(indptr), _ptr(indices), _ptr(values), k,
+                                               _ptr(idx), _ptr(dist)), "fdr_knn_sparse")
+        else:
+            self._check(self._L.fdr_knn_sparse_metric(self._h, code, n, F, _ptr(indptr), _ptr(indices),
+                                                      _ptr(values), k, _ptr(idx), _ptr(dist)),
+                        "fdr_knn_sparse_metric")
         return idx, dist
 
     def embed_knn(self, a_indptr, a_indices, k, return_embedding=False, out=None):

@@ -4,7 +4,7 @@
 //   K2 normalize_rows_kernel E -> Ehat          (done inside pynndescent in the reference)
 //   K3 knn_tile_kernel       exact cosine top-k (nearest_neighbors.py:39-55 -> pynndescent)
 //   K4 knn_merge_kernel      merge of per-segment top-k lists
-//   S1-S4 (knn_sparse.inc)   exact cosine top-k on the sparse feature rows themselves (no projection)
+//   S1-S4 (knn_sparse.inc)   exact cosine (S1j, S3j: Jaccard) top-k on the sparse feature rows themselves (no projection)
 //
 // Written for wave64 / MFMA / 160 KB LDS directly; there is no other backend.
 // ABI: include/fedrann_hip.h.  Design notes and rooflines: DESIGN.md.
@@ -532,7 +532,7 @@ struct fdr_ctx {
     DevBuf kc_a0, kc_a1, kc_c0, kc_c1, kc_mk, kc_mv, kc_rc;  // counting in blocks: accumulated table (ping / pong), merge buffers
     // sparse k-NN (knn_sparse.inc)
     DevBuf sp_ip, sp_ix, sp_val, sp_xhat, sp_keys, sp_keys2, sp_pos, sp_pos2, sp_efeat, sp_pval, sp_runptr, sp_heavy,
-        sp_cnt, sp_tmp;
+        sp_cnt, sp_tmp, sp_asize;
     long long ks_nnz = 0, kc_n = 0;
     int64_t kc_block_chars = 0;  // fdr_set_kmer_count_block
     int kc_blocks = 0;           // blocks of the last fdr_kmer_count
@@ -1903,7 +1903,7 @@ FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indp
     return knn_from_device_E(ctx, (const float *)ctx->E.p, n_rows, ctx->d, k, idx_out, dist_out);
 }
 
-#include "knn_sparse.inc"  // S1 .. S4: exact cosine k-NN on sparse feature rows (fdr_knn_sparse)
+#include "knn_sparse.inc"  // S1 .. S4: exact cosine / Jaccard k-NN on sparse feature rows (fdr_knn_sparse[_metric])
 #include "kmer_search.inc"
 #include "kmer_output_loader.inc"
 #include "reads_parser.inc"

@@ -30,8 +30,21 @@
 // Cost model: the pair updates are sum over features f of df_f^2 (df_f = posting length); each reads an 8-byte
 // posting entry (row, value), so the search moves ~8 * sum df_f^2 bytes, mostly from L2.  A range-split query
 // costs ceil(n / SP_W) binary searches per stored entry on top.
+//
+// S1j / S3j / S3rj  exact Jaccard k-NN on the same rows (fdr_knn_sparse_metric, FDR_METRIC_JACCARD).  A row's set is
+// its stored entries whose value is not +-0 (every stored entry without values).  With a = |S_q|, b = |S_t|,
+// c = |S_q & S_t| and u = a + b - c, dist = (float)((double)(u - c) / (double)u), 0 for u = 0 (DESIGN.md section 4).
+//   S1j sp_rows_jaccard_kernel  per row: the argument checks of S1, the set size a_r, the empty flag, one posting key
+//                          per present entry; no xhat.  The sort, the run flags, the scan and S2 (without values) follow.
+//   S3j / S3rj knn_sparse_kernel<RANGE, FDR_METRIC_JACCARD>  the walk of S3 / S3r with an int32 count in the table
+//                          slot: a feature step adds 1 where the cosine instance does its fma (the lanes of a step hit
+//                          distinct targets, so a plain LDS increment under the step barrier is enough).  At the end
+//                          of a table the sizes a_t of the occupied slots are read and the distance is formed in fp64.
+//                          The hand-off at SP_LIMIT, the ranges, the merge, the distance-1 fill and S4 (the empty
+//                          rows take the zero rows' place) are shared.
+// Cost model: the same sum over features of df_f^2 pair updates, each reading a 4-byte posting entry (the row only).
 // ------------------------------------------------------------------------------------------
-#define SP_CAP 1024    // hash-table slots per query (key int32 | fp32 accumulator: 8 KiB of LDS)
+#define SP_CAP 1024    // hash-table slots per query (key int32 | fp32 accumulator or int32 count: 8 KiB of LDS)
 #define SP_LOG2CAP 10
 #define SP_LIMIT 512   // more distinct targets than this before a chunk of 64 postings: the range-split kernel
 #define SP_W 512       // target rows per range of the range-split kernel (<= SP_CAP: the table cannot fill)
@@ -44,8 +57,8 @@ static_assert((1 << SP_LOG2CAP) == SP_CAP, "SP_CAP is a power of two");
 
 // counters of one call (u64 each)
 #define SP_CNT_ERR 0      // or of SP_ERR_* bits
-#define SP_CNT_DROPPED 1  // stored entries without a posting (xhat = +-0)
-#define SP_CNT_ZERO 2     // zero rows
+#define SP_CNT_DROPPED 1  // stored entries without a posting (xhat = +-0; Jaccard: value = +-0)
+#define SP_CNT_ZERO 2     // zero rows (Jaccard: empty rows)
 #define SP_CNT_HEAVY 3    // queries handed to the range-split kernel
 #define SP_ERR_RANGE 1u
 #define SP_ERR_ORDER 2u
@@ -91,6 +104,40 @@ __global__ __launch_bounds__(256) void sp_rows_kernel(long long n, long long F, 
     if (dropped) atomicAdd(&cnt[SP_CNT_DROPPED], dropped);
 }
 
+// S1j: one thread per row
+__global__ __launch_bounds__(256) void sp_rows_jaccard_kernel(long long n, long long F,
+                                                              const long long *__restrict__ indptr,
+                                                              const int *__restrict__ indices,
+                                                              const float *__restrict__ vals, int *__restrict__ asize,
+                                                              u64 *__restrict__ keys, unsigned *__restrict__ pos,
+                                                              int *__restrict__ efeat, unsigned char *__restrict__ zero,
+                                                              u64 *__restrict__ cnt) {
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    const long long b = indptr[q], e = indptr[q + 1];
+    unsigned err = 0;
+    long long prev = -1;
+    int a = 0;  // |S_q|: the stored entries whose value is not +-0
+    for (long long j = b; j < e; ++j) {
+        const long long f = indices[j];
+        const float v = vals ? vals[j] : 1.0f;
+        if (f < 0 || f >= F) err |= SP_ERR_RANGE;
+        else if (f <= prev) err |= SP_ERR_ORDER;
+        prev = f;
+        if (!isfinite(v)) err |= SP_ERR_VALUE;
+        const bool present = v != 0.0f;
+        keys[j] = (present && err == 0u) ? (((u64)f << 32) | (u64)q) : ((u64)F << 32);  // (F << 32: after every posting)
+        pos[j] = (unsigned)j;
+        efeat[j] = -1;
+        a += present ? 1 : 0;
+    }
+    asize[q] = a;
+    zero[q] = a > 0 ? 0 : 1;
+    if (a == 0) atomicAdd(&cnt[SP_CNT_ZERO], 1ull);
+    if (err) atomicOr(&cnt[SP_CNT_ERR], (u64)err);
+    if (e - b > a) atomicAdd(&cnt[SP_CNT_DROPPED], (u64)(e - b - a));  // (without an error: the entries at +-0)
+}
+
 __global__ __launch_bounds__(256) void sp_run_flags_kernel(long long m, const u64 *__restrict__ keys,
                                                            int *__restrict__ flag) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -98,7 +145,7 @@ __global__ __launch_bounds__(256) void sp_run_flags_kernel(long long m, const u6
 }
 
 // S2: sorted postings -> run offsets, rows, values, and each stored entry's run id (features renumbered densely in
-// ascending order, so no array is as long as F)
+// ascending order, so no array is as long as F); xhat = pval = null (Jaccard): no values
 __global__ __launch_bounds__(256) void sp_postings_kernel(long long m, const u64 *__restrict__ keys,
                                                           const unsigned *__restrict__ pos,
                                                           const int *__restrict__ run_incl,
@@ -111,7 +158,7 @@ __global__ __launch_bounds__(256) void sp_postings_kernel(long long m, const u64
     const unsigned p = pos[i];
     efeat[p] = c;
     prow[i] = (int)(unsigned)keys[i];
-    pval[i] = xhat[p];
+    if (pval) pval[i] = xhat[p];
     if (i == 0 || run_incl[i - 1] != run_incl[i]) runptr[c] = i;
     if (i == m - 1) runptr[c + 1] = m;
 }
@@ -190,18 +237,21 @@ __device__ __forceinline__ long long sp_lower_bound(const int *__restrict__ a, l
     return lo;
 }
 
-// S3 / S3r: one wave (one workgroup) per query
-template <bool RANGE>
+// S3 / S3r (METRIC = FDR_METRIC_COSINE) and S3j / S3rj (FDR_METRIC_JACCARD: xhat = pval = null, asize = the set
+// sizes): one wave (one workgroup) per query
+template <bool RANGE, int METRIC>
 __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, const long long *__restrict__ indptr,
                                                         const int *__restrict__ efeat, const float *__restrict__ xhat,
                                                         const long long *__restrict__ runptr,
                                                         const int *__restrict__ prow, const float *__restrict__ pval,
+                                                        const int *__restrict__ asize,
                                                         const unsigned char *__restrict__ zero, int k,
                                                         const int *__restrict__ zidx, const float *__restrict__ zdist,
                                                         int *__restrict__ heavy, u64 *__restrict__ cnt,
                                                         int *__restrict__ idx_out, float *__restrict__ dist_out) {
     __shared__ u64 buf[SP_LIST + SP_CAP];  // [0, k): the query's list; [SP_LIST, ...): the table, then the sort buffer
     int *tab = reinterpret_cast<int *>(buf + SP_LIST);  // slot s: tab[2 s] = target row (SP_EMPTY), tab[2 s + 1] = acc
+    constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;  // (... or the int32 count of shared features)
     const int lane = threadIdx.x;
     const long long q = RANGE ? (long long)heavy[blockIdx.x] : (long long)blockIdx.x;
     int *out_i = idx_out + q * k;
@@ -214,13 +264,14 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, const long 
         return;
     }
     const long long qb = indptr[q], qe = indptr[q + 1];
+    const int qa = JAC ? asize[q] : 0;  // |S_q|
     for (int i = lane; i < SP_LIST; i += 64) buf[i] = KEY_INF;
     const long long nranges = RANGE ? (n + SP_W - 1) / SP_W : 1;
     const u64 lt = (1ull << lane) - 1ull;
     for (long long r = 0; r < nranges; ++r) {
         const int lo = RANGE ? (int)(r * SP_W) : 0;
         const int hi = RANGE ? (int)min(n, (long long)lo + SP_W) : (int)n;
-        for (int i = lane; i < SP_CAP; i += 64) buf[SP_LIST + i] = 0x00000000FFFFFFFFull;  // key SP_EMPTY, acc +0
+        for (int i = lane; i < SP_CAP; i += 64) buf[SP_LIST + i] = 0x00000000FFFFFFFFull;  // key SP_EMPTY, acc +0 / count 0
         __syncthreads();
         int count = 0;  // distinct targets in the table (wave-uniform)
         bool overflow = false;
@@ -233,7 +284,7 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, const long 
             if (j < qe) {
                 c = efeat[j];
                 if (c >= 0) {
-                    qv = xhat[j];
+                    if (!JAC) qv = xhat[j];
                     ps = runptr[c];
                     pe = runptr[c + 1];
                     if (RANGE) {
@@ -258,8 +309,12 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, const long 
                     if (e < s1) {
                         const int s = sp_insert(tab, prow[e], isnew);
                         if (s >= 0) {
-                            float *a = reinterpret_cast<float *>(&tab[2 * s + 1]);
-                            *a = __builtin_fmaf(v, pval[e], isnew ? 0.0f : *a);
+                            if (JAC) {
+                                tab[2 * s + 1] += 1;  // (a new slot holds 0; one lane per target in a step)
+                            } else {
+                                float *a = reinterpret_cast<float *>(&tab[2 * s + 1]);
+                                *a = __builtin_fmaf(v, pval[e], isnew ? 0.0f : *a);
+                            }
                         }
                     }
                     count += __popcll(__ballot(isnew));
@@ -280,7 +335,14 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, const long 
             const int t = (int)(unsigned)w;
             u64 key = KEY_INF;
             if (t != SP_EMPTY) {
-                const float d = dist_from_sim(__uint_as_float((unsigned)(w >> 32)));
+                float d;
+                if (JAC) {  // c >= 1 shared features: u = a + b - c >= 1, one fp64 division, one rounding
+                    const int c = (int)(unsigned)(w >> 32);
+                    const int u = qa + asize[t] - c;
+                    d = (float)((double)(u - c) / (double)u);
+                } else {
+                    d = dist_from_sim(__uint_as_float((unsigned)(w >> 32)));
+                }
                 if (d < 1.0f) key = ((u64)__float_as_uint(d) << 32) | (unsigned)t;
             }
             cand[i] = key;
@@ -335,12 +397,43 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, const long 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-FDR_EXPORT int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const int64_t *indptr,
-                              const int32_t *indices, const float *values, int32_t k, int32_t *idx_out,
-                              float *dist_out) {
+// S3 over every query, then S3r over the queries it handed on (h_heavy of them)
+template <int METRIC>
+static int sp_search(fdr_ctx *ctx, int64_t n, int32_t k, const int *zidx, const float *zdist, u64 *cnt,
+                     u64 &h_heavy) {
+    const hipStream_t st = ctx->stream;
+    constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;
+    const float *xhat = JAC ? nullptr : (const float *)ctx->sp_xhat.p;
+    const float *pval = JAC ? nullptr : (const float *)ctx->sp_pval.p;
+    const int *asize = JAC ? (const int *)ctx->sp_asize.p : nullptr;
+    hipLaunchKernelGGL((knn_sparse_kernel<false, METRIC>), dim3((unsigned)n), dim3(64), 0, st, (long long)n,
+                       (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_efeat.p, xhat,
+                       (const long long *)ctx->sp_runptr.p, (const int *)ctx->sp_pos.p, pval, asize,
+                       (const unsigned char *)ctx->zero.p, (int)k, zidx, zdist, (int *)ctx->sp_heavy.p, cnt,
+                       (int *)ctx->idx.p, (float *)ctx->dist.p);
+    HIP_TRY(hipGetLastError());
+    h_heavy = 0;
+    HIP_TRY(hipMemcpyAsync(&h_heavy, cnt + SP_CNT_HEAVY, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_heavy > 0) {
+        hipLaunchKernelGGL((knn_sparse_kernel<true, METRIC>), dim3((unsigned)h_heavy), dim3(64), 0, st, (long long)n,
+                           (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_efeat.p, xhat,
+                           (const long long *)ctx->sp_runptr.p, (const int *)ctx->sp_pos.p, pval, asize,
+                           (const unsigned char *)ctx->zero.p, (int)k, zidx, zdist, (int *)ctx->sp_heavy.p, cnt,
+                           (int *)ctx->idx.p, (float *)ctx->dist.p);
+        HIP_TRY(hipGetLastError());
+    }
+    return FDR_OK;
+}
+
+static int sp_knn(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
+                  const int32_t *indices, const float *values, int32_t k, int32_t *idx_out, float *dist_out) {
     int rc = use_device(ctx);
     if (rc) return rc;
     knn_call_begin(ctx);
+    const bool jac = metric == FDR_METRIC_JACCARD;
+    if (!jac && metric != FDR_METRIC_COSINE)
+        return fail(FDR_E_ARG, "knn_sparse: unknown metric %d (FDR_METRIC_COSINE, FDR_METRIC_JACCARD)", metric);
     if (!indptr || !idx_out || !dist_out) return fail(FDR_E_ARG, "knn_sparse: null pointer");
     if (k < 1 || k > FDR_MAX_K) return fail(FDR_E_ARG, "knn_sparse: k=%d unsupported (1..%d)", k, FDR_MAX_K);
     if (n < k) return fail(FDR_E_ARG, "knn_sparse: need n (%lld) >= k (%d)", (long long)n, k);
@@ -359,13 +452,14 @@ FDR_EXPORT int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const
     if ((rc = ctx->sp_ip.reserve((size_t)(n + 1) * 8))) return rc;
     if ((rc = ctx->sp_ix.reserve(m1 * 4))) return rc;
     if (values && (rc = ctx->sp_val.reserve(m1 * 4))) return rc;
-    if ((rc = ctx->sp_xhat.reserve(m1 * 4))) return rc;
+    if (!jac && (rc = ctx->sp_xhat.reserve(m1 * 4))) return rc;
+    if (jac && (rc = ctx->sp_asize.reserve((size_t)n * 4))) return rc;
     if ((rc = ctx->sp_keys.reserve(m1 * 8))) return rc;
     if ((rc = ctx->sp_keys2.reserve(m1 * 8))) return rc;
     if ((rc = ctx->sp_pos.reserve(m1 * 4))) return rc;
     if ((rc = ctx->sp_pos2.reserve(m1 * 4))) return rc;
     if ((rc = ctx->sp_efeat.reserve(m1 * 4))) return rc;
-    if ((rc = ctx->sp_pval.reserve(m1 * 4))) return rc;
+    if (!jac && (rc = ctx->sp_pval.reserve(m1 * 4))) return rc;
     if ((rc = ctx->sp_runptr.reserve((m1 + 1) * 8))) return rc;
     if ((rc = ctx->sp_heavy.reserve((size_t)n * 4))) return rc;
     if ((rc = ctx->sp_cnt.reserve(64 + (size_t)FDR_MAX_K * 8))) return rc;
@@ -381,10 +475,19 @@ FDR_EXPORT int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const
         if (values) HIP_TRY(hipMemcpyAsync(ctx->sp_val.p, values, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipMemsetAsync(cnt, 0, 64, st));
-    hipLaunchKernelGGL(sp_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n,
-                       (long long)n_features, (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_ix.p,
-                       values ? (const float *)ctx->sp_val.p : nullptr, (float *)ctx->sp_xhat.p, (u64 *)ctx->sp_keys.p,
-                       (unsigned *)ctx->sp_pos.p, (int *)ctx->sp_efeat.p, (unsigned char *)ctx->zero.p, cnt);
+    if (jac) {
+        hipLaunchKernelGGL(sp_rows_jaccard_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n,
+                           (long long)n_features, (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_ix.p,
+                           values ? (const float *)ctx->sp_val.p : nullptr, (int *)ctx->sp_asize.p,
+                           (u64 *)ctx->sp_keys.p, (unsigned *)ctx->sp_pos.p, (int *)ctx->sp_efeat.p,
+                           (unsigned char *)ctx->zero.p, cnt);
+    } else {
+        hipLaunchKernelGGL(sp_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n,
+                           (long long)n_features, (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_ix.p,
+                           values ? (const float *)ctx->sp_val.p : nullptr, (float *)ctx->sp_xhat.p,
+                           (u64 *)ctx->sp_keys.p, (unsigned *)ctx->sp_pos.p, (int *)ctx->sp_efeat.p,
+                           (unsigned char *)ctx->zero.p, cnt);
+    }
     HIP_TRY(hipGetLastError());
     u64 h_cnt[4];
     HIP_TRY(hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
@@ -418,8 +521,9 @@ FDR_EXPORT int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const
         HIP_TRY(rocprim::inclusive_scan(ctx->sp_tmp.p, tb, flag, run_incl, (size_t)kept, rocprim::plus<int>(), st));
         // posting rows go where the unsorted positions were
         hipLaunchKernelGGL(sp_postings_kernel, dim3(g), dim3(256), 0, st, kept, (const u64 *)ctx->sp_keys2.p,
-                           (const unsigned *)ctx->sp_pos2.p, (const int *)run_incl, (const float *)ctx->sp_xhat.p,
-                           (int *)ctx->sp_efeat.p, (int *)ctx->sp_pos.p, (float *)ctx->sp_pval.p,
+                           (const unsigned *)ctx->sp_pos2.p, (const int *)run_incl,
+                           jac ? nullptr : (const float *)ctx->sp_xhat.p, (int *)ctx->sp_efeat.p,
+                           (int *)ctx->sp_pos.p, jac ? nullptr : (float *)ctx->sp_pval.p,
                            (long long *)ctx->sp_runptr.p);
         HIP_TRY(hipGetLastError());
     }
@@ -428,24 +532,10 @@ FDR_EXPORT int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const
                            (int)k, zidx, zdist);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(knn_sparse_kernel<false>, dim3((unsigned)n), dim3(64), 0, st, (long long)n,
-                       (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_efeat.p, (const float *)ctx->sp_xhat.p,
-                       (const long long *)ctx->sp_runptr.p, (const int *)ctx->sp_pos.p, (const float *)ctx->sp_pval.p,
-                       (const unsigned char *)ctx->zero.p, (int)k, (const int *)zidx, (const float *)zdist,
-                       (int *)ctx->sp_heavy.p, cnt, (int *)ctx->idx.p, (float *)ctx->dist.p);
-    HIP_TRY(hipGetLastError());
     u64 h_heavy = 0;
-    HIP_TRY(hipMemcpyAsync(&h_heavy, cnt + SP_CNT_HEAVY, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (h_heavy > 0) {
-        hipLaunchKernelGGL(knn_sparse_kernel<true>, dim3((unsigned)h_heavy), dim3(64), 0, st, (long long)n,
-                           (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_efeat.p, (const float *)ctx->sp_xhat.p,
-                           (const long long *)ctx->sp_runptr.p, (const int *)ctx->sp_pos.p,
-                           (const float *)ctx->sp_pval.p, (const unsigned char *)ctx->zero.p, (int)k,
-                           (const int *)zidx, (const float *)zdist, (int *)ctx->sp_heavy.p, cnt, (int *)ctx->idx.p,
-                           (float *)ctx->dist.p);
-        HIP_TRY(hipGetLastError());
-    }
+    rc = jac ? sp_search<FDR_METRIC_JACCARD>(ctx, n, k, zidx, zdist, cnt, h_heavy)
+             : sp_search<FDR_METRIC_COSINE>(ctx, n, k, zidx, zdist, cnt, h_heavy);
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(idx_out, ctx->idx.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(dist_out, ctx->dist.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -457,4 +547,16 @@ FDR_EXPORT int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const
     t.range_queries = (int32_t)h_heavy;
     t.range_chunks = h_heavy ? (int32_t)((n + SP_W - 1) / SP_W) : 0;
     return FDR_OK;
+}
+
+FDR_EXPORT int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const int64_t *indptr,
+                              const int32_t *indices, const float *values, int32_t k, int32_t *idx_out,
+                              float *dist_out) {
+    return sp_knn(ctx, FDR_METRIC_COSINE, n, n_features, indptr, indices, values, k, idx_out, dist_out);
+}
+
+FDR_EXPORT int fdr_knn_sparse_metric(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features,
+                                     const int64_t *indptr, const int32_t *indices, const float *values, int32_t k,
+                                     int32_t *idx_out, float *dist_out) {
+    return sp_knn(ctx, metric, n, n_features, indptr, indices, values, k, idx_out, dist_out);
 }

@@ -1,10 +1,12 @@
-"""All-pairs cosine k-NN on the GPU.
+"""All-pairs cosine (or, on sparse rows, Jaccard) k-NN on the GPU.
 
 Mirror of the reference's fedrann/nearest_neighbors.py (NNDescent_ava.get_neighbors :22-55), which
 wraps pynndescent.NNDescent(...).neighbor_graph.  NN-descent approximates the exact k-NN graph;
 this class returns the exact graph (tiled MFMA distance kernel + top-k, see
 csrc/fedrann_hip.hip), so the forest / descent hyper-parameters are accepted and ignored.  A sparse matrix
 wider than FDR_MAX_DIM columns is searched as it is (csrc/knn_sparse.inc) instead of densified.
+metric="jaccard" (pynndescent's sparse_jaccard, which the reference's `metric` argument reaches) searches the sets of
+non-zero entries of the rows, always on the sparse route.
 Rows come back ascending by (distance, index); a row's self match is a neighbour like any other,
 as in `index.neighbor_graph`.
 """
@@ -27,10 +29,15 @@ class NNDescent_ava(_NearestNeighbors):
     def get_neighbors(self, data, metric="cosine", *, index_n_neighbors=50, n_trees=300,
                       leaf_size=200, n_iters=None, diversify_prob=1, pruning_degree_multiplier=1.5,
                       low_memory=True, n_jobs=64, seed=683985, verbose=True, context=None):
-        if metric != "cosine":
-            raise ValueError("only metric='cosine' is implemented (the reference's only call, "
-                             "__main__.py:186)")
+        if metric not in ("cosine", "jaccard"):
+            raise ValueError("metric must be 'cosine' (the reference's only call, __main__.py:186) or 'jaccard', "
+                             "got %r" % (metric,))
         ctx = context or _lib.default_context()
+        if metric == "jaccard":
+            # the sets depend on the values only through != 0: one route at every width, dense input included
+            if not sp.issparse(data) and np.ndim(data) != 2:
+                raise ValueError("data must be 2-D")
+            return self._sparse_neighbors(sp.csr_matrix(data), int(index_n_neighbors), ctx, verbose, metric="jaccard")
         if sp.issparse(data) and data.ndim == 2 and data.shape[1] > _lib.FDR_MAX_DIM:
             # too wide to densify (F = 2 x sampled k-mers: 1.3 M columns at 100 k reads): the exact search of the
             # sparse rows themselves, same canonical result as the dense route on the densified matrix
@@ -52,15 +59,22 @@ class NNDescent_ava(_NearestNeighbors):
         return nbr_indices, distances
 
     @staticmethod
-    def _sparse_neighbors(data, k, ctx, verbose):
+    def _sparse_neighbors(data, k, ctx, verbose, metric="cosine"):
         A = data.tocsr(copy=True)  # (the caller's matrix is left as it is)
         A.sum_duplicates()  # canonical: summed duplicates, ascending columns per row
         A.sort_indices()
+        if metric == "jaccard":
+            A.eliminate_zeros()  # (a stored zero is absent from the set either way)
         n, F = A.shape
         if n < k:
             raise ValueError("n_neighbors (%d) must not exceed the number of rows (%d)" % (k, n))
         if verbose:
-            logger.info("exact cosine k-NN on %s over the sparse rows: %d rows x %d features, %d stored entries, "
-                        "k = %d", ctx.device_info()["name"], n, F, A.nnz, k)
+            logger.info("exact %s k-NN on %s over the sparse rows: %d rows x %d features, %d stored entries, "
+                        "k = %d", metric, ctx.device_info()["name"], n, F, A.nnz, k)
+        if metric == "jaccard":
+            if not np.all(np.isfinite(A.data)):
+                raise ValueError("values must be finite")
+            # values=None: every stored entry is present (a cast to float32 could turn a tiny value into 0)
+            return ctx.knn_sparse(A.indptr.astype(np.int64), A.indices.astype(np.int32), None, F, k, metric="jaccard")
         return ctx.knn_sparse(A.indptr.astype(np.int64), A.indices.astype(np.int32),
                               np.ascontiguousarray(A.data, dtype=np.float32), F, k)

@@ -126,6 +126,25 @@ int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indptr, const i
 int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const int64_t *indptr, const int32_t *indices,
                    const float *values, int32_t k, int32_t *idx_out, float *dist_out);
 
+/* ---- the same search under a chosen measure  (NNDescent_ava.get_neighbors(data, metric=...) hands `metric` to
+ *      pynndescent, which searches sparse Jaccard natively: nearest_neighbors.py:26, :39-55) -----------------------
+ * FDR_METRIC_COSINE is fdr_knn_sparse itself, the same bits.  FDR_METRIC_JACCARD is the exact Jaccard distance of
+ * the rows' feature sets.  The set S_r of a row is its stored entries whose value is not +-0
+ * (values NULL: every stored entry); non-finite values are refused.  For query q and target t, a = |S_q|, b = |S_t|,
+ * c = |S_q & S_t|, u = a + b - c (all below 2^31, exact in a double): dist = 0.0f if u == 0, else
+ * (float)((double)(u - c) / (double)u), one IEEE double division and one round-to-nearest conversion: pynndescent's
+ * sparse_jaccard value, (union - intersection) / union, stored as float32.  Order (distance bits, index) ascending;
+ * self is a candidate at distance 0, an empty row too.  A target that shares no feature with a non-empty query is
+ * at exactly 1.0f (as is a pair whose quotient rounds to 1.0f), so a list with fewer than k rows below 1 ends in the
+ * smallest row indices not already in it.  An empty query: the first k empty rows at distance 0, then the first
+ * non-empty rows at distance 1.  Arguments, limits and error codes are those of fdr_knn_sparse; an unknown metric is
+ * FDR_E_ARG.  fdr_last_knn_trace reports FDR_TRACE_SPARSE (zero_queries = the empty rows).  Cost: ~4 bytes per
+ * row-pair update (the posting entry is the row alone). */
+#define FDR_METRIC_COSINE 0
+#define FDR_METRIC_JACCARD 1
+int fdr_knn_sparse_metric(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
+                          const int32_t *indices, const float *values, int32_t k, int32_t *idx_out, float *dist_out);
+
 /* ---- device-resident API (multi-GPU host, bench.py) ----------------------------------------
  * All pointers are device pointers; work is enqueued on `stream` (a hipStream_t). */
 int fdr_embed_dev(fdr_ctx *ctx, int64_t n_rows, const int64_t *d_indptr, const int32_t *d_indices,
