@@ -1,7 +1,7 @@
 """Time the exact sparse k-NN (fdr_knn_sparse) on synthetic reads with IDF values, next to the projected search.
 
     python devtools/bench_sparse_knn.py [--reads 100000 1000000] [--k 20] [--steps 3] [--metric cosine|jaccard]
-                                        [--values idf|none]
+                                        [--values idf|none] [--split] [--world W --rank r] [--block-rows B]
 
 Rows: synth(R, doubling=True) (2 R rows), value of feature f = idf[f] (what --no-projection searches).  For each size
 it prints one JSON line: the median wall time of the knn_sparse call (host arrays in, results out: it synchronises;
@@ -11,6 +11,12 @@ compacted CSR, as the command line passes it).  Kernel times alone: run it under
 --metric jaccard times fdr_knn_sparse_metric on the rows' sets (values=None, 4 posting bytes per pair update);
 --values none gives cosine the same rows without values (every stored entry 1), the like-for-like comparison.
 "sparse_ms_all" lists every timed call, so the spread between repetitions is visible.
+--split times the two halves of that call on their own as well: "build_ms" (Context.sparse_index: the host checks, the
+upload, S1, the sort and S2; each build replaces the one before and reuses its buffers, as knn_sparse does) and "search_ms" (SparseIndex.search
+of every row of one index, results copied out), with "index" = SparseIndex.info() (device bytes among it).
+--world W --rank r (implies the index) times the search of that rank's rows of shard_rows(n, W) alone, in query
+blocks of --block-rows rows if given ("rank_search_ms", "rank_rows"): what one rank of distributed.sparse_knn_rank
+searches after its build.
 """
 import argparse
 import json
@@ -45,6 +51,10 @@ def main():
     ap.add_argument("--no-projected", action="store_true", help="skip the d = 128 comparison")
     ap.add_argument("--metric", choices=["cosine", "jaccard"], default="cosine")
     ap.add_argument("--values", choices=["idf", "none"], default="idf", help="cosine only: IDF values, or none (ones)")
+    ap.add_argument("--split", action="store_true", help="time the index build and the search of all rows separately too")
+    ap.add_argument("--world", type=int, default=0, help="with --rank: time the search of one rank's rows of the index")
+    ap.add_argument("--rank", type=int, default=0)
+    ap.add_argument("--block-rows", type=int, default=None, help="with --world: search in query blocks of this many rows")
     a = ap.parse_args()
     ctx = _lib.Context(int(os.environ.get("FEDRANN_DEVICE", "0")))
     for R in a.reads:
@@ -62,6 +72,29 @@ def main():
                "values": "none" if values is None else "idf", "sparse_ms": round(ms, 2), "sparse_ms_all": all_ms,
                "posting_GBps": round(entry_bytes * sum_df2 / (ms * 1e-3) / 1e9, 1), "range_queries": trace["range_queries"],
                "zero_queries": trace["zero_queries"]}
+        if a.split or a.world:
+            from fedrann_amd.distributed import sparse_rank_blocks
+
+            def build():  # (no close(): the next build replaces the index and reuses its buffers)
+                ctx.sparse_index(indptr, indices, values, F, metric=a.metric)
+            if a.split:
+                out["build_ms"], out["build_ms_all"] = _median_ms(build, a.steps)
+                out["build_ms"] = round(out["build_ms"], 2)
+            with ctx.sparse_index(indptr, indices, values, F, metric=a.metric) as index:
+                out["index"] = index.info()
+                if a.split:
+                    ms, out["search_ms_all"] = _median_ms(lambda: index.search(a.k), a.steps)
+                    out["search_ms"] = round(ms, 2)
+                if a.world:
+                    lo, hi, blocks = sparse_rank_blocks(n, a.rank, a.world, a.block_rows)
+                    res = (np.empty((hi - lo, a.k), np.int32), np.empty((hi - lo, a.k), np.float32))
+
+                    def rank_search():
+                        for b0, b1 in blocks:
+                            index.search(a.k, b0, b1, out=(res[0][b0 - lo:b1 - lo], res[1][b0 - lo:b1 - lo]))
+                    ms, out["rank_search_ms_all"] = _median_ms(rank_search, a.steps)
+                    out.update(rank_search_ms=round(ms, 2), rank_rows=[lo, hi], world=a.world, rank=a.rank,
+                               block_rows=a.block_rows)
         if not a.no_projected:
             P = build_precompute_matrix(s["counts"], 128, n_features=F)
             ctx.projection_load(P.indptr, P.indices, P.data, F, 128)

@@ -24,6 +24,7 @@ SYMBOLS = (
     "fdr_kmer_output_append", "fdr_last_query_paths", "fdr_last_knn_trace", "fdr_kmer_count_export_dev",
     "fdr_kmer_count_merge_dev", "fdr_kmer_count_merge", "fdr_set_knn_capture", "fdr_last_candidates",
     "fdr_last_range_sets", "fdr_knn_sparse", "fdr_set_live_chunks", "fdr_knn_sparse_metric",
+    "fdr_sparse_index_build", "fdr_sparse_index_search", "fdr_sparse_index_info", "fdr_sparse_index_free",
 )
 FDR_MAX_K = 128
 KERNELS = ("embed_csr", "normalize_rows", "knn_tile", "knn_merge", "knn_prefilter", "knn_rerank",
@@ -105,6 +106,11 @@ def load_library():
     L.fdr_embed_knn.argtypes = [vp, i64, vp, vp, i32, vp, vp, vp]
     L.fdr_knn_sparse.argtypes = [vp, i64, i64, vp, vp, vp, i32, vp, vp]
     L.fdr_knn_sparse_metric.argtypes = [vp, i32, i64, i64, vp, vp, vp, i32, vp, vp]
+    L.fdr_sparse_index_build.argtypes = [vp, i32, i64, i64, vp, vp, vp]
+    L.fdr_sparse_index_search.argtypes = [vp, i32, i64, i64, vp, vp]
+    L.fdr_sparse_index_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i64),
+                                        ctypes.POINTER(i64), ctypes.POINTER(sz)]
+    L.fdr_sparse_index_free.argtypes = [vp]
     L.fdr_embed_dev.argtypes = [vp, i64, vp, vp, vp, vp]
     L.fdr_normalize_dev.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     L.fdr_knn_workspace_bytes.argtypes = [vp, i64, i64, i32, i32]
@@ -333,6 +339,32 @@ def sparse_metric_code(metric):
 def check_sparse_rows(indptr, indices, values, n_features, k):
     """The argument checks of Context.knn_sparse (fdr_knn_sparse repeats them on the device); needs no GPU.
     Returns (n, k, n_features)."""
+    return _check_sparse(indptr, indices, values, n_features, k)
+
+
+def check_sparse_csr(indptr, indices, values, n_features):
+    """The argument checks of Context.sparse_index: those of check_sparse_rows without a k, and at least one row
+    (fdr_sparse_index_build repeats them on the device); needs no GPU.  Returns (n, n_features)."""
+    n, _, F = _check_sparse(indptr, indices, values, n_features, None)
+    return n, F
+
+
+def check_sparse_search(n, k, lo=0, hi=None):
+    """The argument checks of SparseIndex.search on an index of n rows: 1 <= k <= min(FDR_MAX_K, n) and
+    0 <= lo <= hi <= n (hi=None: n); needs no GPU.  Returns (k, lo, hi)."""
+    for name, v in (("k", k), ("lo", lo), ("hi", hi)):
+        if isinstance(v, bool) or not (isinstance(v, (int, np.integer)) or (name == "hi" and v is None)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    k, lo, hi = int(k), int(lo), int(n if hi is None else hi)
+    if not 1 <= k <= FDR_MAX_K or k > n:
+        raise ValueError("need 1 <= k <= min(%d, n = %d), got k = %d" % (FDR_MAX_K, n, k))
+    if not 0 <= lo <= hi <= n:
+        raise ValueError("need 0 <= lo <= hi <= n = %d, got [%d, %d)" % (n, lo, hi))
+    return k, lo, hi
+
+
+def _check_sparse(indptr, indices, values, n_features, k):
+    """k=None: no k to check, but n >= 1."""
     for name, a, dt in (("indptr", indptr, np.int64), ("indices", indices, np.int32), ("values", values, np.float32)):
         if a is None and name == "values":
             continue
@@ -344,10 +376,13 @@ def check_sparse_rows(indptr, indices, values, n_features, k):
         raise ValueError("indptr is not a CSR row pointer of the indices")
     if values is not None and values.size != indices.size:
         raise ValueError("values and indices differ in length")
-    n, k, F = indptr.size - 1, int(k), int(n_features)
+    n, k, F = indptr.size - 1, None if k is None else int(k), int(n_features)
     if not 1 <= F <= np.iinfo(np.int32).max:
         raise ValueError("n_features must be in [1, 2^31)")
-    if not 1 <= k <= FDR_MAX_K or k > n:
+    if k is None:
+        if n < 1:
+            raise ValueError("need at least one row")
+    elif not 1 <= k <= FDR_MAX_K or k > n:
         raise ValueError("need 1 <= k <= min(%d, n = %d), got k = %d" % (FDR_MAX_K, n, k))
     if indices.size:
         if int(indices.min()) < 0 or int(indices.max()) >= F:
@@ -375,6 +410,7 @@ class Context:
         self.device = int(device)
         self.n_features = 0
         self.d = 0
+        self._sparse_gen = 0  # builds of the context's sparse index so far (SparseIndex: is mine still the one?)
 
     def _err(self):
         return self._L.fdr_last_error().decode("utf-8", "replace")
@@ -653,9 +689,11 @@ class Context:
         metric="cosine" (fdr_knn_sparse): the bits of knn() on the densified matrix, without densifying it.
         metric="jaccard" (fdr_knn_sparse_metric): the Jaccard distance of the rows' sets, a row's set being its stored
         entries with a value other than 0: (float32)((u - c) / u) in float64 for c shared features and a union of u,
-        0 for two empty rows; ascending by (distance, index)."""
+        0 for two empty rows; ascending by (distance, index).
+        The call builds the context's sparse index anew (a SparseIndex of this context is stale afterwards)."""
         code = sparse_metric_code(metric)
         n, k, F = check_sparse_rows(indptr, indices, values, n_features, k)
+        self._sparse_gen += 1
         idx = np.empty((n, k), dtype=np.int32)
         dist = np.empty((n, k), dtype=np.float32)
         if code == METRIC_COSINE:
@@ -666,6 +704,17 @@ class Context:
                                                       _ptr(values), k, _ptr(idx), _ptr(dist)),
                         "fdr_knn_sparse_metric")
         return idx, dist
+
+    def sparse_index(self, indptr, indices, values, n_features, metric="cosine"):
+        """The posting index of a CSR (arguments as knn_sparse, at least one row), kept on the device for any number
+        of SparseIndex.search calls: fdr_sparse_index_build.  A context holds one index: this call, and every
+        knn_sparse, replaces it, and a SparseIndex of the replaced one raises from then on."""
+        code = sparse_metric_code(metric)
+        n, F = check_sparse_csr(indptr, indices, values, n_features)
+        self._sparse_gen += 1
+        self._check(self._L.fdr_sparse_index_build(self._h, code, n, F, _ptr(indptr), _ptr(indices), _ptr(values)),
+                    "fdr_sparse_index_build")
+        return SparseIndex(self, n, metric, self._sparse_gen)
 
     def embed_knn(self, a_indptr, a_indices, k, return_embedding=False, out=None):
         """out=(idx int32 [n,k], dist float32 [n,k]): caller-owned (e.g. pinned, reused) result arrays."""
@@ -719,6 +768,69 @@ class Context:
     def knn_expand_dev(self, q0, nq, t_base, d_idx_u_all, d_dist_u_all, d_idx, d_dist, stream=0, u_row_stride=0):
         self._check(self._L.fdr_knn_expand_dev(self._h, int(q0), int(nq), int(t_base), d_idx_u_all, d_dist_u_all,
                                                int(u_row_stride), d_idx, d_dist, stream or None), "fdr_knn_expand_dev")
+
+
+class SparseIndex:
+    """The sparse index of a Context (Context.sparse_index): search row ranges of it, at any k, any number of times.
+    The index lives in the context, which holds one: once the context has built another (sparse_index, knn_sparse),
+    or after close(), search and info raise FedrannHipError."""
+
+    def __init__(self, ctx, n, metric, gen):
+        self._ctx, self.n, self.metric, self._gen = ctx, int(n), metric, gen
+        self._open = True
+
+    def _live(self, what):
+        if not self._open:
+            raise FedrannHipError("%s: the sparse index is closed" % what)
+        if not getattr(self._ctx, "_h", None):
+            raise FedrannHipError("%s: the context of the sparse index is closed" % what)
+        if self._ctx._sparse_gen != self._gen:
+            raise FedrannHipError("%s: the context has built another sparse index since this one" % what)
+
+    def search(self, k, lo=0, hi=None, out=None):
+        """Neighbours of the rows [lo, hi) (hi=None: n) among all n rows: (idx int32 [hi - lo, k], dist float32
+        [hi - lo, k]), row r the query lo + r, indices global: the rows lo .. hi - 1 of knn_sparse's result, bit for
+        bit.  out=(idx, dist): caller-owned C-contiguous result arrays of that shape."""
+        k, lo, hi = check_sparse_search(self.n, k, lo, hi)
+        nq = hi - lo
+        if out is None:
+            idx = np.empty((nq, k), dtype=np.int32)
+            dist = np.empty((nq, k), dtype=np.float32)
+        else:
+            idx, dist = out
+            if (idx.shape, dist.shape) != ((nq, k), (nq, k)) or idx.dtype != np.int32 or dist.dtype != np.float32 \
+                    or not (idx.flags.c_contiguous and dist.flags.c_contiguous):
+                raise ValueError("out must be C-contiguous (int32 [hi - lo, k], float32 [hi - lo, k])")
+        self._live("SparseIndex.search")
+        c = self._ctx
+        c._check(c._L.fdr_sparse_index_search(c._h, k, lo, hi, _ptr(idx), _ptr(dist)), "fdr_sparse_index_search")
+        return idx, dist
+
+    def info(self):
+        """dict of fdr_sparse_index_info: metric, n, postings (stored entries kept), zero_rows (zero rows; Jaccard:
+        empty rows), device_bytes (what the index holds on the device)."""
+        self._live("SparseIndex.info")
+        c = self._ctx
+        m, n, p, z = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        b = ctypes.c_size_t()
+        c._check(c._L.fdr_sparse_index_info(c._h, ctypes.byref(m), ctypes.byref(n), ctypes.byref(p), ctypes.byref(z),
+                                            ctypes.byref(b)), "fdr_sparse_index_info")
+        name = [s for s, v in SPARSE_METRICS.items() if v == m.value][0]
+        return {"metric": name, "n": int(n.value), "postings": int(p.value), "zero_rows": int(z.value),
+                "device_bytes": int(b.value)}
+
+    def close(self):
+        """Free the index's device memory (if it still is the context's index)."""
+        c = self._ctx
+        if self._open and getattr(c, "_h", None) and c._sparse_gen == self._gen:
+            c._check(c._L.fdr_sparse_index_free(c._h), "fdr_sparse_index_free")
+        self._open = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 _default_ctx = None

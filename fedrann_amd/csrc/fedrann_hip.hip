@@ -16,6 +16,7 @@
 #include <rocprim/device/device_reduce_by_key.hpp>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
@@ -532,7 +533,12 @@ struct fdr_ctx {
     DevBuf kc_a0, kc_a1, kc_c0, kc_c1, kc_mk, kc_mv, kc_rc;  // counting in blocks: accumulated table (ping / pong), merge buffers
     // sparse k-NN (knn_sparse.inc)
     DevBuf sp_ip, sp_ix, sp_val, sp_xhat, sp_keys, sp_keys2, sp_pos, sp_pos2, sp_efeat, sp_pval, sp_runptr, sp_heavy,
-        sp_cnt, sp_tmp, sp_asize;
+        sp_cnt, sp_tmp, sp_asize, sp_zero;
+    struct {  // the sparse index these hold (fdr_sparse_index_build; one per context)
+        bool valid = false;
+        int metric = 0;
+        long long n = 0, kept = 0, nzero = 0;  // rows, postings, zero (Jaccard: empty) rows
+    } spx;
     long long ks_nnz = 0, kc_n = 0;
     int64_t kc_block_chars = 0;  // fdr_set_kmer_count_block
     int kc_blocks = 0;           // blocks of the last fdr_kmer_count

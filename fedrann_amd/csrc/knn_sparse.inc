@@ -43,6 +43,14 @@
 //                          The hand-off at SP_LIMIT, the ranges, the merge, the distance-1 fill and S4 (the empty
 //                          rows take the zero rows' place) are shared.
 // Cost model: the same sum over features of df_f^2 pair updates, each reading a 4-byte posting entry (the row only).
+//
+// The index and its searches.  S1 (S1j), the sort and S2 are the BUILD (fdr_sparse_index_build): what they leave in
+// the context's sp_* buffers -- the rows (indptr, each stored entry's run id, xhat or the set sizes), the postings
+// (run offsets, rows, values) and the zero flags (sp_zero, the index's own: ctx->zero belongs to the dense calls) --
+// is the context's one sparse index, described by ctx->spx.  S4, S3 and S3r are a SEARCH (fdr_sparse_index_search) of
+// the query rows [q_lo, q_hi) against all n rows: S3's grid is the range, the heavy list and its counter are reset per
+// search, and row q - q_lo of the result buffers (sized by the range) is query q.  fdr_knn_sparse[_metric] is a build
+// and a search of [0, n) through the same two functions.
 // ------------------------------------------------------------------------------------------
 #define SP_CAP 1024    // hash-table slots per query (key int32 | fp32 accumulator or int32 count: 8 KiB of LDS)
 #define SP_LOG2CAP 10
@@ -55,11 +63,12 @@ static_assert(SP_LIST + SP_LIMIT + 64 <= SP_LIST + SP_CAP && SP_LIST + SP_W <= S
               "list + candidates of one range fit the sort buffer");
 static_assert((1 << SP_LOG2CAP) == SP_CAP, "SP_CAP is a power of two");
 
-// counters of one call (u64 each)
+// counters (u64 each): [0, 3) of a build, [3, 5) of a search
 #define SP_CNT_ERR 0      // or of SP_ERR_* bits
 #define SP_CNT_DROPPED 1  // stored entries without a posting (xhat = +-0; Jaccard: value = +-0)
 #define SP_CNT_ZERO 2     // zero rows (Jaccard: empty rows)
 #define SP_CNT_HEAVY 3    // queries handed to the range-split kernel
+#define SP_CNT_ZEROQ 4    // zero (empty) rows among the queries
 #define SP_ERR_RANGE 1u
 #define SP_ERR_ORDER 2u
 #define SP_ERR_VALUE 4u
@@ -209,6 +218,19 @@ __global__ __launch_bounds__(64) void sp_zero_row_kernel(long long n, const unsi
     }
 }
 
+// the zero (empty) rows among the queries [q_lo, q_hi), added to cnt[SP_CNT_ZEROQ]: sixteen rows per thread, one
+// atomic per wave that found any
+__global__ __launch_bounds__(256) void sp_count_zero_kernel(long long q_lo, long long q_hi,
+                                                            const unsigned char *__restrict__ zero,
+                                                            u64 *__restrict__ cnt) {
+    const long long base = q_lo + ((long long)blockIdx.x * 256 + threadIdx.x) * 16;
+    int c = 0;
+    for (int b = 0; b < 16; ++b)
+        if (base + b < q_hi) c += zero[base + b] != 0;
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
+    if ((threadIdx.x & 63) == 0 && c > 0) atomicAdd(&cnt[SP_CNT_ZEROQ], (u64)c);
+}
+
 // the slot of target row t (inserted if new); the caller keeps the distinct keys below SP_CAP, so a free slot exists
 __device__ __forceinline__ int sp_insert(int *tab, int t, bool &isnew) {
     unsigned s = ((unsigned)t * 0x9E3779B1u) >> (32 - SP_LOG2CAP);
@@ -238,9 +260,10 @@ __device__ __forceinline__ long long sp_lower_bound(const int *__restrict__ a, l
 }
 
 // S3 / S3r (METRIC = FDR_METRIC_COSINE) and S3j / S3rj (FDR_METRIC_JACCARD: xhat = pval = null, asize = the set
-// sizes): one wave (one workgroup) per query
+// sizes): one wave (one workgroup) per query; the queries are the rows q0 + blockIdx.x (S3) or the heavy list's (S3r),
+// and query q writes row q - q0 of idx_out / dist_out
 template <bool RANGE, int METRIC>
-__global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, const long long *__restrict__ indptr,
+__global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q0, const long long *__restrict__ indptr,
                                                         const int *__restrict__ efeat, const float *__restrict__ xhat,
                                                         const long long *__restrict__ runptr,
                                                         const int *__restrict__ prow, const float *__restrict__ pval,
@@ -253,9 +276,9 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, const long 
     int *tab = reinterpret_cast<int *>(buf + SP_LIST);  // slot s: tab[2 s] = target row (SP_EMPTY), tab[2 s + 1] = acc
     constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;  // (... or the int32 count of shared features)
     const int lane = threadIdx.x;
-    const long long q = RANGE ? (long long)heavy[blockIdx.x] : (long long)blockIdx.x;
-    int *out_i = idx_out + q * k;
-    float *out_d = dist_out + q * k;
+    const long long q = RANGE ? (long long)heavy[blockIdx.x] : q0 + (long long)blockIdx.x;
+    int *out_i = idx_out + (q - q0) * k;
+    float *out_d = dist_out + (q - q0) * k;
     if (!RANGE && zero[q]) {
         for (int i = lane; i < k; i += 64) {
             out_i[i] = zidx[i];
@@ -397,56 +420,64 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, const long 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-// S3 over every query, then S3r over the queries it handed on (h_heavy of them)
+// every device buffer of the sparse path but the shared result buffers (ctx->idx, ctx->dist)
+static std::array<DevBuf *, 16> sp_buffers(fdr_ctx *ctx) {
+    return {&ctx->sp_ip,  &ctx->sp_ix,    &ctx->sp_val,  &ctx->sp_xhat,   &ctx->sp_keys,  &ctx->sp_keys2,
+            &ctx->sp_pos, &ctx->sp_pos2,  &ctx->sp_efeat, &ctx->sp_pval,  &ctx->sp_runptr, &ctx->sp_heavy,
+            &ctx->sp_cnt, &ctx->sp_tmp,   &ctx->sp_asize, &ctx->sp_zero};
+}
+
+// S3 over the queries [q_lo, q_lo + nq), then S3r over the queries it handed on; h = their number, and the zero
+// (empty) rows among the queries
 template <int METRIC>
-static int sp_search(fdr_ctx *ctx, int64_t n, int32_t k, const int *zidx, const float *zdist, u64 *cnt,
-                     u64 &h_heavy) {
+static int sp_search(fdr_ctx *ctx, int64_t n, int32_t k, int64_t q_lo, int64_t nq, const int *zidx, const float *zdist,
+                     u64 *cnt, u64 (&h)[2]) {
     const hipStream_t st = ctx->stream;
     constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;
+    static_assert(SP_CNT_ZEROQ == SP_CNT_HEAVY + 1, "one read-back for both");
     const float *xhat = JAC ? nullptr : (const float *)ctx->sp_xhat.p;
     const float *pval = JAC ? nullptr : (const float *)ctx->sp_pval.p;
     const int *asize = JAC ? (const int *)ctx->sp_asize.p : nullptr;
-    hipLaunchKernelGGL((knn_sparse_kernel<false, METRIC>), dim3((unsigned)n), dim3(64), 0, st, (long long)n,
-                       (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_efeat.p, xhat,
+    hipLaunchKernelGGL((knn_sparse_kernel<false, METRIC>), dim3((unsigned)nq), dim3(64), 0, st, (long long)n,
+                       (long long)q_lo, (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_efeat.p, xhat,
                        (const long long *)ctx->sp_runptr.p, (const int *)ctx->sp_pos.p, pval, asize,
-                       (const unsigned char *)ctx->zero.p, (int)k, zidx, zdist, (int *)ctx->sp_heavy.p, cnt,
+                       (const unsigned char *)ctx->sp_zero.p, (int)k, zidx, zdist, (int *)ctx->sp_heavy.p, cnt,
                        (int *)ctx->idx.p, (float *)ctx->dist.p);
     HIP_TRY(hipGetLastError());
-    h_heavy = 0;
-    HIP_TRY(hipMemcpyAsync(&h_heavy, cnt + SP_CNT_HEAVY, 8, hipMemcpyDeviceToHost, st));
+    h[0] = h[1] = 0;
+    HIP_TRY(hipMemcpyAsync(h, cnt + SP_CNT_HEAVY, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (h_heavy > 0) {
-        hipLaunchKernelGGL((knn_sparse_kernel<true, METRIC>), dim3((unsigned)h_heavy), dim3(64), 0, st, (long long)n,
-                           (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_efeat.p, xhat,
+    if (h[0] > 0) {
+        hipLaunchKernelGGL((knn_sparse_kernel<true, METRIC>), dim3((unsigned)h[0]), dim3(64), 0, st, (long long)n,
+                           (long long)q_lo, (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_efeat.p, xhat,
                            (const long long *)ctx->sp_runptr.p, (const int *)ctx->sp_pos.p, pval, asize,
-                           (const unsigned char *)ctx->zero.p, (int)k, zidx, zdist, (int *)ctx->sp_heavy.p, cnt,
+                           (const unsigned char *)ctx->sp_zero.p, (int)k, zidx, zdist, (int *)ctx->sp_heavy.p, cnt,
                            (int *)ctx->idx.p, (float *)ctx->dist.p);
         HIP_TRY(hipGetLastError());
     }
     return FDR_OK;
 }
 
-static int sp_knn(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
-                  const int32_t *indices, const float *values, int32_t k, int32_t *idx_out, float *dist_out) {
-    int rc = use_device(ctx);
-    if (rc) return rc;
-    knn_call_begin(ctx);
+// The build: the argument checks, the upload, S1 (S1j), the sort, the run flags and scan, S2.  ctx->spx describes the
+// index once everything is enqueued; a refused or failed build leaves none.  `who` names the entry point in messages.
+static int sp_build(fdr_ctx *ctx, const char *who, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
+                    const int32_t *indices, const float *values) {
+    int rc;
+    ctx->spx = {};
     const bool jac = metric == FDR_METRIC_JACCARD;
     if (!jac && metric != FDR_METRIC_COSINE)
-        return fail(FDR_E_ARG, "knn_sparse: unknown metric %d (FDR_METRIC_COSINE, FDR_METRIC_JACCARD)", metric);
-    if (!indptr || !idx_out || !dist_out) return fail(FDR_E_ARG, "knn_sparse: null pointer");
-    if (k < 1 || k > FDR_MAX_K) return fail(FDR_E_ARG, "knn_sparse: k=%d unsupported (1..%d)", k, FDR_MAX_K);
-    if (n < k) return fail(FDR_E_ARG, "knn_sparse: need n (%lld) >= k (%d)", (long long)n, k);
-    if (n > INT32_MAX) return fail(FDR_E_ARG, "knn_sparse: n (%lld) must be below 2^31 rows", (long long)n);
+        return fail(FDR_E_ARG, "%s: unknown metric %d (FDR_METRIC_COSINE, FDR_METRIC_JACCARD)", who, metric);
+    if (!indptr) return fail(FDR_E_ARG, "%s: null pointer", who);
+    if (n < 1) return fail(FDR_E_ARG, "%s: need at least one row, got n = %lld", who, (long long)n);
+    if (n > INT32_MAX) return fail(FDR_E_ARG, "%s: n (%lld) must be below 2^31 rows", who, (long long)n);
     if (n_features < 1 || n_features > INT32_MAX)
-        return fail(FDR_E_ARG, "knn_sparse: n_features (%lld) must be in [1, 2^31)", (long long)n_features);
-    if (indptr[0] != 0) return fail(FDR_E_ARG, "knn_sparse: indptr[0] must be 0");
+        return fail(FDR_E_ARG, "%s: n_features (%lld) must be in [1, 2^31)", who, (long long)n_features);
+    if (indptr[0] != 0) return fail(FDR_E_ARG, "%s: indptr[0] must be 0", who);
     for (int64_t i = 0; i < n; ++i)
-        if (indptr[i + 1] < indptr[i]) return fail(FDR_E_ARG, "knn_sparse: indptr not monotone at row %lld", (long long)i);
+        if (indptr[i + 1] < indptr[i]) return fail(FDR_E_ARG, "%s: indptr not monotone at row %lld", who, (long long)i);
     const int64_t nnz = indptr[n];
-    if (nnz > INT32_MAX)
-        return fail(FDR_E_ARG, "knn_sparse: %lld stored entries (at most 2^31 - 1)", (long long)nnz);
-    if (nnz > 0 && !indices) return fail(FDR_E_ARG, "knn_sparse: indices is null");
+    if (nnz > INT32_MAX) return fail(FDR_E_ARG, "%s: %lld stored entries (at most 2^31 - 1)", who, (long long)nnz);
+    if (nnz > 0 && !indices) return fail(FDR_E_ARG, "%s: indices is null", who);
     const hipStream_t st = ctx->stream;
     const size_t m1 = (size_t)std::max<int64_t>(nnz, 1);
     if ((rc = ctx->sp_ip.reserve((size_t)(n + 1) * 8))) return rc;
@@ -463,12 +494,8 @@ static int sp_knn(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, c
     if ((rc = ctx->sp_runptr.reserve((m1 + 1) * 8))) return rc;
     if ((rc = ctx->sp_heavy.reserve((size_t)n * 4))) return rc;
     if ((rc = ctx->sp_cnt.reserve(64 + (size_t)FDR_MAX_K * 8))) return rc;
-    if ((rc = ctx->zero.reserve((size_t)n))) return rc;
-    if ((rc = ctx->idx.reserve((size_t)n * k * 4))) return rc;
-    if ((rc = ctx->dist.reserve((size_t)n * k * 4))) return rc;
+    if ((rc = ctx->sp_zero.reserve((size_t)n))) return rc;
     u64 *cnt = (u64 *)ctx->sp_cnt.p;
-    int *zidx = (int *)((char *)ctx->sp_cnt.p + 64);
-    float *zdist = (float *)((char *)ctx->sp_cnt.p + 64 + FDR_MAX_K * 4);
     HIP_TRY(hipMemcpyAsync(ctx->sp_ip.p, indptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     if (nnz > 0) {
         HIP_TRY(hipMemcpyAsync(ctx->sp_ix.p, indices, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
@@ -480,25 +507,24 @@ static int sp_knn(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, c
                            (long long)n_features, (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_ix.p,
                            values ? (const float *)ctx->sp_val.p : nullptr, (int *)ctx->sp_asize.p,
                            (u64 *)ctx->sp_keys.p, (unsigned *)ctx->sp_pos.p, (int *)ctx->sp_efeat.p,
-                           (unsigned char *)ctx->zero.p, cnt);
+                           (unsigned char *)ctx->sp_zero.p, cnt);
     } else {
         hipLaunchKernelGGL(sp_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n,
                            (long long)n_features, (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_ix.p,
                            values ? (const float *)ctx->sp_val.p : nullptr, (float *)ctx->sp_xhat.p,
                            (u64 *)ctx->sp_keys.p, (unsigned *)ctx->sp_pos.p, (int *)ctx->sp_efeat.p,
-                           (unsigned char *)ctx->zero.p, cnt);
+                           (unsigned char *)ctx->sp_zero.p, cnt);
     }
     HIP_TRY(hipGetLastError());
-    u64 h_cnt[4];
+    u64 h_cnt[3];
     HIP_TRY(hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (h_cnt[SP_CNT_ERR] & SP_ERR_RANGE)
-        return fail(FDR_E_ARG, "knn_sparse: a feature index is outside [0, %lld)", (long long)n_features);
+        return fail(FDR_E_ARG, "%s: a feature index is outside [0, %lld)", who, (long long)n_features);
     if (h_cnt[SP_CNT_ERR] & SP_ERR_ORDER)
-        return fail(FDR_E_ARG, "knn_sparse: feature indices must be strictly ascending inside a row");
-    if (h_cnt[SP_CNT_ERR] & SP_ERR_VALUE) return fail(FDR_E_ARG, "knn_sparse: non-finite value");
+        return fail(FDR_E_ARG, "%s: feature indices must be strictly ascending inside a row", who);
+    if (h_cnt[SP_CNT_ERR] & SP_ERR_VALUE) return fail(FDR_E_ARG, "%s: non-finite value", who);
     const long long kept = (long long)nnz - (long long)h_cnt[SP_CNT_DROPPED];
-    const long long nzero = (long long)h_cnt[SP_CNT_ZERO];
     if (kept > 0) {
         int end_bit = 32;
         while (end_bit < 64 && ((u64)n_features >> (end_bit - 32)) != 0) ++end_bit;  // (the sentinel F << 32 too)
@@ -527,26 +553,67 @@ static int sp_knn(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, c
                            (long long *)ctx->sp_runptr.p);
         HIP_TRY(hipGetLastError());
     }
-    if (nzero > 0) {
-        hipLaunchKernelGGL(sp_zero_row_kernel, dim3(1), dim3(64), 0, st, (long long)n, (const unsigned char *)ctx->zero.p,
-                           (int)k, zidx, zdist);
-        HIP_TRY(hipGetLastError());
+    ctx->spx.valid = true;
+    ctx->spx.metric = metric;
+    ctx->spx.n = n;
+    ctx->spx.kept = kept;
+    ctx->spx.nzero = (long long)h_cnt[SP_CNT_ZERO];
+    return FDR_OK;
+}
+
+// A search of the context's index (the caller has checked that there is one, and k and the range): S4 when the index
+// has a zero row, S3 / S3r over the queries [q_lo, q_hi), the results and the trace
+static int sp_search_range(fdr_ctx *ctx, int32_t k, int64_t q_lo, int64_t q_hi, int32_t *idx_out, float *dist_out) {
+    int rc;
+    const hipStream_t st = ctx->stream;
+    const int64_t n = ctx->spx.n, nq = q_hi - q_lo;
+    u64 h[2] = {0, 0};  // queries that took S3r; zero (empty) rows among the queries
+    if (nq > 0) {
+        if ((rc = ctx->idx.reserve((size_t)nq * k * 4))) return rc;
+        if ((rc = ctx->dist.reserve((size_t)nq * k * 4))) return rc;
+        u64 *cnt = (u64 *)ctx->sp_cnt.p;
+        int *zidx = (int *)((char *)ctx->sp_cnt.p + 64);
+        float *zdist = (float *)((char *)ctx->sp_cnt.p + 64 + FDR_MAX_K * 4);
+        HIP_TRY(hipMemsetAsync(cnt + SP_CNT_HEAVY, 0, 16, st));  // (the heavy list's counter and the zero queries')
+        if (ctx->spx.nzero > 0) {  // (S4 depends on k: per search)
+            hipLaunchKernelGGL(sp_zero_row_kernel, dim3(1), dim3(64), 0, st, (long long)n,
+                               (const unsigned char *)ctx->sp_zero.p, (int)k, zidx, zdist);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(sp_count_zero_kernel, dim3((unsigned)((nq + 4095) / 4096)), dim3(256), 0, st,
+                               (long long)q_lo, (long long)q_hi, (const unsigned char *)ctx->sp_zero.p, cnt);
+            HIP_TRY(hipGetLastError());
+        }
+        rc = ctx->spx.metric == FDR_METRIC_JACCARD ? sp_search<FDR_METRIC_JACCARD>(ctx, n, k, q_lo, nq, zidx, zdist, cnt, h)
+                                                   : sp_search<FDR_METRIC_COSINE>(ctx, n, k, q_lo, nq, zidx, zdist, cnt, h);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(idx_out, ctx->idx.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(dist_out, ctx->dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
-    u64 h_heavy = 0;
-    rc = jac ? sp_search<FDR_METRIC_JACCARD>(ctx, n, k, zidx, zdist, cnt, h_heavy)
-             : sp_search<FDR_METRIC_COSINE>(ctx, n, k, zidx, zdist, cnt, h_heavy);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(idx_out, ctx->idx.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(dist_out, ctx->dist.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
     fdr_knn_trace &t = ctx->last.trace;
     t.kind = FDR_TRACE_SPARSE;
     t.k = k;
-    t.queries = t.targets = n;
-    t.zero_queries = (int32_t)std::min<long long>(nzero, INT32_MAX);
-    t.range_queries = (int32_t)h_heavy;
-    t.range_chunks = h_heavy ? (int32_t)((n + SP_W - 1) / SP_W) : 0;
+    t.queries = nq;
+    t.targets = n;
+    t.zero_queries = (int32_t)std::min<u64>(h[1], INT32_MAX);
+    t.range_queries = (int32_t)h[0];
+    t.range_chunks = h[0] ? (int32_t)((n + SP_W - 1) / SP_W) : 0;
     return FDR_OK;
+}
+
+static int sp_knn(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
+                  const int32_t *indices, const float *values, int32_t k, int32_t *idx_out, float *dist_out) {
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    knn_call_begin(ctx);
+    ctx->spx = {};  // (the call replaces the context's index, also where it is refused before the build)
+    if (metric != FDR_METRIC_JACCARD && metric != FDR_METRIC_COSINE)
+        return fail(FDR_E_ARG, "knn_sparse: unknown metric %d (FDR_METRIC_COSINE, FDR_METRIC_JACCARD)", metric);
+    if (!indptr || !idx_out || !dist_out) return fail(FDR_E_ARG, "knn_sparse: null pointer");
+    if (k < 1 || k > FDR_MAX_K) return fail(FDR_E_ARG, "knn_sparse: k=%d unsupported (1..%d)", k, FDR_MAX_K);
+    if (n < k) return fail(FDR_E_ARG, "knn_sparse: need n (%lld) >= k (%d)", (long long)n, k);
+    if ((rc = sp_build(ctx, "knn_sparse", metric, n, n_features, indptr, indices, values))) return rc;
+    return sp_search_range(ctx, k, 0, n, idx_out, dist_out);
 }
 
 FDR_EXPORT int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const int64_t *indptr,
@@ -559,4 +626,55 @@ FDR_EXPORT int fdr_knn_sparse_metric(fdr_ctx *ctx, int32_t metric, int64_t n, in
                                      const int64_t *indptr, const int32_t *indices, const float *values, int32_t k,
                                      int32_t *idx_out, float *dist_out) {
     return sp_knn(ctx, metric, n, n_features, indptr, indices, values, k, idx_out, dist_out);
+}
+
+FDR_EXPORT int fdr_sparse_index_build(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features,
+                                      const int64_t *indptr, const int32_t *indices, const float *values) {
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    if ((rc = sp_build(ctx, "sparse_index_build", metric, n, n_features, indptr, indices, values))) return rc;
+    ctx->spx.valid = false;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // (a failure of the sort or of S2 belongs to this call: no index)
+    ctx->spx.valid = true;
+    return FDR_OK;
+}
+
+FDR_EXPORT int fdr_sparse_index_search(fdr_ctx *ctx, int32_t k, int64_t q_lo, int64_t q_hi, int32_t *idx_out,
+                                       float *dist_out) {
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    knn_call_begin(ctx);
+    if (!ctx->spx.valid) return fail(FDR_E_STATE, "sparse_index_search: the context holds no sparse index");
+    const int64_t n = ctx->spx.n;
+    if (k < 1 || k > FDR_MAX_K || k > n)
+        return fail(FDR_E_ARG, "sparse_index_search: k=%d unsupported (1..min(%d, n = %lld))", k, FDR_MAX_K, (long long)n);
+    if (q_lo < 0 || q_hi < q_lo || q_hi > n)
+        return fail(FDR_E_ARG, "sparse_index_search: rows [%lld, %lld) are no range of the %lld rows", (long long)q_lo,
+                    (long long)q_hi, (long long)n);
+    if (q_hi > q_lo && (!idx_out || !dist_out)) return fail(FDR_E_ARG, "sparse_index_search: null pointer");
+    return sp_search_range(ctx, k, q_lo, q_hi, idx_out, dist_out);
+}
+
+FDR_EXPORT int fdr_sparse_index_info(fdr_ctx *ctx, int32_t *metric, int64_t *n, int64_t *postings, int64_t *zero_rows,
+                                     size_t *device_bytes) {
+    if (!ctx) return fail(FDR_E_ARG, "null context");
+    if (!ctx->spx.valid) return fail(FDR_E_STATE, "sparse_index_info: the context holds no sparse index");
+    if (metric) *metric = ctx->spx.metric;
+    if (n) *n = ctx->spx.n;
+    if (postings) *postings = ctx->spx.kept;
+    if (zero_rows) *zero_rows = ctx->spx.nzero;
+    if (device_bytes) {
+        *device_bytes = 0;
+        for (const DevBuf *b : sp_buffers(ctx)) *device_bytes += b->cap;
+    }
+    return FDR_OK;
+}
+
+FDR_EXPORT int fdr_sparse_index_free(fdr_ctx *ctx) {
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->spx = {};
+    for (DevBuf *b : sp_buffers(ctx)) b->release();
+    return FDR_OK;
 }

@@ -155,6 +155,42 @@ class ShardedPipeline:
         return idx, dst, E
 
 
+def sparse_rank_blocks(n_rows, rank, world, block_rows=None):
+    """(lo, hi, blocks): the rows [lo, hi) of `rank` in shard_rows(n_rows, world), and the query blocks
+    sparse_knn_rank searches them in: consecutive ranges of at most block_rows rows (None: one block).  The blocks
+    of all ranks tile [0, n_rows).  Needs no GPU."""
+    rank, world = int(rank), int(world)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("need 0 <= rank < world, got rank %d of %d" % (rank, world))
+    if block_rows is not None and int(block_rows) < 1:
+        raise ValueError("block_rows must be at least 1")
+    lo, hi = shard_rows(int(n_rows), world)[1][rank]
+    step = max(hi - lo, 1) if block_rows is None else int(block_rows)
+    return lo, hi, [(a, min(hi, a + step)) for a in range(lo, hi, step)]
+
+
+def sparse_knn_rank(ctx, indptr, indices, values, n_features, k, rank, world, metric="cosine", block_rows=None):
+    """This rank's share of Context.knn_sparse on the whole CSR: (lo, hi, idx int32 [hi - lo, k], dist float32
+    [hi - lo, k]) for the rows [lo, hi) of `rank` in shard_rows(n, world), the dense pipeline's split; neighbour
+    indices are global rows.  The rank builds the index of the WHOLE CSR (Context.sparse_index) and searches its own
+    rows in query blocks of at most block_rows rows (None: one block), which bounds the device's result buffers.
+
+    No collective and no process group: a search is one independent wave per query, so the ranks' results,
+    concatenated in rank order, are the one-GPU answer bit for bit.  The price is a replicated index: EVERY rank
+    uploads the full CSR and holds about 52 (cosine) or 44 (Jaccard) device bytes per stored entry, plus the
+    sort's temporary storage of about 12 more (64 measured at 1 M reads, cosine), and pays the O(nnz) build; only
+    the search, sum over the features of df^2, is divided by the ranks (by row count, not by cost).  The index is
+    freed before the call returns."""
+    with ctx.sparse_index(indptr, indices, values, n_features, metric=metric) as index:  # (checks the CSR first)
+        lo, hi, blocks = sparse_rank_blocks(index.n, rank, world, block_rows)
+        k = _lib.check_sparse_search(index.n, k)[0]
+        idx = np.empty((hi - lo, k), dtype=np.int32)
+        dist = np.empty((hi - lo, k), dtype=np.float32)
+        for a, b in blocks:
+            index.search(k, a, b, out=(idx[a - lo:b - lo], dist[a - lo:b - lo]))
+    return lo, hi, idx, dist
+
+
 def local_csr(indptr, indices, lo, hi):
     """Rows [lo, hi) of a host CSR, indptr rebased to 0 (numpy)."""
     ip = np.ascontiguousarray(indptr[lo:hi + 1] - indptr[lo], dtype=np.int64)

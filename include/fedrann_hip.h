@@ -145,6 +145,41 @@ int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const int64_t *i
 int fdr_knn_sparse_metric(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
                           const int32_t *indices, const float *values, int32_t k, int32_t *idx_out, float *dist_out);
 
+/* ---- the sparse search in two steps: build the index once, search row ranges of it  (a host that searches in query
+ *      blocks, at several k, or one rank's rows of a row-sharded run: fedrann_amd.distributed.sparse_knn_rank) -------
+ * fdr_sparse_index_build does everything of fdr_knn_sparse_metric that does not depend on k or on the queries: the
+ * argument checks, the upload of the CSR, the rows' norms (set sizes) and zero flags, the sorted postings.  The index
+ * stays in the context, which holds ONE: a build replaces it, and so does every fdr_knn_sparse / fdr_knn_sparse_metric,
+ * which is a build followed by a search of [0, n) through the same code (after it, its index is the context's; where
+ * it is refused or fails, at any point, the context holds none).  No
+ * other call on the context touches the index (fdr_knn, fdr_embed_knn, the _dev calls, the k-mer calls).  Arguments,
+ * limits and error codes are those of fdr_knn_sparse_metric, except that there is no k: 1 <= n < 2^31.  A build that
+ * is refused (also on the device: an index out of range or out of order, a non-finite value; FDR_E_ARG) or that fails
+ * leaves NO index, not the earlier one.  Host pointers; the call synchronises. */
+int fdr_sparse_index_build(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
+                           const int32_t *indices, const float *values);
+/* The k nearest rows, among all n rows of the index, of the query rows [q_lo, q_hi): idx_out int32 [q_hi - q_lo, k],
+ * dist_out float32 [q_hi - q_lo, k] (host pointers; the call synchronises), row r the query q_lo + r, indices global
+ * row numbers: the rows q_lo .. q_hi - 1 of what fdr_knn_sparse_metric gives on the whole CSR, bit for bit, under every
+ * rule stated there ((distance bits, index) order, self a candidate, distance-1 rows in index order over all rows, the
+ * closed form of a zero or empty query over all rows).  1 <= k <= min(FDR_MAX_K, n) and 0 <= q_lo <= q_hi <= n
+ * (FDR_E_ARG); a range shorter than k is fine, q_lo == q_hi is FDR_OK and writes nothing; FDR_E_STATE without an
+ * index.  Any number of searches, at any k and over any ranges, follow one build; the device's result buffers are
+ * sized by q_hi - q_lo.  fdr_last_knn_trace: FDR_TRACE_SPARSE with queries = q_hi - q_lo, targets = n, and
+ * zero_queries / range_queries counting the queries of this call. */
+int fdr_sparse_index_search(fdr_ctx *ctx, int32_t k, int64_t q_lo, int64_t q_hi, int32_t *idx_out, float *dist_out);
+/* The context's index (FDR_E_STATE without one); every out pointer may be NULL.  postings: the stored entries that
+ * got a posting (cosine: scaled value not +-0; Jaccard: value not +-0).  zero_rows: zero rows (Jaccard: empty rows).
+ * device_bytes: the device memory the sparse path holds for the context, the build's scratch (unsorted keys, sort
+ * buffers) included, which is kept so that the next build allocates nothing: about 52 (cosine) or 44 (Jaccard) bytes
+ * per stored entry in the library's own buffers, and the radix sort's temporary storage on top, about 12 more (64 per
+ * stored entry measured at 1 M synthetic reads, cosine).  Buffers only grow: after a larger index the figure is the
+ * larger one's. */
+int fdr_sparse_index_info(fdr_ctx *ctx, int32_t *metric, int64_t *n, int64_t *postings, int64_t *zero_rows,
+                          size_t *device_bytes);
+/* Drops the index and frees that memory (fdr_destroy does too).  Without an index: FDR_OK. */
+int fdr_sparse_index_free(fdr_ctx *ctx);
+
 /* ---- device-resident API (multi-GPU host, bench.py) ----------------------------------------
  * All pointers are device pointers; work is enqueued on `stream` (a hipStream_t). */
 int fdr_embed_dev(fdr_ctx *ctx, int64_t n_rows, const int64_t *d_indptr, const int32_t *d_indices,
@@ -244,14 +279,15 @@ int fdr_last_unique(fdr_ctx *ctx, int *unique_targets, int *unique_queries);
 int fdr_last_prefilter_launches(fdr_ctx *ctx, int *launches, int *queues);
 /* Diagnostics (test support; nothing in the product reads it): which kernels the most recent k-NN call ran.  With
  * the duplicate-row layer active it describes the inner search of the unique rows.  Every k-NN entry point
- * (fdr_knn_dev, fdr_knn, fdr_embed_knn, fdr_knn_classes_dev, fdr_knn_unique_dev, fdr_knn_expand_dev, fdr_knn_sparse)
- * clears it, and
+ * (fdr_knn_dev, fdr_knn, fdr_embed_knn, fdr_knn_classes_dev, fdr_knn_unique_dev, fdr_knn_expand_dev, fdr_knn_sparse,
+ * fdr_knn_sparse_metric, fdr_sparse_index_search) clears it, and
  * the per-query path codes, before it checks its arguments. */
 #define FDR_TRACE_NONE 0       /* no k-NN search ran (a cleared trace, or a call that failed or found nothing to do) */
 #define FDR_TRACE_EXACT 1      /* exact mode: the fp32 kernel for every query */
 #define FDR_TRACE_PREFILTER 2  /* fp16 candidate pass + certificate (+ range pass, + exact fallback) */
 #define FDR_TRACE_GENERIC 3    /* d > 1024, or k > 64 / d > 512 below 8192 targets: the generic kernel */
-#define FDR_TRACE_SPARSE 4     /* fdr_knn_sparse: zero_queries = zero rows; range_queries = queries whose targets
+#define FDR_TRACE_SPARSE 4     /* fdr_knn_sparse, fdr_sparse_index_search: zero_queries = zero rows among the queries;
+                                  range_queries = queries whose targets
                                   overflowed the table and were searched over row ranges, range_chunks = the ranges
                                   of each */
 #define FDR_FALLBACK_NONE 0
