@@ -450,7 +450,51 @@ struct DevBuf {
     ~DevBuf() { release(); }  // (fdr_destroy has made the context's device current)
 };
 
-// its pinned twin on the host
+// A DevBuf of elements of T (the scratch of the k-mer stages and of the sparse index): reserve() counts elements and
+// ptr() is the one statement of the element type.  Non-copyable through its member.
+template <class T>
+struct DevArray {
+    DevBuf buf;
+    int reserve(size_t count) { return buf.reserve(count * sizeof(T)); }
+    T *ptr() const { return static_cast<T *>(buf.p); }
+    void release() { buf.release(); }
+    size_t bytes() const { return buf.cap; }  // the capacity
+};
+template <class... A>
+static void release_all(A &...arrays) {
+    (arrays.release(), ...);
+}
+
+// A rocprim algorithm on temporary storage that the context owns.  `call(tmp, bytes)` makes the rocprim call with these
+// two as its first arguments, so the algorithm's other arguments are written once: rocprim_reserve asks it for its
+// size (tmp = null) and grows the storage, rocprim_run does the same and then runs it.  At least one byte is held, so
+// the run never passes the null pointer that rocprim takes for another size query.  A sequence of several algorithms
+// calls rocprim_reserve with all of them first: then no run of the sequence regrows the storage (a regrow would be
+// safe, hipFree waits for the device, but it stalls the queue).
+template <class... F>
+static int rocprim_reserve(DevArray<char> &tmp, const F &...calls) {
+    size_t need = 1;
+    hipError_t e = hipSuccess;
+    auto ask = [&](const auto &call) {
+        size_t bytes = 0;
+        if (e == hipSuccess) e = call(nullptr, bytes);
+        need = std::max(need, bytes);
+    };
+    (ask(calls), ...);
+    if (e != hipSuccess) return fail(FDR_E_HIP, "rocprim temporary storage size query failed: %s", hipGetErrorString(e));
+    return tmp.reserve(need);
+}
+template <class F>
+static int rocprim_run(DevArray<char> &tmp, const char *what, const F &call) {
+    if (int rc = rocprim_reserve(tmp, call)) return rc;
+    size_t bytes = tmp.bytes();
+    const hipError_t e = call(tmp.ptr(), bytes);
+    if (e != hipSuccess)  // (HIP_TRY's message)
+        return fail(e == hipErrorOutOfMemory ? FDR_E_NOMEM : FDR_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    return FDR_OK;
+}
+
+// DevBuf's pinned twin on the host
 struct PinnedBuf {
     void *p = nullptr;
     size_t cap = 0;
@@ -508,6 +552,120 @@ struct KnnArgs {
     hipStream_t st;
 };
 
+// The three stages beside the dense path own their device scratch and the state that describes it: release() frees
+// the one and resets the other in the same place, so neither outlives the other.
+
+// fdr_kmer_search / fdr_kmer_search_indices (kmer_search.inc)
+struct KmerSearchScratch {
+    DevArray<unsigned char> seq;           // the reads' characters, concatenated (+ 64 bytes of padding)
+    DevArray<long long> off;               // [n_reads + 1] their offsets
+    DevArray<u64> lib_codes;               // the library's codes
+    DevArray<u64> keys;                    // the table: code + 1 (0: a free slot) ...
+    DevArray<unsigned> vals;               // ... and its library index
+    DevArray<u64> bloom;                   // the filter's words
+    DevArray<unsigned long long> counter;  // hits found (counts past the hit buffer's capacity)
+    DevArray<u64> pairs, sorted;           // the hits (read << 32 | index) as found; sorted
+    DevArray<int> flag, scan;              // 1 where a sorted hit differs from its predecessor; the inclusive scan
+    DevArray<int> indices, rows;           // the unique hits' index and read parts
+    DevArray<long long> indptr;            // [n_reads + 1] the rows' first unique hits
+    DevArray<char> tmp;                    // rocprim's temporary storage
+    long long nnz = 0;                     // unique hits of the last search, until fdr_kmer_search_indices fetches them
+    void release() {
+        release_all(seq, off, lib_codes, keys, vals, bloom, counter, pairs, sorted, flag, scan, indices, rows, indptr, tmp);
+        nnz = 0;
+    }
+};
+
+// fdr_kmer_count_* (kmer_search.inc): counting in blocks, the export, the W-way merge, the fetch
+struct KmerCountScratch {
+    // a block of reads (kc_block_runs)
+    DevArray<unsigned char> seq;  // the block's characters (+ 64 bytes of padding)
+    DevArray<long long> off;      // its reads' offsets
+    DevArray<u64> codes;          // one canonical code per position; once they are sorted, the block's run codes
+    DevArray<u64> sorted;         // the block's sorted codes; after the last block, the KEPT codes that the fetch copies
+    DevArray<unsigned> run_len;   // the runs' lengths ...
+    DevArray<unsigned> n_runs;    // ... and their number
+    DevArray<u64> run_counts;     // the lengths as 64-bit counts
+    // the table accumulated over the blocks: [acc] is current and holds na entries, the other one takes the next merge
+    // (fdr_kmer_count_merge, which replaces the table anyway, puts the host's runs into [0])
+    DevArray<u64> acc_codes[2], acc_counts[2];
+    DevArray<u64> merged_codes, merged_counts;  // table and block merged, equal codes not yet summed; in the W-way merge
+                                                // the owners' codes and totals at their merged places
+    DevArray<unsigned long long> n_table;       // entries after the sum
+    // the threshold (fdr_kmer_count_finish, km_merge)
+    DevArray<int> keep, keep_scan;  // 1 per entry that stays; the inclusive scan
+    DevArray<u64> kept_counts;      // the kept entries' counts (their codes: `sorted`)
+    // the small tables of the W-way merge and of the export
+    DevArray<long long> run_off, samp_pre;  // [n_runs + 1] each: the runs' offsets, the prefix of their sample counts
+    DevArray<u64> samples, bounds;          // every KM_STRIDE-th code of every run; sorted: the tile boundaries
+    DevArray<long long> slices;             // [tiles + 1, n_runs] a tile's first element in each run
+    DevArray<long long> part_off;           // [n_parts + 1] fdr_kmer_count_export_dev
+    DevArray<char> tmp;                     // rocprim's temporary storage
+    int k = 0;         // incremental counting: k (0: not begun, finished, or released)
+    int acc = 0;       // ... which of the two tables is current
+    long long na = 0;  // ... its entries
+    long long n = 0;   // kept entries of the last finish / merge, until fdr_kmer_count_fetch fetches them
+    // These two survive release(): the setting of fdr_set_kmer_count_block, and the blocks of the last count, which
+    // fdr_last_kmer_count_blocks reports after the fetch as well (fdr_kmer_count_begin resets it).
+    int64_t block_chars = 0;
+    int blocks = 0;
+    void release() {
+        release_all(seq, off, codes, sorted, run_len, n_runs, run_counts, acc_codes[0], acc_codes[1], acc_counts[0],
+                    acc_counts[1], merged_codes, merged_counts, n_table, keep, keep_scan, kept_counts, run_off, samp_pre,
+                    samples, bounds, slices, part_off, tmp);
+        k = acc = 0;
+        na = n = 0;
+    }
+};
+
+// The context's one sparse index (knn_sparse.inc): what fdr_sparse_index_build leaves for the searches, and the
+// build's scratch, which is kept with it
+struct SparseIndex {
+    DevArray<long long> indptr;      // [n + 1] the rows
+    DevArray<int> indices;           // the stored entries' features ...
+    DevArray<float> values;          // ... their values, as given (absent: every entry 1) ...
+    DevArray<float> xhat;            // ... normalised (cosine)
+    DevArray<int> asize;             // [n] the rows' set sizes (Jaccard)
+    DevArray<unsigned char> zero;    // [n] zero (Jaccard: empty) rows; the index's own, ctx->zero belongs to the dense calls
+    DevArray<u64> keys, sorted_keys; // S1's posting keys (feature << 32 | row); sorted.  `keys`: see run_flags()
+    DevArray<unsigned> pos, sorted_pos;  // each key's stored entry, the sort's values; sorted.  `pos`: see posting_rows()
+    DevArray<int> efeat;             // each stored entry's run (-1: no posting)
+    DevArray<float> pval;            // the postings' values (cosine)
+    DevArray<long long> runptr;      // [runs + 1] the runs' first postings
+    DevArray<int> heavy;             // [n] a search's queries for S3r
+    DevArray<u64> cnt;               // SP_CNT_* counters in [0, 8); behind them zidx() and zdist()
+    DevArray<char> tmp;              // rocprim's temporary storage
+    struct Built {  // the index these hold; none after a refused or failed build
+        bool valid = false;
+        int metric = 0;
+        long long n = 0, kept = 0, nzero = 0;  // rows, postings, zero (Jaccard: empty) rows
+    } built;
+    // The sort has read the unsorted keys, and nothing reads them again: their 8 bytes per stored entry hold two int32
+    // per posting (kept <= stored entries), the run-start flags in [0, kept) and the inclusive run numbers behind them.
+    int *run_flags() const { return reinterpret_cast<int *>(keys.ptr()); }
+    int *run_numbers(long long kept) const { return run_flags() + kept; }
+    // Likewise S2 reads the sorted positions only, so it writes the posting rows (int32, one per posting, in posting
+    // order) over the unsorted ones; that is where the searches read them.
+    int *posting_rows() const { return reinterpret_cast<int *>(pos.ptr()); }
+    // S4's closed-form row of a zero query lies behind the eight counters: FDR_MAX_K indices, then FDR_MAX_K distances
+    // (written per search, read by S3 in the same search).
+    static constexpr size_t cnt_words = 8 + FDR_MAX_K;
+    int *zidx() const { return reinterpret_cast<int *>(cnt.ptr() + 8); }
+    float *zdist() const { return reinterpret_cast<float *>(zidx() + FDR_MAX_K); }
+    template <class F>
+    auto each(F f) {
+        return f(indptr, indices, values, xhat, asize, zero, keys, sorted_keys, pos, sorted_pos, efeat, pval, runptr,
+                 heavy, cnt, tmp);
+    }
+    size_t bytes() {  // fdr_sparse_index_info: everything held, the build's scratch included
+        return each([](auto &...a) { return (a.bytes() + ...); });
+    }
+    void release() {
+        each([](auto &...a) { release_all(a...); });
+        built = {};
+    }
+};
+
 struct fdr_ctx {
     int device = 0;
     int num_cus = 256;
@@ -527,23 +685,9 @@ struct fdr_ctx {
     PinnedBuf stage_ids, stage_ptr;         // ... their pinned staging
     hipEvent_t up_ev[3] = {nullptr, nullptr, nullptr};  // ... the two raw runs in flight; [2] behind the last copy out of the staging
     hup::WorkerPool up_pool;                // ... the helpers
-    // k-mer search (kmer_search.inc)
-    DevBuf ks_seq, ks_off, ks_codes, ks_keys, ks_vals, ks_bloom, ks_counter, ks_pairs, ks_pairs2, ks_flag, ks_pos,
-        ks_idx, ks_rows, ks_indptr, ks_tmp, kc_counts;
-    DevBuf kc_a0, kc_a1, kc_c0, kc_c1, kc_mk, kc_mv, kc_rc;  // counting in blocks: accumulated table (ping / pong), merge buffers
-    // sparse k-NN (knn_sparse.inc)
-    DevBuf sp_ip, sp_ix, sp_val, sp_xhat, sp_keys, sp_keys2, sp_pos, sp_pos2, sp_efeat, sp_pval, sp_runptr, sp_heavy,
-        sp_cnt, sp_tmp, sp_asize, sp_zero;
-    struct {  // the sparse index these hold (fdr_sparse_index_build; one per context)
-        bool valid = false;
-        int metric = 0;
-        long long n = 0, kept = 0, nzero = 0;  // rows, postings, zero (Jaccard: empty) rows
-    } spx;
-    long long ks_nnz = 0, kc_n = 0;
-    int64_t kc_block_chars = 0;  // fdr_set_kmer_count_block
-    int kc_blocks = 0;           // blocks of the last fdr_kmer_count
-    int kc_k = 0, kc_acc = 0;    // incremental counting: k (0: not begun), which of the ping / pong tables is current
-    long long kc_na = 0;         // ... its entries
+    KmerSearchScratch ks;  // k-mer search, k-mer count / merge (kmer_search.inc): both released at every fetch
+    KmerCountScratch kc;
+    SparseIndex sp;        // sparse k-NN (knn_sparse.inc): kept until fdr_sparse_index_free
     // timing: when enabled, every launch of kernel kind i gets its own hipEvent pair on the launch
     // stream; fdr_timing_read() sums the elapsed times of all launches since the last read
     int knn_mode = FDR_MODE_AUTO;

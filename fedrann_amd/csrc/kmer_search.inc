@@ -18,6 +18,16 @@
 //     owns 16 consecutive window ends, builds the first code from k bytes and rolls the other 15;
 //   * hits are appended as (read << 32 | index) with one wave-aggregated atomic per wave, sorted with
 //     rocprim's radix sort, de-duplicated, and cut into rows by a binary search per read.
+//
+// Device scratch and state (fedrann_hip.hip): ctx->ks (struct KmerSearchScratch) is the search's -- inputs, table and
+// filter, the hits, their sorted copy, flags, scan, the unique hits' indices and rows, indptr, and `nnz` until
+// fdr_kmer_search_indices fetches them; ctx->kc (struct KmerCountScratch) is the count's -- a block's characters, codes
+// and runs, the two accumulated tables with `k`, `acc`, `na`, the merge and threshold arrays, the small tables of the
+// W-way merge and the export, and `n` until fdr_kmer_count_fetch.  One typed array per job; two arrays of the count
+// serve two jobs in turn and say so where they are declared (codes: a block's window codes, then its run codes; sorted:
+// a block's sorted codes, at the end the kept codes).  The two stages share nothing.  Either fetch releases both
+// (kmer_release_scratch), arrays and state together: a count whose table a fetch has freed is no longer under way.
+// Every rocprim call goes through rocprim_run with the stage's `tmp`; a sequence is sized by rocprim_reserve first.
 #define KS_CHUNK 4096
 #define KS_PER_THREAD 16
 
@@ -353,60 +363,56 @@ FDR_EXPORT int fdr_kmer_search(fdr_ctx *ctx, const uint8_t *seqs, const int64_t 
         if (seq_off[r + 1] < seq_off[r]) return fail(FDR_E_ARG, "fdr_kmer_search: seq_off is not monotone");
     const int64_t total = seq_off[n_reads];
     if (total > 0 && !seqs) return fail(FDR_E_ARG, "fdr_kmer_search: seqs is null");
-    ctx->ks_nnz = 0;
+    KmerSearchScratch &ks = ctx->ks;
+    ks.nnz = 0;
     indptr_out[0] = 0;
     *nnz_out = 0;
     if (n_reads == 0) return FDR_OK;
     hipStream_t st = ctx->stream;
 
     // inputs
-    if (int rc = ctx->ks_seq.reserve((size_t)total + 64)) return rc;
-    if (int rc = ctx->ks_off.reserve((size_t)(n_reads + 1) * 8)) return rc;
-    HIP_TRY(hipMemsetAsync(static_cast<char *>(ctx->ks_seq.p) + total, 0, 64, st));
-    if (total) HIP_TRY(hipMemcpyAsync(ctx->ks_seq.p, seqs, (size_t)total, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->ks_off.p, seq_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
+    if (int rc = ks.seq.reserve((size_t)total + 64)) return rc;
+    if (int rc = ks.off.reserve((size_t)(n_reads + 1))) return rc;
+    HIP_TRY(hipMemsetAsync(ks.seq.ptr() + total, 0, 64, st));
+    if (total) HIP_TRY(hipMemcpyAsync(ks.seq.ptr(), seqs, (size_t)total, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ks.off.ptr(), seq_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
     // library table + Bloom filter
     u64 tsize = 1024, bwords = 1024;
     while (tsize < 2ull * (u64)n_lib) tsize <<= 1;
     while (bwords < (u64)n_lib / 4) bwords <<= 1;  // 16 bits per key
-    if (int rc = ctx->ks_codes.reserve((size_t)std::max<int64_t>(n_lib, 1) * 8)) return rc;
-    if (int rc = ctx->ks_keys.reserve((size_t)tsize * 8)) return rc;
-    if (int rc = ctx->ks_vals.reserve((size_t)tsize * 4)) return rc;
-    if (int rc = ctx->ks_bloom.reserve((size_t)bwords * 8)) return rc;
-    if (int rc = ctx->ks_counter.reserve(256)) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->ks_keys.p, 0, (size_t)tsize * 8, st));
-    HIP_TRY(hipMemsetAsync(ctx->ks_bloom.p, 0, (size_t)bwords * 8, st));
+    if (int rc = ks.lib_codes.reserve((size_t)std::max<int64_t>(n_lib, 1))) return rc;
+    if (int rc = ks.keys.reserve((size_t)tsize)) return rc;
+    if (int rc = ks.vals.reserve((size_t)tsize)) return rc;
+    if (int rc = ks.bloom.reserve((size_t)bwords)) return rc;
+    if (int rc = ks.counter.reserve(32)) return rc;
+    HIP_TRY(hipMemsetAsync(ks.keys.ptr(), 0, (size_t)tsize * 8, st));
+    HIP_TRY(hipMemsetAsync(ks.bloom.ptr(), 0, (size_t)bwords * 8, st));
     int trc = timing_begin(ctx, FDR_KERNEL_KMER_SEARCH, st);
     if (trc) return trc;
     if (n_lib) {
-        HIP_TRY(hipMemcpyAsync(ctx->ks_codes.p, lib_codes, (size_t)n_lib * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(ks_build_kernel, dim3((unsigned)((n_lib + 255) / 256)), dim3(256), 0, st,
-                           (const u64 *)ctx->ks_codes.p, (long long)n_lib, (u64 *)ctx->ks_keys.p,
-                           (unsigned *)ctx->ks_vals.p, tsize - 1, (u64 *)ctx->ks_bloom.p, bwords - 1);
+        HIP_TRY(hipMemcpyAsync(ks.lib_codes.ptr(), lib_codes, (size_t)n_lib * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(ks_build_kernel, dim3((unsigned)((n_lib + 255) / 256)), dim3(256), 0, st, ks.lib_codes.ptr(),
+                           (long long)n_lib, ks.keys.ptr(), ks.vals.ptr(), tsize - 1, ks.bloom.ptr(), bwords - 1);
         HIP_TRY(hipGetLastError());
     }
     // search; the hit buffer is sized by a guess and the pass repeated once if it was too small
     long long cap = std::max<long long>(1 << 20, total / 4 + n_reads);
     unsigned long long count = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        if (int rc = ctx->ks_pairs.reserve((size_t)cap * 8)) return rc;
-        HIP_TRY(hipMemsetAsync(ctx->ks_counter.p, 0, 8, st));
+        if (int rc = ks.pairs.reserve((size_t)cap)) return rc;
+        HIP_TRY(hipMemsetAsync(ks.counter.ptr(), 0, 8, st));
         if (total > 0) {
             const long long chunks = (total + KS_CHUNK - 1) / KS_CHUNK;
             const unsigned grid = (unsigned)std::min<long long>(chunks, (long long)ctx->num_cus * 8);
-            hipLaunchKernelGGL(ks_search_kernel, dim3(grid), dim3(256), 0, st, (const unsigned char *)ctx->ks_seq.p,
-                               (long long)total, (const long long *)ctx->ks_off.p, (int)n_reads, (int)k,
-                               (const u64 *)ctx->ks_keys.p, (const unsigned *)ctx->ks_vals.p, tsize - 1,
-                               (const u64 *)ctx->ks_bloom.p, bwords - 1, (u64 *)ctx->ks_pairs.p, cap,
-                               (unsigned long long *)ctx->ks_counter.p);
+            hipLaunchKernelGGL(ks_search_kernel, dim3(grid), dim3(256), 0, st, ks.seq.ptr(), (long long)total,
+                               ks.off.ptr(), (int)n_reads, (int)k, ks.keys.ptr(), ks.vals.ptr(), tsize - 1,
+                               ks.bloom.ptr(), bwords - 1, ks.pairs.ptr(), cap, ks.counter.ptr());
         }
         hipLaunchKernelGGL(ks_short_reads_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, st,
-                           (const unsigned char *)ctx->ks_seq.p, (const long long *)ctx->ks_off.p, (int)n_reads,
-                           (int)k, (const u64 *)ctx->ks_keys.p, (const unsigned *)ctx->ks_vals.p, tsize - 1,
-                           (const u64 *)ctx->ks_bloom.p, bwords - 1, (u64 *)ctx->ks_pairs.p, cap,
-                           (unsigned long long *)ctx->ks_counter.p);
+                           ks.seq.ptr(), ks.off.ptr(), (int)n_reads, (int)k, ks.keys.ptr(), ks.vals.ptr(), tsize - 1,
+                           ks.bloom.ptr(), bwords - 1, ks.pairs.ptr(), cap, ks.counter.ptr());
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&count, ctx->ks_counter.p, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&count, ks.counter.ptr(), 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if ((long long)count <= cap) break;
         if (attempt == 1) return fail(FDR_E_STATE, "fdr_kmer_search: hit count changed between passes");
@@ -416,72 +422,64 @@ FDR_EXPORT int fdr_kmer_search(fdr_ctx *ctx, const uint8_t *seqs, const int64_t 
     if (count >= 0x7fffffffull) return fail(FDR_E_ARG, "fdr_kmer_search: %llu hits (limit 2^31)", count);
     const long long n = (long long)count;
     if ((trc = timing_begin(ctx, FDR_KERNEL_KMER_COMPACT, st))) return trc;
-    if (int rc = ctx->ks_indptr.reserve((size_t)(n_reads + 1) * 8)) return rc;
+    if (int rc = ks.indptr.reserve((size_t)(n_reads + 1))) return rc;
     long long nu = 0;
     if (n > 0) {
         // sort (read, index), drop repeats, cut into rows
-        size_t t_sort = 0, t_scan = 0;
-        (void)rocprim::radix_sort_keys(nullptr, t_sort, (u64 *)nullptr, (u64 *)nullptr, (size_t)n, 0, 64,
-                                       (hipStream_t) nullptr);
-        (void)rocprim::inclusive_scan(nullptr, t_scan, (int *)nullptr, (int *)nullptr, (size_t)n,
-                                      rocprim::plus<int>(), (hipStream_t) nullptr);
-        if (int rc = ctx->ks_tmp.reserve(std::max(t_sort, t_scan))) return rc;
-        if (int rc = ctx->ks_pairs2.reserve((size_t)n * 8)) return rc;
-        if (int rc = ctx->ks_flag.reserve((size_t)n * 4)) return rc;
-        if (int rc = ctx->ks_pos.reserve((size_t)n * 4)) return rc;
-        if (int rc = ctx->ks_idx.reserve((size_t)n * 4)) return rc;
-        if (int rc = ctx->ks_rows.reserve((size_t)n * 4)) return rc;
-        size_t tb = ctx->ks_tmp.cap;
-        HIP_TRY(rocprim::radix_sort_keys(ctx->ks_tmp.p, tb, (u64 *)ctx->ks_pairs.p, (u64 *)ctx->ks_pairs2.p,
-                                         (size_t)n, 0, 64, st));
+        if (int rc = ks.sorted.reserve((size_t)n)) return rc;
+        if (int rc = ks.flag.reserve((size_t)n)) return rc;
+        if (int rc = ks.scan.reserve((size_t)n)) return rc;
+        if (int rc = ks.indices.reserve((size_t)n)) return rc;
+        if (int rc = ks.rows.reserve((size_t)n)) return rc;
+        auto sort_hits = [&](void *tmp, size_t &bytes) {
+            return rocprim::radix_sort_keys(tmp, bytes, ks.pairs.ptr(), ks.sorted.ptr(), (size_t)n, 0, 64, st);
+        };
+        auto scan_flags = [&](void *tmp, size_t &bytes) {
+            return rocprim::inclusive_scan(tmp, bytes, ks.flag.ptr(), ks.scan.ptr(), (size_t)n, rocprim::plus<int>(), st);
+        };
+        if (int rc = rocprim_reserve(ks.tmp, sort_hits, scan_flags)) return rc;  // (for both: the scan regrows nothing)
+        if (int rc = rocprim_run(ks.tmp, "rocprim::radix_sort_keys", sort_hits)) return rc;
         const unsigned g = (unsigned)((n + 255) / 256);
-        hipLaunchKernelGGL(ks_mark_unique_kernel, dim3(g), dim3(256), 0, st, (const u64 *)ctx->ks_pairs2.p, n,
-                           (int *)ctx->ks_flag.p);
-        tb = ctx->ks_tmp.cap;
-        HIP_TRY(rocprim::inclusive_scan(ctx->ks_tmp.p, tb, (int *)ctx->ks_flag.p, (int *)ctx->ks_pos.p, (size_t)n,
-                                        rocprim::plus<int>(), st));
-        hipLaunchKernelGGL(ks_compact_kernel, dim3(g), dim3(256), 0, st, (const u64 *)ctx->ks_pairs2.p, n,
-                           (const int *)ctx->ks_flag.p, (const int *)ctx->ks_pos.p, (int *)ctx->ks_idx.p,
-                           (int *)ctx->ks_rows.p);
+        hipLaunchKernelGGL(ks_mark_unique_kernel, dim3(g), dim3(256), 0, st, ks.sorted.ptr(), n, ks.flag.ptr());
+        if (int rc = rocprim_run(ks.tmp, "rocprim::inclusive_scan", scan_flags)) return rc;
+        hipLaunchKernelGGL(ks_compact_kernel, dim3(g), dim3(256), 0, st, ks.sorted.ptr(), n, ks.flag.ptr(),
+                           ks.scan.ptr(), ks.indices.ptr(), ks.rows.ptr());
         HIP_TRY(hipGetLastError());
         int last = 0;
-        HIP_TRY(hipMemcpyAsync(&last, static_cast<int *>(ctx->ks_pos.p) + (n - 1), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&last, ks.scan.ptr() + (n - 1), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         nu = last;
         hipLaunchKernelGGL(ks_indptr_kernel, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, st,
-                           (const int *)ctx->ks_rows.p, nu, (int)n_reads, (long long *)ctx->ks_indptr.p);
+                           ks.rows.ptr(), nu, (int)n_reads, ks.indptr.ptr());
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(indptr_out, ctx->ks_indptr.p, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(indptr_out, ks.indptr.ptr(), (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
     } else {
         memset(indptr_out, 0, (size_t)(n_reads + 1) * 8);
     }
     if ((trc = timing_end(ctx, FDR_KERNEL_KMER_COMPACT, st))) return trc;
     HIP_TRY(hipStreamSynchronize(st));
-    ctx->ks_nnz = nu;
+    ks.nnz = nu;
     *nnz_out = nu;
     return FDR_OK;
 }
 
-// the k-mer search / counting scratch (sequences, codes, tables, (read, index) pairs, sort buffers): released
-// once a call's results have been fetched
-static void ks_release_scratch(fdr_ctx *ctx) {
-    DevBuf *bufs[] = {&ctx->ks_seq, &ctx->ks_off, &ctx->ks_codes, &ctx->ks_keys, &ctx->ks_vals, &ctx->ks_bloom,
-                      &ctx->ks_counter, &ctx->ks_pairs, &ctx->ks_pairs2, &ctx->ks_flag, &ctx->ks_pos, &ctx->ks_idx,
-                      &ctx->ks_rows, &ctx->ks_indptr, &ctx->ks_tmp, &ctx->kc_counts, &ctx->kc_a0, &ctx->kc_a1, &ctx->kc_c0,
-                      &ctx->kc_c1, &ctx->kc_mk, &ctx->kc_mv, &ctx->kc_rc};
-    for (DevBuf *b : bufs) b->release();
+// A fetch releases all k-mer scratch, the search's and the count's (~28 B per base: not to be held through the embed /
+// k-NN stages), each with its state: what a released array held cannot be fetched again or, for a count under way,
+// resumed (fdr_kmer_count_add then asks for fdr_kmer_count_begin)
+static void kmer_release_scratch(fdr_ctx *ctx) {
+    ctx->ks.release();
+    ctx->kc.release();
 }
 
 FDR_EXPORT int fdr_kmer_search_indices(fdr_ctx *ctx, int32_t *indices_out) {
     if (int rc = use_device(ctx)) return rc;
-    if (ctx->ks_nnz > 0 && !indices_out) return fail(FDR_E_ARG, "fdr_kmer_search_indices: null output");
-    if (ctx->ks_nnz > 0) {
-        HIP_TRY(hipMemcpyAsync(indices_out, ctx->ks_idx.p, (size_t)ctx->ks_nnz * 4, hipMemcpyDeviceToHost,
-                               ctx->stream));
+    const long long nnz = ctx->ks.nnz;
+    if (nnz > 0 && !indices_out) return fail(FDR_E_ARG, "fdr_kmer_search_indices: null output");
+    if (nnz > 0) {
+        HIP_TRY(hipMemcpyAsync(indices_out, ctx->ks.indices.ptr(), (size_t)nnz * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
-    ks_release_scratch(ctx);  // the search's buffers are per call: free them for the embed / k-NN stages
-    ctx->ks_nnz = 0;
+    kmer_release_scratch(ctx);
     return FDR_OK;
 }
 
@@ -600,47 +598,41 @@ __global__ __launch_bounds__(256) void kc_widen_kernel(const unsigned *__restric
 }
 
 // One block of reads (`total` < 2^32 characters): canonical codes of every position, sorted, run-length encoded.
-// Leaves the run codes (ascending; the "no k-mer here" marker ~0 last, if any) in ks_pairs and their lengths in
-// ks_flag; *nruns_out = number of runs.
+// Leaves the run codes (ascending; the "no k-mer here" marker ~0 last, if any) in kc.codes and their lengths in
+// kc.run_len; *nruns_out = number of runs.
 static int kc_block_runs(fdr_ctx *ctx, const uint8_t *seqs, const int64_t *off_rel, int64_t n_reads, int64_t total,
                          int k, unsigned *nruns_out) {
     hipStream_t st = ctx->stream;
-    if (int rc = ctx->ks_seq.reserve((size_t)total + 64)) return rc;
-    if (int rc = ctx->ks_off.reserve((size_t)(n_reads + 1) * 8)) return rc;
-    HIP_TRY(hipMemsetAsync(static_cast<char *>(ctx->ks_seq.p) + total, 0, 64, st));
-    HIP_TRY(hipMemcpyAsync(ctx->ks_seq.p, seqs, (size_t)total, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->ks_off.p, off_rel, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-    size_t t_sort = 0, t_rle = 0, t_scan = 0;
-    (void)rocprim::radix_sort_keys(nullptr, t_sort, (u64 *)nullptr, (u64 *)nullptr, (size_t)total, 0, 2 * k + 1,
-                                   (hipStream_t) nullptr);
-    (void)rocprim::run_length_encode(nullptr, t_rle, (u64 *)nullptr, (unsigned)total, (u64 *)nullptr,
-                                     (unsigned *)nullptr, (unsigned *)nullptr, (hipStream_t) nullptr);
-    (void)rocprim::inclusive_scan(nullptr, t_scan, (int *)nullptr, (int *)nullptr, (size_t)total,
-                                  rocprim::plus<int>(), (hipStream_t) nullptr);
-    if (int rc = ctx->ks_tmp.reserve(std::max(t_sort, std::max(t_rle, t_scan)))) return rc;
-    if (int rc = ctx->ks_pairs.reserve((size_t)total * 8)) return rc;   // codes, later the run codes
-    if (int rc = ctx->ks_pairs2.reserve((size_t)total * 8)) return rc;  // sorted codes, later the kept codes
-    if (int rc = ctx->ks_flag.reserve((size_t)total * 4)) return rc;    // run counts
-    if (int rc = ctx->ks_pos.reserve((size_t)total * 4)) return rc;     // keep flags
-    if (int rc = ctx->ks_rows.reserve((size_t)total * 4)) return rc;    // scan of the flags
-    if (int rc = ctx->ks_counter.reserve(256)) return rc;
+    KmerCountScratch &kc = ctx->kc;
+    if (int rc = kc.seq.reserve((size_t)total + 64)) return rc;
+    if (int rc = kc.off.reserve((size_t)(n_reads + 1))) return rc;
+    HIP_TRY(hipMemsetAsync(kc.seq.ptr() + total, 0, 64, st));
+    HIP_TRY(hipMemcpyAsync(kc.seq.ptr(), seqs, (size_t)total, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(kc.off.ptr(), off_rel, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
+    if (int rc = kc.codes.reserve((size_t)total)) return rc;
+    if (int rc = kc.sorted.reserve((size_t)total)) return rc;
+    if (int rc = kc.run_len.reserve((size_t)total)) return rc;
+    if (int rc = kc.n_runs.reserve(1)) return rc;
+    auto sort_codes = [&](void *tmp, size_t &bytes) {  // (the all-ones marker needs bit 2k: codes use 2k bits)
+        return rocprim::radix_sort_keys(tmp, bytes, kc.codes.ptr(), kc.sorted.ptr(), (size_t)total, 0, 2 * k + 1, st);
+    };
+    auto encode_runs = [&](void *tmp, size_t &bytes) {  // (the sorted codes in, the run codes over the unsorted ones)
+        return rocprim::run_length_encode(tmp, bytes, kc.sorted.ptr(), (unsigned)total, kc.codes.ptr(),
+                                          kc.run_len.ptr(), kc.n_runs.ptr(), st);
+    };
+    if (int rc = rocprim_reserve(kc.tmp, sort_codes, encode_runs)) return rc;  // (for both: nothing regrows under way)
     int trc = timing_begin(ctx, FDR_KERNEL_KMER_SEARCH, st);
     if (trc) return trc;
     const long long chunks = (total + KS_CHUNK - 1) / KS_CHUNK;
     hipLaunchKernelGGL(kc_codes_kernel, dim3((unsigned)std::min<long long>(chunks, (long long)ctx->num_cus * 8)),
-                       dim3(256), 0, st, (const unsigned char *)ctx->ks_seq.p, (long long)total,
-                       (const long long *)ctx->ks_off.p, (int)n_reads, (int)k, (u64 *)ctx->ks_pairs.p);
+                       dim3(256), 0, st, kc.seq.ptr(), (long long)total, kc.off.ptr(), (int)n_reads, (int)k,
+                       kc.codes.ptr());
     HIP_TRY(hipGetLastError());
     if ((trc = timing_end(ctx, FDR_KERNEL_KMER_SEARCH, st))) return trc;
     if ((trc = timing_begin(ctx, FDR_KERNEL_KMER_COMPACT, st))) return trc;
-    size_t tb = ctx->ks_tmp.cap;  // (the all-ones marker needs bit 2k: codes use 2k bits)
-    HIP_TRY(rocprim::radix_sort_keys(ctx->ks_tmp.p, tb, (u64 *)ctx->ks_pairs.p, (u64 *)ctx->ks_pairs2.p,
-                                     (size_t)total, 0, 2 * k + 1, st));
-    tb = ctx->ks_tmp.cap;
-    HIP_TRY(rocprim::run_length_encode(ctx->ks_tmp.p, tb, (u64 *)ctx->ks_pairs2.p, (unsigned)total,
-                                       (u64 *)ctx->ks_pairs.p, (unsigned *)ctx->ks_flag.p,
-                                       (unsigned *)ctx->ks_counter.p, st));
-    HIP_TRY(hipMemcpyAsync(nruns_out, ctx->ks_counter.p, 4, hipMemcpyDeviceToHost, st));
+    if (int rc = rocprim_run(kc.tmp, "rocprim::radix_sort_keys", sort_codes)) return rc;
+    if (int rc = rocprim_run(kc.tmp, "rocprim::run_length_encode", encode_runs)) return rc;
+    HIP_TRY(hipMemcpyAsync(nruns_out, kc.n_runs.ptr(), 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return timing_end(ctx, FDR_KERNEL_KMER_COMPACT, st);
 }
@@ -657,17 +649,17 @@ static int kc_block_runs(fdr_ctx *ctx, const uint8_t *seqs, const int64_t *off_r
 FDR_EXPORT int fdr_kmer_count_begin(fdr_ctx *ctx, int32_t k) {
     if (int rc = use_device(ctx)) return rc;
     if (k <= 0 || k > 31) return fail(FDR_E_ARG, "fdr_kmer_count: k must be in [1, 31] (got %d)", k);
-    ctx->kc_k = k;
-    ctx->kc_na = 0;
-    ctx->kc_acc = 0;
-    ctx->kc_blocks = 0;
-    ctx->kc_n = 0;
+    ctx->kc.k = k;
+    ctx->kc.na = 0;
+    ctx->kc.acc = 0;
+    ctx->kc.blocks = 0;
+    ctx->kc.n = 0;
     return FDR_OK;
 }
 
 FDR_EXPORT int fdr_kmer_count_add(fdr_ctx *ctx, const uint8_t *seqs, const int64_t *seq_off, int64_t n_reads) {
     if (int rc = use_device(ctx)) return rc;
-    if (ctx->kc_k <= 0) return fail(FDR_E_STATE, "fdr_kmer_count_add: call fdr_kmer_count_begin first");
+    if (ctx->kc.k <= 0) return fail(FDR_E_STATE, "fdr_kmer_count_add: call fdr_kmer_count_begin first");
     if (!seq_off || n_reads < 0) return fail(FDR_E_ARG, "fdr_kmer_count: bad argument");
     if (n_reads >= 0x7fffffffll) return fail(FDR_E_ARG, "fdr_kmer_count: read count must be below 2^31");
     if (n_reads > 0 && seq_off[0] != 0) return fail(FDR_E_ARG, "fdr_kmer_count: seq_off[0] must be 0");
@@ -676,9 +668,10 @@ FDR_EXPORT int fdr_kmer_count_add(fdr_ctx *ctx, const uint8_t *seqs, const int64
     const int64_t total = n_reads > 0 ? seq_off[n_reads] : 0;
     if (total > 0 && !seqs) return fail(FDR_E_ARG, "fdr_kmer_count: seqs is null");
     if (total == 0) return FDR_OK;
-    const int k = ctx->kc_k;
+    KmerCountScratch &kc = ctx->kc;
+    const int k = kc.k;
     hipStream_t st = ctx->stream;
-    const int64_t limit = ctx->kc_block_chars > 0 ? ctx->kc_block_chars : (int64_t)1 << 31;  // characters per block
+    const int64_t limit = kc.block_chars > 0 ? kc.block_chars : (int64_t)1 << 31;  // characters per block
     int trc;
     for (int64_t r0 = 0; r0 < n_reads;) {
         // whole reads, fewer than `limit` characters (a single longer read cannot be counted)
@@ -696,50 +689,47 @@ FDR_EXPORT int fdr_kmer_count_add(fdr_ctx *ctx, const uint8_t *seqs, const int64
         }
         r0 = r1;
         if (nruns == 0) continue;
-        ++ctx->kc_blocks;
-        DevBuf *acc_codes = ctx->kc_acc ? &ctx->kc_a1 : &ctx->kc_a0, *acc_counts = ctx->kc_acc ? &ctx->kc_c1 : &ctx->kc_c0;
-        DevBuf *nxt_codes = ctx->kc_acc ? &ctx->kc_a0 : &ctx->kc_a1, *nxt_counts = ctx->kc_acc ? &ctx->kc_c0 : &ctx->kc_c1;
+        ++kc.blocks;
+        DevArray<u64> &acc_codes = kc.acc_codes[kc.acc], &acc_counts = kc.acc_counts[kc.acc];
+        DevArray<u64> &nxt_codes = kc.acc_codes[kc.acc ^ 1], &nxt_counts = kc.acc_counts[kc.acc ^ 1];
         if ((trc = timing_begin(ctx, FDR_KERNEL_KMER_COMPACT, st))) return trc;
-        if (int rc = ctx->kc_rc.reserve((size_t)nruns * 8)) return rc;
-        hipLaunchKernelGGL(kc_widen_kernel, dim3((nruns + 255) / 256), dim3(256), 0, st, (const unsigned *)ctx->ks_flag.p,
-                           (long long)nruns, (u64 *)ctx->kc_rc.p);
+        if (int rc = kc.run_counts.reserve(nruns)) return rc;
+        hipLaunchKernelGGL(kc_widen_kernel, dim3((nruns + 255) / 256), dim3(256), 0, st, kc.run_len.ptr(),
+                           (long long)nruns, kc.run_counts.ptr());
         HIP_TRY(hipGetLastError());
-        if (ctx->kc_na == 0) {  // the first block: its runs are the table so far
-            if (int rc = acc_codes->reserve((size_t)nruns * 8)) return rc;
-            if (int rc = acc_counts->reserve((size_t)nruns * 8)) return rc;
-            HIP_TRY(hipMemcpyAsync(acc_codes->p, ctx->ks_pairs.p, (size_t)nruns * 8, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(acc_counts->p, ctx->kc_rc.p, (size_t)nruns * 8, hipMemcpyDeviceToDevice, st));
+        if (kc.na == 0) {  // the first block: its runs are the table so far
+            if (int rc = acc_codes.reserve(nruns)) return rc;
+            if (int rc = acc_counts.reserve(nruns)) return rc;
+            HIP_TRY(hipMemcpyAsync(acc_codes.ptr(), kc.codes.ptr(), (size_t)nruns * 8, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(acc_counts.ptr(), kc.run_counts.ptr(), (size_t)nruns * 8, hipMemcpyDeviceToDevice, st));
             HIP_TRY(hipStreamSynchronize(st));  // (the next block reuses the run buffers)
-            ctx->kc_na = nruns;
+            kc.na = nruns;
         } else {
-            const long long na = ctx->kc_na;
+            const long long na = kc.na;
             const size_t nm = (size_t)na + nruns;
-            if (int rc = ctx->kc_mk.reserve(nm * 8)) return rc;
-            if (int rc = ctx->kc_mv.reserve(nm * 8)) return rc;
-            if (int rc = nxt_codes->reserve(nm * 8)) return rc;
-            if (int rc = nxt_counts->reserve(nm * 8)) return rc;
-            size_t t_merge = 0, t_red = 0;
-            (void)rocprim::merge(nullptr, t_merge, (u64 *)nullptr, (u64 *)nullptr, (u64 *)nullptr, (u64 *)nullptr,
-                                 (u64 *)nullptr, (u64 *)nullptr, (size_t)na, (size_t)nruns, rocprim::less<u64>(),
-                                 (hipStream_t) nullptr);
-            (void)rocprim::reduce_by_key(nullptr, t_red, (u64 *)nullptr, (u64 *)nullptr, nm, (u64 *)nullptr,
-                                         (u64 *)nullptr, (unsigned long long *)nullptr, rocprim::plus<u64>(),
-                                         rocprim::equal_to<u64>(), (hipStream_t) nullptr);
-            if (int rc = ctx->ks_tmp.reserve(std::max(t_merge, t_red))) return rc;
-            size_t tb = ctx->ks_tmp.cap;
-            HIP_TRY(rocprim::merge(ctx->ks_tmp.p, tb, (u64 *)acc_codes->p, (u64 *)ctx->ks_pairs.p, (u64 *)ctx->kc_mk.p,
-                                   (u64 *)acc_counts->p, (u64 *)ctx->kc_rc.p, (u64 *)ctx->kc_mv.p, (size_t)na,
-                                   (size_t)nruns, rocprim::less<u64>(), st));
-            tb = ctx->ks_tmp.cap;
-            HIP_TRY(rocprim::reduce_by_key(ctx->ks_tmp.p, tb, (u64 *)ctx->kc_mk.p, (u64 *)ctx->kc_mv.p, nm,
-                                           (u64 *)nxt_codes->p, (u64 *)nxt_counts->p,
-                                           (unsigned long long *)ctx->ks_counter.p, rocprim::plus<u64>(),
-                                           rocprim::equal_to<u64>(), st));
+            if (int rc = kc.merged_codes.reserve(nm)) return rc;
+            if (int rc = kc.merged_counts.reserve(nm)) return rc;
+            if (int rc = nxt_codes.reserve(nm)) return rc;
+            if (int rc = nxt_counts.reserve(nm)) return rc;
+            if (int rc = kc.n_table.reserve(1)) return rc;
+            auto merge_runs = [&](void *tmp, size_t &bytes) {
+                return rocprim::merge(tmp, bytes, acc_codes.ptr(), kc.codes.ptr(), kc.merged_codes.ptr(), acc_counts.ptr(),
+                                      kc.run_counts.ptr(), kc.merged_counts.ptr(), (size_t)na, (size_t)nruns,
+                                      rocprim::less<u64>(), st);
+            };
+            auto sum_equal = [&](void *tmp, size_t &bytes) {
+                return rocprim::reduce_by_key(tmp, bytes, kc.merged_codes.ptr(), kc.merged_counts.ptr(), nm,
+                                              nxt_codes.ptr(), nxt_counts.ptr(), kc.n_table.ptr(), rocprim::plus<u64>(),
+                                              rocprim::equal_to<u64>(), st);
+            };
+            if (int rc = rocprim_reserve(kc.tmp, merge_runs, sum_equal)) return rc;  // (for both)
+            if (int rc = rocprim_run(kc.tmp, "rocprim::merge", merge_runs)) return rc;
+            if (int rc = rocprim_run(kc.tmp, "rocprim::reduce_by_key", sum_equal)) return rc;
             unsigned long long nu = 0;
-            HIP_TRY(hipMemcpyAsync(&nu, ctx->ks_counter.p, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(&nu, kc.n_table.ptr(), 8, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            ctx->kc_na = (long long)nu;
-            ctx->kc_acc ^= 1;
+            kc.na = (long long)nu;
+            kc.acc ^= 1;
         }
         if ((trc = timing_end(ctx, FDR_KERNEL_KMER_COMPACT, st))) return trc;
     }
@@ -749,48 +739,46 @@ FDR_EXPORT int fdr_kmer_count_add(fdr_ctx *ctx, const uint8_t *seqs, const int64
 FDR_EXPORT int fdr_kmer_count_finish(fdr_ctx *ctx, int64_t min_count, int64_t *n_out) {
     if (int rc = use_device(ctx)) return rc;
     if (!n_out) return fail(FDR_E_ARG, "fdr_kmer_count: bad argument");
-    if (ctx->kc_k <= 0) return fail(FDR_E_STATE, "fdr_kmer_count_finish: call fdr_kmer_count_begin first");
+    if (ctx->kc.k <= 0) return fail(FDR_E_STATE, "fdr_kmer_count_finish: call fdr_kmer_count_begin first");
+    KmerCountScratch &kc = ctx->kc;
     hipStream_t st = ctx->stream;
     const u64 minc = (u64)std::max<int64_t>(1, min_count);
-    const u64 *d_codes = (const u64 *)(ctx->kc_acc ? ctx->kc_a1.p : ctx->kc_a0.p);   // the table the threshold is applied to
-    const u64 *d_counts = (const u64 *)(ctx->kc_acc ? ctx->kc_c1.p : ctx->kc_c0.p);  // (64-bit counts)
-    const long long n_table = ctx->kc_na;
-    ctx->kc_k = 0;
-    ctx->kc_n = 0;
+    const u64 *d_codes = kc.acc_codes[kc.acc].ptr();    // the table the threshold is applied to
+    const u64 *d_counts = kc.acc_counts[kc.acc].ptr();  // (64-bit counts)
+    const long long n_table = kc.na;
+    kc.k = 0;
+    kc.n = 0;
     *n_out = 0;
     int trc;
     long long kept = 0;
     if (n_table > 0) {
         if (n_table >= 0x7fffffffll) return fail(FDR_E_ARG, "fdr_kmer_count: %lld distinct k-mers (limit 2^31)", n_table);
         if ((trc = timing_begin(ctx, FDR_KERNEL_KMER_COMPACT, st))) return trc;
-        size_t t_scan = 0;
-        (void)rocprim::inclusive_scan(nullptr, t_scan, (int *)nullptr, (int *)nullptr, (size_t)n_table,
-                                      rocprim::plus<int>(), (hipStream_t) nullptr);
-        if (int rc = ctx->ks_tmp.reserve(t_scan)) return rc;
-        if (int rc = ctx->ks_pos.reserve((size_t)n_table * 4)) return rc;
-        if (int rc = ctx->ks_rows.reserve((size_t)n_table * 4)) return rc;
+        if (int rc = kc.keep.reserve((size_t)n_table)) return rc;
+        if (int rc = kc.keep_scan.reserve((size_t)n_table)) return rc;
+        auto scan_keep = [&](void *tmp, size_t &bytes) {
+            return rocprim::inclusive_scan(tmp, bytes, kc.keep.ptr(), kc.keep_scan.ptr(), (size_t)n_table,
+                                           rocprim::plus<int>(), st);
+        };
+        if (int rc = rocprim_reserve(kc.tmp, scan_keep)) return rc;  // (ahead of the launch)
         const unsigned g = (unsigned)((n_table + 255) / 256);
-        hipLaunchKernelGGL(kc_flag64_kernel, dim3(g), dim3(256), 0, st, d_codes, d_counts, n_table, minc,
-                           (int *)ctx->ks_pos.p);
-        size_t tb = ctx->ks_tmp.cap;
-        HIP_TRY(rocprim::inclusive_scan(ctx->ks_tmp.p, tb, (int *)ctx->ks_pos.p, (int *)ctx->ks_rows.p,
-                                        (size_t)n_table, rocprim::plus<int>(), st));
+        hipLaunchKernelGGL(kc_flag64_kernel, dim3(g), dim3(256), 0, st, d_codes, d_counts, n_table, minc, kc.keep.ptr());
+        if (int rc = rocprim_run(kc.tmp, "rocprim::inclusive_scan", scan_keep)) return rc;
         int last = 0;
-        HIP_TRY(hipMemcpyAsync(&last, static_cast<int *>(ctx->ks_rows.p) + (n_table - 1), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&last, kc.keep_scan.ptr() + (n_table - 1), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         kept = last;
         if (kept > 0) {
-            if (int rc = ctx->ks_pairs2.reserve((size_t)kept * 8)) return rc;
-            if (int rc = ctx->kc_counts.reserve((size_t)kept * 8)) return rc;
-            hipLaunchKernelGGL(kc_compact64_kernel, dim3(g), dim3(256), 0, st, d_codes, d_counts, n_table,
-                               (const int *)ctx->ks_pos.p, (const int *)ctx->ks_rows.p, (u64 *)ctx->ks_pairs2.p,
-                               (u64 *)ctx->kc_counts.p);
+            if (int rc = kc.sorted.reserve((size_t)kept)) return rc;  // (no block is under way: the kept codes)
+            if (int rc = kc.kept_counts.reserve((size_t)kept)) return rc;
+            hipLaunchKernelGGL(kc_compact64_kernel, dim3(g), dim3(256), 0, st, d_codes, d_counts, n_table, kc.keep.ptr(),
+                               kc.keep_scan.ptr(), kc.sorted.ptr(), kc.kept_counts.ptr());
             HIP_TRY(hipGetLastError());
         }
         if ((trc = timing_end(ctx, FDR_KERNEL_KMER_COMPACT, st))) return trc;
     }
     HIP_TRY(hipStreamSynchronize(st));
-    ctx->kc_n = kept;
+    kc.n = kept;
     *n_out = kept;
     return FDR_OK;
 }
@@ -809,22 +797,22 @@ FDR_EXPORT int fdr_kmer_count(fdr_ctx *ctx, const uint8_t *seqs, const int64_t *
 FDR_EXPORT int fdr_set_kmer_count_block(fdr_ctx *ctx, int64_t chars) {
     if (!ctx) return fail(FDR_E_ARG, "null context");
     if (chars < 0 || chars > 0xffffffffll) return fail(FDR_E_ARG, "fdr_set_kmer_count_block: 0 .. 2^32 - 1 characters");
-    ctx->kc_block_chars = chars;
+    ctx->kc.block_chars = chars;
     return FDR_OK;
 }
 
-FDR_EXPORT int fdr_last_kmer_count_blocks(fdr_ctx *ctx) { return ctx ? ctx->kc_blocks : 0; }
+FDR_EXPORT int fdr_last_kmer_count_blocks(fdr_ctx *ctx) { return ctx ? ctx->kc.blocks : 0; }
 
 FDR_EXPORT int fdr_kmer_count_fetch(fdr_ctx *ctx, uint64_t *codes_out, uint64_t *counts_out) {
     if (int rc = use_device(ctx)) return rc;
-    if (ctx->kc_n > 0 && (!codes_out || !counts_out)) return fail(FDR_E_ARG, "fdr_kmer_count_fetch: null output");
-    if (ctx->kc_n > 0) {
-        HIP_TRY(hipMemcpyAsync(codes_out, ctx->ks_pairs2.p, (size_t)ctx->kc_n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(counts_out, ctx->kc_counts.p, (size_t)ctx->kc_n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    const long long n = ctx->kc.n;
+    if (n > 0 && (!codes_out || !counts_out)) return fail(FDR_E_ARG, "fdr_kmer_count_fetch: null output");
+    if (n > 0) {
+        HIP_TRY(hipMemcpyAsync(codes_out, ctx->kc.sorted.ptr(), (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(counts_out, ctx->kc.kept_counts.ptr(), (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
-    ks_release_scratch(ctx);  // ~28 B per base: not to be held through the embed / k-NN stages
-    ctx->kc_n = 0;
+    kmer_release_scratch(ctx);
     return FDR_OK;
 }
 
@@ -972,24 +960,25 @@ FDR_EXPORT int fdr_kmer_count_export_dev(fdr_ctx *ctx, const uint64_t *d_splitte
                                          uint64_t *d_codes_out, uint64_t *d_counts_out, int64_t *part_off_out,
                                          void *stream) {
     if (int rc = use_device(ctx)) return rc;
-    if (ctx->kc_k <= 0) return fail(FDR_E_STATE, "fdr_kmer_count_export_dev: call fdr_kmer_count_begin first");
+    if (ctx->kc.k <= 0) return fail(FDR_E_STATE, "fdr_kmer_count_export_dev: call fdr_kmer_count_begin first");
     if (n_parts < 1 || !part_off_out || (n_parts > 1 && !d_splitters) || (!d_codes_out != !d_counts_out))
         return fail(FDR_E_ARG, "fdr_kmer_count_export_dev: bad argument");
+    KmerCountScratch &kc = ctx->kc;
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    const u64 *d_codes = (const u64 *)(ctx->kc_acc ? ctx->kc_a1.p : ctx->kc_a0.p);
-    const u64 *d_counts = (const u64 *)(ctx->kc_acc ? ctx->kc_c1.p : ctx->kc_c0.p);
-    long long n = ctx->kc_na;
+    const u64 *d_codes = kc.acc_codes[kc.acc].ptr();
+    const u64 *d_counts = kc.acc_counts[kc.acc].ptr();
+    long long n = kc.na;
     if (n > 0) {  // the "no k-mer here" marker ~0 sorts last and is no k-mer: not exported
         u64 last = 0;
         HIP_TRY(hipMemcpyAsync(&last, d_codes + (n - 1), 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (last == ~0ull) --n;
     }
-    if (int rc = ctx->ks_indptr.reserve((size_t)(n_parts + 1) * 8)) return rc;
+    if (int rc = kc.part_off.reserve((size_t)(n_parts + 1))) return rc;
     hipLaunchKernelGGL(km_parts_kernel, dim3((unsigned)((n_parts + 256) / 256)), dim3(256), 0, st, d_codes, n,
-                       (const u64 *)d_splitters, (int)n_parts, (long long *)ctx->ks_indptr.p);
+                       (const u64 *)d_splitters, (int)n_parts, kc.part_off.ptr());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(part_off_out, ctx->ks_indptr.p, (size_t)(n_parts + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(part_off_out, kc.part_off.ptr(), (size_t)(n_parts + 1) * 8, hipMemcpyDeviceToHost, st));
     if (d_codes_out && n > 0) {
         HIP_TRY(hipMemcpyAsync(d_codes_out, d_codes, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_counts_out, d_counts, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
@@ -1001,9 +990,10 @@ FDR_EXPORT int fdr_kmer_count_export_dev(fdr_ctx *ctx, const uint64_t *d_splitte
 // the merge of n_runs runs already on the device (d_codes / d_counts at run_off[r] .. run_off[r + 1])
 static int km_merge(fdr_ctx *ctx, int32_t n_runs, const int64_t *run_off, const u64 *d_codes, const u64 *d_counts,
                     int64_t min_count, int64_t *n_out, hipStream_t st) {
+    KmerCountScratch &kc = ctx->kc;
     const long long M = run_off[n_runs];
-    ctx->kc_k = 0;
-    ctx->kc_n = 0;
+    kc.k = 0;
+    kc.n = 0;
     *n_out = 0;
     if (M == 0) return FDR_OK;
     if (M >= 0x7fffffffll) return fail(FDR_E_ARG, "fdr_kmer_count_merge: %lld entries (limit 2^31)", M);
@@ -1014,59 +1004,54 @@ static int km_merge(fdr_ctx *ctx, int32_t n_runs, const int64_t *run_off, const 
         samp_pre[(size_t)r + 1] = samp_pre[(size_t)r] + (len > 0 ? (len - 1) / KM_STRIDE : 0);
     }
     const long long n_s = samp_pre[(size_t)n_runs], n_tiles = n_s + 1;
-    size_t t_sort = 0, t_scan = 0;
-    (void)rocprim::radix_sort_keys(nullptr, t_sort, (u64 *)nullptr, (u64 *)nullptr, (size_t)std::max(n_s, 1ll), 0, 64,
-                                   (hipStream_t) nullptr);
-    (void)rocprim::inclusive_scan(nullptr, t_scan, (int *)nullptr, (int *)nullptr, (size_t)M, rocprim::plus<int>(),
-                                  (hipStream_t) nullptr);
-    if (int rc = ctx->ks_tmp.reserve(std::max(t_sort, t_scan))) return rc;
-    if (int rc = ctx->ks_off.reserve((size_t)(2 * n_runs + 2) * 8)) return rc;  // run offsets, sample prefix
-    if (int rc = ctx->ks_codes.reserve((size_t)std::max(n_s, 1ll) * 8)) return rc;  // samples
-    if (int rc = ctx->ks_keys.reserve((size_t)std::max(n_s, 1ll) * 8)) return rc;   // sorted samples = boundaries
-    if (int rc = ctx->ks_idx.reserve((size_t)(n_tiles + 1) * n_runs * 8)) return rc;  // slices
-    if (int rc = ctx->kc_mk.reserve((size_t)M * 8)) return rc;   // owners' codes at their merged place
-    if (int rc = ctx->kc_mv.reserve((size_t)M * 8)) return rc;   // ... their totals
-    if (int rc = ctx->ks_pos.reserve((size_t)M * 4)) return rc;  // keep flags
-    if (int rc = ctx->ks_rows.reserve((size_t)M * 4)) return rc; // their inclusive scan
-    long long *d_roff = (long long *)ctx->ks_off.p, *d_spre = d_roff + n_runs + 1;
-    HIP_TRY(hipMemcpyAsync(d_roff, run_off, (size_t)(n_runs + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_spre, samp_pre.data(), (size_t)(n_runs + 1) * 8, hipMemcpyHostToDevice, st));
+    if (int rc = kc.run_off.reserve((size_t)n_runs + 1)) return rc;
+    if (int rc = kc.samp_pre.reserve((size_t)n_runs + 1)) return rc;
+    if (int rc = kc.samples.reserve((size_t)std::max(n_s, 1ll))) return rc;
+    if (int rc = kc.bounds.reserve((size_t)std::max(n_s, 1ll))) return rc;
+    if (int rc = kc.slices.reserve((size_t)(n_tiles + 1) * n_runs)) return rc;
+    if (int rc = kc.merged_codes.reserve((size_t)M)) return rc;   // owners' codes at their merged place
+    if (int rc = kc.merged_counts.reserve((size_t)M)) return rc;  // ... their totals
+    if (int rc = kc.keep.reserve((size_t)M)) return rc;
+    if (int rc = kc.keep_scan.reserve((size_t)M)) return rc;
+    auto sort_samples = [&](void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_keys(tmp, bytes, kc.samples.ptr(), kc.bounds.ptr(), (size_t)n_s, 0, 64, st);
+    };
+    auto scan_keep = [&](void *tmp, size_t &bytes) {
+        return rocprim::inclusive_scan(tmp, bytes, kc.keep.ptr(), kc.keep_scan.ptr(), (size_t)M, rocprim::plus<int>(), st);
+    };
+    if (int rc = rocprim_reserve(kc.tmp, sort_samples, scan_keep)) return rc;  // (for both: nothing regrows under way)
+    HIP_TRY(hipMemcpyAsync(kc.run_off.ptr(), run_off, (size_t)(n_runs + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(kc.samp_pre.ptr(), samp_pre.data(), (size_t)(n_runs + 1) * 8, hipMemcpyHostToDevice, st));
     int trc = timing_begin(ctx, FDR_KERNEL_KMER_COMPACT, st);
     if (trc) return trc;
     if (n_s > 0) {
         hipLaunchKernelGGL(km_sample_kernel, dim3((unsigned)((n_s + 255) / 256)), dim3(256), 0, st, d_codes,
-                           (const long long *)d_roff, (const long long *)d_spre, (int)n_runs, n_s, (u64 *)ctx->ks_codes.p);
+                           kc.run_off.ptr(), kc.samp_pre.ptr(), (int)n_runs, n_s, kc.samples.ptr());
         HIP_TRY(hipGetLastError());
-        size_t tb = ctx->ks_tmp.cap;
-        HIP_TRY(rocprim::radix_sort_keys(ctx->ks_tmp.p, tb, (u64 *)ctx->ks_codes.p, (u64 *)ctx->ks_keys.p, (size_t)n_s,
-                                         0, 64, st));
+        if (int rc = rocprim_run(kc.tmp, "rocprim::radix_sort_keys", sort_samples)) return rc;
     }
     const long long nb = (n_tiles + 1) * n_runs;
-    hipLaunchKernelGGL(km_bounds_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, d_codes,
-                       (const long long *)d_roff, (const u64 *)ctx->ks_keys.p, n_tiles, (int)n_runs,
-                       (long long *)ctx->ks_idx.p);
+    hipLaunchKernelGGL(km_bounds_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, d_codes, kc.run_off.ptr(),
+                       kc.bounds.ptr(), n_tiles, (int)n_runs, kc.slices.ptr());
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(km_tile_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, d_codes, d_counts,
-                       (const long long *)d_roff, (const long long *)ctx->ks_idx.p, (int)n_runs, minc,
-                       (u64 *)ctx->kc_mk.p, (u64 *)ctx->kc_mv.p, (int *)ctx->ks_pos.p);
+    hipLaunchKernelGGL(km_tile_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, d_codes, d_counts, kc.run_off.ptr(),
+                       kc.slices.ptr(), (int)n_runs, minc, kc.merged_codes.ptr(), kc.merged_counts.ptr(), kc.keep.ptr());
     HIP_TRY(hipGetLastError());
-    size_t tb = ctx->ks_tmp.cap;
-    HIP_TRY(rocprim::inclusive_scan(ctx->ks_tmp.p, tb, (int *)ctx->ks_pos.p, (int *)ctx->ks_rows.p, (size_t)M,
-                                    rocprim::plus<int>(), st));
+    if (int rc = rocprim_run(kc.tmp, "rocprim::inclusive_scan", scan_keep)) return rc;
     int kept = 0;
-    HIP_TRY(hipMemcpyAsync(&kept, static_cast<int *>(ctx->ks_rows.p) + (M - 1), 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&kept, kc.keep_scan.ptr() + (M - 1), 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (kept > 0) {
-        if (int rc = ctx->ks_pairs2.reserve((size_t)kept * 8)) return rc;
-        if (int rc = ctx->kc_counts.reserve((size_t)kept * 8)) return rc;
+        if (int rc = kc.sorted.reserve((size_t)kept)) return rc;  // (no block is under way: the kept codes)
+        if (int rc = kc.kept_counts.reserve((size_t)kept)) return rc;
         hipLaunchKernelGGL(kc_compact64_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st,
-                           (const u64 *)ctx->kc_mk.p, (const u64 *)ctx->kc_mv.p, M, (const int *)ctx->ks_pos.p,
-                           (const int *)ctx->ks_rows.p, (u64 *)ctx->ks_pairs2.p, (u64 *)ctx->kc_counts.p);
+                           kc.merged_codes.ptr(), kc.merged_counts.ptr(), M, kc.keep.ptr(), kc.keep_scan.ptr(),
+                           kc.sorted.ptr(), kc.kept_counts.ptr());
         HIP_TRY(hipGetLastError());
     }
     if ((trc = timing_end(ctx, FDR_KERNEL_KMER_COMPACT, st))) return trc;
     HIP_TRY(hipStreamSynchronize(st));
-    ctx->kc_n = kept;
+    kc.n = kept;
     *n_out = kept;
     return FDR_OK;
 }
@@ -1096,11 +1081,12 @@ FDR_EXPORT int fdr_kmer_count_merge(fdr_ctx *ctx, int32_t n_runs, const int64_t 
     const int64_t M = run_off[n_runs];
     if (M > 0 && (!codes || !counts)) return fail(FDR_E_ARG, "fdr_kmer_count_merge: null input");
     hipStream_t st = ctx->stream;
-    if (M > 0) {  // (the accumulated-table buffers hold the inputs: the merge replaces that table anyway)
-        if (int rc = ctx->kc_a0.reserve((size_t)M * 8)) return rc;
-        if (int rc = ctx->kc_c0.reserve((size_t)M * 8)) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->kc_a0.p, codes, (size_t)M * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ctx->kc_c0.p, counts, (size_t)M * 8, hipMemcpyHostToDevice, st));
+    DevArray<u64> &d_codes = ctx->kc.acc_codes[0], &d_counts = ctx->kc.acc_counts[0];  // (the merge replaces that table anyway)
+    if (M > 0) {
+        if (int rc = d_codes.reserve((size_t)M)) return rc;
+        if (int rc = d_counts.reserve((size_t)M)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_codes.ptr(), codes, (size_t)M * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_counts.ptr(), counts, (size_t)M * 8, hipMemcpyHostToDevice, st));
     }
-    return km_merge(ctx, n_runs, run_off, (const u64 *)ctx->kc_a0.p, (const u64 *)ctx->kc_c0.p, min_count, n_out, st);
+    return km_merge(ctx, n_runs, run_off, d_codes.ptr(), d_counts.ptr(), min_count, n_out, st);
 }

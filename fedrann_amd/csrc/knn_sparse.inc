@@ -45,9 +45,13 @@
 // Cost model: the same sum over features of df_f^2 pair updates, each reading a 4-byte posting entry (the row only).
 //
 // The index and its searches.  S1 (S1j), the sort and S2 are the BUILD (fdr_sparse_index_build): what they leave in
-// the context's sp_* buffers -- the rows (indptr, each stored entry's run id, xhat or the set sizes), the postings
-// (run offsets, rows, values) and the zero flags (sp_zero, the index's own: ctx->zero belongs to the dense calls) --
-// is the context's one sparse index, described by ctx->spx.  S4, S3 and S3r are a SEARCH (fdr_sparse_index_search) of
+// ctx->sp (struct SparseIndex, fedrann_hip.hip: one typed array per buffer) -- the rows (indptr, each stored entry's
+// run id efeat, xhat or the set sizes asize), the postings (runptr, posting_rows(), pval) and the zero flags (zero, the
+// index's own: ctx->zero belongs to the dense calls) -- is the context's one sparse index, described by sp.built; the
+// build's scratch (keys, sorted_keys, sorted_pos, tmp) is kept with it.  Two arrays change their contents on the way and
+// a third is cut up: the accessors run_flags() / run_numbers(), posting_rows() and zidx() / zdist() of the struct hold
+// the casts and say why the first contents are dead by then.  release() frees the arrays and forgets the index in one
+// place (fdr_sparse_index_free).  S4, S3 and S3r are a SEARCH (fdr_sparse_index_search) of
 // the query rows [q_lo, q_hi) against all n rows: S3's grid is the range, the heavy list and its counter are reset per
 // search, and row q - q_lo of the result buffers (sized by the range) is query q.  fdr_knn_sparse[_metric] is a build
 // and a search of [0, n) through the same two functions.
@@ -420,50 +424,39 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-// every device buffer of the sparse path but the shared result buffers (ctx->idx, ctx->dist)
-static std::array<DevBuf *, 16> sp_buffers(fdr_ctx *ctx) {
-    return {&ctx->sp_ip,  &ctx->sp_ix,    &ctx->sp_val,  &ctx->sp_xhat,   &ctx->sp_keys,  &ctx->sp_keys2,
-            &ctx->sp_pos, &ctx->sp_pos2,  &ctx->sp_efeat, &ctx->sp_pval,  &ctx->sp_runptr, &ctx->sp_heavy,
-            &ctx->sp_cnt, &ctx->sp_tmp,   &ctx->sp_asize, &ctx->sp_zero};
-}
-
 // S3 over the queries [q_lo, q_lo + nq), then S3r over the queries it handed on; h = their number, and the zero
-// (empty) rows among the queries
+// (empty) rows among the queries.  d_idx / d_dist: [nq, k] results on the device.
 template <int METRIC>
-static int sp_search(fdr_ctx *ctx, int64_t n, int32_t k, int64_t q_lo, int64_t nq, const int *zidx, const float *zdist,
-                     u64 *cnt, u64 (&h)[2]) {
+static int sp_search(fdr_ctx *ctx, int64_t n, int32_t k, int64_t q_lo, int64_t nq, int *d_idx, float *d_dist, u64 (&h)[2]) {
     const hipStream_t st = ctx->stream;
+    SparseIndex &sp = ctx->sp;
     constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;
     static_assert(SP_CNT_ZEROQ == SP_CNT_HEAVY + 1, "one read-back for both");
-    const float *xhat = JAC ? nullptr : (const float *)ctx->sp_xhat.p;
-    const float *pval = JAC ? nullptr : (const float *)ctx->sp_pval.p;
-    const int *asize = JAC ? (const int *)ctx->sp_asize.p : nullptr;
-    hipLaunchKernelGGL((knn_sparse_kernel<false, METRIC>), dim3((unsigned)nq), dim3(64), 0, st, (long long)n,
-                       (long long)q_lo, (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_efeat.p, xhat,
-                       (const long long *)ctx->sp_runptr.p, (const int *)ctx->sp_pos.p, pval, asize,
-                       (const unsigned char *)ctx->sp_zero.p, (int)k, zidx, zdist, (int *)ctx->sp_heavy.p, cnt,
-                       (int *)ctx->idx.p, (float *)ctx->dist.p);
+    auto launch = [&](auto range, unsigned grid) {  // S3 (std::false_type) or S3r (std::true_type)
+        hipLaunchKernelGGL((knn_sparse_kernel<decltype(range)::value, METRIC>), dim3(grid), dim3(64), 0, st, (long long)n,
+                           (long long)q_lo, sp.indptr.ptr(), sp.efeat.ptr(), JAC ? nullptr : sp.xhat.ptr(),
+                           sp.runptr.ptr(), sp.posting_rows(), JAC ? nullptr : sp.pval.ptr(),
+                           JAC ? sp.asize.ptr() : nullptr, sp.zero.ptr(), (int)k, sp.zidx(), sp.zdist(), sp.heavy.ptr(),
+                           sp.cnt.ptr(), d_idx, d_dist);
+    };
+    launch(std::false_type{}, (unsigned)nq);
     HIP_TRY(hipGetLastError());
     h[0] = h[1] = 0;
-    HIP_TRY(hipMemcpyAsync(h, cnt + SP_CNT_HEAVY, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h, sp.cnt.ptr() + SP_CNT_HEAVY, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (h[0] > 0) {
-        hipLaunchKernelGGL((knn_sparse_kernel<true, METRIC>), dim3((unsigned)h[0]), dim3(64), 0, st, (long long)n,
-                           (long long)q_lo, (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_efeat.p, xhat,
-                           (const long long *)ctx->sp_runptr.p, (const int *)ctx->sp_pos.p, pval, asize,
-                           (const unsigned char *)ctx->sp_zero.p, (int)k, zidx, zdist, (int *)ctx->sp_heavy.p, cnt,
-                           (int *)ctx->idx.p, (float *)ctx->dist.p);
+        launch(std::true_type{}, (unsigned)h[0]);
         HIP_TRY(hipGetLastError());
     }
     return FDR_OK;
 }
 
-// The build: the argument checks, the upload, S1 (S1j), the sort, the run flags and scan, S2.  ctx->spx describes the
+// The build: the argument checks, the upload, S1 (S1j), the sort, the run flags and scan, S2.  sp.built describes the
 // index once everything is enqueued; a refused or failed build leaves none.  `who` names the entry point in messages.
 static int sp_build(fdr_ctx *ctx, const char *who, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
                     const int32_t *indices, const float *values) {
     int rc;
-    ctx->spx = {};
+    ctx->sp.built = {};
     const bool jac = metric == FDR_METRIC_JACCARD;
     if (!jac && metric != FDR_METRIC_COSINE)
         return fail(FDR_E_ARG, "%s: unknown metric %d (FDR_METRIC_COSINE, FDR_METRIC_JACCARD)", who, metric);
@@ -479,41 +472,38 @@ static int sp_build(fdr_ctx *ctx, const char *who, int32_t metric, int64_t n, in
     if (nnz > INT32_MAX) return fail(FDR_E_ARG, "%s: %lld stored entries (at most 2^31 - 1)", who, (long long)nnz);
     if (nnz > 0 && !indices) return fail(FDR_E_ARG, "%s: indices is null", who);
     const hipStream_t st = ctx->stream;
+    SparseIndex &sp = ctx->sp;
     const size_t m1 = (size_t)std::max<int64_t>(nnz, 1);
-    if ((rc = ctx->sp_ip.reserve((size_t)(n + 1) * 8))) return rc;
-    if ((rc = ctx->sp_ix.reserve(m1 * 4))) return rc;
-    if (values && (rc = ctx->sp_val.reserve(m1 * 4))) return rc;
-    if (!jac && (rc = ctx->sp_xhat.reserve(m1 * 4))) return rc;
-    if (jac && (rc = ctx->sp_asize.reserve((size_t)n * 4))) return rc;
-    if ((rc = ctx->sp_keys.reserve(m1 * 8))) return rc;
-    if ((rc = ctx->sp_keys2.reserve(m1 * 8))) return rc;
-    if ((rc = ctx->sp_pos.reserve(m1 * 4))) return rc;
-    if ((rc = ctx->sp_pos2.reserve(m1 * 4))) return rc;
-    if ((rc = ctx->sp_efeat.reserve(m1 * 4))) return rc;
-    if (!jac && (rc = ctx->sp_pval.reserve(m1 * 4))) return rc;
-    if ((rc = ctx->sp_runptr.reserve((m1 + 1) * 8))) return rc;
-    if ((rc = ctx->sp_heavy.reserve((size_t)n * 4))) return rc;
-    if ((rc = ctx->sp_cnt.reserve(64 + (size_t)FDR_MAX_K * 8))) return rc;
-    if ((rc = ctx->sp_zero.reserve((size_t)n))) return rc;
-    u64 *cnt = (u64 *)ctx->sp_cnt.p;
-    HIP_TRY(hipMemcpyAsync(ctx->sp_ip.p, indptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+    if ((rc = sp.indptr.reserve((size_t)(n + 1)))) return rc;
+    if ((rc = sp.indices.reserve(m1))) return rc;
+    if (values && (rc = sp.values.reserve(m1))) return rc;
+    if (!jac && (rc = sp.xhat.reserve(m1))) return rc;
+    if (jac && (rc = sp.asize.reserve((size_t)n))) return rc;
+    if ((rc = sp.keys.reserve(m1))) return rc;
+    if ((rc = sp.sorted_keys.reserve(m1))) return rc;
+    if ((rc = sp.pos.reserve(m1))) return rc;
+    if ((rc = sp.sorted_pos.reserve(m1))) return rc;
+    if ((rc = sp.efeat.reserve(m1))) return rc;
+    if (!jac && (rc = sp.pval.reserve(m1))) return rc;
+    if ((rc = sp.runptr.reserve(m1 + 1))) return rc;
+    if ((rc = sp.heavy.reserve((size_t)n))) return rc;
+    if ((rc = sp.cnt.reserve(SparseIndex::cnt_words))) return rc;
+    if ((rc = sp.zero.reserve((size_t)n))) return rc;
+    u64 *cnt = sp.cnt.ptr();
+    HIP_TRY(hipMemcpyAsync(sp.indptr.ptr(), indptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     if (nnz > 0) {
-        HIP_TRY(hipMemcpyAsync(ctx->sp_ix.p, indices, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-        if (values) HIP_TRY(hipMemcpyAsync(ctx->sp_val.p, values, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(sp.indices.ptr(), indices, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+        if (values) HIP_TRY(hipMemcpyAsync(sp.values.ptr(), values, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipMemsetAsync(cnt, 0, 64, st));
     if (jac) {
         hipLaunchKernelGGL(sp_rows_jaccard_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n,
-                           (long long)n_features, (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_ix.p,
-                           values ? (const float *)ctx->sp_val.p : nullptr, (int *)ctx->sp_asize.p,
-                           (u64 *)ctx->sp_keys.p, (unsigned *)ctx->sp_pos.p, (int *)ctx->sp_efeat.p,
-                           (unsigned char *)ctx->sp_zero.p, cnt);
+                           (long long)n_features, sp.indptr.ptr(), sp.indices.ptr(), values ? sp.values.ptr() : nullptr,
+                           sp.asize.ptr(), sp.keys.ptr(), sp.pos.ptr(), sp.efeat.ptr(), sp.zero.ptr(), cnt);
     } else {
         hipLaunchKernelGGL(sp_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n,
-                           (long long)n_features, (const long long *)ctx->sp_ip.p, (const int *)ctx->sp_ix.p,
-                           values ? (const float *)ctx->sp_val.p : nullptr, (float *)ctx->sp_xhat.p,
-                           (u64 *)ctx->sp_keys.p, (unsigned *)ctx->sp_pos.p, (int *)ctx->sp_efeat.p,
-                           (unsigned char *)ctx->sp_zero.p, cnt);
+                           (long long)n_features, sp.indptr.ptr(), sp.indices.ptr(), values ? sp.values.ptr() : nullptr,
+                           sp.xhat.ptr(), sp.keys.ptr(), sp.pos.ptr(), sp.efeat.ptr(), sp.zero.ptr(), cnt);
     }
     HIP_TRY(hipGetLastError());
     u64 h_cnt[3];
@@ -528,36 +518,30 @@ static int sp_build(fdr_ctx *ctx, const char *who, int32_t metric, int64_t n, in
     if (kept > 0) {
         int end_bit = 32;
         while (end_bit < 64 && ((u64)n_features >> (end_bit - 32)) != 0) ++end_bit;  // (the sentinel F << 32 too)
-        size_t t_sort = 0, t_scan = 0;
-        (void)rocprim::radix_sort_pairs(nullptr, t_sort, (u64 *)nullptr, (u64 *)nullptr, (unsigned *)nullptr,
-                                        (unsigned *)nullptr, (size_t)nnz, 0, end_bit, (hipStream_t) nullptr);
-        (void)rocprim::inclusive_scan(nullptr, t_scan, (int *)nullptr, (int *)nullptr, (size_t)kept,
-                                      rocprim::plus<int>(), (hipStream_t) nullptr);
-        if ((rc = ctx->sp_tmp.reserve(std::max(t_sort, t_scan)))) return rc;
-        size_t tb = ctx->sp_tmp.cap;
-        HIP_TRY(rocprim::radix_sort_pairs(ctx->sp_tmp.p, tb, (u64 *)ctx->sp_keys.p, (u64 *)ctx->sp_keys2.p,
-                                          (unsigned *)ctx->sp_pos.p, (unsigned *)ctx->sp_pos2.p, (size_t)nnz, 0,
-                                          end_bit, st));
-        // the unsorted keys are free now: run-start flags and inclusive run numbers (two int32 per entry fit)
-        int *flag = (int *)ctx->sp_keys.p, *run_incl = flag + kept;
+        int *flag = sp.run_flags(), *run_incl = sp.run_numbers(kept);
+        auto sort = [&](void *tmp, size_t &bytes) {
+            return rocprim::radix_sort_pairs(tmp, bytes, sp.keys.ptr(), sp.sorted_keys.ptr(), sp.pos.ptr(),
+                                             sp.sorted_pos.ptr(), (size_t)nnz, 0, end_bit, st);
+        };
+        auto scan = [&](void *tmp, size_t &bytes) {
+            return rocprim::inclusive_scan(tmp, bytes, flag, run_incl, (size_t)kept, rocprim::plus<int>(), st);
+        };
+        if ((rc = rocprim_reserve(sp.tmp, sort, scan))) return rc;  // (sized for both: the scan never regrows it)
+        if ((rc = rocprim_run(sp.tmp, "rocprim::radix_sort_pairs", sort))) return rc;
         const unsigned g = (unsigned)((kept + 255) / 256);
-        hipLaunchKernelGGL(sp_run_flags_kernel, dim3(g), dim3(256), 0, st, kept, (const u64 *)ctx->sp_keys2.p, flag);
+        hipLaunchKernelGGL(sp_run_flags_kernel, dim3(g), dim3(256), 0, st, kept, sp.sorted_keys.ptr(), flag);
         HIP_TRY(hipGetLastError());
-        tb = ctx->sp_tmp.cap;
-        HIP_TRY(rocprim::inclusive_scan(ctx->sp_tmp.p, tb, flag, run_incl, (size_t)kept, rocprim::plus<int>(), st));
-        // posting rows go where the unsorted positions were
-        hipLaunchKernelGGL(sp_postings_kernel, dim3(g), dim3(256), 0, st, kept, (const u64 *)ctx->sp_keys2.p,
-                           (const unsigned *)ctx->sp_pos2.p, (const int *)run_incl,
-                           jac ? nullptr : (const float *)ctx->sp_xhat.p, (int *)ctx->sp_efeat.p,
-                           (int *)ctx->sp_pos.p, jac ? nullptr : (float *)ctx->sp_pval.p,
-                           (long long *)ctx->sp_runptr.p);
+        if ((rc = rocprim_run(sp.tmp, "rocprim::inclusive_scan", scan))) return rc;
+        hipLaunchKernelGGL(sp_postings_kernel, dim3(g), dim3(256), 0, st, kept, sp.sorted_keys.ptr(),
+                           sp.sorted_pos.ptr(), run_incl, jac ? nullptr : sp.xhat.ptr(), sp.efeat.ptr(),
+                           sp.posting_rows(), jac ? nullptr : sp.pval.ptr(), sp.runptr.ptr());
         HIP_TRY(hipGetLastError());
     }
-    ctx->spx.valid = true;
-    ctx->spx.metric = metric;
-    ctx->spx.n = n;
-    ctx->spx.kept = kept;
-    ctx->spx.nzero = (long long)h_cnt[SP_CNT_ZERO];
+    sp.built.valid = true;
+    sp.built.metric = metric;
+    sp.built.n = n;
+    sp.built.kept = kept;
+    sp.built.nzero = (long long)h_cnt[SP_CNT_ZERO];
     return FDR_OK;
 }
 
@@ -566,28 +550,29 @@ static int sp_build(fdr_ctx *ctx, const char *who, int32_t metric, int64_t n, in
 static int sp_search_range(fdr_ctx *ctx, int32_t k, int64_t q_lo, int64_t q_hi, int32_t *idx_out, float *dist_out) {
     int rc;
     const hipStream_t st = ctx->stream;
-    const int64_t n = ctx->spx.n, nq = q_hi - q_lo;
+    SparseIndex &sp = ctx->sp;
+    const int64_t n = sp.built.n, nq = q_hi - q_lo;
     u64 h[2] = {0, 0};  // queries that took S3r; zero (empty) rows among the queries
     if (nq > 0) {
         if ((rc = ctx->idx.reserve((size_t)nq * k * 4))) return rc;
         if ((rc = ctx->dist.reserve((size_t)nq * k * 4))) return rc;
-        u64 *cnt = (u64 *)ctx->sp_cnt.p;
-        int *zidx = (int *)((char *)ctx->sp_cnt.p + 64);
-        float *zdist = (float *)((char *)ctx->sp_cnt.p + 64 + FDR_MAX_K * 4);
-        HIP_TRY(hipMemsetAsync(cnt + SP_CNT_HEAVY, 0, 16, st));  // (the heavy list's counter and the zero queries')
-        if (ctx->spx.nzero > 0) {  // (S4 depends on k: per search)
-            hipLaunchKernelGGL(sp_zero_row_kernel, dim3(1), dim3(64), 0, st, (long long)n,
-                               (const unsigned char *)ctx->sp_zero.p, (int)k, zidx, zdist);
+        // (the result buffers are the dense calls' untyped ones, shared with them)
+        int *d_idx = static_cast<int *>(ctx->idx.p);
+        float *d_dist = static_cast<float *>(ctx->dist.p);
+        HIP_TRY(hipMemsetAsync(sp.cnt.ptr() + SP_CNT_HEAVY, 0, 16, st));  // (the heavy list's counter and the zero queries')
+        if (sp.built.nzero > 0) {  // (S4 depends on k: per search)
+            hipLaunchKernelGGL(sp_zero_row_kernel, dim3(1), dim3(64), 0, st, (long long)n, sp.zero.ptr(), (int)k,
+                               sp.zidx(), sp.zdist());
             HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(sp_count_zero_kernel, dim3((unsigned)((nq + 4095) / 4096)), dim3(256), 0, st,
-                               (long long)q_lo, (long long)q_hi, (const unsigned char *)ctx->sp_zero.p, cnt);
+                               (long long)q_lo, (long long)q_hi, sp.zero.ptr(), sp.cnt.ptr());
             HIP_TRY(hipGetLastError());
         }
-        rc = ctx->spx.metric == FDR_METRIC_JACCARD ? sp_search<FDR_METRIC_JACCARD>(ctx, n, k, q_lo, nq, zidx, zdist, cnt, h)
-                                                   : sp_search<FDR_METRIC_COSINE>(ctx, n, k, q_lo, nq, zidx, zdist, cnt, h);
+        rc = sp.built.metric == FDR_METRIC_JACCARD ? sp_search<FDR_METRIC_JACCARD>(ctx, n, k, q_lo, nq, d_idx, d_dist, h)
+                                                   : sp_search<FDR_METRIC_COSINE>(ctx, n, k, q_lo, nq, d_idx, d_dist, h);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(idx_out, ctx->idx.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(dist_out, ctx->dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(idx_out, d_idx, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(dist_out, d_dist, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     fdr_knn_trace &t = ctx->last.trace;
@@ -606,7 +591,7 @@ static int sp_knn(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, c
     int rc = use_device(ctx);
     if (rc) return rc;
     knn_call_begin(ctx);
-    ctx->spx = {};  // (the call replaces the context's index, also where it is refused before the build)
+    ctx->sp.built = {};  // (the call replaces the context's index, also where it is refused before the build)
     if (metric != FDR_METRIC_JACCARD && metric != FDR_METRIC_COSINE)
         return fail(FDR_E_ARG, "knn_sparse: unknown metric %d (FDR_METRIC_COSINE, FDR_METRIC_JACCARD)", metric);
     if (!indptr || !idx_out || !dist_out) return fail(FDR_E_ARG, "knn_sparse: null pointer");
@@ -633,9 +618,9 @@ FDR_EXPORT int fdr_sparse_index_build(fdr_ctx *ctx, int32_t metric, int64_t n, i
     int rc = use_device(ctx);
     if (rc) return rc;
     if ((rc = sp_build(ctx, "sparse_index_build", metric, n, n_features, indptr, indices, values))) return rc;
-    ctx->spx.valid = false;
+    ctx->sp.built.valid = false;
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // (a failure of the sort or of S2 belongs to this call: no index)
-    ctx->spx.valid = true;
+    ctx->sp.built.valid = true;
     return FDR_OK;
 }
 
@@ -644,8 +629,8 @@ FDR_EXPORT int fdr_sparse_index_search(fdr_ctx *ctx, int32_t k, int64_t q_lo, in
     int rc = use_device(ctx);
     if (rc) return rc;
     knn_call_begin(ctx);
-    if (!ctx->spx.valid) return fail(FDR_E_STATE, "sparse_index_search: the context holds no sparse index");
-    const int64_t n = ctx->spx.n;
+    if (!ctx->sp.built.valid) return fail(FDR_E_STATE, "sparse_index_search: the context holds no sparse index");
+    const int64_t n = ctx->sp.built.n;
     if (k < 1 || k > FDR_MAX_K || k > n)
         return fail(FDR_E_ARG, "sparse_index_search: k=%d unsupported (1..min(%d, n = %lld))", k, FDR_MAX_K, (long long)n);
     if (q_lo < 0 || q_hi < q_lo || q_hi > n)
@@ -658,14 +643,13 @@ FDR_EXPORT int fdr_sparse_index_search(fdr_ctx *ctx, int32_t k, int64_t q_lo, in
 FDR_EXPORT int fdr_sparse_index_info(fdr_ctx *ctx, int32_t *metric, int64_t *n, int64_t *postings, int64_t *zero_rows,
                                      size_t *device_bytes) {
     if (!ctx) return fail(FDR_E_ARG, "null context");
-    if (!ctx->spx.valid) return fail(FDR_E_STATE, "sparse_index_info: the context holds no sparse index");
-    if (metric) *metric = ctx->spx.metric;
-    if (n) *n = ctx->spx.n;
-    if (postings) *postings = ctx->spx.kept;
-    if (zero_rows) *zero_rows = ctx->spx.nzero;
+    if (!ctx->sp.built.valid) return fail(FDR_E_STATE, "sparse_index_info: the context holds no sparse index");
+    if (metric) *metric = ctx->sp.built.metric;
+    if (n) *n = ctx->sp.built.n;
+    if (postings) *postings = ctx->sp.built.kept;
+    if (zero_rows) *zero_rows = ctx->sp.built.nzero;
     if (device_bytes) {
-        *device_bytes = 0;
-        for (const DevBuf *b : sp_buffers(ctx)) *device_bytes += b->cap;
+        *device_bytes = ctx->sp.bytes();
     }
     return FDR_OK;
 }
@@ -674,7 +658,6 @@ FDR_EXPORT int fdr_sparse_index_free(fdr_ctx *ctx) {
     int rc = use_device(ctx);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->spx = {};
-    for (DevBuf *b : sp_buffers(ctx)) b->release();
+    ctx->sp.release();
     return FDR_OK;
 }
