@@ -24,6 +24,7 @@ SYMBOLS = (
     "fdr_kmer_output_append", "fdr_last_query_paths", "fdr_last_knn_trace", "fdr_kmer_count_export_dev",
     "fdr_kmer_count_merge_dev", "fdr_kmer_count_merge", "fdr_set_knn_capture", "fdr_last_candidates",
     "fdr_last_range_sets", "fdr_knn_sparse", "fdr_set_live_chunks", "fdr_knn_sparse_metric",
+    "fdr_set_live_skip", "fdr_last_live_stage_lists",
     "fdr_sparse_index_build", "fdr_sparse_index_search", "fdr_sparse_index_info", "fdr_sparse_index_free",
 )
 FDR_MAX_K = 128
@@ -36,7 +37,7 @@ PATH_CERTIFIED, PATH_RANGE, PATH_EXACT, PATH_ZERO, PATH_RANGE_OVERFLOW, PATH_GEN
 TRACE_KINDS = ("none", "exact", "prefilter", "generic", "sparse")
 FALLBACKS = ("none", "chunked", "whole")
 # fdr_set_knn_capture (include/fedrann_hip.h: FDR_CAPTURE_*, FDR_RANGE_CAP)
-CAPTURE_CANDIDATES, CAPTURE_RANGE = 1, 2
+CAPTURE_CANDIDATES, CAPTURE_RANGE, CAPTURE_LIVE_LISTS = 1, 2, 4
 RANGE_CAP = 1024
 # fdr_knn_sparse_metric (include/fedrann_hip.h: FDR_METRIC_*)
 METRIC_COSINE, METRIC_JACCARD = 0, 1
@@ -52,7 +53,8 @@ class KnnTrace(ctypes.Structure):
             "pass_segments", "uncertified", "zero_queries", "range_queries", "range_chunks", "range_pp_chunks",
             "range_w8_chunks", "range_overflow", "exact_fallback", "exact_calls", "exact_queries", "exact_waves",
             "exact_qsets", "generic", "exact_segments", "pass_live", "pass_live_items_2", "pass_live_items_3",
-            "pass_live_items_4", "pass_live_items_5", "pass_live_items_6", "pass_live_dense_items")]
+            "pass_live_items_4", "pass_live_items_5", "pass_live_items_6", "pass_live_dense_items", "skip_live")] + \
+        [(n, ctypes.c_int64) for n in ("skip_stages_walked", "skip_stages_skipped")]
 
 
 class FedrannHipError(RuntimeError):
@@ -128,6 +130,8 @@ def load_library():
     L.fdr_last_range_sets.argtypes = [vp, i64, vp, vp, vp, vp]
     L.fdr_set_dedup_mode.argtypes = [vp, ctypes.c_int]
     L.fdr_set_live_chunks.argtypes = [vp, ctypes.c_int]
+    L.fdr_set_live_skip.argtypes = [vp, ctypes.c_int]
+    L.fdr_last_live_stage_lists.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp]
     L.fdr_last_unique.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     L.fdr_last_prefilter_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     p64 = ctypes.POINTER(ctypes.c_int64)
@@ -466,6 +470,26 @@ class Context:
         code = {"auto": 0, "off": 1, "force": 2}[mode]
         self._check(self._L.fdr_set_live_chunks(self._h, code), "fdr_set_live_chunks")
 
+    def set_live_skip(self, mode):
+        """Stage skipping of the live-chunk pass: "auto" (default: on whenever that pass runs) or "off" -- same
+        results, see include/fedrann_hip.h."""
+        code = {"auto": 0, "off": 1}[mode]
+        self._check(self._L.fdr_set_live_skip(self._h, code), "fdr_set_live_skip")
+
+    def last_live_stage_lists(self, segment):
+        """Test support: (first row, lens int32 [256], lists uint16 [256, stages]) of one target segment of the last
+        live-chunk pass -- the segment's first row in the scan order and, per query-block mask value, the stages of 128
+        rows a block of that mask walks (0xffff behind a list's end).  Needs CAPTURE_LIVE_LISTS set during the call."""
+        first, nst = ctypes.c_int32(), ctypes.c_int32()
+        lens = np.empty(256, dtype=np.int32)
+        self._check(self._L.fdr_last_live_stage_lists(self._h, int(segment), ctypes.byref(first), ctypes.byref(nst),
+                                                      lens.ctypes.data, None), "fdr_last_live_stage_lists")
+        lists = np.empty((256, nst.value), dtype=np.uint16)
+        if nst.value:
+            self._check(self._L.fdr_last_live_stage_lists(self._h, int(segment), None, ctypes.byref(nst), None,
+                                                          lists.ctypes.data), "fdr_last_live_stage_lists")
+        return first.value, lens, lists
+
     def kmer_search(self, seqs, seq_off, lib_codes, k):
         """Per-read ascending unique library indices: (indptr int64 [R+1], indices int32 [nnz])."""
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
@@ -597,7 +621,7 @@ class Context:
         return out
 
     def set_knn_capture(self, what):
-        """Or of CAPTURE_CANDIDATES / CAPTURE_RANGE (0: off): fdr_set_knn_capture.  Test support."""
+        """Or of CAPTURE_CANDIDATES / CAPTURE_RANGE / CAPTURE_LIVE_LISTS (0: off): fdr_set_knn_capture.  Test support."""
         self._check(self._L.fdr_set_knn_capture(self._h, int(what)), "fdr_set_knn_capture")
 
     def last_candidates(self, n_queries, kp):

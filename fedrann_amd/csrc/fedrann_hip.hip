@@ -534,6 +534,13 @@ struct KnnCallRecord {
         hipStream_t stream = nullptr;
     } paths;
     fdr_knn_trace trace = {};  // fdr_last_knn_trace: the kernels the call ran
+    // fdr_last_live_stage_lists: the geometry of the live-chunk pass's stage lists (the lists themselves: cap.lists)
+    struct {
+        int nseg = 0;  // 0: nothing recorded
+        int nt = 0;
+        SegBounds segs;
+        hipStream_t stream = nullptr;
+    } skip;
 };
 
 // The arguments of a k-NN call: nq query rows against nt target rows numbered from t_base, k neighbours each.
@@ -694,6 +701,8 @@ struct fdr_ctx {
     int dedup_mode = FDR_DEDUP_AUTO;
     int live_mode = FDR_LIVE_AUTO;  // fdr_set_live_chunks
     std::vector<unsigned> live_host;  // the live-chunk plan's read-back: the query blocks' masks
+    int skip_mode = FDR_SKIP_AUTO;    // fdr_set_live_skip
+    std::vector<int> skip_host;       // ... and the lengths of the stage lists, [segment][mask value]
     KnnCallRecord last;  // what the fdr_last_* getters report
     // fdr_set_knn_capture / fdr_last_candidates / fdr_last_range_sets: the prefilter pass's intermediate results
     struct {
@@ -702,6 +711,7 @@ struct fdr_ctx {
         int64_t nq = 0, n_range = 0;
         int kp = 0, qbits = 0;
         DevBuf cand, rq, rtheta, rcnt, rrows;  // ctx-owned copies: [nq, kp] keys; per range query id, theta, count, rows
+        DevBuf lists;                          // ... and the live-chunk pass's stage lists (FDR_CAPTURE_LIVE_LISTS)
         hipStream_t stream = nullptr;
     } cap;
     // duplicate-row classes built by fdr_knn_classes_dev for the calls that follow it (fdr_knn_unique_dev /
@@ -726,6 +736,7 @@ struct fdr_ctx {
 static void knn_call_begin(fdr_ctx *ctx) {
     ctx->last.trace = fdr_knn_trace{};
     ctx->last.paths = {};
+    ctx->last.skip.nseg = 0;
     ctx->cap.cand_valid = ctx->cap.range_valid = false;
     ctx->cap.nq = ctx->cap.n_range = 0;
 }
@@ -872,7 +883,7 @@ FDR_EXPORT int fdr_last_knn_trace(fdr_ctx *ctx, fdr_knn_trace *out) {
 }
 
 FDR_EXPORT int fdr_set_knn_capture(fdr_ctx *ctx, int what) {
-    if (!ctx || what < 0 || what > (FDR_CAPTURE_CANDIDATES | FDR_CAPTURE_RANGE)) return fail(FDR_E_ARG, "bad capture flags");
+    if (!ctx || what < 0 || what > (FDR_CAPTURE_CANDIDATES | FDR_CAPTURE_RANGE | FDR_CAPTURE_LIVE_LISTS)) return fail(FDR_E_ARG, "bad capture flags");
     ctx->cap.what = what;
     return FDR_OK;
 }
@@ -926,6 +937,37 @@ FDR_EXPORT int fdr_set_dedup_mode(fdr_ctx *ctx, int mode) {
 FDR_EXPORT int fdr_set_live_chunks(fdr_ctx *ctx, int mode) {
     if (!ctx || mode < FDR_LIVE_AUTO || mode > FDR_LIVE_FORCE) return fail(FDR_E_ARG, "bad live-chunk mode");
     ctx->live_mode = mode;
+    return FDR_OK;
+}
+
+FDR_EXPORT int fdr_set_live_skip(fdr_ctx *ctx, int mode) {
+    if (!ctx || mode < FDR_SKIP_AUTO || mode > FDR_SKIP_OFF) return fail(FDR_E_ARG, "bad stage-skip mode");
+    ctx->skip_mode = mode;
+    return FDR_OK;
+}
+
+FDR_EXPORT int fdr_last_live_stage_lists(fdr_ctx *ctx, int32_t segment, int32_t *first_row_out, int32_t *nstages_out,
+                                         int32_t *lens, uint16_t *lists) {
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    const auto &rec = ctx->last.skip;
+    if (rec.nseg <= 0)
+        return fail(FDR_E_STATE, "last_live_stage_lists: the last k-NN call captured no live-chunk pass's stage lists");
+    if (segment < 0 || segment >= rec.nseg || !nstages_out)
+        return fail(FDR_E_ARG, "last_live_stage_lists: bad argument (the pass had %d segments)", rec.nseg);
+    const int t_begin = rec.segs.b[segment], t_end = std::min(rec.nt, rec.segs.b[segment + 1]);
+    const int nstages = t_end > t_begin ? (t_end - t_begin + 127) >> 7 : 0;
+    *nstages_out = nstages;
+    if (first_row_out) *first_row_out = t_begin;
+    if (lens) memcpy(lens, ctx->skip_host.data() + (size_t)segment * 256, 256 * sizeof(int));
+    if (!lists || nstages == 0) return FDR_OK;
+    const int stride = live_list_stride(nstages);
+    HIP_TRY(hipMemcpy2DAsync(lists, (size_t)nstages * 2, static_cast<const uint16_t *>(ctx->cap.lists.p) + (size_t)live_stage_row(t_begin, segment) * 256,
+                             (size_t)stride * 2, (size_t)nstages * 2, 256, hipMemcpyDeviceToHost, rec.stream));
+    HIP_TRY(hipStreamSynchronize(rec.stream));
+    for (int v = 0; v < 256; ++v)  // (the entries behind a list's end hold whatever the workspace held)
+        for (int i = std::max(0, std::min(ctx->skip_host[(size_t)segment * 256 + v], nstages)); i < nstages; ++i)
+            lists[(size_t)v * nstages + i] = 0xffffu;
     return FDR_OK;
 }
 
@@ -1325,6 +1367,18 @@ int PrefilterCall::setup() {
         };
         int orc;
         if ((orc = order(a.That, nt, L.perm_t, ho_t))) return orc;
+        if (L.live) {  // the stages' masks, while the sorted keys are the targets'; the lists a block of each mask value walks
+            int max_stages = 1;
+            for (int i = 0; i < p.nseg; ++i)
+                max_stages = std::max(max_stages, (std::min<int>((int)nt, p.segs.b[i + 1]) - p.segs.b[i] + 127) >> 7);
+            hipLaunchKernelGGL(live_stage_masks_kernel, dim3((unsigned)max_stages, (unsigned)p.nseg), dim3(64), 0, st,
+                               (const u64 *)L.okeys_s, (int)nt, p.segs, L.live_smask);
+            const int all = !(FDR_SKIP_AUTO_ON && ctx->skip_mode == FDR_SKIP_AUTO);
+            hipLaunchKernelGGL(live_stage_lists_kernel, dim3(256, (unsigned)p.nseg), dim3(64), 0, st,
+                               (const uint8_t *)L.live_smask, (int)nt, p.segs, all, L.live_lists, L.live_lens);
+            HIP_TRY(hipGetLastError());
+            ctx->last.trace.skip_live = !all;
+        }
         if (!self && (orc = order(a.Qhat, nq, L.perm_q, ho_q))) return orc;
         ord.perm_t = L.perm_t;
         p1_t = ho_t;
@@ -1371,7 +1425,20 @@ int PrefilterCall::pass_live(Rounds &r) {
     std::vector<unsigned> &masks = ctx->live_host;
     masks.resize((size_t)nqb);
     HIP_TRY(hipMemcpyAsync(masks.data(), L.live_masks, (size_t)nqb * 4, hipMemcpyDeviceToHost, st));
+    std::vector<int> &lens = ctx->skip_host;  // (the same synchronisation brings the stage lists' lengths)
+    lens.resize((size_t)p.nseg * 256);
+    HIP_TRY(hipMemcpyAsync(lens.data(), L.live_lens, (size_t)p.nseg * 256 * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    if (ctx->cap.what & FDR_CAPTURE_LIVE_LISTS) {  // (test support: fdr_last_live_stage_lists)
+        const size_t bytes = live_stage_rows(a.nt) * 256 * sizeof(uint16_t);
+        int crc = ctx->cap.lists.reserve(bytes);
+        if (crc) return crc;
+        HIP_TRY(hipMemcpyAsync(ctx->cap.lists.p, L.live_lists, bytes, hipMemcpyDeviceToDevice, st));
+        ctx->last.skip.nseg = p.nseg;
+        ctx->last.skip.nt = (int)a.nt;
+        ctx->last.skip.segs = p.segs;
+        ctx->last.skip.stream = st;
+    }
     const LivePlan lp = live_plan(masks.data(), nqb, p.nseg, ctx->live_mode == FDR_LIVE_FORCE ? 0 : p.cohort);
     HIP_TRY(hipMemcpyAsync(L.live_ids, lp.ids.data(), (size_t)nqb * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(L.live_order, lp.order.data(), (size_t)nqb * 4, hipMemcpyHostToDevice, st));
@@ -1383,6 +1450,15 @@ int PrefilterCall::pass_live(Rounds &r) {
         items.push_back((long long)g.count * p.nseg);
         if (g.nl != FDR_LIVE_DENSE) {
             tr.pass_live_items[g.nl - FDR_LIVE_MIN_NL] = g.count * p.nseg;
+            for (int sg = 0; sg < p.nseg; ++sg) {  // the stages its work items walk, of those the segments hold
+                const int len = std::min<int>((int)a.nt, p.segs.b[sg + 1]) - p.segs.b[sg];
+                const int64_t nst = len > 0 ? (len + 127) >> 7 : 0;
+                int64_t walked = 0;
+                for (int i = 0; i < g.count; ++i)
+                    walked += std::min<int64_t>(nst, lens[(size_t)sg * 256 + (masks[(size_t)lp.order[(size_t)(g.first + i)]] & 0xffu)]);
+                tr.skip_stages_walked += walked;
+                tr.skip_stages_skipped += nst * g.count - walked;
+            }
             continue;
         }
         tr.pass_live_dense_items = g.count * p.nseg;
@@ -1407,7 +1483,8 @@ int PrefilterCall::pass_live(Rounds &r) {
             hipLaunchKernelGGL(kLiveKernels[g.nl - FDR_LIVE_MIN_NL], dim3(grid), dim3(512), live_lds_bytes(g.nl), s,
                                p1_q, (int)a.nq, (const _Float16 *)L.hb_t, (int)a.nt, (int)a.t_base, p.segs, kp, p.nq_pad,
                                R.partial, R.shared, ib, base, g.count, (const int *)(L.live_order + g.first),
-                               (const unsigned *)L.live_ids, ord);
+                               (const unsigned *)L.live_ids, ord, (const unsigned *)L.live_masks,
+                               reinterpret_cast<const unsigned *>(L.live_lists), (const int *)L.live_lens);
     });
 }
 

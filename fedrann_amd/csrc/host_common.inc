@@ -1,6 +1,12 @@
 // Part of libfedrann_hip.so (included by fedrann_hip.hip) and of the host-only sanitizer build
 // (tests/host_san/host_san.cpp): plain C++, no HIP.
 #define FDR_EXPORT extern "C" __attribute__((visibility("default")))
+// a helper that the kernels and the host share (the host-only sanitizer build has no HIP attributes)
+#ifdef __HIPCC__
+#define FDR_HOST_DEVICE __host__ __device__
+#else
+#define FDR_HOST_DEVICE
+#endif
 typedef unsigned long long u64;
 
 // Development knobs: ONE table, read in ONE place.  The release library compiles the defaults in -- no getenv, no

@@ -34,6 +34,56 @@ __global__ __launch_bounds__(64) void live_block_masks_kernel(const u64 *__restr
     if (lane == 0) masks[b] = m;
 }
 
+// Stage skipping.  The targets are scanned in (live chunks, mask) order, so a stage -- four tiles = 128 ordered rows
+// counted from its segment's first row, as the kernel below cuts them -- holds one mask or few.  Where the OR of its
+// rows' masks shares no chunk with the query block's mask, every similarity of the stage is exactly 0: it can enter no
+// list that is full, and a work item need not visit it.  Stage 0 of a segment is always visited: it fills a list that
+// nothing else fills with d~ = 1 entries, as the whole scan did.
+//
+// smask[live_stage_row(segment) + stage] = the OR of the masks of the stage's rows (rows from the segment's end on, or
+// from nt on, contribute nothing).  keys_s = the TARGETS' sorted keys.  One wave a stage: grid (stages of the longest
+// segment, segments).
+__global__ __launch_bounds__(64) void live_stage_masks_kernel(const u64 *__restrict__ keys_s, int nt, SegBounds segs,
+                                                              uint8_t *__restrict__ smask) {
+    const int seg = blockIdx.y, stage = blockIdx.x, lane = threadIdx.x;
+    const int t_begin = segs.b[seg], t_end = min(nt, segs.b[seg + 1]);
+    const int r0 = t_begin + stage * 128;
+    if (r0 >= t_end) return;
+    unsigned m = 0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int r = r0 + i * 64 + lane;
+        if (r < t_end) m |= (unsigned)keys_s[r] & 0xffu;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) m |= __shfl_xor(m, off);
+    if (lane == 0) smask[live_stage_row(t_begin, seg) + stage] = (uint8_t)m;
+}
+
+// The lists: for segment blockIdx.y and block mask value v = blockIdx.x, ascending, stage 0 and every stage whose mask
+// shares a chunk with v (all != 0: every stage -- the switch's off position), and lens[segment * 256 + v] = their
+// number.  One wave a list, 64 stages a step: a lane's entry goes behind those of the lanes below it.
+__global__ __launch_bounds__(64) void live_stage_lists_kernel(const uint8_t *__restrict__ smask, int nt, SegBounds segs,
+                                                              int all, uint16_t *__restrict__ lists,
+                                                              int *__restrict__ lens) {
+    const int seg = blockIdx.y, lane = threadIdx.x;
+    const unsigned v = blockIdx.x;
+    const int t_begin = segs.b[seg], t_end = min(nt, segs.b[seg + 1]);
+    const int nstages = t_end > t_begin ? (t_end - t_begin + 127) >> 7 : 0;
+    const size_t row = (size_t)live_stage_row(t_begin, seg);
+    const uint8_t *sm = smask + row;
+    uint16_t *out = lists + row * 256 + (size_t)v * live_list_stride(nstages);
+    int count = 0;
+    for (int s0 = 0; s0 < nstages; s0 += 64) {
+        const int s = s0 + lane;
+        const bool keep = s < nstages && (s == 0 || all != 0 || (sm[s] & v) != 0u);
+        const unsigned long long kept = __ballot(keep);
+        if (keep) out[count + __popcll(kept & ((1ull << lane) - 1ull))] = (uint16_t)s;
+        count += __popcll(kept);
+    }
+    if (lane == 0) lens[seg * 256 + (int)v] = count;
+}
+
 // Ehat fp32 [n, 128] (k0 k2 k4 k6 k1 k3 k5 k7 inside each group of 8), rows in the order `perm` -> the blocked fp16 copy
 // of `tiles` tiles (rows from n on: zeros).  One thread per 8 components.
 __global__ __launch_bounds__(256) void to_half_blocked_kernel(const float *__restrict__ Ehat,
@@ -89,7 +139,8 @@ template <int NL>
 __global__ __launch_bounds__(512, 4) void knn_prefilter_live_kernel(
     const _Float16 *__restrict__ Qh, int nq, const _Float16 *__restrict__ Tb, int nt, int t_base, SegBounds segs, int K,
     int nq_pad, u64 *__restrict__ partial, unsigned *__restrict__ tau_shared, int ib, int item_base, int nb,
-    const int *__restrict__ blocks, const unsigned *__restrict__ live_ids, OrderArgs ord) {
+    const int *__restrict__ blocks, const unsigned *__restrict__ live_ids, OrderArgs ord,
+    const unsigned *__restrict__ masks, const unsigned *__restrict__ lists, const int *__restrict__ lens) {
     static_assert(NL >= FDR_LIVE_MIN_NL && NL <= FDR_LIVE_MAX_NL, "instances NL = 2 .. 6");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int DP = 128, NW = 8, U = 4, LH = 16, QW = 32 * NW;
@@ -102,6 +153,7 @@ __global__ __launch_bounds__(512, 4) void knn_prefilter_live_kernel(
     const int seg = item / nb;
     const int qb = __builtin_amdgcn_readfirstlane(blocks[item - seg * nb]);
     const unsigned ids = __builtin_amdgcn_readfirstlane(live_ids[qb]);
+    const unsigned bmask = __builtin_amdgcn_readfirstlane(masks[qb]) & 0xffu;  // the block's own mask: its list
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -155,6 +207,17 @@ __global__ __launch_bounds__(512, 4) void knn_prefilter_live_kernel(
     const int t_end = min(nt, segs.b[seg + 1]);
     const int nunits = (t_end - t_begin + 31) >> 5;  // tiles
     const int nstages = (nunits + U - 1) / U;
+    // The stages this work item walks (live_stage_lists_kernel): nlist numbers, ascending, 16 bits each, from a word
+    // boundary on.  entry(i) is a scalar load of the word that holds number min(i, nlist - 1); the loop keeps the number
+    // of the stage it multiplies, of the one before (whose last pair the late half scores) and of the one it issues, and
+    // asks for the next one an iteration ahead of its use.
+    const int nlist = nstages > 0 ? min(lens[seg * 256 + (int)bmask], nstages) : 0;
+    const unsigned *list = lists + (((size_t)live_stage_row(t_begin, seg) * 256 + (size_t)bmask * live_list_stride(nstages)) >> 1);
+    auto entry = [&](int i) -> int {
+        const int e = max(min(i, nlist - 1), 0);
+        const unsigned w = __builtin_amdgcn_readfirstlane(list[e >> 1]);
+        return min((int)((w >> (16 * (e & 1))) & 0xffffu), max(nstages - 1, 0));  // (never past the segment, whatever the table holds)
+    };
 
     // LDS-DMA: piece p = wave + 8 u of a stage is live chunk p % NL of the stage's tile p / NL and lands at p KiB of the
     // stage.  Its source offset inside the stage's four tiles is loop-invariant (a scalar per piece); the stage advances
@@ -167,20 +230,21 @@ __global__ __launch_bounds__(512, 4) void knn_prefilter_live_kernel(
         const int tl = p / NL, s = p - tl * NL;
         poff[u] = (unsigned)(tl * TILE_BYTES) + ((ids >> (4 * s)) & 7u) * 1024u;
     }
-    unsigned soff = (unsigned)((lane & 31) * 32 + (lane >> 5) * 16);  // this lane's 16 bytes of a piece, + the stage issued next
-    auto issue_stage = [&](auto par_c) {  // par = parity of the stage being issued
+    const unsigned soff = (unsigned)((lane & 31) * 32 + (lane >> 5) * 16);  // this lane's 16 bytes of a piece
+    auto issue_stage = [&](auto par_c, int sn) {  // par = parity of the list position being issued, sn = its stage
+        const unsigned stoff = (unsigned)sn * (unsigned)(U * TILE_BYTES);
         constexpr int par = decltype(par_c)::value;
         unsigned char *dst = smem + par * STAGE_BYTES;
         static_for(std::make_integer_sequence<int, PPW>{}, [&](auto u_c) {
             constexpr int u = decltype(u_c)::value;
             if (NW * (u + 1) <= NPIECE || wave < NPIECE - NW * u)  // (wave-uniform; a literal for every u but the last)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(seg_base + (soff + poff[u])),
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(seg_base + (soff + (poff[u] + stoff))),
                                                  (__attribute__((address_space(3))) void *)(dst + (wave + NW * u) * 1024),
                                                  16, 0, 0);
         });
-        soff += (unsigned)(U * TILE_BYTES);
     };
-    if (nstages > 0) issue_stage(std::integral_constant<int, 0>{});
+    int sprev = 0, scur = entry(0), snext = entry(1);
+    if (nlist > 0) issue_stage(std::integral_constant<int, 0>{}, scur);
     __syncthreads();  // (hipcc drains the DMA before the barrier)
 
     unsigned q0 = PK_EMPTY, q1 = PK_EMPTY;  // two-entry candidate queue per lane (knn_prefilter_kernel)
@@ -244,10 +308,11 @@ __global__ __launch_bounds__(512, 4) void knn_prefilter_live_kernel(
     unsigned stamp_acc[6] = {0, 0, 0, 0, 0, 0};
     const bool stamp_on = blockIdx.x == 0;
 #endif
-    auto stage_body = [&](auto par_c, int it) {
+    auto stage_body = [&](auto par_c, int it) {  // it = position in the list; stage scur is multiplied, snext issued
         constexpr int par = decltype(par_c)::value;
         STAMP(ts0);
-        if (it + 1 < nstages) issue_stage(std::integral_constant<int, par ^ 1>{});  // lands before the barrier below
+        const int safter = entry(it + 2);
+        if (it + 1 < nlist) issue_stage(std::integral_constant<int, par ^ 1>{}, snext);  // lands before the barrier below
         STAMP(ts1);
         STAMP_ADD(0, ts0, ts1);
         auto mfma_pair = [&](auto p_c) __attribute__((always_inline)) {  // tiles 2 p, 2 p + 1 of the stage
@@ -276,11 +341,11 @@ __global__ __launch_bounds__(512, 4) void knn_prefilter_live_kernel(
             score(acc, ts);
             if (ts + 1 < nunits) score(accB, ts + 1);  // (the second tile of a last, odd pair is padding)
         };
-        if (late && it > 0 && U * it - 2 < nunits) score_pair(U * it - 2);
-        if (it < nstages) {
+        if (late && it > 0 && U * sprev + U - 2 < nunits) score_pair(U * sprev + U - 2);
+        if (it < nlist) {
             static_for(std::make_integer_sequence<int, NP>{}, [&](auto p_c) {
                 constexpr int p = decltype(p_c)::value;
-                const int tp = U * it + 2 * p;
+                const int tp = U * scur + 2 * p;
                 if (tp < nunits) {  // (wave-uniform; a segment's last stage may hold one pair only)
                     mfma_pair(p_c);
                     if (!late || p < NP - 1) score_pair(tp);
@@ -305,10 +370,13 @@ __global__ __launch_bounds__(512, 4) void knn_prefilter_live_kernel(
         STAMP_ADD(4, ts3b, ts4);
         if (stamp_on) stamp_acc[5] += 1;
 #else
-        __syncthreads();  // stage it+1 is complete (all waves' pieces) before anyone reads it
+        __syncthreads();  // position it+1 is complete (all waves' pieces) before anyone reads it
 #endif
+        sprev = scur;
+        scur = snext;
+        snext = safter;
     };
-    const int niter = nstages + 1;  // (one MFMA-less iteration: the late half scores the last stage's last pair)
+    const int niter = nlist + 1;  // (one MFMA-less iteration: the late half scores the last stage's last pair)
     for (int it0 = 0; it0 < niter; it0 += 2) {
         stage_body(std::integral_constant<int, 0>{}, it0);
         if (it0 + 1 < niter) stage_body(std::integral_constant<int, 1>{}, it0 + 1);
@@ -338,7 +406,8 @@ __global__ __launch_bounds__(512, 4) void knn_prefilter_live_kernel(
 }
 
 typedef void (*LiveKernel)(const _Float16 *, int, const _Float16 *, int, int, SegBounds, int, int, u64 *, unsigned *, int,
-                           int, int, const int *, const unsigned *, OrderArgs);
+                           int, int, const int *, const unsigned *, OrderArgs, const unsigned *, const unsigned *,
+                           const int *);
 static constexpr LiveKernel kLiveKernels[FDR_LIVE_MAX_NL - FDR_LIVE_MIN_NL + 1] = {
     knn_prefilter_live_kernel<2>, knn_prefilter_live_kernel<3>, knn_prefilter_live_kernel<4>,
     knn_prefilter_live_kernel<5>, knn_prefilter_live_kernel<6>};

@@ -75,6 +75,17 @@ static bool live_chunks_wanted(int live_mode, int shape, const KnnPlan &pp) {
     return live_mode == FDR_LIVE_FORCE || (FDR_LIVE_AUTO_ON && pp.cohort > 0 && pp.queues == 2);
 }
 
+// Stage skipping of the live-chunk pass (live_stage_masks_kernel, live_stage_lists_kernel; DESIGN.md section 6).  A
+// stage is 128 ordered rows counted from its segment's first row; the tables are laid out in "stage rows", one per
+// stage and two spare ones per segment, so that the place of segment g's tables follows from its first row alone:
+// two segments' first rows that lie S stages apart differ by at least S - 1 in (row >> 7).
+// FDR_SKIP_AUTO_ON: whether AUTO walks the lists -- decided by measurement, docs/experiments.md A-26.
+#define FDR_SKIP_AUTO_ON 1
+static FDR_HOST_DEVICE inline int live_stage_row(int t_begin, int seg) { return (t_begin >> 7) + 2 * seg; }
+// the list of one mask value takes an even number of 16-bit entries: every list starts on a 32-bit word
+static FDR_HOST_DEVICE inline int live_list_stride(int nstages) { return (nstages + 1) & ~1; }
+static size_t live_stage_rows(int64_t nt) { return (size_t)(nt >> 7) + 2 * FDR_MAX_SEG + 2; }
+
 // mode: FDR_MODE_AUTO uses the fp16 prefilter whenever it applies (d <= 512, k + 8 <= 64) and the target set is large
 // enough to pay for it; fdr_set_knn_mode / FDR_KNN_MODE=exact|prefilter override it.
 static bool knn_prefilter_wanted(int knn_mode, int64_t nt, int k) {
@@ -130,6 +141,12 @@ struct PrefilterWs {
     ws_half *hb_t;
     unsigned *live_masks, *live_ids;
     int *live_order;
+    // ... the stage-skip tables: per stage row the OR of its rows' masks; per (segment, block mask value 0 .. 255) the
+    // ascending list of the segment's stages a block of that mask walks -- 256 lists of live_list_stride(stages) 16-bit
+    // entries from entry 256 * live_stage_row(segment) on -- and their lengths [segment][mask value]
+    uint8_t *live_smask;
+    uint16_t *live_lists;
+    int *live_lens;
     // ... and the dense group's queries side by side (the shipped kernel takes a block RANGE): rows, order table, bounds
     ws_half *live_hq;
     int *live_perm;
@@ -196,6 +213,9 @@ static PrefilterWs prefilter_ws(const WsEnv &env, void *base, int64_t nq, int64_
         L.live_masks = A.take<unsigned>(nqb);
         L.live_ids = A.take<unsigned>(nqb);
         L.live_order = A.take<int>(nqb);
+        L.live_smask = A.take<uint8_t>(live_stage_rows(nt));
+        L.live_lists = A.take<uint16_t>(live_stage_rows(nt) * 256);
+        L.live_lens = A.take<int>((size_t)FDR_MAX_SEG * 256);
         L.live_hq = A.take<ws_half>(nqb * 256 * dp);
         L.live_perm = A.take<int>(nqb * 256);
         L.live_tau = A.take<unsigned>(nqb * 256);

@@ -270,6 +270,21 @@ int fdr_set_dedup_mode(fdr_ctx *ctx, int mode);
 #define FDR_LIVE_OFF 1
 #define FDR_LIVE_FORCE 2
 int fdr_set_live_chunks(fdr_ctx *ctx, int mode);
+/* Stage skipping of the live-chunk pass: a work item visits stage 0 of its segment and the
+ * stages -- 128 consecutive rows of the scan order -- that share a chunk with its query block's mask; in every other
+ * stage each similarity is exactly 0.  AUTO (default): whenever the live-chunk pass runs.  OFF: every stage, through
+ * the same kernels (the parity tests, A/B measurements). */
+#define FDR_SKIP_AUTO 0
+#define FDR_SKIP_OFF 1
+int fdr_set_live_skip(fdr_ctx *ctx, int mode);
+/* Diagnostics (test support): the stage lists of target segment `segment` of the most recent call that ran the
+ * live-chunk pass.  *first_row_out (may be NULL) = the segment's first row in the scan order, *nstages_out = its stages
+ * of 128 rows; lens[256] (may be NULL) = per block mask value the number of
+ * stages a block of that mask walks; lists[256][nstages] (may be NULL) = the stage numbers, ascending, 0xffff behind a
+ * list's end.  The lists are a copy the context owns, taken while FDR_CAPTURE_LIVE_LISTS is set
+ * (fdr_set_knn_capture): FDR_E_STATE when the last k-NN call ran no live-chunk pass or captured none. */
+int fdr_last_live_stage_lists(fdr_ctx *ctx, int32_t segment, int32_t *first_row_out, int32_t *nstages_out, int32_t *lens,
+                              uint16_t *lists);
 /* Unique target / query rows the most recent k-NN call
  * actually searched (= the row counts when the call found too few duplicates to bother). */
 int fdr_last_unique(fdr_ctx *ctx, int *unique_targets, int *unique_queries);
@@ -322,6 +337,9 @@ typedef struct fdr_knn_trace {
     int32_t pass_live;         /* 1: the pass ran grouped by live chunks (knn_prefilter_live_kernel<NL> + the dense kernel) */
     int32_t pass_live_items[5];    /* its work items (query block x segment) on the NL = 2, 3, 4, 5, 6 instances */
     int32_t pass_live_dense_items; /* ... and on the dense kernel (blocks with seven or eight live chunks) */
+    int32_t skip_live;             /* 1: its work items walked stage lists that leave disjoint stages out (fdr_set_live_skip) */
+    int64_t skip_stages_walked;    /* stages (128 target rows) on the lists of the NL instances' work items (summed by the host) ... */
+    int64_t skip_stages_skipped;   /* ... and left out: walked + skipped = the stages of their segments */
 } fdr_knn_trace;
 int fdr_last_knn_trace(fdr_ctx *ctx, fdr_knn_trace *out);
 /* Prefilter mode only: number of query rows of the most recent k-NN call whose candidate set could
@@ -351,10 +369,12 @@ int fdr_last_query_paths(fdr_ctx *ctx, uint8_t *paths, int64_t n_queries);
  *   FDR_CAPTURE_CANDIDATES  the merged candidate lists, n_queries x K' keys (fdr_last_candidates);
  *   FDR_CAPTURE_RANGE       per range-pass query: its query row, the bound theta, the count of targets the pass
  *                           found with d~ <= theta and the first min(count, 1024) of them (fdr_last_range_sets).
+ *   FDR_CAPTURE_LIVE_LISTS  the live-chunk pass's stage lists, where that pass runs (fdr_last_live_stage_lists).
  * With the duplicate-row layer active the capture describes the inner search of the unique rows.  Every k-NN entry
  * point clears the capture; asking after an exact-mode, generic, failed or non-capturing call is FDR_E_STATE. */
 #define FDR_CAPTURE_CANDIDATES 1
 #define FDR_CAPTURE_RANGE 2
+#define FDR_CAPTURE_LIVE_LISTS 4  /* the live-chunk pass's stage lists (fdr_last_live_stage_lists) */
 #define FDR_RANGE_CAP 1024  /* row slots per range query of fdr_last_range_sets */
 int fdr_set_knn_capture(fdr_ctx *ctx, int what);
 /* The candidate lists of the last call: keys [n_queries, kp] (n_queries and kp = K' as in fdr_last_knn_trace), one
