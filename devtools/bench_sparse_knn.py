@@ -1,6 +1,6 @@
 """Time the exact sparse k-NN (fdr_knn_sparse) on synthetic reads with IDF values, next to the projected search.
 
-    python devtools/bench_sparse_knn.py [--reads 100000 1000000] [--k 20] [--steps 3] [--metric cosine|jaccard]
+    python devtools/bench_sparse_knn.py [--reads 100000 1000000] [--k 20] [--steps 3] [--metric cosine|jaccard|weighted_jaccard]
                                         [--values idf|none] [--split] [--world W --rank r] [--block-rows B]
 
 Rows: synth(R, doubling=True) (2 R rows), value of feature f = idf[f] (what --no-projection searches).  For each size
@@ -10,6 +10,8 @@ that time, and the median wall time of embed_knn at d = 128 on the same rows (th
 compacted CSR, as the command line passes it).  Kernel times alone: run it under rocprofv3 --kernel-trace --stats.
 --metric jaccard times fdr_knn_sparse_metric on the rows' sets (values=None, 4 posting bytes per pair update);
 --values none gives cosine the same rows without values (every stored entry 1), the like-for-like comparison.
+--metric weighted_jaccard times fdr_knn_sparse_metric on the rows with IDF values clamped at 0, as the command line
+passes them (8 posting bytes per pair update, as cosine); --values none gives it ones.
 "sparse_ms_all" lists every timed call, so the spread between repetitions is visible.
 --split times the two halves of that call on their own as well: "build_ms" (Context.sparse_index: the host checks, the
 upload, S1, the sort and S2; each build replaces the one before and reuses its buffers, as knn_sparse does) and "search_ms" (SparseIndex.search
@@ -49,8 +51,9 @@ def main():
     ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--no-projected", action="store_true", help="skip the d = 128 comparison")
-    ap.add_argument("--metric", choices=["cosine", "jaccard"], default="cosine")
-    ap.add_argument("--values", choices=["idf", "none"], default="idf", help="cosine only: IDF values, or none (ones)")
+    ap.add_argument("--metric", choices=["cosine", "jaccard", "weighted_jaccard"], default="cosine")
+    ap.add_argument("--values", choices=["idf", "none"], default="idf",
+                    help="cosine, weighted_jaccard: IDF values, or none (ones)")
     ap.add_argument("--split", action="store_true", help="time the index build and the search of all rows separately too")
     ap.add_argument("--world", type=int, default=0, help="with --rank: time the search of one rank's rows of the index")
     ap.add_argument("--rank", type=int, default=0)
@@ -61,6 +64,8 @@ def main():
         s = synth(R, doubling=True)
         indptr, indices, F = s["indptr"], s["indices"], s["n_features"]
         values = None if a.metric == "jaccard" or a.values == "none" else idf_weights(s["counts"], F)[indices]
+        if values is not None and a.metric == "weighted_jaccard":
+            values = np.maximum(values, np.float32(0))  # (a negative IDF carries weight 0, as on the command line)
         entry_bytes = 4 if a.metric == "jaccard" else 8
         n = indptr.size - 1
         df = np.bincount(indices, minlength=F).astype(np.float64)

@@ -15,6 +15,8 @@ projection matrix -> embeddings -> k-NN -> overlaps.tsv.  Entry points:
 projection and the embeddings, and stage 4 searches them exactly (fdr_knn_sparse); -n is ignored.  One GPU.
 --no-projection-metric jaccard (with --no-projection): stage 2 builds no weights and stage 4 searches the rows'
 k-mer sets by exact Jaccard distance (fdr_knn_sparse_metric), the quantity MinHash tools estimate.
+--no-projection-metric weighted_jaccard: stage 2 builds the IDF weights as for cosine (a negative weight, count > F,
+becomes 0) and stage 4 searches the weighted rows by exact weighted Jaccard (Ruzicka) distance.
 
 --devices 0,1,...: every stage is sharded over several GPUs of the node.  The parent process starts one
 child per GPU BEFORE it touches a GPU itself; from reads, every child counts and searches its byte range of
@@ -96,9 +98,10 @@ def build_parser():
     g.add_argument("--no-projection", action="store_true", default=False,
                    help="Search the IDF-weighted feature rows themselves (exact cosine k-NN, no random projection: "
                         "the ground truth the projection approximates); -n is ignored.  One GPU only.")
-    g.add_argument("--no-projection-metric", choices=["cosine", "jaccard"], default="cosine",
-                   help="With --no-projection: cosine on the IDF-weighted rows, or the exact Jaccard distance of the "
-                        "rows' feature sets (no weights).")
+    g.add_argument("--no-projection-metric", choices=["cosine", "jaccard", "weighted_jaccard"], default="cosine",
+                   help="With --no-projection: cosine on the IDF-weighted rows, the exact Jaccard distance of the "
+                        "rows' feature sets (no weights), or the exact weighted Jaccard distance of the IDF-weighted "
+                        "rows (sum of minima over sum of maxima; a negative IDF counts as 0).")
     g.add_argument("--device", type=int, default=None, help="GPU ordinal (default $LOCAL_RANK or 0).")
     g.add_argument("--devices", type=str, default=None,
                    help="Comma-separated GPU ordinals: shard the rows over these GPUs (one process each).")
@@ -204,7 +207,7 @@ def load_inputs(*, output_dir, embedding_dimension, save_feature_matrix, kmer_se
     """Stages 2-3a of the reference pipeline on the host (__main__.py:329-345): the projection matrix and
     the read x feature CSR.  Returns (indptr, indices, n_features, P, read_names, strands); with no_projection the
     IDF weights of the features (float32 [n_features]) take P's place, or None with metric="jaccard" (sets have
-    no weights)."""
+    no weights); with metric="weighted_jaccard" the weights are clamped at 0 (a feature with count > n_features)."""
     jaccard = no_projection and metric == "jaccard"
     if jaccard:
         logger.info("--- 2. (skipped) no IDF weights: the Jaccard search takes the feature sets, values=None ---")
@@ -235,6 +238,11 @@ def load_inputs(*, output_dir, embedding_dimension, save_feature_matrix, kmer_se
             P = build_precompute_matrix(counts, embedding_dimension, n_features=n_features)
         logger.info("--- 3. Generate feature matrix ---")
         read_names, strands = _load_names(read_names_path, indptr.size - 1)
+    if no_projection and metric == "weighted_jaccard":
+        negative = int(np.count_nonzero(P < 0))
+        logger.info("weighted Jaccard takes weights >= 0: %d of %d features have a negative IDF (count > %d) and "
+                    "carry weight 0", negative, n_features, n_features)
+        P = np.maximum(P, np.float32(0))
     if save_feature_matrix and save:
         save_feature_matrix_npz(join(output_dir, "feature_matrix.npz"), indptr, indices, n_features)
     return indptr, indices, n_features, P, read_names, strands
@@ -249,7 +257,8 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     HBM between the projection and the search (fdr_embed_knn), and only the features P has entries for
     cross PCIe (fdr_csr_compact; the saved feature_matrix.npz is the full matrix).  no_projection: stage 4
     searches the IDF-weighted feature rows themselves (value of feature f = idf[f]; fdr_knn_sparse), or with
-    no_projection_metric="jaccard" their sets by Jaccard distance (fdr_knn_sparse_metric)."""
+    no_projection_metric="jaccard" their sets by Jaccard distance, with "weighted_jaccard" the rows with the IDF
+    weights clamped at 0 by weighted Jaccard distance (both fdr_knn_sparse_metric)."""
     from . import _lib
     from .feature_extraction import _projection_csr
     if kmer_searcher_output:
@@ -271,10 +280,12 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
         _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates)
         return
     if no_projection:
-        logger.info("--- 4. Nearest Neighbors Search (exact, metric = cosine, on the IDF-weighted feature rows) ---")
+        logger.info("--- 4. Nearest Neighbors Search (exact, metric = %s, on the IDF-weighted feature rows) ---",
+                    no_projection_metric)
         logger.info("--no-projection: -n/--embedding-dimension (%d) is ignored; %d rows x %d features, %d stored "
                     "entries", embedding_dimension, indptr.size - 1, n_features, indices.size)
-        neighbor_matrix, distances = ctx.knn_sparse(indptr, indices, P[indices], n_features, nndescent_n_neighbors)
+        neighbor_matrix, distances = ctx.knn_sparse(indptr, indices, P[indices], n_features, nndescent_n_neighbors,
+                                                    metric=no_projection_metric)
         _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates)
         return
     Pc = _projection_csr(P)

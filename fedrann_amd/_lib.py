@@ -40,8 +40,8 @@ FALLBACKS = ("none", "chunked", "whole")
 CAPTURE_CANDIDATES, CAPTURE_RANGE, CAPTURE_LIVE_LISTS = 1, 2, 4
 RANGE_CAP = 1024
 # fdr_knn_sparse_metric (include/fedrann_hip.h: FDR_METRIC_*)
-METRIC_COSINE, METRIC_JACCARD = 0, 1
-SPARSE_METRICS = {"cosine": METRIC_COSINE, "jaccard": METRIC_JACCARD}
+METRIC_COSINE, METRIC_JACCARD, METRIC_WEIGHTED_JACCARD = 0, 1, 2
+SPARSE_METRICS = {"cosine": METRIC_COSINE, "jaccard": METRIC_JACCARD, "weighted_jaccard": METRIC_WEIGHTED_JACCARD}
 
 
 class KnnTrace(ctypes.Structure):
@@ -336,20 +336,21 @@ def overlaps_write(path, idx, dist, name_off, names, strands, row0=0, append=Fal
 def sparse_metric_code(metric):
     """FDR_METRIC_* of a metric name of Context.knn_sparse; needs no GPU."""
     if not isinstance(metric, str) or metric not in SPARSE_METRICS:
-        raise ValueError("metric must be 'cosine' or 'jaccard', got %r" % (metric,))
+        raise ValueError("metric must be 'cosine', 'jaccard' or 'weighted_jaccard', got %r" % (metric,))
     return SPARSE_METRICS[metric]
 
 
-def check_sparse_rows(indptr, indices, values, n_features, k):
+def check_sparse_rows(indptr, indices, values, n_features, k, metric="cosine"):
     """The argument checks of Context.knn_sparse (fdr_knn_sparse repeats them on the device); needs no GPU.
+    metric="weighted_jaccard" also refuses a negative value and a row whose float32 mass chain is not finite.
     Returns (n, k, n_features)."""
-    return _check_sparse(indptr, indices, values, n_features, k)
+    return _check_sparse(indptr, indices, values, n_features, k, metric)
 
 
-def check_sparse_csr(indptr, indices, values, n_features):
+def check_sparse_csr(indptr, indices, values, n_features, metric="cosine"):
     """The argument checks of Context.sparse_index: those of check_sparse_rows without a k, and at least one row
     (fdr_sparse_index_build repeats them on the device); needs no GPU.  Returns (n, n_features)."""
-    n, _, F = _check_sparse(indptr, indices, values, n_features, None)
+    n, _, F = _check_sparse(indptr, indices, values, n_features, None, metric)
     return n, F
 
 
@@ -367,7 +368,20 @@ def check_sparse_search(n, k, lo=0, hi=None):
     return k, lo, hi
 
 
-def _check_sparse(indptr, indices, values, n_features, k):
+def _row_mass_overflows(indptr, values, largest):
+    """Whether a row's float32 add chain over its values (all finite and >= 0, none above `largest`) reaches +inf.  A
+    chain of m such terms is at most m * largest * (1 + 2^-24)^m, below 1.07e38 for m <= 2^20 and m * largest < 1e38;
+    only the rows beyond that bound run the chain itself (np.cumsum in float32 adds in order)."""
+    lens = np.diff(indptr)
+    suspects = np.flatnonzero((lens > (1 << 20)) | (lens.astype(np.float64) * largest >= 1e38))
+    with np.errstate(over="ignore"):
+        for r in suspects:
+            if not np.isfinite(np.cumsum(values[indptr[r]:indptr[r + 1]], dtype=np.float32)[-1]):
+                return True
+    return False
+
+
+def _check_sparse(indptr, indices, values, n_features, k, metric="cosine"):
     """k=None: no k to check, but n >= 1."""
     for name, a, dt in (("indptr", indptr, np.int64), ("indices", indices, np.int32), ("values", values, np.float32)):
         if a is None and name == "values":
@@ -396,7 +410,16 @@ def _check_sparse(indptr, indices, values, n_features, k):
         ascending[starts[(starts > 0) & (starts < indices.size)] - 1] = True  # (a row's first id follows another row)
         if not np.all(ascending):
             raise ValueError("feature indices must be strictly ascending inside each row (sorted, no duplicates)")
-    if values is not None and not np.all(np.isfinite(values)):
+    if metric == "weighted_jaccard" and values is not None and values.size:
+        lo, hi = float(values.min()), float(values.max())  # (two reductions without a temporary; a NaN comes through)
+        if not (np.isfinite(lo) and np.isfinite(hi)):
+            raise ValueError("values must be finite")
+        if lo < 0:
+            raise ValueError("values must not be negative under metric='weighted_jaccard'")
+        if _row_mass_overflows(indptr, values, hi):
+            raise ValueError("a row's float32 sum of values is not finite (metric='weighted_jaccard' needs a finite "
+                             "mass per row)")
+    elif values is not None and not np.all(np.isfinite(values)):
         raise ValueError("values must be finite")
     return n, k, F
 
@@ -714,9 +737,14 @@ class Context:
         metric="jaccard" (fdr_knn_sparse_metric): the Jaccard distance of the rows' sets, a row's set being its stored
         entries with a value other than 0: (float32)((u - c) / u) in float64 for c shared features and a union of u,
         0 for two empty rows; ascending by (distance, index).
+        metric="weighted_jaccard" (fdr_knn_sparse_metric): the weighted Jaccard (Ruzicka) distance of rows with values
+        >= 0 (a stored 0 is absent; None: every entry 1): with A the float32 sum of a row's values in order, m the
+        float32 sum of min(x_q, x_t) over the shared features in ascending order and u = A_q + A_t - m in float64,
+        (float32)((u - m) / u), 0 for two zero-mass rows.  Negative values and a row whose mass is not finite are
+        refused (ValueError).
         The call builds the context's sparse index anew (a SparseIndex of this context is stale afterwards)."""
         code = sparse_metric_code(metric)
-        n, k, F = check_sparse_rows(indptr, indices, values, n_features, k)
+        n, k, F = check_sparse_rows(indptr, indices, values, n_features, k, metric=metric)
         self._sparse_gen += 1
         idx = np.empty((n, k), dtype=np.int32)
         dist = np.empty((n, k), dtype=np.float32)
@@ -734,7 +762,7 @@ class Context:
         of SparseIndex.search calls: fdr_sparse_index_build.  A context holds one index: this call, and every
         knn_sparse, replaces it, and a SparseIndex of the replaced one raises from then on."""
         code = sparse_metric_code(metric)
-        n, F = check_sparse_csr(indptr, indices, values, n_features)
+        n, F = check_sparse_csr(indptr, indices, values, n_features, metric=metric)
         self._sparse_gen += 1
         self._check(self._L.fdr_sparse_index_build(self._h, code, n, F, _ptr(indptr), _ptr(indices), _ptr(values)),
                     "fdr_sparse_index_build")
@@ -832,7 +860,7 @@ class SparseIndex:
 
     def info(self):
         """dict of fdr_sparse_index_info: metric, n, postings (stored entries kept), zero_rows (zero rows; Jaccard:
-        empty rows), device_bytes (what the index holds on the device)."""
+        empty rows; weighted Jaccard: zero-mass rows), device_bytes (what the index holds on the device)."""
         self._live("SparseIndex.info")
         c = self._ctx
         m, n, p, z = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()

@@ -4,7 +4,8 @@
 //   K2 normalize_rows_kernel E -> Ehat          (done inside pynndescent in the reference)
 //   K3 knn_tile_kernel       exact cosine top-k (nearest_neighbors.py:39-55 -> pynndescent)
 //   K4 knn_merge_kernel      merge of per-segment top-k lists
-//   S1-S4 (knn_sparse.inc)   exact cosine (S1j, S3j: Jaccard) top-k on the sparse feature rows themselves (no projection)
+//   S1-S4 (knn_sparse.inc)   exact cosine (S1j, S3j: Jaccard; S1w, S3w: weighted Jaccard) top-k on the sparse feature
+//                            rows themselves (no projection)
 //
 // Written for wave64 / MFMA / 160 KB LDS directly; there is no other backend.
 // ABI: include/fedrann_hip.h.  Design notes and rooflines: DESIGN.md.
@@ -631,13 +632,14 @@ struct SparseIndex {
     DevArray<long long> indptr;      // [n + 1] the rows
     DevArray<int> indices;           // the stored entries' features ...
     DevArray<float> values;          // ... their values, as given (absent: every entry 1) ...
-    DevArray<float> xhat;            // ... normalised (cosine)
+    DevArray<float> xhat;            // ... normalised (cosine); as the postings take them (weighted Jaccard)
     DevArray<int> asize;             // [n] the rows' set sizes (Jaccard)
+    DevArray<float> mass;            // [n] the rows' fp32 sums of values (weighted Jaccard)
     DevArray<unsigned char> zero;    // [n] zero (Jaccard: empty) rows; the index's own, ctx->zero belongs to the dense calls
     DevArray<u64> keys, sorted_keys; // S1's posting keys (feature << 32 | row); sorted.  `keys`: see run_flags()
     DevArray<unsigned> pos, sorted_pos;  // each key's stored entry, the sort's values; sorted.  `pos`: see posting_rows()
     DevArray<int> efeat;             // each stored entry's run (-1: no posting)
-    DevArray<float> pval;            // the postings' values (cosine)
+    DevArray<float> pval;            // the postings' values (cosine, weighted Jaccard)
     DevArray<long long> runptr;      // [runs + 1] the runs' first postings
     DevArray<int> heavy;             // [n] a search's queries for S3r
     DevArray<u64> cnt;               // SP_CNT_* counters in [0, 8); behind them zidx() and zdist()
@@ -661,7 +663,7 @@ struct SparseIndex {
     float *zdist() const { return reinterpret_cast<float *>(zidx() + FDR_MAX_K); }
     template <class F>
     auto each(F f) {
-        return f(indptr, indices, values, xhat, asize, zero, keys, sorted_keys, pos, sorted_pos, efeat, pval, runptr,
+        return f(indptr, indices, values, xhat, asize, mass, zero, keys, sorted_keys, pos, sorted_pos, efeat, pval, runptr,
                  heavy, cnt, tmp);
     }
     size_t bytes() {  // fdr_sparse_index_info: everything held, the build's scratch included

@@ -44,10 +44,25 @@
 //                          rows take the zero rows' place) are shared.
 // Cost model: the same sum over features of df_f^2 pair updates, each reading a 4-byte posting entry (the row only).
 //
+// S1w / S3w / S3rw  exact weighted Jaccard (Ruzicka) k-NN on the same rows (FDR_METRIC_WEIGHTED_JACCARD), values >= 0.
+// A row's mass A_r is the fp32 add chain over its stored values in order; the shared weight m(q, t) is the fp32 add
+// chain of min(x_qf, x_tf) over the features both rows hold with a value > 0, in ascending order; u = ((double)A_q +
+// (double)A_t) - (double)m, dist = (float)((u - m) / u), 0 for u = 0 (DESIGN.md section 4).
+//   S1w sp_rows_wjaccard_kernel  per row: the argument checks of S1, a negative value and a mass chain that is not
+//                          finite refused too; the mass, the zero flag (mass > 0 ? 0 : 1), one posting key per entry
+//                          with a value > 0; the raw value goes where S1 puts xhat, so the sort and S2 follow as for
+//                          cosine and pval holds the raw values.
+//   S3w / S3rw knn_sparse_kernel<RANGE, FDR_METRIC_WEIGHTED_JACCARD>  the walk of S3 / S3r with the same fp32
+//                          accumulator in the table slot: a feature step does acc + min(qv, pval[e]) where the cosine
+//                          instance does its fma.  At the end of a table the masses of the occupied slots are read
+//                          and the distance is formed in fp64.  Everything else is shared.
+// Cost model: that of the cosine search (an 8-byte posting entry per pair update).
+//
 // The index and its searches.  S1 (S1j), the sort and S2 are the BUILD (fdr_sparse_index_build): what they leave in
 // ctx->sp (struct SparseIndex, fedrann_hip.hip: one typed array per buffer) -- the rows (indptr, each stored entry's
-// run id efeat, xhat or the set sizes asize), the postings (runptr, posting_rows(), pval) and the zero flags (zero, the
-// index's own: ctx->zero belongs to the dense calls) -- is the context's one sparse index, described by sp.built; the
+// run id efeat, xhat (weighted Jaccard: the raw values), the set sizes asize or the masses mass), the postings (runptr,
+// posting_rows(), pval) and the zero flags (zero, the index's own: ctx->zero belongs to the dense calls) -- is the
+// context's one sparse index, described by sp.built; the
 // build's scratch (keys, sorted_keys, sorted_pos, tmp) is kept with it.  Two arrays change their contents on the way and
 // a third is cut up: the accessors run_flags() / run_numbers(), posting_rows() and zidx() / zdist() of the struct hold
 // the casts and say why the first contents are dead by then.  release() frees the arrays and forgets the index in one
@@ -69,13 +84,15 @@ static_assert((1 << SP_LOG2CAP) == SP_CAP, "SP_CAP is a power of two");
 
 // counters (u64 each): [0, 3) of a build, [3, 5) of a search
 #define SP_CNT_ERR 0      // or of SP_ERR_* bits
-#define SP_CNT_DROPPED 1  // stored entries without a posting (xhat = +-0; Jaccard: value = +-0)
-#define SP_CNT_ZERO 2     // zero rows (Jaccard: empty rows)
+#define SP_CNT_DROPPED 1  // stored entries without a posting (xhat = +-0; Jaccard: value = +-0; weighted: not > 0)
+#define SP_CNT_ZERO 2     // zero rows (Jaccard: empty rows; weighted Jaccard: zero-mass rows)
 #define SP_CNT_HEAVY 3    // queries handed to the range-split kernel
 #define SP_CNT_ZEROQ 4    // zero (empty) rows among the queries
 #define SP_ERR_RANGE 1u
 #define SP_ERR_ORDER 2u
 #define SP_ERR_VALUE 4u
+#define SP_ERR_NEGATIVE 8u  // weighted Jaccard: a value below 0
+#define SP_ERR_MASS 16u     // weighted Jaccard: a row's mass chain is not finite
 
 // S1: one thread per row
 __global__ __launch_bounds__(256) void sp_rows_kernel(long long n, long long F, const long long *__restrict__ indptr,
@@ -151,6 +168,46 @@ __global__ __launch_bounds__(256) void sp_rows_jaccard_kernel(long long n, long 
     if (e - b > a) atomicAdd(&cnt[SP_CNT_DROPPED], (u64)(e - b - a));  // (without an error: the entries at +-0)
 }
 
+// S1w: one thread per row
+__global__ __launch_bounds__(256) void sp_rows_wjaccard_kernel(long long n, long long F,
+                                                               const long long *__restrict__ indptr,
+                                                               const int *__restrict__ indices,
+                                                               const float *__restrict__ vals, float *__restrict__ xraw,
+                                                               float *__restrict__ mass, u64 *__restrict__ keys,
+                                                               unsigned *__restrict__ pos, int *__restrict__ efeat,
+                                                               unsigned char *__restrict__ zero,
+                                                               u64 *__restrict__ cnt) {
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    const long long b = indptr[q], e = indptr[q + 1];
+    unsigned err = 0;
+    long long prev = -1;
+    float A = 0.0f;  // the canonical mass chain over the stored values in order (a stored +-0 adds nothing)
+    u64 dropped = 0;
+    for (long long j = b; j < e; ++j) {
+        const long long f = indices[j];
+        const float v = vals ? vals[j] : 1.0f;
+        if (f < 0 || f >= F) err |= SP_ERR_RANGE;
+        else if (f <= prev) err |= SP_ERR_ORDER;
+        prev = f;
+        if (!isfinite(v)) err |= SP_ERR_VALUE;
+        else if (v < 0.0f) err |= SP_ERR_NEGATIVE;
+        A = A + v;
+        const bool keep = v > 0.0f && err == 0u;
+        xraw[j] = v;
+        keys[j] = keep ? (((u64)f << 32) | (u64)q) : ((u64)F << 32);  // (F << 32: after every posting)
+        pos[j] = (unsigned)j;
+        efeat[j] = -1;
+        dropped += keep ? 0 : 1;
+    }
+    if (!isfinite(A)) err |= SP_ERR_MASS;  // (+inf from finite values: the union of a pair would be infinite)
+    mass[q] = A;
+    zero[q] = A > 0.0f ? 0 : 1;
+    if (!(A > 0.0f)) atomicAdd(&cnt[SP_CNT_ZERO], 1ull);
+    if (err) atomicOr(&cnt[SP_CNT_ERR], (u64)err);
+    if (dropped) atomicAdd(&cnt[SP_CNT_DROPPED], dropped);
+}
+
 __global__ __launch_bounds__(256) void sp_run_flags_kernel(long long m, const u64 *__restrict__ keys,
                                                            int *__restrict__ flag) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -158,7 +215,8 @@ __global__ __launch_bounds__(256) void sp_run_flags_kernel(long long m, const u6
 }
 
 // S2: sorted postings -> run offsets, rows, values, and each stored entry's run id (features renumbered densely in
-// ascending order, so no array is as long as F); xhat = pval = null (Jaccard): no values
+// ascending order, so no array is as long as F); xhat = pval = null (Jaccard): no values; weighted Jaccard: xhat
+// holds the raw values
 __global__ __launch_bounds__(256) void sp_postings_kernel(long long m, const u64 *__restrict__ keys,
                                                           const unsigned *__restrict__ pos,
                                                           const int *__restrict__ run_incl,
@@ -263,22 +321,25 @@ __device__ __forceinline__ long long sp_lower_bound(const int *__restrict__ a, l
     return lo;
 }
 
-// S3 / S3r (METRIC = FDR_METRIC_COSINE) and S3j / S3rj (FDR_METRIC_JACCARD: xhat = pval = null, asize = the set
-// sizes): one wave (one workgroup) per query; the queries are the rows q0 + blockIdx.x (S3) or the heavy list's (S3r),
-// and query q writes row q - q0 of idx_out / dist_out
+// S3 / S3r (METRIC = FDR_METRIC_COSINE), S3j / S3rj (FDR_METRIC_JACCARD: xhat = pval = null, asize = the set sizes)
+// and S3w / S3rw (FDR_METRIC_WEIGHTED_JACCARD: xhat / pval = the raw values, mass = the rows' masses): one wave (one
+// workgroup) per query; the queries are the rows q0 + blockIdx.x (S3) or the heavy list's (S3r), and query q writes
+// row q - q0 of idx_out / dist_out
 template <bool RANGE, int METRIC>
 __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q0, const long long *__restrict__ indptr,
                                                         const int *__restrict__ efeat, const float *__restrict__ xhat,
                                                         const long long *__restrict__ runptr,
                                                         const int *__restrict__ prow, const float *__restrict__ pval,
                                                         const int *__restrict__ asize,
+                                                        const float *__restrict__ mass,
                                                         const unsigned char *__restrict__ zero, int k,
                                                         const int *__restrict__ zidx, const float *__restrict__ zdist,
                                                         int *__restrict__ heavy, u64 *__restrict__ cnt,
                                                         int *__restrict__ idx_out, float *__restrict__ dist_out) {
     __shared__ u64 buf[SP_LIST + SP_CAP];  // [0, k): the query's list; [SP_LIST, ...): the table, then the sort buffer
     int *tab = reinterpret_cast<int *>(buf + SP_LIST);  // slot s: tab[2 s] = target row (SP_EMPTY), tab[2 s + 1] = acc
-    constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;  // (... or the int32 count of shared features)
+    constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;  // (... or the int32 count of shared features: no values)
+    constexpr bool WJ = METRIC == FDR_METRIC_WEIGHTED_JACCARD;  // (acc = the fp32 chain of the minima)
     const int lane = threadIdx.x;
     const long long q = RANGE ? (long long)heavy[blockIdx.x] : q0 + (long long)blockIdx.x;
     int *out_i = idx_out + (q - q0) * k;
@@ -292,6 +353,7 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q
     }
     const long long qb = indptr[q], qe = indptr[q + 1];
     const int qa = JAC ? asize[q] : 0;  // |S_q|
+    const double qm = WJ ? (double)mass[q] : 0.0;  // A_q
     for (int i = lane; i < SP_LIST; i += 64) buf[i] = KEY_INF;
     const long long nranges = RANGE ? (n + SP_W - 1) / SP_W : 1;
     const u64 lt = (1ull << lane) - 1ull;
@@ -338,6 +400,9 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q
                         if (s >= 0) {
                             if (JAC) {
                                 tab[2 * s + 1] += 1;  // (a new slot holds 0; one lane per target in a step)
+                            } else if (WJ) {
+                                float *a = reinterpret_cast<float *>(&tab[2 * s + 1]);
+                                *a = (isnew ? 0.0f : *a) + fminf(v, pval[e]);
                             } else {
                                 float *a = reinterpret_cast<float *>(&tab[2 * s + 1]);
                                 *a = __builtin_fmaf(v, pval[e], isnew ? 0.0f : *a);
@@ -367,6 +432,10 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q
                     const int c = (int)(unsigned)(w >> 32);
                     const int u = qa + asize[t] - c;
                     d = (float)((double)(u - c) / (double)u);
+                } else if (WJ) {  // m <= min(A_q, A_t) on the bits and both > 0: u >= max(A_q, A_t) > 0
+                    const double m = (double)__uint_as_float((unsigned)(w >> 32));
+                    const double u = (qm + (double)mass[t]) - m;
+                    d = (float)((u - m) / u);
                 } else {
                     d = dist_from_sim(__uint_as_float((unsigned)(w >> 32)));
                 }
@@ -431,13 +500,14 @@ static int sp_search(fdr_ctx *ctx, int64_t n, int32_t k, int64_t q_lo, int64_t n
     const hipStream_t st = ctx->stream;
     SparseIndex &sp = ctx->sp;
     constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;
+    constexpr bool WJ = METRIC == FDR_METRIC_WEIGHTED_JACCARD;
     static_assert(SP_CNT_ZEROQ == SP_CNT_HEAVY + 1, "one read-back for both");
     auto launch = [&](auto range, unsigned grid) {  // S3 (std::false_type) or S3r (std::true_type)
         hipLaunchKernelGGL((knn_sparse_kernel<decltype(range)::value, METRIC>), dim3(grid), dim3(64), 0, st, (long long)n,
                            (long long)q_lo, sp.indptr.ptr(), sp.efeat.ptr(), JAC ? nullptr : sp.xhat.ptr(),
                            sp.runptr.ptr(), sp.posting_rows(), JAC ? nullptr : sp.pval.ptr(),
-                           JAC ? sp.asize.ptr() : nullptr, sp.zero.ptr(), (int)k, sp.zidx(), sp.zdist(), sp.heavy.ptr(),
-                           sp.cnt.ptr(), d_idx, d_dist);
+                           JAC ? sp.asize.ptr() : nullptr, WJ ? sp.mass.ptr() : nullptr, sp.zero.ptr(), (int)k,
+                           sp.zidx(), sp.zdist(), sp.heavy.ptr(), sp.cnt.ptr(), d_idx, d_dist);
     };
     launch(std::false_type{}, (unsigned)nq);
     HIP_TRY(hipGetLastError());
@@ -457,9 +527,10 @@ static int sp_build(fdr_ctx *ctx, const char *who, int32_t metric, int64_t n, in
                     const int32_t *indices, const float *values) {
     int rc;
     ctx->sp.built = {};
-    const bool jac = metric == FDR_METRIC_JACCARD;
-    if (!jac && metric != FDR_METRIC_COSINE)
-        return fail(FDR_E_ARG, "%s: unknown metric %d (FDR_METRIC_COSINE, FDR_METRIC_JACCARD)", who, metric);
+    const bool jac = metric == FDR_METRIC_JACCARD, wj = metric == FDR_METRIC_WEIGHTED_JACCARD;
+    if (!jac && !wj && metric != FDR_METRIC_COSINE)
+        return fail(FDR_E_ARG, "%s: unknown metric %d (FDR_METRIC_COSINE, FDR_METRIC_JACCARD, "
+                    "FDR_METRIC_WEIGHTED_JACCARD)", who, metric);
     if (!indptr) return fail(FDR_E_ARG, "%s: null pointer", who);
     if (n < 1) return fail(FDR_E_ARG, "%s: need at least one row, got n = %lld", who, (long long)n);
     if (n > INT32_MAX) return fail(FDR_E_ARG, "%s: n (%lld) must be below 2^31 rows", who, (long long)n);
@@ -479,6 +550,7 @@ static int sp_build(fdr_ctx *ctx, const char *who, int32_t metric, int64_t n, in
     if (values && (rc = sp.values.reserve(m1))) return rc;
     if (!jac && (rc = sp.xhat.reserve(m1))) return rc;
     if (jac && (rc = sp.asize.reserve((size_t)n))) return rc;
+    if (wj && (rc = sp.mass.reserve((size_t)n))) return rc;
     if ((rc = sp.keys.reserve(m1))) return rc;
     if ((rc = sp.sorted_keys.reserve(m1))) return rc;
     if ((rc = sp.pos.reserve(m1))) return rc;
@@ -500,6 +572,10 @@ static int sp_build(fdr_ctx *ctx, const char *who, int32_t metric, int64_t n, in
         hipLaunchKernelGGL(sp_rows_jaccard_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n,
                            (long long)n_features, sp.indptr.ptr(), sp.indices.ptr(), values ? sp.values.ptr() : nullptr,
                            sp.asize.ptr(), sp.keys.ptr(), sp.pos.ptr(), sp.efeat.ptr(), sp.zero.ptr(), cnt);
+    } else if (wj) {
+        hipLaunchKernelGGL(sp_rows_wjaccard_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n,
+                           (long long)n_features, sp.indptr.ptr(), sp.indices.ptr(), values ? sp.values.ptr() : nullptr,
+                           sp.xhat.ptr(), sp.mass.ptr(), sp.keys.ptr(), sp.pos.ptr(), sp.efeat.ptr(), sp.zero.ptr(), cnt);
     } else {
         hipLaunchKernelGGL(sp_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n,
                            (long long)n_features, sp.indptr.ptr(), sp.indices.ptr(), values ? sp.values.ptr() : nullptr,
@@ -514,6 +590,11 @@ static int sp_build(fdr_ctx *ctx, const char *who, int32_t metric, int64_t n, in
     if (h_cnt[SP_CNT_ERR] & SP_ERR_ORDER)
         return fail(FDR_E_ARG, "%s: feature indices must be strictly ascending inside a row", who);
     if (h_cnt[SP_CNT_ERR] & SP_ERR_VALUE) return fail(FDR_E_ARG, "%s: non-finite value", who);
+    if (h_cnt[SP_CNT_ERR] & SP_ERR_NEGATIVE)
+        return fail(FDR_E_ARG, "%s: negative value (the weighted Jaccard metric takes values >= 0)", who);
+    if (h_cnt[SP_CNT_ERR] & SP_ERR_MASS)
+        return fail(FDR_E_ARG, "%s: a row's fp32 sum of values is not finite (the weighted Jaccard metric needs a "
+                    "finite mass per row)", who);
     const long long kept = (long long)nnz - (long long)h_cnt[SP_CNT_DROPPED];
     if (kept > 0) {
         int end_bit = 32;
@@ -568,8 +649,12 @@ static int sp_search_range(fdr_ctx *ctx, int32_t k, int64_t q_lo, int64_t q_hi, 
                                (long long)q_lo, (long long)q_hi, sp.zero.ptr(), sp.cnt.ptr());
             HIP_TRY(hipGetLastError());
         }
-        rc = sp.built.metric == FDR_METRIC_JACCARD ? sp_search<FDR_METRIC_JACCARD>(ctx, n, k, q_lo, nq, d_idx, d_dist, h)
-                                                   : sp_search<FDR_METRIC_COSINE>(ctx, n, k, q_lo, nq, d_idx, d_dist, h);
+        if (sp.built.metric == FDR_METRIC_JACCARD)
+            rc = sp_search<FDR_METRIC_JACCARD>(ctx, n, k, q_lo, nq, d_idx, d_dist, h);
+        else if (sp.built.metric == FDR_METRIC_WEIGHTED_JACCARD)
+            rc = sp_search<FDR_METRIC_WEIGHTED_JACCARD>(ctx, n, k, q_lo, nq, d_idx, d_dist, h);
+        else
+            rc = sp_search<FDR_METRIC_COSINE>(ctx, n, k, q_lo, nq, d_idx, d_dist, h);
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(idx_out, d_idx, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(dist_out, d_dist, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
@@ -592,8 +677,9 @@ static int sp_knn(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, c
     if (rc) return rc;
     knn_call_begin(ctx);
     ctx->sp.built = {};  // (the call replaces the context's index, also where it is refused before the build)
-    if (metric != FDR_METRIC_JACCARD && metric != FDR_METRIC_COSINE)
-        return fail(FDR_E_ARG, "knn_sparse: unknown metric %d (FDR_METRIC_COSINE, FDR_METRIC_JACCARD)", metric);
+    if (metric != FDR_METRIC_JACCARD && metric != FDR_METRIC_WEIGHTED_JACCARD && metric != FDR_METRIC_COSINE)
+        return fail(FDR_E_ARG, "knn_sparse: unknown metric %d (FDR_METRIC_COSINE, FDR_METRIC_JACCARD, "
+                    "FDR_METRIC_WEIGHTED_JACCARD)", metric);
     if (!indptr || !idx_out || !dist_out) return fail(FDR_E_ARG, "knn_sparse: null pointer");
     if (k < 1 || k > FDR_MAX_K) return fail(FDR_E_ARG, "knn_sparse: k=%d unsupported (1..%d)", k, FDR_MAX_K);
     if (n < k) return fail(FDR_E_ARG, "knn_sparse: need n (%lld) >= k (%d)", (long long)n, k);

@@ -177,8 +177,8 @@ def sparse_knn_rank(ctx, indptr, indices, values, n_features, k, rank, world, me
 
     No collective and no process group: a search is one independent wave per query, so the ranks' results,
     concatenated in rank order, are the one-GPU answer bit for bit.  The price is a replicated index: EVERY rank
-    uploads the full CSR and holds about 52 (cosine) or 44 (Jaccard) device bytes per stored entry, plus the
-    sort's temporary storage of about 12 more (64 measured at 1 M reads, cosine), and pays the O(nnz) build; only
+    uploads the full CSR and holds about 52 (cosine, weighted Jaccard) or 44 (Jaccard) device bytes per stored entry,
+    plus the sort's temporary storage of about 12 more (64 measured at 1 M reads, cosine), and pays the O(nnz) build; only
     the search, sum over the features of df^2, is divided by the ranks (by row count, not by cost).  The index is
     freed before the call returns."""
     with ctx.sparse_index(indptr, indices, values, n_features, metric=metric) as index:  # (checks the CSR first)

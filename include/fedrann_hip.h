@@ -139,22 +139,38 @@ int fdr_knn_sparse(fdr_ctx *ctx, int64_t n, int64_t n_features, const int64_t *i
  * smallest row indices not already in it.  An empty query: the first k empty rows at distance 0, then the first
  * non-empty rows at distance 1.  Arguments, limits and error codes are those of fdr_knn_sparse; an unknown metric is
  * FDR_E_ARG.  fdr_last_knn_trace reports FDR_TRACE_SPARSE (zero_queries = the empty rows).  Cost: ~4 bytes per
- * row-pair update (the posting entry is the row alone). */
+ * row-pair update (the posting entry is the row alone).
+ * FDR_METRIC_WEIGHTED_JACCARD is the exact weighted Jaccard (Ruzicka) distance of rows with values >= 0, 1 - sum of
+ * minima / sum of maxima.  A stored +-0 is an absent entry; values NULL: every stored entry is
+ * 1.  The mass A_r of a row is the fp32 chain A <- A + x over its stored values in stored order from +0.  The shared
+ * weight m(q, t) is the fp32 chain m <- m + min(x_q, x_t) over the features both rows hold with a value > 0, in
+ * ascending feature order from +0 (plain fp32 additions, denormals kept).  u = ((double)A_q + (double)A_t) - (double)m
+ * in that order: dist = 0.0f if u == 0 (two zero-mass rows), else (float)((u - (double)m) / u), one IEEE double
+ * division and one round-to-nearest conversion.  fp32 addition is monotone, so m <= min(A_q, A_t) on the bits and
+ * dist lies in [0, 1]; a row is at 0 from itself and its duplicates; with every value 1 and fewer than 2^24 entries
+ * per row the result has the bits of FDR_METRIC_JACCARD.  Order (distance bits, index) ascending, self a candidate;
+ * rows that share nothing, and pairs whose quotient rounds to 1.0f, are distance-1 rows taken in index order.  A
+ * zero-mass query: the first k zero-mass rows at distance 0, then the first other rows at distance 1 (zero_queries
+ * counts them).  Refused with FDR_E_ARG, the cause in fdr_last_error: a negative value, a non-finite value, a row
+ * whose mass chain is not finite (an overflow to +inf from finite values).  Otherwise arguments, limits and error
+ * codes are those of fdr_knn_sparse.  Cost: that of the cosine search, ~8 bytes per row-pair update. */
 #define FDR_METRIC_COSINE 0
 #define FDR_METRIC_JACCARD 1
+#define FDR_METRIC_WEIGHTED_JACCARD 2
 int fdr_knn_sparse_metric(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
                           const int32_t *indices, const float *values, int32_t k, int32_t *idx_out, float *dist_out);
 
 /* ---- the sparse search in two steps: build the index once, search row ranges of it  (a host that searches in query
  *      blocks, at several k, or one rank's rows of a row-sharded run: fedrann_amd.distributed.sparse_knn_rank) -------
  * fdr_sparse_index_build does everything of fdr_knn_sparse_metric that does not depend on k or on the queries: the
- * argument checks, the upload of the CSR, the rows' norms (set sizes) and zero flags, the sorted postings.  The index
+ * argument checks, the upload of the CSR, the rows' norms (set sizes, masses) and zero flags, the sorted postings.  The index
  * stays in the context, which holds ONE: a build replaces it, and so does every fdr_knn_sparse / fdr_knn_sparse_metric,
  * which is a build followed by a search of [0, n) through the same code (after it, its index is the context's; where
  * it is refused or fails, at any point, the context holds none).  No
  * other call on the context touches the index (fdr_knn, fdr_embed_knn, the _dev calls, the k-mer calls).  Arguments,
  * limits and error codes are those of fdr_knn_sparse_metric, except that there is no k: 1 <= n < 2^31.  A build that
- * is refused (also on the device: an index out of range or out of order, a non-finite value; FDR_E_ARG) or that fails
+ * is refused (also on the device: an index out of range or out of order, a non-finite value, under
+ * FDR_METRIC_WEIGHTED_JACCARD a negative value or a row mass that is not finite; FDR_E_ARG) or that fails
  * leaves NO index, not the earlier one.  Host pointers; the call synchronises. */
 int fdr_sparse_index_build(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
                            const int32_t *indices, const float *values);
@@ -169,10 +185,11 @@ int fdr_sparse_index_build(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_fe
  * zero_queries / range_queries counting the queries of this call. */
 int fdr_sparse_index_search(fdr_ctx *ctx, int32_t k, int64_t q_lo, int64_t q_hi, int32_t *idx_out, float *dist_out);
 /* The context's index (FDR_E_STATE without one); every out pointer may be NULL.  postings: the stored entries that
- * got a posting (cosine: scaled value not +-0; Jaccard: value not +-0).  zero_rows: zero rows (Jaccard: empty rows).
+ * got a posting (cosine: scaled value not +-0; Jaccard: value not +-0; weighted Jaccard: value > 0).  zero_rows: zero
+ * rows (Jaccard: empty rows; weighted Jaccard: zero-mass rows).
  * device_bytes: the device memory the sparse path holds for the context, the build's scratch (unsorted keys, sort
- * buffers) included, which is kept so that the next build allocates nothing: about 52 (cosine) or 44 (Jaccard) bytes
- * per stored entry in the library's own buffers, and the radix sort's temporary storage on top, about 12 more (64 per
+ * buffers) included, which is kept so that the next build allocates nothing: about 52 (cosine, weighted Jaccard) or 44
+ * (Jaccard) bytes per stored entry in the library's own buffers, and the radix sort's temporary storage on top, about 12 more (64 per
  * stored entry measured at 1 M synthetic reads, cosine).  Buffers only grow: after a larger index the figure is the
  * larger one's. */
 int fdr_sparse_index_info(fdr_ctx *ctx, int32_t *metric, int64_t *n, int64_t *postings, int64_t *zero_rows,
