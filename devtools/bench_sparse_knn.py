@@ -1,7 +1,7 @@
 """Time the exact sparse k-NN (fdr_knn_sparse) on synthetic reads with IDF values, next to the projected search.
 
     python devtools/bench_sparse_knn.py [--reads 100000 1000000] [--k 20] [--steps 3] [--metric cosine|jaccard|weighted_jaccard]
-                                        [--values idf|none] [--split] [--world W --rank r] [--block-rows B]
+                                        [--values idf|none] [--split] [--world W --rank r] [--block-rows B] [--external]
 
 Rows: synth(R, doubling=True) (2 R rows), value of feature f = idf[f] (what --no-projection searches).  For each size
 it prints one JSON line: the median wall time of the knn_sparse call (host arrays in, results out: it synchronises;
@@ -19,6 +19,10 @@ of every row of one index, results copied out), with "index" = SparseIndex.info(
 --world W --rank r (implies the index) times the search of that rank's rows of shard_rows(n, W) alone, in query
 blocks of --block-rows rows if given ("rank_search_ms", "rank_rows"): what one rank of distributed.sparse_knn_rank
 searches after its build.
+--external (implies the index) times SparseIndex.query of the index's OWN rows, passed as a query CSR, against
+SparseIndex.search of the same rows, alternating the two calls ("ext_search_ms", "ext_query_ms", each with its _all
+list): the same search kernels on the same rows with the same results, so "ext_extra_ms" = query - search is the
+queries' upload, their row kernel and the run lookup, and "ext_extra_share" is that over the search.
 """
 import argparse
 import json
@@ -58,6 +62,8 @@ def main():
     ap.add_argument("--world", type=int, default=0, help="with --rank: time the search of one rank's rows of the index")
     ap.add_argument("--rank", type=int, default=0)
     ap.add_argument("--block-rows", type=int, default=None, help="with --world: search in query blocks of this many rows")
+    ap.add_argument("--external", action="store_true",
+                    help="time SparseIndex.query of the index's own rows against SparseIndex.search of them")
     a = ap.parse_args()
     ctx = _lib.Context(int(os.environ.get("FEDRANN_DEVICE", "0")))
     for R in a.reads:
@@ -77,7 +83,7 @@ def main():
                "values": "none" if values is None else "idf", "sparse_ms": round(ms, 2), "sparse_ms_all": all_ms,
                "posting_GBps": round(entry_bytes * sum_df2 / (ms * 1e-3) / 1e9, 1), "range_queries": trace["range_queries"],
                "zero_queries": trace["zero_queries"]}
-        if a.split or a.world:
+        if a.split or a.world or a.external:
             from fedrann_amd.distributed import sparse_rank_blocks
 
             def build():  # (no close(): the next build replaces the index and reuses its buffers)
@@ -90,6 +96,26 @@ def main():
                 if a.split:
                     ms, out["search_ms_all"] = _median_ms(lambda: index.search(a.k), a.steps)
                     out["search_ms"] = round(ms, 2)
+                if a.external:
+                    t_search, t_query = [], []
+                    index.search(a.k)  # warm-up: allocations, first launches
+                    index.query(indptr, indices, values, a.k)
+                    for _ in range(a.steps):
+                        t0 = time.perf_counter()
+                        want = index.search(a.k)
+                        t1 = time.perf_counter()
+                        got = index.query(indptr, indices, values, a.k)
+                        t2 = time.perf_counter()
+                        t_search.append((t1 - t0) * 1e3)
+                        t_query.append((t2 - t1) * 1e3)
+                    if not (np.array_equal(got[0], want[0]) and
+                            np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32))):
+                        raise SystemExit("query of the index's own rows differs from the search of them")
+                    sm, qm = float(np.median(t_search)), float(np.median(t_query))
+                    out.update(ext_search_ms=round(sm, 2), ext_search_ms_all=[round(x, 2) for x in t_search],
+                               ext_query_ms=round(qm, 2), ext_query_ms_all=[round(x, 2) for x in t_query],
+                               ext_extra_ms=round(qm - sm, 2), ext_extra_share=round((qm - sm) / sm, 4),
+                               index_after_query=index.info())
                 if a.world:
                     lo, hi, blocks = sparse_rank_blocks(n, a.rank, a.world, a.block_rows)
                     res = (np.empty((hi - lo, a.k), np.int32), np.empty((hi - lo, a.k), np.float32))

@@ -26,6 +26,7 @@ SYMBOLS = (
     "fdr_last_range_sets", "fdr_knn_sparse", "fdr_set_live_chunks", "fdr_knn_sparse_metric",
     "fdr_set_live_skip", "fdr_last_live_stage_lists",
     "fdr_sparse_index_build", "fdr_sparse_index_search", "fdr_sparse_index_info", "fdr_sparse_index_free",
+    "fdr_sparse_index_query",
 )
 FDR_MAX_K = 128
 KERNELS = ("embed_csr", "normalize_rows", "knn_tile", "knn_merge", "knn_prefilter", "knn_rerank",
@@ -110,6 +111,7 @@ def load_library():
     L.fdr_knn_sparse_metric.argtypes = [vp, i32, i64, i64, vp, vp, vp, i32, vp, vp]
     L.fdr_sparse_index_build.argtypes = [vp, i32, i64, i64, vp, vp, vp]
     L.fdr_sparse_index_search.argtypes = [vp, i32, i64, i64, vp, vp]
+    L.fdr_sparse_index_query.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp]
     L.fdr_sparse_index_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i64),
                                         ctypes.POINTER(i64), ctypes.POINTER(sz)]
     L.fdr_sparse_index_free.argtypes = [vp]
@@ -368,6 +370,22 @@ def check_sparse_search(n, k, lo=0, hi=None):
     return k, lo, hi
 
 
+def check_sparse_queries(n, n_features, metric, indptr, indices, values, k):
+    """The argument checks of SparseIndex.query on an index of n rows and n_features columns under `metric`
+    (fdr_sparse_index_query repeats them on the device); needs no GPU.  The query CSR is checked as
+    check_sparse_rows checks the indexed one (ids in [0, n_features), strictly ascending inside a row; finite values;
+    metric="weighted_jaccard": none negative and a finite mass per row), but it may hold any number of rows, none
+    included, and empty rows; 1 <= k <= min(FDR_MAX_K, n) as in check_sparse_search.  Returns (nq, k)."""
+    sparse_metric_code(metric)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError("k must be an integer, got %r" % (k,))
+    k = check_sparse_search(int(n), k)[0]
+    nq = _check_sparse(indptr, indices, values, n_features, None, metric, min_rows=0)[0]
+    if nq > np.iinfo(np.int32).max or indices.size > np.iinfo(np.int32).max:
+        raise ValueError("need fewer than 2^31 query rows and stored entries")
+    return nq, k
+
+
 def _row_mass_overflows(indptr, values, largest):
     """Whether a row's float32 add chain over its values (all finite and >= 0, none above `largest`) reaches +inf.  A
     chain of m such terms is at most m * largest * (1 + 2^-24)^m, below 1.07e38 for m <= 2^20 and m * largest < 1e38;
@@ -381,8 +399,8 @@ def _row_mass_overflows(indptr, values, largest):
     return False
 
 
-def _check_sparse(indptr, indices, values, n_features, k, metric="cosine"):
-    """k=None: no k to check, but n >= 1."""
+def _check_sparse(indptr, indices, values, n_features, k, metric="cosine", min_rows=1):
+    """k=None: no k to check, but n >= min_rows."""
     for name, a, dt in (("indptr", indptr, np.int64), ("indices", indices, np.int32), ("values", values, np.float32)):
         if a is None and name == "values":
             continue
@@ -398,7 +416,7 @@ def _check_sparse(indptr, indices, values, n_features, k, metric="cosine"):
     if not 1 <= F <= np.iinfo(np.int32).max:
         raise ValueError("n_features must be in [1, 2^31)")
     if k is None:
-        if n < 1:
+        if n < min_rows:
             raise ValueError("need at least one row")
     elif not 1 <= k <= FDR_MAX_K or k > n:
         raise ValueError("need 1 <= k <= min(%d, n = %d), got k = %d" % (FDR_MAX_K, n, k))
@@ -766,7 +784,7 @@ class Context:
         self._sparse_gen += 1
         self._check(self._L.fdr_sparse_index_build(self._h, code, n, F, _ptr(indptr), _ptr(indices), _ptr(values)),
                     "fdr_sparse_index_build")
-        return SparseIndex(self, n, metric, self._sparse_gen)
+        return SparseIndex(self, n, metric, self._sparse_gen, n_features=F)
 
     def embed_knn(self, a_indptr, a_indices, k, return_embedding=False, out=None):
         """out=(idx int32 [n,k], dist float32 [n,k]): caller-owned (e.g. pinned, reused) result arrays."""
@@ -827,8 +845,9 @@ class SparseIndex:
     The index lives in the context, which holds one: once the context has built another (sparse_index, knn_sparse),
     or after close(), search and info raise FedrannHipError."""
 
-    def __init__(self, ctx, n, metric, gen):
+    def __init__(self, ctx, n, metric, gen, n_features=None):
         self._ctx, self.n, self.metric, self._gen = ctx, int(n), metric, gen
+        self.n_features = None if n_features is None else int(n_features)  # (None: query() is not available)
         self._open = True
 
     def _live(self, what):
@@ -856,6 +875,45 @@ class SparseIndex:
         self._live("SparseIndex.search")
         c = self._ctx
         c._check(c._L.fdr_sparse_index_search(c._h, k, lo, hi, _ptr(idx), _ptr(dist)), "fdr_sparse_index_search")
+        return idx, dist
+
+    def query(self, indptr, indices, values, k, out=None, block_rows=None):
+        """Neighbours, among the n rows of the index, of query rows that need not be in it: a CSR of their own (indptr
+        int64 [nq + 1], indices int32 in [0, n_features) ascending inside a row, values float32 or None: every stored
+        entry 1, whatever the index was built with).  Returns (idx int32 [nq, k], dist float32 [nq, k]), idx holding
+        rows of the index: fdr_sparse_index_query, under the rules of the index's metric with the query's norm, set
+        size or mass formed as a row's of the index is, so the rows [lo, hi) of the indexed CSR give search(k, lo, hi)
+        bit for bit.  A zero (empty, zero-mass) query gets the index's first k zero rows at 0, then its first other
+        rows at 1.  block_rows: the queries go to the device in consecutive blocks of at most that many rows, each
+        with its indptr rebased to 0 (one C call per block: the device's result buffers hold block_rows * k entries);
+        the bits do not depend on it.  out=(idx, dist): caller-owned C-contiguous result arrays."""
+        if self.n_features is None:
+            raise ValueError("SparseIndex.query needs the index's n_features")
+        nq, k = check_sparse_queries(self.n, self.n_features, self.metric, indptr, indices, values, k)
+        if block_rows is not None and (isinstance(block_rows, bool) or not isinstance(block_rows, (int, np.integer))
+                                       or int(block_rows) < 1):
+            raise ValueError("block_rows must be an integer >= 1, got %r" % (block_rows,))
+        if out is None:
+            idx = np.empty((nq, k), dtype=np.int32)
+            dist = np.empty((nq, k), dtype=np.float32)
+        else:
+            idx, dist = out
+            if (idx.shape, dist.shape) != ((nq, k), (nq, k)) or idx.dtype != np.int32 or dist.dtype != np.float32 \
+                    or not (idx.flags.c_contiguous and dist.flags.c_contiguous):
+                raise ValueError("out must be C-contiguous (int32 [nq, k], float32 [nq, k])")
+        self._live("SparseIndex.query")
+        c = self._ctx
+        step = max(nq, 1) if block_rows is None else int(block_rows)
+        for a in range(0, max(nq, 1), step):  # (nq = 0: one call, which records the trace)
+            b = min(nq, a + step)
+            if a == 0 and b == nq:
+                ip, ix, vals = indptr, indices, values
+            else:
+                ip = np.ascontiguousarray(indptr[a:b + 1] - indptr[a])
+                ix = indices[indptr[a]:indptr[b]]
+                vals = None if values is None else values[indptr[a]:indptr[b]]
+            c._check(c._L.fdr_sparse_index_query(c._h, k, b - a, _ptr(ip), _ptr(ix), _ptr(vals), _ptr(idx[a:b]),
+                                                 _ptr(dist[a:b])), "fdr_sparse_index_query")
         return idx, dist
 
     def info(self):

@@ -641,13 +641,15 @@ struct SparseIndex {
     DevArray<int> efeat;             // each stored entry's run (-1: no posting)
     DevArray<float> pval;            // the postings' values (cosine, weighted Jaccard)
     DevArray<long long> runptr;      // [runs + 1] the runs' first postings
+    DevArray<int> runfeat;           // [runs] the runs' features, ascending: how a query row outside the index finds a run
     DevArray<int> heavy;             // [n] a search's queries for S3r
-    DevArray<u64> cnt;               // SP_CNT_* counters in [0, 8); behind them zidx() and zdist()
+    DevArray<u64> cnt;               // SP_CNT_* counters in [0, 8) (SP_CNT_RUNS: the number of runs); behind them zidx() and zdist()
     DevArray<char> tmp;              // rocprim's temporary storage
     struct Built {  // the index these hold; none after a refused or failed build
         bool valid = false;
         int metric = 0;
         long long n = 0, kept = 0, nzero = 0;  // rows, postings, zero (Jaccard: empty) rows
+        long long n_features = 0;              // the columns: the ids a query row may hold
     } built;
     // The sort has read the unsorted keys, and nothing reads them again: their 8 bytes per stored entry hold two int32
     // per posting (kept <= stored entries), the run-start flags in [0, kept) and the inclusive run numbers behind them.
@@ -664,7 +666,7 @@ struct SparseIndex {
     template <class F>
     auto each(F f) {
         return f(indptr, indices, values, xhat, asize, mass, zero, keys, sorted_keys, pos, sorted_pos, efeat, pval, runptr,
-                 heavy, cnt, tmp);
+                 runfeat, heavy, cnt, tmp);
     }
     size_t bytes() {  // fdr_sparse_index_info: everything held, the build's scratch included
         return each([](auto &...a) { return (a.bytes() + ...); });
@@ -672,6 +674,30 @@ struct SparseIndex {
     void release() {
         each([](auto &...a) { release_all(a...); });
         built = {};
+    }
+};
+
+// The query rows of fdr_sparse_index_query (knn_sparse.inc): a CSR of rows that need not be in the index, uploaded per
+// call, and what S1q makes of them, the query side of that call's search.  Grows as needed; released with the index.
+struct SparseQuerySet {
+    DevArray<long long> indptr;    // [nq + 1] the query rows
+    DevArray<int> indices;         // the stored entries' features ...
+    DevArray<float> values;        // ... their values, as given (absent: every entry 1) ...
+    DevArray<float> xhat;          // ... normalised (cosine); raw (weighted Jaccard)
+    DevArray<int> efeat;           // each stored entry's run in the INDEX (-1: none)
+    DevArray<int> asize;           // [nq] the set sizes (Jaccard)
+    DevArray<float> mass;          // [nq] the masses (weighted Jaccard)
+    DevArray<unsigned char> zero;  // [nq] zero (empty, zero-mass) queries
+    DevArray<int> heavy;           // [nq] the call's queries for S3r
+    template <class F>
+    auto each(F f) {
+        return f(indptr, indices, values, xhat, efeat, asize, mass, zero, heavy);
+    }
+    size_t bytes() {
+        return each([](auto &...a) { return (a.bytes() + ...); });
+    }
+    void release() {
+        each([](auto &...a) { release_all(a...); });
     }
 };
 
@@ -697,6 +723,7 @@ struct fdr_ctx {
     KmerSearchScratch ks;  // k-mer search, k-mer count / merge (kmer_search.inc): both released at every fetch
     KmerCountScratch kc;
     SparseIndex sp;        // sparse k-NN (knn_sparse.inc): kept until fdr_sparse_index_free
+    SparseQuerySet spq;    // ... and the query rows of fdr_sparse_index_query, released with it
     // timing: when enabled, every launch of kernel kind i gets its own hipEvent pair on the launch
     // stream; fdr_timing_read() sums the elapsed times of all launches since the last read
     int knn_mode = FDR_MODE_AUTO;

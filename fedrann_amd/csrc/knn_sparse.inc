@@ -11,7 +11,8 @@
 //                          checks (ids in [0, F), strictly ascending; finite values); one posting key per stored
 //                          entry whose xhat is not +-0 (an entry with xhat = +-0 cannot change an accumulator)
 //   (rocprim radix sort of (feature << 32 | row) keys: the postings, ascending by row inside a feature)
-//   S2 sp_postings_kernel  per-feature runs: run offsets (int64), posting rows / values, each entry's run id
+//   S2 sp_postings_kernel  per-feature runs: run offsets (int64), posting rows / values, each entry's run id, and
+//                          each run's feature id (runfeat, ascending) with the number of runs (cnt[SP_CNT_RUNS])
 //   S3 knn_sparse_kernel   one wave per query: walk the query's features in ascending order; the lanes take the
 //                          feature's posting entries and update an LDS hash table keyed by target row that holds the
 //                          fp32 accumulator.  A target occurs once per feature, so one lane writes a slot per feature
@@ -70,6 +71,22 @@
 // the query rows [q_lo, q_hi) against all n rows: S3's grid is the range, the heavy list and its counter are reset per
 // search, and row q - q_lo of the result buffers (sized by the range) is query q.  fdr_knn_sparse[_metric] is a build
 // and a search of [0, n) through the same two functions.
+//
+// The query side.  S3 / S3r read the TARGETS through the postings (runptr, posting_rows(), pval), the targets' set sizes
+// or masses and S4's closed-form row, and the QUERIES through one small struct of pointers (SpQuerySide: indptr, efeat,
+// xhat, asize, mass, zero, the heavy list) and the first row's number.  A search of the index's own rows passes the
+// index's arrays.  fdr_sparse_index_query passes the arrays of a query set that need not be in the index (ctx->spq,
+// struct SparseQuerySet: uploaded per call, grown as needed, released with the index), after
+//   S1q sp_query_rows_kernel<METRIC>  one thread per query row: the argument checks of S1 / S1j / S1w, the row's rinv /
+//                          xhat, set size or mass and its zero flag -- through sp_row<METRIC>, the one device function
+//                          the build's S1 kernels call too, so a row gives the same bits on either side -- and for
+//                          each stored entry the run of its feature in the index by binary search in runfeat: -1
+//                          where no index row holds the feature or where a build would give the entry no posting.
+// A query feature without a run counts in the query's norm, size or mass and in nothing else.  S4 runs when a QUERY is
+// zero (the index need not hold a zero row), and the zero queries are counted by S1q.  The kernel is the same code
+// for both: the heavy list holds row numbers of the query side and has room for all of its rows, and the result row
+// is q - q0 with q0 = 0 for a query set.  A refused query (the checks of S1q included) has written nothing of the
+// index but the search's counters.
 // ------------------------------------------------------------------------------------------
 #define SP_CAP 1024    // hash-table slots per query (key int32 | fp32 accumulator or int32 count: 8 KiB of LDS)
 #define SP_LOG2CAP 10
@@ -82,59 +99,131 @@ static_assert(SP_LIST + SP_LIMIT + 64 <= SP_LIST + SP_CAP && SP_LIST + SP_W <= S
               "list + candidates of one range fit the sort buffer");
 static_assert((1 << SP_LOG2CAP) == SP_CAP, "SP_CAP is a power of two");
 
-// counters (u64 each): [0, 3) of a build, [3, 5) of a search
+// counters (u64 each): [0, 3) and SP_CNT_RUNS of a build, [3, 6) of a search or a query call
 #define SP_CNT_ERR 0      // or of SP_ERR_* bits
 #define SP_CNT_DROPPED 1  // stored entries without a posting (xhat = +-0; Jaccard: value = +-0; weighted: not > 0)
 #define SP_CNT_ZERO 2     // zero rows (Jaccard: empty rows; weighted Jaccard: zero-mass rows)
 #define SP_CNT_HEAVY 3    // queries handed to the range-split kernel
 #define SP_CNT_ZEROQ 4    // zero (empty) rows among the queries
+#define SP_CNT_QERR 5     // or of SP_ERR_* bits of the query rows (fdr_sparse_index_query)
+#define SP_CNT_RUNS 6     // the index's runs (features with a posting): written by S2, kept with the index
 #define SP_ERR_RANGE 1u
 #define SP_ERR_ORDER 2u
 #define SP_ERR_VALUE 4u
 #define SP_ERR_NEGATIVE 8u  // weighted Jaccard: a value below 0
 #define SP_ERR_MASS 16u     // weighted Jaccard: a row's mass chain is not finite
 
-// S1: one thread per row
+__device__ __forceinline__ long long sp_lower_bound(const int *__restrict__ a, long long lo, long long hi, int v) {
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (a[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// What S1 / S1j / S1w and the query rows' S1q learn of one row
+struct SpRow {
+    unsigned err;  // SP_ERR_* bits
+    u64 dropped;   // stored entries without a posting
+    bool zero;     // the zero rule: norm chain not > 0 (cosine), empty set (Jaccard), mass not > 0 (weighted Jaccard)
+    int a;         // |S_r| (Jaccard)
+    float mass;    // A_r (weighted Jaccard)
+};
+
+// The row arithmetic, once: the argument checks (ids in [0, F), strictly ascending; finite values; weighted Jaccard:
+// no negative value, a finite mass), the norm chain over the stored values in order with rinv (cosine), the set size
+// over the values that are not +-0 (Jaccard), the mass chain in stored order (weighted Jaccard), and the zero rule.
+// entry(j, f, x, keep) is called per stored entry j in stored order: f its feature, x what the postings take of it
+// (cosine: xhat = v * rinv; otherwise the raw value), keep whether a build gives it a posting (cosine: x not +-0;
+// Jaccard: v not +-0; weighted Jaccard: v > 0; never once the row has shown an error).  An index row (the build) and
+// a query row (fdr_sparse_index_query) go through this one function, so a row gives the same bits as either.
+template <int METRIC, class Entry>
+__device__ __forceinline__ SpRow sp_row(long long F, const int *__restrict__ indices, const float *__restrict__ vals,
+                                        long long b, long long e, Entry entry) {
+    constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;
+    constexpr bool WJ = METRIC == FDR_METRIC_WEIGHTED_JACCARD;
+    SpRow r = {0u, 0ull, false, 0, 0.0f};
+    float ri = 0.0f;
+    if (!JAC && !WJ) {
+        float nn = 0.0f;  // the canonical norm chain over the stored values in order (zeros between them add nothing)
+        for (long long j = b; j < e; ++j) {
+            const float v = vals ? vals[j] : 1.0f;
+            nn = __builtin_fmaf(v, v, nn);
+        }
+        if (nn > 0.0f) ri = (float)(1.0 / sqrt((double)nn));
+        r.zero = !(nn > 0.0f);
+    }
+    long long prev = -1;
+    float A = 0.0f;  // the canonical mass chain over the stored values in order (a stored +-0 adds nothing)
+    for (long long j = b; j < e; ++j) {
+        const long long f = indices[j];
+        const float v = vals ? vals[j] : 1.0f;
+        if (f < 0 || f >= F) r.err |= SP_ERR_RANGE;
+        else if (f <= prev) r.err |= SP_ERR_ORDER;
+        prev = f;
+        if (!isfinite(v)) r.err |= SP_ERR_VALUE;
+        else if (WJ && v < 0.0f) r.err |= SP_ERR_NEGATIVE;
+        float x = v;
+        bool keep;
+        if (JAC) {
+            keep = v != 0.0f;  // |S_r|: the stored entries whose value is not +-0
+            r.a += keep ? 1 : 0;
+        } else if (WJ) {
+            A = A + v;
+            keep = v > 0.0f;
+        } else {
+            x = v * ri;
+            keep = x != 0.0f;  // (an entry with xhat = +-0 cannot change an accumulator)
+        }
+        keep = keep && r.err == 0u;
+        entry(j, f, x, keep);
+        r.dropped += keep ? 0 : 1;
+    }
+    if (JAC) r.zero = r.a == 0;
+    if (WJ) {
+        if (!isfinite(A)) r.err |= SP_ERR_MASS;  // (+inf from finite values: the union of a pair would be infinite)
+        r.mass = A;
+        r.zero = !(A > 0.0f);
+    }
+    return r;
+}
+
+// S1 / S1j / S1w: one thread per row.  xhat: cosine, weighted Jaccard (the raw values); asize: Jaccard; mass:
+// weighted Jaccard; the others null
+template <int METRIC>
+__device__ __forceinline__ void sp_build_row(long long n, long long F, const long long *__restrict__ indptr,
+                                             const int *__restrict__ indices, const float *__restrict__ vals,
+                                             float *__restrict__ xhat, int *__restrict__ asize,
+                                             float *__restrict__ mass, u64 *__restrict__ keys,
+                                             unsigned *__restrict__ pos, int *__restrict__ efeat,
+                                             unsigned char *__restrict__ zero, u64 *__restrict__ cnt) {
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    const SpRow r = sp_row<METRIC>(F, indices, vals, indptr[q], indptr[q + 1],
+                                   [&](long long j, long long f, float x, bool keep) {
+                                       if (METRIC != FDR_METRIC_JACCARD) xhat[j] = x;
+                                       // (F << 32: after every posting)
+                                       keys[j] = keep ? (((u64)f << 32) | (u64)q) : ((u64)F << 32);
+                                       pos[j] = (unsigned)j;
+                                       efeat[j] = -1;
+                                   });
+    if (METRIC == FDR_METRIC_JACCARD) asize[q] = r.a;
+    if (METRIC == FDR_METRIC_WEIGHTED_JACCARD) mass[q] = r.mass;
+    zero[q] = r.zero ? 1 : 0;
+    if (r.zero) atomicAdd(&cnt[SP_CNT_ZERO], 1ull);
+    if (r.err) atomicOr(&cnt[SP_CNT_ERR], (u64)r.err);
+    if (r.dropped) atomicAdd(&cnt[SP_CNT_DROPPED], r.dropped);
+}
+
 __global__ __launch_bounds__(256) void sp_rows_kernel(long long n, long long F, const long long *__restrict__ indptr,
                                                       const int *__restrict__ indices, const float *__restrict__ vals,
                                                       float *__restrict__ xhat, u64 *__restrict__ keys,
                                                       unsigned *__restrict__ pos, int *__restrict__ efeat,
                                                       unsigned char *__restrict__ zero, u64 *__restrict__ cnt) {
-    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (q >= n) return;
-    const long long b = indptr[q], e = indptr[q + 1];
-    float nn = 0.0f;  // the canonical norm chain over the stored values in order (zeros between them add nothing)
-    for (long long j = b; j < e; ++j) {
-        const float v = vals ? vals[j] : 1.0f;
-        nn = __builtin_fmaf(v, v, nn);
-    }
-    float ri = 0.0f;
-    if (nn > 0.0f) ri = (float)(1.0 / sqrt((double)nn));
-    zero[q] = nn > 0.0f ? 0 : 1;
-    if (!(nn > 0.0f)) atomicAdd(&cnt[SP_CNT_ZERO], 1ull);
-    unsigned err = 0;
-    long long prev = -1;
-    u64 dropped = 0;
-    for (long long j = b; j < e; ++j) {
-        const long long f = indices[j];
-        const float v = vals ? vals[j] : 1.0f;
-        if (f < 0 || f >= F) err |= SP_ERR_RANGE;
-        else if (f <= prev) err |= SP_ERR_ORDER;
-        prev = f;
-        if (!isfinite(v)) err |= SP_ERR_VALUE;
-        const float x = v * ri;
-        const bool keep = x != 0.0f && err == 0u;
-        xhat[j] = x;
-        keys[j] = keep ? (((u64)f << 32) | (u64)q) : ((u64)F << 32);  // (F << 32: after every posting)
-        pos[j] = (unsigned)j;
-        efeat[j] = -1;
-        dropped += keep ? 0 : 1;
-    }
-    if (err) atomicOr(&cnt[SP_CNT_ERR], (u64)err);
-    if (dropped) atomicAdd(&cnt[SP_CNT_DROPPED], dropped);
+    sp_build_row<FDR_METRIC_COSINE>(n, F, indptr, indices, vals, xhat, nullptr, nullptr, keys, pos, efeat, zero, cnt);
 }
 
-// S1j: one thread per row
 __global__ __launch_bounds__(256) void sp_rows_jaccard_kernel(long long n, long long F,
                                                               const long long *__restrict__ indptr,
                                                               const int *__restrict__ indices,
@@ -142,33 +231,9 @@ __global__ __launch_bounds__(256) void sp_rows_jaccard_kernel(long long n, long 
                                                               u64 *__restrict__ keys, unsigned *__restrict__ pos,
                                                               int *__restrict__ efeat, unsigned char *__restrict__ zero,
                                                               u64 *__restrict__ cnt) {
-    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (q >= n) return;
-    const long long b = indptr[q], e = indptr[q + 1];
-    unsigned err = 0;
-    long long prev = -1;
-    int a = 0;  // |S_q|: the stored entries whose value is not +-0
-    for (long long j = b; j < e; ++j) {
-        const long long f = indices[j];
-        const float v = vals ? vals[j] : 1.0f;
-        if (f < 0 || f >= F) err |= SP_ERR_RANGE;
-        else if (f <= prev) err |= SP_ERR_ORDER;
-        prev = f;
-        if (!isfinite(v)) err |= SP_ERR_VALUE;
-        const bool present = v != 0.0f;
-        keys[j] = (present && err == 0u) ? (((u64)f << 32) | (u64)q) : ((u64)F << 32);  // (F << 32: after every posting)
-        pos[j] = (unsigned)j;
-        efeat[j] = -1;
-        a += present ? 1 : 0;
-    }
-    asize[q] = a;
-    zero[q] = a > 0 ? 0 : 1;
-    if (a == 0) atomicAdd(&cnt[SP_CNT_ZERO], 1ull);
-    if (err) atomicOr(&cnt[SP_CNT_ERR], (u64)err);
-    if (e - b > a) atomicAdd(&cnt[SP_CNT_DROPPED], (u64)(e - b - a));  // (without an error: the entries at +-0)
+    sp_build_row<FDR_METRIC_JACCARD>(n, F, indptr, indices, vals, nullptr, asize, nullptr, keys, pos, efeat, zero, cnt);
 }
 
-// S1w: one thread per row
 __global__ __launch_bounds__(256) void sp_rows_wjaccard_kernel(long long n, long long F,
                                                                const long long *__restrict__ indptr,
                                                                const int *__restrict__ indices,
@@ -177,35 +242,41 @@ __global__ __launch_bounds__(256) void sp_rows_wjaccard_kernel(long long n, long
                                                                unsigned *__restrict__ pos, int *__restrict__ efeat,
                                                                unsigned char *__restrict__ zero,
                                                                u64 *__restrict__ cnt) {
+    sp_build_row<FDR_METRIC_WEIGHTED_JACCARD>(n, F, indptr, indices, vals, xraw, nullptr, mass, keys, pos, efeat, zero,
+                                              cnt);
+}
+
+// S1q: one thread per query row of fdr_sparse_index_query.  The row's own quantities as the build forms an index
+// row's (sp_row), and for each stored entry the run of its feature in the index, found by binary search in the runs'
+// ascending feature ids (runfeat [runs], runs = cnt[SP_CNT_RUNS] of the build): -1 where the index has no run for
+// the feature or where a build would give the entry no posting.  Errors go to cnt[SP_CNT_QERR], the zero (empty)
+// queries are counted in cnt[SP_CNT_ZEROQ].
+template <int METRIC>
+__global__ __launch_bounds__(256) void sp_query_rows_kernel(long long nq, long long F,
+                                                            const long long *__restrict__ indptr,
+                                                            const int *__restrict__ indices,
+                                                            const float *__restrict__ vals, float *__restrict__ xhat,
+                                                            int *__restrict__ asize, float *__restrict__ mass,
+                                                            int *__restrict__ efeat, unsigned char *__restrict__ zero,
+                                                            const int *__restrict__ runfeat, u64 *__restrict__ cnt) {
     const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (q >= n) return;
-    const long long b = indptr[q], e = indptr[q + 1];
-    unsigned err = 0;
-    long long prev = -1;
-    float A = 0.0f;  // the canonical mass chain over the stored values in order (a stored +-0 adds nothing)
-    u64 dropped = 0;
-    for (long long j = b; j < e; ++j) {
-        const long long f = indices[j];
-        const float v = vals ? vals[j] : 1.0f;
-        if (f < 0 || f >= F) err |= SP_ERR_RANGE;
-        else if (f <= prev) err |= SP_ERR_ORDER;
-        prev = f;
-        if (!isfinite(v)) err |= SP_ERR_VALUE;
-        else if (v < 0.0f) err |= SP_ERR_NEGATIVE;
-        A = A + v;
-        const bool keep = v > 0.0f && err == 0u;
-        xraw[j] = v;
-        keys[j] = keep ? (((u64)f << 32) | (u64)q) : ((u64)F << 32);  // (F << 32: after every posting)
-        pos[j] = (unsigned)j;
-        efeat[j] = -1;
-        dropped += keep ? 0 : 1;
-    }
-    if (!isfinite(A)) err |= SP_ERR_MASS;  // (+inf from finite values: the union of a pair would be infinite)
-    mass[q] = A;
-    zero[q] = A > 0.0f ? 0 : 1;
-    if (!(A > 0.0f)) atomicAdd(&cnt[SP_CNT_ZERO], 1ull);
-    if (err) atomicOr(&cnt[SP_CNT_ERR], (u64)err);
-    if (dropped) atomicAdd(&cnt[SP_CNT_DROPPED], dropped);
+    if (q >= nq) return;
+    const long long runs = (long long)cnt[SP_CNT_RUNS];
+    const SpRow r = sp_row<METRIC>(F, indices, vals, indptr[q], indptr[q + 1],
+                                   [&](long long j, long long f, float x, bool keep) {
+                                       if (METRIC != FDR_METRIC_JACCARD) xhat[j] = x;
+                                       int c = -1;
+                                       if (keep) {  // (keep: f in [0, F))
+                                           const long long at = sp_lower_bound(runfeat, 0, runs, (int)f);
+                                           if (at < runs && runfeat[at] == (int)f) c = (int)at;
+                                       }
+                                       efeat[j] = c;
+                                   });
+    if (METRIC == FDR_METRIC_JACCARD) asize[q] = r.a;
+    if (METRIC == FDR_METRIC_WEIGHTED_JACCARD) mass[q] = r.mass;
+    zero[q] = r.zero ? 1 : 0;
+    if (r.zero) atomicAdd(&cnt[SP_CNT_ZEROQ], 1ull);
+    if (r.err) atomicOr(&cnt[SP_CNT_QERR], (u64)r.err);
 }
 
 __global__ __launch_bounds__(256) void sp_run_flags_kernel(long long m, const u64 *__restrict__ keys,
@@ -216,13 +287,15 @@ __global__ __launch_bounds__(256) void sp_run_flags_kernel(long long m, const u6
 
 // S2: sorted postings -> run offsets, rows, values, and each stored entry's run id (features renumbered densely in
 // ascending order, so no array is as long as F); xhat = pval = null (Jaccard): no values; weighted Jaccard: xhat
-// holds the raw values
+// holds the raw values.  runfeat[c] = the feature of run c (ascending), *nruns = the number of runs: what a query
+// row that is not in the index finds its entries' runs by
 __global__ __launch_bounds__(256) void sp_postings_kernel(long long m, const u64 *__restrict__ keys,
                                                           const unsigned *__restrict__ pos,
                                                           const int *__restrict__ run_incl,
                                                           const float *__restrict__ xhat, int *__restrict__ efeat,
                                                           int *__restrict__ prow, float *__restrict__ pval,
-                                                          long long *__restrict__ runptr) {
+                                                          long long *__restrict__ runptr, int *__restrict__ runfeat,
+                                                          u64 *__restrict__ nruns) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
     const int c = run_incl[i] - 1;
@@ -230,8 +303,14 @@ __global__ __launch_bounds__(256) void sp_postings_kernel(long long m, const u64
     efeat[p] = c;
     prow[i] = (int)(unsigned)keys[i];
     if (pval) pval[i] = xhat[p];
-    if (i == 0 || run_incl[i - 1] != run_incl[i]) runptr[c] = i;
-    if (i == m - 1) runptr[c + 1] = m;
+    if (i == 0 || run_incl[i - 1] != run_incl[i]) {
+        runptr[c] = i;
+        runfeat[c] = (int)(keys[i] >> 32);
+    }
+    if (i == m - 1) {
+        runptr[c + 1] = m;
+        *nruns = (u64)(c + 1);
+    }
 }
 
 // S4: one wave, sixteen rows per lane and turn; stops once it has k of each kind
@@ -312,30 +391,38 @@ __device__ __forceinline__ int sp_insert(int *tab, int t, bool &isnew) {
     return -1;  // (unreachable: fewer than SP_CAP distinct keys)
 }
 
-__device__ __forceinline__ long long sp_lower_bound(const int *__restrict__ a, long long lo, long long hi, int v) {
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
+// The query side of a search: the rows the queries are taken from.  A search of the index's own rows passes the
+// index's arrays (SparseIndex), fdr_sparse_index_query those of the uploaded query set (SparseQuerySet), whose efeat
+// S1q has filled with runs of the index.  Rows are numbered as in these arrays; heavy holds such numbers and has room
+// for every query of the call.
+struct SpQuerySide {
+    const long long *indptr;    // [rows + 1]
+    const int *efeat;           // each stored entry's run in the index (-1: none)
+    const float *xhat;          // cosine: normalised values; weighted Jaccard: raw values; Jaccard: null
+    const int *asize;           // Jaccard: the set sizes
+    const float *mass;          // weighted Jaccard: the masses
+    const unsigned char *zero;  // the zero (empty, zero-mass) flags
+    int *heavy;                 // the queries handed to S3r
+};
 
 // S3 / S3r (METRIC = FDR_METRIC_COSINE), S3j / S3rj (FDR_METRIC_JACCARD: xhat = pval = null, asize = the set sizes)
 // and S3w / S3rw (FDR_METRIC_WEIGHTED_JACCARD: xhat / pval = the raw values, mass = the rows' masses): one wave (one
-// workgroup) per query; the queries are the rows q0 + blockIdx.x (S3) or the heavy list's (S3r), and query q writes
-// row q - q0 of idx_out / dist_out
+// workgroup) per query; the queries are the rows q0 + blockIdx.x of the query side (S3) or the heavy list's (S3r), and
+// query q writes row q - q0 of idx_out / dist_out.  The target side (runptr, prow, pval, t_asize, t_mass, zidx / zdist)
+// is the index's
 template <bool RANGE, int METRIC>
-__global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q0, const long long *__restrict__ indptr,
-                                                        const int *__restrict__ efeat, const float *__restrict__ xhat,
+__global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q0, const SpQuerySide qs,
                                                         const long long *__restrict__ runptr,
                                                         const int *__restrict__ prow, const float *__restrict__ pval,
-                                                        const int *__restrict__ asize,
-                                                        const float *__restrict__ mass,
-                                                        const unsigned char *__restrict__ zero, int k,
+                                                        const int *__restrict__ t_asize,
+                                                        const float *__restrict__ t_mass, int k,
                                                         const int *__restrict__ zidx, const float *__restrict__ zdist,
-                                                        int *__restrict__ heavy, u64 *__restrict__ cnt,
-                                                        int *__restrict__ idx_out, float *__restrict__ dist_out) {
+                                                        u64 *__restrict__ cnt, int *__restrict__ idx_out,
+                                                        float *__restrict__ dist_out) {
+    const long long *__restrict__ indptr = qs.indptr;
+    const int *__restrict__ efeat = qs.efeat;
+    const float *__restrict__ xhat = qs.xhat;
+    int *__restrict__ heavy = qs.heavy;
     __shared__ u64 buf[SP_LIST + SP_CAP];  // [0, k): the query's list; [SP_LIST, ...): the table, then the sort buffer
     int *tab = reinterpret_cast<int *>(buf + SP_LIST);  // slot s: tab[2 s] = target row (SP_EMPTY), tab[2 s + 1] = acc
     constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;  // (... or the int32 count of shared features: no values)
@@ -344,7 +431,7 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q
     const long long q = RANGE ? (long long)heavy[blockIdx.x] : q0 + (long long)blockIdx.x;
     int *out_i = idx_out + (q - q0) * k;
     float *out_d = dist_out + (q - q0) * k;
-    if (!RANGE && zero[q]) {
+    if (!RANGE && qs.zero[q]) {
         for (int i = lane; i < k; i += 64) {
             out_i[i] = zidx[i];
             out_d[i] = zdist[i];
@@ -352,8 +439,8 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q
         return;
     }
     const long long qb = indptr[q], qe = indptr[q + 1];
-    const int qa = JAC ? asize[q] : 0;  // |S_q|
-    const double qm = WJ ? (double)mass[q] : 0.0;  // A_q
+    const int qa = JAC ? qs.asize[q] : 0;  // |S_q|
+    const double qm = WJ ? (double)qs.mass[q] : 0.0;  // A_q
     for (int i = lane; i < SP_LIST; i += 64) buf[i] = KEY_INF;
     const long long nranges = RANGE ? (n + SP_W - 1) / SP_W : 1;
     const u64 lt = (1ull << lane) - 1ull;
@@ -430,11 +517,11 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q
                 float d;
                 if (JAC) {  // c >= 1 shared features: u = a + b - c >= 1, one fp64 division, one rounding
                     const int c = (int)(unsigned)(w >> 32);
-                    const int u = qa + asize[t] - c;
+                    const int u = qa + t_asize[t] - c;
                     d = (float)((double)(u - c) / (double)u);
                 } else if (WJ) {  // m <= min(A_q, A_t) on the bits and both > 0: u >= max(A_q, A_t) > 0
                     const double m = (double)__uint_as_float((unsigned)(w >> 32));
-                    const double u = (qm + (double)mass[t]) - m;
+                    const double u = (qm + (double)t_mass[t]) - m;
                     d = (float)((u - m) / u);
                 } else {
                     d = dist_from_sim(__uint_as_float((unsigned)(w >> 32)));
@@ -493,10 +580,11 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-// S3 over the queries [q_lo, q_lo + nq), then S3r over the queries it handed on; h = their number, and the zero
-// (empty) rows among the queries.  d_idx / d_dist: [nq, k] results on the device.
+// S3 over the queries [q_lo, q_lo + nq) of the query side, then S3r over the queries it handed on; h = their number,
+// and the zero (empty) rows among the queries.  d_idx / d_dist: [nq, k] results on the device.
 template <int METRIC>
-static int sp_search(fdr_ctx *ctx, int64_t n, int32_t k, int64_t q_lo, int64_t nq, int *d_idx, float *d_dist, u64 (&h)[2]) {
+static int sp_search(fdr_ctx *ctx, const SpQuerySide &qs, int64_t n, int32_t k, int64_t q_lo, int64_t nq, int *d_idx,
+                     float *d_dist, u64 (&h)[2]) {
     const hipStream_t st = ctx->stream;
     SparseIndex &sp = ctx->sp;
     constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;
@@ -504,10 +592,9 @@ static int sp_search(fdr_ctx *ctx, int64_t n, int32_t k, int64_t q_lo, int64_t n
     static_assert(SP_CNT_ZEROQ == SP_CNT_HEAVY + 1, "one read-back for both");
     auto launch = [&](auto range, unsigned grid) {  // S3 (std::false_type) or S3r (std::true_type)
         hipLaunchKernelGGL((knn_sparse_kernel<decltype(range)::value, METRIC>), dim3(grid), dim3(64), 0, st, (long long)n,
-                           (long long)q_lo, sp.indptr.ptr(), sp.efeat.ptr(), JAC ? nullptr : sp.xhat.ptr(),
-                           sp.runptr.ptr(), sp.posting_rows(), JAC ? nullptr : sp.pval.ptr(),
-                           JAC ? sp.asize.ptr() : nullptr, WJ ? sp.mass.ptr() : nullptr, sp.zero.ptr(), (int)k,
-                           sp.zidx(), sp.zdist(), sp.heavy.ptr(), sp.cnt.ptr(), d_idx, d_dist);
+                           (long long)q_lo, qs, sp.runptr.ptr(), sp.posting_rows(), JAC ? nullptr : sp.pval.ptr(),
+                           JAC ? sp.asize.ptr() : nullptr, WJ ? sp.mass.ptr() : nullptr, (int)k, sp.zidx(), sp.zdist(),
+                           sp.cnt.ptr(), d_idx, d_dist);
     };
     launch(std::false_type{}, (unsigned)nq);
     HIP_TRY(hipGetLastError());
@@ -518,6 +605,19 @@ static int sp_search(fdr_ctx *ctx, int64_t n, int32_t k, int64_t q_lo, int64_t n
         launch(std::true_type{}, (unsigned)h[0]);
         HIP_TRY(hipGetLastError());
     }
+    return FDR_OK;
+}
+
+// What the row kernels (S1 / S1j / S1w, S1q) found wrong with the rows: FDR_E_ARG and its message, or FDR_OK
+static int sp_refuse(const char *who, u64 err, int64_t n_features) {
+    if (err & SP_ERR_RANGE) return fail(FDR_E_ARG, "%s: a feature index is outside [0, %lld)", who, (long long)n_features);
+    if (err & SP_ERR_ORDER) return fail(FDR_E_ARG, "%s: feature indices must be strictly ascending inside a row", who);
+    if (err & SP_ERR_VALUE) return fail(FDR_E_ARG, "%s: non-finite value", who);
+    if (err & SP_ERR_NEGATIVE)
+        return fail(FDR_E_ARG, "%s: negative value (the weighted Jaccard metric takes values >= 0)", who);
+    if (err & SP_ERR_MASS)
+        return fail(FDR_E_ARG, "%s: a row's fp32 sum of values is not finite (the weighted Jaccard metric needs a "
+                    "finite mass per row)", who);
     return FDR_OK;
 }
 
@@ -558,6 +658,7 @@ static int sp_build(fdr_ctx *ctx, const char *who, int32_t metric, int64_t n, in
     if ((rc = sp.efeat.reserve(m1))) return rc;
     if (!jac && (rc = sp.pval.reserve(m1))) return rc;
     if ((rc = sp.runptr.reserve(m1 + 1))) return rc;
+    if ((rc = sp.runfeat.reserve(std::min(m1, (size_t)n_features)))) return rc;  // (a run per feature with a posting)
     if ((rc = sp.heavy.reserve((size_t)n))) return rc;
     if ((rc = sp.cnt.reserve(SparseIndex::cnt_words))) return rc;
     if ((rc = sp.zero.reserve((size_t)n))) return rc;
@@ -585,16 +686,7 @@ static int sp_build(fdr_ctx *ctx, const char *who, int32_t metric, int64_t n, in
     u64 h_cnt[3];
     HIP_TRY(hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (h_cnt[SP_CNT_ERR] & SP_ERR_RANGE)
-        return fail(FDR_E_ARG, "%s: a feature index is outside [0, %lld)", who, (long long)n_features);
-    if (h_cnt[SP_CNT_ERR] & SP_ERR_ORDER)
-        return fail(FDR_E_ARG, "%s: feature indices must be strictly ascending inside a row", who);
-    if (h_cnt[SP_CNT_ERR] & SP_ERR_VALUE) return fail(FDR_E_ARG, "%s: non-finite value", who);
-    if (h_cnt[SP_CNT_ERR] & SP_ERR_NEGATIVE)
-        return fail(FDR_E_ARG, "%s: negative value (the weighted Jaccard metric takes values >= 0)", who);
-    if (h_cnt[SP_CNT_ERR] & SP_ERR_MASS)
-        return fail(FDR_E_ARG, "%s: a row's fp32 sum of values is not finite (the weighted Jaccard metric needs a "
-                    "finite mass per row)", who);
+    if ((rc = sp_refuse(who, h_cnt[SP_CNT_ERR], n_features))) return rc;
     const long long kept = (long long)nnz - (long long)h_cnt[SP_CNT_DROPPED];
     if (kept > 0) {
         int end_bit = 32;
@@ -615,24 +707,27 @@ static int sp_build(fdr_ctx *ctx, const char *who, int32_t metric, int64_t n, in
         if ((rc = rocprim_run(sp.tmp, "rocprim::inclusive_scan", scan))) return rc;
         hipLaunchKernelGGL(sp_postings_kernel, dim3(g), dim3(256), 0, st, kept, sp.sorted_keys.ptr(),
                            sp.sorted_pos.ptr(), run_incl, jac ? nullptr : sp.xhat.ptr(), sp.efeat.ptr(),
-                           sp.posting_rows(), jac ? nullptr : sp.pval.ptr(), sp.runptr.ptr());
+                           sp.posting_rows(), jac ? nullptr : sp.pval.ptr(), sp.runptr.ptr(), sp.runfeat.ptr(),
+                           cnt + SP_CNT_RUNS);
         HIP_TRY(hipGetLastError());
     }
     sp.built.valid = true;
     sp.built.metric = metric;
     sp.built.n = n;
+    sp.built.n_features = n_features;
     sp.built.kept = kept;
     sp.built.nzero = (long long)h_cnt[SP_CNT_ZERO];
     return FDR_OK;
 }
 
-// A search of the context's index (the caller has checked that there is one, and k and the range): S4 when the index
-// has a zero row, S3 / S3r over the queries [q_lo, q_hi), the results and the trace
-static int sp_search_range(fdr_ctx *ctx, int32_t k, int64_t q_lo, int64_t q_hi, int32_t *idx_out, float *dist_out) {
+// The tail of every search: S3 / S3r by the index's metric over the queries [q0, q0 + nq) of the query side (the
+// caller has reset the search's counters and enqueued S4 where a query is zero), the results and the trace
+static int sp_search_tail(fdr_ctx *ctx, const SpQuerySide &qs, int32_t k, int64_t q0, int64_t nq, int32_t *idx_out,
+                          float *dist_out) {
     int rc;
     const hipStream_t st = ctx->stream;
     SparseIndex &sp = ctx->sp;
-    const int64_t n = sp.built.n, nq = q_hi - q_lo;
+    const int64_t n = sp.built.n;
     u64 h[2] = {0, 0};  // queries that took S3r; zero (empty) rows among the queries
     if (nq > 0) {
         if ((rc = ctx->idx.reserve((size_t)nq * k * 4))) return rc;
@@ -640,21 +735,12 @@ static int sp_search_range(fdr_ctx *ctx, int32_t k, int64_t q_lo, int64_t q_hi, 
         // (the result buffers are the dense calls' untyped ones, shared with them)
         int *d_idx = static_cast<int *>(ctx->idx.p);
         float *d_dist = static_cast<float *>(ctx->dist.p);
-        HIP_TRY(hipMemsetAsync(sp.cnt.ptr() + SP_CNT_HEAVY, 0, 16, st));  // (the heavy list's counter and the zero queries')
-        if (sp.built.nzero > 0) {  // (S4 depends on k: per search)
-            hipLaunchKernelGGL(sp_zero_row_kernel, dim3(1), dim3(64), 0, st, (long long)n, sp.zero.ptr(), (int)k,
-                               sp.zidx(), sp.zdist());
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(sp_count_zero_kernel, dim3((unsigned)((nq + 4095) / 4096)), dim3(256), 0, st,
-                               (long long)q_lo, (long long)q_hi, sp.zero.ptr(), sp.cnt.ptr());
-            HIP_TRY(hipGetLastError());
-        }
         if (sp.built.metric == FDR_METRIC_JACCARD)
-            rc = sp_search<FDR_METRIC_JACCARD>(ctx, n, k, q_lo, nq, d_idx, d_dist, h);
+            rc = sp_search<FDR_METRIC_JACCARD>(ctx, qs, n, k, q0, nq, d_idx, d_dist, h);
         else if (sp.built.metric == FDR_METRIC_WEIGHTED_JACCARD)
-            rc = sp_search<FDR_METRIC_WEIGHTED_JACCARD>(ctx, n, k, q_lo, nq, d_idx, d_dist, h);
+            rc = sp_search<FDR_METRIC_WEIGHTED_JACCARD>(ctx, qs, n, k, q0, nq, d_idx, d_dist, h);
         else
-            rc = sp_search<FDR_METRIC_COSINE>(ctx, n, k, q_lo, nq, d_idx, d_dist, h);
+            rc = sp_search<FDR_METRIC_COSINE>(ctx, qs, n, k, q0, nq, d_idx, d_dist, h);
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(idx_out, d_idx, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(dist_out, d_dist, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
@@ -669,6 +755,91 @@ static int sp_search_range(fdr_ctx *ctx, int32_t k, int64_t q_lo, int64_t q_hi, 
     t.range_queries = (int32_t)h[0];
     t.range_chunks = h[0] ? (int32_t)((n + SP_W - 1) / SP_W) : 0;
     return FDR_OK;
+}
+
+static int sp_zero_row(fdr_ctx *ctx, int32_t k) {  // S4 (depends on k: per search)
+    SparseIndex &sp = ctx->sp;
+    hipLaunchKernelGGL(sp_zero_row_kernel, dim3(1), dim3(64), 0, ctx->stream, (long long)sp.built.n, sp.zero.ptr(), (int)k,
+                       sp.zidx(), sp.zdist());
+    HIP_TRY(hipGetLastError());
+    return FDR_OK;
+}
+
+// A search of the context's index (the caller has checked that there is one, and k and the range): S4 when the index
+// has a zero row, S3 / S3r over the queries [q_lo, q_hi), the results and the trace.  The query side is the index itself.
+static int sp_search_range(fdr_ctx *ctx, int32_t k, int64_t q_lo, int64_t q_hi, int32_t *idx_out, float *dist_out) {
+    int rc;
+    const hipStream_t st = ctx->stream;
+    SparseIndex &sp = ctx->sp;
+    const int64_t nq = q_hi - q_lo;
+    if (nq > 0) {
+        HIP_TRY(hipMemsetAsync(sp.cnt.ptr() + SP_CNT_HEAVY, 0, 16, st));  // (the heavy list's counter and the zero queries')
+        if (sp.built.nzero > 0) {
+            if ((rc = sp_zero_row(ctx, k))) return rc;
+            hipLaunchKernelGGL(sp_count_zero_kernel, dim3((unsigned)((nq + 4095) / 4096)), dim3(256), 0, st,
+                               (long long)q_lo, (long long)q_hi, sp.zero.ptr(), sp.cnt.ptr());
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    const SpQuerySide own = {sp.indptr.ptr(), sp.efeat.ptr(), sp.xhat.ptr(),  sp.asize.ptr(),
+                             sp.mass.ptr(),   sp.zero.ptr(),  sp.heavy.ptr()};
+    return sp_search_tail(ctx, own, k, q_lo, nq, idx_out, dist_out);
+}
+
+// fdr_sparse_index_query behind its checks of the context, k and the result pointers: the checks of the query CSR, its
+// upload into the context's query set, S1q, S4 when a query is zero, and the search's tail with the query set as the
+// query side.  Nothing of the index is written except the search's counters.
+static int sp_query(fdr_ctx *ctx, int32_t k, int64_t nq, const int64_t *indptr, const int32_t *indices,
+                    const float *values, int32_t *idx_out, float *dist_out) {
+    static const char who[] = "sparse_index_query";
+    int rc;
+    const hipStream_t st = ctx->stream;
+    SparseIndex &sp = ctx->sp;
+    SparseQuerySet &qset = ctx->spq;
+    const int metric = sp.built.metric;
+    const bool jac = metric == FDR_METRIC_JACCARD, wj = metric == FDR_METRIC_WEIGHTED_JACCARD;
+    if (indptr[0] != 0) return fail(FDR_E_ARG, "%s: indptr[0] must be 0", who);
+    for (int64_t i = 0; i < nq; ++i)
+        if (indptr[i + 1] < indptr[i]) return fail(FDR_E_ARG, "%s: indptr not monotone at row %lld", who, (long long)i);
+    const int64_t nnz = indptr[nq];
+    if (nnz > INT32_MAX) return fail(FDR_E_ARG, "%s: %lld stored entries (at most 2^31 - 1)", who, (long long)nnz);
+    if (nnz > 0 && !indices) return fail(FDR_E_ARG, "%s: indices is null", who);
+    const size_t m1 = (size_t)std::max<int64_t>(nnz, 1);
+    if ((rc = qset.indptr.reserve((size_t)(nq + 1)))) return rc;
+    if ((rc = qset.indices.reserve(m1))) return rc;
+    if (values && (rc = qset.values.reserve(m1))) return rc;
+    if (!jac && (rc = qset.xhat.reserve(m1))) return rc;
+    if ((rc = qset.efeat.reserve(m1))) return rc;
+    if (jac && (rc = qset.asize.reserve((size_t)nq))) return rc;
+    if (wj && (rc = qset.mass.reserve((size_t)nq))) return rc;
+    if ((rc = qset.zero.reserve((size_t)nq))) return rc;
+    if ((rc = qset.heavy.reserve((size_t)nq))) return rc;
+    HIP_TRY(hipMemcpyAsync(qset.indptr.ptr(), indptr, (size_t)(nq + 1) * 8, hipMemcpyHostToDevice, st));
+    if (nnz > 0) {
+        HIP_TRY(hipMemcpyAsync(qset.indices.ptr(), indices, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+        if (values) HIP_TRY(hipMemcpyAsync(qset.values.ptr(), values, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+    }
+    static_assert(SP_CNT_ZEROQ == SP_CNT_HEAVY + 1 && SP_CNT_QERR == SP_CNT_HEAVY + 2, "one reset for the three");
+    HIP_TRY(hipMemsetAsync(sp.cnt.ptr() + SP_CNT_HEAVY, 0, 24, st));
+    auto rows = [&](auto m) {  // S1q
+        hipLaunchKernelGGL((sp_query_rows_kernel<decltype(m)::value>), dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st,
+                           (long long)nq, (long long)sp.built.n_features, qset.indptr.ptr(), qset.indices.ptr(),
+                           values ? qset.values.ptr() : nullptr, jac ? nullptr : qset.xhat.ptr(),
+                           jac ? qset.asize.ptr() : nullptr, wj ? qset.mass.ptr() : nullptr, qset.efeat.ptr(),
+                           qset.zero.ptr(), sp.runfeat.ptr(), sp.cnt.ptr());
+    };
+    if (jac) rows(std::integral_constant<int, FDR_METRIC_JACCARD>{});
+    else if (wj) rows(std::integral_constant<int, FDR_METRIC_WEIGHTED_JACCARD>{});
+    else rows(std::integral_constant<int, FDR_METRIC_COSINE>{});
+    HIP_TRY(hipGetLastError());
+    u64 h[2] = {0, 0};  // zero (empty) queries; error bits
+    HIP_TRY(hipMemcpyAsync(h, sp.cnt.ptr() + SP_CNT_ZEROQ, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = sp_refuse(who, h[1], sp.built.n_features))) return rc;
+    if (h[0] > 0 && (rc = sp_zero_row(ctx, k))) return rc;  // (the index need not hold a zero row for a query to be one)
+    const SpQuerySide side = {qset.indptr.ptr(), qset.efeat.ptr(), qset.xhat.ptr(),  qset.asize.ptr(),
+                              qset.mass.ptr(),   qset.zero.ptr(),  qset.heavy.ptr()};
+    return sp_search_tail(ctx, side, k, 0, nq, idx_out, dist_out);
 }
 
 static int sp_knn(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
@@ -726,6 +897,23 @@ FDR_EXPORT int fdr_sparse_index_search(fdr_ctx *ctx, int32_t k, int64_t q_lo, in
     return sp_search_range(ctx, k, q_lo, q_hi, idx_out, dist_out);
 }
 
+FDR_EXPORT int fdr_sparse_index_query(fdr_ctx *ctx, int32_t k, int64_t nq, const int64_t *q_indptr,
+                                      const int32_t *q_indices, const float *q_values, int32_t *idx_out,
+                                      float *dist_out) {
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    knn_call_begin(ctx);
+    if (!ctx->sp.built.valid) return fail(FDR_E_STATE, "sparse_index_query: the context holds no sparse index");
+    const int64_t n = ctx->sp.built.n;
+    if (k < 1 || k > FDR_MAX_K || k > n)
+        return fail(FDR_E_ARG, "sparse_index_query: k=%d unsupported (1..min(%d, n = %lld))", k, FDR_MAX_K, (long long)n);
+    if (nq < 0 || nq > INT32_MAX)
+        return fail(FDR_E_ARG, "sparse_index_query: nq (%lld) must be in [0, 2^31)", (long long)nq);
+    if (nq == 0) return sp_search_tail(ctx, SpQuerySide{}, k, 0, 0, idx_out, dist_out);  // (the trace alone)
+    if (!q_indptr || !idx_out || !dist_out) return fail(FDR_E_ARG, "sparse_index_query: null pointer");
+    return sp_query(ctx, k, nq, q_indptr, q_indices, q_values, idx_out, dist_out);
+}
+
 FDR_EXPORT int fdr_sparse_index_info(fdr_ctx *ctx, int32_t *metric, int64_t *n, int64_t *postings, int64_t *zero_rows,
                                      size_t *device_bytes) {
     if (!ctx) return fail(FDR_E_ARG, "null context");
@@ -735,7 +923,7 @@ FDR_EXPORT int fdr_sparse_index_info(fdr_ctx *ctx, int32_t *metric, int64_t *n, 
     if (postings) *postings = ctx->sp.built.kept;
     if (zero_rows) *zero_rows = ctx->sp.built.nzero;
     if (device_bytes) {
-        *device_bytes = ctx->sp.bytes();
+        *device_bytes = ctx->sp.bytes() + ctx->spq.bytes();  // (the query set of fdr_sparse_index_query too)
     }
     return FDR_OK;
 }
@@ -745,5 +933,6 @@ FDR_EXPORT int fdr_sparse_index_free(fdr_ctx *ctx) {
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->sp.release();
+    ctx->spq.release();
     return FDR_OK;
 }

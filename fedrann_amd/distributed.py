@@ -180,7 +180,13 @@ def sparse_knn_rank(ctx, indptr, indices, values, n_features, k, rank, world, me
     uploads the full CSR and holds about 52 (cosine, weighted Jaccard) or 44 (Jaccard) device bytes per stored entry,
     plus the sort's temporary storage of about 12 more (64 measured at 1 M reads, cosine), and pays the O(nnz) build; only
     the search, sum over the features of df^2, is divided by the ranks (by row count, not by cost).  The index is
-    freed before the call returns."""
+    freed before the call returns.
+
+    The alternative is sparse_knn_target_shard, which divides the TARGETS: a rank indexes only its own rows, so it
+    holds 1 / world of the index and pays 1 / world of the build, but it sees every query (all n rows go through
+    SparseIndex.query, their upload included), and the ranks exchange k candidates per query and rank, which
+    merge_sparse_topk merges exactly.  Replicated index: the work is divided by queries and nothing is exchanged;
+    sharded index: memory and build are divided, the read set is no longer bounded by one GPU's memory."""
     with ctx.sparse_index(indptr, indices, values, n_features, metric=metric) as index:  # (checks the CSR first)
         lo, hi, blocks = sparse_rank_blocks(index.n, rank, world, block_rows)
         k = _lib.check_sparse_search(index.n, k)[0]
@@ -189,6 +195,55 @@ def sparse_knn_rank(ctx, indptr, indices, values, n_features, k, rank, world, me
         for a, b in blocks:
             index.search(k, a, b, out=(idx[a - lo:b - lo], dist[a - lo:b - lo]))
     return lo, hi, idx, dist
+
+
+def sparse_knn_target_shard(ctx, indptr, indices, values, n_features, k, rank, world, metric="cosine",
+                            block_rows=None):
+    """This rank's part of Context.knn_sparse on the whole CSR with the TARGETS divided: (lo, hi, idx int32 [n, k],
+    dist float32 [n, k]), the k nearest rows among the rank's own rows [lo, hi) of shard_rows(n, world) for EVERY row
+    of the CSR, neighbour indices global.  The rank builds the index of its own rows only (local_csr, the values
+    sliced alongside) and asks it about all n rows with SparseIndex.query, in blocks of at most block_rows query rows
+    (None: one block); the shard's first row is added to the indices.  merge_sparse_topk of the ranks' (idx, dist)
+    is the one-GPU answer bit for bit.  No collective and no process group: a caller on several GPUs gathers the
+    parts itself.  Needs k <= hi - lo on every rank that is asked (ValueError, before any GPU work); the index is
+    freed before the call returns."""
+    n, F = _lib.check_sparse_csr(indptr, indices, values, n_features, metric=metric)
+    lo, hi, _ = sparse_rank_blocks(n, rank, world)
+    k = _lib.check_sparse_search(n, k)[0]
+    if k > hi - lo:
+        raise ValueError("rank %d of %d holds the %d target rows [%d, %d): need k = %d <= that"
+                         % (rank, world, hi - lo, lo, hi, k))
+    ip, ix = local_csr(indptr, indices, lo, hi)
+    vals = None if values is None else np.ascontiguousarray(values[indptr[lo]:indptr[hi]])
+    with ctx.sparse_index(ip, ix, vals, F, metric=metric) as index:
+        idx, dist = index.query(indptr, indices, values, k, block_rows=block_rows)
+    idx += np.int32(lo)
+    return lo, hi, idx, dist
+
+
+def merge_sparse_topk(parts, k):
+    """The k nearest targets per query over the ranks' lists: parts is a sequence of (idx int32 [nq, k_r], dist
+    float32 [nq, k_r]) with k_r >= min(k, targets of that rank) and global, pairwise distinct target indices; returns
+    (idx int32 [nq, k], dist float32 [nq, k]), per query the k smallest by (distance bits as uint32, index).  Plain
+    numpy.
+
+    This is exact.  Every rule of the sparse search -- the order by (distance bits, index), the distance-1 fill in
+    index order, the closed form of a zero query (zero rows at 0 in index order, then the others at 1 in index order)
+    -- is "the first k targets under ONE total order of the targets", the order by (distance bits, index), and a
+    target's distance from a query does not depend on which other targets are indexed with it.  A rank's list is the
+    first k of its own targets under that order, so every one of the first k targets overall is in its rank's list,
+    and the first k of the union of the lists is the answer of the whole call bit for bit, whatever the order of the
+    parts."""
+    k = int(k)
+    if not parts:
+        raise ValueError("merge_sparse_topk needs at least one part")
+    idx = np.concatenate([np.asarray(p[0], dtype=np.int32) for p in parts], axis=1)
+    dist = np.concatenate([np.asarray(p[1], dtype=np.float32) for p in parts], axis=1)
+    if idx.shape != dist.shape or idx.ndim != 2 or not 1 <= k <= idx.shape[1]:
+        raise ValueError("parts must be (idx [nq, k_r], dist [nq, k_r]) pairs with at least k = %d columns in all" % k)
+    key = (np.ascontiguousarray(dist).view(np.uint32).astype(np.uint64) << np.uint64(32)) | idx.astype(np.uint32)
+    order = np.argsort(key, axis=1, kind="stable")[:, :k]
+    return np.take_along_axis(idx, order, axis=1), np.take_along_axis(dist, order, axis=1)
 
 
 def local_csr(indptr, indices, lo, hi):

@@ -184,13 +184,45 @@ int fdr_sparse_index_build(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_fe
  * sized by q_hi - q_lo.  fdr_last_knn_trace: FDR_TRACE_SPARSE with queries = q_hi - q_lo, targets = n, and
  * zero_queries / range_queries counting the queries of this call. */
 int fdr_sparse_index_search(fdr_ctx *ctx, int32_t k, int64_t q_lo, int64_t q_hi, int32_t *idx_out, float *dist_out);
+/* ---- query the index with rows that are not in it  (nearest_neighbors.py:39-55 builds a
+ *      pynndescent.NNDescent and reads only its neighbor_graph; this is the shape of that class's
+ *      NNDescent.query(query_data, k) -> (indices, distances), exact) ---------------------------------------------------
+ * The k nearest rows of the context's index for each of nq query rows, which come as a host CSR of their own: q_indptr
+ * int64 [nq + 1] with q_indptr[0] == 0, monotone, fewer than 2^31 stored entries; q_indices int32, in [0, n_features of
+ * the index) and strictly ascending inside a row; q_values float32, finite (NULL: every stored entry is 1, whether
+ * the index was built with values or not).  idx_out int32 [nq, k] holds row numbers of the index, dist_out float32
+ * [nq, k]; host pointers; the call synchronises.  The rules of the index's metric, stated above for fdr_knn_sparse and
+ * fdr_knn_sparse_metric, hold unchanged; only the query is no row of the index.  Its own quantities are formed as the
+ * build forms a row's, by the same device function: the norm chain over its stored values in order, rinv and xhat =
+ * x * rinv (cosine), the set size over the values that are not +-0 (Jaccard), the fp32 mass chain in stored order
+ * (weighted Jaccard).  The chain over the shared features runs in ascending feature order (an fma, a +1, or a
+ * + min(x_q, x_t) per step), the distance is formed as in a search, the order is (distance bits, index), the distance-1
+ * fill runs in index order over all n rows, and a zero, empty or zero-mass QUERY gets the closed form: the first k zero
+ * rows of the index at distance 0, then the first other rows at distance 1.  A query feature that no index row holds
+ * counts in the query's norm, size or mass and in nothing else.  There is no self: a query equal to an index row
+ * finds it at distance 0 like any other row.  So the rows [lo, hi) of the CSR the index was built from, passed as
+ * queries with the same values, give fdr_sparse_index_search(k, lo, hi) bit for bit under every metric.
+ * 1 <= k <= min(FDR_MAX_K, n); 0 <= nq < 2^31, nq == 0 is FDR_OK and writes nothing; under
+ * FDR_METRIC_WEIGHTED_JACCARD values >= 0 and a finite mass chain per row; a null pointer where one is needed, and
+ * every violation of the above (the rows' ones found on the device before any search runs): FDR_E_ARG, the cause in
+ * fdr_last_error.  FDR_E_STATE without an index.  A refused or failed query leaves the index AS IT WAS (unlike a
+ * refused build): a search after it gives the bits from before.  The query rows' device arrays (12 bytes per
+ * stored query entry, 8 under Jaccard, and 4 more with values) grow as needed, are counted in fdr_sparse_index_info's device_bytes and are
+ * freed by fdr_sparse_index_free; the device's result buffers are sized by nq * k, so a host bounds them by querying in
+ * row blocks.  fdr_last_knn_trace: FDR_TRACE_SPARSE with queries = nq, targets = n, zero_queries / range_queries of
+ * this call.  Cost: the search's, plus the upload and one binary search over the index's features per stored query
+ * entry. */
+int fdr_sparse_index_query(fdr_ctx *ctx, int32_t k, int64_t nq, const int64_t *q_indptr, const int32_t *q_indices,
+                           const float *q_values, int32_t *idx_out, float *dist_out);
 /* The context's index (FDR_E_STATE without one); every out pointer may be NULL.  postings: the stored entries that
  * got a posting (cosine: scaled value not +-0; Jaccard: value not +-0; weighted Jaccard: value > 0).  zero_rows: zero
  * rows (Jaccard: empty rows; weighted Jaccard: zero-mass rows).
  * device_bytes: the device memory the sparse path holds for the context, the build's scratch (unsorted keys, sort
- * buffers) included, which is kept so that the next build allocates nothing: about 52 (cosine, weighted Jaccard) or 44
- * (Jaccard) bytes per stored entry in the library's own buffers, and the radix sort's temporary storage on top, about 12 more (64 per
- * stored entry measured at 1 M synthetic reads, cosine).  Buffers only grow: after a larger index the figure is the
+ * buffers) included, which is kept so that the next build allocates nothing, and the query rows of
+ * fdr_sparse_index_query: about 52 (cosine, weighted Jaccard) or 44
+ * (Jaccard) bytes per stored entry in the library's own buffers, 4 bytes per feature that may get a run (the runs'
+ * feature ids, sized by min(stored entries, n_features)), and the radix sort's temporary storage on top, about 12 more
+ * per stored entry (64 per stored entry measured at 100 k and 1 M synthetic reads, cosine).  Buffers only grow: after a larger index the figure is the
  * larger one's. */
 int fdr_sparse_index_info(fdr_ctx *ctx, int32_t *metric, int64_t *n, int64_t *postings, int64_t *zero_rows,
                           size_t *device_bytes);
@@ -312,13 +344,13 @@ int fdr_last_prefilter_launches(fdr_ctx *ctx, int *launches, int *queues);
 /* Diagnostics (test support; nothing in the product reads it): which kernels the most recent k-NN call ran.  With
  * the duplicate-row layer active it describes the inner search of the unique rows.  Every k-NN entry point
  * (fdr_knn_dev, fdr_knn, fdr_embed_knn, fdr_knn_classes_dev, fdr_knn_unique_dev, fdr_knn_expand_dev, fdr_knn_sparse,
- * fdr_knn_sparse_metric, fdr_sparse_index_search) clears it, and
+ * fdr_knn_sparse_metric, fdr_sparse_index_search, fdr_sparse_index_query) clears it, and
  * the per-query path codes, before it checks its arguments. */
 #define FDR_TRACE_NONE 0       /* no k-NN search ran (a cleared trace, or a call that failed or found nothing to do) */
 #define FDR_TRACE_EXACT 1      /* exact mode: the fp32 kernel for every query */
 #define FDR_TRACE_PREFILTER 2  /* fp16 candidate pass + certificate (+ range pass, + exact fallback) */
 #define FDR_TRACE_GENERIC 3    /* d > 1024, or k > 64 / d > 512 below 8192 targets: the generic kernel */
-#define FDR_TRACE_SPARSE 4     /* fdr_knn_sparse, fdr_sparse_index_search: zero_queries = zero rows among the queries;
+#define FDR_TRACE_SPARSE 4     /* fdr_knn_sparse, fdr_sparse_index_search / _query: zero_queries = zero rows among the queries;
                                   range_queries = queries whose targets
                                   overflowed the table and were searched over row ranges, range_chunks = the ranges
                                   of each */
