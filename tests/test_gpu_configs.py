@@ -13,6 +13,7 @@ for bit, + whole-result properties."""
 import numpy as np
 import pytest
 
+from _guarded import knn_dev_guarded
 from _rank_share import assert_trace_strata
 from _strata import stratified_rows
 
@@ -56,8 +57,8 @@ def _check_rank_share(ctx, oracle, E, nq, k, sample=256):
     eng.normalize(E, Ehat, zero)
     need = ctx.knn_workspace_bytes(nq, n, d, k)
     assert need < 200e9
-    idx, dst = eng.knn(Ehat[:nq], zero[:nq], nq, Ehat, zero, n, d, k)
-    torch.cuda.synchronize(dev)
+    # (workspace and outputs hold 0xFF bytes between canaries, checked after the synchronise: tests/_guarded.py)
+    idx, dst, ws = knn_dev_guarded(ctx, Ehat, zero, 0, nq, 0, d, k, stream=eng._stream())
     ut, uq = ctx.last_unique()
     paths, trace = ctx.last_query_paths(nq), ctx.last_knn_trace()
     idx, dst = idx.cpu().numpy(), dst.cpu().numpy()

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import _live_rows as LR
+from _guarded import knn_dev_guarded
 from fedrann_amd import _lib
 from test_gpu_candidates import CAPTURE
 from test_gpu_live_chunks import _device_rows, _oracle_rows, same_bits
@@ -33,19 +34,14 @@ def _call(ctx, Ehat, zero, q0, nq, t_base, skip):
     keys, tables); tables[g] = (first row, lens[256], lists[256, stages]) of target segment g (the context's
     own copy: read after the workspace is freed)."""
     import torch
-    dev, n = Ehat.device, Ehat.shape[0]
     ctx.set_knn_mode("prefilter")
     ctx.set_dedup_mode("off")
     ctx.set_live_chunks("force")
     ctx.set_live_skip(skip)
     ctx.set_knn_capture(CAPTURE | _lib.CAPTURE_LIVE_LISTS)
     try:
-        ws = torch.empty(ctx.knn_workspace_bytes(nq, n, D, K), dtype=torch.uint8, device=dev)
-        idx = torch.empty((nq, K), dtype=torch.int32, device=dev)
-        dst = torch.empty((nq, K), dtype=torch.float32, device=dev)
-        ctx.knn_dev(Ehat[q0].data_ptr(), zero[q0:].data_ptr(), nq, Ehat.data_ptr(), zero.data_ptr(), n, t_base, D, K,
-                    idx.data_ptr(), dst.data_ptr(), ws.data_ptr(), ws.numel())
-        torch.cuda.synchronize(dev)
+        # (workspace and outputs hold 0xFF bytes between canaries, checked after the synchronise: tests/_guarded.py)
+        idx, dst, ws = knn_dev_guarded(ctx, Ehat, zero, q0, nq, t_base, D, K)
         paths = ctx.last_query_paths(nq)
         tr = ctx.last_knn_trace()
         assert tr["kind"] == "prefilter" and tr["pass_live"] == 1, tr

@@ -19,6 +19,7 @@ import zlib
 import numpy as np
 import pytest
 
+from _guarded import knn_dev_guarded
 from _paths_rows import CASES, MIX, RESERVED, _normalize, _paths_input
 from _strata import stratified_rows
 from fedrann_amd import _lib
@@ -30,17 +31,10 @@ PER = 32      # oracle rows per stratum
 
 def _knn(ctx, Ehat, zero, q0, nq, d, k, t_base, mode, dedup):
     """fdr_knn_dev of rows [q0, q0 + nq) against all rows: (idx, dist, paths, trace) on the host."""
-    import torch
-    dev = Ehat.device
-    n, dp = Ehat.shape
     ctx.set_knn_mode(mode)
     ctx.set_dedup_mode(dedup)
-    ws = torch.empty(ctx.knn_workspace_bytes(nq, n, d, k), dtype=torch.uint8, device=dev)
-    idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
-    dst = torch.empty((nq, k), dtype=torch.float32, device=dev)
-    ctx.knn_dev(Ehat[q0].data_ptr(), zero[q0:].data_ptr(), nq, Ehat.data_ptr(), zero.data_ptr(), n, t_base, d, k,
-                idx.data_ptr(), dst.data_ptr(), ws.data_ptr(), ws.numel())
-    torch.cuda.synchronize(dev)
+    # (workspace and outputs hold 0xFF bytes between canaries, checked after the synchronise: tests/_guarded.py)
+    idx, dst, ws = knn_dev_guarded(ctx, Ehat, zero, q0, nq, t_base, d, k)
     paths = ctx.last_query_paths(nq)
     trace = ctx.last_knn_trace()
     del ws

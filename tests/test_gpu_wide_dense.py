@@ -9,6 +9,7 @@ import pytest
 
 from fedrann_amd import _lib
 from _dense_rows import mixed, sample_rows
+from _guarded import knn_dev_guarded
 from test_gpu_wide_knn import _assert_mfma_trace
 
 pytestmark = pytest.mark.gpu
@@ -103,13 +104,8 @@ def test_wide_merge_at_its_cap_eight_segments(ctx, oracle):
     zero = torch.zeros((n,), dtype=torch.uint8, device=dev)
     HipEngine(ctx, dev).normalize(torch.from_numpy(E).to(dev), Ehat, zero)
     q0 = 4000
-    need = ctx.knn_workspace_bytes(nq, n, d, k)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
-    dst = torch.empty((nq, k), dtype=torch.float32, device=dev)
-    ctx.knn_dev(Ehat[q0:q0 + nq].data_ptr(), zero[q0:q0 + nq].data_ptr(), nq, Ehat.data_ptr(), zero.data_ptr(), n, 0,
-                d, k, idx.data_ptr(), dst.data_ptr(), ws.data_ptr(), need, torch.cuda.current_stream(dev).cuda_stream)
-    torch.cuda.synchronize(dev)
+    # (workspace and outputs hold 0xFF bytes between canaries, checked after the synchronise: tests/_guarded.py)
+    idx, dst, _ = knn_dev_guarded(ctx, Ehat, zero, q0, nq, 0, d, k, stream=torch.cuda.current_stream(dev).cuda_stream)
     _assert_mfma_trace(ctx, nq, dp, k)
     tr = ctx.last_knn_trace()
     if ctx.device_info()["cus"] == 256:
@@ -156,14 +152,9 @@ def test_wide_dense_knn_dev_ragged_block(ctx, oracle, d, k):
     Eh, _, oz = oracle.normalize(E)
     for q0, q1 in ((0, 3001), (6033, 9050)):
         nq = q1 - q0
-        need = ctx.knn_workspace_bytes(nq, n, d, k)
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
-        dst = torch.empty((nq, k), dtype=torch.float32, device=dev)
-        ctx.knn_dev(Ehat[q0:q1].data_ptr(), zero[q0:q1].data_ptr(), nq, Ehat.data_ptr(), zero.data_ptr(), n, t_base,
-                    d, k, idx.data_ptr(), dst.data_ptr(), ws.data_ptr(), need,
-                    torch.cuda.current_stream(dev).cuda_stream)
-        torch.cuda.synchronize(dev)
+        # (workspace and outputs hold 0xFF bytes between canaries, checked after the synchronise: tests/_guarded.py)
+        idx, dst, _ = knn_dev_guarded(ctx, Ehat, zero, q0, nq, t_base, d, k,
+                                      stream=torch.cuda.current_stream(dev).cuda_stream)
         _assert_mfma_trace(ctx, nq, dp, k)
         rows = q0 + sample_rows(nq, q0, extra[(extra >= q0) & (extra < q1)] - q0)
         wi, wd = oracle.knn_normalized(Eh[rows], oz[rows], Eh, oz, k)

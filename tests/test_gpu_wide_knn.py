@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 
+from _guarded import knn_dev_guarded
 from fedrann_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -105,14 +106,9 @@ def test_wide_knn_dev_on_a_row_block(ctx, oracle, d):
     Eh, _, ozero = oracle.normalize(E)
     for q0, q1 in ((0, 3008), (6016, 9000)):  # (the last of three 32-row-aligned blocks is ragged)
         nq = q1 - q0
-        need = ctx.knn_workspace_bytes(nq, n, d, k)
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
-        dst = torch.empty((nq, k), dtype=torch.float32, device=dev)
-        ctx.knn_dev(Ehat[q0:q1].data_ptr(), zero[q0:q1].data_ptr(), nq, Ehat.data_ptr(), zero.data_ptr(), n, t_base,
-                    d, k, idx.data_ptr(), dst.data_ptr(), ws.data_ptr(), need,
-                    torch.cuda.current_stream(dev).cuda_stream)
-        torch.cuda.synchronize(dev)
+        # (workspace and outputs hold 0xFF bytes between canaries, checked after the synchronise: tests/_guarded.py)
+        idx, dst, _ = knn_dev_guarded(ctx, Ehat, zero, q0, nq, t_base, d, k,
+                                      stream=torch.cuda.current_stream(dev).cuda_stream)
         _assert_mfma_trace(ctx, nq, dp, k)
         rows = q0 + _sample(nq, q0)
         wi, wd = oracle.knn_normalized(Eh[rows], ozero[rows], Eh, ozero, k)
