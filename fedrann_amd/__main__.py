@@ -12,7 +12,10 @@ projection matrix -> embeddings -> k-NN -> overlaps.tsv.  Entry points:
         (scipy.sparse.save_npz binary CSR of the rows to search; see feature_extraction.py).
 
 --no-projection: stages 2-3 build the IDF-weighted feature rows (value of feature f = idf[f]) instead of the
-projection and the embeddings, and stage 4 searches them exactly (fdr_knn_sparse); -n is ignored.  One GPU.
+projection and the embeddings, and stage 4 searches them exactly (fdr_knn_sparse); -n is ignored.  Over several
+--devices the user chooses what is divided, --sparse-shard targets (each rank indexes its own rows, the ranks exchange
+query blocks and k candidates per query, fdr_topk_merge merges them) or queries (each rank indexes all rows and
+searches its own); either way overlaps.tsv is the one-GPU file byte for byte.
 --no-projection-metric jaccard (with --no-projection): stage 2 builds no weights and stage 4 searches the rows'
 k-mer sets by exact Jaccard distance (fdr_knn_sparse_metric), the quantity MinHash tools estimate.
 --no-projection-metric weighted_jaccard: stage 2 builds the IDF weights as for cosine (a negative weight, count > F,
@@ -22,7 +25,8 @@ becomes 0) and stage 4 searches the weighted rows by exact weighted Jaccard (Ruz
 child per GPU BEFORE it touches a GPU itself; from reads, every child counts and searches its byte range of
 the file (stage1_sharded.py), then embeds its row block, the blocks are all-gathered (RCCL), every child
 searches its rows against all rows and writes its part of overlaps.tsv; the parent concatenates the parts in
-rank order (byte-identical to the single-GPU file).
+rank order (byte-identical to the single-GPU file).  With --no-projection the children run the sparse search under
+--sparse-shard instead of the embed / all-gather / search.
 """
 import argparse
 import logging
@@ -97,11 +101,18 @@ def build_parser():
                    help="With --feature-matrix: text file, one 'name<TAB>strand' (or just name) per row.")
     g.add_argument("--no-projection", action="store_true", default=False,
                    help="Search the IDF-weighted feature rows themselves (exact cosine k-NN, no random projection: "
-                        "the ground truth the projection approximates); -n is ignored.  One GPU only.")
+                        "the ground truth the projection approximates); -n is ignored.  Over several --devices: "
+                        "see --sparse-shard.")
     g.add_argument("--no-projection-metric", choices=["cosine", "jaccard", "weighted_jaccard"], default="cosine",
                    help="With --no-projection: cosine on the IDF-weighted rows, the exact Jaccard distance of the "
                         "rows' feature sets (no weights), or the exact weighted Jaccard distance of the IDF-weighted "
                         "rows (sum of minima over sum of maxima; a negative IDF counts as 0).")
+    g.add_argument("--sparse-shard", choices=["targets", "queries"], default=None,
+                   help="With --no-projection and several --devices (required there): what the ranks divide.  targets: "
+                        "a rank loads and indexes only its own rows (1 / ranks of the index memory and of the build), "
+                        "sees every query and the ranks exchange k candidates per query; needs k <= the rows of every "
+                        "rank.  queries: every rank loads and indexes all rows and searches its own; nothing is "
+                        "exchanged.")
     g.add_argument("--device", type=int, default=None, help="GPU ordinal (default $LOCAL_RANK or 0).")
     g.add_argument("--devices", type=str, default=None,
                    help="Comma-separated GPU ordinals: shard the rows over these GPUs (one process each).")
@@ -201,6 +212,46 @@ def check_limits(embedding_dimension, nndescent_n_neighbors):
                          % (_lib.FDR_MAX_K, nndescent_n_neighbors))
 
 
+SPARSE_QUERY_BLOCK_ROWS = 1 << 16  # query rows per call of a sharded sparse search: bounds the device's result buffers
+
+
+def device_list(devices):
+    """The ordinals of --devices (None or empty: none)."""
+    return [int(x) for x in (devices or "").split(",") if x.strip() != ""]
+
+
+def check_sparse_shard(args):
+    """--no-projection, --devices and --sparse-shard against each other, before any work: dividing a sparse search has
+    two costs to choose between (a replicated index, or every query on every rank plus an exchange), so over several
+    GPUs the user chooses."""
+    several = len(device_list(args.devices)) > 1
+    if args.sparse_shard and not args.no_projection:
+        raise SystemExit("--sparse-shard %s needs --no-projection (the projected search shards its rows by itself)"
+                         % args.sparse_shard)
+    if args.sparse_shard and not several:
+        raise SystemExit("--sparse-shard %s needs --devices with at least two GPUs (on one GPU there is nothing to "
+                         "divide)" % args.sparse_shard)
+    if args.no_projection and several and not args.sparse_shard:
+        raise SystemExit("--no-projection with --devices over several GPUs needs to know what to divide: the index "
+                         "(1 / ranks of its memory per GPU, candidates exchanged) or the queries (the whole index on "
+                         "every GPU, nothing exchanged); choose with --sparse-shard targets|queries")
+
+
+def sparse_weights(counts, n_features, metric):
+    """Stage 2 of --no-projection: the feature weights that take the projection's place, float32 [n_features].  The IDF
+    weights for metric="cosine"; clamped at 0 for "weighted_jaccard" (a feature with count > n_features has a negative
+    IDF); None for "jaccard" (sets have no weights).  A row's values are weights[indices]."""
+    if metric == "jaccard":
+        return None
+    w = idf_weights(counts, n_features)
+    if metric == "weighted_jaccard":
+        negative = int(np.count_nonzero(w < 0))
+        logger.info("weighted Jaccard takes weights >= 0: %d of %d features have a negative IDF (count > %d) and "
+                    "carry weight 0", negative, n_features, n_features)
+        w = np.maximum(w, np.float32(0))
+    return w
+
+
 def load_inputs(*, output_dir, embedding_dimension, save_feature_matrix, kmer_searcher_output=None,
                 kmer_library=None, feature_matrix=None, kmer_counts=None, read_names_path=None, save=True,
                 no_projection=False, metric="cosine"):
@@ -218,7 +269,7 @@ def load_inputs(*, output_dir, embedding_dimension, save_feature_matrix, kmer_se
             P = None
         elif no_projection:
             logger.info("--- 2. Generate IDF weights (no projection) ---")
-            P = idf_weights(read_kmer_counts(kmer_library), n_features)
+            P = sparse_weights(read_kmer_counts(kmer_library), n_features, metric)
         else:
             logger.info("--- 2. Generate dimension reduction and IDF matrix ---")
             P, n_features = get_precompute_matrix(n_components=embedding_dimension, counter_file=kmer_library,
@@ -232,17 +283,12 @@ def load_inputs(*, output_dir, embedding_dimension, save_feature_matrix, kmer_se
             P = None
         elif no_projection:
             logger.info("--- 2. Generate IDF weights (no projection) ---")
-            P = idf_weights(counts, n_features)
+            P = sparse_weights(counts, n_features, metric)
         else:
             logger.info("--- 2. Generate dimension reduction and IDF matrix ---")
             P = build_precompute_matrix(counts, embedding_dimension, n_features=n_features)
         logger.info("--- 3. Generate feature matrix ---")
         read_names, strands = _load_names(read_names_path, indptr.size - 1)
-    if no_projection and metric == "weighted_jaccard":
-        negative = int(np.count_nonzero(P < 0))
-        logger.info("weighted Jaccard takes weights >= 0: %d of %d features have a negative IDF (count > %d) and "
-                    "carry weight 0", negative, n_features, n_features)
-        P = np.maximum(P, np.float32(0))
     if save_feature_matrix and save:
         save_feature_matrix_npz(join(output_dir, "feature_matrix.npz"), indptr, indices, n_features)
     return indptr, indices, n_features, P, read_names, strands
@@ -332,14 +378,18 @@ def load_rank_inputs(args, output_dir, rank, world):
     CSR (1 / world of the matrix: the ranged native loader for output.bin; a feature_matrix.npz is inflated whole
     and sliced, scipy's format has no random access) and the names / strands of all rows for the writer.
     Returns (n_rows, lo, hi, indptr, indices, n_features, P, name_off, names, strands); strands is None when
-    name_off / names describe the R records of a doubled matrix (fdr_overlaps_write's doubled-rows mode)."""
+    name_off / names describe the R records of a doubled matrix (fdr_overlaps_write's doubled-rows mode).  With
+    --no-projection the feature weights take P's place (sparse_weights, as in load_inputs: None for jaccard)."""
     from . import _lib
     from .distributed import local_csr, shard_rows
     if args.kmer_searcher_output:
         from .precompute import read_kmer_counts
         n_features = 2 * int(read_kmer_counts(args.kmer_library).size)  # (count_kmers.py:148)
-        P, n_features = get_precompute_matrix(n_components=args.embedding_dimension, counter_file=args.kmer_library,
-                                              n_features=n_features)
+        if args.no_projection:
+            P = sparse_weights(read_kmer_counts(args.kmer_library), n_features, args.no_projection_metric)
+        else:
+            P, n_features = get_precompute_matrix(n_components=args.embedding_dimension,
+                                                  counter_file=args.kmer_library, n_features=n_features)
         try:
             R = _lib.kmer_output_records(args.kmer_searcher_output)  # (the header's count: no record is walked for it)
             n = 2 * R
@@ -361,7 +411,11 @@ def load_rank_inputs(args, output_dir, rank, world):
             del fip, fix
     else:
         indptr, indices, n_features = load_feature_matrix_npz(args.feature_matrix)
-        P = build_precompute_matrix(_load_counts(args.kmer_counts), args.embedding_dimension, n_features=n_features)
+        if args.no_projection:
+            P = sparse_weights(_load_counts(args.kmer_counts), n_features, args.no_projection_metric)
+        else:
+            P = build_precompute_matrix(_load_counts(args.kmer_counts), args.embedding_dimension,
+                                        n_features=n_features)
         n = indptr.size - 1
         _, blocks = shard_rows(n, world)
         lo, hi = blocks[rank]
@@ -411,9 +465,19 @@ def run_rank_worker(args, output_dir, temp_dir):
                         world)
         args.kmer_searcher_output, args.kmer_library = run_stage1_rank(args, temp_dir, ctx, device, args.dist_backend,
                                                                        cuts, is_fastq, args.input)
+    k = args.nndescent_n_neighbors
+    if args.no_projection:
+        idx, dst, lo, name_off, names, strands = _sparse_rank_search(args, output_dir, ctx, rank, world, k)
+        part = join(temp_dir, "overlaps.rank%d.tsv" % rank)
+        rows = _lib.overlaps_write(part, idx, dst, name_off, names, strands, row0=lo, header=rank == 0,
+                                   n_threads=global_variables.threads if global_variables.threads > 1 else 0)
+        logger.debug("rank %d: rows [%d, %d), %d overlap rows", rank, lo, lo + idx.shape[0], rows)
+        dist.barrier()
+        dist.destroy_process_group()
+        ctx.close()
+        return
     n, lo, hi, ip, ix, n_features, P, name_off, names, strands = load_rank_inputs(args, output_dir, rank, world)
     dist.barrier()  # every rank has its rows: what follows is GPU work and short collectives
-    k = args.nndescent_n_neighbors
     Pc = _projection_csr(P)
     ctx.projection_load(Pc.indptr, Pc.indices, Pc.data, n_features, args.embedding_dimension)
     pipe = ShardedPipeline(HipEngine(ctx, device), n, args.embedding_dimension, k, rank=rank, world_size=world,
@@ -433,6 +497,45 @@ def run_rank_worker(args, output_dir, temp_dir):
     dist.barrier()
     dist.destroy_process_group()
     ctx.close()
+
+
+def _sparse_rank_search(args, output_dir, ctx, rank, world, k):
+    """Stage 4 of one rank of `--no-projection --devices ... --sparse-shard ...`: (idx, dist, lo, name_off, names,
+    strands), the rank's rows [lo, lo + rows) of the one-GPU search and what the writer needs.
+    targets: the rank loads ITS row block (load_rank_inputs) and runs distributed.sparse_knn_sharded, whose collectives
+    travel on a gloo group.  queries: the rank loads the whole matrix (load_inputs) and runs distributed.sparse_knn_rank;
+    no collective beyond the worker's barriers."""
+    import torch.distributed as dist
+    from . import _lib
+    from .distributed import sparse_knn_rank, sparse_knn_sharded
+    metric = args.no_projection_metric
+    if args.sparse_shard == "targets":
+        n, lo, hi, ip, ix, n_features, w, name_off, names, strands = load_rank_inputs(args, output_dir, rank, world)
+        dist.barrier()  # every rank has its rows
+        if rank == 0:
+            logger.info("--- 4. Nearest Neighbors Search (exact, metric = %s, %d rows, targets over %d GPUs) ---",
+                        metric, n, world)
+        logger.debug("rank %d of %d holds rows [%d, %d) of %d: %d column ids", rank, world, lo, hi, n, ix.size)
+        try:
+            got = sparse_knn_sharded(ctx, ip, ix, None if w is None else w[ix], n_features, k, metric=metric,
+                                     block_rows=SPARSE_QUERY_BLOCK_ROWS)
+        except ValueError as e:  # (k above a rank's rows: the same words on every rank, before any GPU work)
+            raise SystemExit("--sparse-shard targets: %s" % e) from None
+        assert got[:2] == (lo, hi)
+        return got[2], got[3], lo, name_off, names, strands
+    indptr, indices, n_features, w, read_names, strand_list = load_inputs(
+        output_dir=output_dir, embedding_dimension=args.embedding_dimension,
+        save_feature_matrix=args.save_feature_matrix, kmer_searcher_output=args.kmer_searcher_output,
+        kmer_library=args.kmer_library, feature_matrix=args.feature_matrix, kmer_counts=args.kmer_counts,
+        read_names_path=args.read_names, save=rank == 0, no_projection=True, metric=metric)
+    dist.barrier()  # every rank has the matrix
+    if rank == 0:
+        logger.info("--- 4. Nearest Neighbors Search (exact, metric = %s, %d rows, queries over %d GPUs) ---", metric,
+                    indptr.size - 1, world)
+    lo, hi, idx, dst = sparse_knn_rank(ctx, indptr, indices, None if w is None else w[indices], n_features, k, rank,
+                                       world, metric=metric, block_rows=SPARSE_QUERY_BLOCK_ROWS)
+    name_off, names = _lib.pack_names(read_names)
+    return idx, dst, lo, name_off, names, np.asarray(strand_list, dtype=np.uint8)
 
 
 def launch_rank_workers(argv, args, devices, output_dir, temp_dir, keep_intermediates):
@@ -541,9 +644,7 @@ def main(argv=None):
     global_variables.seed = args.seed
     check_limits(1 if args.no_projection else args.embedding_dimension,  # (-n is not used without the projection)
                  args.nndescent_n_neighbors)  # before any work (the library would only refuse them after stages 1-3)
-    if args.no_projection and args.devices and len([x for x in args.devices.split(",") if x.strip()]) > 1:
-        raise SystemExit("--no-projection runs on one GPU: it cannot be combined with --devices over several GPUs "
-                         "(sharding the sparse search is not implemented)")
+    check_sparse_shard(args)
     if args.no_projection_metric != "cosine" and not args.no_projection:
         raise SystemExit("--no-projection-metric %s needs --no-projection (the projected search is cosine only)"
                          % args.no_projection_metric)
@@ -571,7 +672,7 @@ def main(argv=None):
     logger.info("FEDRANN (MI355X hot path) version: %s", __version__)
     logger.debug("Parameters: %s", args)
     if args.devices:
-        devices = [int(x) for x in args.devices.split(",") if x.strip() != ""]
+        devices = device_list(args.devices)
         if len(devices) > 1:
             return launch_rank_workers(argv, args, devices, output_dir, temp_dir, args.keep_intermediates)
         if devices:

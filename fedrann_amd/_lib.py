@@ -26,12 +26,13 @@ SYMBOLS = (
     "fdr_last_range_sets", "fdr_knn_sparse", "fdr_set_live_chunks", "fdr_knn_sparse_metric",
     "fdr_set_live_skip", "fdr_last_live_stage_lists",
     "fdr_sparse_index_build", "fdr_sparse_index_search", "fdr_sparse_index_info", "fdr_sparse_index_free",
-    "fdr_sparse_index_query",
+    "fdr_sparse_index_query", "fdr_topk_merge",
 )
 FDR_MAX_K = 128
 KERNELS = ("embed_csr", "normalize_rows", "knn_tile", "knn_merge", "knn_prefilter", "knn_rerank",
            "knn_dedup", "kmer_search", "kmer_compact")
 FDR_MAX_DIM = 2048
+TOPK_MERGE_MAX_PARTS = 64  # fdr_topk_merge: one lane of a wave per part
 # fdr_last_query_paths codes (include/fedrann_hip.h: FDR_PATH_*)
 PATH_CERTIFIED, PATH_RANGE, PATH_EXACT, PATH_ZERO, PATH_RANGE_OVERFLOW, PATH_GENERIC, PATH_CLASS_MEMBER = 1, 2, 3, 4, 5, 6, 0x80
 # fdr_last_knn_trace (include/fedrann_hip.h: FDR_TRACE_*, FDR_FALLBACK_*)
@@ -115,6 +116,7 @@ def load_library():
     L.fdr_sparse_index_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i64),
                                         ctypes.POINTER(i64), ctypes.POINTER(sz)]
     L.fdr_sparse_index_free.argtypes = [vp]
+    L.fdr_topk_merge.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp]
     L.fdr_embed_dev.argtypes = [vp, i64, vp, vp, vp, vp]
     L.fdr_normalize_dev.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     L.fdr_knn_workspace_bytes.argtypes = [vp, i64, i64, i32, i32]
@@ -384,6 +386,39 @@ def check_sparse_queries(n, n_features, metric, indptr, indices, values, k):
     if nq > np.iinfo(np.int32).max or indices.size > np.iinfo(np.int32).max:
         raise ValueError("need fewer than 2^31 query rows and stored entries")
     return nq, k
+
+
+def check_topk_merge(idx_parts, dist_parts, k, out=None):
+    """The argument checks of Context.topk_merge (fdr_topk_merge repeats the limits); needs no GPU.  idx_parts int32
+    and dist_parts float32, both C-contiguous [n_parts, nq, kp] with 1 <= n_parts <= 64 and 1 <= kp <= FDR_MAX_K;
+    1 <= k <= min(FDR_MAX_K, n_parts * kp); fewer than 2^31 queries, candidates per part and results; out, if given,
+    C-contiguous (int32 [nq, k], float32 [nq, k]).  What the rows hold (ascending keys, distances >= 0 and not NaN,
+    indices >= 0) is checked on the device.  Returns (n_parts, nq, kp, k)."""
+    for name, a, dt in (("idx_parts", idx_parts, np.int32), ("dist_parts", dist_parts, np.float32)):
+        if not isinstance(a, np.ndarray) or a.dtype != dt:
+            raise TypeError("%s must be a numpy %s array" % (name, np.dtype(dt)))
+        if a.ndim != 3 or not a.flags.c_contiguous:
+            raise ValueError("%s must be a C-contiguous [n_parts, nq, kp] array" % name)
+    if idx_parts.shape != dist_parts.shape:
+        raise ValueError("idx_parts %s and dist_parts %s differ in shape" % (idx_parts.shape, dist_parts.shape))
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError("k must be an integer, got %r" % (k,))
+    (n_parts, nq, kp), k = idx_parts.shape, int(k)
+    if not 1 <= n_parts <= TOPK_MERGE_MAX_PARTS:
+        raise ValueError("need 1 <= n_parts <= %d, got %d" % (TOPK_MERGE_MAX_PARTS, n_parts))
+    if not 1 <= kp <= FDR_MAX_K:
+        raise ValueError("need 1 <= kp <= %d candidates per part, got %d" % (FDR_MAX_K, kp))
+    if not 1 <= k <= FDR_MAX_K or k > n_parts * kp:
+        raise ValueError("need 1 <= k <= min(%d, n_parts * kp = %d), got k = %d" % (FDR_MAX_K, n_parts * kp, k))
+    if nq * max(kp, k) > np.iinfo(np.int32).max:
+        raise ValueError("need fewer than 2^31 candidates per part and results (nq = %d)" % nq)
+    if out is not None:
+        idx, dist = out
+        if not (isinstance(idx, np.ndarray) and isinstance(dist, np.ndarray)) \
+                or (idx.shape, dist.shape) != ((nq, k), (nq, k)) or idx.dtype != np.int32 \
+                or dist.dtype != np.float32 or not (idx.flags.c_contiguous and dist.flags.c_contiguous):
+            raise ValueError("out must be C-contiguous (int32 [nq, k], float32 [nq, k])")
+    return n_parts, nq, kp, k
 
 
 def _row_mass_overflows(indptr, values, largest):
@@ -785,6 +820,20 @@ class Context:
         self._check(self._L.fdr_sparse_index_build(self._h, code, n, F, _ptr(indptr), _ptr(indices), _ptr(values)),
                     "fdr_sparse_index_build")
         return SparseIndex(self, n, metric, self._sparse_gen, n_features=F)
+
+    def topk_merge(self, idx_parts, dist_parts, k, out=None):
+        """The k nearest targets per query over the candidate lists of n_parts ranks: idx_parts int32 and dist_parts
+        float32 [n_parts, nq, kp], part-major as a gather by source rank leaves them, each row ascending by (distance
+        bits, index), the indices global and distinct across a query's parts.  Returns (idx int32 [nq, k], dist
+        float32 [nq, k]): distributed.merge_sparse_topk of the parts bit for bit, merged on the GPU (fdr_topk_merge).
+        A row out of order, a negative or NaN distance and a negative index are refused (FedrannHipError) with
+        nothing written.  out=(idx, dist): caller-owned C-contiguous result arrays.  The context's sparse index and
+        its last k-NN trace stay as they are."""
+        n_parts, nq, kp, k = check_topk_merge(idx_parts, dist_parts, k, out)
+        idx, dist = out if out is not None else (np.empty((nq, k), np.int32), np.empty((nq, k), np.float32))
+        self._check(self._L.fdr_topk_merge(self._h, nq, n_parts, kp, k, _ptr(idx_parts), _ptr(dist_parts), _ptr(idx),
+                                           _ptr(dist)), "fdr_topk_merge")
+        return idx, dist
 
     def embed_knn(self, a_indptr, a_indices, k, return_embedding=False, out=None):
         """out=(idx int32 [n,k], dist float32 [n,k]): caller-owned (e.g. pinned, reused) result arrays."""

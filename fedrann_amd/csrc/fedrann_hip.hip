@@ -701,6 +701,17 @@ struct SparseQuerySet {
     }
 };
 
+// fdr_topk_merge (topk_merge.inc): the parts as uploaded, the merged rows before they are copied out, and the record
+// of a refused call.  Grows as needed; freed with the context.
+struct TopkMergeScratch {
+    DevArray<int> idx_parts;     // [n_parts, nq, kp] the candidates' indices ...
+    DevArray<float> dist_parts;  // ... and distances, part-major
+    DevArray<int> idx_out;       // [nq, k] the merged rows
+    DevArray<float> dist_out;
+    DevArray<u64> refusal;       // [1] the smallest (query, part, rule) the check found; all ones: none
+    void release() { release_all(idx_parts, dist_parts, idx_out, dist_out, refusal); }
+};
+
 struct fdr_ctx {
     int device = 0;
     int num_cus = 256;
@@ -724,6 +735,7 @@ struct fdr_ctx {
     KmerCountScratch kc;
     SparseIndex sp;        // sparse k-NN (knn_sparse.inc): kept until fdr_sparse_index_free
     SparseQuerySet spq;    // ... and the query rows of fdr_sparse_index_query, released with it
+    TopkMergeScratch tm;   // the merge of the ranks' candidate lists (topk_merge.inc): kept until fdr_destroy
     // timing: when enabled, every launch of kernel kind i gets its own hipEvent pair on the launch
     // stream; fdr_timing_read() sums the elapsed times of all launches since the last read
     int knn_mode = FDR_MODE_AUTO;
@@ -2160,6 +2172,7 @@ FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indp
 }
 
 #include "knn_sparse.inc"  // S1 .. S4: exact cosine / Jaccard k-NN on sparse feature rows (fdr_knn_sparse[_metric])
+#include "topk_merge.inc"  // T1: the exact merge of the ranks' candidate lists of a target-sharded sparse search
 #include "kmer_search.inc"
 #include "kmer_output_loader.inc"
 #include "reads_parser.inc"

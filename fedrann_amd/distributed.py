@@ -246,6 +246,116 @@ def merge_sparse_topk(parts, k):
     return np.take_along_axis(idx, order, axis=1), np.take_along_axis(dist, order, axis=1)
 
 
+def sparse_shard_offsets(counts, k):
+    """The ranks' row ranges [(lo, hi), ...] of a target-sharded sparse search from their row counts, in rank order
+    (the counts of shard_rows give its blocks back), after the check that every rank can answer k: a rank's list
+    holds k of ITS rows, so k may not exceed the smallest count.  ValueError otherwise, the same words on every rank,
+    naming the first rank with the fewest rows.  Needs no GPU."""
+    counts = [int(c) for c in counts]
+    if not counts or min(counts) < 0:
+        raise ValueError("need the row count, >= 0, of at least one rank, got %r" % (counts,))
+    k = int(k)
+    short = min(range(len(counts)), key=lambda r: (counts[r], r))
+    if k > counts[short]:
+        raise ValueError("rank %d of %d holds %d target rows: a target-sharded sparse search needs k = %d <= the rows of "
+                         "every rank (use fewer ranks, a smaller k, or shard the queries instead)"
+                         % (short, len(counts), counts[short], k))
+    his = np.cumsum(counts).tolist()
+    return [(hi - c, hi) for c, hi in zip(counts, his)]
+
+
+_gloo_groups = {}  # process group (None: the default one) -> its gloo twin, created once
+
+
+def _host_group(group):
+    """The group the host arrays of sparse_knn_sharded travel on: `group` itself (None: the default group) when its
+    backend is gloo, else a gloo group of the same ranks, created on first use and kept (every rank of the group gets
+    here in the same call, as new_group requires).  Under nccl that creation is the one line of this path that a
+    one-GPU rehearsal cannot run."""
+    if dist.get_backend(group) == "gloo":
+        return group
+    if group not in _gloo_groups:
+        ranks = None if group is None else dist.get_process_group_ranks(group)
+        _gloo_groups[group] = dist.new_group(ranks=ranks, backend="gloo")
+    return _gloo_groups[group]
+
+
+def sparse_knn_sharded(ctx, indptr_local, indices_local, values_local, n_features, k, metric="cosine", group=None,
+                       block_rows=None):
+    """Context.knn_sparse over the ranks of a process group with the TARGETS divided, collective included: every rank
+    calls this with ITS rows only (a CSR with indptr rebased to 0, values alongside or None; the ranks' blocks, in rank
+    order, are the whole matrix) and gets (lo, hi, idx int32 [hi - lo, k], dist float32 [hi - lo, k]): the rows
+    [lo, hi) of knn_sparse on the concatenated CSR bit for bit, neighbour indices global.
+
+    Rounds.  (1) One all-gather of (rows, stored entries, values given?) per rank: every rank knows every lo.  (2)
+    sparse_shard_offsets: k above the smallest rank's rows is the same ValueError on every rank, before any GPU work.
+    (3) Each rank builds the index of its own rows.  (4) For each source rank s in turn: s broadcasts its block (indptr,
+    indices, and values unless they are None), every rank asks its index about the block (SparseIndex.query in blocks of
+    block_rows rows) and adds its own lo to the indices, and the [rows_s, k] lists are gathered to s into one part-major
+    buffer [world, rows_s, k], which is what fdr_topk_merge takes: nothing is transposed.  (5) The index is freed; each
+    rank merges its buffer on its GPU (Context.topk_merge, exact: merge_sparse_topk's docstring), all ranks at once.
+
+    A rank holds on the host its own block, one foreign block, a foreign block's k lists, and world x k candidates for
+    each of its own rows; never the whole CSR, never [n, k].  On the device it holds 1 / world of the index.  Every
+    rank sees every query: the posting walk is divided by the ranks, the upload of the queries is not.
+
+    The arrays are host arrays on both ends (the sparse API takes host pointers), so the exchange runs on a gloo group:
+    `group` (None: the default group) when that is gloo, else a gloo group of the same ranks created once.  Without an
+    initialised process group the call is the one-rank case.  sparse_knn_rank is the alternative that replicates the
+    index and exchanges nothing."""
+    _lib.sparse_metric_code(metric)
+    # (a rank without rows gets as far as the k check, which every rank fails together)
+    n_loc, _, F = _lib._check_sparse(indptr_local, indices_local, values_local, n_features, None, metric, min_rows=0)
+    multi = dist.is_initialized()
+    g = _host_group(group) if multi else None
+    rank, world = (dist.get_rank(g), dist.get_world_size(g)) if multi else (0, 1)
+    src = (lambda s: s if g is None else dist.get_global_rank(g, s))
+    # (1) the row counts
+    mine = torch.tensor([n_loc, indices_local.size, 0 if values_local is None else 1], dtype=torch.int64)
+    every = [torch.empty_like(mine) for _ in range(world)]
+    if multi:
+        dist.all_gather(every, mine, group=g)
+    else:
+        every = [mine]
+    rows, nnz, has_values = (tuple(int(t[c]) for t in every) for c in range(3))
+    if len(set(has_values)) != 1:
+        raise ValueError("the ranks disagree on whether the rows carry values: %r" % (has_values,))
+    # (2) k against the smallest shard, before any GPU work
+    blocks = sparse_shard_offsets(rows, k)
+    lo, hi = blocks[rank]
+    if hi > np.iinfo(np.int32).max:
+        raise ValueError("need fewer than 2^31 rows in all")
+    k = _lib.check_sparse_search(n_loc, k)[0]
+    idx_parts = np.empty((world, n_loc, k), dtype=np.int32)  # the gather's receive buffers, part-major
+    dist_parts = np.empty((world, n_loc, k), dtype=np.float32)
+    # (3), (4)
+    with ctx.sparse_index(indptr_local, indices_local, values_local, F, metric=metric) as index:
+        for s in range(world):
+            if s == rank:
+                ip, ix, vals = indptr_local, indices_local, values_local
+            else:
+                ip = np.empty(rows[s] + 1, dtype=np.int64)
+                ix = np.empty(nnz[s], dtype=np.int32)
+                vals = np.empty(nnz[s], dtype=np.float32) if has_values[s] else None
+            if multi:
+                dist.broadcast(torch.from_numpy(ip), src(s), group=g)
+                if nnz[s]:
+                    dist.broadcast(torch.from_numpy(ix), src(s), group=g)
+                    if vals is not None:
+                        dist.broadcast(torch.from_numpy(vals), src(s), group=g)
+            out = (idx_parts[rank], dist_parts[rank]) if s == rank else None  # (the owner's own part is in place)
+            qi, qd = index.query(ip, ix, vals, k, out=out, block_rows=block_rows)
+            qi += np.int32(lo)
+            if multi:
+                for part, buf in ((qi, idx_parts), (qd, dist_parts)):
+                    dist.gather(torch.from_numpy(part), list(torch.from_numpy(buf).unbind(0)) if s == rank else None,
+                                dst=src(s), group=g)
+            del ip, ix, vals, qi, qd
+    # (5) the index is freed; every rank merges its own rows' lists
+    idx, dst = ctx.topk_merge(idx_parts, dist_parts, k)
+    return lo, hi, idx, dst
+
+
 def local_csr(indptr, indices, lo, hi):
     """Rows [lo, hi) of a host CSR, indptr rebased to 0 (numpy)."""
     ip = np.ascontiguousarray(indptr[lo:hi + 1] - indptr[lo], dtype=np.int64)

@@ -229,6 +229,28 @@ int fdr_sparse_index_info(fdr_ctx *ctx, int32_t *metric, int64_t *n, int64_t *po
 /* Drops the index and frees that memory (fdr_destroy does too).  Without an index: FDR_OK. */
 int fdr_sparse_index_free(fdr_ctx *ctx);
 
+/* ---- merge the candidate lists of a target-sharded sparse search  (fedrann_amd.distributed.sparse_knn_sharded: every
+ *      rank indexes its own rows, answers every query among them, and the owner of a query block merges the ranks'
+ *      lists) -----------------------------------------------------------------------------------------------------------
+ * idx_parts int32 [n_parts, nq, kp] and dist_parts float32 [n_parts, nq, kp], PART-MAJOR: part p's kp candidates of
+ * query q at ((p * nq) + q) * kp, the layout a gather by source rank leaves in its receive buffer.  idx_out int32
+ * [nq, k], dist_out float32 [nq, k].  Host pointers; the call synchronises.  The key of an entry is
+ * (uint64)distance bits << 32 | (uint32)index; row q of the result is the first k entries, ascending by key, of the
+ * union of the query's n_parts rows: fedrann_amd.distributed.merge_sparse_topk bit for bit, whose docstring proves
+ * that this is the one-GPU search's answer under every sparse rule ((distance bits, index) order, the distance-1 fill in
+ * index order, the closed form of a zero query) when each part is a rank's list for the same queries with global indices.
+ * Checked on the device before anything is written to idx_out / dist_out (FDR_E_ARG, fdr_last_error names the rule and
+ * the smallest (query, part) that breaks one): every index >= 0; every distance a non-negative, non-NaN float (sign
+ * bit clear and bits <= 0x7f800000, so bit order is value order); each part's row of each query strictly ascending
+ * by key.  NOT checked, the caller's promise: a query's indices are pairwise distinct across its parts; an index that
+ * two parts hold at the same distance comes out twice, the lower part's first.  Limits (FDR_E_ARG): 1 <= k <=
+ * FDR_MAX_K, 1 <= kp <= FDR_MAX_K, 1 <= n_parts <= 64, n_parts * kp >= k, 0 <= nq < 2^31, nq * kp and nq * k below
+ * 2^31; nq == 0 is FDR_OK and writes nothing; a null context, or a null pointer with nq > 0.  The call touches neither
+ * the context's sparse index nor fdr_last_knn_trace.  Its device buffers (8 bytes per candidate and per result) belong
+ * to the context, only grow and are freed by fdr_destroy.  Cost: the upload of the parts; the kernel reads them once. */
+int fdr_topk_merge(fdr_ctx *ctx, int64_t nq, int32_t n_parts, int32_t kp, int32_t k, const int32_t *idx_parts,
+                   const float *dist_parts, int32_t *idx_out, float *dist_out);
+
 /* ---- device-resident API (multi-GPU host, bench.py) ----------------------------------------
  * All pointers are device pointers; work is enqueued on `stream` (a hipStream_t). */
 int fdr_embed_dev(fdr_ctx *ctx, int64_t n_rows, const int64_t *d_indptr, const int32_t *d_indices,
