@@ -20,6 +20,8 @@ searches its own); either way overlaps.tsv is the one-GPU file byte for byte.
 k-mer sets by exact Jaccard distance (fdr_knn_sparse_metric), the quantity MinHash tools estimate.
 --no-projection-metric weighted_jaccard: stage 2 builds the IDF weights as for cosine (a negative weight, count > F,
 becomes 0) and stage 4 searches the weighted rows by exact weighted Jaccard (Ruzicka) distance.
+--no-projection-radius R (with --no-projection, any metric, one GPU): instead of k neighbours, stage 4 writes every read
+within distance R of each read (0 <= R < 1; fdr_sparse_index_radius_search), a block of rows at a time.
 
 --devices 0,1,...: every stage is sharded over several GPUs of the node.  The parent process starts one
 child per GPU BEFORE it touches a GPU itself; from reads, every child counts and searches its byte range of
@@ -114,6 +116,11 @@ def build_parser():
                         "rank.  queries: every rank loads and indexes all rows and searches its own; nothing is "
                         "exchanged.")
     g.add_argument("--device", type=int, default=None, help="GPU ordinal (default $LOCAL_RANK or 0).")
+    g.add_argument("--no-projection-radius", type=float, default=None, metavar="R",
+                   help="With --no-projection: instead of the k nearest rows, write every row within distance R of "
+                        "each read (0 <= R < 1, under the --no-projection-metric; exact).  overlaps.tsv then holds "
+                        "as many lines per read as it has such neighbours, ranked by distance; "
+                        "--nndescent-n-neighbors is ignored.  One GPU only.")
     g.add_argument("--devices", type=str, default=None,
                    help="Comma-separated GPU ordinals: shard the rows over these GPUs (one process each).")
     g.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
@@ -178,6 +185,43 @@ def write_overlaps(path, neighbor_matrix, distances, read_names, strands, row0=0
     return _lib.overlaps_write(path, np.asarray(neighbor_matrix), np.asarray(distances), name_off, names,
                                np.asarray(strands, dtype=np.uint8), row0=row0, header=header,
                                n_threads=global_variables.threads if global_variables.threads > 1 else 0)
+
+
+RADIUS_BLOCK_ROWS = 1 << 16  # query rows per radius_search call of --no-projection-radius
+RADIUS_MAX_HITS = 1 << 26    # ... and the cap on the hits of one device call (8 bytes held, 8 of scratch, 8 on the host)
+
+
+def check_radius(args):
+    """--no-projection-radius against the other options, before any work."""
+    r = args.no_projection_radius
+    if r is None:
+        return
+    if not args.no_projection:
+        raise SystemExit("--no-projection-radius needs --no-projection (the projected search has no radius form)")
+    if not 0.0 <= np.float32(r) < 1.0:  # (NaN fails both)
+        raise SystemExit("--no-projection-radius must be in [0, 1), got %r (every read is within 1 of every other)" % r)
+    if len(device_list(args.devices)) > 1:
+        raise SystemExit("--no-projection-radius runs on one GPU: the radius search is not sharded over --devices")
+
+
+def write_radius_overlaps(path, index, radius, read_names, strands, block_rows=None, max_hits=None):
+    """overlaps.tsv of a radius search of all rows of `index`, a block of rows at a time: each block's ragged result
+    is appended through fdr_overlaps_write_csr, so the host holds one block's hits.  block_rows / max_hits = None:
+    RADIUS_BLOCK_ROWS / RADIUS_MAX_HITS as they stand at the call.  Returns the data lines."""
+    from . import _lib
+    block_rows = RADIUS_BLOCK_ROWS if block_rows is None else block_rows
+    max_hits = RADIUS_MAX_HITS if max_hits is None else max_hits
+    name_off, names = _lib.pack_names(read_names)
+    strands = np.asarray(strands, dtype=np.uint8)
+    threads = global_variables.threads if global_variables.threads > 1 else 0
+    lines = 0
+    for lo in range(0, index.n, block_rows):
+        hi = min(index.n, lo + block_rows)
+        ip, idx, dist = index.radius_search(radius, lo, hi, max_hits=max_hits)
+        lines += _lib.overlaps_write_csr(path, ip, idx, dist, name_off, names, strands, row0=lo, append=lo > 0,
+                                         header=lo == 0, n_threads=threads)
+        logger.debug("radius search: rows [%d, %d), %d hits", lo, hi, int(ip[-1]))
+    return lines
 
 
 def _load_counts(path):
@@ -298,13 +342,15 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                          nndescent_n_neighbors, save_feature_matrix, keep_intermediates, chunk_size,
                          kmer_searcher_output=None, kmer_library=None, feature_matrix=None,
                          kmer_counts=None, read_names_path=None, no_projection=False,
-                         no_projection_metric="cosine"):
+                         no_projection_metric="cosine", no_projection_radius=None):
     """Stages 2-4 of the reference pipeline (__main__.py:329-391) on one GPU.  The embeddings never leave
     HBM between the projection and the search (fdr_embed_knn), and only the features P has entries for
     cross PCIe (fdr_csr_compact; the saved feature_matrix.npz is the full matrix).  no_projection: stage 4
     searches the IDF-weighted feature rows themselves (value of feature f = idf[f]; fdr_knn_sparse), or with
     no_projection_metric="jaccard" their sets by Jaccard distance, with "weighted_jaccard" the rows with the IDF
-    weights clamped at 0 by weighted Jaccard distance (both fdr_knn_sparse_metric)."""
+    weights clamped at 0 by weighted Jaccard distance (both fdr_knn_sparse_metric).  no_projection_radius: stage 4
+    builds the sparse index and writes every row within that distance of each read (fdr_sparse_index_radius_search)
+    in row blocks, instead of k neighbours."""
     from . import _lib
     from .feature_extraction import _projection_csr
     if kmer_searcher_output:
@@ -317,6 +363,19 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
         kmer_counts=kmer_counts, read_names_path=read_names_path, no_projection=no_projection,
         metric=no_projection_metric)
     ctx = _lib.default_context()
+    if no_projection and no_projection_radius is not None:
+        logger.info("--- 4. Radius search (exact, metric = %s, radius = %g, on the feature rows) ---",
+                    no_projection_metric, no_projection_radius)
+        logger.info("--no-projection-radius: -n/--embedding-dimension (%d) and --nndescent-n-neighbors (%d) are "
+                    "ignored; %d rows x %d features, %d stored entries", embedding_dimension, nndescent_n_neighbors,
+                    indptr.size - 1, n_features, indices.size)
+        values = None if no_projection_metric == "jaccard" else P[indices]
+        with ctx.sparse_index(indptr, indices, values, n_features, metric=no_projection_metric) as index:
+            rows = write_radius_overlaps(join(output_dir, "overlaps.tsv"), index, no_projection_radius, read_names,
+                                         strands)
+        logger.debug("wrote %d overlap rows", rows)
+        _cleanup(keep_intermediates)
+        return
     if no_projection and no_projection_metric == "jaccard":
         logger.info("--- 4. Nearest Neighbors Search (exact, metric = jaccard, on the feature sets) ---")
         logger.info("--no-projection: -n/--embedding-dimension (%d) is ignored; %d rows x %d features, %d stored "
@@ -351,6 +410,10 @@ def _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_in
     logger.debug("Saving overlap table to %s", nbr_output_file)
     rows = write_overlaps(nbr_output_file, neighbor_matrix, distances, read_names, strands)
     logger.debug("wrote %d overlap rows", rows)
+    _cleanup(keep_intermediates)
+
+
+def _cleanup(keep_intermediates):
     if not keep_intermediates and global_variables.temp_dir and os.path.isdir(global_variables.temp_dir):
         logger.debug("Removing intermediate files")
         rmtree(global_variables.temp_dir)
@@ -643,7 +706,10 @@ def main(argv=None):
     global_variables.threads = args.threads
     global_variables.seed = args.seed
     check_limits(1 if args.no_projection else args.embedding_dimension,  # (-n is not used without the projection)
-                 args.nndescent_n_neighbors)  # before any work (the library would only refuse them after stages 1-3)
+                 # (... nor --nndescent-n-neighbors by a radius search)
+                 1 if args.no_projection_radius is not None else args.nndescent_n_neighbors)
+    # (before any work: the library would only refuse them after stages 1-3)
+    check_radius(args)
     check_sparse_shard(args)
     if args.no_projection_metric != "cosine" and not args.no_projection:
         raise SystemExit("--no-projection-metric %s needs --no-projection (the projected search is cosine only)"
@@ -701,7 +767,7 @@ def main(argv=None):
         chunk_size=args.chunk_size, kmer_searcher_output=args.kmer_searcher_output,
         kmer_library=args.kmer_library, feature_matrix=args.feature_matrix,
         kmer_counts=args.kmer_counts, read_names_path=args.read_names, no_projection=args.no_projection,
-        no_projection_metric=args.no_projection_metric)
+        no_projection_metric=args.no_projection_metric, no_projection_radius=args.no_projection_radius)
 
 
 if __name__ == "__main__":

@@ -26,9 +26,11 @@ SYMBOLS = (
     "fdr_last_range_sets", "fdr_knn_sparse", "fdr_set_live_chunks", "fdr_knn_sparse_metric",
     "fdr_set_live_skip", "fdr_last_live_stage_lists",
     "fdr_sparse_index_build", "fdr_sparse_index_search", "fdr_sparse_index_info", "fdr_sparse_index_free",
-    "fdr_sparse_index_query", "fdr_topk_merge",
+    "fdr_sparse_index_query", "fdr_topk_merge", "fdr_sparse_index_radius_search", "fdr_sparse_index_radius_query",
+    "fdr_sparse_index_radius_fetch", "fdr_overlaps_write_csr",
 )
 FDR_MAX_K = 128
+FDR_E_ARG, FDR_E_HIP, FDR_E_NOMEM, FDR_E_STATE, FDR_E_IO = -1, -2, -4, -5, -6  # include/fedrann_hip.h: FDR_E_*
 KERNELS = ("embed_csr", "normalize_rows", "knn_tile", "knn_merge", "knn_prefilter", "knn_rerank",
            "knn_dedup", "kmer_search", "kmer_compact")
 FDR_MAX_DIM = 2048
@@ -113,6 +115,9 @@ def load_library():
     L.fdr_sparse_index_build.argtypes = [vp, i32, i64, i64, vp, vp, vp]
     L.fdr_sparse_index_search.argtypes = [vp, i32, i64, i64, vp, vp]
     L.fdr_sparse_index_query.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp]
+    L.fdr_sparse_index_radius_search.argtypes = [vp, ctypes.c_float, i64, i64, i64, vp]
+    L.fdr_sparse_index_radius_query.argtypes = [vp, ctypes.c_float, i64, vp, vp, vp, i64, vp]
+    L.fdr_sparse_index_radius_fetch.argtypes = [vp, i64, vp, vp]
     L.fdr_sparse_index_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i64),
                                         ctypes.POINTER(i64), ctypes.POINTER(sz)]
     L.fdr_sparse_index_free.argtypes = [vp]
@@ -151,6 +156,7 @@ def load_library():
     L.fdr_host_unregister.argtypes = [vp, vp]
     L.fdr_overlaps_write.argtypes = [ctypes.c_char_p, i32, i32, i64, i64, i64, i32, vp, vp, vp, vp, vp, i32, p64]
     L.fdr_kmer_search.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp, p64]
+    L.fdr_overlaps_write_csr.argtypes = [ctypes.c_char_p, i32, i32, i64, i64, i64, vp, vp, vp, vp, vp, vp, i32, p64]
     L.fdr_kmer_search_indices.argtypes = [vp, vp]
     L.fdr_kmer_count.argtypes = [vp, vp, vp, i64, i32, i64, p64]
     L.fdr_kmer_count_fetch.argtypes = [vp, vp, vp]
@@ -335,6 +341,68 @@ def overlaps_write(path, idx, dist, name_off, names, strands, row0=0, append=Fal
     if rc != 0:
         raise FedrannHipError("fdr_overlaps_write failed (%d): %s" % (rc, L.fdr_last_error().decode()))
     return int(lines.value)
+
+
+def overlaps_write_csr(path, indptr, idx, dist, name_off, names, strands, row0=0, append=False, header=True,
+                       n_threads=0):
+    """overlaps_write for ragged rows (the result of a radius search): row r's entries are idx / dist [indptr[r],
+    indptr[r + 1]), indptr int64 [rows + 1]; neighbor_rank is an entry's position in its row.  See
+    fdr_overlaps_write_csr.  Host only; returns the number of data lines."""
+    L = load_library()
+    indptr = _as(indptr, np.int64, "indptr")
+    idx = _as(idx, np.int32, "idx")
+    dist = _as(dist, np.float32, "dist")
+    if indptr.ndim != 1 or indptr.size < 1 or idx.ndim != 1 or dist.shape != idx.shape:
+        raise ValueError("indptr must be a [rows + 1] array, idx and dist 1-D arrays of the same length")
+    if indptr[0] < 0 or np.any(np.diff(indptr) < 0) or indptr[-1] > idx.size:
+        raise ValueError("indptr is not a row pointer of idx")
+    name_off = _as(name_off, np.int64, "name_off")
+    names = np.ascontiguousarray(names, dtype=np.uint8)
+    if strands is None:  # doubled rows: one name per RECORD, row t = record t >> 1 on strand t & 1
+        n_total = 2 * (name_off.size - 1)
+    else:
+        strands = np.ascontiguousarray(strands, dtype=np.uint8)
+        n_total = name_off.size - 1
+        if strands.size != n_total:
+            raise ValueError("strands must have one entry per row")
+    lines = ctypes.c_int64()
+    rc = L.fdr_overlaps_write_csr(os.fsencode(path), 1 if append else 0, 1 if header else 0, n_total, int(row0),
+                                  indptr.size - 1, _ptr(indptr), _ptr(idx), _ptr(dist), _ptr(name_off),
+                                  names.ctypes.data if names.size else None,
+                                  _ptr(strands) if strands is not None else None, int(n_threads), ctypes.byref(lines))
+    if rc != 0:
+        raise FedrannHipError("fdr_overlaps_write_csr failed (%d): %s" % (rc, L.fdr_last_error().decode()))
+    return int(lines.value)
+
+
+def check_sparse_radius(radius, max_hits=1 << 26):
+    """The argument checks of SparseIndex.radius_search / radius_query that need no GPU: 0 <= radius < 1 (a real number,
+    no NaN) and 1 <= max_hits < 2^31.  Returns (radius as float32, max_hits)."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise ValueError("radius must be a number, got %r" % (radius,))
+    r = np.float32(radius)
+    if not (r >= 0 and r < 1):
+        raise ValueError("need 0 <= radius < 1, got %r (every row is within 1 of every query: search(k) ranks them)"
+                         % (radius,))
+    if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not 1 <= int(max_hits) < 2 ** 31:
+        raise ValueError("max_hits must be an integer in [1, 2^31), got %r" % (max_hits,))
+    return r, int(max_hits)
+
+
+def radius_pieces(counts, max_hits):
+    """Cut rows with the hit counts `counts` into consecutive pieces whose hits fit max_hits: [(a, b), ...] covering
+    [0, len(counts)); None when one row alone exceeds it.  Needs no GPU."""
+    pieces, a, acc = [], 0, 0
+    for i, c in enumerate(counts):
+        c = int(c)
+        if c > max_hits:
+            return None
+        if acc + c > max_hits:
+            pieces.append((a, i))
+            a, acc = i, 0
+        acc += c
+    pieces.append((a, len(counts)))
+    return pieces
 
 
 def sparse_metric_code(metric):
@@ -964,6 +1032,100 @@ class SparseIndex:
             c._check(c._L.fdr_sparse_index_query(c._h, k, b - a, _ptr(ip), _ptr(ix), _ptr(vals), _ptr(idx[a:b]),
                                                  _ptr(dist[a:b])), "fdr_sparse_index_query")
         return idx, dist
+
+    def _radius_call(self, what, call, nq, max_hits):
+        """One raw radius call over nq queries, call(max_hits, indptr) -> rc.  Returns (indptr, idx, dist), or
+        (indptr, None, None) where the total exceeds max_hits: the one refusal that leaves the counts."""
+        c = self._ctx
+        indptr = np.full(nq + 1, -1, dtype=np.int64)
+        rc = call(max_hits, indptr)
+        if rc == FDR_E_ARG and indptr[0] == 0 and indptr[-1] > max_hits:
+            return indptr, None, None
+        c._check(rc, what)
+        total = int(indptr[-1])
+        idx = np.empty(total, dtype=np.int32)
+        dist = np.empty(total, dtype=np.float32)
+        c._check(c._L.fdr_sparse_index_radius_fetch(c._h, total, _ptr(idx), _ptr(dist)), "fdr_sparse_index_radius_fetch")
+        return indptr, idx, dist
+
+    def _radius_rows(self, what, piece, nq, max_hits, first_row):
+        """Rows [0, nq) through piece(a, b) -> the raw call of the rows [a, b); a block over the cap is cut by its
+        counts into pieces that fit, run one by one and concatenated: the uncapped result."""
+        indptr, idx, dist = self._radius_call(what, piece(0, nq), nq, max_hits)
+        if idx is not None:
+            return indptr, idx, dist
+        counts = np.diff(indptr)
+        pieces = radius_pieces(counts, max_hits)
+        if pieces is None:
+            q = int(np.argmax(counts > max_hits))
+            raise FedrannHipError("%s: query %d alone has %d hits, above max_hits = %d"
+                                  % (what, first_row + q, int(counts[q]), max_hits))
+        parts = []
+        for a, b in pieces:
+            ip, ix, ds = self._radius_call(what, piece(a, b), b - a, max_hits)
+            if ix is None or not np.array_equal(np.diff(ip), counts[a:b]):
+                raise FedrannHipError("%s: the rows [%d, %d) gave other counts on their own" % (what, a, b))
+            parts.append((ix, ds))
+        return (indptr, np.concatenate([p[0] for p in parts]) if parts else np.empty(0, np.int32),
+                np.concatenate([p[1] for p in parts]) if parts else np.empty(0, np.float32))
+
+    def radius_search(self, radius, lo=0, hi=None, max_hits=1 << 26):
+        """Every row of the index within distance `radius` (0 <= radius < 1) of each of the rows [lo, hi) (hi=None: n):
+        (indptr int64 [hi - lo + 1], idx int32 [total], dist float32 [total]), row r's hits at [indptr[r], indptr[r + 1])
+        in (distance bits, index) order, self among them: fdr_sparse_index_radius_search, the distances a search(k)
+        reports, bit for bit.  max_hits caps the hits of one device call (8 bytes each, 8 more of scratch); a range
+        with more is cut by its counts into pieces that fit, and the result is the same.  One row with more hits than
+        max_hits raises FedrannHipError."""
+        if isinstance(lo, bool) or isinstance(hi, bool) or not isinstance(lo, (int, np.integer)) \
+                or not (hi is None or isinstance(hi, (int, np.integer))):
+            raise ValueError("lo and hi must be integers, got %r, %r" % (lo, hi))
+        lo, hi = int(lo), int(self.n if hi is None else hi)
+        if not 0 <= lo <= hi <= self.n:
+            raise ValueError("need 0 <= lo <= hi <= n = %d, got [%d, %d)" % (self.n, lo, hi))
+        r, max_hits = check_sparse_radius(radius, max_hits)
+        self._live("SparseIndex.radius_search")
+        c = self._ctx
+
+        def piece(a, b):
+            return lambda cap, ip: c._L.fdr_sparse_index_radius_search(c._h, r, lo + a, lo + b, cap, _ptr(ip))
+        return self._radius_rows("fdr_sparse_index_radius_search", piece, hi - lo, max_hits, lo)
+
+    def radius_query(self, indptr, indices, values, radius, block_rows=None, max_hits=1 << 26):
+        """radius_search for query rows that need not be in the index (a CSR as in query(); there is no self):
+        fdr_sparse_index_radius_query.  Returns (indptr int64 [nq + 1], idx int32 [total], dist float32 [total]).  The
+        index's own rows [lo, hi) give radius_search(radius, lo, hi) bit for bit.  block_rows: the queries go to the
+        device in consecutive blocks of at most that many rows; max_hits as in radius_search, per block."""
+        if self.n_features is None:
+            raise ValueError("SparseIndex.radius_query needs the index's n_features")
+        nq = check_sparse_queries(self.n, self.n_features, self.metric, indptr, indices, values, 1)[0]
+        if block_rows is not None and (isinstance(block_rows, bool) or not isinstance(block_rows, (int, np.integer))
+                                       or int(block_rows) < 1):
+            raise ValueError("block_rows must be an integer >= 1, got %r" % (block_rows,))
+        r, max_hits = check_sparse_radius(radius, max_hits)
+        self._live("SparseIndex.radius_query")
+        c = self._ctx
+        step = max(nq, 1) if block_rows is None else int(block_rows)
+        outs = []
+        for a0 in range(0, max(nq, 1), step):  # (nq = 0: one call, which records the trace)
+            b0 = min(nq, a0 + step)
+
+            def piece(a, b, a0=a0):
+                a, b = a0 + a, a0 + b
+                if a == 0 and b == nq:
+                    ip, ix, vals = indptr, indices, values
+                else:
+                    ip = np.ascontiguousarray(indptr[a:b + 1] - indptr[a])
+                    ix = indices[indptr[a]:indptr[b]]
+                    vals = None if values is None else values[indptr[a]:indptr[b]]
+                return lambda cap, out: c._L.fdr_sparse_index_radius_query(c._h, r, b - a, _ptr(ip), _ptr(ix),
+                                                                           _ptr(vals), cap, _ptr(out))
+            outs.append(self._radius_rows("fdr_sparse_index_radius_query", piece, b0 - a0, max_hits, a0))
+        if len(outs) == 1:
+            return outs[0]
+        lens = np.concatenate([np.diff(o[0]) for o in outs])
+        out_ip = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum(lens, out=out_ip[1:])
+        return out_ip, np.concatenate([o[1] for o in outs]), np.concatenate([o[2] for o in outs])
 
     def info(self):
         """dict of fdr_sparse_index_info: metric, n, postings (stored entries kept), zero_rows (zero rows; Jaccard:

@@ -701,6 +701,33 @@ struct SparseQuerySet {
     }
 };
 
+// The radius searches of the sparse index (knn_sparse_radius.inc): the per-query counts and their scan, the hits as
+// keys (dist_bits << 32 | row) and the held result of the last call, which fdr_sparse_index_radius_fetch copies out.
+// Grows as needed; released with the index.
+struct SparseRadius {
+    DevArray<long long> count, off;  // [nq + 1] the queries' hit counts (a 0 behind them); their exclusive scan
+    DevArray<u64> keys, sorted;      // [total] the heavy queries' hits as found, then the result (see idx());
+                                     // every query's hits in (distance bits, index) order
+    DevArray<long long> seg_lo, seg_hi;  // [heavy queries] their segments of the keys, for the segmented sort
+    DevArray<int> zlist;             // [zero rows of the index] in index order: the row of a zero query
+    DevArray<unsigned char> handed;  // [nq] queries the count pass handed to its range form: the emit pass skips them
+    DevArray<u64> flags;             // [0] queries whose emitted count differs from the counted one; [1] zlist's length
+    long long held = -1;             // hits of the last radius call, until the next sparse call (-1: none)
+    // The heavy queries' unsorted keys are dead once the segmented sort has read them: their 8 bytes per hit take
+    // the result, `held` indices (int32) and behind them `held` distances.
+    int *idx() const { return reinterpret_cast<int *>(keys.ptr()); }
+    float *dist() const { return reinterpret_cast<float *>(idx() + held); }
+    void drop() { held = -1; }
+    size_t bytes() const {
+        return count.bytes() + off.bytes() + keys.bytes() + sorted.bytes() + seg_lo.bytes() + seg_hi.bytes() +
+               zlist.bytes() + handed.bytes() + flags.bytes();
+    }
+    void release() {
+        release_all(count, off, keys, sorted, seg_lo, seg_hi, zlist, handed, flags);
+        held = -1;
+    }
+};
+
 // fdr_topk_merge (topk_merge.inc): the parts as uploaded, the merged rows before they are copied out, and the record
 // of a refused call.  Grows as needed; freed with the context.
 struct TopkMergeScratch {
@@ -735,6 +762,7 @@ struct fdr_ctx {
     KmerCountScratch kc;
     SparseIndex sp;        // sparse k-NN (knn_sparse.inc): kept until fdr_sparse_index_free
     SparseQuerySet spq;    // ... and the query rows of fdr_sparse_index_query, released with it
+    SparseRadius spr;      // ... and the radius searches' counts and hits (knn_sparse_radius.inc), released with it
     TopkMergeScratch tm;   // the merge of the ranks' candidate lists (topk_merge.inc): kept until fdr_destroy
     // timing: when enabled, every launch of kernel kind i gets its own hipEvent pair on the launch
     // stream; fdr_timing_read() sums the elapsed times of all launches since the last read
@@ -2172,6 +2200,7 @@ FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indp
 }
 
 #include "knn_sparse.inc"  // S1 .. S4: exact cosine / Jaccard k-NN on sparse feature rows (fdr_knn_sparse[_metric])
+#include "knn_sparse_radius.inc"  // R1 .. R3: every row within a distance bound (fdr_sparse_index_radius_*)
 #include "topk_merge.inc"  // T1: the exact merge of the ranks' candidate lists of a target-sharded sparse search
 #include "kmer_search.inc"
 #include "kmer_output_loader.inc"

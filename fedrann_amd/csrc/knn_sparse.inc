@@ -405,6 +405,111 @@ struct SpQuerySide {
     int *heavy;                 // the queries handed to S3r
 };
 
+// The table walk of S3 / S3r, shared by the k-NN kernel and the radius kernels (knn_sparse_radius.inc), so a pair gets
+// the same accumulator bits on either path: reset the table, then take the query's stored entries [qb, qe) sixty-four
+// at a time and their features in ascending order; the lanes take a feature's posting entries (RANGE: its slice of the
+// target rows [lo, hi), by binary search) and update the slot of each target.  Returns true where the table would pass
+// SP_LIMIT distinct targets before a chunk of 64 postings (never with RANGE): the hand-off to the range form.  One
+// wave; ends behind a barrier, the table complete.
+template <bool RANGE, int METRIC>
+__device__ __forceinline__ bool sp_walk(u64 *__restrict__ tabw, const long long *__restrict__ runptr,
+                                        const int *__restrict__ prow, const float *__restrict__ pval,
+                                        const int *__restrict__ efeat, const float *__restrict__ xhat, long long qb,
+                                        long long qe, int lo, int hi, int lane) {
+    constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;
+    constexpr bool WJ = METRIC == FDR_METRIC_WEIGHTED_JACCARD;
+    int *tab = reinterpret_cast<int *>(tabw);  // slot s: tab[2 s] = target row (SP_EMPTY), tab[2 s + 1] = acc
+    for (int i = lane; i < SP_CAP; i += 64) tabw[i] = 0x00000000FFFFFFFFull;  // key SP_EMPTY, acc +0 / count 0
+    __syncthreads();
+    int count = 0;  // distinct targets in the table (wave-uniform)
+    bool overflow = false;
+    for (long long j0 = qb; j0 < qe && !overflow; j0 += 64) {
+        // lane l holds the query's stored entry j0 + l: its value and its feature's posting slice
+        const long long j = j0 + lane;
+        int c = -1;
+        float qv = 0.0f;
+        long long ps = 0, pe = 0;
+        if (j < qe) {
+            c = efeat[j];
+            if (c >= 0) {
+                if (!JAC) qv = xhat[j];
+                ps = runptr[c];
+                pe = runptr[c + 1];
+                if (RANGE) {
+                    ps = sp_lower_bound(prow, ps, pe, lo);
+                    pe = sp_lower_bound(prow, ps, pe, hi);
+                }
+            }
+        }
+        u64 live = __ballot(c >= 0 && pe > ps);
+        while (live) {  // the features in ascending order (wave-uniform)
+            const int src = __builtin_ctzll(live);
+            live &= live - 1;
+            const float v = __shfl(qv, src);
+            const long long s0 = __shfl(ps, src), s1 = __shfl(pe, src);
+            for (long long base = s0; base < s1; base += 64) {
+                if (!RANGE && count > SP_LIMIT) {
+                    overflow = true;
+                    break;
+                }
+                const long long e = base + lane;
+                bool isnew = false;
+                if (e < s1) {
+                    const int s = sp_insert(tab, prow[e], isnew);
+                    if (s >= 0) {
+                        if (JAC) {
+                            tab[2 * s + 1] += 1;  // (a new slot holds 0; one lane per target in a step)
+                        } else if (WJ) {
+                            float *a = reinterpret_cast<float *>(&tab[2 * s + 1]);
+                            *a = (isnew ? 0.0f : *a) + fminf(v, pval[e]);
+                        } else {
+                            float *a = reinterpret_cast<float *>(&tab[2 * s + 1]);
+                            *a = __builtin_fmaf(v, pval[e], isnew ? 0.0f : *a);
+                        }
+                    }
+                }
+                count += __popcll(__ballot(isnew));
+                __syncthreads();  // (one wave: orders this step's table writes before the next step's reads)
+            }
+            if (overflow) break;
+        }
+    }
+    return overflow;
+}
+
+// The distance of the query from the target t of an occupied table slot w (target | accumulator << 32): qa = |S_q|
+// (Jaccard), qm = A_q (weighted Jaccard).  Shared like sp_walk.
+template <int METRIC>
+__device__ __forceinline__ float sp_slot_dist(u64 w, int t, int qa, double qm, const int *__restrict__ t_asize,
+                                              const float *__restrict__ t_mass) {
+    if (METRIC == FDR_METRIC_JACCARD) {  // c >= 1 shared features: u = a + b - c >= 1, one fp64 division, one rounding
+        const int c = (int)(unsigned)(w >> 32);
+        const int u = qa + t_asize[t] - c;
+        return (float)((double)(u - c) / (double)u);
+    } else if (METRIC == FDR_METRIC_WEIGHTED_JACCARD) {  // m <= min(A_q, A_t) on the bits and both > 0: u >= max(A_q, A_t) > 0
+        const double m = (double)__uint_as_float((unsigned)(w >> 32));
+        const double u = (qm + (double)t_mass[t]) - m;
+        return (float)((u - m) / u);
+    }
+    return dist_from_sim(__uint_as_float((unsigned)(w >> 32)));
+}
+
+// buf[0, P) ascending, P a power of two >= 64: the bitonic network of one wave; ends behind a barrier
+__device__ __forceinline__ void sp_bitonic(u64 *buf, int P, int lane) {
+    for (int k2 = 2; k2 <= P; k2 <<= 1)
+        for (int jj = k2 >> 1; jj > 0; jj >>= 1) {
+            for (int p = lane; p < P / 2; p += 64) {
+                const int i = ((p & ~(jj - 1)) << 1) | (p & (jj - 1)), ixj = i + jj;
+                const u64 a = buf[i], b = buf[ixj];
+                if ((a > b) == ((i & k2) == 0)) {
+                    buf[i] = b;
+                    buf[ixj] = a;
+                }
+            }
+            __syncthreads();
+        }
+}
+
 // S3 / S3r (METRIC = FDR_METRIC_COSINE), S3j / S3rj (FDR_METRIC_JACCARD: xhat = pval = null, asize = the set sizes)
 // and S3w / S3rw (FDR_METRIC_WEIGHTED_JACCARD: xhat / pval = the raw values, mass = the rows' masses): one wave (one
 // workgroup) per query; the queries are the rows q0 + blockIdx.x of the query side (S3) or the heavy list's (S3r), and
@@ -424,7 +529,6 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q
     const float *__restrict__ xhat = qs.xhat;
     int *__restrict__ heavy = qs.heavy;
     __shared__ u64 buf[SP_LIST + SP_CAP];  // [0, k): the query's list; [SP_LIST, ...): the table, then the sort buffer
-    int *tab = reinterpret_cast<int *>(buf + SP_LIST);  // slot s: tab[2 s] = target row (SP_EMPTY), tab[2 s + 1] = acc
     constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;  // (... or the int32 count of shared features: no values)
     constexpr bool WJ = METRIC == FDR_METRIC_WEIGHTED_JACCARD;  // (acc = the fp32 chain of the minima)
     const int lane = threadIdx.x;
@@ -447,61 +551,8 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q
     for (long long r = 0; r < nranges; ++r) {
         const int lo = RANGE ? (int)(r * SP_W) : 0;
         const int hi = RANGE ? (int)min(n, (long long)lo + SP_W) : (int)n;
-        for (int i = lane; i < SP_CAP; i += 64) buf[SP_LIST + i] = 0x00000000FFFFFFFFull;  // key SP_EMPTY, acc +0 / count 0
-        __syncthreads();
-        int count = 0;  // distinct targets in the table (wave-uniform)
-        bool overflow = false;
-        for (long long j0 = qb; j0 < qe && !overflow; j0 += 64) {
-            // lane l holds the query's stored entry j0 + l: its value and its feature's posting slice
-            const long long j = j0 + lane;
-            int c = -1;
-            float qv = 0.0f;
-            long long ps = 0, pe = 0;
-            if (j < qe) {
-                c = efeat[j];
-                if (c >= 0) {
-                    if (!JAC) qv = xhat[j];
-                    ps = runptr[c];
-                    pe = runptr[c + 1];
-                    if (RANGE) {
-                        ps = sp_lower_bound(prow, ps, pe, lo);
-                        pe = sp_lower_bound(prow, ps, pe, hi);
-                    }
-                }
-            }
-            u64 live = __ballot(c >= 0 && pe > ps);
-            while (live) {  // the features in ascending order (wave-uniform)
-                const int src = __builtin_ctzll(live);
-                live &= live - 1;
-                const float v = __shfl(qv, src);
-                const long long s0 = __shfl(ps, src), s1 = __shfl(pe, src);
-                for (long long base = s0; base < s1; base += 64) {
-                    if (!RANGE && count > SP_LIMIT) {
-                        overflow = true;
-                        break;
-                    }
-                    const long long e = base + lane;
-                    bool isnew = false;
-                    if (e < s1) {
-                        const int s = sp_insert(tab, prow[e], isnew);
-                        if (s >= 0) {
-                            if (JAC) {
-                                tab[2 * s + 1] += 1;  // (a new slot holds 0; one lane per target in a step)
-                            } else if (WJ) {
-                                float *a = reinterpret_cast<float *>(&tab[2 * s + 1]);
-                                *a = (isnew ? 0.0f : *a) + fminf(v, pval[e]);
-                            } else {
-                                float *a = reinterpret_cast<float *>(&tab[2 * s + 1]);
-                                *a = __builtin_fmaf(v, pval[e], isnew ? 0.0f : *a);
-                            }
-                        }
-                    }
-                    count += __popcll(__ballot(isnew));
-                    __syncthreads();  // (one wave: orders this step's table writes before the next step's reads)
-                }
-                if (overflow) break;
-            }
-        }
+        const bool overflow =
+            sp_walk<RANGE, METRIC>(buf + SP_LIST, runptr, prow, pval, efeat, xhat, qb, qe, lo, hi, lane);
         if (overflow) {
             if (lane == 0) heavy[atomicAdd(&cnt[SP_CNT_HEAVY], 1ull)] = (int)q;
             return;
@@ -514,18 +565,7 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q
             const int t = (int)(unsigned)w;
             u64 key = KEY_INF;
             if (t != SP_EMPTY) {
-                float d;
-                if (JAC) {  // c >= 1 shared features: u = a + b - c >= 1, one fp64 division, one rounding
-                    const int c = (int)(unsigned)(w >> 32);
-                    const int u = qa + t_asize[t] - c;
-                    d = (float)((double)(u - c) / (double)u);
-                } else if (WJ) {  // m <= min(A_q, A_t) on the bits and both > 0: u >= max(A_q, A_t) > 0
-                    const double m = (double)__uint_as_float((unsigned)(w >> 32));
-                    const double u = (qm + (double)t_mass[t]) - m;
-                    d = (float)((u - m) / u);
-                } else {
-                    d = dist_from_sim(__uint_as_float((unsigned)(w >> 32)));
-                }
+                const float d = sp_slot_dist<METRIC>(w, t, qa, qm, t_asize, t_mass);
                 if (d < 1.0f) key = ((u64)__float_as_uint(d) << 32) | (unsigned)t;
             }
             cand[i] = key;
@@ -543,18 +583,7 @@ __global__ __launch_bounds__(64) void knn_sparse_kernel(long long n, long long q
         while (P < m) P <<= 1;
         for (int i = m + lane; i < P; i += 64) buf[i] = KEY_INF;
         __syncthreads();
-        for (int k2 = 2; k2 <= P; k2 <<= 1)
-            for (int jj = k2 >> 1; jj > 0; jj >>= 1) {
-                for (int p = lane; p < P / 2; p += 64) {
-                    const int i = ((p & ~(jj - 1)) << 1) | (p & (jj - 1)), ixj = i + jj;
-                    const u64 a = buf[i], b = buf[ixj];
-                    if ((a > b) == ((i & k2) == 0)) {
-                        buf[i] = b;
-                        buf[ixj] = a;
-                    }
-                }
-                __syncthreads();
-            }
+        sp_bitonic(buf, P, lane);
     }
     // the list's keys (all at dist < 1), then the smallest rows outside it at distance 1
     int have = 0;
@@ -786,12 +815,12 @@ static int sp_search_range(fdr_ctx *ctx, int32_t k, int64_t q_lo, int64_t q_hi, 
     return sp_search_tail(ctx, own, k, q_lo, nq, idx_out, dist_out);
 }
 
-// fdr_sparse_index_query behind its checks of the context, k and the result pointers: the checks of the query CSR, its
-// upload into the context's query set, S1q, S4 when a query is zero, and the search's tail with the query set as the
-// query side.  Nothing of the index is written except the search's counters.
-static int sp_query(fdr_ctx *ctx, int32_t k, int64_t nq, const int64_t *indptr, const int32_t *indices,
-                    const float *values, int32_t *idx_out, float *dist_out) {
-    static const char who[] = "sparse_index_query";
+// The query rows of fdr_sparse_index_query and fdr_sparse_index_radius_query (`who` names the entry point in messages):
+// the checks of the query CSR, its upload into the context's query set, the reset of the search's counters and S1q.
+// side = the query set as a query side, zeroq = the zero (empty) rows among the queries.  Nothing of the index is
+// written except the search's counters.
+static int sp_query_side(fdr_ctx *ctx, const char *who, int64_t nq, const int64_t *indptr, const int32_t *indices,
+                         const float *values, SpQuerySide &side, u64 &zeroq) {
     int rc;
     const hipStream_t st = ctx->stream;
     SparseIndex &sp = ctx->sp;
@@ -836,9 +865,21 @@ static int sp_query(fdr_ctx *ctx, int32_t k, int64_t nq, const int64_t *indptr, 
     HIP_TRY(hipMemcpyAsync(h, sp.cnt.ptr() + SP_CNT_ZEROQ, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if ((rc = sp_refuse(who, h[1], sp.built.n_features))) return rc;
-    if (h[0] > 0 && (rc = sp_zero_row(ctx, k))) return rc;  // (the index need not hold a zero row for a query to be one)
-    const SpQuerySide side = {qset.indptr.ptr(), qset.efeat.ptr(), qset.xhat.ptr(),  qset.asize.ptr(),
-                              qset.mass.ptr(),   qset.zero.ptr(),  qset.heavy.ptr()};
+    side = {qset.indptr.ptr(), qset.efeat.ptr(), qset.xhat.ptr(), qset.asize.ptr(),
+            qset.mass.ptr(),   qset.zero.ptr(),  qset.heavy.ptr()};
+    zeroq = h[0];
+    return FDR_OK;
+}
+
+// fdr_sparse_index_query behind its checks of the context, k and the result pointers: the query rows, S4 when a query
+// is zero, and the search's tail with the query set as the query side.
+static int sp_query(fdr_ctx *ctx, int32_t k, int64_t nq, const int64_t *indptr, const int32_t *indices,
+                    const float *values, int32_t *idx_out, float *dist_out) {
+    int rc;
+    SpQuerySide side = {};
+    u64 zeroq = 0;
+    if ((rc = sp_query_side(ctx, "sparse_index_query", nq, indptr, indices, values, side, zeroq))) return rc;
+    if (zeroq > 0 && (rc = sp_zero_row(ctx, k))) return rc;  // (the index need not hold a zero row for a query to be one)
     return sp_search_tail(ctx, side, k, 0, nq, idx_out, dist_out);
 }
 
@@ -848,6 +889,7 @@ static int sp_knn(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, c
     if (rc) return rc;
     knn_call_begin(ctx);
     ctx->sp.built = {};  // (the call replaces the context's index, also where it is refused before the build)
+    ctx->spr.drop();
     if (metric != FDR_METRIC_JACCARD && metric != FDR_METRIC_WEIGHTED_JACCARD && metric != FDR_METRIC_COSINE)
         return fail(FDR_E_ARG, "knn_sparse: unknown metric %d (FDR_METRIC_COSINE, FDR_METRIC_JACCARD, "
                     "FDR_METRIC_WEIGHTED_JACCARD)", metric);
@@ -874,6 +916,7 @@ FDR_EXPORT int fdr_sparse_index_build(fdr_ctx *ctx, int32_t metric, int64_t n, i
                                       const int64_t *indptr, const int32_t *indices, const float *values) {
     int rc = use_device(ctx);
     if (rc) return rc;
+    ctx->spr.drop();
     if ((rc = sp_build(ctx, "sparse_index_build", metric, n, n_features, indptr, indices, values))) return rc;
     ctx->sp.built.valid = false;
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // (a failure of the sort or of S2 belongs to this call: no index)
@@ -886,6 +929,7 @@ FDR_EXPORT int fdr_sparse_index_search(fdr_ctx *ctx, int32_t k, int64_t q_lo, in
     int rc = use_device(ctx);
     if (rc) return rc;
     knn_call_begin(ctx);
+    ctx->spr.drop();
     if (!ctx->sp.built.valid) return fail(FDR_E_STATE, "sparse_index_search: the context holds no sparse index");
     const int64_t n = ctx->sp.built.n;
     if (k < 1 || k > FDR_MAX_K || k > n)
@@ -903,6 +947,7 @@ FDR_EXPORT int fdr_sparse_index_query(fdr_ctx *ctx, int32_t k, int64_t nq, const
     int rc = use_device(ctx);
     if (rc) return rc;
     knn_call_begin(ctx);
+    ctx->spr.drop();
     if (!ctx->sp.built.valid) return fail(FDR_E_STATE, "sparse_index_query: the context holds no sparse index");
     const int64_t n = ctx->sp.built.n;
     if (k < 1 || k > FDR_MAX_K || k > n)
@@ -923,7 +968,8 @@ FDR_EXPORT int fdr_sparse_index_info(fdr_ctx *ctx, int32_t *metric, int64_t *n, 
     if (postings) *postings = ctx->sp.built.kept;
     if (zero_rows) *zero_rows = ctx->sp.built.nzero;
     if (device_bytes) {
-        *device_bytes = ctx->sp.bytes() + ctx->spq.bytes();  // (the query set of fdr_sparse_index_query too)
+        // (the query set of fdr_sparse_index_query and the buffers of the radius searches too)
+        *device_bytes = ctx->sp.bytes() + ctx->spq.bytes() + ctx->spr.bytes();
     }
     return FDR_OK;
 }
@@ -934,5 +980,6 @@ FDR_EXPORT int fdr_sparse_index_free(fdr_ctx *ctx) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->sp.release();
     ctx->spq.release();
+    ctx->spr.release();
     return FDR_OK;
 }

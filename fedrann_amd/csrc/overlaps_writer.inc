@@ -140,32 +140,43 @@ static const char kHeader[] = "query_name\tquery_orientation\ttarget_name\ttarge
 
 }  // namespace ovw
 
-FDR_EXPORT int fdr_overlaps_write(const char *path, int32_t append, int32_t write_header, int64_t n_total,
-                                  int64_t row0, int64_t n_rows, int32_t k, const int32_t *idx, const float *dist,
-                                  const int64_t *name_off, const char *names, const uint8_t *strands, int32_t n_threads,
-                                  int64_t *lines_out) {
-    if (!path || n_total <= 0 || row0 < 0 || n_rows < 0 || row0 + n_rows > n_total || k < 1 || !name_off ||
-        (n_rows > 0 && (!idx || !dist)))
-        return fail(FDR_E_ARG, "overlaps_write: bad argument");
+namespace ovw {
+
+// fdr_overlaps_write (indptr == nullptr: row r's entries are [r k, (r + 1) k)) and fdr_overlaps_write_csr (row r's
+// entries are [indptr[r], indptr[r + 1])): one body, one line formatter
+static int write_rows(const char *who, const char *path, int32_t append, int32_t write_header, int64_t n_total,
+                      int64_t row0, int64_t n_rows, int32_t k, const int64_t *indptr, const int32_t *idx,
+                      const float *dist, const int64_t *name_off, const char *names, const uint8_t *strands,
+                      int32_t n_threads, int64_t *lines_out) {
+    if (!path || n_total <= 0 || row0 < 0 || n_rows < 0 || row0 + n_rows > n_total || k < 1 || !name_off)
+        return fail(FDR_E_ARG, "%s: bad argument", who);
+    int64_t n_entries = n_rows * (int64_t)k;
+    if (indptr) {
+        if (indptr[0] < 0) return fail(FDR_E_ARG, "%s: indptr[0] is negative", who);
+        for (int64_t r = 0; r < n_rows; ++r)
+            if (indptr[r + 1] < indptr[r]) return fail(FDR_E_ARG, "%s: indptr not monotone at row %lld", who, (long long)r);
+        n_entries = indptr[n_rows] - indptr[0];
+    }
+    if (n_entries > 0 && (!idx || !dist)) return fail(FDR_E_ARG, "%s: bad argument", who);
     // strands == NULL: fwd / rev doubled rows as parse_kmer_searcher_output yields them (feature_extraction.py:136-140):
     // names / name_off describe the n_total / 2 RECORDS, row t carries record t >> 1's id and strand t & 1 -- the ids are
     // never materialised twice (10 M reads: 0.7 GB of id bytes per copy, per rank)
     const bool doubled = strands == nullptr;
-    if (doubled && (n_total & 1)) return fail(FDR_E_ARG, "overlaps_write: doubled rows need an even row count");
+    if (doubled && (n_total & 1)) return fail(FDR_E_ARG, "%s: doubled rows need an even row count", who);
     const int64_t n_names = doubled ? n_total / 2 : n_total;
     const int nshift = doubled ? 1 : 0;
-    if (name_off[0] < 0 || (name_off[n_names] > 0 && !names)) return fail(FDR_E_ARG, "overlaps_write: bad names");
+    if (name_off[0] < 0 || (name_off[n_names] > 0 && !names)) return fail(FDR_E_ARG, "%s: bad names", who);
     for (int64_t i = 0; i < n_names; ++i)
-        if (name_off[i + 1] < name_off[i]) return fail(FDR_E_ARG, "overlaps_write: name offsets not monotone at %lld", (long long)i);
+        if (name_off[i + 1] < name_off[i]) return fail(FDR_E_ARG, "%s: name offsets not monotone at %lld", who, (long long)i);
     FILE *f = fopen(path, append ? "ab" : "wb");
     if (!f) return fail(FDR_E_IO, "cannot open %s for writing", path);
-    if (write_header && fwrite(ovw::kHeader, 1, sizeof(ovw::kHeader) - 1, f) != sizeof(ovw::kHeader) - 1) {
+    if (write_header && fwrite(kHeader, 1, sizeof(kHeader) - 1, f) != sizeof(kHeader) - 1) {
         fclose(f);
         return fail(FDR_E_IO, "write to %s failed", path);
     }
     int nthr = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
     nthr = std::max(1, std::min(nthr, 64));
-    if (n_rows * (int64_t)k < (1 << 15)) nthr = 1;
+    if (n_entries < (1 << 15)) nthr = 1;
     const int64_t BLOCK = 4096;  // rows per formatted block
     const int64_t nblocks = (n_rows + BLOCK - 1) / BLOCK;
     std::atomic<int64_t> bad{-1};
@@ -188,8 +199,10 @@ FDR_EXPORT int fdr_overlaps_write(const char *path, int32_t append, int32_t writ
                 const char *qn = names + name_off[qi];
                 const size_t ql = (size_t)(name_off[qi + 1] - name_off[qi]);
                 const char qo = (doubled ? (int)(q & 1) : (int)strands[q]) ? '-' : '+';
-                for (int c = 0; c < k; ++c) {
-                    int64_t t = idx[r * (int64_t)k + c];
+                const int64_t e0 = indptr ? indptr[r] : r * (int64_t)k;
+                const int64_t len = indptr ? indptr[r + 1] - e0 : (int64_t)k;
+                for (int64_t c = 0; c < len; ++c) {
+                    int64_t t = idx[e0 + c];
                     if (t == q) continue;
                     if (t < 0) t += n_total;  // Python's negative indexing (names[-1] is the last read)
                     if (t < 0 || t >= n_total) {
@@ -197,18 +210,18 @@ FDR_EXPORT int fdr_overlaps_write(const char *path, int32_t append, int32_t writ
                         bad.compare_exchange_strong(exp, q);
                         continue;
                     }
-                    ovw::put_name(out, qn, ql);
+                    put_name(out, qn, ql);
                     out.push_back('\t');
                     out.push_back(qo);
                     out.push_back('\t');
                     const int64_t ti = t >> nshift;
-                    ovw::put_name(out, names + name_off[ti], (size_t)(name_off[ti + 1] - name_off[ti]));
+                    put_name(out, names + name_off[ti], (size_t)(name_off[ti + 1] - name_off[ti]));
                     out.push_back('\t');
                     out.push_back((doubled ? (int)(t & 1) : (int)strands[t]) ? '-' : '+');
                     out.push_back('\t');
-                    char *o = ovw::put_uint(tail, (unsigned)c);
+                    char *o = put_uint(tail, (unsigned)c);
                     *o++ = '\t';
-                    o += ovw::format_float32(dist[r * (int64_t)k + c], o);
+                    o += format_float32(dist[e0 + c], o);
                     *o++ = '\n';
                     out.append(tail, (size_t)(o - tail));
                     ++made;
@@ -234,8 +247,28 @@ FDR_EXPORT int fdr_overlaps_write(const char *path, int32_t append, int32_t writ
     }
     if (fclose(f) != 0 && rc == FDR_OK) rc = fail(FDR_E_IO, "closing %s failed", path);
     if (rc == FDR_OK && bad.load() >= 0)
-        rc = fail(FDR_E_ARG, "overlaps_write: row %lld has a neighbour index outside [-%lld, %lld)", (long long)bad.load(),
+        rc = fail(FDR_E_ARG, "%s: row %lld has a neighbour index outside [-%lld, %lld)", who, (long long)bad.load(),
                   (long long)n_total, (long long)n_total);
     if (lines_out) *lines_out = lines;
     return rc;
+}
+
+}  // namespace ovw
+
+FDR_EXPORT int fdr_overlaps_write(const char *path, int32_t append, int32_t write_header, int64_t n_total,
+                                  int64_t row0, int64_t n_rows, int32_t k, const int32_t *idx, const float *dist,
+                                  const int64_t *name_off, const char *names, const uint8_t *strands, int32_t n_threads,
+                                  int64_t *lines_out) {
+    return ovw::write_rows("overlaps_write", path, append, write_header, n_total, row0, n_rows, k, nullptr, idx, dist,
+                           name_off, names, strands, n_threads, lines_out);
+}
+
+// The ragged form: row r's entries are idx / dist [indptr[r], indptr[r + 1]) (the result of a radius search)
+FDR_EXPORT int fdr_overlaps_write_csr(const char *path, int32_t append, int32_t write_header, int64_t n_total,
+                                      int64_t row0, int64_t n_rows, const int64_t *indptr, const int32_t *idx,
+                                      const float *dist, const int64_t *name_off, const char *names,
+                                      const uint8_t *strands, int32_t n_threads, int64_t *lines_out) {
+    if (!indptr) return fail(FDR_E_ARG, "overlaps_write_csr: bad argument");
+    return ovw::write_rows("overlaps_write_csr", path, append, write_header, n_total, row0, n_rows, 1, indptr, idx,
+                           dist, name_off, names, strands, n_threads, lines_out);
 }

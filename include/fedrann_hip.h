@@ -214,6 +214,49 @@ int fdr_sparse_index_search(fdr_ctx *ctx, int32_t k, int64_t q_lo, int64_t q_hi,
  * entry. */
 int fdr_sparse_index_query(fdr_ctx *ctx, int32_t k, int64_t nq, const int64_t *q_indptr, const int32_t *q_indices,
                            const float *q_values, int32_t *idx_out, float *dist_out);
+/* ---- radius search: every index row within a distance bound  (scikit-learn's radius_neighbors; the overlapper's
+ *      "which reads are within distance r of this one", where a fixed k either cuts a deep region short or pads a
+ *      shallow one with distance-1 rows) ----------------------------------------------------------------------------
+ * For a query q and a radius r (float32) the result row is every index row t with dist(q, t) <= r.  The comparison is
+ * made on the float32 distance a k-NN search of the index reports for that pair, under the index's metric, bit for
+ * bit (the same device functions walk the postings and form the distance), and a row is ordered by (distance bits,
+ * index) ascending, the k-NN order.  So:
+ *   - radius domain: 0 <= r < 1.  NaN, a negative r and r >= 1 are FDR_E_ARG: every row is within 1 of every query, and
+ *     ranking them is what fdr_sparse_index_search does;
+ *   - a pair at exactly 1.0f is never a hit: a pair without a shared feature, a Jaccard or weighted-Jaccard quotient
+ *     that rounds to 1.0f, a cosine similarity <= 0;
+ *   - own rows (_radius_search of the rows [q_lo, q_hi)): self is a hit at its distance, as in the k-NN search (the
+ *     overlaps writer drops it); outside rows (_radius_query): there is no self;
+ *   - a zero, empty or zero-mass query: all zero rows of the index, in index order, at distance 0; none against an
+ *     index without zero rows;
+ *   - prefix property: for any k, the entries of fdr_sparse_index_search at k with distance <= r are exactly the first
+ *     min(k, count) entries of the radius row;
+ *   - the index's own rows [lo, hi) passed to _radius_query give _radius_search of [lo, hi) bit for bit.
+ * Counts come first.  The call counts every query's hits before it allocates anything for them and writes indptr_out
+ * (int64 [queries + 1], a host pointer): indptr_out[0] = 0, the last entry the total, row i's hits at [indptr_out[i],
+ * indptr_out[i + 1]).  Only then does it produce the hits, into buffers the context owns (8 bytes per hit held, 8 more
+ * of scratch), and fdr_sparse_index_radius_fetch copies them out: idx_out int32 [hits] (rows of the index), dist_out
+ * float32 [hits]; its `hits` must equal the total (FDR_E_ARG otherwise).  The pattern of fdr_kmer_search /
+ * fdr_kmer_search_indices.  1 <= max_hits < 2^31 (FDR_E_ARG); a total above max_hits is FDR_E_ARG, the message names
+ * the total and the cap, and this is the ONE refusal that has written its output: indptr_out is complete and valid,
+ * so the caller can cut its row block by the counts.  Nothing was allocated for the hits then, nothing is held for
+ * _fetch, and the index is as it was.  The held result is dropped by the next sparse call on the context (a build, a
+ * search, a query, a radius call, fdr_sparse_index_free, fdr_knn_sparse[_metric]); _fetch without one is FDR_E_STATE,
+ * and a fetch leaves it held.  Without an index the radius calls are FDR_E_STATE.  A refused or failed radius call
+ * leaves the index AS IT WAS: a later fdr_sparse_index_search gives the bits from before.  q_lo == q_hi or nq == 0 is
+ * FDR_OK with indptr_out[0] = 0.  0 <= q_lo <= q_hi <= n; the query CSR, its checks, limits and messages are those of
+ * fdr_sparse_index_query.  Host pointers; the calls synchronise; one GPU (the sharded sparse search has no radius
+ * form).  fdr_last_knn_trace: FDR_TRACE_SPARSE with k = 0 and queries, targets, zero_queries, range_queries,
+ * range_chunks as for a search.  The buffers (17 bytes per query of the largest call, 16 per hit of the largest
+ * result, 4 per zero row) are counted in fdr_sparse_index_info's device_bytes and freed by fdr_sparse_index_free and
+ * fdr_destroy.  Cost: the postings are walked twice (count, then emit), about twice the pair updates of a k-NN
+ * search of the same queries; DESIGN.md section 5. */
+int fdr_sparse_index_radius_search(fdr_ctx *ctx, float radius, int64_t q_lo, int64_t q_hi, int64_t max_hits,
+                                   int64_t *indptr_out);
+int fdr_sparse_index_radius_query(fdr_ctx *ctx, float radius, int64_t nq, const int64_t *q_indptr,
+                                  const int32_t *q_indices, const float *q_values, int64_t max_hits,
+                                  int64_t *indptr_out);
+int fdr_sparse_index_radius_fetch(fdr_ctx *ctx, int64_t hits, int32_t *idx_out, float *dist_out);
 /* The context's index (FDR_E_STATE without one); every out pointer may be NULL.  postings: the stored entries that
  * got a posting (cosine: scaled value not +-0; Jaccard: value not +-0; weighted Jaccard: value > 0).  zero_rows: zero
  * rows (Jaccard: empty rows; weighted Jaccard: zero-mass rows).
@@ -366,13 +409,15 @@ int fdr_last_prefilter_launches(fdr_ctx *ctx, int *launches, int *queues);
 /* Diagnostics (test support; nothing in the product reads it): which kernels the most recent k-NN call ran.  With
  * the duplicate-row layer active it describes the inner search of the unique rows.  Every k-NN entry point
  * (fdr_knn_dev, fdr_knn, fdr_embed_knn, fdr_knn_classes_dev, fdr_knn_unique_dev, fdr_knn_expand_dev, fdr_knn_sparse,
- * fdr_knn_sparse_metric, fdr_sparse_index_search, fdr_sparse_index_query) clears it, and
+ * fdr_knn_sparse_metric, fdr_sparse_index_search, fdr_sparse_index_query, fdr_sparse_index_radius_search,
+ * fdr_sparse_index_radius_query) clears it, and
  * the per-query path codes, before it checks its arguments. */
 #define FDR_TRACE_NONE 0       /* no k-NN search ran (a cleared trace, or a call that failed or found nothing to do) */
 #define FDR_TRACE_EXACT 1      /* exact mode: the fp32 kernel for every query */
 #define FDR_TRACE_PREFILTER 2  /* fp16 candidate pass + certificate (+ range pass, + exact fallback) */
 #define FDR_TRACE_GENERIC 3    /* d > 1024, or k > 64 / d > 512 below 8192 targets: the generic kernel */
-#define FDR_TRACE_SPARSE 4     /* fdr_knn_sparse, fdr_sparse_index_search / _query: zero_queries = zero rows among the queries;
+#define FDR_TRACE_SPARSE 4     /* fdr_knn_sparse, fdr_sparse_index_search / _query, the radius searches (k = 0):
+                                  zero_queries = zero rows among the queries;
                                   range_queries = queries whose targets
                                   overflowed the table and were searched over row ranges, range_chunks = the ranges
                                   of each */
@@ -588,6 +633,16 @@ int fdr_kmer_output_append(const char *path, int64_t n_records, const int64_t *n
 int fdr_overlaps_write(const char *path, int32_t append, int32_t write_header, int64_t n_total, int64_t row0,
                        int64_t n_rows, int32_t k, const int32_t *idx, const float *dist, const int64_t *name_off,
                        const char *names, const uint8_t *strands, int32_t n_threads, int64_t *lines_out);
+
+/* The same writer for ragged rows (the result of a radius search): row r's entries are idx / dist [indptr[r],
+ * indptr[r + 1]) instead of [r k, (r + 1) k); indptr int64 [n_rows + 1], monotone, indptr[0] >= 0.  Everything else
+ * is fdr_overlaps_write, through the same line formatter: the entry at position c of its row (a skipped self entry
+ * counts) is written with neighbor_rank c.  A CSR whose rows all have k entries gives fdr_overlaps_write's bytes.
+ * Host only. */
+int fdr_overlaps_write_csr(const char *path, int32_t append, int32_t write_header, int64_t n_total, int64_t row0,
+                           int64_t n_rows, const int64_t *indptr, const int32_t *idx, const float *dist,
+                           const int64_t *name_off, const char *names, const uint8_t *strands, int32_t n_threads,
+                           int64_t *lines_out);
 
 #ifdef __cplusplus
 }
