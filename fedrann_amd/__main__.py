@@ -22,6 +22,9 @@ k-mer sets by exact Jaccard distance (fdr_knn_sparse_metric), the quantity MinHa
 becomes 0) and stage 4 searches the weighted rows by exact weighted Jaccard (Ruzicka) distance.
 --no-projection-radius R (with --no-projection, any metric, one GPU): instead of k neighbours, stage 4 writes every read
 within distance R of each read (0 <= R < 1; fdr_sparse_index_radius_search), a block of rows at a time.
+--radius R (the default, projected mode, one GPU, -n <= 512): stage 4 embeds the rows once, keeps them on the device
+(fdr_dense_index_embed) and writes every read within cosine distance R of each read (0 <= R < 1;
+fdr_dense_index_radius_search), a block of rows at a time; --nndescent-n-neighbors is ignored.
 
 --devices 0,1,...: every stage is sharded over several GPUs of the node.  The parent process starts one
 child per GPU BEFORE it touches a GPU itself; from reads, every child counts and searches its byte range of
@@ -121,6 +124,12 @@ def build_parser():
                         "each read (0 <= R < 1, under the --no-projection-metric; exact).  overlaps.tsv then holds "
                         "as many lines per read as it has such neighbours, ranked by distance; "
                         "--nndescent-n-neighbors is ignored.  One GPU only.")
+    g.add_argument("--radius", type=float, default=None, metavar="R",
+                   help="In the default, projected mode: instead of the k nearest rows, write every row within cosine "
+                        "distance R of each read (0 <= R < 1: the distances the k-NN search reports).  overlaps.tsv "
+                        "then holds as many lines per read as it has such neighbours, ranked by distance; "
+                        "--nndescent-n-neighbors is ignored.  One GPU only, -n up to 512.  With --no-projection: "
+                        "--no-projection-radius.")
     g.add_argument("--devices", type=str, default=None,
                    help="Comma-separated GPU ordinals: shard the rows over these GPUs (one process each).")
     g.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
@@ -187,8 +196,9 @@ def write_overlaps(path, neighbor_matrix, distances, read_names, strands, row0=0
                                n_threads=global_variables.threads if global_variables.threads > 1 else 0)
 
 
-RADIUS_BLOCK_ROWS = 1 << 16  # query rows per radius_search call of --no-projection-radius
-RADIUS_MAX_HITS = 1 << 26    # ... and the cap on the hits of one device call (8 bytes held, 8 of scratch, 8 on the host)
+RADIUS_BLOCK_ROWS = 1 << 16  # query rows per radius_search call of --no-projection-radius and --radius
+RADIUS_MAX_HITS = 1 << 26    # ... and the cap on the hits of one device call (8 bytes held, 8 of scratch, 8 on the host;
+                             # --radius: on its fp16 candidates, 16 bytes each)
 
 
 def check_radius(args):
@@ -204,8 +214,26 @@ def check_radius(args):
         raise SystemExit("--no-projection-radius runs on one GPU: the radius search is not sharded over --devices")
 
 
+def check_dense_radius_args(args):
+    """--radius against the other options, before any work."""
+    from . import _lib
+    r = args.radius
+    if r is None:
+        return
+    if args.no_projection:
+        raise SystemExit("--radius is the projected search's; with --no-projection use --no-projection-radius")
+    if not 0.0 <= np.float32(r) < 1.0:  # (NaN fails both)
+        raise SystemExit("--radius must be in [0, 1), got %r (every read is within 1 of every other)" % r)
+    if len(device_list(args.devices)) > 1:
+        raise SystemExit("--radius runs on one GPU: the radius search is not sharded over --devices")
+    if args.embedding_dimension > _lib.FDR_FAST_MAX_DIM:
+        raise SystemExit("--radius needs -n/--embedding-dimension <= %d, the reach of the fp16 passes (got %d)"
+                         % (_lib.FDR_FAST_MAX_DIM, args.embedding_dimension))
+
+
 def write_radius_overlaps(path, index, radius, read_names, strands, block_rows=None, max_hits=None):
-    """overlaps.tsv of a radius search of all rows of `index`, a block of rows at a time: each block's ragged result
+    """overlaps.tsv of a radius search of all rows of `index` (a SparseIndex or a DenseIndex: both have n and
+    radius_search(radius, lo, hi, max_hits=)), a block of rows at a time: each block's ragged result
     is appended through fdr_overlaps_write_csr, so the host holds one block's hits.  block_rows / max_hits = None:
     RADIUS_BLOCK_ROWS / RADIUS_MAX_HITS as they stand at the call.  Returns the data lines."""
     from . import _lib
@@ -342,7 +370,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                          nndescent_n_neighbors, save_feature_matrix, keep_intermediates, chunk_size,
                          kmer_searcher_output=None, kmer_library=None, feature_matrix=None,
                          kmer_counts=None, read_names_path=None, no_projection=False,
-                         no_projection_metric="cosine", no_projection_radius=None):
+                         no_projection_metric="cosine", no_projection_radius=None, radius=None):
     """Stages 2-4 of the reference pipeline (__main__.py:329-391) on one GPU.  The embeddings never leave
     HBM between the projection and the search (fdr_embed_knn), and only the features P has entries for
     cross PCIe (fdr_csr_compact; the saved feature_matrix.npz is the full matrix).  no_projection: stage 4
@@ -350,7 +378,9 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     no_projection_metric="jaccard" their sets by Jaccard distance, with "weighted_jaccard" the rows with the IDF
     weights clamped at 0 by weighted Jaccard distance (both fdr_knn_sparse_metric).  no_projection_radius: stage 4
     builds the sparse index and writes every row within that distance of each read (fdr_sparse_index_radius_search)
-    in row blocks, instead of k neighbours."""
+    in row blocks, instead of k neighbours.  radius (projected mode): stage 4 embeds once into the context's dense
+    index (fdr_dense_index_embed) and writes every row within that cosine distance of each read
+    (fdr_dense_index_radius_search) in row blocks."""
     from . import _lib
     from .feature_extraction import _projection_csr
     if kmer_searcher_output:
@@ -398,6 +428,15 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     cip, cix = ctx.csr_compact(indptr, indices)
     logger.debug("embedding %d rows: %d of %d feature ids have an entry in P", indptr.size - 1, cix.size, indices.size)
     del indptr, indices
+    if radius is not None:
+        logger.info("--- 4. Radius search (projected rows, cosine, radius = %g) ---", radius)
+        logger.info("--radius: --nndescent-n-neighbors (%d) is ignored; %d rows, d = %d", nndescent_n_neighbors,
+                    cip.size - 1, embedding_dimension)
+        with ctx.dense_index_from_csr(cip, cix) as index:
+            rows = write_radius_overlaps(join(output_dir, "overlaps.tsv"), index, radius, read_names, strands)
+        logger.debug("wrote %d overlap rows", rows)
+        _cleanup(keep_intermediates)
+        return
     logger.info("--- 4. Nearest Neighbors Search ---")
     logger.info("Using exact GPU k-NN in place of NNDescent (n_trees = %s, leaf_size = %s are inert)",
                 nndescent_n_trees, 200)
@@ -707,9 +746,10 @@ def main(argv=None):
     global_variables.seed = args.seed
     check_limits(1 if args.no_projection else args.embedding_dimension,  # (-n is not used without the projection)
                  # (... nor --nndescent-n-neighbors by a radius search)
-                 1 if args.no_projection_radius is not None else args.nndescent_n_neighbors)
+                 1 if args.no_projection_radius is not None or args.radius is not None else args.nndescent_n_neighbors)
     # (before any work: the library would only refuse them after stages 1-3)
     check_radius(args)
+    check_dense_radius_args(args)
     check_sparse_shard(args)
     if args.no_projection_metric != "cosine" and not args.no_projection:
         raise SystemExit("--no-projection-metric %s needs --no-projection (the projected search is cosine only)"
@@ -767,7 +807,8 @@ def main(argv=None):
         chunk_size=args.chunk_size, kmer_searcher_output=args.kmer_searcher_output,
         kmer_library=args.kmer_library, feature_matrix=args.feature_matrix,
         kmer_counts=args.kmer_counts, read_names_path=args.read_names, no_projection=args.no_projection,
-        no_projection_metric=args.no_projection_metric, no_projection_radius=args.no_projection_radius)
+        no_projection_metric=args.no_projection_metric, no_projection_radius=args.no_projection_radius,
+        radius=args.radius)
 
 
 if __name__ == "__main__":

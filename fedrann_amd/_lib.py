@@ -28,7 +28,10 @@ SYMBOLS = (
     "fdr_sparse_index_build", "fdr_sparse_index_search", "fdr_sparse_index_info", "fdr_sparse_index_free",
     "fdr_sparse_index_query", "fdr_topk_merge", "fdr_sparse_index_radius_search", "fdr_sparse_index_radius_query",
     "fdr_sparse_index_radius_fetch", "fdr_overlaps_write_csr",
+    "fdr_dense_index_build", "fdr_dense_index_embed", "fdr_dense_index_radius_search", "fdr_dense_index_radius_query",
+    "fdr_dense_index_radius_fetch", "fdr_dense_index_info", "fdr_dense_index_free",
 )
+FDR_FAST_MAX_DIM = 512  # the reach of the fp16 passes, and so of the dense index (csrc/knn_plan.inc)
 FDR_MAX_K = 128
 FDR_E_ARG, FDR_E_HIP, FDR_E_NOMEM, FDR_E_STATE, FDR_E_IO = -1, -2, -4, -5, -6  # include/fedrann_hip.h: FDR_E_*
 KERNELS = ("embed_csr", "normalize_rows", "knn_tile", "knn_merge", "knn_prefilter", "knn_rerank",
@@ -121,6 +124,15 @@ def load_library():
     L.fdr_sparse_index_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i64),
                                         ctypes.POINTER(i64), ctypes.POINTER(sz)]
     L.fdr_sparse_index_free.argtypes = [vp]
+    L.fdr_dense_index_build.argtypes = [vp, vp, i64, i32]
+    L.fdr_dense_index_embed.argtypes = [vp, i64, vp, vp]
+    L.fdr_dense_index_radius_search.argtypes = [vp, ctypes.c_float, i64, i64, i64, vp]
+    L.fdr_dense_index_radius_query.argtypes = [vp, ctypes.c_float, i64, vp, i64, vp]
+    L.fdr_dense_index_radius_fetch.argtypes = [vp, i64, vp, vp]
+    L.fdr_dense_index_info.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(sz),
+                                       ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                       ctypes.POINTER(i32)]
+    L.fdr_dense_index_free.argtypes = [vp]
     L.fdr_topk_merge.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp]
     L.fdr_embed_dev.argtypes = [vp, i64, vp, vp, vp, vp]
     L.fdr_normalize_dev.argtypes = [vp, vp, i64, i32, vp, vp, vp]
@@ -389,6 +401,33 @@ def check_sparse_radius(radius, max_hits=1 << 26):
     return r, int(max_hits)
 
 
+def check_dense_radius(n, d, radius, lo=0, hi=None, max_hits=1 << 26):
+    """The argument checks of DenseIndex.radius_search that need no GPU, for an index of n rows of dimension d:
+    1 <= n < 2^31, 1 <= d <= 512 (the reach of the fp16 passes), 0 <= radius < 1 (a real number, no NaN), 0 <= lo <= hi
+    <= n (hi=None: n) and 1 <= max_hits < 2^31.  Returns (radius as float32, lo, hi, max_hits)."""
+    for name, v in (("n", n), ("d", d), ("lo", lo)) + ((("hi", hi),) if hi is not None else ()):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    n, d = int(n), int(d)
+    if not 1 <= n < 2 ** 31:
+        raise ValueError("the dense index needs 1 <= n < 2^31 rows, got %d" % n)
+    if not 1 <= d <= FDR_FAST_MAX_DIM:
+        raise ValueError("the dense index needs 1 <= d <= %d (the reach of the fp16 passes), got %d"
+                         % (FDR_FAST_MAX_DIM, d))
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise ValueError("radius must be a number, got %r" % (radius,))
+    r = np.float32(radius)
+    if not (r >= 0 and r < 1):
+        raise ValueError("need 0 <= radius < 1, got %r (every row is within 1 of every query: knn(E, k) ranks them)"
+                         % (radius,))
+    lo, hi = int(lo), int(n if hi is None else hi)
+    if not 0 <= lo <= hi <= n:
+        raise ValueError("need 0 <= lo <= hi <= n = %d, got [%d, %d)" % (n, lo, hi))
+    if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not 1 <= int(max_hits) < 2 ** 31:
+        raise ValueError("max_hits must be an integer in [1, 2^31), got %r" % (max_hits,))
+    return r, lo, hi, int(max_hits)
+
+
 def radius_pieces(counts, max_hits):
     """Cut rows with the hit counts `counts` into consecutive pieces whose hits fit max_hits: [(a, b), ...] covering
     [0, len(counts)); None when one row alone exceeds it.  Needs no GPU."""
@@ -559,6 +598,7 @@ class Context:
         self.n_features = 0
         self.d = 0
         self._sparse_gen = 0  # builds of the context's sparse index so far (SparseIndex: is mine still the one?)
+        self._dense_gen = 0   # ... and of its dense index (DenseIndex)
 
     def _err(self):
         return self._L.fdr_last_error().decode("utf-8", "replace")
@@ -889,6 +929,33 @@ class Context:
                     "fdr_sparse_index_build")
         return SparseIndex(self, n, metric, self._sparse_gen, n_features=F)
 
+    def dense_index(self, E):
+        """The dense index of the rows E float32 [n, d] (not normalised, knn()'s argument; 1 <= d <= 512), kept on the
+        device for any number of DenseIndex.radius_search / radius_query calls: fdr_dense_index_build.  A context
+        holds one dense index, beside its sparse one: this call and dense_index_from_csr replace it, and a DenseIndex
+        of the replaced one raises from then on."""
+        E = _as(E, np.float32, "E")
+        if E.ndim != 2:
+            raise ValueError("E must be 2-D")
+        n, d = E.shape
+        check_dense_radius(n, d, 0.0)
+        self._dense_gen += 1
+        self._check(self._L.fdr_dense_index_build(self._h, _ptr(E), n, d), "fdr_dense_index_build")
+        return DenseIndex(self, n, d, self._dense_gen)
+
+    def dense_index_from_csr(self, a_indptr, a_indices):
+        """The dense index of the rows embed(a_indptr, a_indices) would return, which stay on the device:
+        fdr_dense_index_embed.  Needs projection_load; the same index as dense_index(embed(...)), bit for bit."""
+        a_indptr = _as(a_indptr, np.int64, "a_indptr")
+        a_indices = _as(a_indices, np.int32, "a_indices")
+        n = a_indptr.shape[0] - 1
+        if self.d < 1:
+            raise FedrannHipError("dense_index_from_csr: no projection loaded")
+        check_dense_radius(n, self.d, 0.0)
+        self._dense_gen += 1
+        self._check(self._L.fdr_dense_index_embed(self._h, n, _ptr(a_indptr), _ptr(a_indices)), "fdr_dense_index_embed")
+        return DenseIndex(self, n, self.d, self._dense_gen)
+
     def topk_merge(self, idx_parts, dist_parts, k, out=None):
         """The k nearest targets per query over the candidate lists of n_parts ranks: idx_parts int32 and dist_parts
         float32 [n_parts, nq, kp], part-major as a gather by source rank leaves them, each row ascending by (distance
@@ -957,23 +1024,75 @@ class Context:
                                                int(u_row_stride), d_idx, d_dist, stream or None), "fdr_knn_expand_dev")
 
 
-class SparseIndex:
+class _HeldIndex:
+    """What SparseIndex and DenseIndex share: the liveness guard of an index that lives in its context, and the radius
+    calls' protocol (counts first, one refusal that leaves them, a fetch; a block over the cap cut by its counts).  A
+    subclass names its kind, the context's generation counter, its fetch symbol, what max_hits counts, and whether
+    the counts a refusal leaves are exact (sparse: the hits) or upper bounds of the pieces' counts (dense: the fp16
+    candidates)."""
+    _kind = _gen_attr = _fetch = _counted = None
+    _exact_counts = True
+
+    def _live(self, what):
+        if not self._open:
+            raise FedrannHipError("%s: the %s index is closed" % (what, self._kind))
+        if not getattr(self._ctx, "_h", None):
+            raise FedrannHipError("%s: the context of the %s index is closed" % (what, self._kind))
+        if getattr(self._ctx, self._gen_attr) != self._gen:
+            raise FedrannHipError("%s: the context has built another %s index since this one" % (what, self._kind))
+
+    def _radius_call(self, what, call, nq, max_hits):
+        """One raw radius call over nq queries, call(max_hits, indptr) -> rc.  Returns (indptr, idx, dist), or
+        (indptr, None, None) where the total exceeds max_hits: the one refusal that leaves the counts."""
+        c = self._ctx
+        indptr = np.full(nq + 1, -1, dtype=np.int64)
+        rc = call(max_hits, indptr)
+        if rc == FDR_E_ARG and indptr[0] == 0 and indptr[-1] > max_hits:
+            return indptr, None, None
+        c._check(rc, what)
+        total = int(indptr[-1])
+        idx = np.empty(total, dtype=np.int32)
+        dist = np.empty(total, dtype=np.float32)
+        c._check(getattr(c._L, self._fetch)(c._h, total, _ptr(idx), _ptr(dist)), self._fetch)
+        return indptr, idx, dist
+
+    def _radius_rows(self, what, piece, nq, max_hits, first_row):
+        """Rows [0, nq) through piece(a, b) -> the raw call of the rows [a, b); a block over the cap is cut by its
+        counts into pieces that fit, run one by one and concatenated: the uncapped result."""
+        indptr, idx, dist = self._radius_call(what, piece(0, nq), nq, max_hits)
+        if idx is not None:
+            return indptr, idx, dist
+        counts = np.diff(indptr)
+        pieces = radius_pieces(counts, max_hits)
+        if pieces is None:
+            q = int(np.argmax(counts > max_hits))
+            raise FedrannHipError("%s: query %d alone has %d %s, above max_hits = %d"
+                                  % (what, first_row + q, int(counts[q]), self._counted, max_hits))
+        parts = []
+        for a, b in pieces:
+            ip, ix, ds = self._radius_call(what, piece(a, b), b - a, max_hits)
+            got = None if ix is None else np.diff(ip)
+            if got is None or (not np.array_equal(got, counts[a:b]) if self._exact_counts else np.any(got > counts[a:b])):
+                raise FedrannHipError("%s: the rows [%d, %d) gave other counts on their own" % (what, a, b))
+            parts.append((got, ix, ds))
+        out_ip = np.zeros(nq + 1, dtype=np.int64)
+        if parts:
+            np.cumsum(np.concatenate([p[0] for p in parts]), out=out_ip[1:])
+        return (out_ip, np.concatenate([p[1] for p in parts]) if parts else np.empty(0, np.int32),
+                np.concatenate([p[2] for p in parts]) if parts else np.empty(0, np.float32))
+
+
+class SparseIndex(_HeldIndex):
     """The sparse index of a Context (Context.sparse_index): search row ranges of it, at any k, any number of times.
     The index lives in the context, which holds one: once the context has built another (sparse_index, knn_sparse),
     or after close(), search and info raise FedrannHipError."""
+
+    _kind, _gen_attr, _fetch, _counted = "sparse", "_sparse_gen", "fdr_sparse_index_radius_fetch", "hits"
 
     def __init__(self, ctx, n, metric, gen, n_features=None):
         self._ctx, self.n, self.metric, self._gen = ctx, int(n), metric, gen
         self.n_features = None if n_features is None else int(n_features)  # (None: query() is not available)
         self._open = True
-
-    def _live(self, what):
-        if not self._open:
-            raise FedrannHipError("%s: the sparse index is closed" % what)
-        if not getattr(self._ctx, "_h", None):
-            raise FedrannHipError("%s: the context of the sparse index is closed" % what)
-        if self._ctx._sparse_gen != self._gen:
-            raise FedrannHipError("%s: the context has built another sparse index since this one" % what)
 
     def search(self, k, lo=0, hi=None, out=None):
         """Neighbours of the rows [lo, hi) (hi=None: n) among all n rows: (idx int32 [hi - lo, k], dist float32
@@ -1032,42 +1151,6 @@ class SparseIndex:
             c._check(c._L.fdr_sparse_index_query(c._h, k, b - a, _ptr(ip), _ptr(ix), _ptr(vals), _ptr(idx[a:b]),
                                                  _ptr(dist[a:b])), "fdr_sparse_index_query")
         return idx, dist
-
-    def _radius_call(self, what, call, nq, max_hits):
-        """One raw radius call over nq queries, call(max_hits, indptr) -> rc.  Returns (indptr, idx, dist), or
-        (indptr, None, None) where the total exceeds max_hits: the one refusal that leaves the counts."""
-        c = self._ctx
-        indptr = np.full(nq + 1, -1, dtype=np.int64)
-        rc = call(max_hits, indptr)
-        if rc == FDR_E_ARG and indptr[0] == 0 and indptr[-1] > max_hits:
-            return indptr, None, None
-        c._check(rc, what)
-        total = int(indptr[-1])
-        idx = np.empty(total, dtype=np.int32)
-        dist = np.empty(total, dtype=np.float32)
-        c._check(c._L.fdr_sparse_index_radius_fetch(c._h, total, _ptr(idx), _ptr(dist)), "fdr_sparse_index_radius_fetch")
-        return indptr, idx, dist
-
-    def _radius_rows(self, what, piece, nq, max_hits, first_row):
-        """Rows [0, nq) through piece(a, b) -> the raw call of the rows [a, b); a block over the cap is cut by its
-        counts into pieces that fit, run one by one and concatenated: the uncapped result."""
-        indptr, idx, dist = self._radius_call(what, piece(0, nq), nq, max_hits)
-        if idx is not None:
-            return indptr, idx, dist
-        counts = np.diff(indptr)
-        pieces = radius_pieces(counts, max_hits)
-        if pieces is None:
-            q = int(np.argmax(counts > max_hits))
-            raise FedrannHipError("%s: query %d alone has %d hits, above max_hits = %d"
-                                  % (what, first_row + q, int(counts[q]), max_hits))
-        parts = []
-        for a, b in pieces:
-            ip, ix, ds = self._radius_call(what, piece(a, b), b - a, max_hits)
-            if ix is None or not np.array_equal(np.diff(ip), counts[a:b]):
-                raise FedrannHipError("%s: the rows [%d, %d) gave other counts on their own" % (what, a, b))
-            parts.append((ix, ds))
-        return (indptr, np.concatenate([p[0] for p in parts]) if parts else np.empty(0, np.int32),
-                np.concatenate([p[1] for p in parts]) if parts else np.empty(0, np.float32))
 
     def radius_search(self, radius, lo=0, hi=None, max_hits=1 << 26):
         """Every row of the index within distance `radius` (0 <= radius < 1) of each of the rows [lo, hi) (hi=None: n):
@@ -1145,6 +1228,92 @@ class SparseIndex:
         c = self._ctx
         if self._open and getattr(c, "_h", None) and c._sparse_gen == self._gen:
             c._check(c._L.fdr_sparse_index_free(c._h), "fdr_sparse_index_free")
+        self._open = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class DenseIndex(_HeldIndex):
+    """The dense index of a Context (Context.dense_index / dense_index_from_csr): radius searches on the projected rows,
+    any number of times.  The index lives in the context, which holds one: once the context has built another, or
+    after close(), the calls raise FedrannHipError."""
+
+    _kind, _gen_attr, _fetch, _counted = "dense", "_dense_gen", "fdr_dense_index_radius_fetch", "candidates"
+    _exact_counts = False  # (a refusal leaves candidate counts: upper bounds of what the pieces return)
+
+    def __init__(self, ctx, n, d, gen):
+        self._ctx, self.n, self.d, self._gen = ctx, int(n), int(d), gen
+        self._open = True
+
+    def radius_search(self, radius, lo=0, hi=None, max_hits=1 << 26):
+        """Every row of the index within cosine distance `radius` (0 <= radius < 1) of each of the rows [lo, hi)
+        (hi=None: n): (indptr int64 [hi - lo + 1], idx int32 [total], dist float32 [total]), row r's hits at
+        [indptr[r], indptr[r + 1]) in (distance bits, index) order, self among them: fdr_dense_index_radius_search, the
+        distances knn(E, k) reports, bit for bit.  max_hits caps the fp16 CANDIDATES of one device call (16 bytes
+        each); a range with more is cut by its candidate counts into pieces that fit, and the result is the same.  One
+        row with more candidates than max_hits raises FedrannHipError."""
+        r, lo, hi, max_hits = check_dense_radius(self.n, self.d, radius, lo, hi, max_hits)
+        self._live("DenseIndex.radius_search")
+        c = self._ctx
+
+        def piece(a, b):
+            return lambda cap, ip: c._L.fdr_dense_index_radius_search(c._h, r, lo + a, lo + b, cap, _ptr(ip))
+        return self._radius_rows("fdr_dense_index_radius_search", piece, hi - lo, max_hits, lo)
+
+    def radius_query(self, Q, radius, block_rows=None, max_hits=1 << 26):
+        """radius_search for query rows Q float32 [nq, d] that need not be in the index (not normalised; there is no
+        self): fdr_dense_index_radius_query.  Returns (indptr int64 [nq + 1], idx int32 [total], dist float32
+        [total]).  The rows [lo, hi) of the indexed E give radius_search(radius, lo, hi) bit for bit.  block_rows: the
+        queries go to the device in consecutive blocks of at most that many rows; max_hits as in radius_search, per
+        block."""
+        Q = _as(Q, np.float32, "Q")
+        if Q.ndim != 2 or Q.shape[1] != self.d:
+            raise ValueError("Q must be [nq, %d], got shape %r" % (self.d, Q.shape))
+        nq = Q.shape[0]
+        if block_rows is not None and (isinstance(block_rows, bool) or not isinstance(block_rows, (int, np.integer))
+                                       or int(block_rows) < 1):
+            raise ValueError("block_rows must be an integer >= 1, got %r" % (block_rows,))
+        r, _, _, max_hits = check_dense_radius(self.n, self.d, radius, 0, None, max_hits)
+        self._live("DenseIndex.radius_query")
+        c = self._ctx
+        step = max(nq, 1) if block_rows is None else int(block_rows)
+        outs = []
+        for a0 in range(0, max(nq, 1), step):
+            b0 = min(nq, a0 + step)
+
+            def piece(a, b, a0=a0):
+                rows = Q[a0 + a:a0 + b]  # (a row block of a C-contiguous array is C-contiguous)
+                return lambda cap, out: c._L.fdr_dense_index_radius_query(c._h, r, b - a, _ptr(rows) if b > a else None,
+                                                                          cap, _ptr(out))
+            outs.append(self._radius_rows("fdr_dense_index_radius_query", piece, b0 - a0, max_hits, a0))
+        if len(outs) == 1:
+            return outs[0]
+        out_ip = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum(np.concatenate([np.diff(o[0]) for o in outs]), out=out_ip[1:])
+        return out_ip, np.concatenate([o[1] for o in outs]), np.concatenate([o[2] for o in outs])
+
+    def info(self):
+        """dict of fdr_dense_index_info: n, d, device_bytes (what the dense index holds on the device, the radius
+        calls' buffers included) and, of the last radius call, last_candidates (fp16 candidates), last_hits,
+        last_query_blocks and last_segments (the grid of its range pass)."""
+        self._live("DenseIndex.info")
+        c = self._ctx
+        n, d, b = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_size_t()
+        lc, lh, qb, sg = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+        c._check(c._L.fdr_dense_index_info(c._h, ctypes.byref(n), ctypes.byref(d), ctypes.byref(b), ctypes.byref(lc),
+                                           ctypes.byref(lh), ctypes.byref(qb), ctypes.byref(sg)), "fdr_dense_index_info")
+        return {"n": int(n.value), "d": int(d.value), "device_bytes": int(b.value), "last_candidates": int(lc.value),
+                "last_hits": int(lh.value), "last_query_blocks": int(qb.value), "last_segments": int(sg.value)}
+
+    def close(self):
+        """Free the index's device memory (if it still is the context's dense index)."""
+        c = self._ctx
+        if self._open and getattr(c, "_h", None) and c._dense_gen == self._gen:
+            c._check(c._L.fdr_dense_index_free(c._h), "fdr_dense_index_free")
         self._open = False
 
     def __enter__(self):

@@ -728,6 +728,51 @@ struct SparseRadius {
     }
 };
 
+// The context's one dense index (knn_dense_radius.inc): what fdr_dense_index_build / _embed leave for the radius
+// searches, and those searches' buffers.  Independent of the sparse index; grows as needed; kept until
+// fdr_dense_index_free.
+struct DenseIndex {
+    DevArray<float> ehat;          // [n, dp] the normalised rows (normalize_rows_kernel's layout)
+    DevArray<_Float16> half;       // ... their fp16 copy, which the range pass streams
+    DevArray<unsigned char> zero;  // [n] zero rows
+    DevArray<float> qhat;          // fdr_dense_index_radius_query: the call's query rows, likewise
+    DevArray<_Float16> qhalf;
+    DevArray<unsigned char> qzero;
+    DevArray<float> theta;         // [nq] the queries' thresholds (a zero query: -inf)
+    DevArray<long long> count, off, ind;  // [nq + 1] candidates, then hits, per query (a 0 behind them); the candidates'
+                                          // exclusive scan (their segments); the hits' (the result's indptr)
+    DevArray<int> fill;            // [nq] rows the emit pass wrote, or would have written, per query
+    DevArray<u64> keys, sorted;    // [candidates] D-R3's keys, then the result (see idx()); D-R2's rows in the first half,
+                                   // then the sorted keys
+    DevArray<int> zlist;           // [zero rows] in index order: the row of a zero query
+    DevArray<u64> flags;           // DR_FLAG_*
+    DevArray<char> tmp;            // rocprim's temporary storage
+    bool valid = false;
+    long long n = 0, nzero = 0;
+    int d = 0, dp = 0;
+    long long held = -1;           // hits of the last radius call, until the next dense-index call (-1: none)
+    long long last_candidates = 0, last_hits = 0;  // fdr_dense_index_info: the last radius call
+    int last_query_blocks = 0, last_segments = 0;
+    int *idx() const { return reinterpret_cast<int *>(keys.ptr()); }
+    float *dist() const { return reinterpret_cast<float *>(idx() + held); }
+    template <class F>
+    auto each(F f) {
+        return f(ehat, half, zero, qhat, qhalf, qzero, theta, count, off, ind, fill, keys, sorted, zlist, flags, tmp);
+    }
+    size_t bytes() {
+        return each([](auto &...a) { return (a.bytes() + ...); });
+    }
+    void release() {
+        each([](auto &...a) { release_all(a...); });
+        valid = false;
+        n = nzero = 0;
+        d = dp = 0;
+        held = -1;
+        last_candidates = last_hits = 0;
+        last_query_blocks = last_segments = 0;
+    }
+};
+
 // fdr_topk_merge (topk_merge.inc): the parts as uploaded, the merged rows before they are copied out, and the record
 // of a refused call.  Grows as needed; freed with the context.
 struct TopkMergeScratch {
@@ -763,6 +808,7 @@ struct fdr_ctx {
     SparseIndex sp;        // sparse k-NN (knn_sparse.inc): kept until fdr_sparse_index_free
     SparseQuerySet spq;    // ... and the query rows of fdr_sparse_index_query, released with it
     SparseRadius spr;      // ... and the radius searches' counts and hits (knn_sparse_radius.inc), released with it
+    DenseIndex di;         // the dense index and its radius searches (knn_dense_radius.inc): kept until fdr_dense_index_free
     TopkMergeScratch tm;   // the merge of the ranks' candidate lists (topk_merge.inc): kept until fdr_destroy
     // timing: when enabled, every launch of kernel kind i gets its own hipEvent pair on the launch
     // stream; fdr_timing_read() sums the elapsed times of all launches since the last read
@@ -1224,7 +1270,7 @@ typedef void (*TileKernel)(const float *, const unsigned char *, int, const floa
                            int, int, u64 *, unsigned *, int, int, int FDR_DBG_PARAM);
 typedef void (*PassKernel)(const _Float16 *, int, const _Float16 *, int, int, SegBounds, int, int, u64 *, unsigned *, int,
                            int, int, OrderArgs FDR_DBG_PARAM);
-typedef void (*RangeKernel)(const _Float16 *, const float *, int, const _Float16 *, int, int, SegBounds, int *, int *);
+typedef void (*RangeKernel)(const _Float16 *, const float *, int, const _Float16 *, int, int, SegBounds, RangeOut);
 static_assert(kShapes[FDR_R128].tps == RANGE_STAGES && kShapes[FDR_R256].tps == RANGE_STAGES &&
               kShapes[FDR_R512].tps == RANGE_STAGES, "the range kernel's ring");
 
@@ -1631,7 +1677,7 @@ int PrefilterCall::range(PrefilterCounts &n) {
         if (rsh.family == FDR_FAM_RANGE_PP)
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(rk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
         hipLaunchKernelGGL(rk, dim3((unsigned)rp.nqb, (unsigned)rp.nseg), dim3(64 * rsh.nw), rlds, st, (const _Float16 *)L.hqc,
-                           (const float *)L.thetac, cq, (const _Float16 *)L.ht, (int)a.nt, (int)a.t_base, rp.segs, L.cnt, L.rcand);
+                           (const float *)L.thetac, cq, (const _Float16 *)L.ht, (int)a.nt, (int)a.t_base, rp.segs, RangeOut{L.cnt, L.rcand});
         HIP_TRY(hipGetLastError());
         tr.range_chunks++;
         tr.range_pp_chunks += rsh.family == FDR_FAM_RANGE_PP;
@@ -2201,6 +2247,7 @@ FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indp
 
 #include "knn_sparse.inc"  // S1 .. S4: exact cosine / Jaccard k-NN on sparse feature rows (fdr_knn_sparse[_metric])
 #include "knn_sparse_radius.inc"  // R1 .. R3: every row within a distance bound (fdr_sparse_index_radius_*)
+#include "knn_dense_radius.inc"  // D-R1 .. D-R3: the same on the projected rows, through the fp16 range pass (fdr_dense_index_*)
 #include "topk_merge.inc"  // T1: the exact merge of the ranks' candidate lists of a target-sharded sparse search
 #include "kmer_search.inc"
 #include "kmer_output_loader.inc"

@@ -48,6 +48,24 @@ static float prefilter_eps(int ib) {
     return FDR_PREFILTER_EPS + 0.5f / (float)((1u << qbits) - 2u) + 1.0e-6f;
 }
 
+// The threshold margin of the dense index's radius search (knn_dense_radius.inc): its fp16 range pass admits
+// d~ <= th, th = r + radius_margin(), and the canonical chain then decides dist <= r.  No key-grid term: nothing is
+// quantised there.  Proof that {d~ <= th} holds every hit: dist <= r and |d~ - dist| <= FDR_PREFILTER_EPS give
+// d~ <= r + FDR_PREFILTER_EPS; the fp32 rounding of the sum r + M (r < 1, so the sum is below 2) is below 1.2e-7,
+// which the 1.0e-6 covers.  th >= 1 is legal: every row is a candidate then, and max_hits decides.
+static float radius_margin() { return FDR_PREFILTER_EPS + 1.0e-6f; }
+
+// The target chunks of that search.  A plan of the fp16 shapes holds at most FDR_MAX_SEG segments of at most
+// 2^FDR_PREFILTER_MAX_IB rows (knn_plan_compute; the k-NN search leaves the prefilter mode above that many targets,
+// knn_prefilter_wanted), so an index of more rows is scanned in chunks of at most that many, each with a plan of its
+// own and its first row as t_base: equal chunks, a multiple of 32 rows each but the last.
+#define FDR_RADIUS_CHUNK_ROWS ((int64_t)FDR_MAX_SEG << FDR_PREFILTER_MAX_IB)
+static int64_t radius_chunks(int64_t n) { return n <= 0 ? 0 : (n + FDR_RADIUS_CHUNK_ROWS - 1) / FDR_RADIUS_CHUNK_ROWS; }
+static int64_t radius_chunk_rows(int64_t n) {  // rows of every chunk but the last
+    const int64_t c = radius_chunks(n);
+    return c == 0 ? 0 : ((n + c - 1) / c + 31) / 32 * 32;
+}
+
 // Candidates kept beyond k.  k + 8 is the base; k + 12 when that costs no registers (the two lanes of a query hold
 // 2 x 16 or 2 x 32 keys: K' = 32 for k = 20, K' = 62 for k = 50) -- at 10 M rows (config 4) the queries that cannot be
 // certified from K' candidates and go through the range pass fall from 165 k to 99 k of 916 k (a rank's k-NN: 0.713 ->
@@ -129,7 +147,9 @@ static constexpr KnnShape kShapes[] = {
     {FDR_FAM_PINGPONG, 512, 1, 8, 2, 8, false, 32, true},   // PP512_U4
     // the range pass: the candidate pass's geometry, RANGE_STAGES one-unit stages (d > 128: compiled for 256 VGPRs; at
     // d <= 256 it takes 148, so the three workgroups per CU of wps = 3 fit); from 4096 plateau queries the ping-pong
-    // skeleton with eight-unit stages
+    // skeleton with eight-unit stages.  The radius search of the dense index (knn_dense_radius.inc) runs the same
+    // entries with its counting and emitting sinks over ALL queries of a call x the plan's segments: R128 / R256 / R512
+    // below 4096 queries, RPP128 / RPP256 / RPP512 from there (range_shape(dp, nq, nq))
     {FDR_FAM_RANGE, 128, 1, 4, 4, 4, false, 0, true},      // R128
     {FDR_FAM_RANGE, 128, 1, 8, 4, 4, false, 0, true},      // R128_W8
     {FDR_FAM_RANGE, 256, 1, 4, 3, 4, false, 0, true},      // R256

@@ -1030,13 +1030,27 @@ __global__ __launch_bounds__(256) void knn_rerank_kernel(
 // A lane's hits wait in its own RANGE_LANE_BUF-entry LDS buffer (behind the ring) and leave with ONE returning atomic per
 // batch: a plateau query collects hundreds of rows, and a wave that waits ~2 us for every single `atomicAdd(cnt + q, 1)`
 // spent most of a short scan doing so (1100 queries at 1 M rows / 8: 387 us).
+// RangeHits is the k-NN search's sink, the default of the two range kernels; the radius search of the dense index
+// runs the same kernels with a counting and an emitting one (knn_dense_radius.inc).  A sink has an Out (what the
+// kernel is given for it), make(lane buffer, out, query, thread), add(row) and finish().
+struct RangeOut {
+    int *cnt;   // per-query hit counters
+    int *cand;  // [nq][RANGE_CAP]
+};
 template <int NT>  // threads per workgroup = the buffer's stride
 struct RangeHits {
+    typedef RangeOut Out;
     int *lbuf;    // [RANGE_LANE_BUF][NT]; this lane's entries are lbuf[i * NT + tid]
     int *cnt;     // per-query hit counters
     int *cand;    // [nq][RANGE_CAP]
     int qg, tid;  // this lane's query and thread number
     int lcount;
+    static __device__ __forceinline__ RangeHits make(int *lbuf, const Out &o, int qg, int tid) {
+        return RangeHits{lbuf, o.cnt, o.cand, qg, tid, 0};
+    }
+    __device__ __forceinline__ void finish() {
+        if (lcount > 0) flush();
+    }
     __device__ __forceinline__ void flush() {
         const int pos = atomicAdd(cnt + qg, lcount);
         for (int i = 0; i < lcount; ++i)
@@ -1047,26 +1061,27 @@ struct RangeHits {
         lbuf[lcount * NT + tid] = row;
         if (++lcount == RANGE_LANE_BUF) flush();
     }
-    // the hits of one finished tile some lane of which is above its floor: acc[r] is the similarity with row
-    // row0 + (r & 3) + 8 * (r >> 2); sfloor is the conservative similarity form of d~ <= th
-    __device__ __forceinline__ void collect(const f32x16 &acc, int row0, float sfloor, float th, int t_end, int t_base) {
+};
+// the hits of one finished tile some lane of which is above its floor: acc[r] is the similarity with row
+// row0 + (r & 3) + 8 * (r >> 2); sfloor is the conservative similarity form of d~ <= th
+template <class Sink>
+__device__ __forceinline__ void range_collect(Sink &sink, const f32x16 &acc, int row0, float sfloor, float th, int t_end,
+                                              int t_base) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            if (acc[r] > sfloor) {
-                float a1 = acc[r];
-                asm volatile("" : "+v"(a1));
-                const int row = row0 + (r & 3) + 8 * (r >> 2);
-                if (dist_from_sim(a1) <= th && row < t_end) add(t_base + row);
-            }
+    for (int r = 0; r < 16; ++r) {
+        if (acc[r] > sfloor) {
+            float a1 = acc[r];
+            asm volatile("" : "+v"(a1));
+            const int row = row0 + (r & 3) + 8 * (r >> 2);
+            if (dist_from_sim(a1) <= th && row < t_end) sink.add(t_base + row);
         }
     }
-};
+}
 
-template <int DP, int NW, int WPS>
+template <int DP, int NW, int WPS, class Sink = RangeHits<64 * NW>>
 __global__ __launch_bounds__(64 * NW, WPS) void knn_range_kernel(
     const _Float16 *__restrict__ Qh, const float *__restrict__ theta, int nq,
-    const _Float16 *__restrict__ Th, int nt, int t_base, SegBounds segs, int *__restrict__ cnt,
-    int *__restrict__ cand) {
+    const _Float16 *__restrict__ Th, int nt, int t_base, SegBounds segs, const typename Sink::Out out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int QW = 32 * NW;
     constexpr int NCH = DP / 128;
@@ -1113,7 +1128,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_range_kernel(
                                              16, 0, 0);
         }
     };
-    RangeHits<64 * NW> hits{reinterpret_cast<int *>(smem + RANGE_STAGES * UNIT_BYTES), cnt, cand, qg, tid, 0};
+    Sink hits = Sink::make(reinterpret_cast<int *>(smem + RANGE_STAGES * UNIT_BYTES), out, qg, tid);
 #pragma unroll
     for (int i = 0; i < RANGE_STAGES - 1; ++i)
         if (i < nunits) issue_stage(i);
@@ -1155,7 +1170,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_range_kernel(
             for (int r = 1; r < 16; ++r) mx = fmaxf(mx, acc[r]);
             if (__any(mx > sfloor)) {
                 const int t = it / NCH;
-                hits.collect(acc, t_begin + 32 * t + 4 * h, sfloor, th, t_end, t_base);
+                range_collect(hits, acc, t_begin + 32 * t + 4 * h, sfloor, th, t_end, t_base);
             }
         }
     };
@@ -1164,7 +1179,25 @@ __global__ __launch_bounds__(64 * NW, WPS) void knn_range_kernel(
             if (it0 + decltype(sc)::value < nunits) unit(sc, it0 + decltype(sc)::value);
         });
     }
-    if (hits.lcount > 0) hits.flush();
+    hits.finish();
+}
+
+// The canonical similarity chain of two rows in the kernels' layout (groups of eight components, [k0 k2 k4 k6 | k1 k3
+// k5 k7]): fp32 fma over ascending components, the bits every dense k-NN route reports.
+__device__ __forceinline__ float canonical_chain(const f32x4 *__restrict__ qp, const f32x4 *__restrict__ tp, int DP) {
+    float c = 0.0f;
+    for (int g = 0; g < DP / 8; ++g) {
+        const f32x4 qe = qp[2 * g], qo = qp[2 * g + 1], te = tp[2 * g], to = tp[2 * g + 1];
+        c = __builtin_fmaf(qe.x, te.x, c);
+        c = __builtin_fmaf(qo.x, to.x, c);
+        c = __builtin_fmaf(qe.y, te.y, c);
+        c = __builtin_fmaf(qo.y, to.y, c);
+        c = __builtin_fmaf(qe.z, te.z, c);
+        c = __builtin_fmaf(qo.z, to.z, c);
+        c = __builtin_fmaf(qe.w, te.w, c);
+        c = __builtin_fmaf(qo.w, to.w, c);
+    }
+    return c;
 }
 
 // exact ranking of a collected range: one wave per query, keys staged in LDS
@@ -1190,18 +1223,7 @@ __global__ __launch_bounds__(256) void knn_rerank_long_kernel(
     for (int m = lane; m < n; m += 64) {
         const int tidx = cand[(size_t)i * RANGE_CAP + m];
         const f32x4 *tp = reinterpret_cast<const f32x4 *>(That + (size_t)(tidx - t_base) * DP);
-        float c = 0.0f;
-        for (int g = 0; g < DP / 8; ++g) {  // canonical chain, ascending components
-            const f32x4 qe = qp[2 * g], qo = qp[2 * g + 1], te = tp[2 * g], to = tp[2 * g + 1];
-            c = __builtin_fmaf(qe.x, te.x, c);
-            c = __builtin_fmaf(qo.x, to.x, c);
-            c = __builtin_fmaf(qe.y, te.y, c);
-            c = __builtin_fmaf(qo.y, to.y, c);
-            c = __builtin_fmaf(qe.z, te.z, c);
-            c = __builtin_fmaf(qo.z, to.z, c);
-            c = __builtin_fmaf(qe.w, te.w, c);
-            c = __builtin_fmaf(qo.w, to.w, c);
-        }
+        const float c = canonical_chain(qp, tp, DP);
         keys[wave][m] = ((u64)__float_as_uint(dist_from_sim(c)) << 32) | (unsigned)tidx;
     }
     u64 prev1 = 0, mine = 0;

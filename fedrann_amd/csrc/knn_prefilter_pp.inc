@@ -366,11 +366,10 @@ __global__ __launch_bounds__(512, 2) void knn_prefilter_pp_kernel(
 // scratch, docs/experiments.md A-21.  This copy clamps an empty segment's descriptor and last row; the candidate pass's
 // work items are the plan's segments, which each hold at least one row.)
 // Grid: x = query block (256 queries), y = target segment.
-template <int DP, int U>
+template <int DP, int U, class Sink = RangeHits<512>>
 __global__ __launch_bounds__(512, 2) void knn_range_pp_kernel(
     const _Float16 *__restrict__ Qh, const float *__restrict__ theta, int nq,
-    const _Float16 *__restrict__ Th, int nt, int t_base, SegBounds segs, int *__restrict__ cnt,
-    int *__restrict__ cand) {
+    const _Float16 *__restrict__ Th, int nt, int t_base, SegBounds segs, const typename Sink::Out out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NW = 8, QW = 32 * NW;
     constexpr int NCH = DP / 128, TPS = U / NCH;
@@ -420,7 +419,7 @@ __global__ __launch_bounds__(512, 2) void knn_range_pp_kernel(
                 (int)vo, (u % NCH) * 256, 0, 0);
         });
     };
-    RangeHits<512> hits{reinterpret_cast<int *>(smem + 2 * STAGE_BYTES), cnt, cand, qg, tid, 0};  // (behind the ring)
+    Sink hits = Sink::make(reinterpret_cast<int *>(smem + 2 * STAGE_BYTES), out, qg, tid);  // (the lane buffers: behind the ring)
     unsigned fa[8];
     fragment_addresses(fa, smem, j, h);
     f32x16 acc[TPS];
@@ -464,7 +463,7 @@ __global__ __launch_bounds__(512, 2) void knn_range_pp_kernel(
             static_for(std::make_integer_sequence<int, TPS>{}, [&](auto t_c) {
                 if (tl == decltype(t_c)::value) cur = acc[decltype(t_c)::value];
             });
-            hits.collect(cur, t_begin + 32 * (it * TPS + tl) + 4 * h, sfloor, th, t_end, t_base);
+            range_collect(hits, cur, t_begin + 32 * (it * TPS + tl) + 4 * h, sfloor, th, t_end, t_base);
         }
     };
     auto next_slot = [&](const int par) __attribute__((always_inline)) {
@@ -503,5 +502,5 @@ __global__ __launch_bounds__(512, 2) void knn_range_pp_kernel(
         }
         if (nstages > 0) score_turn(nstages - 1);
     }
-    if (live && hits.lcount > 0) hits.flush();
+    if (live) hits.finish();
 }

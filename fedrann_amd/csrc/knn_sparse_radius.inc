@@ -149,12 +149,28 @@ __global__ __launch_bounds__(256) void sp_radius_segments_kernel(long long nheav
     seg_hi[i] = off[row + 1];
 }
 
-// R3
+// R3.  COMPACT (the dense index's D-R3, knn_dense_radius.inc; dst_off / src_off [nseg + 1] each) compacts as it
+// splits: output entry i belongs to the segment s with dst_off[s] <= i < dst_off[s + 1] and is the key at
+// src_off[s] + (i - dst_off[s]), the first dst_off[s + 1] - dst_off[s] keys of each source segment.  The sparse
+// search's instantiation, COMPACT = false, reads key i and none of the three.
+template <bool COMPACT>
 __global__ __launch_bounds__(256) void sp_radius_split_kernel(long long total, const u64 *__restrict__ keys,
-                                                              int *__restrict__ idx, float *__restrict__ dist) {
+                                                              int *__restrict__ idx, float *__restrict__ dist,
+                                                              long long nseg, const long long *__restrict__ dst_off,
+                                                              const long long *__restrict__ src_off) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
-    const u64 key = keys[i];
+    long long src = i;
+    if constexpr (COMPACT) {
+        long long lo = 0, hi = nseg;  // the last s in [0, nseg) with dst_off[s] <= i (dst_off[0] = 0 <= i < dst_off[nseg])
+        while (hi - lo > 1) {
+            const long long mid = (lo + hi) >> 1;
+            if (dst_off[mid] <= i) lo = mid;
+            else hi = mid;
+        }
+        src = src_off[lo] + (i - dst_off[lo]);
+    }
+    const u64 key = keys[src];
     idx[i] = (int)(unsigned)key;
     dist[i] = __uint_as_float((unsigned)(key >> 32));
 }
@@ -254,8 +270,9 @@ static int sp_radius_passes(fdr_ctx *ctx, const char *who, const SpQuerySide &qs
     HIP_TRY(hipGetLastError());
     // R3 (the unsorted keys are dead: the result takes their place)
     int *d_idx = reinterpret_cast<int *>(sr.keys.ptr());
-    hipLaunchKernelGGL(sp_radius_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (long long)total,
-                       sr.sorted.ptr(), d_idx, reinterpret_cast<float *>(d_idx + total));
+    hipLaunchKernelGGL(sp_radius_split_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (long long)total,
+                       sr.sorted.ptr(), d_idx, reinterpret_cast<float *>(d_idx + total), 0ll, (const long long *)nullptr,
+                       (const long long *)nullptr);
     HIP_TRY(hipGetLastError());
     u64 f[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(f, sr.flags.ptr(), 16, hipMemcpyDeviceToHost, st));

@@ -272,6 +272,70 @@ int fdr_sparse_index_info(fdr_ctx *ctx, int32_t *metric, int64_t *n, int64_t *po
 /* Drops the index and frees that memory (fdr_destroy does too).  Without an index: FDR_OK. */
 int fdr_sparse_index_free(fdr_ctx *ctx);
 
+/* ---- radius search on the projected rows: a dense index held by the context  (the default, embedded path: the same
+ *      "which reads are within distance r of this one" as fdr_sparse_index_radius_search, on the rows fdr_embed makes
+ *      and fdr_knn searches) -------------------------------------------------------------------------------------------
+ * The context holds ONE dense index, beside the sparse one and independent of it.  fdr_dense_index_build takes host
+ * rows E float32 [n, d], not normalised (fdr_knn's argument); fdr_dense_index_embed takes fdr_embed's arguments and
+ * keeps E in HBM (a projection must be loaded: FDR_E_STATE otherwise).  Either keeps, on the device, the normalised
+ * rows in the kernels' layout (fdr_normalize_dev's output, fdr_padded_dim(d) floats per row), the fp16 copy of them
+ * that the fp16 passes read, and the zero-row flags.  1 <= n < 2^31; 1 <= d <= 512, the reach of the fp16 passes: a
+ * larger d is FDR_E_ARG (there is no vector-ALU or CPU fallback).  A build or embed replaces the index; one that is
+ * refused or fails leaves NO index.  No other call on the context touches the index (fdr_knn, fdr_embed_knn, the _dev
+ * calls, the sparse and k-mer calls), and the dense-index calls touch neither the sparse index nor fdr_last_knn_trace.
+ * Host pointers; the calls synchronise; one GPU.
+ * Result contract: that of fdr_sparse_index_radius_search with the canonical dense cosine distance (DESIGN.md section
+ * 4) as the metric.  Row i holds every index row t with dist(q_i, t) <= r, the comparison made on the float32 that
+ * fdr_knn reports for that pair, ordered by (distance bits, index).  So:
+ *   - radius domain: 0 <= r < 1.  NaN, a negative r and r >= 1 are FDR_E_ARG;
+ *   - a pair at exactly 1.0f is never a hit (a similarity <= 0; a non-zero query against a zero row);
+ *   - own rows (_radius_search of the rows [q_lo, q_hi)): self is a hit at its distance; outside rows (_radius_query,
+ *     Q float32 [nq, d] on the host, d the index's): there is no self;
+ *   - a zero query: all zero rows of the index, in index order, at distance 0; none against an index without them.  A
+ *     non-zero query never hits a zero row;
+ *   - prefix property: for any k, the entries of fdr_knn(E, k) with distance <= r are exactly the first min(k, count)
+ *     entries of the radius row;
+ *   - Q is normalised by the same device function as the index rows, so the rows [lo, hi) of E passed to _radius_query
+ *     give _radius_search(lo, hi) bit for bit;
+ *   - q_lo == q_hi or nq == 0 is FDR_OK with indptr_out[0] = 0; 0 <= q_lo <= q_hi <= n, 0 <= nq < 2^31.
+ * How: an fp16 MFMA range pass over all queries of the call x all rows finds, per query, every row whose approximate
+ * distance is within r + 0.001051 (a proven superset of the hits: DESIGN.md section 5), first counting, then emitting;
+ * the canonical fp32 chain then decides each candidate.  ONE difference from the sparse call follows: the call must
+ * hold the fp16 CANDIDATES before it knows the exact hits, so max_hits (1 <= max_hits < 2^31, FDR_E_ARG otherwise)
+ * caps the CANDIDATE total of the call.  A candidate total above max_hits is FDR_E_ARG, and this is the one refusal
+ * that has written its output: indptr_out (int64 [queries + 1]) then holds the prefix sums of the per-query candidate
+ * counts, which are UPPER BOUNDS of the hit counts (the message says so), and the caller cuts its row block by them.
+ * Nothing was allocated for the hits then, nothing is held for _fetch, and the index is as it was.  On success
+ * indptr_out is exact: indptr_out[0] = 0, the last entry the total, row i's hits at [indptr_out[i], indptr_out[i + 1]).
+ * Device memory for the hits never exceeds 16 bytes x max_hits (8 of keys and 8 of sort space per candidate; the
+ * result takes the keys' place), plus 32 bytes of counters per query and the segmented sort's temporary storage.
+ * fdr_dense_index_radius_fetch copies the held result out: idx_out int32 [hits] (rows of the index), dist_out float32
+ * [hits]; `hits` must equal the total (FDR_E_ARG otherwise); without a held result FDR_E_STATE; a fetch leaves it
+ * held, and the next dense-index call (a build, an embed, a radius call, a free) drops it.  Without an index the radius
+ * calls are FDR_E_STATE.  A refused or failed radius call leaves the index AS IT WAS.
+ * fdr_dense_index_info (FDR_E_STATE without an index; every out pointer may be NULL): n, d; device_bytes, everything
+ * the dense index holds on the device, the radius calls' buffers included (buffers only grow: after a larger index
+ * or call the figure is the larger one's); of the last radius call its candidates, its hits (candidates >= hits), the
+ * query blocks and the target segments of its range pass (0 where it ran none).  fdr_dense_index_free drops the index
+ * and frees that memory (fdr_destroy does too); without an index FDR_OK.
+ * Limits of the implementation: an index of more than 50 331 648 rows (96 segments of 2^19 rows, what one plan of the
+ * fp16 passes holds) is scanned in target chunks of at most that many rows, one launch each; the result is the same.
+ * Cost: two fp16 scans of queries x rows plus a tail proportional to the candidates.  The model is about twice the
+ * candidate pass of a k-NN search of the same rows; measured, the two scans cost 1.4-2.3 such passes at 100 k rows
+ * and 5.1-5.8 at 1 M rows, where the k-NN pass searches unique rows only, skips empty chunks and runs in synchronised
+ * rounds and this scan does none of that; DESIGN.md section 5.  Not here: duplicate-row classes, live-chunk skipping,
+ * several devices, d > 512. */
+int fdr_dense_index_build(fdr_ctx *ctx, const float *E, int64_t n, int32_t d);
+int fdr_dense_index_embed(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indptr, const int32_t *a_indices);
+int fdr_dense_index_radius_search(fdr_ctx *ctx, float radius, int64_t q_lo, int64_t q_hi, int64_t max_hits,
+                                  int64_t *indptr_out);
+int fdr_dense_index_radius_query(fdr_ctx *ctx, float radius, int64_t nq, const float *Q, int64_t max_hits,
+                                 int64_t *indptr_out);
+int fdr_dense_index_radius_fetch(fdr_ctx *ctx, int64_t hits, int32_t *idx_out, float *dist_out);
+int fdr_dense_index_info(fdr_ctx *ctx, int64_t *n, int32_t *d, size_t *device_bytes, int64_t *last_candidates,
+                         int64_t *last_hits, int32_t *last_query_blocks, int32_t *last_segments);
+int fdr_dense_index_free(fdr_ctx *ctx);
+
 /* ---- merge the candidate lists of a target-sharded sparse search  (fedrann_amd.distributed.sparse_knn_sharded: every
  *      rank indexes its own rows, answers every query among them, and the owner of a query block merges the ranks'
  *      lists) -----------------------------------------------------------------------------------------------------------
