@@ -201,32 +201,21 @@ RADIUS_MAX_HITS = 1 << 26    # ... and the cap on the hits of one device call (8
                              # --radius: on its fp16 candidates, 16 bytes each)
 
 
-def check_radius(args):
-    """--no-projection-radius against the other options, before any work."""
-    r = args.no_projection_radius
+def check_radius(args, flag, r, needs_no_projection):
+    """A radius option (`flag`, its value r; None: not given) against the other options, before any work:
+    --no-projection-radius needs --no-projection, --radius refuses it and is bound to the fp16 passes' dimensions."""
     if r is None:
         return
-    if not args.no_projection:
+    if needs_no_projection and not args.no_projection:
         raise SystemExit("--no-projection-radius needs --no-projection (the projected search has no radius form)")
-    if not 0.0 <= np.float32(r) < 1.0:  # (NaN fails both)
-        raise SystemExit("--no-projection-radius must be in [0, 1), got %r (every read is within 1 of every other)" % r)
-    if len(device_list(args.devices)) > 1:
-        raise SystemExit("--no-projection-radius runs on one GPU: the radius search is not sharded over --devices")
-
-
-def check_dense_radius_args(args):
-    """--radius against the other options, before any work."""
-    from . import _lib
-    r = args.radius
-    if r is None:
-        return
-    if args.no_projection:
+    if not needs_no_projection and args.no_projection:
         raise SystemExit("--radius is the projected search's; with --no-projection use --no-projection-radius")
     if not 0.0 <= np.float32(r) < 1.0:  # (NaN fails both)
-        raise SystemExit("--radius must be in [0, 1), got %r (every read is within 1 of every other)" % r)
+        raise SystemExit("%s must be in [0, 1), got %r (every read is within 1 of every other)" % (flag, r))
     if len(device_list(args.devices)) > 1:
-        raise SystemExit("--radius runs on one GPU: the radius search is not sharded over --devices")
-    if args.embedding_dimension > _lib.FDR_FAST_MAX_DIM:
+        raise SystemExit("%s runs on one GPU: the radius search is not sharded over --devices" % flag)
+    from . import _lib
+    if not needs_no_projection and args.embedding_dimension > _lib.FDR_FAST_MAX_DIM:
         raise SystemExit("--radius needs -n/--embedding-dimension <= %d, the reach of the fp16 passes (got %d)"
                          % (_lib.FDR_FAST_MAX_DIM, args.embedding_dimension))
 
@@ -748,8 +737,8 @@ def main(argv=None):
                  # (... nor --nndescent-n-neighbors by a radius search)
                  1 if args.no_projection_radius is not None or args.radius is not None else args.nndescent_n_neighbors)
     # (before any work: the library would only refuse them after stages 1-3)
-    check_radius(args)
-    check_dense_radius_args(args)
+    check_radius(args, "--no-projection-radius", args.no_projection_radius, True)
+    check_radius(args, "--radius", args.radius, False)
     check_sparse_shard(args)
     if args.no_projection_metric != "cosine" and not args.no_projection:
         raise SystemExit("--no-projection-metric %s needs --no-projection (the projected search is cosine only)"

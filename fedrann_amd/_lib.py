@@ -387,18 +387,31 @@ def overlaps_write_csr(path, indptr, idx, dist, name_off, names, strands, row0=0
     return int(lines.value)
 
 
-def check_sparse_radius(radius, max_hits=1 << 26):
-    """The argument checks of SparseIndex.radius_search / radius_query that need no GPU: 0 <= radius < 1 (a real number,
-    no NaN) and 1 <= max_hits < 2^31.  Returns (radius as float32, max_hits)."""
+def _check_radius_cap(radius, max_hits, ranks):
+    """What both radius checks ask of (radius, max_hits); `ranks` names the k-NN call that ranks every row instead.
+    Returns (radius as float32, max_hits)."""
     if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
         raise ValueError("radius must be a number, got %r" % (radius,))
     r = np.float32(radius)
     if not (r >= 0 and r < 1):
-        raise ValueError("need 0 <= radius < 1, got %r (every row is within 1 of every query: search(k) ranks them)"
-                         % (radius,))
+        raise ValueError("need 0 <= radius < 1, got %r (every row is within 1 of every query: %s ranks them)"
+                         % (radius, ranks))
     if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not 1 <= int(max_hits) < 2 ** 31:
         raise ValueError("max_hits must be an integer in [1, 2^31), got %r" % (max_hits,))
     return r, int(max_hits)
+
+
+def _check_block_rows(block_rows):
+    """block_rows of query() / radius_query(): None (one block) or an integer >= 1."""
+    if block_rows is not None and (isinstance(block_rows, bool) or not isinstance(block_rows, (int, np.integer))
+                                   or int(block_rows) < 1):
+        raise ValueError("block_rows must be an integer >= 1, got %r" % (block_rows,))
+
+
+def check_sparse_radius(radius, max_hits=1 << 26):
+    """The argument checks of SparseIndex.radius_search / radius_query that need no GPU: 0 <= radius < 1 (a real number,
+    no NaN) and 1 <= max_hits < 2^31.  Returns (radius as float32, max_hits)."""
+    return _check_radius_cap(radius, max_hits, "search(k)")
 
 
 def check_dense_radius(n, d, radius, lo=0, hi=None, max_hits=1 << 26):
@@ -414,18 +427,11 @@ def check_dense_radius(n, d, radius, lo=0, hi=None, max_hits=1 << 26):
     if not 1 <= d <= FDR_FAST_MAX_DIM:
         raise ValueError("the dense index needs 1 <= d <= %d (the reach of the fp16 passes), got %d"
                          % (FDR_FAST_MAX_DIM, d))
-    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
-        raise ValueError("radius must be a number, got %r" % (radius,))
-    r = np.float32(radius)
-    if not (r >= 0 and r < 1):
-        raise ValueError("need 0 <= radius < 1, got %r (every row is within 1 of every query: knn(E, k) ranks them)"
-                         % (radius,))
+    r, max_hits = _check_radius_cap(radius, max_hits, "knn(E, k)")
     lo, hi = int(lo), int(n if hi is None else hi)
     if not 0 <= lo <= hi <= n:
         raise ValueError("need 0 <= lo <= hi <= n = %d, got [%d, %d)" % (n, lo, hi))
-    if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not 1 <= int(max_hits) < 2 ** 31:
-        raise ValueError("max_hits must be an integer in [1, 2^31), got %r" % (max_hits,))
-    return r, lo, hi, int(max_hits)
+    return r, lo, hi, max_hits
 
 
 def radius_pieces(counts, max_hits):
@@ -1081,6 +1087,20 @@ class _HeldIndex:
         return (out_ip, np.concatenate([p[1] for p in parts]) if parts else np.empty(0, np.int32),
                 np.concatenate([p[2] for p in parts]) if parts else np.empty(0, np.float32))
 
+    def _radius_blocks(self, what, piece, nq, block_rows, max_hits):
+        """Query rows [0, nq) in consecutive blocks of at most block_rows rows (None: one block), each through
+        _radius_rows with piece(a, b) -> the raw call of the query rows [a, b); the blocks' results concatenated."""
+        step = max(nq, 1) if block_rows is None else int(block_rows)
+        outs = []
+        for a0 in range(0, max(nq, 1), step):  # (nq = 0: one call, which records the trace)
+            b0 = min(nq, a0 + step)
+            outs.append(self._radius_rows(what, lambda a, b, a0=a0: piece(a0 + a, a0 + b), b0 - a0, max_hits, a0))
+        if len(outs) == 1:
+            return outs[0]
+        out_ip = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum(np.concatenate([np.diff(o[0]) for o in outs]), out=out_ip[1:])
+        return out_ip, np.concatenate([o[1] for o in outs]), np.concatenate([o[2] for o in outs])
+
 
 class SparseIndex(_HeldIndex):
     """The sparse index of a Context (Context.sparse_index): search row ranges of it, at any k, any number of times.
@@ -1126,9 +1146,7 @@ class SparseIndex(_HeldIndex):
         if self.n_features is None:
             raise ValueError("SparseIndex.query needs the index's n_features")
         nq, k = check_sparse_queries(self.n, self.n_features, self.metric, indptr, indices, values, k)
-        if block_rows is not None and (isinstance(block_rows, bool) or not isinstance(block_rows, (int, np.integer))
-                                       or int(block_rows) < 1):
-            raise ValueError("block_rows must be an integer >= 1, got %r" % (block_rows,))
+        _check_block_rows(block_rows)
         if out is None:
             idx = np.empty((nq, k), dtype=np.int32)
             dist = np.empty((nq, k), dtype=np.float32)
@@ -1181,34 +1199,21 @@ class SparseIndex(_HeldIndex):
         if self.n_features is None:
             raise ValueError("SparseIndex.radius_query needs the index's n_features")
         nq = check_sparse_queries(self.n, self.n_features, self.metric, indptr, indices, values, 1)[0]
-        if block_rows is not None and (isinstance(block_rows, bool) or not isinstance(block_rows, (int, np.integer))
-                                       or int(block_rows) < 1):
-            raise ValueError("block_rows must be an integer >= 1, got %r" % (block_rows,))
+        _check_block_rows(block_rows)
         r, max_hits = check_sparse_radius(radius, max_hits)
         self._live("SparseIndex.radius_query")
         c = self._ctx
-        step = max(nq, 1) if block_rows is None else int(block_rows)
-        outs = []
-        for a0 in range(0, max(nq, 1), step):  # (nq = 0: one call, which records the trace)
-            b0 = min(nq, a0 + step)
 
-            def piece(a, b, a0=a0):
-                a, b = a0 + a, a0 + b
-                if a == 0 and b == nq:
-                    ip, ix, vals = indptr, indices, values
-                else:
-                    ip = np.ascontiguousarray(indptr[a:b + 1] - indptr[a])
-                    ix = indices[indptr[a]:indptr[b]]
-                    vals = None if values is None else values[indptr[a]:indptr[b]]
-                return lambda cap, out: c._L.fdr_sparse_index_radius_query(c._h, r, b - a, _ptr(ip), _ptr(ix),
-                                                                           _ptr(vals), cap, _ptr(out))
-            outs.append(self._radius_rows("fdr_sparse_index_radius_query", piece, b0 - a0, max_hits, a0))
-        if len(outs) == 1:
-            return outs[0]
-        lens = np.concatenate([np.diff(o[0]) for o in outs])
-        out_ip = np.zeros(nq + 1, dtype=np.int64)
-        np.cumsum(lens, out=out_ip[1:])
-        return out_ip, np.concatenate([o[1] for o in outs]), np.concatenate([o[2] for o in outs])
+        def piece(a, b):
+            if a == 0 and b == nq:
+                ip, ix, vals = indptr, indices, values
+            else:
+                ip = np.ascontiguousarray(indptr[a:b + 1] - indptr[a])
+                ix = indices[indptr[a]:indptr[b]]
+                vals = None if values is None else values[indptr[a]:indptr[b]]
+            return lambda cap, out: c._L.fdr_sparse_index_radius_query(c._h, r, b - a, _ptr(ip), _ptr(ix), _ptr(vals),
+                                                                       cap, _ptr(out))
+        return self._radius_blocks("fdr_sparse_index_radius_query", piece, nq, block_rows, max_hits)
 
     def info(self):
         """dict of fdr_sparse_index_info: metric, n, postings (stored entries kept), zero_rows (zero rows; Jaccard:
@@ -1274,27 +1279,16 @@ class DenseIndex(_HeldIndex):
         if Q.ndim != 2 or Q.shape[1] != self.d:
             raise ValueError("Q must be [nq, %d], got shape %r" % (self.d, Q.shape))
         nq = Q.shape[0]
-        if block_rows is not None and (isinstance(block_rows, bool) or not isinstance(block_rows, (int, np.integer))
-                                       or int(block_rows) < 1):
-            raise ValueError("block_rows must be an integer >= 1, got %r" % (block_rows,))
+        _check_block_rows(block_rows)
         r, _, _, max_hits = check_dense_radius(self.n, self.d, radius, 0, None, max_hits)
         self._live("DenseIndex.radius_query")
         c = self._ctx
-        step = max(nq, 1) if block_rows is None else int(block_rows)
-        outs = []
-        for a0 in range(0, max(nq, 1), step):
-            b0 = min(nq, a0 + step)
 
-            def piece(a, b, a0=a0):
-                rows = Q[a0 + a:a0 + b]  # (a row block of a C-contiguous array is C-contiguous)
-                return lambda cap, out: c._L.fdr_dense_index_radius_query(c._h, r, b - a, _ptr(rows) if b > a else None,
-                                                                          cap, _ptr(out))
-            outs.append(self._radius_rows("fdr_dense_index_radius_query", piece, b0 - a0, max_hits, a0))
-        if len(outs) == 1:
-            return outs[0]
-        out_ip = np.zeros(nq + 1, dtype=np.int64)
-        np.cumsum(np.concatenate([np.diff(o[0]) for o in outs]), out=out_ip[1:])
-        return out_ip, np.concatenate([o[1] for o in outs]), np.concatenate([o[2] for o in outs])
+        def piece(a, b):
+            rows = Q[a:b]  # (a row block of a C-contiguous array is C-contiguous)
+            return lambda cap, out: c._L.fdr_dense_index_radius_query(c._h, r, b - a, _ptr(rows) if b > a else None,
+                                                                      cap, _ptr(out))
+        return self._radius_blocks("fdr_dense_index_radius_query", piece, nq, block_rows, max_hits)
 
     def info(self):
         """dict of fdr_dense_index_info: n, d, device_bytes (what the dense index holds on the device, the radius

@@ -701,30 +701,47 @@ struct SparseQuerySet {
     }
 };
 
-// The radius searches of the sparse index (knn_sparse_radius.inc): the per-query counts and their scan, the hits as
-// keys (dist_bits << 32 | row) and the held result of the last call, which fdr_sparse_index_radius_fetch copies out.
-// Grows as needed; released with the index.
-struct SparseRadius {
-    DevArray<long long> count, off;  // [nq + 1] the queries' hit counts (a 0 behind them); their exclusive scan
-    DevArray<u64> keys, sorted;      // [total] the heavy queries' hits as found, then the result (see idx());
-                                     // every query's hits in (distance bits, index) order
-    DevArray<long long> seg_lo, seg_hi;  // [heavy queries] their segments of the keys, for the segmented sort
+// What a radius search counts, emits and holds (knn_radius_common.inc: the protocol; each index owns one): the
+// per-query counts and their scan, the counted entries as keys (dist_bits << 32 | row) and the held result of the last
+// call, which the owner's *_radius_fetch copies out.  Grows as needed; released with its owner.
+#define RR_FLAG_MISMATCH 0  // queries whose emitted count differs from the counted one (or that hold a row out of range)
+#define RR_FLAG_ZLIST 1     // the zero rows that zlist took
+#define RR_FLAG_ZEROQ 2     // the dense search's: zero rows among the call's queries ...
+#define RR_FLAG_NZERO 3     // ... and the index's zero rows (a build's count)
+#define RR_FLAGS 4
+struct RadiusResult {
+    DevArray<long long> count, off;  // [nq + 1] the queries' counts (a 0 behind them); their exclusive scan
+    DevArray<u64> keys, sorted;      // [counted] the keys as the emit pass leaves them, then the result (see idx());
+                                     // every query's keys in (distance bits, index) order
     DevArray<int> zlist;             // [zero rows of the index] in index order: the row of a zero query
-    DevArray<unsigned char> handed;  // [nq] queries the count pass handed to its range form: the emit pass skips them
-    DevArray<u64> flags;             // [0] queries whose emitted count differs from the counted one; [1] zlist's length
-    long long held = -1;             // hits of the last radius call, until the next sparse call (-1: none)
-    // The heavy queries' unsorted keys are dead once the segmented sort has read them: their 8 bytes per hit take
-    // the result, `held` indices (int32) and behind them `held` distances.
+    DevArray<u64> flags;             // RR_FLAG_*
+    long long counted = 0;           // the total of the last call's counts: the entries of keys and sorted
+    long long held = -1;             // hits of the last radius call, until the owner's next call (-1: none)
+    // The unsorted keys are dead once the sort has read them: their 8 bytes per entry take the result, `held`
+    // indices (int32) and behind them `held` distances (held <= counted).
     int *idx() const { return reinterpret_cast<int *>(keys.ptr()); }
     float *dist() const { return reinterpret_cast<float *>(idx() + held); }
     void drop() { held = -1; }
-    size_t bytes() const {
-        return count.bytes() + off.bytes() + keys.bytes() + sorted.bytes() + seg_lo.bytes() + seg_hi.bytes() +
-               zlist.bytes() + handed.bytes() + flags.bytes();
-    }
+    template <class F>
+    auto each(F f) { return f(count, off, keys, sorted, zlist, flags); }
+    size_t bytes() { return each([](auto &...a) { return (a.bytes() + ...); }); }
     void release() {
-        release_all(count, off, keys, sorted, seg_lo, seg_hi, zlist, handed, flags);
+        each([](auto &...a) { release_all(a...); });
+        counted = 0;
         held = -1;
+    }
+};
+
+// The radius searches of the sparse index (knn_sparse_radius.inc): what they hold beside their RadiusResult, in which
+// `keys` takes the heavy queries' hits as found.  Released with the index.
+struct SparseRadius {
+    RadiusResult rr;
+    DevArray<long long> seg_lo, seg_hi;  // [heavy queries] their segments of the keys, for the segmented sort
+    DevArray<unsigned char> handed;  // [nq] queries the count pass handed to its range form: the emit pass skips them
+    size_t bytes() { return rr.bytes() + seg_lo.bytes() + seg_hi.bytes() + handed.bytes(); }
+    void release() {
+        rr.release();
+        release_all(seg_lo, seg_hi, handed);
     }
 };
 
@@ -739,35 +756,27 @@ struct DenseIndex {
     DevArray<_Float16> qhalf;
     DevArray<unsigned char> qzero;
     DevArray<float> theta;         // [nq] the queries' thresholds (a zero query: -inf)
-    DevArray<long long> count, off, ind;  // [nq + 1] candidates, then hits, per query (a 0 behind them); the candidates'
-                                          // exclusive scan (their segments); the hits' (the result's indptr)
+    RadiusResult rr;               // count: the candidates, then the hits, per query; off: the candidates' segments;
+                                   // keys: D-R3's; sorted: D-R2's rows in the first half, then the sorted keys
+    DevArray<long long> ind;       // [nq + 1] the hits' exclusive scan (the result's indptr)
     DevArray<int> fill;            // [nq] rows the emit pass wrote, or would have written, per query
-    DevArray<u64> keys, sorted;    // [candidates] D-R3's keys, then the result (see idx()); D-R2's rows in the first half,
-                                   // then the sorted keys
-    DevArray<int> zlist;           // [zero rows] in index order: the row of a zero query
-    DevArray<u64> flags;           // DR_FLAG_*
     DevArray<char> tmp;            // rocprim's temporary storage
     bool valid = false;
     long long n = 0, nzero = 0;
     int d = 0, dp = 0;
-    long long held = -1;           // hits of the last radius call, until the next dense-index call (-1: none)
     long long last_candidates = 0, last_hits = 0;  // fdr_dense_index_info: the last radius call
     int last_query_blocks = 0, last_segments = 0;
-    int *idx() const { return reinterpret_cast<int *>(keys.ptr()); }
-    float *dist() const { return reinterpret_cast<float *>(idx() + held); }
     template <class F>
     auto each(F f) {
-        return f(ehat, half, zero, qhat, qhalf, qzero, theta, count, off, ind, fill, keys, sorted, zlist, flags, tmp);
+        return f(ehat, half, zero, qhat, qhalf, qzero, theta, ind, fill, tmp);
     }
-    size_t bytes() {
-        return each([](auto &...a) { return (a.bytes() + ...); });
-    }
+    size_t bytes() { return rr.bytes() + each([](auto &...a) { return (a.bytes() + ...); }); }
     void release() {
         each([](auto &...a) { release_all(a...); });
+        rr.release();
         valid = false;
         n = nzero = 0;
         d = dp = 0;
-        held = -1;
         last_candidates = last_hits = 0;
         last_query_blocks = last_segments = 0;
     }
@@ -2246,6 +2255,7 @@ FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indp
 }
 
 #include "knn_sparse.inc"  // S1 .. S4: exact cosine / Jaccard k-NN on sparse feature rows (fdr_knn_sparse[_metric])
+#include "knn_radius_common.inc"  // the count / scan / emit / hold protocol of both radius searches, on a RadiusResult
 #include "knn_sparse_radius.inc"  // R1 .. R3: every row within a distance bound (fdr_sparse_index_radius_*)
 #include "knn_dense_radius.inc"  // D-R1 .. D-R3: the same on the projected rows, through the fp16 range pass (fdr_dense_index_*)
 #include "topk_merge.inc"  // T1: the exact merge of the ranks' candidate lists of a target-sharded sparse search

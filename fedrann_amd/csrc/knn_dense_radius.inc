@@ -6,22 +6,19 @@
 // The index (DenseIndex, fedrann_hip.hip) holds the normalised rows (fdr_normalize_dev's layout), their fp16 copy and
 // the zero-row flags.  The fp16 range pass (knn_range_kernel / knn_range_pp_kernel, the shape range_shape() picks for
 // the call's queries) finds, per query, every target with approximate distance d~ <= th, th = r + radius_margin()
-// (knn_plan.inc: a superset of the rows with canonical distance <= r), and the canonical fp32 chain decides.
+// (knn_plan.inc: a superset of the rows with canonical distance <= r), and the canonical fp32 chain decides.  The
+// protocol around the passes (the scan, the cap, the zero rows' list, the cross-check, the held result) is
+// knn_radius_common.inc's; what it counts and caps here are the CANDIDATES, upper bounds of the hit counts.
 //   D-R1  the range pass with the RangeCount sink: each lane counts its query's candidates in a register and adds
 //         them to count[q] with one atomic at the end.  A zero query takes no part (its threshold is -inf): its count
 //         is the index's zero rows.
-//   (rocprim exclusive scan of the counts, int64: the candidate segments, copied to the host BEFORE anything is
-//    allocated for them; the candidate total against max_hits is checked there)
 //   D-R2  the same pass with the RangeEmit sink: a lane's candidates wait in its LDS buffer, as RangeHits' do, and
-//         leave with one returning atomic per batch into the query's segment; every write is bounded by the segment
-//         D-R1 counted, and a query whose emitted count differs from the counted one is counted in flags[0] (the call
-//         then fails, FDR_E_HIP "internal: ...": both passes run the same arithmetic, so it stays 0).
+//         leave with one returning atomic per batch into the query's segment, bounded by what D-R1 counted.
 //   D-R3  dr_exact_kernel, one wave per query: the canonical chain (canonical_chain, knn_rerank_long_kernel's own)
-//         over the segment, key = dist_bits << 32 | row where dist <= r, else KEY_INF; the hits are counted.  A zero
-//         query's keys are the index's zero rows at distance bits 0 (rocprim::select builds their list once per call,
-//         and only for a call with a zero query).  Then the scan of the hit counts (the exact indptr), ONE rocprim
-//         segmented radix sort over the candidate segments (the misses sort to each segment's tail) and
-//         sp_radius_split_kernel<true>, its compacting form: the first count[q] keys of each segment -> idx / dist.
+//         over the segment, key = dist_bits << 32 | row where dist <= r, else KEY_INF; the hits are counted.  Then
+//         the scan of the hit counts (the exact indptr), ONE rocprim segmented radix sort over the candidate segments
+//         (the misses sort to each segment's tail) and radius_split_kernel<true>, the compacting form: the first
+//         count[q] keys of each segment -> idx / dist.
 // Memory: 16 bytes per candidate (8 of keys, which take the result afterwards; 8 of sorted keys, whose first half
 // holds D-R2's rows before the sort), 32 bytes per query of the largest call, 4 per zero row.
 // Cost model: two fp16 scans of queries x targets at the staging rate plus a tail proportional to the candidates
@@ -29,11 +26,6 @@
 // An index of more than 96 << 19 rows, what one plan of the fp16 shapes holds, is scanned in target chunks (dr_scan).
 // Out of scope: duplicate-row classes, live-chunk skipping, several devices, d > 512.
 // ------------------------------------------------------------------------------------------
-#define DR_FLAG_MISMATCH 0  // queries whose emitted count differs from the counted one (or that hold a row out of range)
-#define DR_FLAG_ZLIST 1     // the zero rows rocprim::select found
-#define DR_FLAG_ZEROQ 2     // zero rows among the call's queries
-#define DR_FLAG_NZERO 3     // the index's zero rows (a build's count)
-#define DR_FLAGS 4
 
 // ---- the sinks of the range kernels (RangeHits, knn_prefilter.inc, is the k-NN search's) ----------------------------
 struct RangeCountOut {
@@ -118,14 +110,7 @@ __global__ __launch_bounds__(256) void dr_prepare_kernel(long long nq, const uns
         if (z) count[i] = nzero;
     }
     const u64 m = __ballot(z);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&flags[DR_FLAG_ZEROQ], (u64)__popcll(m));
-}
-
-__global__ __launch_bounds__(256) void dr_count_zero_kernel(long long n, const unsigned char *__restrict__ zero,
-                                                            u64 *__restrict__ flags) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    const u64 m = __ballot(i < n && zero[i] != 0);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&flags[DR_FLAG_NZERO], (u64)__popcll(m));
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&flags[RR_FLAG_ZEROQ], (u64)__popcll(m));
 }
 
 // D-R3: one wave per query.  rows / keys [off[nq]]: the query's segment is [off[q], off[q + 1]); fill [nq]: what D-R2
@@ -141,11 +126,11 @@ __global__ __launch_bounds__(256) void dr_exact_kernel(long long nq, long long n
     const long long q = (long long)blockIdx.x * 4 + wave;
     if (q >= nq) return;
     const long long seg0 = off[q], seg = off[q + 1] - seg0;
-    if (qzero[q]) {  // every zero row of the index, at distance 0
+    if (qzero[q]) {  // every zero row of the index, at distance 0 (radius_emit_zero, written out: see there)
         for (long long m = lane; m < min(seg, nzero); m += 64) keys[seg0 + m] = (u64)(unsigned)zlist[m];
         if (lane == 0) {
             count[q] = min(seg, nzero);
-            if (seg != nzero) atomicAdd(&flags[DR_FLAG_MISMATCH], 1ull);
+            if (seg != nzero) atomicAdd(&flags[RR_FLAG_MISMATCH], 1ull);
         }
         return;
     }
@@ -175,7 +160,7 @@ __global__ __launch_bounds__(256) void dr_exact_kernel(long long nq, long long n
     const bool anybad = __any(bad);
     if (lane == 0) {
         count[q] = hits;
-        if (anybad) atomicAdd(&flags[DR_FLAG_MISMATCH], 1ull);
+        if (anybad) atomicAdd(&flags[RR_FLAG_MISMATCH], 1ull);
     }
 }
 
@@ -220,96 +205,64 @@ static int dr_radius_passes(fdr_ctx *ctx, const char *who, const float *Qhat, co
     int rc;
     const hipStream_t st = ctx->stream;
     DenseIndex &di = ctx->di;
+    RadiusResult &rr = di.rr;
+    const RadiusCall call = {st, who, nq, max_hits, indptr_out};
     const int64_t n = di.n;
     const long long nzero = di.nzero;
+    di.last_candidates = di.last_hits = 0;
+    if ((rc = radius_reserve(rr, call))) return rc;
     if ((rc = di.theta.reserve((size_t)nq))) return rc;
-    if ((rc = di.count.reserve((size_t)nq + 1))) return rc;
-    if ((rc = di.off.reserve((size_t)nq + 1))) return rc;
     if ((rc = di.ind.reserve((size_t)nq + 1))) return rc;
     if ((rc = di.fill.reserve((size_t)nq))) return rc;
-    if ((rc = di.flags.reserve(DR_FLAGS))) return rc;
-    HIP_TRY(hipMemsetAsync(di.count.ptr(), 0, ((size_t)nq + 1) * 8, st));
     HIP_TRY(hipMemsetAsync(di.fill.ptr(), 0, (size_t)nq * 4, st));
-    HIP_TRY(hipMemsetAsync(di.flags.ptr(), 0, DR_FLAGS * 8, st));
     const float th = radius + radius_margin();
     hipLaunchKernelGGL(dr_prepare_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, (long long)nq, qzero, th,
-                       nzero, di.theta.ptr(), di.count.ptr(), di.flags.ptr());
+                       nzero, di.theta.ptr(), rr.count.ptr(), rr.flags.ptr());
     HIP_TRY(hipGetLastError());
     int shape = range_shape(di.dp, (int)nq, (int)nq);
     if (shape == FDR_R128_W8) shape = FDR_R128;  // (a development knob's eight-wave form: not built with these sinks)
     // D-R1
-    if ((rc = dr_scan<RangeCount>(ctx, Qh, nq, shape, RangeCountOut{reinterpret_cast<unsigned long long *>(di.count.ptr())},
+    if ((rc = dr_scan<RangeCount>(ctx, Qh, nq, shape, RangeCountOut{reinterpret_cast<unsigned long long *>(rr.count.ptr())},
                                   &di.last_query_blocks, &di.last_segments)))
         return rc;
-    auto scan = [&](long long *to) {
-        return [&, to](void *tmp, size_t &bytes) {
-            return rocprim::exclusive_scan(tmp, bytes, di.count.ptr(), to, 0ll, (size_t)nq + 1, rocprim::plus<long long>(), st);
-        };
-    };
-    if ((rc = rocprim_run(di.tmp, "rocprim::exclusive_scan", scan(di.off.ptr())))) return rc;
-    u64 f[DR_FLAGS] = {};
-    HIP_TRY(hipMemcpyAsync(indptr_out, di.off.ptr(), ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(f, di.flags.ptr(), DR_FLAGS * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t total = indptr_out[nq];
-    const u64 zeroq = f[DR_FLAG_ZEROQ];
-    di.last_candidates = total;
-    di.last_hits = 0;
-    if (total > max_hits)  // (the one refusal that has written its output: the caller cuts the block by the counts)
-        return fail(FDR_E_ARG, "%s: %lld candidates exceed max_hits = %lld (indptr_out holds the candidate counts, upper "
-                    "bounds of the hit counts: search fewer rows per call)", who, (long long)total, (long long)max_hits);
-    if (total == 0) {  // (no candidate, no hit: the counts are exact)
-        di.held = 0;
-        return FDR_OK;
-    }
+    u64 f[RR_FLAGS] = {};  // (with the offsets: the zero queries that dr_prepare_kernel counted)
+    rc = radius_offsets(rr, di.tmp, call, "candidates", "candidate counts, upper bounds of the hit counts", f);
+    const long long total = di.last_candidates = rr.counted;
+    if (rc || total == 0) return rc;  // (no candidate, no hit: the counts are exact)
     // D-R2 (the rows wait in the first half of `sorted`, which the sort overwrites once D-R3 has read them)
-    if ((rc = di.keys.reserve((size_t)total))) return rc;
-    if ((rc = di.sorted.reserve((size_t)total))) return rc;
-    int *rows = reinterpret_cast<int *>(di.sorted.ptr());
-    if (zeroq > 0 && nzero > 0) {  // the zero rows' list
-        if ((rc = di.zlist.reserve((size_t)nzero))) return rc;
-        auto select = [&](void *tmp, size_t &bytes) {
-            return rocprim::select(tmp, bytes, rocprim::counting_iterator<int>(0), di.zero.ptr(), di.zlist.ptr(),
-                                   di.flags.ptr() + DR_FLAG_ZLIST, (size_t)n, st);
-        };
-        if ((rc = rocprim_run(di.tmp, "rocprim::select", select))) return rc;
-    }
-    if ((rc = dr_scan<RangeEmit>(ctx, Qh, nq, shape, RangeEmitOut{di.fill.ptr(), di.off.ptr(), rows}, &di.last_query_blocks,
+    int *rows = reinterpret_cast<int *>(rr.sorted.ptr());
+    const bool zeros = f[RR_FLAG_ZEROQ] > 0 && nzero > 0;  // a zero query, and zero rows for it
+    if (zeros && (rc = radius_zero_list(rr, di.tmp, call, di.zero.ptr(), n, nzero))) return rc;
+    if ((rc = dr_scan<RangeEmit>(ctx, Qh, nq, shape, RangeEmitOut{di.fill.ptr(), rr.off.ptr(), rows}, &di.last_query_blocks,
                                  &di.last_segments)))
         return rc;
     // D-R3
     if ((rc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, st))) return rc;
     hipLaunchKernelGGL(dr_exact_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, (long long)nq, (long long)n, di.dp,
-                       Qhat, qzero, (const float *)di.ehat.ptr(), radius, (const long long *)di.off.ptr(), (const int *)rows,
-                       (const int *)di.fill.ptr(), nzero, (const int *)di.zlist.ptr(), di.keys.ptr(), di.count.ptr(),
-                       di.flags.ptr());
+                       Qhat, qzero, (const float *)di.ehat.ptr(), radius, (const long long *)rr.off.ptr(), (const int *)rows,
+                       (const int *)di.fill.ptr(), nzero, (const int *)rr.zlist.ptr(), rr.keys.ptr(), rr.count.ptr(),
+                       rr.flags.ptr());
     HIP_TRY(hipGetLastError());
-    if ((rc = rocprim_run(di.tmp, "rocprim::exclusive_scan", scan(di.ind.ptr())))) return rc;
+    if ((rc = radius_scan(rr, di.tmp, call, di.ind.ptr()))) return rc;
     auto sort = [&](void *tmp, size_t &bytes) {  // (KEY_INF, a miss, lies below 2^63 and above every hit)
-        return rocprim::segmented_radix_sort_keys(tmp, bytes, di.keys.ptr(), di.sorted.ptr(), (unsigned)total, (unsigned)nq,
-                                                  di.off.ptr(), di.off.ptr() + 1, 0, 63, st);
+        return rocprim::segmented_radix_sort_keys(tmp, bytes, rr.keys.ptr(), rr.sorted.ptr(), (unsigned)total, (unsigned)nq,
+                                                  rr.off.ptr(), rr.off.ptr() + 1, 0, 63, st);
     };
     if ((rc = rocprim_run(di.tmp, "rocprim::segmented_radix_sort_keys", sort))) return rc;
     HIP_TRY(hipMemcpyAsync(indptr_out, di.ind.ptr(), ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(f, di.flags.ptr(), DR_FLAGS * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (f[DR_FLAG_MISMATCH] != 0 || (zeroq > 0 && nzero > 0 && f[DR_FLAG_ZLIST] != (u64)nzero))
-        return fail(FDR_E_HIP, "internal: %s: the emit pass disagrees with the count pass on %llu queries (zero rows "
-                    "listed: %llu of %lld)", who, (unsigned long long)f[DR_FLAG_MISMATCH],
-                    (unsigned long long)f[DR_FLAG_ZLIST], nzero);
+    if ((rc = radius_check(rr, call, zeros, nzero))) return rc;
     const int64_t hits = indptr_out[nq];
-    if (hits < 0 || hits > total) return fail(FDR_E_HIP, "internal: %s: %lld hits of %lld candidates", who, (long long)hits, (long long)total);
-    if (hits > 0) {  // (the unsorted keys are dead: the result takes their place)
-        int *d_idx = reinterpret_cast<int *>(di.keys.ptr());
-        hipLaunchKernelGGL(sp_radius_split_kernel<true>, dim3((unsigned)((hits + 255) / 256)), dim3(256), 0, st, (long long)hits,
-                           (const u64 *)di.sorted.ptr(), d_idx, reinterpret_cast<float *>(d_idx + hits), (long long)nq,
-                           (const long long *)di.ind.ptr(), (const long long *)di.off.ptr());
+    if (hits < 0 || hits > total) return fail(FDR_E_HIP, "internal: %s: %lld hits of %lld candidates", who, (long long)hits, total);
+    if (hits > 0) {
+        hipLaunchKernelGGL(radius_split_kernel<true>, dim3((unsigned)((hits + 255) / 256)), dim3(256), 0, st, (long long)hits,
+                           (const u64 *)rr.sorted.ptr(), rr.idx(), reinterpret_cast<float *>(rr.idx() + hits), (long long)nq,
+                           (const long long *)di.ind.ptr(), (const long long *)rr.off.ptr());
         HIP_TRY(hipGetLastError());
     }
     if ((rc = timing_end(ctx, FDR_KERNEL_KNN_RERANK, st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     di.last_hits = hits;
-    di.held = hits;
+    rr.held = hits;
     return FDR_OK;
 }
 
@@ -322,17 +275,18 @@ static int dr_index_from_device_E(fdr_ctx *ctx, const float *d_E, int64_t n, int
     if ((rc = di.ehat.reserve((size_t)n * dp))) return rc;
     if ((rc = di.half.reserve((size_t)n * dp))) return rc;
     if ((rc = di.zero.reserve((size_t)n))) return rc;
-    if ((rc = di.flags.reserve(DR_FLAGS))) return rc;
+    if ((rc = di.rr.flags.reserve(RR_FLAGS))) return rc;
     if ((rc = launch_normalize(ctx, d_E, n, d, di.ehat.ptr(), di.zero.ptr(), st))) return rc;
     hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)((n * (dp / 8) + 255) / 256)), dim3(256), 0, st,
                        (const float *)di.ehat.ptr(), (long long)n * (dp / 8), di.half.ptr());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(di.flags.ptr(), 0, DR_FLAGS * 8, st));
-    hipLaunchKernelGGL(dr_count_zero_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n,
-                       (const unsigned char *)di.zero.ptr(), di.flags.ptr());
+    u64 *const d_nzero = di.rr.flags.ptr() + RR_FLAG_NZERO;
+    HIP_TRY(hipMemsetAsync(di.rr.flags.ptr(), 0, RR_FLAGS * 8, st));
+    hipLaunchKernelGGL(radius_count_flags_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n,
+                       (const unsigned char *)di.zero.ptr(), d_nzero);
     HIP_TRY(hipGetLastError());
     u64 nzero = 0;
-    HIP_TRY(hipMemcpyAsync(&nzero, di.flags.ptr() + DR_FLAG_NZERO, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&nzero, d_nzero, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     di.n = n;
     di.d = d;
@@ -345,7 +299,7 @@ static int dr_index_from_device_E(fdr_ctx *ctx, const float *d_E, int64_t n, int
 // what a build and an embed do first: no index, no held result, no figures of an earlier call
 static void dr_index_reset(DenseIndex &di) {
     di.valid = false;
-    di.held = -1;
+    di.rr.drop();
     di.last_candidates = di.last_hits = 0;
     di.last_query_blocks = di.last_segments = 0;
 }
@@ -380,26 +334,17 @@ FDR_EXPORT int fdr_dense_index_embed(fdr_ctx *ctx, int64_t n_rows, const int64_t
     return dr_index_from_device_E(ctx, (const float *)ctx->E.p, n_rows, ctx->d);
 }
 
-// what the two radius entries check alike, before anything else: the index, the radius, the cap
+// what the two radius entries do first: no held result; the index, the radius, the cap
 static int dr_radius_args(fdr_ctx *ctx, const char *who, float radius, int64_t max_hits) {
-    if (!ctx->di.valid) return fail(FDR_E_STATE, "%s: the context holds no dense index", who);
-    if (radius != radius || radius < 0.0f)
-        return fail(FDR_E_ARG, "%s: the radius must be in [0, 1), got %g", who, (double)radius);
-    if (radius >= 1.0f)
-        return fail(FDR_E_ARG, "%s: the radius must be in [0, 1), got %g: every row is within 1 of every query, and "
-                    "fdr_knn ranks them", who, (double)radius);
-    if (max_hits < 1 || max_hits > INT32_MAX)
-        return fail(FDR_E_ARG, "%s: max_hits (%lld) must be in [1, 2^31)", who, (long long)max_hits);
-    return FDR_OK;
+    ctx->di.rr.drop();
+    return radius_args(ctx->di.valid, who, "dense", "fdr_knn", radius, max_hits);
 }
 
-// a call without queries: an empty result
+// a call without queries: its figures, an empty result
 static int dr_radius_none(DenseIndex &di, int64_t *indptr_out) {
-    indptr_out[0] = 0;
     di.last_candidates = di.last_hits = 0;
     di.last_query_blocks = di.last_segments = 0;
-    di.held = 0;
-    return FDR_OK;
+    return radius_none(di.rr, indptr_out);
 }
 
 FDR_EXPORT int fdr_dense_index_radius_search(fdr_ctx *ctx, float radius, int64_t q_lo, int64_t q_hi, int64_t max_hits,
@@ -408,7 +353,6 @@ FDR_EXPORT int fdr_dense_index_radius_search(fdr_ctx *ctx, float radius, int64_t
     int rc = use_device(ctx);
     if (rc) return rc;
     DenseIndex &di = ctx->di;
-    di.held = -1;
     if ((rc = dr_radius_args(ctx, who, radius, max_hits))) return rc;
     if (q_lo < 0 || q_hi < q_lo || q_hi > di.n)
         return fail(FDR_E_ARG, "%s: rows [%lld, %lld) are no range of the %lld rows", who, (long long)q_lo,
@@ -426,7 +370,6 @@ FDR_EXPORT int fdr_dense_index_radius_query(fdr_ctx *ctx, float radius, int64_t 
     int rc = use_device(ctx);
     if (rc) return rc;
     DenseIndex &di = ctx->di;
-    di.held = -1;
     if ((rc = dr_radius_args(ctx, who, radius, max_hits))) return rc;
     if (nq < 0 || nq > INT32_MAX) return fail(FDR_E_ARG, "%s: nq (%lld) must be in [0, 2^31)", who, (long long)nq);
     if (!indptr_out) return fail(FDR_E_ARG, "%s: null pointer", who);
@@ -447,21 +390,8 @@ FDR_EXPORT int fdr_dense_index_radius_query(fdr_ctx *ctx, float radius, int64_t 
 }
 
 FDR_EXPORT int fdr_dense_index_radius_fetch(fdr_ctx *ctx, int64_t hits, int32_t *idx_out, float *dist_out) {
-    int rc = use_device(ctx);
-    if (rc) return rc;
-    DenseIndex &di = ctx->di;
-    if (di.held < 0)
-        return fail(FDR_E_STATE, "dense_index_radius_fetch: the context holds no radius result (the next dense-index call "
-                    "after a radius search drops it)");
-    if (hits != di.held)
-        return fail(FDR_E_ARG, "dense_index_radius_fetch: hits = %lld, the held result has %lld", (long long)hits, di.held);
-    if (hits == 0) return FDR_OK;
-    if (!idx_out || !dist_out) return fail(FDR_E_ARG, "dense_index_radius_fetch: null pointer");
-    const hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(idx_out, di.idx(), (size_t)hits * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(dist_out, di.dist(), (size_t)hits * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return FDR_OK;
+    if (int rc = use_device(ctx)) return rc;
+    return radius_fetch(ctx->stream, ctx->di.rr, "dense_index_radius_fetch", "next dense-index call", hits, idx_out, dist_out);
 }
 
 FDR_EXPORT int fdr_dense_index_info(fdr_ctx *ctx, int64_t *n, int32_t *d, size_t *device_bytes, int64_t *last_candidates,

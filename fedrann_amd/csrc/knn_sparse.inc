@@ -889,7 +889,7 @@ static int sp_knn(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, c
     if (rc) return rc;
     knn_call_begin(ctx);
     ctx->sp.built = {};  // (the call replaces the context's index, also where it is refused before the build)
-    ctx->spr.drop();
+    ctx->spr.rr.drop();
     if (metric != FDR_METRIC_JACCARD && metric != FDR_METRIC_WEIGHTED_JACCARD && metric != FDR_METRIC_COSINE)
         return fail(FDR_E_ARG, "knn_sparse: unknown metric %d (FDR_METRIC_COSINE, FDR_METRIC_JACCARD, "
                     "FDR_METRIC_WEIGHTED_JACCARD)", metric);
@@ -916,7 +916,7 @@ FDR_EXPORT int fdr_sparse_index_build(fdr_ctx *ctx, int32_t metric, int64_t n, i
                                       const int64_t *indptr, const int32_t *indices, const float *values) {
     int rc = use_device(ctx);
     if (rc) return rc;
-    ctx->spr.drop();
+    ctx->spr.rr.drop();
     if ((rc = sp_build(ctx, "sparse_index_build", metric, n, n_features, indptr, indices, values))) return rc;
     ctx->sp.built.valid = false;
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // (a failure of the sort or of S2 belongs to this call: no index)
@@ -929,7 +929,7 @@ FDR_EXPORT int fdr_sparse_index_search(fdr_ctx *ctx, int32_t k, int64_t q_lo, in
     int rc = use_device(ctx);
     if (rc) return rc;
     knn_call_begin(ctx);
-    ctx->spr.drop();
+    ctx->spr.rr.drop();
     if (!ctx->sp.built.valid) return fail(FDR_E_STATE, "sparse_index_search: the context holds no sparse index");
     const int64_t n = ctx->sp.built.n;
     if (k < 1 || k > FDR_MAX_K || k > n)
@@ -947,7 +947,7 @@ FDR_EXPORT int fdr_sparse_index_query(fdr_ctx *ctx, int32_t k, int64_t nq, const
     int rc = use_device(ctx);
     if (rc) return rc;
     knn_call_begin(ctx);
-    ctx->spr.drop();
+    ctx->spr.rr.drop();
     if (!ctx->sp.built.valid) return fail(FDR_E_STATE, "sparse_index_query: the context holds no sparse index");
     const int64_t n = ctx->sp.built.n;
     if (k < 1 || k > FDR_MAX_K || k > n)

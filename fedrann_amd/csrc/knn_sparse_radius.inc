@@ -1,4 +1,4 @@
-// Part of libfedrann_hip.so: included by fedrann_hip.hip (one translation unit) behind knn_sparse.inc.
+// Part of libfedrann_hip.so: included by fedrann_hip.hip (one translation unit) behind knn_radius_common.inc.
 // ------------------------------------------------------------------------------------------
 // R1 .. R3  radius search on the sparse index (fdr_sparse_index_radius_search / _query / _fetch): every index row
 // within a distance bound r of each query, 0 <= r < 1, under the index's metric.
@@ -7,39 +7,28 @@
 // and keep k of them.  A radius search keeps every row of that table with dist <= r; every row outside the table is
 // at exactly 1.0f, so a bound below 1 never needs one.  The table walk (sp_walk) and the distance formation
 // (sp_slot_dist) are the k-NN kernel's own device functions, so a pair has the same distance bits on either path
-// and the comparison dist <= r is made on the float32 a k-NN search reports.
+// and the comparison dist <= r is made on the float32 a k-NN search reports.  The protocol around the passes (the
+// scan, the cap, the zero rows' list, the cross-check, the held result) is knn_radius_common.inc's; the counts are hit
+// counts, so their scan is the result's indptr.
 //   R1 sp_radius_kernel<RANGE, false>  the COUNT pass.  One wave per query, as S3: walk, then count the table's keys
 //                          with dist <= r into count[q].  A query whose table would pass SP_LIMIT goes to the heavy
 //                          list, as in S3, and the range form (RANGE, as S3r) adds up the counts of its ranges.  A
 //                          zero (empty, zero-mass) query counts the index's zero rows.
-//   (rocprim exclusive scan of the counts, int64: the result's indptr, copied to the host BEFORE anything is
-//    allocated for the hits; the total against max_hits is checked there)
 //   R2 sp_radius_kernel<RANGE, true>   the EMIT pass repeats the walk.  A query that is not heavy holds at most
-//                          SP_LIMIT + 64 table entries: its hits, as keys (dist_bits << 32 | row), are sorted in LDS
-//                          by S3's bitonic network and written to its segment.  A heavy query writes each range's
-//                          hits at a running offset inside its segment; the heavy segments (up to n hits each, far
-//                          more than LDS holds) are then put in order by ONE rocprim segmented radix sort over them
-//                          alone.  A zero query copies the list of the index's zero rows (distance bits 0, index
-//                          order), which rocprim::select builds once per call, and only for a call with a zero query.
-//                          Every write is bounded by the segment the count pass measured; a query whose emitted
-//                          count differs from the counted one is counted in flags[0], and the call then fails
-//                          (FDR_E_HIP, "internal: ..."): the two passes run the same arithmetic, so it stays 0.
+//                          SP_LIMIT + 64 table entries: its hits, as keys, are sorted in LDS by S3's bitonic network
+//                          and written to its segment.  A heavy query writes each range's hits at a running offset
+//                          inside its segment; the heavy segments (up to n hits each, far more than LDS holds) are
+//                          then put in order by ONE rocprim segmented radix sort over them alone.
 //                          R1 marks each query it hands on in handed[], and R2 leaves a marked query to its range
 //                          form without walking it: a heavy query is walked to its overflow point once (R1), then
 //                          once per pass in the range form.
-//   R3 sp_radius_split_kernel  keys -> idx (int32) / dist (float32), the arrays fdr_sparse_index_radius_fetch copies.
+//   R3 radius_split_kernel<false>  keys -> idx / dist, the arrays fdr_sparse_index_radius_fetch copies.
 // Memory: 17 bytes per counted query, and per hit 8 bytes of sorted keys plus the 8 bytes that hold the heavy
 // queries' unsorted keys first and the result afterwards.
 // Cost model: two walks, so about twice the pair updates of a k-NN search of the same queries (sum over features of
 // df_f^2 each), without S3's distance-1 fill; a heavy query adds R1's walk up to its overflow point and the radix
 // sort of its hits.
 // ------------------------------------------------------------------------------------------
-#include <rocprim/device/device_segmented_radix_sort.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-
-#define SPR_FLAG_MISMATCH 0  // queries whose emitted count differs from the counted one
-#define SPR_FLAG_ZLIST 1     // the zero rows rocprim::select found
 
 // R1 (EMIT = false) and R2 (EMIT = true); the queries, the target side and the metric as in knn_sparse_kernel.
 // count [nq]: R1's result (R1 of the heavy list overwrites the heavy queries' entries); off [nq + 1]: its scan, the
@@ -67,8 +56,7 @@ __global__ __launch_bounds__(64) void sp_radius_kernel(long long n, long long q0
         if (!EMIT) {
             if (lane == 0) count[row] = nzero;
         } else {
-            for (long long i = lane; i < min(nzero, seg); i += 64) keys_out[seg0 + i] = (u64)(unsigned)zlist[i];
-            if (lane == 0 && seg != nzero) atomicAdd(&flags[SPR_FLAG_MISMATCH], 1ull);
+            radius_emit_zero(lane, seg0, seg, nzero, zlist, keys_out, flags);
         }
         return;
     }
@@ -88,7 +76,7 @@ __global__ __launch_bounds__(64) void sp_radius_kernel(long long n, long long q0
                 qs.heavy[atomicAdd(&cnt[SP_CNT_HEAVY], 1ull)] = (int)q;
                 handed[row] = 1;
             } else if (EMIT && lane == 0) {
-                atomicAdd(&flags[SPR_FLAG_MISMATCH], 1ull);
+                atomicAdd(&flags[RR_FLAG_MISMATCH], 1ull);
             }
             return;
         }
@@ -132,7 +120,7 @@ __global__ __launch_bounds__(64) void sp_radius_kernel(long long n, long long q0
     }
     if (lane == 0) {
         if (!EMIT) count[row] = hits;
-        else if (hits != seg) atomicAdd(&flags[SPR_FLAG_MISMATCH], 1ull);
+        else if (hits != seg) atomicAdd(&flags[RR_FLAG_MISMATCH], 1ull);
     }
 }
 
@@ -149,32 +137,6 @@ __global__ __launch_bounds__(256) void sp_radius_segments_kernel(long long nheav
     seg_hi[i] = off[row + 1];
 }
 
-// R3.  COMPACT (the dense index's D-R3, knn_dense_radius.inc; dst_off / src_off [nseg + 1] each) compacts as it
-// splits: output entry i belongs to the segment s with dst_off[s] <= i < dst_off[s + 1] and is the key at
-// src_off[s] + (i - dst_off[s]), the first dst_off[s + 1] - dst_off[s] keys of each source segment.  The sparse
-// search's instantiation, COMPACT = false, reads key i and none of the three.
-template <bool COMPACT>
-__global__ __launch_bounds__(256) void sp_radius_split_kernel(long long total, const u64 *__restrict__ keys,
-                                                              int *__restrict__ idx, float *__restrict__ dist,
-                                                              long long nseg, const long long *__restrict__ dst_off,
-                                                              const long long *__restrict__ src_off) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    long long src = i;
-    if constexpr (COMPACT) {
-        long long lo = 0, hi = nseg;  // the last s in [0, nseg) with dst_off[s] <= i (dst_off[0] = 0 <= i < dst_off[nseg])
-        while (hi - lo > 1) {
-            const long long mid = (lo + hi) >> 1;
-            if (dst_off[mid] <= i) lo = mid;
-            else hi = mid;
-        }
-        src = src_off[lo] + (i - dst_off[lo]);
-    }
-    const u64 key = keys[src];
-    idx[i] = (int)(unsigned)key;
-    dist[i] = __uint_as_float((unsigned)(key >> 32));
-}
-
 // ---- host side ----------------------------------------------------------------------------------------------------
 // Both passes of a radius call over the queries [q0, q0 + nq) of the query side (the caller has reset the search's
 // counters and counted the zero queries where they come from the index): R1, the scan, indptr_out, the cap, R2, the
@@ -186,23 +148,21 @@ static int sp_radius_passes(fdr_ctx *ctx, const char *who, const SpQuerySide &qs
     const hipStream_t st = ctx->stream;
     SparseIndex &sp = ctx->sp;
     SparseRadius &sr = ctx->spr;
+    RadiusResult &rr = sr.rr;
+    const RadiusCall call = {st, who, nq, max_hits, indptr_out};
     constexpr bool JAC = METRIC == FDR_METRIC_JACCARD;
     constexpr bool WJ = METRIC == FDR_METRIC_WEIGHTED_JACCARD;
     const int64_t n = sp.built.n;
     const long long nzero = sp.built.nzero;
-    if ((rc = sr.count.reserve((size_t)nq + 1))) return rc;
-    if ((rc = sr.off.reserve((size_t)nq + 1))) return rc;
-    if ((rc = sr.flags.reserve(2))) return rc;
+    if ((rc = radius_reserve(rr, call))) return rc;
     if ((rc = sr.handed.reserve((size_t)nq))) return rc;
-    HIP_TRY(hipMemsetAsync(sr.count.ptr(), 0, ((size_t)nq + 1) * 8, st));
     HIP_TRY(hipMemsetAsync(sr.handed.ptr(), 0, (size_t)nq, st));
-    HIP_TRY(hipMemsetAsync(sr.flags.ptr(), 0, 16, st));
     auto launch = [&](auto range, auto emit, unsigned grid, u64 *keys_out) {  // (keys_out: R2's)
         hipLaunchKernelGGL((sp_radius_kernel<decltype(range)::value, decltype(emit)::value, METRIC>), dim3(grid), dim3(64),
                            0, st, (long long)n, (long long)q0, qs, sp.runptr.ptr(), sp.posting_rows(),
                            JAC ? nullptr : sp.pval.ptr(), JAC ? sp.asize.ptr() : nullptr, WJ ? sp.mass.ptr() : nullptr,
-                           radius, nzero, sr.zlist.ptr(), sp.cnt.ptr(), sr.count.ptr(), sr.handed.ptr(), sr.off.ptr(),
-                           keys_out, sr.flags.ptr());
+                           radius, nzero, rr.zlist.ptr(), sp.cnt.ptr(), rr.count.ptr(), sr.handed.ptr(), rr.off.ptr(),
+                           keys_out, rr.flags.ptr());
     };
     // R1
     launch(std::false_type{}, std::false_type{}, (unsigned)nq, nullptr);
@@ -217,14 +177,6 @@ static int sp_radius_passes(fdr_ctx *ctx, const char *who, const SpQuerySide &qs
         launch(std::true_type{}, std::false_type{}, (unsigned)h[0], nullptr);
         HIP_TRY(hipGetLastError());
     }
-    auto scan = [&](void *tmp, size_t &bytes) {
-        return rocprim::exclusive_scan(tmp, bytes, sr.count.ptr(), sr.off.ptr(), 0ll, (size_t)nq + 1,
-                                       rocprim::plus<long long>(), st);
-    };
-    if ((rc = rocprim_run(sp.tmp, "rocprim::exclusive_scan", scan))) return rc;
-    static_assert(sizeof(long long) == sizeof(int64_t), "the scan is the result's indptr");
-    HIP_TRY(hipMemcpyAsync(indptr_out, sr.off.ptr(), ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
     fdr_knn_trace &t = ctx->last.trace;
     t.kind = FDR_TRACE_SPARSE;
     t.k = 0;
@@ -233,55 +185,34 @@ static int sp_radius_passes(fdr_ctx *ctx, const char *who, const SpQuerySide &qs
     t.zero_queries = (int32_t)std::min<u64>(h[1], INT32_MAX);
     t.range_queries = (int32_t)h[0];
     t.range_chunks = h[0] ? (int32_t)((n + SP_W - 1) / SP_W) : 0;
-    const int64_t total = indptr_out[nq];
-    if (total > max_hits)  // (the one refusal that has written its output: the caller cuts the block by the counts)
-        return fail(FDR_E_ARG, "%s: %lld hits exceed max_hits = %lld (indptr_out holds the counts: search fewer rows "
-                    "per call)", who, (long long)total, (long long)max_hits);
-    if (total == 0) {
-        sr.held = 0;
-        return FDR_OK;
-    }
+    if ((rc = radius_offsets(rr, sp.tmp, call, "hits", "counts", nullptr)) || rr.counted == 0) return rc;
+    const long long total = rr.counted;
     // R2
-    if ((rc = sr.keys.reserve((size_t)total))) return rc;
-    if ((rc = sr.sorted.reserve((size_t)total))) return rc;
-    if (h[1] > 0 && nzero > 0) {  // the zero rows' list
-        if ((rc = sr.zlist.reserve((size_t)nzero))) return rc;
-        auto select = [&](void *tmp, size_t &bytes) {
-            return rocprim::select(tmp, bytes, rocprim::counting_iterator<int>(0), sp.zero.ptr(), sr.zlist.ptr(),
-                                   sr.flags.ptr() + SPR_FLAG_ZLIST, (size_t)n, st);
-        };
-        if ((rc = rocprim_run(sp.tmp, "rocprim::select", select))) return rc;
-    }
+    const bool zeros = h[1] > 0 && nzero > 0;  // a zero query, and zero rows for it
+    if (zeros && (rc = radius_zero_list(rr, sp.tmp, call, sp.zero.ptr(), n, nzero))) return rc;
     if (h[0] > 0) {
         if ((rc = sr.seg_lo.reserve((size_t)h[0]))) return rc;
         if ((rc = sr.seg_hi.reserve((size_t)h[0]))) return rc;
         hipLaunchKernelGGL(sp_radius_segments_kernel, dim3((unsigned)((h[0] + 255) / 256)), dim3(256), 0, st,
-                           (long long)h[0], (long long)q0, qs.heavy, sr.off.ptr(), sr.seg_lo.ptr(), sr.seg_hi.ptr());
+                           (long long)h[0], (long long)q0, qs.heavy, rr.off.ptr(), sr.seg_lo.ptr(), sr.seg_hi.ptr());
         HIP_TRY(hipGetLastError());
-        launch(std::true_type{}, std::true_type{}, (unsigned)h[0], sr.keys.ptr());
+        launch(std::true_type{}, std::true_type{}, (unsigned)h[0], rr.keys.ptr());
         HIP_TRY(hipGetLastError());
         auto sort = [&](void *tmp, size_t &bytes) {  // (dist <= r < 1: the keys lie below 2^62)
-            return rocprim::segmented_radix_sort_keys(tmp, bytes, sr.keys.ptr(), sr.sorted.ptr(), (unsigned)total,
+            return rocprim::segmented_radix_sort_keys(tmp, bytes, rr.keys.ptr(), rr.sorted.ptr(), (unsigned)total,
                                                       (unsigned)h[0], sr.seg_lo.ptr(), sr.seg_hi.ptr(), 0, 62, st);
         };
         if ((rc = rocprim_run(sp.tmp, "rocprim::segmented_radix_sort_keys", sort))) return rc;
     }
-    launch(std::false_type{}, std::true_type{}, (unsigned)nq, sr.sorted.ptr());  // (every other query, sorted in LDS)
+    launch(std::false_type{}, std::true_type{}, (unsigned)nq, rr.sorted.ptr());  // (every other query, sorted in LDS)
     HIP_TRY(hipGetLastError());
-    // R3 (the unsorted keys are dead: the result takes their place)
-    int *d_idx = reinterpret_cast<int *>(sr.keys.ptr());
-    hipLaunchKernelGGL(sp_radius_split_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (long long)total,
-                       sr.sorted.ptr(), d_idx, reinterpret_cast<float *>(d_idx + total), 0ll, (const long long *)nullptr,
-                       (const long long *)nullptr);
+    // R3
+    hipLaunchKernelGGL(radius_split_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total,
+                       rr.sorted.ptr(), rr.idx(), reinterpret_cast<float *>(rr.idx() + total), 0ll,
+                       (const long long *)nullptr, (const long long *)nullptr);
     HIP_TRY(hipGetLastError());
-    u64 f[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(f, sr.flags.ptr(), 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (f[SPR_FLAG_MISMATCH] != 0 || (h[1] > 0 && nzero > 0 && f[SPR_FLAG_ZLIST] != (u64)nzero))
-        return fail(FDR_E_HIP, "internal: %s: the emit pass disagrees with the count pass on %llu queries (zero rows "
-                    "listed: %llu of %lld)", who, (unsigned long long)f[SPR_FLAG_MISMATCH],
-                    (unsigned long long)f[SPR_FLAG_ZLIST], nzero);
-    sr.held = total;
+    if ((rc = radius_check(rr, call, zeros, nzero))) return rc;
+    rr.held = total;
     return FDR_OK;
 }
 
@@ -294,29 +225,20 @@ static int sp_radius(fdr_ctx *ctx, const char *who, const SpQuerySide &qs, float
     return sp_radius_passes<FDR_METRIC_COSINE>(ctx, who, qs, radius, q0, nq, max_hits, indptr_out);
 }
 
-// what the two radius entries check alike, before anything else: the index, the radius, the cap
+// what the two radius entries do first: no held result; the index, the radius, the cap
 static int sp_radius_args(fdr_ctx *ctx, const char *who, float radius, int64_t max_hits) {
-    if (!ctx->sp.built.valid) return fail(FDR_E_STATE, "%s: the context holds no sparse index", who);
-    if (radius != radius || radius < 0.0f)
-        return fail(FDR_E_ARG, "%s: the radius must be in [0, 1), got %g", who, (double)radius);
-    if (radius >= 1.0f)
-        return fail(FDR_E_ARG, "%s: the radius must be in [0, 1), got %g: every row is within 1 of every query, and "
-                    "fdr_sparse_index_search ranks them", who, (double)radius);
-    if (max_hits < 1 || max_hits > INT32_MAX)
-        return fail(FDR_E_ARG, "%s: max_hits (%lld) must be in [1, 2^31)", who, (long long)max_hits);
-    return FDR_OK;
+    ctx->spr.rr.drop();
+    return radius_args(ctx->sp.built.valid, who, "sparse", "fdr_sparse_index_search", radius, max_hits);
 }
 
 // a call without queries: the trace, an empty result
 static int sp_radius_none(fdr_ctx *ctx, int64_t *indptr_out) {
-    indptr_out[0] = 0;
     fdr_knn_trace &t = ctx->last.trace;
     t.kind = FDR_TRACE_SPARSE;
     t.k = 0;
     t.queries = 0;
     t.targets = ctx->sp.built.n;
-    ctx->spr.held = 0;
-    return FDR_OK;
+    return radius_none(ctx->spr.rr, indptr_out);
 }
 
 FDR_EXPORT int fdr_sparse_index_radius_search(fdr_ctx *ctx, float radius, int64_t q_lo, int64_t q_hi, int64_t max_hits,
@@ -325,7 +247,6 @@ FDR_EXPORT int fdr_sparse_index_radius_search(fdr_ctx *ctx, float radius, int64_
     int rc = use_device(ctx);
     if (rc) return rc;
     knn_call_begin(ctx);
-    ctx->spr.drop();
     if ((rc = sp_radius_args(ctx, who, radius, max_hits))) return rc;
     SparseIndex &sp = ctx->sp;
     const int64_t n = sp.built.n;
@@ -354,7 +275,6 @@ FDR_EXPORT int fdr_sparse_index_radius_query(fdr_ctx *ctx, float radius, int64_t
     int rc = use_device(ctx);
     if (rc) return rc;
     knn_call_begin(ctx);
-    ctx->spr.drop();
     if ((rc = sp_radius_args(ctx, who, radius, max_hits))) return rc;
     if (nq < 0 || nq > INT32_MAX) return fail(FDR_E_ARG, "%s: nq (%lld) must be in [0, 2^31)", who, (long long)nq);
     if (!indptr_out) return fail(FDR_E_ARG, "%s: null pointer", who);
@@ -367,20 +287,6 @@ FDR_EXPORT int fdr_sparse_index_radius_query(fdr_ctx *ctx, float radius, int64_t
 }
 
 FDR_EXPORT int fdr_sparse_index_radius_fetch(fdr_ctx *ctx, int64_t hits, int32_t *idx_out, float *dist_out) {
-    int rc = use_device(ctx);
-    if (rc) return rc;
-    SparseRadius &sr = ctx->spr;
-    if (sr.held < 0)
-        return fail(FDR_E_STATE, "sparse_index_radius_fetch: the context holds no radius result (the next sparse call "
-                    "after a radius search drops it)");
-    if (hits != sr.held)
-        return fail(FDR_E_ARG, "sparse_index_radius_fetch: hits = %lld, the held result has %lld", (long long)hits,
-                    sr.held);
-    if (hits == 0) return FDR_OK;
-    if (!idx_out || !dist_out) return fail(FDR_E_ARG, "sparse_index_radius_fetch: null pointer");
-    const hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(idx_out, sr.idx(), (size_t)hits * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(dist_out, sr.dist(), (size_t)hits * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return FDR_OK;
+    if (int rc = use_device(ctx)) return rc;
+    return radius_fetch(ctx->stream, ctx->spr.rr, "sparse_index_radius_fetch", "next sparse call", hits, idx_out, dist_out);
 }

@@ -276,6 +276,51 @@ def test_state_rules(ctx):
         index2.info()
 
 
+def test_the_two_held_radius_results_are_independent(ctx):
+    """One context, a Jaccard sparse index (64 rows over 50 features) and a dense index (64 rows, d = 8), each with a
+    zero row: the result a raw radius search leaves in one index is untouched by the other index's search, in either
+    order, and a sparse k-NN search drops the sparse result alone."""
+    L, h = ctx._L, ctx._h
+    rng = np.random.default_rng(64)
+    rows = [np.sort(rng.choice(50, size=rng.integers(1, 6), replace=False)).astype(np.int32) for _ in range(64)]
+    rows[5] = rows[40] = np.empty(0, np.int32)  # (two empty rows: a zero query finds the other one, too)
+    sp_ip = np.zeros(65, np.int64)
+    sp_ip[1:] = np.cumsum([r.size for r in rows])
+    sp_ix = np.concatenate(rows)
+    E = plain_rows(64, 8, 64)  # (rows 3, 32 and 63 are zero)
+    rs, rd = ctypes.c_float(0.7), ctypes.c_float(0.3)
+
+    def fetch(name, total):
+        ix, ds = np.empty(total, np.int32), np.empty(total, np.float32)
+        rc = getattr(L, name)(h, total, vp(ix.ctypes.data), vp(ds.ctypes.data))
+        return rc, ix, ds.view(np.uint32)
+
+    with ctx.sparse_index(sp_ip, sp_ix, None, 50, metric="jaccard") as sparse, ctx.dense_index(E) as dense:
+        assert sparse.info()["zero_rows"] == 2
+        want = {"sparse": sparse.radius_search(rs.value), "dense": dense.radius_search(rd.value)}
+        for res in want.values():
+            assert res[0][-1] > 64 and np.all(np.diff(res[0]) >= 1)  # non-empty, the zero queries' rows included
+        assert not np.array_equal(want["sparse"][1], want["dense"][1])
+        search = {"sparse": lambda ip: L.fdr_sparse_index_radius_search(h, rs, 0, 64, 1 << 20, vp(ip.ctypes.data)),
+                  "dense": lambda ip: L.fdr_dense_index_radius_search(h, rd, 0, 64, 1 << 20, vp(ip.ctypes.data))}
+        for order in (("sparse", "dense"), ("dense", "sparse")):
+            ips = {}
+            for kind in order:  # both searches first ...
+                ips[kind] = np.full(65, -1, np.int64)
+                assert search[kind](ips[kind]) == 0, L.fdr_last_error().decode()
+            for kind in order:  # ... then both fetches
+                assert np.array_equal(ips[kind], want[kind][0])
+                rc, ix, bits = fetch("fdr_%s_index_radius_fetch" % kind, int(ips[kind][-1]))
+                assert rc == 0, L.fdr_last_error().decode()
+                assert np.array_equal(ix, want[kind][1]) and np.array_equal(bits, want[kind][2].view(np.uint32))
+        sparse.search(3)  # (a sparse call drops the sparse result; the dense one is not its business)
+        assert fetch("fdr_sparse_index_radius_fetch", int(want["sparse"][0][-1]))[0] == E_STATE
+        assert "no radius result" in L.fdr_last_error().decode()
+        rc, ix, bits = fetch("fdr_dense_index_radius_fetch", int(want["dense"][0][-1]))
+        assert rc == 0, L.fdr_last_error().decode()
+        assert np.array_equal(ix, want["dense"][1]) and np.array_equal(bits, want["dense"][2].view(np.uint32))
+
+
 def test_dense_and_sparse_calls_do_not_disturb_each_other(ctx, oracle):
     E = plain_rows(400, 100, 4)
     rng = np.random.default_rng(8)
