@@ -827,6 +827,7 @@ struct fdr_ctx {
     std::vector<unsigned> live_host;  // the live-chunk plan's read-back: the query blocks' masks
     int skip_mode = FDR_SKIP_AUTO;    // fdr_set_live_skip
     std::vector<int> skip_host;       // ... and the lengths of the stage lists, [segment][mask value]
+    int compact_mode = FDR_COMPACT_AUTO;  // fdr_set_rerank_compact
     KnnCallRecord last;  // what the fdr_last_* getters report
     // fdr_set_knn_capture / fdr_last_candidates / fdr_last_range_sets: the prefilter pass's intermediate results
     struct {
@@ -1070,6 +1071,12 @@ FDR_EXPORT int fdr_set_live_skip(fdr_ctx *ctx, int mode) {
     return FDR_OK;
 }
 
+FDR_EXPORT int fdr_set_rerank_compact(fdr_ctx *ctx, int mode) {
+    if (!ctx || mode < FDR_COMPACT_AUTO || mode > FDR_COMPACT_FORCE) return fail(FDR_E_ARG, "bad compact re-rank mode");
+    ctx->compact_mode = mode;
+    return FDR_OK;
+}
+
 FDR_EXPORT int fdr_last_live_stage_lists(fdr_ctx *ctx, int32_t segment, int32_t *first_row_out, int32_t *nstages_out,
                                          int32_t *lens, uint16_t *lists) {
     int rc = use_device(ctx);
@@ -1256,7 +1263,8 @@ static size_t class_tables_tmp_bytes(size_t rows) {
     return std::max(t_sort, t_scan);
 }
 static WsEnv ws_env(const fdr_ctx *ctx) {
-    return {ctx->num_cus, ctx->knn_mode, ctx->dedup_mode, order_sort_tmp_bytes, class_tables_tmp_bytes, ctx->live_mode};
+    return {ctx->num_cus, ctx->knn_mode, ctx->dedup_mode, order_sort_tmp_bytes, class_tables_tmp_bytes, ctx->live_mode,
+            ctx->compact_mode};
 }
 
 FDR_EXPORT size_t fdr_knn_workspace_bytes(fdr_ctx *ctx, int64_t nq, int64_t nt, int32_t d,
@@ -1465,8 +1473,13 @@ int PrefilterCall::setup() {
     const int64_t nq = a.nq, nt = a.nt;
     int trc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, st);
     if (trc) return trc;
-    hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)((nt * (dp / 8) + 255) / 256)), dim3(256), 0, st, a.That,
-                       (long long)nt * (dp / 8), L.ht);
+    HIP_TRY(hipMemsetAsync(L.counter, 0, 64, st));  // certify()'s counters [0 .. 2] and the records' long-row count [8]
+    if (L.rc) {  // (d <= 128: the compact records of the re-rank come out of the same pass over the rows)
+        hipLaunchKernelGGL(to_half_compact_kernel, dim3((unsigned)((nt * (dp / 8) + 255) / 256)), dim3(256), 0, st, a.That,
+                           (long long)nt * (dp / 8), L.ht, L.rc, L.counter + 8);
+    } else
+        hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)((nt * (dp / 8) + 255) / 256)), dim3(256), 0, st, a.That,
+                           (long long)nt * (dp / 8), L.ht);
     if (!self)
         hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)((nq * (dp / 8) + 255) / 256)), dim3(256), 0, st, a.Qhat,
                            (long long)nq * (dp / 8), L.hq);
@@ -1632,13 +1645,17 @@ int PrefilterCall::certify(PrefilterCounts &n) {
         ctx->cap.stream = st;
         ctx->cap.cand_valid = true;
     }
-    HIP_TRY(hipMemsetAsync(L.counter, 0, 16, st));
     const float margin = 2.0f * prefilter_eps(ib) + 4.0e-7f;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_rerank_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, RERANK_LDS_BYTES));
-    hipLaunchKernelGGL(knn_rerank_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), RERANK_LDS_BYTES, st,
+    // Beside the records the kernel's dense batches are short (the instance of RERANK_ROWS_COMPACT rows).  Whether the
+    // records are read is the kernel's own decision, from the long-row count their build left in counter[8] (knn_workspace.inc:
+    // RC_LONG_SHARE): no read-back in front of this launch.
+    const auto rerank = L.rc ? knn_rerank_kernel<RERANK_ROWS_COMPACT> : knn_rerank_kernel<RERANK_ROWS_DENSE>;
+    const int rerank_lds = L.rc ? RERANK_LDS_BYTES(RERANK_ROWS_COMPACT) : RERANK_LDS_BYTES(RERANK_ROWS_DENSE);
+    const int long_limit = ctx->compact_mode == FDR_COMPACT_FORCE ? 0x7fffffff : (int)(a.nt / RC_LONG_SHARE);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(rerank), hipFuncAttributeMaxDynamicSharedMemorySize, rerank_lds));
+    hipLaunchKernelGGL(rerank, dim3((unsigned)((nq + 3) / 4)), dim3(256), rerank_lds, st,
                        (const u64 *)L.cand, kp, k, a.Qhat, a.qzero, a.That, (int)nq, dp, (int)a.t_base, margin,
-                       a.idx, a.dist, L.counter, L.flagged, L.rlist, L.theta, L.path);
+                       a.idx, a.dist, L.counter, L.flagged, L.rlist, L.theta, L.path, (const unsigned char *)L.rc, long_limit);
     // all-zero queries share one closed-form answer (their number is only known on the device yet)
     hipLaunchKernelGGL(zero_answer_kernel, dim3(1), dim3(1024), 0, st, (const unsigned *)R.bits, (int)a.nt,
                        (int)a.t_base, k, L.zidx, L.zdist);
@@ -1647,9 +1664,13 @@ int PrefilterCall::certify(PrefilterCounts &n) {
                        (const int *)L.flagged, (int)nq, (const int *)L.counter, k, a.idx, a.dist);
     HIP_TRY(hipGetLastError());
     if ((trc = timing_end(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
-    n = {0, 0, 0};  // how many queries could not be certified / are all-zero / need a range pass?
-    HIP_TRY(hipMemcpyAsync(&n, L.counter, 12, hipMemcpyDeviceToHost, st));
+    int counts[9] = {};  // how many queries could not be certified / are all-zero / need a range pass?  [8]: long rows
+    HIP_TRY(hipMemcpyAsync(counts, L.counter, sizeof counts, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    n = {counts[0], counts[1], counts[2]};
+    ctx->last.trace.rerank_compact = L.rc && counts[8] <= long_limit;  // (the kernel's own test)
+    ctx->last.trace.rerank_compact_entries = L.rc ? RC_ENTRIES : 0;
+    ctx->last.trace.rerank_compact_long = counts[8];
     ctx->last.pass.flagged = n.exact + n.range;
     ctx->last.trace.uncertified = n.exact;
     ctx->last.trace.zero_queries = n.zero;

@@ -25,16 +25,72 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // (FDR_PREFILTER_EPS / _EXTRA / _MAX_IB, prefilter_index_bits(), prefilter_eps(), prefilter_extra(): knn_plan.inc)
 
 // Ehat fp32 [n, DP] (k0 k2 k4 k6 k1 k3 k5 k7 inside each group of 8) -> fp16 [n, DP], natural order
+// group t of 8 components: v[] = its fp32 values in natural (canonical-chain) order, their fp16 roundings stored
+__device__ __forceinline__ void to_half_group(const float *__restrict__ Ehat, long long t, _Float16 *__restrict__ out,
+                                              float (&v)[8]) {
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(Ehat) + t * 2;
+    const f32x4 e = src[0], o = src[1];  // even components k0 k2 k4 k6 | odd components k1 k3 k5 k7
+    v[0] = e.x; v[1] = o.x; v[2] = e.y; v[3] = o.y; v[4] = e.z; v[5] = o.z; v[6] = e.w; v[7] = o.w;
+    f16x8 h;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) h[i] = (_Float16)v[i];
+    reinterpret_cast<f16x8 *>(out)[t] = h;
+}
 __global__ __launch_bounds__(256) void to_half_kernel(const float *__restrict__ Ehat, long long n_groups,
                                                       _Float16 *__restrict__ out) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;  // one thread per 8 components
     if (t >= n_groups) return;
-    const f32x4 *src = reinterpret_cast<const f32x4 *>(Ehat) + t * 2;
-    const f32x4 e = src[0], o = src[1];  // even components k0 k2 k4 k6 | odd components k1 k3 k5 k7
-    f16x8 h;
-    h[0] = (_Float16)e.x; h[1] = (_Float16)o.x; h[2] = (_Float16)e.y; h[3] = (_Float16)o.y;
-    h[4] = (_Float16)e.z; h[5] = (_Float16)o.z; h[6] = (_Float16)e.w; h[7] = (_Float16)o.w;
-    reinterpret_cast<f16x8 *>(out)[t] = h;
+    float v[8];
+    to_half_group(Ehat, t, out, v);
+}
+
+// to_half_kernel for rows of RC_DP components that also writes each row's compact record (knn_workspace.inc: RC_*)
+// while the row is in registers: the 16 threads of a row are 16 adjacent lanes, a prefix sum over them gives every
+// non-zero component (bits & 0x7fffffff != 0: -0.0f is a zero) its entry number in canonical-chain order.  A row with
+// more than RC_ENTRIES non-zeros gets its count alone; such rows are counted in *n_long, one atomic per workgroup.
+__global__ __launch_bounds__(256) void to_half_compact_kernel(const float *__restrict__ Ehat, long long n_groups,
+                                                              _Float16 *__restrict__ out, unsigned char *__restrict__ rc,
+                                                              int *__restrict__ n_long) {
+    __shared__ int wg_long;
+    if (threadIdx.x == 0) wg_long = 0;
+    __syncthreads();
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = t < n_groups;  // (n_groups is a multiple of 16: the lanes of a row are live together)
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (live) to_half_group(Ehat, t, out, v);
+    const int g = (int)(t & 15);
+    unsigned nzm = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) nzm |= (unsigned)((__float_as_uint(v[i]) & 0x7fffffffu) != 0u) << i;
+    const int mine = __popc(nzm);
+    int incl = mine;
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+        const int below = __shfl_up(incl, off, 16);
+        if (g >= off) incl += below;
+    }
+    const int total = __shfl(incl, 15, 16);  // (<= RC_DP: fits the count byte)
+    if (live) {
+        unsigned char *rec = rc + (size_t)(t >> 4) * RC_BYTES;
+        if (g == 0) rec[0] = (unsigned char)total;
+        if (total <= RC_ENTRIES) {
+            int e = incl - mine;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if ((nzm >> i) & 1u) {
+                    unsigned char *hf = rec + 64 * (e / RC_HALF_ENTRIES);
+                    const int s = e % RC_HALF_ENTRIES;
+                    hf[1 + s] = (unsigned char)(8 * g + (i & 1) * 4 + (i >> 1));  // where component 8 g + i is stored
+                    reinterpret_cast<float *>(hf + 16)[s] = v[i];
+                    ++e;
+                }
+            }
+        }
+    }
+    const u64 lm = __ballot(live && g == 0 && total > RC_ENTRIES);
+    if ((threadIdx.x & 63) == 0 && lm) atomicAdd(&wg_long, __popcll(lm));
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_long) atomicAdd(n_long, wg_long);
 }
 
 // ds_read_b128 with an immediate offset, outside hipcc's waitcnt bookkeeping (the caller waits with a
@@ -913,23 +969,39 @@ __global__ __launch_bounds__(256) void knn_merge_keys_kernel(const u64 *__restri
 }
 
 // P2: certificate + exact re-rank.  One wave per query, one lane per candidate.
-// The candidates' fp32 rows are fetched by the whole wave, 128 components of 32 rows at a time (a half-wave per
+// The candidates' fp32 rows are fetched by the whole wave, 128 components of ROWS rows at a time (a half-wave per
 // row and load: whole 512-byte runs instead of 16 bytes from each of K' rows), and turned through LDS (rows
 // RERANK_STRIDE floats apart: lane r reading row r meets no bank conflict) so that each lane still runs the
 // canonical chain of its own candidate; the query row is wave-uniform and read through the scalar cache.
-#define RERANK_ROWS 32
+//
+// Compact route (rc != null; DP = RC_DP): a needed candidate's lane reads the row's own record instead (knn_workspace.inc:
+// RC_*, written by to_half_compact_kernel) and runs c = fmaf(q[pos_e], val_e, c) over its entries in record order --
+// the dense chain with the terms of the zero components left out, which changes no bit (DESIGN.md section 6).  The
+// query row sits in LDS for that, read with a per-lane position; the loop runs to the wave's largest count with the
+// lanes past their own count predicated off, and the second half of a record is read only by the lanes whose count
+// says so.  A candidate whose record is long keeps the dense route, which then fetches the long rows only.
+// ROWS = rows of a dense batch (lane l's candidate is row l % ROWS of batch l / ROWS): 32 where every candidate takes the
+// dense route (67.6 KB of rows a workgroup, 8 waves per CU), 16 beside the compact route, where a batch serves the few
+// long rows (35.8 KB, 16 waves per CU: the record reads are latency-bound).
+#define RERANK_ROWS_DENSE 32
+#define RERANK_ROWS_COMPACT 16
 #define RERANK_STRIDE 132
-#define RERANK_LDS_BYTES (4 * RERANK_ROWS * RERANK_STRIDE * 4)  // four waves per workgroup
+// a wave's rows and, in the instance that reads records, its query row
+#define RERANK_WAVE_FLOATS(ROWS) ((ROWS) * RERANK_STRIDE + ((ROWS) == RERANK_ROWS_COMPACT ? RC_DP : 0))
+#define RERANK_LDS_BYTES(ROWS) (4 * RERANK_WAVE_FLOATS(ROWS) * 4)  // four waves per workgroup
+template <int ROWS>
 __global__ __launch_bounds__(256) void knn_rerank_kernel(
     const u64 *__restrict__ cand, int KP, int K, const float *__restrict__ Qhat,
     const unsigned char *__restrict__ qzero, const float *__restrict__ That, int nq, int DP, int t_base,
     float margin, int *__restrict__ idx_out, float *__restrict__ dist_out, int *__restrict__ counter,
     int *__restrict__ flagged, int *__restrict__ range_list, float *__restrict__ theta,
-    unsigned char *__restrict__ path) {  // path[q]: how query q's result is produced (FDR_PATH_*: fdr_last_query_paths)
+    unsigned char *__restrict__ path,  // path[q]: how query q's result is produced (FDR_PATH_*: fdr_last_query_paths)
+    const unsigned char *__restrict__ rc,  // the targets' compact records, from row t_base on (null: dense route only)
+    int long_limit) {  // ... read only if their build counted at most so many long rows (counter[8]; knn_workspace.inc)
     extern __shared__ float rerank_rows[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    float *rows = rerank_rows + wave * (RERANK_ROWS * RERANK_STRIDE);
+    float *rows = rerank_rows + wave * RERANK_WAVE_FLOATS(ROWS);
     const int q = blockIdx.x * 4 + wave;
     if (q >= nq) return;
     if (qzero[q]) {  // all-zero query: closed-form answer (zero_answer_kernel); listed from the back
@@ -962,31 +1034,70 @@ __global__ __launch_bounds__(256) void knn_rerank_kernel(
     if (lane == 0) path[q] = FDR_PATH_CERTIFIED;
     const bool need = lane < KP && key < KEY_INF && dt <= dK + margin;
     const int tidx = (int)(unsigned)(key & 0xffffffffull);
-    const u64 needmask = __ballot(need);
+    u64 densemask = __ballot(need);  // the candidates of the dense route
     const int half = lane >> 5, l5 = lane & 31;
     float c = 0.0f;
-    for (int b = 0; b * RERANK_ROWS < KP; ++b) {
-        const unsigned bm = (unsigned)(needmask >> (RERANK_ROWS * b));
+    if (ROWS == RERANK_ROWS_COMPACT && rc && counter[8] <= long_limit) {  // (wave-uniform; the other instance has no query row)
+        float *qs = rows + ROWS * RERANK_STRIDE;
+        reinterpret_cast<float2 *>(qs)[lane] = reinterpret_cast<const float2 *>(Qhat + (size_t)q * RC_DP)[lane];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the wave's own LDS writes, read by its other lanes)
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint4 *rec = reinterpret_cast<const uint4 *>(rc + (size_t)(need ? tidx - t_base : 0) * RC_BYTES);
+        int mine = 0;  // entries this lane's chain runs over (0: not needed, or long)
+        int most = 0;  // ... and the wave's largest such count (wave-uniform)
+#pragma unroll
+        for (int h = 0; h < RC_HALVES; ++h) {
+            if (h > 0 && most <= RC_HALF_ENTRIES * h) continue;
+            const bool live = h == 0 ? need : mine > RC_HALF_ENTRIES * h;
+            unsigned w[16] = {};
+            if (live) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint4 x = rec[4 * h + i];
+                    w[4 * i] = x.x; w[4 * i + 1] = x.y; w[4 * i + 2] = x.z; w[4 * i + 3] = x.w;
+                }
+            }
+            if (h == 0) {
+                const int cnt = (int)(w[0] & 0xffu);
+                mine = cnt <= RC_ENTRIES ? cnt : 0;
+                densemask = __ballot(need && cnt > RC_ENTRIES);
+                static_assert(RC_ENTRIES < 32, "the largest count is found over five bits");
+#pragma unroll
+                for (int bit = 4; bit >= 0; --bit)  // from the top bit down: does a lane that ties so far hold it?
+                    if (__ballot((mine >> bit) == ((most >> bit) | 1))) most |= 1 << bit;
+            }
+#pragma unroll
+            for (int e = 0; e < RC_HALF_ENTRIES; ++e) {
+                if (RC_HALF_ENTRIES * h + e < most) {  // (wave-uniform; the lanes past their own count are predicated off)
+                    const int pos = (int)((w[(1 + e) >> 2] >> (8 * ((1 + e) & 3))) & (RC_DP - 1));
+                    if (RC_HALF_ENTRIES * h + e < mine) c = __builtin_fmaf(qs[pos], __uint_as_float(w[4 + e]), c);
+                }
+            }
+        }
+    }
+    for (int b = 0; b * ROWS < KP; ++b) {
+        const unsigned bm = (unsigned)(densemask >> (ROWS * b)) & (unsigned)((1ull << ROWS) - 1ull);
         if (!bm) continue;  // (wave-uniform)
-        int trow[RERANK_ROWS / 2];
+        int trow[ROWS / 2];
 #pragma unroll
-        for (int it = 0; it < RERANK_ROWS / 2; ++it) trow[it] = __shfl(tidx, RERANK_ROWS * b + 2 * it + half) - t_base;
+        for (int it = 0; it < ROWS / 2; ++it) trow[it] = __shfl(tidx, ROWS * b + 2 * it + half) - t_base;
         for (int ch = 0; ch < DP / 128; ++ch) {
-            f32x4 v[RERANK_ROWS / 2];
+            f32x4 v[ROWS / 2];
 #pragma unroll
-            for (int it = 0; it < RERANK_ROWS / 2; ++it) {
+            for (int it = 0; it < ROWS / 2; ++it) {
                 v[it] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
                 if ((bm >> (2 * it + half)) & 1u)
                     v[it] = *reinterpret_cast<const f32x4 *>(That + (size_t)trow[it] * DP + ch * 128 + l5 * 4);
             }
 #pragma unroll
-            for (int it = 0; it < RERANK_ROWS / 2; ++it)
+            for (int it = 0; it < ROWS / 2; ++it)
                 *reinterpret_cast<f32x4 *>(rows + (2 * it + half) * RERANK_STRIDE + l5 * 4) = v[it];
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the wave's own LDS writes, read by its other lanes)
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (half == b && need) {
-                const f32x4 *tp = reinterpret_cast<const f32x4 *>(rows + l5 * RERANK_STRIDE);
+            if (lane / ROWS == b && ((densemask >> lane) & 1ull)) {
+                const f32x4 *tp = reinterpret_cast<const f32x4 *>(rows + (lane % ROWS) * RERANK_STRIDE);
                 const f32x4 *qp = reinterpret_cast<const f32x4 *>(Qhat + (size_t)q * DP + ch * 128);
 #pragma unroll
                 for (int g = 0; g < 16; ++g) {  // canonical chain: components 8g .. 8g+7 of this chunk, in the kernels' order

@@ -58,7 +58,34 @@ struct WsEnv {
     size_t (*order_sort_tmp)(size_t rows);    // radix sort of `rows` (u64, int) pairs over 40 key bits
     size_t (*class_tables_tmp)(size_t rows);  // the larger of: radix sort of `rows` pairs over 64 bits, inclusive int scan
     int live_mode = FDR_LIVE_AUTO;            // fdr_set_live_chunks
+    int compact_mode = FDR_COMPACT_AUTO;      // fdr_set_rerank_compact
 };
+
+// The compact records of the target rows (to_half_compact_kernel writes them, knn_rerank_kernel reads them;
+// DESIGN.md section 5).  One record of RC_HALVES 64-byte halves per row; half h holds entries RC_HALF_ENTRIES * h ..
+// of the row's non-zero components in canonical-chain order: byte 1 + e the position of entry e in the row as stored,
+// the float at byte 16 + 4 e its value; byte 0 of half 0 is the row's number of non-zeros, and a count above
+// RC_ENTRIES marks the row long (no entry of such a record is used).  A half is loaded whole; bytes the count does not
+// cover are never used (the position is masked, the fmaf predicated off), so they may hold anything.
+#ifndef RC_HALVES
+#define RC_HALVES 2  // (1: the 64-byte form; docs/experiments.md A-32 has both forms' numbers)
+#endif
+#define RC_HALF_ENTRIES 12
+#define RC_ENTRIES (RC_HALF_ENTRIES * RC_HALVES)
+#define RC_BYTES (64 * RC_HALVES)
+#define RC_DP 128  // the one width the records serve: positions are bytes
+// FDR_COMPACT_AUTO_ON: whether AUTO builds and reads the records where the width allows -- decided by measurement,
+// docs/experiments.md A-32.
+#define FDR_COMPACT_AUTO_ON 1
+static bool rerank_compact_wanted(int compact_mode, int dp) {  // are the records built?
+    if (compact_mode == FDR_COMPACT_OFF || dp != RC_DP) return false;
+    return compact_mode == FDR_COMPACT_FORCE || FDR_COMPACT_AUTO_ON;
+}
+// ... and read: under AUTO only while at most one target row in RC_LONG_SHARE is long.  A query of ~23 needed candidates
+// then has no long one, and skips the dense route, about every second time; at 100 k reads (17.8 % long rows) nearly every
+// query ran both routes and the step lost 1 % (A-32).
+#define RC_LONG_SHARE 32
+// The test is knn_rerank_kernel's own, on the count the build left on the device: n_long <= nt / RC_LONG_SHARE.
 
 // The live-chunk candidate pass (knn_prefilter_live.inc).  FDR_LIVE_AUTO_ON: whether AUTO takes it where it applies --
 // decided by measurement, docs/experiments.md A-22: 96.5 -> 70.9 ms per step at 1 M reads, so it does.
@@ -151,6 +178,9 @@ struct PrefilterWs {
     ws_half *live_hq;
     int *live_perm;
     unsigned *live_tau;
+    // compact re-rank only (else null): one RC_BYTES record per target row; its build counts the long rows in
+    // counter[8] (zeroed with the other counters, read back with them)
+    uint8_t *rc;
 };
 
 static PrefilterWs prefilter_ws(const WsEnv &env, void *base, int64_t nq, int64_t nt, int d, int k,
@@ -220,6 +250,7 @@ static PrefilterWs prefilter_ws(const WsEnv &env, void *base, int64_t nq, int64_
         L.live_perm = A.take<int>(nqb * 256);
         L.live_tau = A.take<unsigned>(nqb * 256);
     }
+    if (rerank_compact_wanted(env.compact_mode, dp)) L.rc = A.take<uint8_t>((size_t)nt * RC_BYTES);
     L.total = A.at;
     return L;
 }

@@ -455,6 +455,17 @@ int fdr_set_live_chunks(fdr_ctx *ctx, int mode);
 #define FDR_SKIP_AUTO 0
 #define FDR_SKIP_OFF 1
 int fdr_set_live_skip(fdr_ctx *ctx, int mode);
+/* Compact re-rank (DESIGN.md sections 5 and 6): where the padded width is 128 (d <= 128) the prefilter mode keeps, beside the fp16 copies, one
+ * fixed-size record per target row that lists the row's non-zero components in the order of the canonical chain, and
+ * the certificate kernel re-ranks a candidate from its record; a row with more non-zeros than a record holds takes
+ * the dense route (its whole fp32 row) -- the same bits either way.  AUTO (default): the records are built wherever
+ * the width allows and read unless more than 1 target row in 32 is too long for its record (then nearly every query
+ * would run both routes).  OFF: no records are built and every candidate takes the dense route (the parity tests,
+ * A/B measurements).  FORCE: built and read wherever the width allows, however many rows are long (the parity tests). */
+#define FDR_COMPACT_AUTO 0
+#define FDR_COMPACT_OFF 1
+#define FDR_COMPACT_FORCE 2
+int fdr_set_rerank_compact(fdr_ctx *ctx, int mode);
 /* Diagnostics (test support): the stage lists of target segment `segment` of the most recent call that ran the
  * live-chunk pass.  *first_row_out (may be NULL) = the segment's first row in the scan order, *nstages_out = its stages
  * of 128 rows; lens[256] (may be NULL) = per block mask value the number of
@@ -520,6 +531,10 @@ typedef struct fdr_knn_trace {
     int32_t skip_live;             /* 1: its work items walked stage lists that leave disjoint stages out (fdr_set_live_skip) */
     int64_t skip_stages_walked;    /* stages (128 target rows) on the lists of the NL instances' work items (summed by the host) ... */
     int64_t skip_stages_skipped;   /* ... and left out: walked + skipped = the stages of their segments */
+    /* compact re-rank (prefilter only; fdr_set_rerank_compact) */
+    int64_t rerank_compact_long;    /* target rows with more non-zeros than a record holds (counted by the build) */
+    int32_t rerank_compact;         /* 1: knn_rerank_kernel read the records (0: none built, or too many long rows) */
+    int32_t rerank_compact_entries; /* non-zeros a record holds (0: no records were built) */
 } fdr_knn_trace;
 int fdr_last_knn_trace(fdr_ctx *ctx, fdr_knn_trace *out);
 /* Prefilter mode only: number of query rows of the most recent k-NN call whose candidate set could
