@@ -424,46 +424,57 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float *__rest
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-struct DevBuf {
+// The one idea of a buffer that the context has: an array of T that only grows, in device memory (DevArray<T>) or
+// in pinned host memory (PinnedArray<T>).  reserve() counts elements, frees before it allocates and holds at least
+// one byte once it has allocated; ptr() is the one statement of the element type.  Non-copyable.
+template <class T, bool Pinned>
+class GrowArray {
     void *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes) {
+    size_t cap = 0;  // bytes
+
+public:
+    int reserve(size_t count) {
+        const size_t bytes = count * sizeof(T), ask = bytes ? bytes : 1;
         if (bytes <= cap) return FDR_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
+        release();
+        const hipError_t e = Pinned ? hipHostMalloc(&p, ask, hipHostMallocDefault) : hipMalloc(&p, ask);
         if (e != hipSuccess) {
             p = nullptr;
-            return fail(FDR_E_NOMEM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+            return fail(FDR_E_NOMEM, "%s(%zu bytes) failed: %s", Pinned ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
         }
         cap = bytes;
         return FDR_OK;
     }
+    T *ptr() const { return static_cast<T *>(p); }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
         p = nullptr;
         cap = 0;
     }
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }  // (fdr_destroy has made the context's device current)
+    size_t bytes() const { return cap; }  // the capacity
+    GrowArray() = default;
+    GrowArray(const GrowArray &) = delete;
+    GrowArray &operator=(const GrowArray &) = delete;
+    ~GrowArray() { release(); }  // (fdr_destroy has made the context's device current)
 };
-
-// A DevBuf of elements of T (the scratch of the k-mer stages and of the sparse index): reserve() counts elements and
-// ptr() is the one statement of the element type.  Non-copyable through its member.
 template <class T>
-struct DevArray {
-    DevBuf buf;
-    int reserve(size_t count) { return buf.reserve(count * sizeof(T)); }
-    T *ptr() const { return static_cast<T *>(buf.p); }
-    void release() { buf.release(); }
-    size_t bytes() const { return buf.cap; }  // the capacity
-};
+using DevArray = GrowArray<T, false>;
+template <class T>
+using PinnedArray = GrowArray<T, true>;
 template <class... A>
 static void release_all(A &...arrays) {
     (arrays.release(), ...);
+}
+
+// `count` elements between the host and a device array: one hipMemcpyAsync, whose size and types the array states.
+// Neither reserves nor synchronises.
+template <class T>
+static hipError_t upload(const DevArray<T> &to, const T *src, size_t count, hipStream_t st) {
+    return hipMemcpyAsync(to.ptr(), src, count * sizeof(T), hipMemcpyHostToDevice, st);
+}
+template <class T>
+static hipError_t download(T *dst, const DevArray<T> &from, size_t count, hipStream_t st) {
+    return hipMemcpyAsync(dst, from.ptr(), count * sizeof(T), hipMemcpyDeviceToHost, st);
 }
 
 // A rocprim algorithm on temporary storage that the context owns.  `call(tmp, bytes)` makes the rocprim call with these
@@ -495,31 +506,6 @@ static int rocprim_run(DevArray<char> &tmp, const char *what, const F &call) {
     return FDR_OK;
 }
 
-// DevBuf's pinned twin on the host
-struct PinnedBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return FDR_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return fail(FDR_E_NOMEM, "hipHostMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        }
-        cap = bytes;
-        return FDR_OK;
-    }
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf &) = delete;
-    PinnedBuf &operator=(const PinnedBuf &) = delete;
-    ~PinnedBuf() {
-        if (p) (void)hipHostFree(p);
-    }
-};
-
 // What the last k-NN call did, for the fdr_last_* getters.
 struct KnnCallRecord {
     struct {
@@ -535,13 +521,6 @@ struct KnnCallRecord {
         hipStream_t stream = nullptr;
     } paths;
     fdr_knn_trace trace = {};  // fdr_last_knn_trace: the kernels the call ran
-    // fdr_last_live_stage_lists: the geometry of the live-chunk pass's stage lists (the lists themselves: cap.lists)
-    struct {
-        int nseg = 0;  // 0: nothing recorded
-        int nt = 0;
-        SegBounds segs;
-        hipStream_t stream = nullptr;
-    } skip;
 };
 
 // The arguments of a k-NN call: nq query rows against nt target rows numbered from t_base, k neighbours each.
@@ -560,7 +539,7 @@ struct KnnArgs {
     hipStream_t st;
 };
 
-// The three stages beside the dense path own their device scratch and the state that describes it: release() frees
+// Every stage owns its device scratch and the state that describes it, in one struct of the context: release() frees
 // the one and resets the other in the same place, so neither outlives the other.
 
 // fdr_kmer_search / fdr_kmer_search_indices (kmer_search.inc)
@@ -635,7 +614,7 @@ struct SparseIndex {
     DevArray<float> xhat;            // ... normalised (cosine); as the postings take them (weighted Jaccard)
     DevArray<int> asize;             // [n] the rows' set sizes (Jaccard)
     DevArray<float> mass;            // [n] the rows' fp32 sums of values (weighted Jaccard)
-    DevArray<unsigned char> zero;    // [n] zero (Jaccard: empty) rows; the index's own, ctx->zero belongs to the dense calls
+    DevArray<unsigned char> zero;    // [n] zero (Jaccard: empty) rows
     DevArray<u64> keys, sorted_keys; // S1's posting keys (feature << 32 | row); sorted.  `keys`: see run_flags()
     DevArray<unsigned> pos, sorted_pos;  // each key's stored entry, the sort's values; sorted.  `pos`: see posting_rows()
     DevArray<int> efeat;             // each stored entry's run (-1: no posting)
@@ -793,6 +772,107 @@ struct TopkMergeScratch {
     void release() { release_all(idx_parts, dist_parts, idx_out, dist_out, refusal); }
 };
 
+// The projection that fdr_projection_load left for launch_embed (K1's tables, see embed_csr_kernel), fdr_csr_compact
+// and the upload scheduler (the bitmap's host copy).
+struct Projection {
+    DevArray<uint2> ftab;          // [ceil(n_features / 32)] bitmap word, prefix
+    DevArray<uint4> crow;          // [p_rows] the non-empty rows' records (the kernel's rowinfo)
+    DevArray<uint2> ent;           // the entries beyond a row's first
+    std::vector<uint32_t> h_bits;  // host copy of ftab's bitmap words
+    long long n_features = 0;
+    int d = 0;
+    long long p_nnz = 0, p_rows = 0;
+    bool loaded() const { return n_features > 0; }
+    // The host builds the tables as plain C++ records (projection_tables.inc, shared with the sanitizer build); the
+    // kernel reads the same bytes as uint2 / uint4.
+    static const uint2 *as_dev(const PU2 *t) { return reinterpret_cast<const uint2 *>(t); }
+    static const uint4 *as_dev(const PU4 *t) { return reinterpret_cast<const uint4 *>(t); }
+    static_assert(sizeof(PU2) == sizeof(uint2) && sizeof(PU4) == sizeof(uint4), "table records = the kernel's uint2 / uint4");
+    void release() {
+        release_all(ftab, crow, ent);
+        h_bits.clear();
+        n_features = p_nnz = p_rows = 0;
+        d = 0;
+    }
+};
+
+// A host CSR on its way to the device (upload_csr, upload_embed_pipelined and its UploadLink): valid within one call.
+struct CsrUpload {
+    DevArray<int64_t> a_indptr, c_indptr;    // the caller's rows as they are; the chunks the host compacted
+    DevArray<int32_t> a_indices, c_indices;
+    PinnedArray<int32_t> stage_ids;          // the compacted chunks' pinned staging, which the helpers fill
+    PinnedArray<int64_t> stage_ptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // the two raw runs in flight; [2] behind the last copy out of the staging
+    hup::WorkerPool pool;                    // the helpers
+    // Before a pipelined upload reserves or fills anything: the events exist, and the staging is not touched (grown,
+    // or written by this call's helpers) under a copy the last call left in flight.
+    int begin() {
+        for (hipEvent_t &e : ev)
+            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIP_TRY(hipEventSynchronize(ev[2]));
+        return FDR_OK;
+    }
+    void release() {  // (the caller has synchronised the stream and stopped the pool)
+        for (hipEvent_t &e : ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+        release_all(a_indptr, c_indptr, a_indices, c_indices, stage_ids, stage_ptr);
+    }
+};
+
+// The scratch of the calls that take host pointers (fdr_embed, fdr_knn, fdr_embed_knn; fdr_dense_index_build / _embed /
+// _radius_query for E).  Grows as needed, freed with the context; the contents are valid only inside the call that
+// wrote them, so nothing that outlives a call (an index, a held result) may live here.
+struct CallScratch {
+    DevArray<float> E;      // [n, d] the call's rows as uploaded or embedded
+    DevArray<float> Ehat;   // [n, dp] ... normalised (normalize_rows_kernel's layout)
+    DevArray<uint8_t> zero; // [n] ... their all-zero flags
+    DevArray<char> ws;      // the k-NN workspace: bytes, which knn_workspace.inc carves by offset (KnnArgs::ws)
+    void release() { release_all(E, Ehat, zero, ws); }
+};
+// Where a search's [nq, k] results wait for their copy to the host: the dense host-pointer calls (knn_from_device_E)
+// and the sparse index's searches (sp_search_tail) both stage here, each for the length of one call.
+struct ResultStaging {
+    DevArray<int32_t> idx;
+    DevArray<float> dist;
+    void release() { release_all(idx, dist); }
+};
+
+// fdr_set_knn_capture / fdr_last_candidates / fdr_last_range_sets / fdr_last_live_stage_lists (test support): the
+// context's copies of the prefilter pass's intermediate results, taken out of the call's workspace.
+struct KnnCapture {
+    int what = 0;                                  // FDR_CAPTURE_* of fdr_set_knn_capture; survives the calls
+    bool cand_valid = false, range_valid = false;
+    int64_t nq = 0, n_range = 0;
+    int kp = 0, qbits = 0;
+    DevArray<u64> cand;                            // [nq, kp] the merged candidate keys
+    DevArray<int> rq, rcnt, rrows;                 // per range query: id, count, [RANGE_CAP] rows ...
+    DevArray<float> rtheta;                        // ... and threshold
+    hipStream_t stream = nullptr;                  // of the call that wrote these
+    DevArray<uint16_t> lists;                      // the live-chunk pass's stage lists (FDR_CAPTURE_LIVE_LISTS) ...
+    struct {                                       // ... and their geometry
+        int nseg = 0;  // 0: nothing recorded
+        int nt = 0;
+        SegBounds segs;
+        hipStream_t stream = nullptr;
+    } skip;
+    // `count` elements of a call's workspace, device to device, behind the first `at` of one of the arrays
+    template <class T>
+    static hipError_t keep(const DevArray<T> &to, size_t at, const T *from, size_t count, hipStream_t st) {
+        return hipMemcpyAsync(to.ptr() + at, from, count * sizeof(T), hipMemcpyDeviceToDevice, st);
+    }
+    void invalidate() {  // every k-NN entry point, and a prefilter call that failed: the getters refuse
+        cand_valid = range_valid = false;
+        nq = n_range = 0;
+        skip.nseg = 0;
+    }
+    void release() {
+        release_all(cand, rq, rcnt, rrows, rtheta, lists);
+        invalidate();
+    }
+};
+
 struct fdr_ctx {
     int device = 0;
     int num_cus = 256;
@@ -800,18 +880,10 @@ struct fdr_ctx {
     hipStream_t aux_stream[3] = {nullptr, nullptr, nullptr};  // further queues for the prefilter pass's launches
     hipEvent_t aux_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // [0] fork, [1..3] joins
     hipDeviceProp_t prop;
-    // projection
-    long long n_features = 0;
-    int d = 0;
-    long long p_nnz = 0, p_rows = 0;
-    DevBuf ftab, crow, ent;
-    std::vector<uint32_t> h_bits;  // host copy of ftab's bitmap words
-    // scratch for the host-pointer API
-    DevBuf a_indptr, a_indices, E, Ehat, zero, idx, dist, ws;
-    DevBuf c_indptr, c_indices;             // ... the chunks the host compacted (upload_embed_pipelined)
-    PinnedBuf stage_ids, stage_ptr;         // ... their pinned staging
-    hipEvent_t up_ev[3] = {nullptr, nullptr, nullptr};  // ... the two raw runs in flight; [2] behind the last copy out of the staging
-    hup::WorkerPool up_pool;                // ... the helpers
+    Projection proj;       // fdr_projection_load's tables
+    CsrUpload up;          // the host-pointer calls: a CSR on its way to the device ...
+    CallScratch call;      // ... their rows and workspace ...
+    ResultStaging res;     // ... and results, which the sparse searches stage here too
     KmerSearchScratch ks;  // k-mer search, k-mer count / merge (kmer_search.inc): both released at every fetch
     KmerCountScratch kc;
     SparseIndex sp;        // sparse k-NN (knn_sparse.inc): kept until fdr_sparse_index_free
@@ -829,16 +901,7 @@ struct fdr_ctx {
     std::vector<int> skip_host;       // ... and the lengths of the stage lists, [segment][mask value]
     int compact_mode = FDR_COMPACT_AUTO;  // fdr_set_rerank_compact
     KnnCallRecord last;  // what the fdr_last_* getters report
-    // fdr_set_knn_capture / fdr_last_candidates / fdr_last_range_sets: the prefilter pass's intermediate results
-    struct {
-        int what = 0;                    // FDR_CAPTURE_* of fdr_set_knn_capture
-        bool cand_valid = false, range_valid = false;  // (cleared by every k-NN entry point)
-        int64_t nq = 0, n_range = 0;
-        int kp = 0, qbits = 0;
-        DevBuf cand, rq, rtheta, rcnt, rrows;  // ctx-owned copies: [nq, kp] keys; per range query id, theta, count, rows
-        DevBuf lists;                          // ... and the live-chunk pass's stage lists (FDR_CAPTURE_LIVE_LISTS)
-        hipStream_t stream = nullptr;
-    } cap;
+    KnnCapture cap;      // the prefilter pass's intermediate results, where fdr_set_knn_capture asked for them
     // duplicate-row classes built by fdr_knn_classes_dev for the calls that follow it (fdr_knn_unique_dev /
     // fdr_knn_expand_dev): the tables live in the caller's workspace
     struct {
@@ -861,9 +924,7 @@ struct fdr_ctx {
 static void knn_call_begin(fdr_ctx *ctx) {
     ctx->last.trace = fdr_knn_trace{};
     ctx->last.paths = {};
-    ctx->last.skip.nseg = 0;
-    ctx->cap.cand_valid = ctx->cap.range_valid = false;
-    ctx->cap.nq = ctx->cap.n_range = 0;
+    ctx->cap.invalidate();
 }
 
 // the trace's header: a call of `kind` on (dp, k, nq, nt)
@@ -944,9 +1005,8 @@ FDR_EXPORT int fdr_destroy(fdr_ctx *ctx) {
     if (!ctx) return FDR_OK;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    ctx->up_pool.stop();
-    for (hipEvent_t e : ctx->up_ev)
-        if (e) (void)hipEventDestroy(e);
+    ctx->up.pool.stop();
+    ctx->up.release();
     for (int i = 0; i < FDR_NUM_KERNELS; ++i)
         for (hipEvent_t e : ctx->ev_pool[i]) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(ctx->stream);
@@ -1021,7 +1081,8 @@ FDR_EXPORT int fdr_last_candidates(fdr_ctx *ctx, uint64_t *keys, int64_t n_queri
     if (ctx->cap.nq != n_queries || ctx->cap.kp != kp)
         return fail(FDR_E_STATE, "last_candidates: the last k-NN call captured %lld x %d keys, not %lld x %d",
                     (long long)ctx->cap.nq, ctx->cap.kp, (long long)n_queries, kp);
-    HIP_TRY(hipMemcpyAsync(keys, ctx->cap.cand.p, (size_t)n_queries * kp * 8, hipMemcpyDeviceToHost, ctx->cap.stream));
+    static_assert(sizeof(u64) == sizeof(uint64_t), "the ABI's keys are the kernels'");
+    HIP_TRY(download(reinterpret_cast<u64 *>(keys), ctx->cap.cand, (size_t)n_queries * kp, ctx->cap.stream));
     HIP_TRY(hipStreamSynchronize(ctx->cap.stream));
     if (qbits_out) *qbits_out = ctx->cap.qbits;
     return FDR_OK;
@@ -1037,10 +1098,10 @@ FDR_EXPORT int fdr_last_range_sets(fdr_ctx *ctx, int64_t n_range, int32_t *queri
         return fail(FDR_E_STATE, "last_range_sets: the last k-NN call captured %lld range queries, not %lld",
                     (long long)ctx->cap.n_range, (long long)n_range);
     const hipStream_t st = ctx->cap.stream;
-    HIP_TRY(hipMemcpyAsync(queries, ctx->cap.rq.p, (size_t)n_range * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(theta, ctx->cap.rtheta.p, (size_t)n_range * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(counts, ctx->cap.rcnt.p, (size_t)n_range * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(rows, ctx->cap.rrows.p, (size_t)n_range * RANGE_CAP * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(download(queries, ctx->cap.rq, (size_t)n_range, st));
+    HIP_TRY(download(theta, ctx->cap.rtheta, (size_t)n_range, st));
+    HIP_TRY(download(counts, ctx->cap.rcnt, (size_t)n_range, st));
+    HIP_TRY(download(rows, ctx->cap.rrows, (size_t)n_range * RANGE_CAP, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (int64_t i = 0; i < n_range; ++i)  // (the slots the pass did not fill hold whatever the workspace held)
         for (int m = std::max(0, std::min(counts[i], RANGE_CAP)); m < RANGE_CAP; ++m) rows[i * RANGE_CAP + m] = -1;
@@ -1081,7 +1142,7 @@ FDR_EXPORT int fdr_last_live_stage_lists(fdr_ctx *ctx, int32_t segment, int32_t 
                                          int32_t *lens, uint16_t *lists) {
     int rc = use_device(ctx);
     if (rc) return rc;
-    const auto &rec = ctx->last.skip;
+    const auto &rec = ctx->cap.skip;
     if (rec.nseg <= 0)
         return fail(FDR_E_STATE, "last_live_stage_lists: the last k-NN call captured no live-chunk pass's stage lists");
     if (segment < 0 || segment >= rec.nseg || !nstages_out)
@@ -1093,8 +1154,9 @@ FDR_EXPORT int fdr_last_live_stage_lists(fdr_ctx *ctx, int32_t segment, int32_t 
     if (lens) memcpy(lens, ctx->skip_host.data() + (size_t)segment * 256, 256 * sizeof(int));
     if (!lists || nstages == 0) return FDR_OK;
     const int stride = live_list_stride(nstages);
-    HIP_TRY(hipMemcpy2DAsync(lists, (size_t)nstages * 2, static_cast<const uint16_t *>(ctx->cap.lists.p) + (size_t)live_stage_row(t_begin, segment) * 256,
-                             (size_t)stride * 2, (size_t)nstages * 2, 256, hipMemcpyDeviceToHost, rec.stream));
+    const size_t row = (size_t)nstages * sizeof *lists;  // (a list's entries, in bytes)
+    HIP_TRY(hipMemcpy2DAsync(lists, row, ctx->cap.lists.ptr() + (size_t)live_stage_row(t_begin, segment) * 256,
+                             (size_t)stride * sizeof *lists, row, 256, hipMemcpyDeviceToHost, rec.stream));
     HIP_TRY(hipStreamSynchronize(rec.stream));
     for (int v = 0; v < 256; ++v)  // (the entries behind a list's end hold whatever the workspace held)
         for (int i = std::max(0, std::min(ctx->skip_host[(size_t)segment * 256 + v], nstages)); i < nstages; ++i)
@@ -1138,30 +1200,28 @@ FDR_EXPORT int fdr_projection_load(fdr_ctx *ctx, int64_t n_features, int32_t d,
     if ((rc = build_projection_tables(n_features, d, p_indptr, p_cols, p_vals, T))) return rc;
     const std::vector<PU2> &ftab = T.ftab, &ent = T.ent;
     const std::vector<PU4> &crow = T.rowinfo;
-    const int64_t nnz = p_indptr[n_features];
-    const unsigned rows = T.rows;
-    static_assert(sizeof(PU2) == sizeof(uint2) && sizeof(PU4) == sizeof(uint4), "table records = the kernel's uint2 / uint4");
-    if ((rc = ctx->ftab.reserve(ftab.size() * sizeof(uint2)))) return rc;
-    if ((rc = ctx->crow.reserve(crow.size() * sizeof(uint4)))) return rc;
-    if ((rc = ctx->ent.reserve(ent.size() * sizeof(uint2)))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->ftab.p, ftab.data(), ftab.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->crow.p, crow.data(), crow.size() * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->ent.p, ent.data(), ent.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
+    Projection &P = ctx->proj;
+    if ((rc = P.ftab.reserve(ftab.size()))) return rc;
+    if ((rc = P.crow.reserve(crow.size()))) return rc;
+    if ((rc = P.ent.reserve(ent.size()))) return rc;
+    HIP_TRY(upload(P.ftab, P.as_dev(ftab.data()), ftab.size(), ctx->stream));
+    HIP_TRY(upload(P.crow, P.as_dev(crow.data()), crow.size(), ctx->stream));
+    HIP_TRY(upload(P.ent, P.as_dev(ent.data()), ent.size(), ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->n_features = n_features;
-    ctx->d = d;
-    ctx->p_nnz = nnz;
-    ctx->p_rows = rows;
-    ctx->h_bits.resize(ftab.size());  // host copy of the bitmap: fdr_csr_compact
-    for (size_t w = 0; w < ftab.size(); ++w) ctx->h_bits[w] = ftab[w].x;
+    P.n_features = n_features;
+    P.d = d;
+    P.p_nnz = p_indptr[n_features];
+    P.p_rows = T.rows;
+    P.h_bits.resize(ftab.size());  // host copy of the bitmap: fdr_csr_compact
+    for (size_t w = 0; w < ftab.size(); ++w) P.h_bits[w] = ftab[w].x;
     return FDR_OK;
 }
 
 FDR_EXPORT int fdr_csr_compact(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indptr, const int32_t *a_indices,
                                int64_t *out_indptr, int32_t *out_indices, int64_t out_capacity, int32_t n_threads) {
     if (!ctx) return fail(FDR_E_ARG, "null context");
-    if (ctx->n_features <= 0) return fail(FDR_E_STATE, "csr_compact: no projection loaded");
-    return csrc::compact(ctx->h_bits, ctx->n_features, n_rows, a_indptr, a_indices, out_indptr, out_indices,
+    if (!ctx->proj.loaded()) return fail(FDR_E_STATE, "csr_compact: no projection loaded");
+    return csrc::compact(ctx->proj.h_bits, ctx->proj.n_features, n_rows, a_indptr, a_indices, out_indptr, out_indices,
                          out_capacity, n_threads);
 }
 
@@ -1184,19 +1244,19 @@ FDR_EXPORT int fdr_host_unregister(fdr_ctx *ctx, void *ptr) {
 // ---- launches --------------------------------------------------------------------------------
 static int launch_embed(fdr_ctx *ctx, int64_t n_rows, const int64_t *d_indptr,
                         const int32_t *d_indices, float *d_E, hipStream_t st) {
-    if (ctx->n_features <= 0) return fail(FDR_E_STATE, "embed: no projection loaded");
+    const Projection &P = ctx->proj;
+    if (!P.loaded()) return fail(FDR_E_STATE, "embed: no projection loaded");
     if (n_rows < 0) return fail(FDR_E_ARG, "embed: n_rows < 0");
     if (n_rows == 0) return FDR_OK;
-    const int dp = fdr_padded_dim(ctx->d);
+    const int dp = fdr_padded_dim(P.d);
     const long long blocks_needed = (n_rows + 7) / 8;  // (four waves per block, two to eight rows per wave and turn; grid-stride)
     const int grid = (int)std::min<long long>(blocks_needed, (long long)ctx->num_cus * 8 * 4);
     int trc = timing_begin(ctx, FDR_KERNEL_EMBED, st);
     if (trc) return trc;
 #define FDR_LAUNCH_EMBED(DP_)                                                                   \
     hipLaunchKernelGGL(FDR_EMBED_KERNEL<DP_>, dim3(grid), dim3(256), 0, st, (long long)n_rows,  \
-                       (const long long *)d_indptr, d_indices, ctx->n_features,                 \
-                       (const uint2 *)ctx->ftab.p, (const uint4 *)ctx->crow.p,                  \
-                       (const uint2 *)ctx->ent.p, ctx->d, d_E)
+                       (const long long *)d_indptr, d_indices, P.n_features, P.ftab.ptr(),      \
+                       P.crow.ptr(), P.ent.ptr(), P.d, d_E)
 #define FDR_EMBED_KERNEL embed_csr_kernel
     if (dp == 128)
         FDR_LAUNCH_EMBED(128);
@@ -1567,14 +1627,11 @@ int PrefilterCall::pass_live(Rounds &r) {
     HIP_TRY(hipMemcpyAsync(lens.data(), L.live_lens, (size_t)p.nseg * 256 * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (ctx->cap.what & FDR_CAPTURE_LIVE_LISTS) {  // (test support: fdr_last_live_stage_lists)
-        const size_t bytes = live_stage_rows(a.nt) * 256 * sizeof(uint16_t);
-        int crc = ctx->cap.lists.reserve(bytes);
+        const size_t entries = live_stage_rows(a.nt) * 256;
+        int crc = ctx->cap.lists.reserve(entries);
         if (crc) return crc;
-        HIP_TRY(hipMemcpyAsync(ctx->cap.lists.p, L.live_lists, bytes, hipMemcpyDeviceToDevice, st));
-        ctx->last.skip.nseg = p.nseg;
-        ctx->last.skip.nt = (int)a.nt;
-        ctx->last.skip.segs = p.segs;
-        ctx->last.skip.stream = st;
+        HIP_TRY(ctx->cap.keep(ctx->cap.lists, 0, L.live_lists, entries, st));
+        ctx->cap.skip = {p.nseg, (int)a.nt, p.segs, st};
     }
     const LivePlan lp = live_plan(masks.data(), nqb, p.nseg, ctx->live_mode == FDR_LIVE_FORCE ? 0 : p.cohort);
     HIP_TRY(hipMemcpyAsync(L.live_ids, lp.ids.data(), (size_t)nqb * 4, hipMemcpyHostToDevice, st));
@@ -1637,8 +1694,8 @@ int PrefilterCall::certify(PrefilterCounts &n) {
                        (const u64 *)R.partial, p.nseg, (int)nq, p.nq_pad, kp, L.cand);
     HIP_TRY(hipGetLastError());
     if (ctx->cap.what & FDR_CAPTURE_CANDIDATES) {  // (test support: fdr_last_candidates)
-        if ((trc = ctx->cap.cand.reserve((size_t)nq * kp * 8))) return trc;
-        HIP_TRY(hipMemcpyAsync(ctx->cap.cand.p, L.cand, (size_t)nq * kp * 8, hipMemcpyDeviceToDevice, st));
+        if ((trc = ctx->cap.cand.reserve((size_t)nq * kp))) return trc;
+        HIP_TRY(ctx->cap.keep(ctx->cap.cand, 0, L.cand, (size_t)nq * kp, st));
         ctx->cap.nq = nq;
         ctx->cap.kp = kp;
         ctx->cap.qbits = std::min(20, 32 - ib);
@@ -1688,8 +1745,8 @@ int PrefilterCall::range(PrefilterCounts &n) {
     if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
     const bool rcap = ctx->cap.what & FDR_CAPTURE_RANGE;  // (test support: fdr_last_range_sets)
     if (rcap) {
-        if ((trc = ctx->cap.rq.reserve((size_t)rcount * 4)) || (trc = ctx->cap.rtheta.reserve((size_t)rcount * 4)) ||
-            (trc = ctx->cap.rcnt.reserve((size_t)rcount * 4)) || (trc = ctx->cap.rrows.reserve((size_t)rcount * RANGE_CAP * 4)))
+        if ((trc = ctx->cap.rq.reserve((size_t)rcount)) || (trc = ctx->cap.rtheta.reserve((size_t)rcount)) ||
+            (trc = ctx->cap.rcnt.reserve((size_t)rcount)) || (trc = ctx->cap.rrows.reserve((size_t)rcount * RANGE_CAP)))
             return trc;
         ctx->cap.stream = st;
     }
@@ -1712,14 +1769,12 @@ int PrefilterCall::range(PrefilterCounts &n) {
         tr.range_chunks++;
         tr.range_pp_chunks += rsh.family == FDR_FAM_RANGE_PP;
         tr.range_w8_chunks += rs == FDR_R128_W8;
-        if (rcap) {
-            auto keep = [&](const DevBuf &to, const void *from, size_t row_bytes) {  // this chunk's rows, behind the earlier ones
-                return hipMemcpyAsync(static_cast<char *>(to.p) + first * row_bytes, from, cq * row_bytes, hipMemcpyDeviceToDevice, st);
-            };
-            HIP_TRY(keep(ctx->cap.rq, L.rlist + first, 4));
-            HIP_TRY(keep(ctx->cap.rtheta, L.thetac, 4));
-            HIP_TRY(keep(ctx->cap.rcnt, L.cnt, 4));
-            HIP_TRY(keep(ctx->cap.rrows, L.rcand, (size_t)RANGE_CAP * 4));
+        if (rcap) {  // this chunk's rows, behind the earlier ones
+            const KnnCapture &c = ctx->cap;
+            HIP_TRY(c.keep(c.rq, first, L.rlist + first, cq, st));
+            HIP_TRY(c.keep(c.rtheta, first, L.thetac, cq, st));
+            HIP_TRY(c.keep(c.rcnt, first, L.cnt, cq, st));
+            HIP_TRY(c.keep(c.rrows, (size_t)first * RANGE_CAP, L.rcand, (size_t)cq * RANGE_CAP, st));
         }
         hipLaunchKernelGGL(knn_rerank_long_kernel, dim3((unsigned)((cq + 3) / 4)), dim3(256), 0, st,
                            (const int *)(L.rlist + first), cq, (const int *)L.cnt, (const int *)L.rcand, a.k,
@@ -1818,7 +1873,7 @@ static int launch_knn_mode(fdr_ctx *ctx, const KnnArgs &a) {
     const int dp = fdr_padded_dim(a.d);
     if (knn_route(dp, a.k, a.nt) == FDR_ROUTE_FAST && a.nq > 0 && knn_prefilter_wanted(ctx->knn_mode, a.nt, a.k)) {
         const int rc = launch_knn_prefilter(ctx, a);
-        if (rc) ctx->cap.cand_valid = ctx->cap.range_valid = false;  // (a failed call leaves no capture)
+        if (rc) ctx->cap.invalidate();  // (a failed call leaves no capture)
         return rc;
     }
     knn_call_whole(ctx, FDR_PATH_EXACT, FDR_TRACE_EXACT, dp, a.k, a.nq, a.nt);
@@ -2126,12 +2181,12 @@ static int check_csr(int64_t n_rows, const int64_t *a_indptr, const int32_t *a_i
 static int upload_csr(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indptr,
                       const int32_t *a_indices) {
     int rc;
+    CsrUpload &up = ctx->up;
     const int64_t nnz = a_indptr[n_rows];
-    if ((rc = ctx->a_indptr.reserve((size_t)(n_rows + 1) * 8))) return rc;
-    if ((rc = ctx->a_indices.reserve((size_t)std::max<int64_t>(nnz, 1) * 4))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->a_indptr.p, a_indptr, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (nnz > 0)
-        HIP_TRY(hipMemcpyAsync(ctx->a_indices.p, a_indices, (size_t)nnz * 4, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = up.a_indptr.reserve((size_t)(n_rows + 1)))) return rc;
+    if ((rc = up.a_indices.reserve((size_t)std::max<int64_t>(nnz, 1)))) return rc;
+    HIP_TRY(upload(up.a_indptr, a_indptr, (size_t)(n_rows + 1), ctx->stream));
+    if (nnz > 0) HIP_TRY(upload(up.a_indices, a_indices, (size_t)nnz, ctx->stream));
     return FDR_OK;
 }
 
@@ -2146,32 +2201,32 @@ struct UploadLink {
     // rows [r0, r1) as they are, the embed kernel behind them
     int send_raw(int64_t r0, int64_t r1, int slot) {
         hipStream_t st = ctx->stream;
+        const CsrUpload &up = ctx->up;
         const int64_t o = a_indptr[r0], len = a_indptr[r1] - o;
         if (len > 0)
-            HIP_TRY(hipMemcpyAsync((int32_t *)ctx->a_indices.p + o, a_indices + o, (size_t)len * 4, hipMemcpyHostToDevice, st));
-        int erc = launch_embed(ctx, r1 - r0, (const int64_t *)ctx->a_indptr.p + r0, (const int32_t *)ctx->a_indices.p,
-                               d_E + (size_t)r0 * ctx->d, st);
+            HIP_TRY(hipMemcpyAsync(up.a_indices.ptr() + o, a_indices + o, (size_t)len * sizeof *a_indices, hipMemcpyHostToDevice, st));
+        int erc = launch_embed(ctx, r1 - r0, up.a_indptr.ptr() + r0, up.a_indices.ptr(), d_E + (size_t)r0 * ctx->proj.d, st);
         if (erc) return erc;
-        if (slot >= 0) HIP_TRY(hipEventRecord(ctx->up_ev[slot], st));
+        if (slot >= 0) HIP_TRY(hipEventRecord(up.ev[slot], st));
         return FDR_OK;
     }
     int wait_slot(int slot) {
-        HIP_TRY(hipEventSynchronize(ctx->up_ev[slot]));
+        HIP_TRY(hipEventSynchronize(ctx->up.ev[slot]));
         return FDR_OK;
     }
     // what the helpers staged, rows [rb, n_rows): two copies and one launch
     int send_staged(int64_t rb, int64_t used) {
         hipStream_t st = ctx->stream;
-        const int32_t *stage_ids = (const int32_t *)ctx->stage_ids.p;
-        const int64_t *stage_ptr = (const int64_t *)ctx->stage_ptr.p;
+        const CsrUpload &up = ctx->up;
+        const int32_t *stage_ids = up.stage_ids.ptr();
+        const int64_t *stage_ptr = up.stage_ptr.ptr();
         if (used > 0)
-            HIP_TRY(hipMemcpyAsync((int32_t *)ctx->c_indices.p + (stage_cap - used), stage_ids + (stage_cap - used),
-                                   (size_t)used * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync((int64_t *)ctx->c_indptr.p + rb, stage_ptr + rb, (size_t)(n_rows - rb + 1) * 8,
+            HIP_TRY(hipMemcpyAsync(up.c_indices.ptr() + (stage_cap - used), stage_ids + (stage_cap - used),
+                                   (size_t)used * sizeof *stage_ids, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(up.c_indptr.ptr() + rb, stage_ptr + rb, (size_t)(n_rows - rb + 1) * sizeof *stage_ptr,
                                hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(ctx->up_ev[2], st));  // (the next call's helpers write the staging again: it waits for this)
-        return launch_embed(ctx, n_rows - rb, (const int64_t *)ctx->c_indptr.p + rb, (const int32_t *)ctx->c_indices.p,
-                            d_E + (size_t)rb * ctx->d, st);
+        HIP_TRY(hipEventRecord(up.ev[2], st));  // (the next call's helpers write the staging again: it waits for this)
+        return launch_embed(ctx, n_rows - rb, up.c_indptr.ptr() + rb, up.c_indices.ptr(), d_E + (size_t)rb * ctx->proj.d, st);
     }
 };
 
@@ -2179,28 +2234,26 @@ struct UploadLink {
 static int upload_embed_pipelined(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indptr, const int32_t *a_indices,
                                   float *d_E) {
     int rc;
+    CsrUpload &up = ctx->up;
+    const Projection &P = ctx->proj;
     const int64_t nnz = a_indptr[n_rows];
     const hup::Tuning tune;
-    if (nnz < tune.min_ids || ctx->h_bits.empty()) {
+    if (nnz < tune.min_ids || P.h_bits.empty()) {
         if ((rc = upload_csr(ctx, n_rows, a_indptr, a_indices))) return rc;
-        return launch_embed(ctx, n_rows, (const int64_t *)ctx->a_indptr.p, (const int32_t *)ctx->a_indices.p, d_E, ctx->stream);
+        return launch_embed(ctx, n_rows, up.a_indptr.ptr(), up.a_indices.ptr(), d_E, ctx->stream);
     }
-    for (hipEvent_t &e : ctx->up_ev)
-        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    // the staging is not touched (grown, or written by this call's helpers) under a copy the last call left in flight
-    HIP_TRY(hipEventSynchronize(ctx->up_ev[2]));
+    if ((rc = up.begin())) return rc;
     const int64_t stage_cap = hup::Tuning::stage_cap(nnz);
-    if ((rc = ctx->a_indptr.reserve((size_t)(n_rows + 1) * 8))) return rc;
-    if ((rc = ctx->a_indices.reserve((size_t)nnz * 4))) return rc;
-    if ((rc = ctx->c_indptr.reserve((size_t)(n_rows + 1) * 8))) return rc;
-    if ((rc = ctx->c_indices.reserve((size_t)stage_cap * 4))) return rc;
-    if ((rc = ctx->stage_ids.reserve((size_t)stage_cap * 4))) return rc;
-    if ((rc = ctx->stage_ptr.reserve((size_t)(n_rows + 1) * 8))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->a_indptr.p, a_indptr, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = up.a_indptr.reserve((size_t)(n_rows + 1)))) return rc;
+    if ((rc = up.a_indices.reserve((size_t)nnz))) return rc;
+    if ((rc = up.c_indptr.reserve((size_t)(n_rows + 1)))) return rc;
+    if ((rc = up.c_indices.reserve((size_t)stage_cap))) return rc;
+    if ((rc = up.stage_ids.reserve((size_t)stage_cap))) return rc;
+    if ((rc = up.stage_ptr.reserve((size_t)(n_rows + 1)))) return rc;
+    HIP_TRY(upload(up.a_indptr, a_indptr, (size_t)(n_rows + 1), ctx->stream));
     UploadLink link{ctx, n_rows, a_indptr, a_indices, d_E, stage_cap};
-    return hup::upload(tune, n_rows, a_indptr, a_indices, ctx->h_bits.data(), (uint64_t)ctx->n_features,
-                       (int32_t *)ctx->stage_ids.p, (int64_t *)ctx->stage_ptr.p, stage_cap, ctx->up_pool,
-                       hup::Tuning::helpers(host_cpu_budget()), link)
+    return hup::upload(tune, n_rows, a_indptr, a_indices, P.h_bits.data(), (uint64_t)P.n_features, up.stage_ids.ptr(),
+                       up.stage_ptr.ptr(), stage_cap, up.pool, hup::Tuning::helpers(host_cpu_budget()), link)
         .rc;
 }
 
@@ -2209,13 +2262,14 @@ FDR_EXPORT int fdr_embed(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indptr,
     int rc = use_device(ctx);
     if (rc) return rc;
     if ((rc = check_csr(n_rows, a_indptr, a_indices))) return rc;
-    if (ctx->n_features <= 0) return fail(FDR_E_STATE, "embed: no projection loaded");
+    if (!ctx->proj.loaded()) return fail(FDR_E_STATE, "embed: no projection loaded");
     if (n_rows == 0) return FDR_OK;
     if (!E_out) return fail(FDR_E_ARG, "embed: E_out is null");
-    const size_t ebytes = (size_t)n_rows * ctx->d * 4;
-    if ((rc = ctx->E.reserve(ebytes))) return rc;
-    if ((rc = upload_embed_pipelined(ctx, n_rows, a_indptr, a_indices, (float *)ctx->E.p))) return rc;
-    HIP_TRY(hipMemcpyAsync(E_out, ctx->E.p, ebytes, hipMemcpyDeviceToHost, ctx->stream));
+    DevArray<float> &E = ctx->call.E;
+    const size_t ecount = (size_t)n_rows * ctx->proj.d;
+    if ((rc = E.reserve(ecount))) return rc;
+    if ((rc = upload_embed_pipelined(ctx, n_rows, a_indptr, a_indices, E.ptr()))) return rc;
+    HIP_TRY(download(E_out, E, ecount, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FDR_OK;
 }
@@ -2229,20 +2283,20 @@ static int knn_from_device_E(fdr_ctx *ctx, const float *d_E, int64_t n, int d, i
     if (k < 1 || k > FDR_MAX_K) return fail(FDR_E_ARG, "knn: k=%d unsupported (1..%d)", k, FDR_MAX_K);
     if (n < k) return fail(FDR_E_ARG, "knn: need n (%lld) >= k (%d)", (long long)n, k);
     if (!idx_out || !dist_out) return fail(FDR_E_ARG, "knn: null output pointer");
-    if ((rc = ctx->Ehat.reserve((size_t)n * dp * 4))) return rc;
-    if ((rc = ctx->zero.reserve((size_t)n))) return rc;
-    if ((rc = ctx->idx.reserve((size_t)n * k * 4))) return rc;
-    if ((rc = ctx->dist.reserve((size_t)n * k * 4))) return rc;
+    CallScratch &cs = ctx->call;
+    ResultStaging &res = ctx->res;
+    if ((rc = cs.Ehat.reserve((size_t)n * dp))) return rc;
+    if ((rc = cs.zero.reserve((size_t)n))) return rc;
+    if ((rc = res.idx.reserve((size_t)n * k))) return rc;
+    if ((rc = res.dist.reserve((size_t)n * k))) return rc;
     const size_t wsb = fdr_knn_workspace_bytes(ctx, n, n, d, k);
-    if ((rc = ctx->ws.reserve(wsb))) return rc;
-    if ((rc = launch_normalize(ctx, d_E, n, d, (float *)ctx->Ehat.p, (uint8_t *)ctx->zero.p, ctx->stream)))
-        return rc;
-    const float *const Ehat = (const float *)ctx->Ehat.p;
-    const uint8_t *const zero = (const uint8_t *)ctx->zero.p;
-    const KnnArgs a = {Ehat, zero, n, Ehat, zero, n, 0, d, k, (int32_t *)ctx->idx.p, (float *)ctx->dist.p, ctx->ws.p, wsb, ctx->stream};
+    if ((rc = cs.ws.reserve(wsb))) return rc;
+    if ((rc = launch_normalize(ctx, d_E, n, d, cs.Ehat.ptr(), cs.zero.ptr(), ctx->stream))) return rc;
+    const KnnArgs a = {cs.Ehat.ptr(), cs.zero.ptr(), n, cs.Ehat.ptr(), cs.zero.ptr(), n, 0, d, k, res.idx.ptr(), res.dist.ptr(),
+                       cs.ws.ptr(), wsb, ctx->stream};
     if ((rc = launch_knn(ctx, a))) return rc;
-    HIP_TRY(hipMemcpyAsync(idx_out, ctx->idx.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dist_out, ctx->dist.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(download(idx_out, res.idx, (size_t)n * k, ctx->stream));
+    HIP_TRY(download(dist_out, res.dist, (size_t)n * k, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FDR_OK;
 }
@@ -2254,9 +2308,9 @@ FDR_EXPORT int fdr_knn(fdr_ctx *ctx, const float *E, int64_t n, int32_t d, int32
     knn_call_begin(ctx);
     if (!E || n <= 0) return fail(FDR_E_ARG, "knn: empty input");
     if (fdr_padded_dim(d) < 0) return fail(FDR_E_ARG, "knn: dimension %d unsupported (1..%d)", d, FDR_MAX_DIM);
-    if ((rc = ctx->E.reserve((size_t)n * d * 4))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->E.p, E, (size_t)n * d * 4, hipMemcpyHostToDevice, ctx->stream));
-    return knn_from_device_E(ctx, (const float *)ctx->E.p, n, d, k, idx_out, dist_out);
+    if ((rc = ctx->call.E.reserve((size_t)n * d))) return rc;
+    HIP_TRY(upload(ctx->call.E, E, (size_t)n * d, ctx->stream));
+    return knn_from_device_E(ctx, ctx->call.E.ptr(), n, d, k, idx_out, dist_out);
 }
 
 FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indptr,
@@ -2266,13 +2320,14 @@ FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indp
     if (rc) return rc;
     knn_call_begin(ctx);
     if ((rc = check_csr(n_rows, a_indptr, a_indices))) return rc;
-    if (ctx->n_features <= 0) return fail(FDR_E_STATE, "embed: no projection loaded");
+    if (!ctx->proj.loaded()) return fail(FDR_E_STATE, "embed: no projection loaded");
     if (n_rows <= 0) return fail(FDR_E_ARG, "embed_knn: empty input");
-    const size_t ebytes = (size_t)n_rows * ctx->d * 4;
-    if ((rc = ctx->E.reserve(ebytes))) return rc;
-    if ((rc = upload_embed_pipelined(ctx, n_rows, a_indptr, a_indices, (float *)ctx->E.p))) return rc;
-    if (E_out) HIP_TRY(hipMemcpyAsync(E_out, ctx->E.p, ebytes, hipMemcpyDeviceToHost, ctx->stream));
-    return knn_from_device_E(ctx, (const float *)ctx->E.p, n_rows, ctx->d, k, idx_out, dist_out);
+    DevArray<float> &E = ctx->call.E;
+    const size_t ecount = (size_t)n_rows * ctx->proj.d;
+    if ((rc = E.reserve(ecount))) return rc;
+    if ((rc = upload_embed_pipelined(ctx, n_rows, a_indptr, a_indices, E.ptr()))) return rc;
+    if (E_out) HIP_TRY(download(E_out, E, ecount, ctx->stream));
+    return knn_from_device_E(ctx, E.ptr(), n_rows, ctx->proj.d, k, idx_out, dist_out);
 }
 
 #include "knn_sparse.inc"  // S1 .. S4: exact cosine / Jaccard k-NN on sparse feature rows (fdr_knn_sparse[_metric])

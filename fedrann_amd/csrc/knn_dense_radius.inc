@@ -313,9 +313,9 @@ FDR_EXPORT int fdr_dense_index_build(fdr_ctx *ctx, const float *E, int64_t n, in
     if (d < 1 || d > FDR_FAST_MAX_DIM)
         return fail(FDR_E_ARG, "dense_index_build: d = %d is outside [1, %d], the reach of the fp16 passes (the dense index "
                     "has no other path)", d, FDR_FAST_MAX_DIM);
-    if ((rc = ctx->E.reserve((size_t)n * d * 4))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->E.p, E, (size_t)n * d * 4, hipMemcpyHostToDevice, ctx->stream));
-    return dr_index_from_device_E(ctx, (const float *)ctx->E.p, n, d);
+    if ((rc = ctx->call.E.reserve((size_t)n * d))) return rc;
+    HIP_TRY(upload(ctx->call.E, E, (size_t)n * d, ctx->stream));
+    return dr_index_from_device_E(ctx, ctx->call.E.ptr(), n, d);
 }
 
 FDR_EXPORT int fdr_dense_index_embed(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indptr, const int32_t *a_indices) {
@@ -323,15 +323,16 @@ FDR_EXPORT int fdr_dense_index_embed(fdr_ctx *ctx, int64_t n_rows, const int64_t
     if (rc) return rc;
     dr_index_reset(ctx->di);
     if ((rc = check_csr(n_rows, a_indptr, a_indices))) return rc;
-    if (ctx->n_features <= 0) return fail(FDR_E_STATE, "dense_index_embed: no projection loaded");
+    if (!ctx->proj.loaded()) return fail(FDR_E_STATE, "dense_index_embed: no projection loaded");
     if (n_rows < 1 || n_rows > INT32_MAX)
         return fail(FDR_E_ARG, "dense_index_embed: n_rows (%lld) must be in [1, 2^31)", (long long)n_rows);
-    if (ctx->d > FDR_FAST_MAX_DIM)
+    const int d = ctx->proj.d;
+    if (d > FDR_FAST_MAX_DIM)
         return fail(FDR_E_ARG, "dense_index_embed: d = %d is outside [1, %d], the reach of the fp16 passes (the dense index "
-                    "has no other path)", ctx->d, FDR_FAST_MAX_DIM);
-    if ((rc = ctx->E.reserve((size_t)n_rows * ctx->d * 4))) return rc;
-    if ((rc = upload_embed_pipelined(ctx, n_rows, a_indptr, a_indices, (float *)ctx->E.p))) return rc;
-    return dr_index_from_device_E(ctx, (const float *)ctx->E.p, n_rows, ctx->d);
+                    "has no other path)", d, FDR_FAST_MAX_DIM);
+    if ((rc = ctx->call.E.reserve((size_t)n_rows * d))) return rc;
+    if ((rc = upload_embed_pipelined(ctx, n_rows, a_indptr, a_indices, ctx->call.E.ptr()))) return rc;
+    return dr_index_from_device_E(ctx, ctx->call.E.ptr(), n_rows, d);
 }
 
 // what the two radius entries do first: no held result; the index, the radius, the cap
@@ -377,12 +378,12 @@ FDR_EXPORT int fdr_dense_index_radius_query(fdr_ctx *ctx, float radius, int64_t 
     if (!Q) return fail(FDR_E_ARG, "%s: null pointer", who);
     const hipStream_t st = ctx->stream;
     // the queries go the index rows' way: the same upload, the same normalisation, the same fp16 conversion
-    if ((rc = ctx->E.reserve((size_t)nq * di.d * 4))) return rc;
+    if ((rc = ctx->call.E.reserve((size_t)nq * di.d))) return rc;
     if ((rc = di.qhat.reserve((size_t)nq * di.dp))) return rc;
     if ((rc = di.qhalf.reserve((size_t)nq * di.dp))) return rc;
     if ((rc = di.qzero.reserve((size_t)nq))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->E.p, Q, (size_t)nq * di.d * 4, hipMemcpyHostToDevice, st));
-    if ((rc = launch_normalize(ctx, (const float *)ctx->E.p, nq, di.d, di.qhat.ptr(), di.qzero.ptr(), st))) return rc;
+    HIP_TRY(upload(ctx->call.E, Q, (size_t)nq * di.d, st));
+    if ((rc = launch_normalize(ctx, ctx->call.E.ptr(), nq, di.d, di.qhat.ptr(), di.qzero.ptr(), st))) return rc;
     hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)((nq * (di.dp / 8) + 255) / 256)), dim3(256), 0, st,
                        (const float *)di.qhat.ptr(), (long long)nq * (di.dp / 8), di.qhalf.ptr());
     HIP_TRY(hipGetLastError());

@@ -62,8 +62,7 @@
 // The index and its searches.  S1 (S1j), the sort and S2 are the BUILD (fdr_sparse_index_build): what they leave in
 // ctx->sp (struct SparseIndex, fedrann_hip.hip: one typed array per buffer) -- the rows (indptr, each stored entry's
 // run id efeat, xhat (weighted Jaccard: the raw values), the set sizes asize or the masses mass), the postings (runptr,
-// posting_rows(), pval) and the zero flags (zero, the index's own: ctx->zero belongs to the dense calls) -- is the
-// context's one sparse index, described by sp.built; the
+// posting_rows(), pval) and the zero flags (zero) -- is the context's one sparse index, described by sp.built; the
 // build's scratch (keys, sorted_keys, sorted_pos, tmp) is kept with it.  Two arrays change their contents on the way and
 // a third is cut up: the accessors run_flags() / run_numbers(), posting_rows() and zidx() / zdist() of the struct hold
 // the casts and say why the first contents are dead by then.  release() frees the arrays and forgets the index in one
@@ -759,11 +758,11 @@ static int sp_search_tail(fdr_ctx *ctx, const SpQuerySide &qs, int32_t k, int64_
     const int64_t n = sp.built.n;
     u64 h[2] = {0, 0};  // queries that took S3r; zero (empty) rows among the queries
     if (nq > 0) {
-        if ((rc = ctx->idx.reserve((size_t)nq * k * 4))) return rc;
-        if ((rc = ctx->dist.reserve((size_t)nq * k * 4))) return rc;
-        // (the result buffers are the dense calls' untyped ones, shared with them)
-        int *d_idx = static_cast<int *>(ctx->idx.p);
-        float *d_dist = static_cast<float *>(ctx->dist.p);
+        ResultStaging &res = ctx->res;
+        if ((rc = res.idx.reserve((size_t)nq * k))) return rc;
+        if ((rc = res.dist.reserve((size_t)nq * k))) return rc;
+        int *d_idx = res.idx.ptr();
+        float *d_dist = res.dist.ptr();
         if (sp.built.metric == FDR_METRIC_JACCARD)
             rc = sp_search<FDR_METRIC_JACCARD>(ctx, qs, n, k, q0, nq, d_idx, d_dist, h);
         else if (sp.built.metric == FDR_METRIC_WEIGHTED_JACCARD)
@@ -771,8 +770,8 @@ static int sp_search_tail(fdr_ctx *ctx, const SpQuerySide &qs, int32_t k, int64_
         else
             rc = sp_search<FDR_METRIC_COSINE>(ctx, qs, n, k, q0, nq, d_idx, d_dist, h);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(idx_out, d_idx, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(dist_out, d_dist, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(download(idx_out, res.idx, (size_t)nq * k, st));
+        HIP_TRY(download(dist_out, res.dist, (size_t)nq * k, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     fdr_knn_trace &t = ctx->last.trace;

@@ -1,12 +1,16 @@
-"""The k-mer search, the k-mer count / merge and the sparse index own their device scratch and their state (one struct
-each in the context): a context that has run every stage in turn, every buffer regrown at least once on the way,
-gives the bits of a fresh context for every call, and a counting table released by a fetch cannot be resumed."""
+"""Every stage owns its device scratch and its state (one struct each in the context).  The k-mer search, the k-mer
+count / merge and the sparse index: a context that has run every stage in turn, every buffer regrown at least once on
+the way, gives the bits of a fresh context for every call, and a counting table released by a fetch cannot be resumed.
+The dense calls: the result staging that the dense and the sparse searches share, the projection under reloads, and
+the capture across calls, each on one context against fresh ones."""
 import numpy as np
 import pytest
 
 from _kmer_inputs import library_text, random_bases
+from _paths_rows import _paths_input
 from fedrann_amd import _lib
 from fedrann_amd import kmer_search as ks
+from fedrann_amd.precompute import build_precompute_matrix
 from test_gpu_sparse_knn import _hard_rows
 
 pytestmark = pytest.mark.gpu
@@ -135,3 +139,109 @@ def test_a_released_count_cannot_be_resumed():
         c.kmer_count_add(seqs[off[half]:], off[half:] - off[half])
         _same_bits(c.kmer_count_finish(2), want, "count after a refused add")
     assert want[0].size > 0
+
+
+def _fresh(call):
+    with _lib.Context(0) as c:
+        return call(c)
+
+
+def test_result_staging_serves_dense_and_sparse_searches_in_turn():
+    """knn (300 x 5 results) -> a sparse search (2000 x 20: the staging grows under the sparse index's hands) -> the
+    same knn (in the larger staging) -> a search of 40 rows with k = 3 (likewise): each as on a fresh context."""
+    E = np.random.default_rng(11).standard_normal((300, 32)).astype(np.float32)
+    indptr, indices, values = _hard_rows(2000, seed=12, n_ids=400)[:3]
+
+    def index(c):
+        return c.sparse_index(indptr, indices, values, F)
+
+    with _lib.Context(0) as one:
+        first = one.knn(E, 5)
+        sp = index(one)
+        wide = sp.search(20)
+        again = one.knn(E, 5)
+        narrow = sp.search(3, 100, 140)
+    assert wide[0].shape == (2000, 20) and narrow[0].shape == (40, 3)
+    _same_bits(first, _fresh(lambda c: c.knn(E, 5)), "knn")
+    _same_bits(again, first, "knn after the sparse search")
+    _same_bits(wide, _fresh(lambda c: index(c).search(20)), "sparse search")
+    _same_bits(narrow, _fresh(lambda c: index(c).search(3, 100, 140)), "sparse search of a row range")
+
+
+def _projection_and_rows(n_features, d, n_rows, ids_per_row, seed):
+    """(P, indptr, indices): a projection over n_features, and rows of about ids_per_row ascending distinct ids."""
+    rng = np.random.default_rng(seed)
+    P = build_precompute_matrix(rng.integers(1, 50, size=n_features // 2), d)
+    ids = np.sort(rng.integers(0, n_features, size=(n_rows, ids_per_row), dtype=np.int32), axis=1)
+    keep = np.ones(ids.shape, dtype=bool)
+    keep[:, 1:] = ids[:, 1:] != ids[:, :-1]
+    indptr = np.zeros(n_rows + 1, dtype=np.int64)
+    indptr[1:] = np.cumsum(keep.sum(axis=1))
+    return P, indptr, np.ascontiguousarray(ids[keep])
+
+
+def test_projection_reloads():
+    """1 000 features at d = 16, then 50 000 at d = 64 (every table regrows; 1.1 M ids: the pipelined upload, every
+    array of which grows as well), then the first again, in the larger tables: each embed as on a fresh context.  No
+    projection: the state error."""
+    small = _projection_and_rows(1_000, 16, 200, 30, seed=21)
+    large = _projection_and_rows(50_000, 64, 6_000, 190, seed=22)
+    assert large[1][-1] > 1 << 20 > small[1][-1]
+
+    def embed(c, P, indptr, indices):
+        c.projection_load(P.indptr, P.indices, P.data, P.shape[0], P.shape[1])
+        return c.embed(indptr, indices)
+
+    with _lib.Context(0) as one:
+        with pytest.raises(_lib.FedrannHipError, match="no projection loaded"):
+            one.embed(small[1], small[2])
+        got = [embed(one, *p) for p in (small, large, small)]
+    for g, p, what in zip(got, (small, large, small), ("small", "large", "small again")):
+        assert g.shape == (p[1].size - 1, p[0].shape[1]) and np.any(g != 0), what
+        _same_bits([g], [_fresh(lambda c: embed(c, *p))], what)
+
+
+def _captured_call(c, E, k):
+    """A prefilter-mode knn of E with candidate and range capture on, duplicate-row classes off: (idx, dist, keys,
+    range sets).  The range sets in a canonical form: the pass appends queries, and a query's rows, in the order its
+    atomics fall, so queries are sorted and so are the rows of each (none overflows RANGE_CAP here: every set is whole)."""
+    idx, dist = c.knn(E, k)
+    tr = c.last_knn_trace()
+    assert tr["kind"] == "prefilter" and tr["range_queries"] > 0, tr
+    keys, qbits = c.last_candidates(E.shape[0], tr["kp"])
+    rq, theta, cnt, rows = c.last_range_sets(tr["range_queries"])
+    assert 0 < cnt.max() <= _lib.RANGE_CAP
+    order = np.argsort(rq, kind="stable")
+    return idx, dist, keys, np.array([qbits], np.int32), rq[order], theta[order], cnt[order], np.sort(rows[order], axis=1)
+
+
+def test_capture_across_calls():
+    """A captured 9 000-row prefilter call with a range pass, a 300-row exact call (the getters refuse, the arrays
+    stay), the first call again: the same keys and sets, which are a fresh context's too."""
+    E = _paths_input(9_000, 100, seed=31, plateau=(12, 150), overflow=0).cpu().numpy()
+    few = np.random.default_rng(32).standard_normal((300, 100)).astype(np.float32)
+
+    def setup(c):
+        c.set_dedup_mode("off")
+        c.set_knn_capture(_lib.CAPTURE_CANDIDATES | _lib.CAPTURE_RANGE)
+        c.set_knn_mode("prefilter")
+
+    with _lib.Context(0) as one:
+        setup(one)
+        first = _captured_call(one, E, 20)
+        one.set_knn_mode("exact")
+        one.knn(few, 10)
+        assert one.last_knn_trace()["kind"] == "exact"
+        with pytest.raises(_lib.FedrannHipError, match="last_candidates: the last k-NN call captured no candidates"):
+            one.last_candidates(300, 22)
+        with pytest.raises(_lib.FedrannHipError, match="last_range_sets: the last k-NN call captured no range pass"):
+            one.last_range_sets(1)
+        one.set_knn_mode("prefilter")
+        second = _captured_call(one, E, 20)
+    _same_bits(second, first, "the captured call again")
+
+    def fresh(c):
+        setup(c)
+        return _captured_call(c, E, 20)
+
+    _same_bits(first, _fresh(fresh), "the captured call on a fresh context")
