@@ -20,8 +20,10 @@ searches its own); either way overlaps.tsv is the one-GPU file byte for byte.
 k-mer sets by exact Jaccard distance (fdr_knn_sparse_metric), the quantity MinHash tools estimate.
 --no-projection-metric weighted_jaccard: stage 2 builds the IDF weights as for cosine (a negative weight, count > F,
 becomes 0) and stage 4 searches the weighted rows by exact weighted Jaccard (Ruzicka) distance.
---no-projection-radius R (with --no-projection, any metric, one GPU): instead of k neighbours, stage 4 writes every read
-within distance R of each read (0 <= R < 1; fdr_sparse_index_radius_search), a block of rows at a time.
+--no-projection-radius R (with --no-projection, any metric): instead of k neighbours, stage 4 writes every read within
+distance R of each read (0 <= R < 1; fdr_sparse_index_radius_search), a block of rows at a time.  Over several
+--devices only with --sparse-shard targets: each rank indexes its own rows, the ranks exchange query blocks and the
+ragged rows of hits, fdr_radius_merge merges them, and overlaps.tsv is the one-GPU file byte for byte.
 --radius R (the default, projected mode, one GPU, -n <= 512): stage 4 embeds the rows once, keeps them on the device
 (fdr_dense_index_embed) and writes every read within cosine distance R of each read (0 <= R < 1;
 fdr_dense_index_radius_search), a block of rows at a time; --nndescent-n-neighbors is ignored.
@@ -116,14 +118,16 @@ def build_parser():
                    help="With --no-projection and several --devices (required there): what the ranks divide.  targets: "
                         "a rank loads and indexes only its own rows (1 / ranks of the index memory and of the build), "
                         "sees every query and the ranks exchange k candidates per query; needs k <= the rows of every "
-                        "rank.  queries: every rank loads and indexes all rows and searches its own; nothing is "
+                        "rank (with --no-projection-radius: every hit per query, and at least one row on every rank).  "
+                        "queries: every rank loads and indexes all rows and searches its own; nothing is "
                         "exchanged.")
     g.add_argument("--device", type=int, default=None, help="GPU ordinal (default $LOCAL_RANK or 0).")
     g.add_argument("--no-projection-radius", type=float, default=None, metavar="R",
                    help="With --no-projection: instead of the k nearest rows, write every row within distance R of "
                         "each read (0 <= R < 1, under the --no-projection-metric; exact).  overlaps.tsv then holds "
                         "as many lines per read as it has such neighbours, ranked by distance; "
-                        "--nndescent-n-neighbors is ignored.  One GPU only.")
+                        "--nndescent-n-neighbors is ignored.  One GPU, or several --devices with --sparse-shard targets "
+                        "(the ranks' rows of hits are merged exactly: the same file).")
     g.add_argument("--radius", type=float, default=None, metavar="R",
                    help="In the default, projected mode: instead of the k nearest rows, write every row within cosine "
                         "distance R of each read (0 <= R < 1: the distances the k-NN search reports).  overlaps.tsv "
@@ -203,7 +207,8 @@ RADIUS_MAX_HITS = 1 << 26    # ... and the cap on the hits of one device call (8
 
 def check_radius(args, flag, r, needs_no_projection):
     """A radius option (`flag`, its value r; None: not given) against the other options, before any work:
-    --no-projection-radius needs --no-projection, --radius refuses it and is bound to the fp16 passes' dimensions."""
+    --no-projection-radius needs --no-projection, --radius refuses it and is bound to the fp16 passes' dimensions.  Over
+    several --devices only --no-projection-radius with --sparse-shard targets runs (distributed.sparse_radius_sharded)."""
     if r is None:
         return
     if needs_no_projection and not args.no_projection:
@@ -213,7 +218,13 @@ def check_radius(args, flag, r, needs_no_projection):
     if not 0.0 <= np.float32(r) < 1.0:  # (NaN fails both)
         raise SystemExit("%s must be in [0, 1), got %r (every read is within 1 of every other)" % (flag, r))
     if len(device_list(args.devices)) > 1:
-        raise SystemExit("%s runs on one GPU: the radius search is not sharded over --devices" % flag)
+        if not needs_no_projection:
+            raise SystemExit("--radius runs on one GPU: the projected radius search is not sharded over --devices")
+        if args.sparse_shard != "targets":
+            raise SystemExit("--no-projection-radius runs on one GPU, or over --devices with the targets divided: "
+                             "give --sparse-shard targets (%s)"
+                             % ("--sparse-shard queries has no radius form" if args.sparse_shard
+                                else "without --sparse-shard nothing says what to divide"))
     from . import _lib
     if not needs_no_projection and args.embedding_dimension > _lib.FDR_FAST_MAX_DIM:
         raise SystemExit("--radius needs -n/--embedding-dimension <= %d, the reach of the fp16 passes (got %d)"
@@ -557,6 +568,14 @@ def run_rank_worker(args, output_dir, temp_dir):
         args.kmer_searcher_output, args.kmer_library = run_stage1_rank(args, temp_dir, ctx, device, args.dist_backend,
                                                                        cuts, is_fastq, args.input)
     k = args.nndescent_n_neighbors
+    if args.no_projection and args.no_projection_radius is not None:
+        lo, hi, rows = _sparse_rank_radius(args, output_dir, ctx, rank, world,
+                                           join(temp_dir, "overlaps.rank%d.tsv" % rank))
+        logger.debug("rank %d: rows [%d, %d), %d overlap rows", rank, lo, hi, rows)
+        dist.barrier()
+        dist.destroy_process_group()
+        ctx.close()
+        return
     if args.no_projection:
         idx, dst, lo, name_off, names, strands = _sparse_rank_search(args, output_dir, ctx, rank, world, k)
         part = join(temp_dir, "overlaps.rank%d.tsv" % rank)
@@ -627,6 +646,32 @@ def _sparse_rank_search(args, output_dir, ctx, rank, world, k):
                                        world, metric=metric, block_rows=SPARSE_QUERY_BLOCK_ROWS)
     name_off, names = _lib.pack_names(read_names)
     return idx, dst, lo, name_off, names, np.asarray(strand_list, dtype=np.uint8)
+
+
+def _sparse_rank_radius(args, output_dir, ctx, rank, world, part):
+    """Stage 4 of one rank of `--no-projection --no-projection-radius R --devices ... --sparse-shard targets`: the rank
+    loads ITS row block (load_rank_inputs), runs distributed.sparse_radius_sharded (collectives on a gloo group) and
+    writes its rows [lo, hi) of the one-GPU radius search to `part` through fdr_overlaps_write_csr, the header on rank 0
+    only.  RADIUS_BLOCK_ROWS / RADIUS_MAX_HITS bound a device call as on one GPU.  Returns (lo, hi, data lines)."""
+    import torch.distributed as dist
+    from . import _lib
+    from .distributed import sparse_radius_sharded
+    metric = args.no_projection_metric
+    n, lo, hi, ip, ix, n_features, w, name_off, names, strands = load_rank_inputs(args, output_dir, rank, world)
+    dist.barrier()  # every rank has its rows
+    if rank == 0:
+        logger.info("--- 4. Radius search (exact, metric = %s, radius = %g, %d rows, targets over %d GPUs) ---", metric,
+                    args.no_projection_radius, n, world)
+    logger.debug("rank %d of %d holds rows [%d, %d) of %d: %d column ids", rank, world, lo, hi, n, ix.size)
+    try:
+        got = sparse_radius_sharded(ctx, ip, ix, None if w is None else w[ix], n_features, args.no_projection_radius,
+                                    metric=metric, block_rows=RADIUS_BLOCK_ROWS, max_hits=RADIUS_MAX_HITS)
+    except ValueError as e:  # (a rank without rows, a row above the cap: before the file is begun)
+        raise SystemExit("--sparse-shard targets: %s" % e) from None
+    assert got[:2] == (lo, hi)
+    rows = _lib.overlaps_write_csr(part, got[2], got[3], got[4], name_off, names, strands, row0=lo, header=rank == 0,
+                                   n_threads=global_variables.threads if global_variables.threads > 1 else 0)
+    return lo, hi, rows
 
 
 def launch_rank_workers(argv, args, devices, output_dir, temp_dir, keep_intermediates):

@@ -26,7 +26,7 @@ SYMBOLS = (
     "fdr_last_range_sets", "fdr_knn_sparse", "fdr_set_live_chunks", "fdr_knn_sparse_metric",
     "fdr_set_live_skip", "fdr_last_live_stage_lists", "fdr_set_rerank_compact",
     "fdr_sparse_index_build", "fdr_sparse_index_search", "fdr_sparse_index_info", "fdr_sparse_index_free",
-    "fdr_sparse_index_query", "fdr_topk_merge", "fdr_sparse_index_radius_search", "fdr_sparse_index_radius_query",
+    "fdr_sparse_index_query", "fdr_topk_merge", "fdr_radius_merge", "fdr_sparse_index_radius_search", "fdr_sparse_index_radius_query",
     "fdr_sparse_index_radius_fetch", "fdr_overlaps_write_csr",
     "fdr_dense_index_build", "fdr_dense_index_embed", "fdr_dense_index_radius_search", "fdr_dense_index_radius_query",
     "fdr_dense_index_radius_fetch", "fdr_dense_index_info", "fdr_dense_index_free",
@@ -135,6 +135,7 @@ def load_library():
                                        ctypes.POINTER(i32)]
     L.fdr_dense_index_free.argtypes = [vp]
     L.fdr_topk_merge.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp]
+    L.fdr_radius_merge.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp]
     L.fdr_embed_dev.argtypes = [vp, i64, vp, vp, vp, vp]
     L.fdr_normalize_dev.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     L.fdr_knn_workspace_bytes.argtypes = [vp, i64, i64, i32, i32]
@@ -534,6 +535,46 @@ def check_topk_merge(idx_parts, dist_parts, k, out=None):
                 or dist.dtype != np.float32 or not (idx.flags.c_contiguous and dist.flags.c_contiguous):
             raise ValueError("out must be C-contiguous (int32 [nq, k], float32 [nq, k])")
     return n_parts, nq, kp, k
+
+
+def check_radius_merge(parts):
+    """The argument checks of Context.radius_merge (fdr_radius_merge repeats those of the indptrs and the limits);
+    needs no GPU.  parts: a sequence of 1 .. 64 triples (indptr int64 [nq + 1], idx int32 [indptr[-1]], dist float32
+    [indptr[-1]]), C-contiguous 1-D numpy arrays, the same nq in every part; each indptr starts at 0 and never
+    decreases; fewer than 2^31 entries in all.  What the rows hold (ascending keys, distances >= 0 and not NaN, indices
+    >= 0) is checked on the device.  Returns (n_parts, nq, counts int64 [nq]: the merged rows' lengths)."""
+    try:
+        parts = [tuple(p) for p in parts]
+    except TypeError:
+        raise TypeError("parts must be a sequence of (indptr, idx, dist) triples") from None
+    if not 1 <= len(parts) <= TOPK_MERGE_MAX_PARTS:
+        raise ValueError("need 1 <= n_parts <= %d, got %d" % (TOPK_MERGE_MAX_PARTS, len(parts)))
+    for p, part in enumerate(parts):
+        if len(part) != 3:
+            raise ValueError("part %d is not an (indptr, idx, dist) triple" % p)
+        for name, a, dt in zip(("indptr", "idx", "dist"), part, (np.int64, np.int32, np.float32)):
+            if not isinstance(a, np.ndarray) or a.dtype != dt:
+                raise TypeError("part %d: %s must be a numpy %s array" % (p, name, np.dtype(dt)))
+            if a.ndim != 1 or not a.flags.c_contiguous:
+                raise ValueError("part %d: %s must be a C-contiguous 1-D array" % (p, name))
+    nq = parts[0][0].size - 1
+    total = 0
+    for p, (indptr, _, _) in enumerate(parts):
+        if indptr.size != nq + 1 or nq < 0:
+            raise ValueError("part %d: its indptr has %d elements, not nq + 1 = %d" % (p, indptr.size, nq + 1))
+        if indptr[0] != 0 or np.any(np.diff(indptr) < 0):
+            raise ValueError("part %d: its indptr must start at 0 and never decrease" % p)
+        total += int(indptr[-1])
+    if nq > np.iinfo(np.int32).max or total > np.iinfo(np.int32).max:
+        raise ValueError("need fewer than 2^31 queries and fewer than 2^31 entries in all (got %d and %d)" % (nq, total))
+    for p, (indptr, idx, dist) in enumerate(parts):
+        if idx.size != indptr[-1] or dist.size != indptr[-1]:
+            raise ValueError("part %d: idx (%d) and dist (%d) must hold the %d entries its indptr states"
+                             % (p, idx.size, dist.size, int(indptr[-1])))
+    counts = np.zeros(nq, dtype=np.int64)
+    for indptr, _, _ in parts:
+        counts += np.diff(indptr)
+    return len(parts), nq, counts
 
 
 def _row_mass_overflows(indptr, values, largest):
@@ -984,6 +1025,45 @@ class Context:
         self._check(self._L.fdr_topk_merge(self._h, nq, n_parts, kp, k, _ptr(idx_parts), _ptr(dist_parts), _ptr(idx),
                                            _ptr(dist)), "fdr_topk_merge")
         return idx, dist
+
+    def radius_merge(self, parts, max_entries=1 << 26):
+        """The union, per query, of the ragged rows of n_parts ranks: parts is a sequence of (indptr int64 [nq + 1],
+        idx int32, dist float32) as SparseIndex.radius_query returns them, each row ascending by (distance bits, index),
+        the indices global and distinct across a query's parts.  Returns (indptr int64 [nq + 1], idx int32, dist
+        float32): distributed.merge_sparse_radius of the parts bit for bit, merged on the GPU (fdr_radius_merge).  The
+        queries go to the device in consecutive pieces whose merged rows hold at most max_entries entries (16 device
+        bytes each); one query with more is a ValueError, and so are a bad indptr, 2^31 entries or more in all and
+        more than 64 parts, all before the library is called.  A row out of order, a negative or NaN distance and a
+        negative index are refused (FedrannHipError) by the piece that holds them.  The context's sparse index, its
+        held radius result and its last k-NN trace stay as they are."""
+        n_parts, nq, counts = check_radius_merge(parts)
+        if isinstance(max_entries, bool) or not isinstance(max_entries, (int, np.integer)) \
+                or not 1 <= int(max_entries) < 2 ** 31:
+            raise ValueError("max_entries must be an integer in [1, 2^31), got %r" % (max_entries,))
+        # (everything in one piece: the common case, without the walk over the counts)
+        pieces = [(0, nq)] if int(counts.sum()) <= int(max_entries) else radius_pieces(counts, int(max_entries))
+        if pieces is None:
+            q = int(np.argmax(counts > max_entries))
+            raise ValueError("query %d alone has %d entries over the parts, above max_entries = %d"
+                             % (q, int(counts[q]), max_entries))
+        out_ip = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum(counts, out=out_ip[1:])
+        idx = np.empty(int(out_ip[-1]), dtype=np.int32)
+        dist = np.empty(int(out_ip[-1]), dtype=np.float32)
+        for a, b in pieces:
+            ip_parts = np.stack([p[0][a:b + 1] - p[0][a] for p in parts])
+            if len(pieces) == 1 and n_parts == 1:
+                ix_parts, ds_parts = parts[0][1], parts[0][2]
+            else:
+                ix_parts = np.concatenate([p[1][p[0][a]:p[0][b]] for p in parts])
+                ds_parts = np.concatenate([p[2][p[0][a]:p[0][b]] for p in parts])
+            ip = np.full(b - a + 1, -1, dtype=np.int64)
+            lo, hi = int(out_ip[a]), int(out_ip[b])
+            self._check(self._L.fdr_radius_merge(self._h, b - a, n_parts, _ptr(ip_parts), _ptr(ix_parts), _ptr(ds_parts),
+                                                 _ptr(ip), _ptr(idx[lo:hi]), _ptr(dist[lo:hi])), "fdr_radius_merge")
+            if not np.array_equal(ip, out_ip[a:b + 1] - lo):
+                raise FedrannHipError("fdr_radius_merge: the queries [%d, %d) came back with another indptr" % (a, b))
+        return out_ip, idx, dist
 
     def embed_knn(self, a_indptr, a_indices, k, return_embedding=False, out=None):
         """out=(idx int32 [n,k], dist float32 [n,k]): caller-owned (e.g. pinned, reused) result arrays."""

@@ -772,6 +772,22 @@ struct TopkMergeScratch {
     void release() { release_all(idx_parts, dist_parts, idx_out, dist_out, refusal); }
 };
 
+// fdr_radius_merge (radius_merge.inc): the ragged parts as uploaded, where their rows start, the merged rows before
+// they are copied out, and the record of a refused call.  Grows as needed; freed with the context.
+struct RadiusMergeScratch {
+    DevArray<int> starts;             // [n_parts, nq + 1] row (p, q)'s first entry in idx_parts / dist_parts
+    DevArray<int> indptr_out;         // [nq + 1] the merged rows' first entries
+    DevArray<int2> items;             // the kernel's work items: (query, chunk of 64 of its entries)
+    DevArray<int> idx_parts;          // the parts' entries, concatenated in part order: the indices ...
+    DevArray<float> dist_parts;       // ... and the distances
+    DevArray<int> idx_out;            // the merged rows
+    DevArray<float> dist_out;
+    DevArray<u64> refusal;            // [1] the smallest (query, part, rule) the check found; all ones: none
+    std::vector<int> h_starts, h_indptr_out;  // the host's side of starts and indptr_out (built from the checked indptrs)
+    std::vector<int2> h_items;                // ... and of items
+    void release() { release_all(starts, indptr_out, items, idx_parts, dist_parts, idx_out, dist_out, refusal); }
+};
+
 // The projection that fdr_projection_load left for launch_embed (K1's tables, see embed_csr_kernel), fdr_csr_compact
 // and the upload scheduler (the bitmap's host copy).
 struct Projection {
@@ -891,6 +907,7 @@ struct fdr_ctx {
     SparseRadius spr;      // ... and the radius searches' counts and hits (knn_sparse_radius.inc), released with it
     DenseIndex di;         // the dense index and its radius searches (knn_dense_radius.inc): kept until fdr_dense_index_free
     TopkMergeScratch tm;   // the merge of the ranks' candidate lists (topk_merge.inc): kept until fdr_destroy
+    RadiusMergeScratch rm; // the merge of the ranks' ragged radius rows (radius_merge.inc): kept until fdr_destroy
     // timing: when enabled, every launch of kernel kind i gets its own hipEvent pair on the launch
     // stream; fdr_timing_read() sums the elapsed times of all launches since the last read
     int knn_mode = FDR_MODE_AUTO;
@@ -2335,6 +2352,7 @@ FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indp
 #include "knn_sparse_radius.inc"  // R1 .. R3: every row within a distance bound (fdr_sparse_index_radius_*)
 #include "knn_dense_radius.inc"  // D-R1 .. D-R3: the same on the projected rows, through the fp16 range pass (fdr_dense_index_*)
 #include "topk_merge.inc"  // T1: the exact merge of the ranks' candidate lists of a target-sharded sparse search
+#include "radius_merge.inc"  // M1: the exact merge of the ranks' ragged rows of a target-sharded sparse radius search
 #include "kmer_search.inc"
 #include "kmer_output_loader.inc"
 #include "reads_parser.inc"

@@ -246,6 +246,65 @@ def merge_sparse_topk(parts, k):
     return np.take_along_axis(idx, order, axis=1), np.take_along_axis(dist, order, axis=1)
 
 
+def sparse_radius_target_shard(ctx, indptr, indices, values, n_features, radius, rank, world, metric="cosine",
+                               block_rows=None, max_hits=1 << 26):
+    """This rank's part of SparseIndex.radius_search(radius) on the whole CSR with the TARGETS divided: (lo, hi, indptr
+    int64 [n + 1], idx int32, dist float32), for EVERY row of the CSR the rank's own rows [lo, hi) of shard_rows(n,
+    world) within `radius` of it, in (distance bits, index) order, indices global.  The rank builds the index of its
+    own rows only (local_csr, the values sliced alongside) and asks it about all n rows with SparseIndex.radius_query,
+    in blocks of at most block_rows query rows (None: one block), max_hits capping the hits of one device call; the
+    shard's first row is added to the indices.  merge_sparse_radius of the ranks' (indptr, idx, dist) is the one-GPU
+    answer bit for bit.  No collective and no process group: a caller on several GPUs gathers the parts itself.  There
+    is no k, so no rank is too small to answer, but every rank that is asked needs at least one row (the index does);
+    the index is freed before the call returns."""
+    n, F = _lib.check_sparse_csr(indptr, indices, values, n_features, metric=metric)
+    _lib.check_sparse_radius(radius, max_hits)
+    lo, hi, _ = sparse_rank_blocks(n, rank, world)
+    if hi == lo:
+        raise ValueError("rank %d of %d holds no rows of %d: the sparse index needs at least one" % (rank, world, n))
+    ip, ix = local_csr(indptr, indices, lo, hi)
+    vals = None if values is None else np.ascontiguousarray(values[indptr[lo]:indptr[hi]])
+    with ctx.sparse_index(ip, ix, vals, F, metric=metric) as index:
+        out_ip, idx, dist = index.radius_query(indptr, indices, values, radius, block_rows=block_rows,
+                                               max_hits=max_hits)
+    idx += np.int32(lo)
+    return lo, hi, out_ip, idx, dist
+
+
+def merge_sparse_radius(parts):
+    """Every target within the radius per query over the ranks' ragged rows: parts is a sequence of (indptr int64
+    [nq + 1], idx int32 [indptr[-1]], dist float32 [indptr[-1]]), each rank's result for the same nq queries with
+    global, pairwise distinct target indices; returns (indptr int64 [nq + 1], idx int32, dist float32), indptr the
+    sum of the parts' indptrs and row q the union of the parts' rows q, ascending by (distance bits as uint32, index).
+    Plain numpy.
+
+    This is exact.  Every rule of the sparse radius search is "EVERY target whose key is within the bound, under ONE
+    total order of the targets", the order by (distance bits, index): a row holds the targets at distance <= radius in
+    that order, and the closed form of a zero query (zero norm, empty set, zero mass) is the index's zero rows at
+    distance 0 in index order and nothing else (every other row is at 1 > radius).  A target's distance from a query
+    does not depend on which other targets are indexed with it, and whether a row is a zero row is a property of the
+    row alone.  So a rank's row is exactly the targets of the answer that the rank holds, each rank lists its own zero
+    rows at distance 0 for a zero query, and the union of the ranks' rows in key order -- for a zero query all zero
+    rows in index order -- is the row of the whole call bit for bit, whatever the order of the parts.  Equal keys in
+    two parts are a duplicate index, the caller's broken promise: both come out, the earlier part's first."""
+    if not parts:
+        raise ValueError("merge_sparse_radius needs at least one part")
+    ips = [np.asarray(p[0], dtype=np.int64) for p in parts]
+    nq = ips[0].size - 1
+    for ip, p in zip(ips, parts):
+        if ip.ndim != 1 or ip.size != nq + 1 or ip[0] != 0 or np.any(np.diff(ip) < 0) \
+                or np.size(p[1]) != ip[-1] or np.size(p[2]) != ip[-1]:
+            raise ValueError("parts must be (indptr [nq + 1] from 0, never decreasing; idx [indptr[-1]]; dist "
+                             "[indptr[-1]]) triples for the same nq = %d queries" % nq)
+    idx = np.concatenate([np.asarray(p[1], dtype=np.int32).ravel() for p in parts])
+    dist = np.concatenate([np.asarray(p[2], dtype=np.float32).ravel() for p in parts])
+    query = np.concatenate([np.repeat(np.arange(nq, dtype=np.int64), np.diff(ip)) for ip in ips])
+    key = (np.ascontiguousarray(dist).view(np.uint32).astype(np.uint64) << np.uint64(32)) | idx.astype(np.uint32)
+    order = np.lexsort((key, query))  # (stable: equal keys of a query stay in part order)
+    indptr = np.sum(ips, axis=0, dtype=np.int64)
+    return indptr, idx[order], dist[order]
+
+
 def sparse_shard_offsets(counts, k):
     """The ranks' row ranges [(lo, hi), ...] of a target-sharded sparse search from their row counts, in rank order
     (the counts of shard_rows give its blocks back), after the check that every rank can answer k: a rank's list
@@ -354,6 +413,112 @@ def sparse_knn_sharded(ctx, indptr_local, indices_local, values_local, n_feature
     # (5) the index is freed; every rank merges its own rows' lists
     idx, dst = ctx.topk_merge(idx_parts, dist_parts, k)
     return lo, hi, idx, dst
+
+
+def sparse_radius_offsets(counts):
+    """The ranks' row ranges [(lo, hi), ...] of a target-sharded sparse radius search from their row counts, in rank
+    order.  There is no k, so no rank is too small to answer; but the sparse index needs at least one row
+    (Context.sparse_index refuses an empty CSR), so a rank without rows is a ValueError, the same words on every rank,
+    naming the first such rank.  Needs no GPU."""
+    counts = [int(c) for c in counts]
+    if not counts or min(counts) < 0:
+        raise ValueError("need the row count, >= 0, of at least one rank, got %r" % (counts,))
+    if min(counts) == 0:
+        raise ValueError("rank %d of %d holds no rows: a rank of a target-sharded sparse radius search builds the "
+                         "index of its own rows, and the sparse index needs at least one row (use fewer ranks)"
+                         % (counts.index(0), len(counts)))
+    his = np.cumsum(counts).tolist()
+    if his[-1] > np.iinfo(np.int32).max:
+        raise ValueError("need fewer than 2^31 rows in all")
+    return [(hi - c, hi) for c, hi in zip(counts, his)]
+
+
+def sparse_radius_sharded(ctx, indptr_local, indices_local, values_local, n_features, radius, metric="cosine",
+                          group=None, block_rows=None, max_hits=1 << 26):
+    """SparseIndex.radius_search(radius) of the whole CSR over the ranks of a process group with the TARGETS divided,
+    collective included: every rank calls this with ITS rows only (as in sparse_knn_sharded) and gets (lo, hi, indptr
+    int64 [hi - lo + 1], idx int32, dist float32): the rows [lo, hi) of the one-GPU radius search on the concatenated
+    CSR bit for bit, every row within `radius` in (distance bits, index) order, self among them, indices global.
+
+    Rounds, those of sparse_knn_sharded.  (1) One all-gather of (rows, stored entries, values given?) per rank.  (2)
+    The checks, before any GPU work and with the same ValueError on every rank: radius and max_hits
+    (_lib.check_sparse_radius), and sparse_radius_offsets: there is no k and so no k <= smallest-shard condition, but
+    a rank with 0 rows is refused, because the sparse index cannot be built of no rows.  (3) Each rank builds the index
+    of its own rows.  (4) For each source rank s in turn: s broadcasts its block, every rank asks its index about it
+    (SparseIndex.radius_query in blocks of block_rows rows, max_hits capping the hits of one device call) and adds its
+    own lo to the indices; the indptrs, of the fixed shape [rows_s + 1], are gathered to s; the ragged payloads follow
+    point to point (a gather needs equal shapes): every other rank sends its indices, then its distances, and s posts
+    receives of the lengths the indptrs state, rank after rank; an empty payload is not sent.  (5) The index is freed;
+    each rank merges the world's rows of its own queries on its GPU (Context.radius_merge with max_entries = max_hits,
+    exact: merge_sparse_radius's docstring), all ranks at once.
+
+    A rank holds on the host its own block, one foreign block, its answer to a foreign block, and, for its own rows,
+    every rank's hits once as parts and once merged (8 bytes per hit each); never the whole CSR.  On the device it
+    holds 1 / world of the index, one call's hits (max_hits x 16 bytes), and for the merge 16 bytes per entry of a
+    piece.  One row with more than max_hits hits over all ranks is a ValueError of the merge.  Every rank sees every
+    query: the posting walk is divided by the ranks, the upload of the queries is not.  The exchange runs on a gloo
+    group as in sparse_knn_sharded; without an initialised process group the call is the one-rank case."""
+    _lib.sparse_metric_code(metric)
+    n_loc, _, F = _lib._check_sparse(indptr_local, indices_local, values_local, n_features, None, metric, min_rows=0)
+    multi = dist.is_initialized()
+    g = _host_group(group) if multi else None
+    rank, world = (dist.get_rank(g), dist.get_world_size(g)) if multi else (0, 1)
+    src = (lambda s: s if g is None else dist.get_global_rank(g, s))
+    # (1) the row counts
+    mine = torch.tensor([n_loc, indices_local.size, 0 if values_local is None else 1], dtype=torch.int64)
+    every = [torch.empty_like(mine) for _ in range(world)]
+    if multi:
+        dist.all_gather(every, mine, group=g)
+    else:
+        every = [mine]
+    rows, nnz, has_values = (tuple(int(t[c]) for t in every) for c in range(3))
+    if len(set(has_values)) != 1:
+        raise ValueError("the ranks disagree on whether the rows carry values: %r" % (has_values,))
+    # (2) the radius, the cap and the row counts, before any GPU work
+    _lib.check_sparse_radius(radius, max_hits)
+    _lib._check_block_rows(block_rows)
+    lo, hi = sparse_radius_offsets(rows)[rank]
+    parts = [None] * world  # per source rank of the answers to MY rows: (indptr, idx, dist)
+    # (3), (4)
+    with ctx.sparse_index(indptr_local, indices_local, values_local, F, metric=metric) as index:
+        for s in range(world):
+            if s == rank:
+                ip, ix, vals = indptr_local, indices_local, values_local
+            else:
+                ip = np.empty(rows[s] + 1, dtype=np.int64)
+                ix = np.empty(nnz[s], dtype=np.int32)
+                vals = np.empty(nnz[s], dtype=np.float32) if has_values[s] else None
+            if multi:
+                dist.broadcast(torch.from_numpy(ip), src(s), group=g)
+                if nnz[s]:
+                    dist.broadcast(torch.from_numpy(ix), src(s), group=g)
+                    if vals is not None:
+                        dist.broadcast(torch.from_numpy(vals), src(s), group=g)
+            qp, qi, qd = index.radius_query(ip, ix, vals, radius, block_rows=block_rows, max_hits=max_hits)
+            qi += np.int32(lo)
+            if s == rank:
+                parts[rank] = (qp, qi, qd)
+            if multi:
+                ips = np.empty((world, rows[s] + 1), dtype=np.int64) if s == rank else None
+                dist.gather(torch.from_numpy(qp), list(torch.from_numpy(ips).unbind(0)) if s == rank else None,
+                            dst=src(s), group=g)
+                if s == rank:
+                    for r in range(world):
+                        if r == rank:
+                            continue
+                        ri = np.empty(int(ips[r, -1]), dtype=np.int32)
+                        rd = np.empty(int(ips[r, -1]), dtype=np.float32)
+                        if ri.size:
+                            dist.recv(torch.from_numpy(ri), src=src(r), group=g)
+                            dist.recv(torch.from_numpy(rd), src=src(r), group=g)
+                        parts[r] = (ips[r].copy(), ri, rd)
+                elif qi.size:
+                    dist.send(torch.from_numpy(qi), dst=src(s), group=g)
+                    dist.send(torch.from_numpy(qd), dst=src(s), group=g)
+            del ip, ix, vals, qp, qi, qd
+    # (5) the index is freed; every rank merges its own rows' lists
+    indptr, idx, dst = ctx.radius_merge(parts, max_entries=max_hits)
+    return lo, hi, indptr, idx, dst
 
 
 def local_csr(indptr, indices, lo, hi):

@@ -358,6 +358,33 @@ int fdr_dense_index_free(fdr_ctx *ctx);
 int fdr_topk_merge(fdr_ctx *ctx, int64_t nq, int32_t n_parts, int32_t kp, int32_t k, const int32_t *idx_parts,
                    const float *dist_parts, int32_t *idx_out, float *dist_out);
 
+/* ---- merge the ragged rows of a target-sharded sparse radius search  (fedrann_amd.distributed.sparse_radius_sharded:
+ *      every rank indexes its own rows, lists for every query ITS rows within the radius, and the owner of a query block
+ *      merges the ranks' rows) ------------------------------------------------------------------------------------------
+ * indptr_parts int64 [n_parts, nq + 1], PART-MAJOR, each part's starting at 0: part p holds indptr_parts[p][nq] entries,
+ * row q of it at [indptr_parts[p][q], indptr_parts[p][q + 1]).  idx_parts int32 and dist_parts float32: the parts'
+ * entries, concatenated in part order (part p's first entry follows part p - 1's last).  indptr_out int64 [nq + 1],
+ * idx_out int32 and dist_out float32 [the sum of the parts' totals].  Host pointers; the call synchronises.  The key of
+ * an entry is (uint64)distance bits << 32 | (uint32)index; indptr_out[q] is the sum over the parts of indptr_parts[p][q],
+ * and row q of the result is the union of the query's n_parts rows, ascending by key:
+ * fedrann_amd.distributed.merge_sparse_radius bit for bit, whose docstring argues that this is the one-GPU radius
+ * search's row (every target with key <= bound in (distance bits, index) order, a zero query's zero rows at 0 in index
+ * order) when each part is a rank's result for the same queries with global indices.
+ * Checked on the host before anything is uploaded (FDR_E_ARG): each part's indptr starts at 0 and never decreases; the
+ * grand total is below 2^31; 1 <= n_parts <= 64; 0 <= nq < 2^31; a null context, a null indptr pointer, or a null entry
+ * pointer with a total > 0.  Checked on the device before anything is written to the out arrays (FDR_E_ARG,
+ * fdr_last_error names the rule and the smallest (query, part) that breaks one): every index >= 0; every distance a
+ * non-negative, non-NaN float (bits <= 0x7f800000, so bit order is value order); each part's row of each query strictly
+ * ascending by key.  On any refusal indptr_out, idx_out and dist_out are untouched.  NOT checked, the caller's promise:
+ * a query's indices are pairwise distinct across its parts; a key that two parts hold comes out twice, the lower
+ * part's first.  nq == 0 or a total of 0 is FDR_OK with indptr_out written (zeros) and nothing else touched.  The call
+ * touches neither the context's sparse index (its held radius result included) nor fdr_last_knn_trace.  Its device
+ * buffers (16 bytes per entry, 4 per indptr element, 8 per 64 entries of a query) belong to the context, only grow and are freed by fdr_destroy.
+ * Cost: the upload of the parts, plus per entry one binary search in each other part's row of the same query
+ * (no sort: the rows are sorted already); DESIGN.md section 5. */
+int fdr_radius_merge(fdr_ctx *ctx, int64_t nq, int32_t n_parts, const int64_t *indptr_parts, const int32_t *idx_parts,
+                     const float *dist_parts, int64_t *indptr_out, int32_t *idx_out, float *dist_out);
+
 /* ---- device-resident API (multi-GPU host, bench.py) ----------------------------------------
  * All pointers are device pointers; work is enqueued on `stream` (a hipStream_t). */
 int fdr_embed_dev(fdr_ctx *ctx, int64_t n_rows, const int64_t *d_indptr, const int32_t *d_indices,
