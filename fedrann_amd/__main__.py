@@ -27,6 +27,9 @@ ragged rows of hits, fdr_radius_merge merges them, and overlaps.tsv is the one-G
 --radius R (the default, projected mode, one GPU, -n <= 512): stage 4 embeds the rows once, keeps them on the device
 (fdr_dense_index_embed) and writes every read within cosine distance R of each read (0 <= R < 1;
 fdr_dense_index_radius_search), a block of rows at a time; --nndescent-n-neighbors is ignored.
+--rescore METRIC (the default, projected mode, one GPU): stage 4 takes --rescore-candidates K' >= k neighbours per read
+from the projected search, scores exactly those pairs on the feature rows under METRIC (fdr_sparse_rescore: the
+distances of --no-projection --no-projection-metric METRIC, bit for bit) and writes the best k with them.
 
 --devices 0,1,...: every stage is sharded over several GPUs of the node.  The parent process starts one
 child per GPU BEFORE it touches a GPU itself; from reads, every child counts and searches its byte range of
@@ -71,6 +74,7 @@ def _setup_logging(logfile=None):
 
 
 def build_parser():
+    from ._lib import FDR_MAX_K
     p = argparse.ArgumentParser(prog="fedrann", description=__description__,
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("-i", "--input", type=str, required=False, default=None,
@@ -134,6 +138,17 @@ def build_parser():
                         "then holds as many lines per read as it has such neighbours, ranked by distance; "
                         "--nndescent-n-neighbors is ignored.  One GPU only, -n up to 512.  With --no-projection: "
                         "--no-projection-radius.")
+    g.add_argument("--rescore", choices=["cosine", "jaccard", "weighted_jaccard"], default=None,
+                   help="In the default, projected mode: search the projected rows for --rescore-candidates neighbours "
+                        "per read, score exactly those pairs on the feature rows under this metric (the distances "
+                        "--no-projection --no-projection-metric reports, bit for bit) and write the best "
+                        "--nndescent-n-neighbors of them with the exact distances.  One GPU; not with --radius or "
+                        "--no-projection (whose distances are exact already).")
+    g.add_argument("--rescore-candidates", type=int, default=None, metavar="K'",
+                   help="With --rescore: candidates per read taken from the projected search, k <= K' <= min(%d, reads) "
+                        "with k = --nndescent-n-neighbors; by default max(k, min(2 k, 64)), capped by the number of "
+                        "reads.  K' > 64 takes the projected search off its fp16 prefilter (DESIGN.md section 10): a "
+                        "cost cliff, not a slope." % FDR_MAX_K)
     g.add_argument("--devices", type=str, default=None,
                    help="Comma-separated GPU ordinals: shard the rows over these GPUs (one process each).")
     g.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
@@ -229,6 +244,38 @@ def check_radius(args, flag, r, needs_no_projection):
     if not needs_no_projection and args.embedding_dimension > _lib.FDR_FAST_MAX_DIM:
         raise SystemExit("--radius needs -n/--embedding-dimension <= %d, the reach of the fp16 passes (got %d)"
                          % (_lib.FDR_FAST_MAX_DIM, args.embedding_dimension))
+
+
+def default_rescore_candidates(k, n=None):
+    """K' of --rescore where --rescore-candidates is not given: twice k while that stays on the projected search's
+    fp16 prefilter (K' <= 64), never below k, and no more than the n reads there are."""
+    kp = max(k, min(2 * k, 64))
+    return kp if n is None else min(kp, n)
+
+
+def check_rescore(args):
+    """--rescore / --rescore-candidates against the other options, before any work.  Returns K' (None without
+    --rescore); that K' <= the number of reads can only be checked once they are loaded (run_fedrann_pipeline)."""
+    from . import _lib
+    if args.rescore is None:
+        if args.rescore_candidates is not None:
+            raise SystemExit("--rescore-candidates needs --rescore (without it nothing is re-scored)")
+        return None
+    if args.no_projection:
+        raise SystemExit("--rescore is the projected search's second stage; the distances of --no-projection are exact "
+                         "already")
+    if args.radius is not None:
+        raise SystemExit("--rescore re-scores k-NN lists: it does not run with --radius (a radius in the exact metric "
+                         "is --no-projection-radius)")
+    if len(device_list(args.devices)) > 1:
+        raise SystemExit("--rescore runs on one GPU: over --devices a rank holds only its own rows of the feature "
+                         "matrix, and a candidate may be any row")
+    k = args.nndescent_n_neighbors
+    kp = default_rescore_candidates(k) if args.rescore_candidates is None else args.rescore_candidates
+    if not k <= kp <= _lib.FDR_MAX_K:
+        raise SystemExit("--rescore-candidates must be in [--nndescent-n-neighbors = %d, %d], got %d"
+                         % (k, _lib.FDR_MAX_K, kp))
+    return kp
 
 
 def write_radius_overlaps(path, index, radius, read_names, strands, block_rows=None, max_hits=None):
@@ -370,7 +417,8 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                          nndescent_n_neighbors, save_feature_matrix, keep_intermediates, chunk_size,
                          kmer_searcher_output=None, kmer_library=None, feature_matrix=None,
                          kmer_counts=None, read_names_path=None, no_projection=False,
-                         no_projection_metric="cosine", no_projection_radius=None, radius=None):
+                         no_projection_metric="cosine", no_projection_radius=None, radius=None, rescore=None,
+                         rescore_candidates=None):
     """Stages 2-4 of the reference pipeline (__main__.py:329-391) on one GPU.  The embeddings never leave
     HBM between the projection and the search (fdr_embed_knn), and only the features P has entries for
     cross PCIe (fdr_csr_compact; the saved feature_matrix.npz is the full matrix).  no_projection: stage 4
@@ -380,7 +428,10 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     builds the sparse index and writes every row within that distance of each read (fdr_sparse_index_radius_search)
     in row blocks, instead of k neighbours.  radius (projected mode): stage 4 embeds once into the context's dense
     index (fdr_dense_index_embed) and writes every row within that cosine distance of each read
-    (fdr_dense_index_radius_search) in row blocks."""
+    (fdr_dense_index_radius_search) in row blocks.  rescore (projected mode, a sparse metric's name): stage 4 searches
+    the projected rows for rescore_candidates neighbours per read (None: default_rescore_candidates), scores those pairs
+    on the feature rows with the values --no-projection gives them under that metric (fdr_sparse_rescore) and writes the
+    best nndescent_n_neighbors with the exact distances."""
     from . import _lib
     from .feature_extraction import _projection_csr
     if kmer_searcher_output:
@@ -427,6 +478,26 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     ctx.projection_load(Pc.indptr, Pc.indices, Pc.data, n_features, embedding_dimension)
     cip, cix = ctx.csr_compact(indptr, indices)
     logger.debug("embedding %d rows: %d of %d feature ids have an entry in P", indptr.size - 1, cix.size, indices.size)
+    if rescore is not None:
+        n, k = indptr.size - 1, nndescent_n_neighbors
+        kp = default_rescore_candidates(k, n) if rescore_candidates is None else rescore_candidates
+        if not k <= kp <= min(_lib.FDR_MAX_K, n):
+            raise SystemExit("--rescore needs --nndescent-n-neighbors = %d <= K' = %d <= min(%d, the %d reads)"
+                             % (k, kp, _lib.FDR_MAX_K, n))
+        logger.info("--- 4. Nearest Neighbors Search (projected, K' = %d), re-scored on the feature rows (metric = %s, "
+                    "k = %d) ---", kp, rescore, k)
+        candidates, _ = ctx.embed_knn(cip, cix, kp)
+        del cip, cix
+        if rescore == "jaccard":
+            values = None
+        else:  # (the values of --no-projection under this metric)
+            from .precompute import read_kmer_counts
+            counts = read_kmer_counts(kmer_library) if kmer_searcher_output else _load_counts(kmer_counts)
+            values = sparse_weights(counts, n_features, rescore)[indices]
+        neighbor_matrix, distances = ctx.sparse_rescore(indptr, indices, values, n_features, candidates, k=k,
+                                                        metric=rescore)
+        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates)
+        return
     del indptr, indices
     if radius is not None:
         logger.info("--- 4. Radius search (projected rows, cosine, radius = %g) ---", radius)
@@ -785,6 +856,7 @@ def main(argv=None):
     check_radius(args, "--no-projection-radius", args.no_projection_radius, True)
     check_radius(args, "--radius", args.radius, False)
     check_sparse_shard(args)
+    check_rescore(args)
     if args.no_projection_metric != "cosine" and not args.no_projection:
         raise SystemExit("--no-projection-metric %s needs --no-projection (the projected search is cosine only)"
                          % args.no_projection_metric)
@@ -842,7 +914,7 @@ def main(argv=None):
         kmer_library=args.kmer_library, feature_matrix=args.feature_matrix,
         kmer_counts=args.kmer_counts, read_names_path=args.read_names, no_projection=args.no_projection,
         no_projection_metric=args.no_projection_metric, no_projection_radius=args.no_projection_radius,
-        radius=args.radius)
+        radius=args.radius, rescore=args.rescore, rescore_candidates=args.rescore_candidates)
 
 
 if __name__ == "__main__":

@@ -29,7 +29,7 @@ SYMBOLS = (
     "fdr_sparse_index_query", "fdr_topk_merge", "fdr_radius_merge", "fdr_sparse_index_radius_search", "fdr_sparse_index_radius_query",
     "fdr_sparse_index_radius_fetch", "fdr_overlaps_write_csr",
     "fdr_dense_index_build", "fdr_dense_index_embed", "fdr_dense_index_radius_search", "fdr_dense_index_radius_query",
-    "fdr_dense_index_radius_fetch", "fdr_dense_index_info", "fdr_dense_index_free",
+    "fdr_dense_index_radius_fetch", "fdr_dense_index_info", "fdr_dense_index_free", "fdr_sparse_rescore",
 )
 FDR_FAST_MAX_DIM = 512  # the reach of the fp16 passes, and so of the dense index (csrc/knn_plan.inc)
 FDR_MAX_K = 128
@@ -38,6 +38,7 @@ KERNELS = ("embed_csr", "normalize_rows", "knn_tile", "knn_merge", "knn_prefilte
            "knn_dedup", "kmer_search", "kmer_compact")
 FDR_MAX_DIM = 2048
 TOPK_MERGE_MAX_PARTS = 64  # fdr_topk_merge: one lane of a wave per part
+FDR_RESCORE_TILE = 512  # fdr_sparse_rescore: stored entries of a query row staged at once (include/fedrann_hip.h)
 # fdr_last_query_paths codes (include/fedrann_hip.h: FDR_PATH_*)
 PATH_CERTIFIED, PATH_RANGE, PATH_EXACT, PATH_ZERO, PATH_RANGE_OVERFLOW, PATH_GENERIC, PATH_CLASS_MEMBER = 1, 2, 3, 4, 5, 6, 0x80
 # fdr_last_knn_trace (include/fedrann_hip.h: FDR_TRACE_*, FDR_FALLBACK_*)
@@ -136,6 +137,7 @@ def load_library():
     L.fdr_dense_index_free.argtypes = [vp]
     L.fdr_topk_merge.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp]
     L.fdr_radius_merge.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp]
+    L.fdr_sparse_rescore.argtypes = [vp, i32, i64, i64, vp, vp, vp, i64, i64, i32, vp, i32, vp, vp]
     L.fdr_embed_dev.argtypes = [vp, i64, vp, vp, vp, vp]
     L.fdr_normalize_dev.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     L.fdr_knn_workspace_bytes.argtypes = [vp, i64, i64, i32, i32]
@@ -535,6 +537,39 @@ def check_topk_merge(idx_parts, dist_parts, k, out=None):
                 or dist.dtype != np.float32 or not (idx.flags.c_contiguous and dist.flags.c_contiguous):
             raise ValueError("out must be C-contiguous (int32 [nq, k], float32 [nq, k])")
     return n_parts, nq, kp, k
+
+
+def check_rescore_args(n, candidates, k=None, metric="cosine", q_lo=0, out=None):
+    """The argument checks of Context.sparse_rescore beside those of the CSR (fdr_sparse_rescore repeats the limits);
+    needs no GPU.  n: the rows of the CSR.  candidates: a C-contiguous numpy int32 [nq, k_in] array with 1 <= k_in <=
+    FDR_MAX_K, row r the candidates of query q_lo + r; 0 <= q_lo and q_lo + nq <= n; 1 <= k <= k_in (None: k_in); fewer
+    than 2^31 candidates in all; a known metric; out, if given, C-contiguous (int32 [nq, k], float32 [nq, k]).  That
+    every candidate is a row in [0, n) is checked on the device.  Returns (nq, k_in, k, q_lo)."""
+    sparse_metric_code(metric)
+    if not isinstance(candidates, np.ndarray) or candidates.dtype != np.int32:
+        raise TypeError("candidates must be a numpy int32 array")
+    if candidates.ndim != 2 or not candidates.flags.c_contiguous:
+        raise ValueError("candidates must be a C-contiguous [nq, k_in] array")
+    for name, v in (("n", n), ("q_lo", q_lo)) + ((("k", k),) if k is not None else ()):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    (nq, k_in), n, q_lo = candidates.shape, int(n), int(q_lo)
+    k = k_in if k is None else int(k)
+    if not 1 <= k_in <= FDR_MAX_K:
+        raise ValueError("need 1 <= k_in <= %d candidates per query, got %d" % (FDR_MAX_K, k_in))
+    if not 1 <= k <= k_in:
+        raise ValueError("need 1 <= k <= k_in = %d, got k = %d" % (k_in, k))
+    if not (0 <= q_lo and q_lo + nq <= n):
+        raise ValueError("the queries [%d, %d) are no range of the n = %d rows" % (q_lo, q_lo + nq, n))
+    if nq * k_in > np.iinfo(np.int32).max:
+        raise ValueError("need fewer than 2^31 candidates in all (nq = %d, k_in = %d)" % (nq, k_in))
+    if out is not None:
+        idx, dist = out
+        if not (isinstance(idx, np.ndarray) and isinstance(dist, np.ndarray)) \
+                or (idx.shape, dist.shape) != ((nq, k), (nq, k)) or idx.dtype != np.int32 \
+                or dist.dtype != np.float32 or not (idx.flags.c_contiguous and dist.flags.c_contiguous):
+            raise ValueError("out must be C-contiguous (int32 [nq, k], float32 [nq, k])")
+    return nq, k_in, k, q_lo
 
 
 def check_radius_merge(parts):
@@ -1064,6 +1099,23 @@ class Context:
             if not np.array_equal(ip, out_ip[a:b + 1] - lo):
                 raise FedrannHipError("fdr_radius_merge: the queries [%d, %d) came back with another indptr" % (a, b))
         return out_ip, idx, dist
+
+    def sparse_rescore(self, indptr, indices, values, n_features, candidates, k=None, metric="cosine", q_lo=0, out=None):
+        """Candidate lists re-scored by exact distance on the rows of a CSR (arguments as knn_sparse): candidates int32
+        [nq, k_in], row r the candidates of query q_lo + r (row numbers of the CSR, e.g. embed_knn's lists at k_in).
+        Returns (idx int32 [nq, k], dist float32 [nq, k]), k = k_in by default: each query's candidates under
+        `metric`, ascending by (distance bits, index), the first k.  A distance is the float32 knn_sparse reports for
+        the pair under that metric, bit for bit, so knn_sparse's own lists come back unchanged (fdr_sparse_rescore).
+        The query's own index is an ordinary candidate (distance 0); a repeated candidate comes out twice; one outside
+        [0, n) is refused (FedrannHipError) with nothing written.  out=(idx, dist): caller-owned C-contiguous result
+        arrays.  The context's sparse index, its dense index and its last k-NN trace stay as they are."""
+        code = sparse_metric_code(metric)
+        n, _, F = check_sparse_rows(indptr, indices, values, n_features, 1, metric=metric)
+        nq, k_in, k, q_lo = check_rescore_args(n, candidates, k, metric, q_lo, out)
+        idx, dist = out if out is not None else (np.empty((nq, k), np.int32), np.empty((nq, k), np.float32))
+        self._check(self._L.fdr_sparse_rescore(self._h, code, n, F, _ptr(indptr), _ptr(indices), _ptr(values), q_lo, nq,
+                                               k_in, _ptr(candidates), k, _ptr(idx), _ptr(dist)), "fdr_sparse_rescore")
+        return idx, dist
 
     def embed_knn(self, a_indptr, a_indices, k, return_embedding=False, out=None):
         """out=(idx int32 [n,k], dist float32 [n,k]): caller-owned (e.g. pinned, reused) result arrays."""

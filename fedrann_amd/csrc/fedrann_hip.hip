@@ -788,6 +788,30 @@ struct RadiusMergeScratch {
     void release() { release_all(starts, indptr_out, items, idx_parts, dist_parts, idx_out, dist_out, refusal); }
 };
 
+// fdr_sparse_rescore (sparse_rescore.inc): the call's CSR as uploaded, what the row pass makes of its rows, the
+// candidate lists, the re-scored rows before they are copied out, and the record of a refused call.  Valid within one
+// call; grows as needed; freed with the context.
+#define RS_CNT_ERR 0      // or of SP_ERR_* bits of the rows
+#define RS_CNT_REFUSAL 1  // the smallest (query row of the call << 8 | slot) whose candidate is outside [0, n); all ones: none
+#define RS_CNT_WORDS 2
+struct SparseRescoreScratch {
+    DevArray<long long> indptr;      // [n + 1] the rows
+    DevArray<int> indices;           // the stored entries' features ...
+    DevArray<float> values;          // ... their values, as given (absent: every entry 1) ...
+    DevArray<float> x;               // ... normalised (cosine); raw (weighted Jaccard)
+    DevArray<unsigned char> present; // ... 1 where the value is not +-0 (Jaccard with values)
+    DevArray<int> asize;             // [n] the set sizes (Jaccard)
+    DevArray<float> mass;            // [n] the masses (weighted Jaccard)
+    DevArray<unsigned char> zero;    // [n] zero (empty, zero-mass) rows
+    DevArray<int> cand;              // [nq, k_in] the candidates
+    DevArray<int> idx_out;           // [nq, k_out] the re-scored rows
+    DevArray<float> dist_out;
+    DevArray<u64> cnt;               // RS_CNT_*
+    void release() {
+        release_all(indptr, indices, values, x, present, asize, mass, zero, cand, idx_out, dist_out, cnt);
+    }
+};
+
 // The projection that fdr_projection_load left for launch_embed (K1's tables, see embed_csr_kernel), fdr_csr_compact
 // and the upload scheduler (the bitmap's host copy).
 struct Projection {
@@ -908,6 +932,7 @@ struct fdr_ctx {
     DenseIndex di;         // the dense index and its radius searches (knn_dense_radius.inc): kept until fdr_dense_index_free
     TopkMergeScratch tm;   // the merge of the ranks' candidate lists (topk_merge.inc): kept until fdr_destroy
     RadiusMergeScratch rm; // the merge of the ranks' ragged radius rows (radius_merge.inc): kept until fdr_destroy
+    SparseRescoreScratch rs;  // the exact re-score of candidate lists (sparse_rescore.inc): kept until fdr_destroy
     // timing: when enabled, every launch of kernel kind i gets its own hipEvent pair on the launch
     // stream; fdr_timing_read() sums the elapsed times of all launches since the last read
     int knn_mode = FDR_MODE_AUTO;
@@ -2353,6 +2378,7 @@ FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indp
 #include "knn_dense_radius.inc"  // D-R1 .. D-R3: the same on the projected rows, through the fp16 range pass (fdr_dense_index_*)
 #include "topk_merge.inc"  // T1: the exact merge of the ranks' candidate lists of a target-sharded sparse search
 #include "radius_merge.inc"  // M1: the exact merge of the ranks' ragged rows of a target-sharded sparse radius search
+#include "sparse_rescore.inc"  // X1 / X2: candidate lists re-scored by exact distance on the sparse rows (fdr_sparse_rescore)
 #include "kmer_search.inc"
 #include "kmer_output_loader.inc"
 #include "reads_parser.inc"

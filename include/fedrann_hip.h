@@ -385,6 +385,42 @@ int fdr_topk_merge(fdr_ctx *ctx, int64_t nq, int32_t n_parts, int32_t kp, int32_
 int fdr_radius_merge(fdr_ctx *ctx, int64_t nq, int32_t n_parts, const int64_t *indptr_parts, const int32_t *idx_parts,
                      const float *dist_parts, int64_t *indptr_out, int32_t *idx_out, float *dist_out);
 
+/* ---- re-score candidate lists by exact distance on the sparse rows  (the second stage of an approximate search:
+ *      NNDescent_ava.get_neighbors on the embeddings names the neighbours, nearest_neighbors.py:39-55, the boundary this
+ *      library replaces; their distances there are the projection's, and this call puts the feature rows' own in their
+ *      place) ---------------------------------------------------------------------------------------------------------
+ * The rows are the CSR of fdr_knn_sparse_metric under its rules: indptr int64 [n + 1], indices int32 strictly ascending
+ * inside a row and in [0, n_features), values float32 finite (NULL: every stored entry is 1), under
+ * FDR_METRIC_WEIGHTED_JACCARD none negative and a finite mass chain per row; the rows' violations are found on the
+ * device before anything is written.  cand_idx int32 [nq, k_in]: row r holds the candidates of query q_lo + r, row
+ * numbers in [0, n).  idx_out int32 [nq, k_out], dist_out float32 [nq, k_out]: row r holds that query's candidates
+ * under `metric`, ascending by (distance bits, index), the first k_out of them.  Host pointers; the call synchronises.
+ * dist(q, t) is, bit for bit, the float32 fdr_knn_sparse_metric on the same CSR reports for the pair whenever t is in
+ * q's list (DESIGN.md section 4 for the arithmetic, section 5 for the argument): a row's norm, set size or mass as a
+ * build forms it; over the features both rows hold, in ascending feature order from +0, the fp32 fma chain of
+ * xhat_q * xhat_t and dist = clamp(1 - c, 0, 1) (cosine), the int32 count c of the features present in both (value not
+ * +-0) and (float)((double)(u - c) / (double)u) with u = a + b - c (Jaccard), the fp32 chain m <- m + min(x_q, x_t)
+ * and (float)((u - m) / u) with u = ((double)A_q + (double)A_t) - (double)m (weighted Jaccard).  Two zero / empty /
+ * zero-mass rows are at 0.0f, exactly one such row at 1.0f, two rows that share nothing at exactly 1.0f.  So the lists
+ * of fdr_knn_sparse_metric at k, fed back with k_in = k_out = k, come back unchanged.  The query's own index is an
+ * ordinary candidate and comes out at its distance (0).
+ * Limits (FDR_E_ARG, the cause in fdr_last_error): 1 <= k_out <= k_in <= FDR_MAX_K; 0 <= q_lo, 0 <= nq, q_lo + nq <= n;
+ * 1 <= n < 2^31, 1 <= n_features < 2^31, fewer than 2^31 stored entries, nq * k_in below 2^31; an unknown metric; a null
+ * pointer where one is needed.  nq == 0 is FDR_OK and writes nothing.  Checked on the device before anything is written
+ * to idx_out / dist_out (FDR_E_ARG, fdr_last_error names the smallest (query, slot)): every candidate in [0, n).  NOT
+ * checked, as with fdr_topk_merge: a query's candidates are pairwise distinct; a repeated index comes out twice.
+ * The call touches neither the context's sparse index (its held radius result included), nor its dense index, nor
+ * fdr_last_knn_trace.  Each call uploads the CSR; its device buffers (4 bytes per stored entry, 4 more with values, 4
+ * more under cosine and weighted Jaccard, 1 more under Jaccard with values; 4 per candidate, 8 per result) belong to
+ * the context, only grow and are freed by fdr_destroy.  A query row is staged FDR_RESCORE_TILE stored entries at a time;
+ * a longer row is walked tile by tile, which changes no bit.  Cost: per pair the candidate's stored entries are read
+ * once per tile of the query (4 to 8 bytes each), plus the upload; DESIGN.md section 5. */
+#define FDR_RESCORE_TILE 512 /* stored entries of a query row staged at once */
+int fdr_sparse_rescore(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
+                       const int32_t *indices, const float *values, int64_t q_lo, int64_t nq, int32_t k_in,
+                       const int32_t *cand_idx /* [nq, k_in] */, int32_t k_out, int32_t *idx_out,
+                       float *dist_out /* [nq, k_out] */);
+
 /* ---- device-resident API (multi-GPU host, bench.py) ----------------------------------------
  * All pointers are device pointers; work is enqueued on `stream` (a hipStream_t). */
 int fdr_embed_dev(fdr_ctx *ctx, int64_t n_rows, const int64_t *d_indptr, const int32_t *d_indices,
