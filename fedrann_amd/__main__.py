@@ -30,6 +30,9 @@ fdr_dense_index_radius_search), a block of rows at a time; --nndescent-n-neighbo
 --rescore METRIC (the default, projected mode, one GPU): stage 4 takes --rescore-candidates K' >= k neighbours per read
 from the projected search, scores exactly those pairs on the feature rows under METRIC (fdr_sparse_rescore: the
 distances of --no-projection --no-projection-metric METRIC, bit for bit) and writes the best k with them.
+--radius R --radius-rescore METRIC [--radius-rescore-bound R2]: the candidates of the projected radius search, every
+pair scored exactly on the feature rows under METRIC (the rows go to the device once: fdr_rescore_rows_build), cut at
+R2 in that metric (default 1: every projected hit is kept) and written in the exact order (fdr_rescore_rows_radius).
 
 --devices 0,1,...: every stage is sharded over several GPUs of the node.  The parent process starts one
 child per GPU BEFORE it touches a GPU itself; from reads, every child counts and searches its byte range of
@@ -149,6 +152,14 @@ def build_parser():
                         "with k = --nndescent-n-neighbors; by default max(k, min(2 k, 64)), capped by the number of "
                         "reads.  K' > 64 takes the projected search off its fp16 prefilter (DESIGN.md section 10): a "
                         "cost cliff, not a slope." % FDR_MAX_K)
+    g.add_argument("--radius-rescore", choices=["cosine", "jaccard", "weighted_jaccard"], default=None,
+                   help="With --radius: score every (read, projected hit) pair on the feature rows under this metric "
+                        "(the distances --no-projection --no-projection-metric reports, bit for bit), keep the pairs "
+                        "within --radius-rescore-bound and write them with the exact distances, ranked by them.  One "
+                        "GPU; not with --no-projection.")
+    g.add_argument("--radius-rescore-bound", type=float, default=None, metavar="R2",
+                   help="With --radius-rescore: the bound in the exact metric, 0 <= R2 <= 1; by default 1, which keeps "
+                        "every hit of the projected radius search.")
     g.add_argument("--devices", type=str, default=None,
                    help="Comma-separated GPU ordinals: shard the rows over these GPUs (one process each).")
     g.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
@@ -276,6 +287,41 @@ def check_rescore(args):
         raise SystemExit("--rescore-candidates must be in [--nndescent-n-neighbors = %d, %d], got %d"
                          % (k, _lib.FDR_MAX_K, kp))
     return kp
+
+
+def check_radius_rescore(args):
+    """--radius-rescore / --radius-rescore-bound against the other options, before any work.  Returns R2 (None without
+    --radius-rescore).  What --radius itself refuses (--no-projection, several --devices, -n > 512) is check_radius's;
+    they are named here too, so that the message speaks of the flag that was given."""
+    if args.radius_rescore is None:
+        if args.radius_rescore_bound is not None:
+            raise SystemExit("--radius-rescore-bound needs --radius-rescore (without it nothing is re-scored)")
+        return None
+    if args.no_projection:
+        raise SystemExit("--radius-rescore is the projected radius search's second stage; the distances of "
+                         "--no-projection-radius are exact already")
+    if args.radius is None:
+        raise SystemExit("--radius-rescore needs --radius (it re-scores the projected radius search's hits)")
+    if len(device_list(args.devices)) > 1:
+        raise SystemExit("--radius-rescore runs on one GPU: the projected radius search is not sharded over --devices")
+    r2 = 1.0 if args.radius_rescore_bound is None else args.radius_rescore_bound
+    if not 0.0 <= np.float32(r2) <= 1.0:  # (NaN fails both)
+        raise SystemExit("--radius-rescore-bound must be in [0, 1], got %r" % (r2,))
+    return r2 + 0.0  # (-0.0 is 0)
+
+
+class RescoredRadius:
+    """write_radius_overlaps' index of --radius-rescore: radius_search(radius, lo, hi, max_hits=) is the dense index's,
+    its rows then re-scored on `rows` (a RescoreRows of the same reads) and cut at `bound` in the exact metric."""
+
+    def __init__(self, index, rows, bound):
+        self.index, self.rows, self.bound, self.n = index, rows, bound, index.n
+        self.candidates = 0  # the projected hits so far
+
+    def radius_search(self, radius, lo, hi, max_hits):
+        ip, idx, _ = self.index.radius_search(radius, lo, hi, max_hits=max_hits)
+        self.candidates += int(ip[-1])
+        return self.rows.radius(ip, idx, self.bound, q_lo=lo, max_entries=max_hits)
 
 
 def write_radius_overlaps(path, index, radius, read_names, strands, block_rows=None, max_hits=None):
@@ -418,7 +464,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                          kmer_searcher_output=None, kmer_library=None, feature_matrix=None,
                          kmer_counts=None, read_names_path=None, no_projection=False,
                          no_projection_metric="cosine", no_projection_radius=None, radius=None, rescore=None,
-                         rescore_candidates=None):
+                         rescore_candidates=None, radius_rescore=None, radius_rescore_bound=None):
     """Stages 2-4 of the reference pipeline (__main__.py:329-391) on one GPU.  The embeddings never leave
     HBM between the projection and the search (fdr_embed_knn), and only the features P has entries for
     cross PCIe (fdr_csr_compact; the saved feature_matrix.npz is the full matrix).  no_projection: stage 4
@@ -431,7 +477,9 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     (fdr_dense_index_radius_search) in row blocks.  rescore (projected mode, a sparse metric's name): stage 4 searches
     the projected rows for rescore_candidates neighbours per read (None: default_rescore_candidates), scores those pairs
     on the feature rows with the values --no-projection gives them under that metric (fdr_sparse_rescore) and writes the
-    best nndescent_n_neighbors with the exact distances."""
+    best nndescent_n_neighbors with the exact distances.  radius_rescore (with radius, a sparse metric's name): the
+    feature rows go to the device once with those values (fdr_rescore_rows_build), and each row block's projected hits
+    are scored on them and cut at radius_rescore_bound (None: 1) in that metric (fdr_rescore_rows_radius)."""
     from . import _lib
     from .feature_extraction import _projection_csr
     if kmer_searcher_output:
@@ -478,6 +526,14 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     ctx.projection_load(Pc.indptr, Pc.indices, Pc.data, n_features, embedding_dimension)
     cip, cix = ctx.csr_compact(indptr, indices)
     logger.debug("embedding %d rows: %d of %d feature ids have an entry in P", indptr.size - 1, cix.size, indices.size)
+
+    def rescore_values(metric):  # the values of --no-projection under this metric
+        if metric == "jaccard":
+            return None
+        from .precompute import read_kmer_counts
+        counts = read_kmer_counts(kmer_library) if kmer_searcher_output else _load_counts(kmer_counts)
+        return sparse_weights(counts, n_features, metric)[indices]
+
     if rescore is not None:
         n, k = indptr.size - 1, nndescent_n_neighbors
         kp = default_rescore_candidates(k, n) if rescore_candidates is None else rescore_candidates
@@ -488,15 +544,25 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                     "k = %d) ---", kp, rescore, k)
         candidates, _ = ctx.embed_knn(cip, cix, kp)
         del cip, cix
-        if rescore == "jaccard":
-            values = None
-        else:  # (the values of --no-projection under this metric)
-            from .precompute import read_kmer_counts
-            counts = read_kmer_counts(kmer_library) if kmer_searcher_output else _load_counts(kmer_counts)
-            values = sparse_weights(counts, n_features, rescore)[indices]
+        values = rescore_values(rescore)
         neighbor_matrix, distances = ctx.sparse_rescore(indptr, indices, values, n_features, candidates, k=k,
                                                         metric=rescore)
         _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates)
+        return
+    if radius is not None and radius_rescore is not None:
+        bound = 1.0 if radius_rescore_bound is None else radius_rescore_bound
+        logger.info("--- 4. Radius search (projected rows, cosine, radius = %g), re-scored on the feature rows (metric = "
+                    "%s, bound = %g) ---", radius, radius_rescore, bound)
+        logger.info("--radius: --nndescent-n-neighbors (%d) is ignored; %d rows, d = %d", nndescent_n_neighbors,
+                    cip.size - 1, embedding_dimension)
+        with ctx.dense_index_from_csr(cip, cix) as index, \
+                ctx.rescore_rows(indptr, indices, rescore_values(radius_rescore), n_features,
+                                 metric=radius_rescore) as held:
+            del cip, cix
+            both = RescoredRadius(index, held, bound)
+            rows = write_radius_overlaps(join(output_dir, "overlaps.tsv"), both, radius, read_names, strands)
+        logger.debug("wrote %d overlap rows of %d projected hits", rows, both.candidates)
+        _cleanup(keep_intermediates)
         return
     del indptr, indices
     if radius is not None:
@@ -857,6 +923,7 @@ def main(argv=None):
     check_radius(args, "--radius", args.radius, False)
     check_sparse_shard(args)
     check_rescore(args)
+    radius_rescore_bound = check_radius_rescore(args)
     if args.no_projection_metric != "cosine" and not args.no_projection:
         raise SystemExit("--no-projection-metric %s needs --no-projection (the projected search is cosine only)"
                          % args.no_projection_metric)
@@ -914,7 +981,8 @@ def main(argv=None):
         kmer_library=args.kmer_library, feature_matrix=args.feature_matrix,
         kmer_counts=args.kmer_counts, read_names_path=args.read_names, no_projection=args.no_projection,
         no_projection_metric=args.no_projection_metric, no_projection_radius=args.no_projection_radius,
-        radius=args.radius, rescore=args.rescore, rescore_candidates=args.rescore_candidates)
+        radius=args.radius, rescore=args.rescore, rescore_candidates=args.rescore_candidates,
+        radius_rescore=args.radius_rescore, radius_rescore_bound=radius_rescore_bound)
 
 
 if __name__ == "__main__":

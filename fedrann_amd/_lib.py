@@ -30,6 +30,8 @@ SYMBOLS = (
     "fdr_sparse_index_radius_fetch", "fdr_overlaps_write_csr",
     "fdr_dense_index_build", "fdr_dense_index_embed", "fdr_dense_index_radius_search", "fdr_dense_index_radius_query",
     "fdr_dense_index_radius_fetch", "fdr_dense_index_info", "fdr_dense_index_free", "fdr_sparse_rescore",
+    "fdr_rescore_rows_build", "fdr_rescore_rows_info", "fdr_rescore_rows_free", "fdr_rescore_rows_knn",
+    "fdr_rescore_rows_radius", "fdr_rescore_rows_radius_fetch",
 )
 FDR_FAST_MAX_DIM = 512  # the reach of the fp16 passes, and so of the dense index (csrc/knn_plan.inc)
 FDR_MAX_K = 128
@@ -138,6 +140,13 @@ def load_library():
     L.fdr_topk_merge.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp]
     L.fdr_radius_merge.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp]
     L.fdr_sparse_rescore.argtypes = [vp, i32, i64, i64, vp, vp, vp, i64, i64, i32, vp, i32, vp, vp]
+    L.fdr_rescore_rows_build.argtypes = [vp, i32, i64, i64, vp, vp, vp]
+    L.fdr_rescore_rows_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i64),
+                                        ctypes.POINTER(sz)]
+    L.fdr_rescore_rows_free.argtypes = [vp]
+    L.fdr_rescore_rows_knn.argtypes = [vp, i64, i64, i32, vp, i32, vp, vp]
+    L.fdr_rescore_rows_radius.argtypes = [vp, ctypes.c_float, i64, i64, vp, vp, vp]
+    L.fdr_rescore_rows_radius_fetch.argtypes = [vp, i64, vp, vp]
     L.fdr_embed_dev.argtypes = [vp, i64, vp, vp, vp, vp]
     L.fdr_normalize_dev.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     L.fdr_knn_workspace_bytes.argtypes = [vp, i64, i64, i32, i32]
@@ -572,6 +581,45 @@ def check_rescore_args(n, candidates, k=None, metric="cosine", q_lo=0, out=None)
     return nq, k_in, k, q_lo
 
 
+def check_rescore_ragged(n, cand_indptr, cand_idx, radius, q_lo=0):
+    """The argument checks of RescoreRows.radius (fdr_rescore_rows_radius repeats those of the indptr and the limits);
+    needs no GPU.  n: the rows of the row set.  cand_indptr int64 [nq + 1] and cand_idx int32 [cand_indptr[-1]],
+    C-contiguous 1-D numpy arrays: row r holds the candidates of query q_lo + r; cand_indptr starts at 0 and never
+    decreases; fewer than 2^31 candidates in all; 0 <= q_lo and q_lo + nq <= n; 0 <= radius <= 1 (a real number, no
+    NaN; 1 keeps every candidate; -0.0 comes back as 0.0).  That every candidate is a row in [0, n) is checked on the device.  Returns
+    (nq, radius as float32, q_lo, counts int64 [nq]: the rows' lengths)."""
+    for name, a, dt in (("cand_indptr", cand_indptr, np.int64), ("cand_idx", cand_idx, np.int32)):
+        if not isinstance(a, np.ndarray) or a.dtype != dt:
+            raise TypeError("%s must be a numpy %s array" % (name, np.dtype(dt)))
+        if a.ndim != 1 or not a.flags.c_contiguous:
+            raise ValueError("%s must be a C-contiguous 1-D array" % name)
+    for name, v in (("n", n), ("q_lo", q_lo)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise ValueError("radius must be a number, got %r" % (radius,))
+    r = np.float32(radius)
+    if not (r >= 0 and r <= 1):
+        raise ValueError("need 0 <= radius <= 1, got %r" % (radius,))
+    r = r + np.float32(0)  # (-0.0 is 0: the sign bit does not reach the library)
+    if cand_indptr.size < 1:
+        raise ValueError("cand_indptr must hold nq + 1 >= 1 elements")
+    nq, n, q_lo = cand_indptr.size - 1, int(n), int(q_lo)
+    if cand_indptr[0] != 0:
+        raise ValueError("cand_indptr must start at 0, got %d" % int(cand_indptr[0]))
+    counts = np.diff(cand_indptr)
+    if np.any(counts < 0):
+        raise ValueError("cand_indptr decreases at query %d" % (q_lo + int(np.argmax(counts < 0))))
+    if int(cand_indptr[-1]) > np.iinfo(np.int32).max:
+        raise ValueError("need fewer than 2^31 candidates in all, got %d" % int(cand_indptr[-1]))
+    if cand_idx.size != cand_indptr[-1]:
+        raise ValueError("cand_idx (%d) must hold the %d candidates cand_indptr states"
+                         % (cand_idx.size, int(cand_indptr[-1])))
+    if not (0 <= q_lo and q_lo + nq <= n):
+        raise ValueError("the queries [%d, %d) are no range of the n = %d rows" % (q_lo, q_lo + nq, n))
+    return nq, r, q_lo, counts
+
+
 def check_radius_merge(parts):
     """The argument checks of Context.radius_merge (fdr_radius_merge repeats those of the indptrs and the limits);
     needs no GPU.  parts: a sequence of 1 .. 64 triples (indptr int64 [nq + 1], idx int32 [indptr[-1]], dist float32
@@ -683,6 +731,7 @@ class Context:
         self.d = 0
         self._sparse_gen = 0  # builds of the context's sparse index so far (SparseIndex: is mine still the one?)
         self._dense_gen = 0   # ... and of its dense index (DenseIndex)
+        self._rescore_gen = 0  # ... and of its re-score row set (RescoreRows)
 
     def _err(self):
         return self._L.fdr_last_error().decode("utf-8", "replace")
@@ -1117,6 +1166,18 @@ class Context:
                                                k_in, _ptr(candidates), k, _ptr(idx), _ptr(dist)), "fdr_sparse_rescore")
         return idx, dist
 
+    def rescore_rows(self, indptr, indices, values, n_features, metric="cosine"):
+        """The rows of a CSR (arguments as sparse_rescore's) kept on the device for any number of RescoreRows.knn /
+        RescoreRows.radius calls: fdr_rescore_rows_build, one upload and one row pass.  A context holds one row set,
+        beside its sparse and its dense index: this call replaces it, and a RescoreRows of the replaced one raises
+        from then on.  A row that breaks the CSR's rules is refused and leaves no row set."""
+        code = sparse_metric_code(metric)
+        n, _, F = check_sparse_rows(indptr, indices, values, n_features, 1, metric=metric)
+        self._rescore_gen += 1
+        self._check(self._L.fdr_rescore_rows_build(self._h, code, n, F, _ptr(indptr), _ptr(indices), _ptr(values)),
+                    "fdr_rescore_rows_build")
+        return RescoreRows(self, n, metric, self._rescore_gen)
+
     def embed_knn(self, a_indptr, a_indices, k, return_embedding=False, out=None):
         """out=(idx int32 [n,k], dist float32 [n,k]): caller-owned (e.g. pinned, reused) result arrays."""
         a_indptr = _as(a_indptr, np.int64, "a_indptr")
@@ -1449,6 +1510,98 @@ class DenseIndex(_HeldIndex):
         c = self._ctx
         if self._open and getattr(c, "_h", None) and c._dense_gen == self._gen:
             c._check(c._L.fdr_dense_index_free(c._h), "fdr_dense_index_free")
+        self._open = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class RescoreRows(_HeldIndex):
+    """The re-score row set of a Context (Context.rescore_rows): candidate lists, rectangular (knn) or ragged (radius),
+    scored exactly on the held rows, any number of times.  The rows live in the context, which holds one set: once
+    the context has built another, or after close(), the calls raise FedrannHipError."""
+
+    _kind, _gen_attr, _fetch, _counted = "re-score row", "_rescore_gen", "fdr_rescore_rows_radius_fetch", "candidates"
+
+    def __init__(self, ctx, n, metric, gen):
+        self._ctx, self.n, self.metric, self._gen = ctx, int(n), metric, gen
+        self._open = True
+
+    def knn(self, candidates, k=None, q_lo=0, out=None):
+        """Context.sparse_rescore on the held rows, without its upload: candidates int32 [nq, k_in], row r the
+        candidates of query q_lo + r.  Returns (idx int32 [nq, k], dist float32 [nq, k]), the bits sparse_rescore
+        gives on the same CSR (fdr_rescore_rows_knn).  A held radius result stays as it is."""
+        nq, k_in, k, q_lo = check_rescore_args(self.n, candidates, k, self.metric, q_lo, out)
+        idx, dist = out if out is not None else (np.empty((nq, k), np.int32), np.empty((nq, k), np.float32))
+        self._live("RescoreRows.knn")
+        c = self._ctx
+        c._check(c._L.fdr_rescore_rows_knn(c._h, q_lo, nq, k_in, _ptr(candidates), k, _ptr(idx), _ptr(dist)),
+                 "fdr_rescore_rows_knn")
+        return idx, dist
+
+    def radius(self, cand_indptr, cand_idx, radius, q_lo=0, max_entries=1 << 26):
+        """Ragged candidate rows re-scored and cut by `radius` in the exact metric: row r of (cand_indptr int64
+        [nq + 1], cand_idx int32) holds the candidates of query q_lo + r, rows of the set in any number and order
+        (DenseIndex.radius_search's rows, for one).  Returns (indptr int64 [nq + 1], idx int32, dist float32): row r
+        holds that row's candidates with distance <= radius (0 <= radius <= 1; 1 keeps them all), the distance the
+        float32 sparse_rescore and knn_sparse report for the pair, in (distance bits, index) order
+        (fdr_rescore_rows_radius).  The query's own index is an ordinary candidate (distance 0); a repeated candidate
+        comes out as often as it goes in; one outside [0, n) is refused (FedrannHipError).  The queries go to the device
+        in consecutive pieces of at most max_entries candidates (20 device bytes each); one query with more is a
+        ValueError that names it."""
+        nq, r, q_lo, counts = check_rescore_ragged(self.n, cand_indptr, cand_idx, radius, q_lo)
+        if isinstance(max_entries, bool) or not isinstance(max_entries, (int, np.integer)) \
+                or not 1 <= int(max_entries) < 2 ** 31:
+            raise ValueError("max_entries must be an integer in [1, 2^31), got %r" % (max_entries,))
+        max_entries = int(max_entries)
+        # (everything in one piece: the common case, without the walk over the counts)
+        pieces = [(0, nq)] if int(cand_indptr[-1]) <= max_entries else radius_pieces(counts, max_entries)
+        if pieces is None:
+            q = int(np.argmax(counts > max_entries))
+            raise ValueError("query %d alone has %d candidates, above max_entries = %d"
+                             % (q_lo + q, int(counts[q]), max_entries))
+        self._live("RescoreRows.radius")
+        c = self._ctx
+        outs = []
+        for a, b in pieces:
+            if a == 0 and b == nq:
+                ip_in, ix_in = cand_indptr, cand_idx
+            else:
+                ip_in = np.ascontiguousarray(cand_indptr[a:b + 1] - cand_indptr[a])
+                ix_in = cand_idx[cand_indptr[a]:cand_indptr[b]]
+            ip = np.full(b - a + 1, -1, dtype=np.int64)
+            c._check(c._L.fdr_rescore_rows_radius(c._h, r, q_lo + a, b - a, _ptr(ip_in), _ptr(ix_in), _ptr(ip)),
+                     "fdr_rescore_rows_radius")
+            total = int(ip[-1])
+            idx = np.empty(total, dtype=np.int32)
+            dist = np.empty(total, dtype=np.float32)
+            c._check(c._L.fdr_rescore_rows_radius_fetch(c._h, total, _ptr(idx), _ptr(dist)), self._fetch)
+            outs.append((ip, idx, dist))
+        if len(outs) == 1:
+            return outs[0]
+        out_ip = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum(np.concatenate([np.diff(o[0]) for o in outs]), out=out_ip[1:])
+        return out_ip, np.concatenate([o[1] for o in outs]), np.concatenate([o[2] for o in outs])
+
+    def info(self):
+        """dict of fdr_rescore_rows_info: metric, n, stored (stored entries), device_bytes (what the row set holds on
+        the device, the calls' buffers included)."""
+        self._live("RescoreRows.info")
+        c = self._ctx
+        m, n, s, b = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_size_t()
+        c._check(c._L.fdr_rescore_rows_info(c._h, ctypes.byref(m), ctypes.byref(n), ctypes.byref(s), ctypes.byref(b)),
+                 "fdr_rescore_rows_info")
+        name = [k for k, v in SPARSE_METRICS.items() if v == m.value][0]
+        return {"metric": name, "n": int(n.value), "stored": int(s.value), "device_bytes": int(b.value)}
+
+    def close(self):
+        """Free the row set's device memory (if it still is the context's row set)."""
+        c = self._ctx
+        if self._open and getattr(c, "_h", None) and c._rescore_gen == self._gen:
+            c._check(c._L.fdr_rescore_rows_free(c._h), "fdr_rescore_rows_free")
         self._open = False
 
     def __enter__(self):

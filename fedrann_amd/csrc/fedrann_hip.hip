@@ -788,13 +788,15 @@ struct RadiusMergeScratch {
     void release() { release_all(starts, indptr_out, items, idx_parts, dist_parts, idx_out, dist_out, refusal); }
 };
 
-// fdr_sparse_rescore (sparse_rescore.inc): the call's CSR as uploaded, what the row pass makes of its rows, the
-// candidate lists, the re-scored rows before they are copied out, and the record of a refused call.  Valid within one
-// call; grows as needed; freed with the context.
+// The re-score calls (sparse_rescore.inc).  RsCsr: a CSR as uploaded and what the row pass X1 makes of its rows.
+// RsLists: rectangular candidate lists, the re-scored rows before they are copied out, and the record of a refused
+// call.  fdr_sparse_rescore owns one of each (SparseRescoreScratch), valid within one call, freed with the context;
+// the held row set of fdr_rescore_rows_* (RescoreRowSet) owns another of each, so neither call sees the other's.
 #define RS_CNT_ERR 0      // or of SP_ERR_* bits of the rows
-#define RS_CNT_REFUSAL 1  // the smallest (query row of the call << 8 | slot) whose candidate is outside [0, n); all ones: none
+#define RS_CNT_REFUSAL 1  // the smallest candidate outside [0, n): X2 (query row of the call << 8 | slot), X3 (query
+                          // row of the call << 32 | position in its row); all ones: none
 #define RS_CNT_WORDS 2
-struct SparseRescoreScratch {
+struct RsCsr {
     DevArray<long long> indptr;      // [n + 1] the rows
     DevArray<int> indices;           // the stored entries' features ...
     DevArray<float> values;          // ... their values, as given (absent: every entry 1) ...
@@ -803,12 +805,55 @@ struct SparseRescoreScratch {
     DevArray<int> asize;             // [n] the set sizes (Jaccard)
     DevArray<float> mass;            // [n] the masses (weighted Jaccard)
     DevArray<unsigned char> zero;    // [n] zero (empty, zero-mass) rows
+    template <class F>
+    auto each(F f) { return f(indptr, indices, values, x, present, asize, mass, zero); }
+    size_t bytes() { return each([](auto &...a) { return (a.bytes() + ...); }); }
+    void release() { each([](auto &...a) { release_all(a...); }); }
+};
+struct RsLists {
     DevArray<int> cand;              // [nq, k_in] the candidates
     DevArray<int> idx_out;           // [nq, k_out] the re-scored rows
     DevArray<float> dist_out;
     DevArray<u64> cnt;               // RS_CNT_*
+    size_t bytes() { return cand.bytes() + idx_out.bytes() + dist_out.bytes() + cnt.bytes(); }
+    void release() { release_all(cand, idx_out, dist_out, cnt); }
+};
+struct SparseRescoreScratch {
+    RsCsr csr;
+    RsLists lists;
     void release() {
-        release_all(indptr, indices, values, x, present, asize, mass, zero, cand, idx_out, dist_out, cnt);
+        csr.release();
+        lists.release();
+    }
+};
+
+// The context's one re-score row set (fdr_rescore_rows_*, sparse_rescore.inc): the rows as fdr_rescore_rows_build's X1
+// left them, for any number of _knn (X2) and _radius (X3) calls, and those calls' buffers.  Independent of the sparse
+// index, the dense index and fdr_sparse_rescore's scratch; grows as needed; kept until fdr_rescore_rows_free.
+struct RescoreRowSet {
+    RsCsr csr;                        // (values: dead behind X1, released by the build)
+    RsLists lists;                    // _knn's lists and results; cand and cnt serve _radius too
+    DevArray<long long> cand_indptr;  // [nq + 1] _radius: the candidates' segments
+    DevArray<int2> items;             // ... its work items: (query row of the call, batch of FDR_MAX_K of its candidates)
+    std::vector<int2> h_items;        // ... as the host lists them while it checks cand_indptr
+    RadiusResult rr;                  // count: the hits per query; off: their scan; keys: X3's, in the candidates'
+                                      // places, then the result; sorted: the candidate segments, sorted
+    DevArray<char> tmp;               // rocprim's temporary storage
+    bool valid = false, has_values = false;
+    int metric = 0;
+    long long n = 0, stored = 0;
+    size_t bytes() {
+        return csr.bytes() + lists.bytes() + cand_indptr.bytes() + items.bytes() + rr.bytes() + tmp.bytes();
+    }
+    void release() {
+        csr.release();
+        lists.release();
+        release_all(cand_indptr, items, tmp);
+        std::vector<int2>().swap(h_items);
+        rr.release();
+        valid = has_values = false;
+        metric = 0;
+        n = stored = 0;
     }
 };
 
@@ -933,6 +978,7 @@ struct fdr_ctx {
     TopkMergeScratch tm;   // the merge of the ranks' candidate lists (topk_merge.inc): kept until fdr_destroy
     RadiusMergeScratch rm; // the merge of the ranks' ragged radius rows (radius_merge.inc): kept until fdr_destroy
     SparseRescoreScratch rs;  // the exact re-score of candidate lists (sparse_rescore.inc): kept until fdr_destroy
+    RescoreRowSet rrs;     // the held re-score rows and their calls (sparse_rescore.inc): kept until fdr_rescore_rows_free
     // timing: when enabled, every launch of kernel kind i gets its own hipEvent pair on the launch
     // stream; fdr_timing_read() sums the elapsed times of all launches since the last read
     int knn_mode = FDR_MODE_AUTO;

@@ -421,6 +421,67 @@ int fdr_sparse_rescore(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_featur
                        const int32_t *cand_idx /* [nq, k_in] */, int32_t k_out, int32_t *idx_out,
                        float *dist_out /* [nq, k_out] */);
 
+/* ---- a held row set for re-scoring, rectangular and ragged  (the same boundary, nearest_neighbors.py:39-55: the rows
+ *      stay on the device for any number of re-score calls, and a radius result of the projected rows, ragged and of
+ *      hundreds of candidates per read, is re-scored and cut by a second bound in the exact metric) ----------------------
+ * The context holds ONE re-score row set, beside its sparse index and its dense index and independent of both, and of
+ * fdr_sparse_rescore, whose scratch and behaviour are untouched.  Host pointers; the calls synchronise; one GPU.
+ * fdr_rescore_rows_build takes the CSR arguments of fdr_sparse_rescore under its rules and limits (1 <= n < 2^31, 1 <=
+ * n_features < 2^31, fewer than 2^31 stored entries, a known metric, indptr starting at 0 and never decreasing: FDR_E_ARG
+ * otherwise), uploads the CSR once and runs the row pass once; the rows' violations (an id outside [0, n_features) or
+ * not strictly ascending inside a row, a value that is not finite, under FDR_METRIC_WEIGHTED_JACCARD a negative value or
+ * a mass chain that is not finite) are found on the device and refuse the build (FDR_E_ARG).  A build replaces the
+ * previous row set and drops a held radius result; one that is refused or fails leaves NO row set.  Without a row set
+ * _info, _knn, _radius and _radius_fetch are FDR_E_STATE, and _free is FDR_OK.  Device memory of the rows: 8 bytes per
+ * row for the indptr, 4 per stored entry, 4 more under cosine and weighted Jaccard, 1 more under Jaccard with values,
+ * 1 to 5 per row.  Buffers only grow, with two deliberate exceptions, both at a build: the values as given are released
+ * once the row pass has read them, and what the new metric does not use of a set built under another metric is released
+ * too, so device_bytes never counts dead arrays.  _free and fdr_destroy release everything.  fdr_rescore_rows_info (every out pointer may be NULL): the metric, n, the stored entries,
+ * and device_bytes, everything the row set holds on the device, the calls' buffers included.
+ * fdr_rescore_rows_knn is fdr_sparse_rescore on the held rows: the same contract, limits and refusals without the CSR
+ * arguments (1 <= k_out <= k_in <= FDR_MAX_K; [q_lo, q_lo + nq) a range of the rows; nq * k_in below 2^31; nq == 0 is
+ * FDR_OK and writes nothing; every candidate in [0, n), checked on the device before anything is written, the smallest
+ * (query, slot) named), and the same bits as fdr_sparse_rescore on the same CSR.  It neither drops nor uses the held
+ * radius result.  NOT checked: that a query's candidates are pairwise distinct.
+ * fdr_rescore_rows_radius: cand_indptr int64 [nq + 1] and cand_idx int32 [cand_indptr[nq]]; row r of the input is
+ * cand_idx[cand_indptr[r] .. cand_indptr[r + 1]), the candidates of query q_lo + r: row numbers in [0, n), of any count,
+ * in any order (a row of fdr_dense_index_radius_search, for one).  Row r of the result holds every candidate t of that
+ * row with dist(q, t) <= radius, the comparison made on the float32 that fdr_sparse_rescore and fdr_knn_sparse_metric
+ * report for the pair (a pair's chain depends on its two rows alone, not on the list it stands in), ordered by
+ * (distance bits, index).  indptr_out int64 [nq + 1]: the exact prefix sums, indptr_out[0] = 0.  The result is held and
+ * fdr_rescore_rows_radius_fetch copies it out: idx_out int32 [hits], dist_out float32 [hits]; `hits` must equal the
+ * total (FDR_E_ARG otherwise); without a held result FDR_E_STATE; a fetch leaves it held, and the next
+ * fdr_rescore_rows_* call other than _info, _knn and _radius_fetch drops it.  So:
+ *   - radius domain: 0 <= radius <= 1.  NaN, a negative radius and one above 1 are FDR_E_ARG; -0.0f is 0;
+ *   - radius == 1 keeps every candidate (a distance lies in [0, 1]): the plain ragged re-score, indptr_out = cand_indptr;
+ *   - below 1 a pair at exactly 1.0f is no hit, the radius searches' rule;
+ *   - the closed forms are fdr_sparse_rescore's: two zero / empty / zero-mass rows at 0.0f, exactly one such row at
+ *     1.0f, two rows that share nothing at exactly 1.0f; the query's own index is an ordinary candidate at distance 0;
+ *   - nq == 0 (indptr_out[0] = 0) and a total of 0 (every entry 0) are FDR_OK, an empty result held.
+ * Checked on the host before any upload (FDR_E_ARG): cand_indptr[0] == 0; cand_indptr never decreases; the total is
+ * below 2^31; [q_lo, q_lo + nq) is a range of the rows; no null pointer where one is needed.  Checked on the device
+ * before indptr_out is written (FDR_E_ARG): every candidate in [0, n); fdr_last_error names the smallest (query,
+ * position in its row) and the value, indptr_out is untouched and no result is held.  NOT checked, the caller's
+ * promise: a row's candidates are pairwise distinct; a repeated candidate comes out as often as it goes in.  There is
+ * no max_hits: the caller supplies the candidates and so knows the cap on the hits.  Device memory of a call: 16 bytes
+ * per candidate (8 of keys, which take the result afterwards; 8 of sort space), 4 more per candidate, 24 per query, 8
+ * per FDR_MAX_K candidates of a row, and the segmented sort's temporary storage.  The calls touch neither the sparse
+ * index, the dense index, their held results, fdr_sparse_rescore's scratch nor fdr_last_knn_trace.
+ * How: a wave scores one batch of at most FDR_MAX_K consecutive candidates of a row, so a row of 5 000 candidates is
+ * 40 waves; the keys land in the candidates' places, one segmented sort orders each row, and the hits, the first keys
+ * of each sorted row, are compacted.  Cost: per pair the candidate's stored entries are read once per tile of the
+ * query, as in fdr_sparse_rescore, without its upload; DESIGN.md section 5 (X3).  Not here: several devices, device
+ * pointers. */
+int fdr_rescore_rows_build(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
+                           const int32_t *indices, const float *values);
+int fdr_rescore_rows_info(fdr_ctx *ctx, int32_t *metric, int64_t *n, int64_t *stored, size_t *device_bytes);
+int fdr_rescore_rows_free(fdr_ctx *ctx);
+int fdr_rescore_rows_knn(fdr_ctx *ctx, int64_t q_lo, int64_t nq, int32_t k_in, const int32_t *cand_idx /* [nq, k_in] */,
+                         int32_t k_out, int32_t *idx_out, float *dist_out /* [nq, k_out] */);
+int fdr_rescore_rows_radius(fdr_ctx *ctx, float radius, int64_t q_lo, int64_t nq, const int64_t *cand_indptr /* [nq + 1] */,
+                            const int32_t *cand_idx, int64_t *indptr_out /* [nq + 1] */);
+int fdr_rescore_rows_radius_fetch(fdr_ctx *ctx, int64_t hits, int32_t *idx_out, float *dist_out);
+
 /* ---- device-resident API (multi-GPU host, bench.py) ----------------------------------------
  * All pointers are device pointers; work is enqueued on `stream` (a hipStream_t). */
 int fdr_embed_dev(fdr_ctx *ctx, int64_t n_rows, const int64_t *d_indptr, const int32_t *d_indices,
