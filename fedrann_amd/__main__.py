@@ -33,6 +33,10 @@ distances of --no-projection --no-projection-metric METRIC, bit for bit) and wri
 --radius R --radius-rescore METRIC [--radius-rescore-bound R2]: the candidates of the projected radius search, every
 pair scored exactly on the feature rows under METRIC (the rows go to the device once: fdr_rescore_rows_build), cut at
 R2 in that metric (default 1: every projected hit is kept) and written in the exact order (fdr_rescore_rows_radius).
+--symmetrize union|mutual (any of the one-GPU modes above): the graph the mode is about to write is symmetrised on the
+GPU first (fdr_graph_symmetrize: a pair under both reads when either lists the other, or only where each lists the
+other, at the smaller distance) and written once through fdr_overlaps_write_csr; the radius modes collect their row
+blocks on the host before that.  Refused over several --devices.
 
 --devices 0,1,...: every stage is sharded over several GPUs of the node.  The parent process starts one
 child per GPU BEFORE it touches a GPU itself; from reads, every child counts and searches its byte range of
@@ -160,6 +164,15 @@ def build_parser():
     g.add_argument("--radius-rescore-bound", type=float, default=None, metavar="R2",
                    help="With --radius-rescore: the bound in the exact metric, 0 <= R2 <= 1; by default 1, which keeps "
                         "every hit of the projected radius search.")
+    g.add_argument("--symmetrize", choices=["union", "mutual"], default=None,
+                   help="Symmetrise the neighbour graph on the GPU before overlaps.tsv is written "
+                        "(fdr_graph_symmetrize): union lists a pair under both reads when either read lists the other, "
+                        "mutual keeps a pair only where each read lists the other; the smaller of the two distances, "
+                        "every read's row ranked by distance.  Applies to what one GPU is about to write, in every "
+                        "one-GPU mode (k-NN, --no-projection, --rescore, --radius, --no-projection-radius, "
+                        "--radius-rescore); the radius modes collect their row blocks on the host first (16 bytes a "
+                        "hit) and are refused at 2^31 hits.  Refused over several --devices: a rank holds only its "
+                        "own rows' lists, while a reverse entry can come from any row.")
     g.add_argument("--devices", type=str, default=None,
                    help="Comma-separated GPU ordinals: shard the rows over these GPUs (one process each).")
     g.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
@@ -324,14 +337,49 @@ class RescoredRadius:
         return self.rows.radius(ip, idx, self.bound, q_lo=lo, max_entries=max_hits)
 
 
-def write_radius_overlaps(path, index, radius, read_names, strands, block_rows=None, max_hits=None):
+def check_symmetrize(args):
+    """--symmetrize against the other options, before any work: one GPU only."""
+    if args.symmetrize is not None and len(device_list(args.devices)) > 1:
+        raise SystemExit("--symmetrize runs on one GPU: over --devices a rank holds only its own rows' lists, and a "
+                         "reverse entry can come from any row")
+
+
+def write_symmetrized(path, ctx, graph, mode, read_names, strands):
+    """overlaps.tsv of the union / mutual rows of `graph` ((idx [n, k], dist [n, k]) or a ragged triple, every row of
+    the graph): Context.graph_symmetrize, then one fdr_overlaps_write_csr.  Returns the data lines."""
+    from . import _lib
+    ip, idx, dist = ctx.graph_symmetrize(graph, mode=mode, max_entries=2 ** 31 - 1)
+    logger.info("--symmetrize %s: %d entries of %d rows became %d", mode, graph[-2].size, ip.size - 1, int(ip[-1]))
+    name_off, names = _lib.pack_names(read_names)
+    return _lib.overlaps_write_csr(path, ip, idx, dist, name_off, names, np.asarray(strands, dtype=np.uint8),
+                                   n_threads=global_variables.threads if global_variables.threads > 1 else 0)
+
+
+def write_radius_overlaps(path, index, radius, read_names, strands, block_rows=None, max_hits=None, symmetrize=None,
+                          ctx=None):
     """overlaps.tsv of a radius search of all rows of `index` (a SparseIndex or a DenseIndex: both have n and
     radius_search(radius, lo, hi, max_hits=)), a block of rows at a time: each block's ragged result
     is appended through fdr_overlaps_write_csr, so the host holds one block's hits.  block_rows / max_hits = None:
-    RADIUS_BLOCK_ROWS / RADIUS_MAX_HITS as they stand at the call.  Returns the data lines."""
+    RADIUS_BLOCK_ROWS / RADIUS_MAX_HITS as they stand at the call.  symmetrize ("union" / "mutual", with the Context
+    ctx): the blocks are collected on the host instead (16 bytes a hit; 2^31 hits or more are refused), symmetrised in
+    one piece and written once (write_symmetrized).  Returns the data lines."""
     from . import _lib
     block_rows = RADIUS_BLOCK_ROWS if block_rows is None else block_rows
     max_hits = RADIUS_MAX_HITS if max_hits is None else max_hits
+    if symmetrize is not None:
+        blocks, total = [], 0
+        for lo in range(0, index.n, block_rows):
+            hi = min(index.n, lo + block_rows)
+            blocks.append(index.radius_search(radius, lo, hi, max_hits=max_hits))
+            total += int(blocks[-1][0][-1])
+            if total >= 2 ** 31:
+                raise SystemExit("--symmetrize: the radius search has found %d hits by row %d, and a graph of 2^31 "
+                                 "entries or more cannot be symmetrised: lower the radius" % (total, hi))
+        starts = np.cumsum([0] + [int(b[0][-1]) for b in blocks[:-1]])
+        indptr = np.concatenate([np.zeros(1, np.int64)] + [b[0][1:] + s for b, s in zip(blocks, starts)])
+        graph = (indptr, np.concatenate([b[1] for b in blocks]), np.concatenate([b[2] for b in blocks]))
+        del blocks
+        return write_symmetrized(path, ctx, graph, symmetrize, read_names, strands)
     name_off, names = _lib.pack_names(read_names)
     strands = np.asarray(strands, dtype=np.uint8)
     threads = global_variables.threads if global_variables.threads > 1 else 0
@@ -464,7 +512,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                          kmer_searcher_output=None, kmer_library=None, feature_matrix=None,
                          kmer_counts=None, read_names_path=None, no_projection=False,
                          no_projection_metric="cosine", no_projection_radius=None, radius=None, rescore=None,
-                         rescore_candidates=None, radius_rescore=None, radius_rescore_bound=None):
+                         rescore_candidates=None, radius_rescore=None, radius_rescore_bound=None, symmetrize=None):
     """Stages 2-4 of the reference pipeline (__main__.py:329-391) on one GPU.  The embeddings never leave
     HBM between the projection and the search (fdr_embed_knn), and only the features P has entries for
     cross PCIe (fdr_csr_compact; the saved feature_matrix.npz is the full matrix).  no_projection: stage 4
@@ -479,7 +527,9 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     on the feature rows with the values --no-projection gives them under that metric (fdr_sparse_rescore) and writes the
     best nndescent_n_neighbors with the exact distances.  radius_rescore (with radius, a sparse metric's name): the
     feature rows go to the device once with those values (fdr_rescore_rows_build), and each row block's projected hits
-    are scored on them and cut at radius_rescore_bound (None: 1) in that metric (fdr_rescore_rows_radius)."""
+    are scored on them and cut at radius_rescore_bound (None: 1) in that metric (fdr_rescore_rows_radius).  symmetrize
+    ("union" / "mutual"; None: the rows as searched): whichever of these modes ran, the graph it is about to write is
+    symmetrised on the GPU first (fdr_graph_symmetrize) and written once through fdr_overlaps_write_csr."""
     from . import _lib
     from .feature_extraction import _projection_csr
     if kmer_searcher_output:
@@ -501,7 +551,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
         values = None if no_projection_metric == "jaccard" else P[indices]
         with ctx.sparse_index(indptr, indices, values, n_features, metric=no_projection_metric) as index:
             rows = write_radius_overlaps(join(output_dir, "overlaps.tsv"), index, no_projection_radius, read_names,
-                                         strands)
+                                         strands, symmetrize=symmetrize, ctx=ctx)
         logger.debug("wrote %d overlap rows", rows)
         _cleanup(keep_intermediates)
         return
@@ -511,7 +561,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                     "entries", embedding_dimension, indptr.size - 1, n_features, indices.size)
         neighbor_matrix, distances = ctx.knn_sparse(indptr, indices, None, n_features, nndescent_n_neighbors,
                                                     metric="jaccard")
-        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates)
+        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize, ctx)
         return
     if no_projection:
         logger.info("--- 4. Nearest Neighbors Search (exact, metric = %s, on the IDF-weighted feature rows) ---",
@@ -520,7 +570,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                     "entries", embedding_dimension, indptr.size - 1, n_features, indices.size)
         neighbor_matrix, distances = ctx.knn_sparse(indptr, indices, P[indices], n_features, nndescent_n_neighbors,
                                                     metric=no_projection_metric)
-        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates)
+        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize, ctx)
         return
     Pc = _projection_csr(P)
     ctx.projection_load(Pc.indptr, Pc.indices, Pc.data, n_features, embedding_dimension)
@@ -547,7 +597,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
         values = rescore_values(rescore)
         neighbor_matrix, distances = ctx.sparse_rescore(indptr, indices, values, n_features, candidates, k=k,
                                                         metric=rescore)
-        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates)
+        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize, ctx)
         return
     if radius is not None and radius_rescore is not None:
         bound = 1.0 if radius_rescore_bound is None else radius_rescore_bound
@@ -560,7 +610,8 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                                  metric=radius_rescore) as held:
             del cip, cix
             both = RescoredRadius(index, held, bound)
-            rows = write_radius_overlaps(join(output_dir, "overlaps.tsv"), both, radius, read_names, strands)
+            rows = write_radius_overlaps(join(output_dir, "overlaps.tsv"), both, radius, read_names, strands,
+                                         symmetrize=symmetrize, ctx=ctx)
         logger.debug("wrote %d overlap rows of %d projected hits", rows, both.candidates)
         _cleanup(keep_intermediates)
         return
@@ -570,7 +621,8 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
         logger.info("--radius: --nndescent-n-neighbors (%d) is ignored; %d rows, d = %d", nndescent_n_neighbors,
                     cip.size - 1, embedding_dimension)
         with ctx.dense_index_from_csr(cip, cix) as index:
-            rows = write_radius_overlaps(join(output_dir, "overlaps.tsv"), index, radius, read_names, strands)
+            rows = write_radius_overlaps(join(output_dir, "overlaps.tsv"), index, radius, read_names, strands,
+                                         symmetrize=symmetrize, ctx=ctx)
         logger.debug("wrote %d overlap rows", rows)
         _cleanup(keep_intermediates)
         return
@@ -578,13 +630,17 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     logger.info("Using exact GPU k-NN in place of NNDescent (n_trees = %s, leaf_size = %s are inert)",
                 nndescent_n_trees, 200)
     neighbor_matrix, distances = ctx.embed_knn(cip, cix, nndescent_n_neighbors)
-    _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates)
+    _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize, ctx)
 
 
-def _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates):
+def _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize=None, ctx=None):
     nbr_output_file = join(output_dir, "overlaps.tsv")
     logger.debug("Saving overlap table to %s", nbr_output_file)
-    rows = write_overlaps(nbr_output_file, neighbor_matrix, distances, read_names, strands)
+    if symmetrize is not None:
+        graph = (np.ascontiguousarray(neighbor_matrix, dtype=np.int32), np.ascontiguousarray(distances, dtype=np.float32))
+        rows = write_symmetrized(nbr_output_file, ctx, graph, symmetrize, read_names, strands)
+    else:
+        rows = write_overlaps(nbr_output_file, neighbor_matrix, distances, read_names, strands)
     logger.debug("wrote %d overlap rows", rows)
     _cleanup(keep_intermediates)
 
@@ -923,6 +979,7 @@ def main(argv=None):
     check_radius(args, "--radius", args.radius, False)
     check_sparse_shard(args)
     check_rescore(args)
+    check_symmetrize(args)
     radius_rescore_bound = check_radius_rescore(args)
     if args.no_projection_metric != "cosine" and not args.no_projection:
         raise SystemExit("--no-projection-metric %s needs --no-projection (the projected search is cosine only)"
@@ -982,7 +1039,7 @@ def main(argv=None):
         kmer_counts=args.kmer_counts, read_names_path=args.read_names, no_projection=args.no_projection,
         no_projection_metric=args.no_projection_metric, no_projection_radius=args.no_projection_radius,
         radius=args.radius, rescore=args.rescore, rescore_candidates=args.rescore_candidates,
-        radius_rescore=args.radius_rescore, radius_rescore_bound=radius_rescore_bound)
+        radius_rescore=args.radius_rescore, radius_rescore_bound=radius_rescore_bound, symmetrize=args.symmetrize)
 
 
 if __name__ == "__main__":

@@ -32,6 +32,7 @@ SYMBOLS = (
     "fdr_dense_index_radius_fetch", "fdr_dense_index_info", "fdr_dense_index_free", "fdr_sparse_rescore",
     "fdr_rescore_rows_build", "fdr_rescore_rows_info", "fdr_rescore_rows_free", "fdr_rescore_rows_knn",
     "fdr_rescore_rows_radius", "fdr_rescore_rows_radius_fetch",
+    "fdr_graph_symmetrize", "fdr_graph_symmetrize_fetch", "fdr_graph_free",
 )
 FDR_FAST_MAX_DIM = 512  # the reach of the fp16 passes, and so of the dense index (csrc/knn_plan.inc)
 FDR_MAX_K = 128
@@ -139,6 +140,9 @@ def load_library():
     L.fdr_dense_index_free.argtypes = [vp]
     L.fdr_topk_merge.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp]
     L.fdr_radius_merge.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp]
+    L.fdr_graph_symmetrize.argtypes = [vp, i32, i64, vp, vp, vp, i64, vp]
+    L.fdr_graph_symmetrize_fetch.argtypes = [vp, i64, vp, vp]
+    L.fdr_graph_free.argtypes = [vp]
     L.fdr_sparse_rescore.argtypes = [vp, i32, i64, i64, vp, vp, vp, i64, i64, i32, vp, i32, vp, vp]
     L.fdr_rescore_rows_build.argtypes = [vp, i32, i64, i64, vp, vp, vp]
     L.fdr_rescore_rows_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i64),
@@ -660,6 +664,24 @@ def check_radius_merge(parts):
     return len(parts), nq, counts
 
 
+def check_graph_symmetrize(graph, mode="union", max_entries=1 << 27):
+    """The argument checks of Context.graph_symmetrize (fdr_graph_symmetrize repeats those of the indptr and the
+    limits); needs no GPU.  graph: (idx int32 [n, k], dist float32 [n, k]) or (indptr int64 [n + 1], idx int32, dist
+    float32), numpy arrays (graph.as_ragged); at least one row, fewer than 2^31 rows and entries; mode "union",
+    "mutual" or "transpose"; 1 <= max_entries < 2^31.  All ValueError.  What the rows hold (indices in [0, n), distances
+    >= 0 and not NaN, no index twice in a row) is checked on the device.  Returns (mode code, n, indptr, idx, dist)."""
+    from . import graph as _graph
+    code = _graph.mode_code(mode)
+    if isinstance(max_entries, bool) or not isinstance(max_entries, (int, np.integer)) \
+            or not 1 <= int(max_entries) < 2 ** 31:
+        raise ValueError("max_entries must be an integer in [1, 2^31), got %r" % (max_entries,))
+    indptr, idx, dist = _graph.as_ragged(graph)
+    n = indptr.size - 1
+    if not 1 <= n <= np.iinfo(np.int32).max or idx.size > np.iinfo(np.int32).max:
+        raise ValueError("need 1 <= n < 2^31 rows and fewer than 2^31 entries (got %d and %d)" % (n, idx.size))
+    return code, n, indptr, idx, dist
+
+
 def _row_mass_overflows(indptr, values, largest):
     """Whether a row's float32 add chain over its values (all finite and >= 0, none above `largest`) reaches +inf.  A
     chain of m such terms is at most m * largest * (1 + 2^-24)^m, below 1.07e38 for m <= 2^20 and m * largest < 1e38;
@@ -1148,6 +1170,31 @@ class Context:
             if not np.array_equal(ip, out_ip[a:b + 1] - lo):
                 raise FedrannHipError("fdr_radius_merge: the queries [%d, %d) came back with another indptr" % (a, b))
         return out_ip, idx, dist
+
+    def graph_symmetrize(self, graph, mode="union", max_entries=1 << 27):
+        """The union, mutual or transposed rows of a neighbour graph: graph is (idx int32 [n, k], dist float32 [n, k]),
+        as knn returns them, or ragged (indptr int64 [n + 1], idx int32, dist float32), as a radius search does; an
+        entry (t, d) of row q says "q lists t at distance d".  Rows need not be sorted and may hold their own index.
+        mode "union": row r names every s that it lists or that lists it; "mutual": only where each lists the other;
+        "transpose": every s that lists r.  Returns (indptr int64 [n + 1], idx int32, dist float32), every row
+        ascending by (distance bits, index): graph.symmetrize_rows bit for bit, computed on the GPU
+        (fdr_graph_symmetrize, then fdr_graph_symmetrize_fetch).  The argument checks (check_graph_symmetrize) are
+        ValueErrors before the library is called; an index outside [0, n), a negative or NaN distance, an index twice
+        in a row and a result of more than max_entries entries (16 device bytes each) are refused by the library
+        (FedrannHipError).  The context's indexes, their held radius results and its last k-NN trace stay as they are."""
+        code, n, indptr, idx, dist = check_graph_symmetrize(graph, mode, max_entries)
+        out_ip = np.empty(n + 1, dtype=np.int64)
+        self._check(self._L.fdr_graph_symmetrize(self._h, code, n, _ptr(indptr), _ptr(idx), _ptr(dist), int(max_entries),
+                                                 _ptr(out_ip)), "fdr_graph_symmetrize")
+        total = int(out_ip[-1])
+        out_idx, out_dist = np.empty(total, dtype=np.int32), np.empty(total, dtype=np.float32)
+        self._check(self._L.fdr_graph_symmetrize_fetch(self._h, total, _ptr(out_idx), _ptr(out_dist)),
+                    "fdr_graph_symmetrize_fetch")
+        return out_ip, out_idx, out_dist
+
+    def graph_free(self):
+        """Free the device memory of graph_symmetrize (it grows with the largest graph seen): fdr_graph_free."""
+        self._check(self._L.fdr_graph_free(self._h), "fdr_graph_free")
 
     def sparse_rescore(self, indptr, indices, values, n_features, candidates, k=None, metric="cosine", q_lo=0, out=None):
         """Candidate lists re-scored by exact distance on the rows of a CSR (arguments as knn_sparse): candidates int32

@@ -788,6 +788,33 @@ struct RadiusMergeScratch {
     void release() { release_all(starts, indptr_out, items, idx_parts, dist_parts, idx_out, dist_out, refusal); }
 };
 
+// fdr_graph_symmetrize (graph_symmetrize.inc): the graph as uploaded, its rows ordered by index, what the count pass
+// found per entry, and the result, counted and held in a RadiusResult of its own (count / off: the result's rows; keys:
+// as the emit pass leaves them, then the held result; sorted: the rows in key order).  Grows as needed; freed by
+// fdr_graph_free and with the context.
+struct GraphSymScratch {
+    RadiusResult rr;
+    DevArray<long long> indptr;    // [n + 1] the input's row pointer
+    DevArray<int> idx;             // the input's entries as uploaded: the indices ...
+    DevArray<float> dist;          // ... and the distances
+    DevArray<int> row;             // per entry: its row
+    DevArray<u64> packed, byidx;   // per entry: index << 32 | distance bits, as uploaded; every row ordered by index
+    DevArray<unsigned> partner;    // per entry of byidx (q -> t): the bits of (t -> q), GS_NO_PARTNER where t does not list q
+    DevArray<unsigned> fill;       // [n] entries the emit pass placed through a row's cursor
+    DevArray<u64> refusal;         // [1] the smallest (row, rule) the checks found; all ones: none
+    DevArray<char> tmp;            // rocprim's temporary storage
+    std::vector<long long> h_off;  // the result's row pointer on its way to indptr_out
+    template <class F>
+    auto each(F f) {
+        return f(indptr, idx, dist, row, packed, byidx, partner, fill, refusal, tmp);
+    }
+    size_t bytes() { return rr.bytes() + each([](auto &...a) { return (a.bytes() + ...); }); }
+    void release() {
+        each([](auto &...a) { release_all(a...); });
+        rr.release();
+    }
+};
+
 // The re-score calls (sparse_rescore.inc).  RsCsr: a CSR as uploaded and what the row pass X1 makes of its rows.
 // RsLists: rectangular candidate lists, the re-scored rows before they are copied out, and the record of a refused
 // call.  fdr_sparse_rescore owns one of each (SparseRescoreScratch), valid within one call, freed with the context;
@@ -979,6 +1006,7 @@ struct fdr_ctx {
     RadiusMergeScratch rm; // the merge of the ranks' ragged radius rows (radius_merge.inc): kept until fdr_destroy
     SparseRescoreScratch rs;  // the exact re-score of candidate lists (sparse_rescore.inc): kept until fdr_destroy
     RescoreRowSet rrs;     // the held re-score rows and their calls (sparse_rescore.inc): kept until fdr_rescore_rows_free
+    GraphSymScratch gs;    // a graph's symmetrised rows and their call (graph_symmetrize.inc): kept until fdr_graph_free
     // timing: when enabled, every launch of kernel kind i gets its own hipEvent pair on the launch
     // stream; fdr_timing_read() sums the elapsed times of all launches since the last read
     int knn_mode = FDR_MODE_AUTO;
@@ -2425,6 +2453,7 @@ FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indp
 #include "topk_merge.inc"  // T1: the exact merge of the ranks' candidate lists of a target-sharded sparse search
 #include "radius_merge.inc"  // M1: the exact merge of the ranks' ragged rows of a target-sharded sparse radius search
 #include "sparse_rescore.inc"  // X1 / X2: candidate lists re-scored by exact distance on the sparse rows (fdr_sparse_rescore)
+#include "graph_symmetrize.inc"  // G1 .. G4: union, mutual and transposed rows of a neighbour graph (fdr_graph_symmetrize)
 #include "kmer_search.inc"
 #include "kmer_output_loader.inc"
 #include "reads_parser.inc"

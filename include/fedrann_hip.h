@@ -385,6 +385,42 @@ int fdr_topk_merge(fdr_ctx *ctx, int64_t nq, int32_t n_parts, int32_t kp, int32_
 int fdr_radius_merge(fdr_ctx *ctx, int64_t nq, int32_t n_parts, const int64_t *indptr_parts, const int32_t *idx_parts,
                      const float *dist_parts, int64_t *indptr_out, int32_t *idx_out, float *dist_out);
 
+/* ---- symmetrise a neighbour graph: union, mutual and transposed rows  (every search here answers the directed question
+ *      "which rows does row q list?", and overlaps.tsv is written from those rows; the reference writes the same directed
+ *      pairs, __main__.py get_output_dataframe, and has no counterpart of this call.  An overlap is undirected: its
+ *      consumers want row t to name every q that listed t, or only the pairs that list each other, or a row's listers) ----
+ * The graph is square, on n rows, as ragged rows: indptr int64 [n + 1], idx int32 and dist float32 [indptr[n]]; an entry
+ * (t, d) of row q says "q lists t at distance d", 0 <= t < n.  Rows need not be sorted; a self entry (q, q) is allowed and
+ * is its own reverse.  Distances compare by their bit patterns, b(q->t), all at most 0x7f800000.  Row r of the result
+ * holds s
+ *   FDR_GRAPH_UNION      iff r lists s or s lists r, at the smaller bits of the directions present;
+ *   FDR_GRAPH_MUTUAL     iff r lists s and s lists r, at min(b(r->s), b(s->r));
+ *   FDR_GRAPH_TRANSPOSE  iff s lists r, at b(s->r);
+ * each row strictly ascending by key = (uint64)distance bits << 32 | (uint32)index, as fdr_overlaps_write_csr takes it:
+ * fedrann_amd.graph.symmetrize_rows bit for bit, a function of the input alone (two runs give the same bytes).
+ * fdr_graph_symmetrize counts: indptr_out int64 [n + 1] takes the result's row pointer, and the entries stay on the device
+ * until the next fdr_graph_symmetrize or fdr_graph_free; fdr_graph_symmetrize_fetch copies them out, idx_out int32 and
+ * dist_out float32 [entries], entries == indptr_out[n] (another value, or nothing held: an error; 0 entries need no
+ * pointers).  Host pointers; both calls synchronise.
+ * Checked on the host before anything is uploaded (FDR_E_ARG): the mode; 1 <= n < 2^31; 1 <= max_entries < 2^31; the
+ * indptr starts at 0, never decreases and totals below 2^31; null pointers (idx / dist may be null for a graph without
+ * entries, whose result is the zero indptr and an empty held result).  Checked on the device before anything is written
+ * to indptr_out (FDR_E_ARG, fdr_last_error names the rule and the smallest (row, rule) that breaks one): an index outside
+ * [0, n); distance bits above 0x7f800000 (negative, -0.0, NaN); an index listed twice in one row.  A result of more than
+ * max_entries entries is refused (FDR_E_ARG) with indptr_out holding the counts, as the radius searches do.  After any
+ * refusal nothing is held.
+ * The call touches neither the sparse index, the dense index, the re-score rows, their held radius results nor
+ * fdr_last_knn_trace.  Its device buffers (32 bytes per input entry, 16 per result entry, 28 per row) belong to the
+ * context, only grow and are freed by fdr_graph_free and fdr_destroy.  Cost: two segmented sorts (the input rows by
+ * index, the result rows by key) and one binary search per entry in the listed row; DESIGN.md section 5. */
+#define FDR_GRAPH_UNION 0
+#define FDR_GRAPH_MUTUAL 1
+#define FDR_GRAPH_TRANSPOSE 2
+int fdr_graph_symmetrize(fdr_ctx *ctx, int32_t mode, int64_t n, const int64_t *indptr, const int32_t *idx,
+                         const float *dist, int64_t max_entries, int64_t *indptr_out /* [n + 1] */);
+int fdr_graph_symmetrize_fetch(fdr_ctx *ctx, int64_t entries, int32_t *idx_out, float *dist_out);
+int fdr_graph_free(fdr_ctx *ctx);
+
 /* ---- re-score candidate lists by exact distance on the sparse rows  (the second stage of an approximate search:
  *      NNDescent_ava.get_neighbors on the embeddings names the neighbours, nearest_neighbors.py:39-55, the boundary this
  *      library replaces; their distances there are the projection's, and this call puts the feature rows' own in their
