@@ -37,6 +37,12 @@ R2 in that metric (default 1: every projected hit is kept) and written in the ex
 GPU first (fdr_graph_symmetrize: a pair under both reads when either lists the other, or only where each lists the
 other, at the smaller distance) and written once through fdr_overlaps_write_csr; the radius modes collect their row
 blocks on the host before that.  Refused over several --devices.
+--components union|mutual [--components-distance D] (the same one-GPU modes): components.tsv beside overlaps.tsv, the
+connected components of the rows as searched, before any --symmetrize (fdr_graph_components: two reads are joined when
+either lists the other, or only where each lists the other, at a distance <= D; by default every listed pair joins).
+One line per read in row order: read_name, orientation, component (numbered by their first read), component_size.
+overlaps.tsv is what the run writes without the flag, byte for byte; the radius modes collect their row blocks on the
+host as for --symmetrize.  Refused over several --devices.
 
 --devices 0,1,...: every stage is sharded over several GPUs of the node.  The parent process starts one
 child per GPU BEFORE it touches a GPU itself; from reads, every child counts and searches its byte range of
@@ -173,6 +179,17 @@ def build_parser():
                         "--radius-rescore); the radius modes collect their row blocks on the host first (16 bytes a "
                         "hit) and are refused at 2^31 hits.  Refused over several --devices: a rank holds only its "
                         "own rows' lists, while a reverse entry can come from any row.")
+    g.add_argument("--components", choices=["union", "mutual"], default=None,
+                   help="Write components.tsv beside overlaps.tsv: the connected components of the neighbour graph as "
+                        "searched (before any --symmetrize), found on the GPU (fdr_graph_components).  union joins two "
+                        "reads when either lists the other, mutual only where each lists the other.  One line per "
+                        "read: read_name, orientation, component (numbered by their first read), component_size.  "
+                        "overlaps.tsv is the file the run writes without this flag.  In every one-GPU mode that "
+                        "--symmetrize serves; the radius modes collect their row blocks on the host as for "
+                        "--symmetrize.  Refused over several --devices.")
+    g.add_argument("--components-distance", type=float, default=None, metavar="D",
+                   help="With --components: join only pairs at distance <= D (mutual: the smaller of the two "
+                        "directions); by default every listed pair joins.  D >= 0.")
     g.add_argument("--devices", type=str, default=None,
                    help="Comma-separated GPU ordinals: shard the rows over these GPUs (one process each).")
     g.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
@@ -344,6 +361,41 @@ def check_symmetrize(args):
                          "reverse entry can come from any row")
 
 
+def check_components(args):
+    """--components / --components-distance against the other options, before any work: one GPU only, the distance
+    only with the flag, and neither negative nor NaN."""
+    if args.components_distance is not None:
+        if args.components is None:
+            raise SystemExit("--components-distance needs --components union|mutual")
+        if np.isnan(args.components_distance) or np.signbit(args.components_distance):  # (-0.0 too: bits decide)
+            raise SystemExit("--components-distance must be a distance >= 0, got %r" % args.components_distance)
+    if args.components is not None and len(device_list(args.devices)) > 1:
+        raise SystemExit("--components runs on one GPU: over --devices a rank holds only its own rows' lists, and a "
+                         "reverse entry can come from any row")
+
+
+def write_components(path, ctx, graph, mode, max_distance, read_names, strands):
+    """components.tsv of `graph` ((idx [n, k], dist [n, k]) or a ragged triple, every row of the graph):
+    Context.graph_components, then one line per row in row order: read_name, orientation (+ / - from the strand, as in
+    overlaps.tsv), component, component_size.  Returns the number of components."""
+    labels, sizes = ctx.graph_components(graph, mode=mode, max_distance=max_distance)
+    logger.info("--components %s: %d components of %d rows, the largest of %d, %d singletons", mode, sizes.size,
+                labels.size, int(sizes.max()), int(np.sum(sizes == 1)))
+    orient = np.where(np.asarray(strands, dtype=np.int64) == 0, "+", "-")
+    of_row = sizes[labels]
+    with open(path, "w") as f:
+        f.write("read_name\torientation\tcomponent\tcomponent_size\n")
+        f.writelines("%s\t%s\t%d\t%d\n" % (read_names[r], orient[r], labels[r], of_row[r]) for r in range(labels.size))
+    return int(sizes.size)
+
+
+def _gathered(blocks):
+    """the ragged graph of a radius search's row blocks, in row order"""
+    starts = np.cumsum([0] + [int(b[0][-1]) for b in blocks[:-1]])
+    indptr = np.concatenate([np.zeros(1, np.int64)] + [b[0][1:] + s for b, s in zip(blocks, starts)])
+    return indptr, np.concatenate([b[1] for b in blocks]), np.concatenate([b[2] for b in blocks])
+
+
 def write_symmetrized(path, ctx, graph, mode, read_names, strands):
     """overlaps.tsv of the union / mutual rows of `graph` ((idx [n, k], dist [n, k]) or a ragged triple, every row of
     the graph): Context.graph_symmetrize, then one fdr_overlaps_write_csr.  Returns the data lines."""
@@ -356,40 +408,49 @@ def write_symmetrized(path, ctx, graph, mode, read_names, strands):
 
 
 def write_radius_overlaps(path, index, radius, read_names, strands, block_rows=None, max_hits=None, symmetrize=None,
-                          ctx=None):
+                          ctx=None, components=None):
     """overlaps.tsv of a radius search of all rows of `index` (a SparseIndex or a DenseIndex: both have n and
     radius_search(radius, lo, hi, max_hits=)), a block of rows at a time: each block's ragged result
     is appended through fdr_overlaps_write_csr, so the host holds one block's hits.  block_rows / max_hits = None:
     RADIUS_BLOCK_ROWS / RADIUS_MAX_HITS as they stand at the call.  symmetrize ("union" / "mutual", with the Context
     ctx): the blocks are collected on the host instead (16 bytes a hit; 2^31 hits or more are refused), symmetrised in
-    one piece and written once (write_symmetrized).  Returns the data lines."""
+    one piece and written once (write_symmetrized).  components ((mode, max_distance), with ctx): the blocks are
+    collected in the same way, under the same refusal, and components.tsv of the rows as searched is written beside
+    `path` (write_components); without symmetrize the blocks are still appended as they come, so overlaps.tsv is the
+    unflagged run's.  Returns the data lines."""
     from . import _lib
     block_rows = RADIUS_BLOCK_ROWS if block_rows is None else block_rows
     max_hits = RADIUS_MAX_HITS if max_hits is None else max_hits
-    if symmetrize is not None:
-        blocks, total = [], 0
-        for lo in range(0, index.n, block_rows):
-            hi = min(index.n, lo + block_rows)
-            blocks.append(index.radius_search(radius, lo, hi, max_hits=max_hits))
-            total += int(blocks[-1][0][-1])
-            if total >= 2 ** 31:
-                raise SystemExit("--symmetrize: the radius search has found %d hits by row %d, and a graph of 2^31 "
-                                 "entries or more cannot be symmetrised: lower the radius" % (total, hi))
-        starts = np.cumsum([0] + [int(b[0][-1]) for b in blocks[:-1]])
-        indptr = np.concatenate([np.zeros(1, np.int64)] + [b[0][1:] + s for b, s in zip(blocks, starts)])
-        graph = (indptr, np.concatenate([b[1] for b in blocks]), np.concatenate([b[2] for b in blocks]))
-        del blocks
-        return write_symmetrized(path, ctx, graph, symmetrize, read_names, strands)
+    collect = symmetrize is not None or components is not None
     name_off, names = _lib.pack_names(read_names)
-    strands = np.asarray(strands, dtype=np.uint8)
+    strand_codes = np.asarray(strands, dtype=np.uint8)
     threads = global_variables.threads if global_variables.threads > 1 else 0
-    lines = 0
+    blocks, total, lines = [], 0, 0
     for lo in range(0, index.n, block_rows):
         hi = min(index.n, lo + block_rows)
         ip, idx, dist = index.radius_search(radius, lo, hi, max_hits=max_hits)
-        lines += _lib.overlaps_write_csr(path, ip, idx, dist, name_off, names, strands, row0=lo, append=lo > 0,
-                                         header=lo == 0, n_threads=threads)
+        if collect:
+            blocks.append((ip, idx, dist))
+            total += int(ip[-1])
+            if total >= 2 ** 31:
+                if symmetrize is not None:
+                    raise SystemExit("--symmetrize: the radius search has found %d hits by row %d, and a graph of 2^31 "
+                                     "entries or more cannot be symmetrised: lower the radius" % (total, hi))
+                raise SystemExit("--components: the radius search has found %d hits by row %d, and a graph of 2^31 "
+                                 "entries or more cannot be labelled: lower the radius" % (total, hi))
+        if symmetrize is None:
+            lines += _lib.overlaps_write_csr(path, ip, idx, dist, name_off, names, strand_codes, row0=lo, append=lo > 0,
+                                             header=lo == 0, n_threads=threads)
         logger.debug("radius search: rows [%d, %d), %d hits", lo, hi, int(ip[-1]))
+    if not collect:
+        return lines
+    graph = _gathered(blocks)
+    del blocks
+    if components is not None:
+        write_components(join(os.path.dirname(path), "components.tsv"), ctx, graph, components[0], components[1],
+                         read_names, strands)
+    if symmetrize is not None:
+        lines = write_symmetrized(path, ctx, graph, symmetrize, read_names, strands)
     return lines
 
 
@@ -512,7 +573,8 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                          kmer_searcher_output=None, kmer_library=None, feature_matrix=None,
                          kmer_counts=None, read_names_path=None, no_projection=False,
                          no_projection_metric="cosine", no_projection_radius=None, radius=None, rescore=None,
-                         rescore_candidates=None, radius_rescore=None, radius_rescore_bound=None, symmetrize=None):
+                         rescore_candidates=None, radius_rescore=None, radius_rescore_bound=None, symmetrize=None,
+                         components=None):
     """Stages 2-4 of the reference pipeline (__main__.py:329-391) on one GPU.  The embeddings never leave
     HBM between the projection and the search (fdr_embed_knn), and only the features P has entries for
     cross PCIe (fdr_csr_compact; the saved feature_matrix.npz is the full matrix).  no_projection: stage 4
@@ -529,7 +591,9 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     feature rows go to the device once with those values (fdr_rescore_rows_build), and each row block's projected hits
     are scored on them and cut at radius_rescore_bound (None: 1) in that metric (fdr_rescore_rows_radius).  symmetrize
     ("union" / "mutual"; None: the rows as searched): whichever of these modes ran, the graph it is about to write is
-    symmetrised on the GPU first (fdr_graph_symmetrize) and written once through fdr_overlaps_write_csr."""
+    symmetrised on the GPU first (fdr_graph_symmetrize) and written once through fdr_overlaps_write_csr.  components
+    ((mode, max_distance); None: no components.tsv): the connected components of the rows as searched, before any
+    symmetrize, are found on the GPU (fdr_graph_components) and written to components.tsv beside overlaps.tsv."""
     from . import _lib
     from .feature_extraction import _projection_csr
     if kmer_searcher_output:
@@ -551,7 +615,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
         values = None if no_projection_metric == "jaccard" else P[indices]
         with ctx.sparse_index(indptr, indices, values, n_features, metric=no_projection_metric) as index:
             rows = write_radius_overlaps(join(output_dir, "overlaps.tsv"), index, no_projection_radius, read_names,
-                                         strands, symmetrize=symmetrize, ctx=ctx)
+                                         strands, symmetrize=symmetrize, ctx=ctx, components=components)
         logger.debug("wrote %d overlap rows", rows)
         _cleanup(keep_intermediates)
         return
@@ -561,7 +625,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                     "entries", embedding_dimension, indptr.size - 1, n_features, indices.size)
         neighbor_matrix, distances = ctx.knn_sparse(indptr, indices, None, n_features, nndescent_n_neighbors,
                                                     metric="jaccard")
-        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize, ctx)
+        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize, ctx, components)
         return
     if no_projection:
         logger.info("--- 4. Nearest Neighbors Search (exact, metric = %s, on the IDF-weighted feature rows) ---",
@@ -570,7 +634,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                     "entries", embedding_dimension, indptr.size - 1, n_features, indices.size)
         neighbor_matrix, distances = ctx.knn_sparse(indptr, indices, P[indices], n_features, nndescent_n_neighbors,
                                                     metric=no_projection_metric)
-        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize, ctx)
+        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize, ctx, components)
         return
     Pc = _projection_csr(P)
     ctx.projection_load(Pc.indptr, Pc.indices, Pc.data, n_features, embedding_dimension)
@@ -597,7 +661,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
         values = rescore_values(rescore)
         neighbor_matrix, distances = ctx.sparse_rescore(indptr, indices, values, n_features, candidates, k=k,
                                                         metric=rescore)
-        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize, ctx)
+        _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize, ctx, components)
         return
     if radius is not None and radius_rescore is not None:
         bound = 1.0 if radius_rescore_bound is None else radius_rescore_bound
@@ -611,7 +675,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
             del cip, cix
             both = RescoredRadius(index, held, bound)
             rows = write_radius_overlaps(join(output_dir, "overlaps.tsv"), both, radius, read_names, strands,
-                                         symmetrize=symmetrize, ctx=ctx)
+                                         symmetrize=symmetrize, ctx=ctx, components=components)
         logger.debug("wrote %d overlap rows of %d projected hits", rows, both.candidates)
         _cleanup(keep_intermediates)
         return
@@ -622,7 +686,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                     cip.size - 1, embedding_dimension)
         with ctx.dense_index_from_csr(cip, cix) as index:
             rows = write_radius_overlaps(join(output_dir, "overlaps.tsv"), index, radius, read_names, strands,
-                                         symmetrize=symmetrize, ctx=ctx)
+                                         symmetrize=symmetrize, ctx=ctx, components=components)
         logger.debug("wrote %d overlap rows", rows)
         _cleanup(keep_intermediates)
         return
@@ -630,14 +694,19 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     logger.info("Using exact GPU k-NN in place of NNDescent (n_trees = %s, leaf_size = %s are inert)",
                 nndescent_n_trees, 200)
     neighbor_matrix, distances = ctx.embed_knn(cip, cix, nndescent_n_neighbors)
-    _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize, ctx)
+    _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize, ctx, components)
 
 
-def _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize=None, ctx=None):
+def _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize=None, ctx=None,
+            components=None):
     nbr_output_file = join(output_dir, "overlaps.tsv")
     logger.debug("Saving overlap table to %s", nbr_output_file)
-    if symmetrize is not None:
+    if symmetrize is not None or components is not None:
         graph = (np.ascontiguousarray(neighbor_matrix, dtype=np.int32), np.ascontiguousarray(distances, dtype=np.float32))
+    if components is not None:
+        write_components(join(output_dir, "components.tsv"), ctx, graph, components[0], components[1], read_names,
+                         strands)
+    if symmetrize is not None:
         rows = write_symmetrized(nbr_output_file, ctx, graph, symmetrize, read_names, strands)
     else:
         rows = write_overlaps(nbr_output_file, neighbor_matrix, distances, read_names, strands)
@@ -980,6 +1049,7 @@ def main(argv=None):
     check_sparse_shard(args)
     check_rescore(args)
     check_symmetrize(args)
+    check_components(args)
     radius_rescore_bound = check_radius_rescore(args)
     if args.no_projection_metric != "cosine" and not args.no_projection:
         raise SystemExit("--no-projection-metric %s needs --no-projection (the projected search is cosine only)"
@@ -1039,7 +1109,8 @@ def main(argv=None):
         kmer_counts=args.kmer_counts, read_names_path=args.read_names, no_projection=args.no_projection,
         no_projection_metric=args.no_projection_metric, no_projection_radius=args.no_projection_radius,
         radius=args.radius, rescore=args.rescore, rescore_candidates=args.rescore_candidates,
-        radius_rescore=args.radius_rescore, radius_rescore_bound=radius_rescore_bound, symmetrize=args.symmetrize)
+        radius_rescore=args.radius_rescore, radius_rescore_bound=radius_rescore_bound, symmetrize=args.symmetrize,
+        components=None if args.components is None else (args.components, args.components_distance))
 
 
 if __name__ == "__main__":

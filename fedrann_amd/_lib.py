@@ -32,7 +32,7 @@ SYMBOLS = (
     "fdr_dense_index_radius_fetch", "fdr_dense_index_info", "fdr_dense_index_free", "fdr_sparse_rescore",
     "fdr_rescore_rows_build", "fdr_rescore_rows_info", "fdr_rescore_rows_free", "fdr_rescore_rows_knn",
     "fdr_rescore_rows_radius", "fdr_rescore_rows_radius_fetch",
-    "fdr_graph_symmetrize", "fdr_graph_symmetrize_fetch", "fdr_graph_free",
+    "fdr_graph_symmetrize", "fdr_graph_symmetrize_fetch", "fdr_graph_free", "fdr_graph_components",
 )
 FDR_FAST_MAX_DIM = 512  # the reach of the fp16 passes, and so of the dense index (csrc/knn_plan.inc)
 FDR_MAX_K = 128
@@ -143,6 +143,7 @@ def load_library():
     L.fdr_graph_symmetrize.argtypes = [vp, i32, i64, vp, vp, vp, i64, vp]
     L.fdr_graph_symmetrize_fetch.argtypes = [vp, i64, vp, vp]
     L.fdr_graph_free.argtypes = [vp]
+    L.fdr_graph_components.argtypes = [vp, i32, i64, vp, vp, vp, ctypes.c_float, vp, vp, vp]
     L.fdr_sparse_rescore.argtypes = [vp, i32, i64, i64, vp, vp, vp, i64, i64, i32, vp, i32, vp, vp]
     L.fdr_rescore_rows_build.argtypes = [vp, i32, i64, i64, vp, vp, vp]
     L.fdr_rescore_rows_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i64),
@@ -682,6 +683,19 @@ def check_graph_symmetrize(graph, mode="union", max_entries=1 << 27):
     return code, n, indptr, idx, dist
 
 
+def check_graph_components(graph, mode="union", max_distance=None):
+    """The argument checks of Context.graph_components (fdr_graph_components repeats those of the indptr, the mode, the
+    bound and the limits); needs no GPU.  graph as check_graph_symmetrize takes it; mode "union" or "mutual"
+    ("transpose" is refused: its components are the union's); max_distance None (+inf: every entry joins) or a number
+    whose float32 bits are at most 0x7f800000 (NaN, negatives and -0.0 are refused).  All ValueError.  What the rows
+    hold is checked on the device.  Returns (mode code, n, indptr, idx, dist, the bound as float32)."""
+    from . import graph as _graph
+    code = _graph.component_mode_code(mode)
+    bound = np.array(_graph.bound_bits(max_distance), dtype=np.uint32).view(np.float32)
+    _, n, indptr, idx, dist = check_graph_symmetrize(graph, "union")
+    return code, n, indptr, idx, dist, bound
+
+
 def _row_mass_overflows(indptr, values, largest):
     """Whether a row's float32 add chain over its values (all finite and >= 0, none above `largest`) reaches +inf.  A
     chain of m such terms is at most m * largest * (1 + 2^-24)^m, below 1.07e38 for m <= 2^20 and m * largest < 1e38;
@@ -1192,8 +1206,26 @@ class Context:
                     "fdr_graph_symmetrize_fetch")
         return out_ip, out_idx, out_dist
 
+    def graph_components(self, graph, mode="union", max_distance=None):
+        """The connected components of a neighbour graph (graph as graph_symmetrize takes it), cut at a distance: rows
+        r != s are joined iff the symmetrised rows of `mode` ("union": either lists the other; "mutual": each lists the
+        other, at the smaller distance) hold (r, s) with distance bits <= those of max_distance (None: +inf, every
+        entry joins).  Returns (labels int32 [n], sizes int64 [C]), the components numbered in ascending order of
+        their smallest row: graph.component_labels, array for array, computed on the GPU (fdr_graph_components).  The
+        argument checks (check_graph_components) are ValueErrors before the library is called; an index outside
+        [0, n), a negative or NaN distance and an index twice in a row are refused by the library (FedrannHipError).
+        The context's indexes, their held radius results, a held symmetrised graph and its last k-NN trace stay as
+        they are."""
+        code, n, indptr, idx, dist, bound = check_graph_components(graph, mode, max_distance)
+        labels, sizes, found = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int64), ctypes.c_int64(-1)
+        self._check(self._L.fdr_graph_components(self._h, code, n, _ptr(indptr), _ptr(idx), _ptr(dist),
+                                                 ctypes.c_float(float(bound)), _ptr(labels), _ptr(sizes),
+                                                 ctypes.addressof(found)), "fdr_graph_components")
+        return labels, sizes[:found.value].copy()
+
     def graph_free(self):
-        """Free the device memory of graph_symmetrize (it grows with the largest graph seen): fdr_graph_free."""
+        """Free the device memory of graph_symmetrize and graph_components (it grows with the largest graph seen):
+        fdr_graph_free."""
         self._check(self._L.fdr_graph_free(self._h), "fdr_graph_free")
 
     def sparse_rescore(self, indptr, indices, values, n_features, candidates, k=None, metric="cosine", q_lo=0, out=None):

@@ -815,6 +815,22 @@ struct GraphSymScratch {
     }
 };
 
+// fdr_graph_components (graph_components.inc): the union-find over the rows and what its labelling passes make of it.
+// The graph itself goes through GraphSymScratch's input arrays.  Grows as needed; freed by fdr_graph_free and with the
+// context.
+struct GraphCompScratch {
+    DevArray<int> parent;        // [n] the union-find: parent[x] <= x, a root is its own parent
+    DevArray<int> root;          // [n] every row's root once the links are in: its component's smallest row
+    DevArray<unsigned> count;    // [n] rows per root (0 at every other row)
+    DevArray<int> flag, rank;    // [n + 1] root[r] == r (a 0 behind them); their exclusive scan, whose last element is C
+    DevArray<int> label;         // [n] rank[root[r]]
+    DevArray<long long> size;    // [n] the first C: count[] of the roots, in label order
+    template <class F>
+    auto each(F f) { return f(parent, root, count, flag, rank, label, size); }
+    size_t bytes() { return each([](auto &...a) { return (a.bytes() + ...); }); }
+    void release() { each([](auto &...a) { release_all(a...); }); }
+};
+
 // The re-score calls (sparse_rescore.inc).  RsCsr: a CSR as uploaded and what the row pass X1 makes of its rows.
 // RsLists: rectangular candidate lists, the re-scored rows before they are copied out, and the record of a refused
 // call.  fdr_sparse_rescore owns one of each (SparseRescoreScratch), valid within one call, freed with the context;
@@ -1007,6 +1023,7 @@ struct fdr_ctx {
     SparseRescoreScratch rs;  // the exact re-score of candidate lists (sparse_rescore.inc): kept until fdr_destroy
     RescoreRowSet rrs;     // the held re-score rows and their calls (sparse_rescore.inc): kept until fdr_rescore_rows_free
     GraphSymScratch gs;    // a graph's symmetrised rows and their call (graph_symmetrize.inc): kept until fdr_graph_free
+    GraphCompScratch gc;   // a graph's union-find and labels (graph_components.inc): kept until fdr_graph_free
     // timing: when enabled, every launch of kernel kind i gets its own hipEvent pair on the launch
     // stream; fdr_timing_read() sums the elapsed times of all launches since the last read
     int knn_mode = FDR_MODE_AUTO;
@@ -2454,6 +2471,7 @@ FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indp
 #include "radius_merge.inc"  // M1: the exact merge of the ranks' ragged rows of a target-sharded sparse radius search
 #include "sparse_rescore.inc"  // X1 / X2: candidate lists re-scored by exact distance on the sparse rows (fdr_sparse_rescore)
 #include "graph_symmetrize.inc"  // G1 .. G4: union, mutual and transposed rows of a neighbour graph (fdr_graph_symmetrize)
+#include "graph_components.inc"  // C0 .. C3: connected components of a neighbour graph, cut at a distance (fdr_graph_components)
 #include "kmer_search.inc"
 #include "kmer_output_loader.inc"
 #include "reads_parser.inc"

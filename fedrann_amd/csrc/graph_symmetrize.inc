@@ -35,6 +35,9 @@
 // Bounds: the host has checked the indptr (it starts at 0, never decreases, totals below 2^31) before the upload, so a
 // row's segment lies in [0, total); G2 searches row t only for 0 <= t < n whatever the entry holds, and G3 runs only
 // after the host has read an empty refusal record; every store of G3 is checked against the end of its row's segment.
+// The front (the host's indptr check, the upload, G1 and the sort by index: gs_check_indptr, gs_rows_by_index), the
+// reverse search of G2 (gs_reverse_bits) and the refusal's words (gs_refused) are functions, because
+// fdr_graph_components (graph_components.inc) starts from the same rows.
 
 constexpr unsigned GS_NO_PARTNER = 0xffffffffu;  // (a listed distance's bits are at most 0x7f800000)
 enum { GS_RULE_INDEX = 1, GS_RULE_DISTANCE = 2, GS_RULE_REPEAT = 3 };
@@ -91,6 +94,24 @@ __global__ __launch_bounds__(256) void gs_pack_kernel(long long total, long long
     gs_refuse(bad, refusal);
 }
 
+// The reverse of an entry (q -> t), 0 <= t < n, among the rows ordered by index: a binary search of row t's entries for
+// q.  The bits of (t -> q), or GS_NO_PARTNER where t does not list q.  (graph_components.inc searches with it too.)
+__device__ __forceinline__ unsigned gs_reverse_bits(const long long *__restrict__ indptr, const u64 *__restrict__ byidx,
+                                                    long long t, int q) {
+    const long long end = indptr[t + 1];
+    long long lo = indptr[t], hi = end;  // the first entry of row t with index >= q
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if ((unsigned)(byidx[mid] >> 32) < (unsigned)q) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo < end) {
+        const u64 found = byidx[lo];
+        if ((unsigned)(found >> 32) == (unsigned)q) return (unsigned)found;
+    }
+    return GS_NO_PARTNER;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void gs_count_kernel(long long total, long long n, const long long *__restrict__ indptr,
                                                        const int *__restrict__ row, const u64 *__restrict__ byidx,
@@ -111,17 +132,7 @@ __global__ __launch_bounds__(256) void gs_count_kernel(long long total, long lon
         unsigned pb = GS_NO_PARTNER;
         if ((long long)listed < n) {  // (G1 refuses every other entry; here the test keeps the search inside the rows)
             t = listed;
-            const long long end = indptr[t + 1];
-            long long lo = indptr[t], hi = end;  // the first entry of row t with index >= q
-            while (lo < hi) {
-                const long long mid = (lo + hi) >> 1;
-                if ((unsigned)(byidx[mid] >> 32) < (unsigned)q) lo = mid + 1;
-                else hi = mid;
-            }
-            if (lo < end) {
-                const u64 found = byidx[lo];
-                if ((unsigned)(found >> 32) == (unsigned)q) pb = (unsigned)found;
-            }
+            pb = gs_reverse_bits(indptr, byidx, t, q);
         }
         partner[i] = pb;
         has = pb != GS_NO_PARTNER;
@@ -209,6 +220,56 @@ static int gs_passes(int mode, int pass, hipStream_t st, GraphSymScratch &gs, lo
     return FDR_OK;
 }
 
+// ---- the front that fdr_graph_symmetrize and fdr_graph_components (graph_components.inc) share ----
+// The indptr, on the host: what keeps the kernels' loads in bounds.
+static int gs_check_indptr(const char *who, int64_t n, const int64_t *indptr) {
+    if (indptr[0] != 0) return fail(FDR_E_ARG, "%s: the indptr starts at %lld, not 0", who, (long long)indptr[0]);
+    for (int64_t r = 0; r < n; ++r)
+        if (indptr[r + 1] < indptr[r]) return fail(FDR_E_ARG, "%s: row %lld: the indptr decreases", who, (long long)r);
+    if (indptr[n] > INT32_MAX) return fail(FDR_E_ARG, "%s: the graph holds 2^31 entries or more", who);
+    return FDR_OK;
+}
+
+// The graph (a checked indptr, total = indptr[n] > 0 entries) to the device, an empty refusal record, G1, and every row
+// ordered by index in gs.byidx.  Enqueues only.
+static int gs_rows_by_index(hipStream_t st, GraphSymScratch &gs, int64_t n, long long total, const int64_t *indptr,
+                            const int32_t *idx, const float *dist) {
+    int rc;
+    const size_t rows = (size_t)n + 1;
+    if ((rc = gs.indptr.reserve(rows))) return rc;
+    if ((rc = gs.idx.reserve((size_t)total))) return rc;
+    if ((rc = gs.dist.reserve((size_t)total))) return rc;
+    if ((rc = gs.row.reserve((size_t)total))) return rc;
+    if ((rc = gs.packed.reserve((size_t)total))) return rc;
+    if ((rc = gs.byidx.reserve((size_t)total))) return rc;
+    if ((rc = gs.refusal.reserve(1))) return rc;
+    static_assert(sizeof(long long) == sizeof(int64_t), "the caller's indptr is the device's");
+    HIP_TRY(upload(gs.indptr, reinterpret_cast<const long long *>(indptr), rows, st));
+    HIP_TRY(upload(gs.idx, idx, (size_t)total, st));
+    HIP_TRY(upload(gs.dist, dist, (size_t)total, st));
+    HIP_TRY(hipMemsetAsync(gs.refusal.ptr(), 0xff, 8, st));
+    // G1, and the rows by index
+    hipLaunchKernelGGL(gs_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, (long long)n,
+                       gs.indptr.ptr(), gs.idx.ptr(), gs.dist.ptr(), gs.row.ptr(), gs.packed.ptr(), gs.refusal.ptr());
+    HIP_TRY(hipGetLastError());
+    // (All 64 bits, not [32, 64): the order by (index, bits) serves as well, and rocprim's comparator for short segments
+    // builds its mask with a shift by begin_bit + length, which a range that ends at bit 64 but starts above 0 overflows.)
+    auto by_index = [&](void *tmp, size_t &bytes) {
+        return rocprim::segmented_radix_sort_keys(tmp, bytes, gs.packed.ptr(), gs.byidx.ptr(), (unsigned)total, (unsigned)n,
+                                                  gs.indptr.ptr(), gs.indptr.ptr() + 1, 0, 64, st);
+    };
+    return rocprim_run(gs.tmp, "rocprim::segmented_radix_sort_keys", by_index);
+}
+
+// a refusal record that the host has read and found set: the call's error
+static int gs_refused(const char *who, u64 refused) {
+    const int rule = (int)(refused & 0xff);
+    const char *what = rule == GS_RULE_INDEX      ? "an index outside [0, n)"
+                       : rule == GS_RULE_DISTANCE ? "a distance that is negative or NaN (its bits must be at most 0x7f800000)"
+                                                  : "an index listed twice";
+    return fail(FDR_E_ARG, "%s: row %lld: %s", who, (long long)(refused >> 8), what);
+}
+
 FDR_EXPORT int fdr_graph_symmetrize(fdr_ctx *ctx, int32_t mode, int64_t n, const int64_t *indptr, const int32_t *idx,
                                     const float *dist, int64_t max_entries, int64_t *indptr_out) {
     static const char who[] = "graph_symmetrize";
@@ -223,11 +284,7 @@ FDR_EXPORT int fdr_graph_symmetrize(fdr_ctx *ctx, int32_t mode, int64_t n, const
     if (max_entries < 1 || max_entries > INT32_MAX)
         return fail(FDR_E_ARG, "%s: max_entries (%lld) must be in [1, 2^31)", who, (long long)max_entries);
     if (!indptr || !indptr_out) return fail(FDR_E_ARG, "%s: null indptr pointer", who);
-    // ---- the indptr, on the host: what keeps the kernels' loads in bounds ----
-    if (indptr[0] != 0) return fail(FDR_E_ARG, "%s: the indptr starts at %lld, not 0", who, (long long)indptr[0]);
-    for (int64_t r = 0; r < n; ++r)
-        if (indptr[r + 1] < indptr[r]) return fail(FDR_E_ARG, "%s: row %lld: the indptr decreases", who, (long long)r);
-    if (indptr[n] > INT32_MAX) return fail(FDR_E_ARG, "%s: the graph holds 2^31 entries or more", who);
+    if ((rc = gs_check_indptr(who, n, indptr))) return rc;
     const long long total = indptr[n];
     const size_t rows = (size_t)n + 1;
     if (total == 0) {  // (no entries: an empty result, held)
@@ -240,33 +297,12 @@ FDR_EXPORT int fdr_graph_symmetrize(fdr_ctx *ctx, int32_t mode, int64_t n, const
     const hipStream_t st = ctx->stream;
     const RadiusCall call = {st, who, n, max_entries, indptr_out};
     if ((rc = radius_reserve(rr, call))) return rc;
-    if ((rc = gs.indptr.reserve(rows))) return rc;
-    if ((rc = gs.idx.reserve((size_t)total))) return rc;
-    if ((rc = gs.dist.reserve((size_t)total))) return rc;
-    if ((rc = gs.row.reserve((size_t)total))) return rc;
-    if ((rc = gs.packed.reserve((size_t)total))) return rc;
-    if ((rc = gs.byidx.reserve((size_t)total))) return rc;
     if ((rc = gs.partner.reserve((size_t)total))) return rc;
     if ((rc = gs.fill.reserve((size_t)n))) return rc;
-    if ((rc = gs.refusal.reserve(1))) return rc;
-    static_assert(sizeof(long long) == sizeof(int64_t), "the caller's indptr is the device's");
-    HIP_TRY(upload(gs.indptr, reinterpret_cast<const long long *>(indptr), rows, st));
-    HIP_TRY(upload(gs.idx, idx, (size_t)total, st));
-    HIP_TRY(upload(gs.dist, dist, (size_t)total, st));
-    HIP_TRY(hipMemsetAsync(gs.refusal.ptr(), 0xff, 8, st));
     HIP_TRY(hipMemsetAsync(gs.fill.ptr(), 0, (size_t)n * 4, st));
-    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    const dim3 block(256);
     // G1, and the rows by index
-    hipLaunchKernelGGL(gs_pack_kernel, grid, block, 0, st, total, (long long)n, gs.indptr.ptr(), gs.idx.ptr(),
-                       gs.dist.ptr(), gs.row.ptr(), gs.packed.ptr(), gs.refusal.ptr());
-    HIP_TRY(hipGetLastError());
-    // (All 64 bits, not [32, 64): the order by (index, bits) serves as well, and rocprim's comparator for short segments
-    // builds its mask with a shift by begin_bit + length, which a range that ends at bit 64 but starts above 0 overflows.)
-    auto by_index = [&](void *tmp, size_t &bytes) {
-        return rocprim::segmented_radix_sort_keys(tmp, bytes, gs.packed.ptr(), gs.byidx.ptr(), (unsigned)total, (unsigned)n,
-                                                  gs.indptr.ptr(), gs.indptr.ptr() + 1, 0, 64, st);
-    };
-    if ((rc = rocprim_run(gs.tmp, "rocprim::segmented_radix_sort_keys", by_index))) return rc;
+    if ((rc = gs_rows_by_index(st, gs, n, total, indptr, idx, dist))) return rc;
     // G2, the scan, the refusal record, indptr_out, the cap
     if ((rc = gs_passes(mode, 2, st, gs, total, n))) return rc;
     if ((rc = radius_scan(rr, gs.tmp, call, rr.off.ptr()))) return rc;
@@ -275,13 +311,7 @@ FDR_EXPORT int fdr_graph_symmetrize(fdr_ctx *ctx, int32_t mode, int64_t n, const
     HIP_TRY(download(gs.h_off.data(), rr.off, rows, st));
     HIP_TRY(download(&refused, gs.refusal, 1, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (refused != TM_NONE) {  // (nothing has been written to indptr_out)
-        const int rule = (int)(refused & 0xff);
-        const char *what = rule == GS_RULE_INDEX      ? "an index outside [0, n)"
-                           : rule == GS_RULE_DISTANCE ? "a distance that is negative or NaN (its bits must be at most 0x7f800000)"
-                                                      : "an index listed twice";
-        return fail(FDR_E_ARG, "%s: row %lld: %s", who, (long long)(refused >> 8), what);
-    }
+    if (refused != TM_NONE) return gs_refused(who, refused);  // (nothing has been written to indptr_out)
     for (size_t r = 0; r < rows; ++r) indptr_out[r] = gs.h_off[r];
     const long long out = rr.counted = gs.h_off[n];
     if (out > max_entries)  // (the one refusal that has written its output, as the radius searches')
@@ -331,5 +361,6 @@ FDR_EXPORT int fdr_graph_free(fdr_ctx *ctx) {
     if (int rc = use_device(ctx)) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->gs.release();
+    ctx->gc.release();
     return FDR_OK;
 }

@@ -13,6 +13,20 @@ bit order is then value order).  Row r of the result holds s
 and every row is strictly ascending by (distance bits, index), like every other ragged result of the package, so
 _lib.overlaps_write_csr takes it as it is.  Refused (ValueError naming the smallest (row, rule), rules in this order):
 an index outside [0, n); distance bits above 0x7f800000; an index listed twice in one row.
+
+Components (component_labels: the statement fdr_graph_components, csrc/graph_components.inc, is held to).  For a graph
+G, a mode m in {union, mutual} and a bound B, the components are the connected components of an undirected graph on the
+n rows: rows r != s are joined iff symmetrize_rows(G, m) has the entry (r, s) with distance bits <= bits(B).  B is a
+float32 with 0 <= bits(B) <= 0x7f800000; the default, +inf, joins every entry.  Spelled out:
+
+    union      an entry (q -> t) with bits <= bits(B) joins q and t
+    mutual     q and t are joined iff each lists the other and min(b(q -> t), b(t -> q)) <= bits(B)
+
+Self entries join nothing; the bound is inclusive and compares bit patterns, so 0.0 and the smallest subnormal are
+different distances.  label[r] in [0, C) numbers the components in ascending order of their smallest row, so the labels
+are a function of the edge set alone; size[c], int64, is the number of rows of component c.  A graph is refused for
+exactly what symmetrize_rows refuses, in both modes and in the same words; transpose is refused as a mode (its
+components are union's).
 """
 import numpy as np
 
@@ -61,10 +75,9 @@ def mode_code(mode):
     return MODES[mode]
 
 
-def symmetrize_rows(indptr, idx, dist, mode):
-    """The union / mutual / transposed rows of the ragged graph (indptr, idx, dist), see the module's docstring:
-    (indptr int64 [n + 1], idx int32, dist float32), a function of the input alone."""
-    code = mode_code(mode)
+def _entries(indptr, idx, dist):
+    """What symmetrize_rows and component_labels share: the rules, then every entry (q -> t) with its reverse.  Returns
+    (n, q int64, t int64, bits uint32, has bool: t lists q, low uint32: the smaller bits of the directions present)."""
     indptr, idx, dist = as_ragged((indptr, idx, dist))
     n = indptr.size - 1
     if n < 1:
@@ -86,6 +99,14 @@ def symmetrize_rows(indptr, idx, dist, mode):
     at = np.minimum(np.searchsorted(pair, t * n + rows), max(t.size - 1, 0))
     has = pair[at] == t * n + rows if t.size else np.zeros(0, bool)
     low = np.where(has, np.minimum(bits, bits[by_index][at]), bits) if t.size else bits
+    return n, rows, t, bits, has, low
+
+
+def symmetrize_rows(indptr, idx, dist, mode):
+    """The union / mutual / transposed rows of the ragged graph (indptr, idx, dist), see the module's docstring:
+    (indptr int64 [n + 1], idx int32, dist float32), a function of the input alone."""
+    code = mode_code(mode)
+    n, rows, t, bits, has, low = _entries(indptr, idx, dist)
     if code == MODES["union"]:
         r, s, b = np.concatenate([rows, t[~has]]), np.concatenate([t, rows[~has]]), np.concatenate([low, bits[~has]])
     elif code == MODES["mutual"]:
@@ -96,3 +117,44 @@ def symmetrize_rows(indptr, idx, dist, mode):
     out = np.zeros(n + 1, np.int64)
     np.cumsum(np.bincount(r, minlength=n), out=out[1:])
     return out, s[order].astype(np.int32), np.ascontiguousarray(b[order]).view(np.float32)
+
+
+def component_mode_code(mode):
+    code = mode_code(mode)
+    if code == MODES["transpose"]:
+        raise ValueError("mode must be union or mutual for components: those of the transposed rows are the union's")
+    return code
+
+
+def bound_bits(max_distance):
+    """The bits of a components bound as float32; None is +inf, which joins every entry.  ValueError unless
+    0 <= bits <= 0x7f800000: NaN, negatives and -0.0 are refused."""
+    if max_distance is None:
+        return MAX_BITS
+    if isinstance(max_distance, (bool, np.bool_)) or not isinstance(max_distance, (int, float, np.integer, np.floating)):
+        raise ValueError("max_distance must be a number or None, got %r" % (max_distance,))
+    with np.errstate(over="ignore"):
+        found = int(np.array(max_distance, dtype=np.float64).astype(np.float32).view(np.uint32))
+    if found > MAX_BITS:
+        raise ValueError("max_distance must be a float32 that is neither negative (-0.0 included) nor NaN: its bits "
+                         "must be at most 0x7f800000, got %r" % (max_distance,))
+    return found
+
+
+def component_labels(indptr, idx, dist, mode="union", max_distance=None):
+    """The connected components of the ragged graph (indptr, idx, dist) under `mode` ("union" / "mutual"), cut at
+    max_distance (None: +inf), see the module's docstring: (labels int32 [n], sizes int64 [C]), components numbered in
+    ascending order of their smallest row.  A function of the edge set alone; refuses what symmetrize_rows refuses."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    code = component_mode_code(mode)
+    bound = bound_bits(max_distance)
+    n, rows, t, bits, has, low = _entries(indptr, idx, dist)
+    joined = (rows != t) & ((bits <= bound) if code == MODES["union"] else (has & (low <= bound)))
+    links = coo_matrix((np.ones(int(joined.sum()), np.int8), (rows[joined], t[joined])), shape=(n, n))
+    _, found = connected_components(links, directed=False)
+    _, first = np.unique(found, return_index=True)  # every component's smallest row
+    number = np.empty(first.size, np.int32)
+    number[np.argsort(first)] = np.arange(first.size, dtype=np.int32)
+    labels = number[found]
+    return labels, np.bincount(labels, minlength=first.size).astype(np.int64)

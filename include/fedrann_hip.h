@@ -421,6 +421,37 @@ int fdr_graph_symmetrize(fdr_ctx *ctx, int32_t mode, int64_t n, const int64_t *i
 int fdr_graph_symmetrize_fetch(fdr_ctx *ctx, int64_t entries, int32_t *idx_out, float *dist_out);
 int fdr_graph_free(fdr_ctx *ctx);
 
+/* ---- connected components of a neighbour graph, cut at a distance  (which reads hang together: bins that assemble
+ *      independently, singletons and small islands to drop, the distance at which the graph falls apart.  The reference
+ *      has no counterpart: it writes directed pairs, __main__.py get_output_dataframe, and stops) ----
+ * The graph is fdr_graph_symmetrize's: n rows, indptr int64 [n + 1], idx int32 and dist float32 [indptr[n]], rows in any
+ * order.  For mode FDR_GRAPH_UNION or FDR_GRAPH_MUTUAL and a bound max_distance, rows r != s are joined iff the
+ * symmetrised rows of that mode hold the entry (r, s) with distance bits <= bits(max_distance):
+ *   FDR_GRAPH_UNION   an entry (q -> t) with bits <= bits(max_distance) joins q and t;
+ *   FDR_GRAPH_MUTUAL  q and t are joined iff each lists the other and min(b(q->t), b(t->q)) <= bits(max_distance);
+ * a self entry joins nothing; the bound is inclusive and compares bit patterns (0.0 and the smallest subnormal are
+ * different distances); +inf joins every entry.  The components are the connected components of those joins.
+ * label_out int32 [n]: label_out[r] in [0, C), the components numbered in ascending order of their smallest row, so the
+ * labels are a function of the edge set alone (two runs give the same bytes).  size_out int64 [n] or NULL: its first C
+ * elements take the components' row counts in label order, the rest are left as they were.  *n_components_out = C.
+ * fedrann_amd.graph.component_labels is the model.  Host pointers; the call synchronises.
+ * Checked on the host before anything is uploaded (FDR_E_ARG): the mode (FDR_GRAPH_TRANSPOSE is refused: its components
+ * are the union's); 1 <= n < 2^31; the bits of max_distance at most 0x7f800000 (NaN, negatives and -0.0 are refused); the
+ * indptr starts at 0, never decreases and totals below 2^31; null pointers (idx / dist may be null for a graph without
+ * entries, which gives C = n, labels 0 .. n - 1 and sizes of 1 with nothing uploaded).  Checked on the device before
+ * anything is written to the outputs (FDR_E_ARG, fdr_last_error names the rule and the smallest (row, rule) that breaks
+ * one, in fdr_graph_symmetrize's words, in both modes): an index outside [0, n); distance bits above 0x7f800000; an index
+ * listed twice in one row.
+ * The call touches neither the sparse index, the dense index, the re-score rows, their held radius results, the held
+ * symmetrised graph (fdr_graph_symmetrize_fetch after it still returns that graph) nor fdr_last_knn_trace.  Its device
+ * buffers (28 bytes per entry, shared with fdr_graph_symmetrize's input, and 40 per row) belong to the context, only
+ * grow and are freed by fdr_graph_free and fdr_destroy.  Cost: one segmented sort (the rows by index), in mutual mode one
+ * binary search per entry in the listed row, and a lock-free union-find; DESIGN.md section 5. */
+int fdr_graph_components(fdr_ctx *ctx, int32_t mode /* FDR_GRAPH_UNION | FDR_GRAPH_MUTUAL */, int64_t n,
+                         const int64_t *indptr, const int32_t *idx, const float *dist, float max_distance,
+                         int32_t *label_out /* [n] */, int64_t *size_out /* [n] or NULL */,
+                         int64_t *n_components_out);
+
 /* ---- re-score candidate lists by exact distance on the sparse rows  (the second stage of an approximate search:
  *      NNDescent_ava.get_neighbors on the embeddings names the neighbours, nearest_neighbors.py:39-55, the boundary this
  *      library replaces; their distances there are the projection's, and this call puts the feature rows' own in their
