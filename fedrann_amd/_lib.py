@@ -24,7 +24,7 @@ SYMBOLS = (
     "fdr_kmer_output_append", "fdr_last_query_paths", "fdr_last_knn_trace", "fdr_kmer_count_export_dev",
     "fdr_kmer_count_merge_dev", "fdr_kmer_count_merge", "fdr_set_knn_capture", "fdr_last_candidates",
     "fdr_last_range_sets", "fdr_knn_sparse", "fdr_set_live_chunks", "fdr_knn_sparse_metric",
-    "fdr_set_live_skip", "fdr_last_live_stage_lists", "fdr_set_rerank_compact",
+    "fdr_set_live_skip", "fdr_last_live_stage_lists", "fdr_set_rerank_compact", "fdr_set_pass_tail",
     "fdr_sparse_index_build", "fdr_sparse_index_search", "fdr_sparse_index_info", "fdr_sparse_index_free",
     "fdr_sparse_index_query", "fdr_topk_merge", "fdr_radius_merge", "fdr_sparse_index_radius_search", "fdr_sparse_index_radius_query",
     "fdr_sparse_index_radius_fetch", "fdr_overlaps_write_csr",
@@ -66,7 +66,8 @@ class KnnTrace(ctypes.Structure):
             "exact_qsets", "generic", "exact_segments", "pass_live", "pass_live_items_2", "pass_live_items_3",
             "pass_live_items_4", "pass_live_items_5", "pass_live_items_6", "pass_live_dense_items", "skip_live")] + \
         [(n, ctypes.c_int64) for n in ("skip_stages_walked", "skip_stages_skipped", "rerank_compact_long")] + \
-        [(n, ctypes.c_int32) for n in ("rerank_compact", "rerank_compact_entries")]
+        [(n, ctypes.c_int32) for n in ("rerank_compact", "rerank_compact_entries", "pass_group_order",
+                                       "rerank_early_queries")]
 
 
 class FedrannHipError(RuntimeError):
@@ -170,6 +171,7 @@ def load_library():
     L.fdr_set_dedup_mode.argtypes = [vp, ctypes.c_int]
     L.fdr_set_live_chunks.argtypes = [vp, ctypes.c_int]
     L.fdr_set_live_skip.argtypes = [vp, ctypes.c_int]
+    L.fdr_set_pass_tail.argtypes = [vp, ctypes.c_int]
     L.fdr_set_rerank_compact.argtypes = [vp, ctypes.c_int]
     L.fdr_last_live_stage_lists.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp]
     L.fdr_last_unique.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
@@ -828,6 +830,13 @@ class Context:
         results, see include/fedrann_hip.h."""
         code = {"auto": 0, "off": 1}[mode]
         self._check(self._L.fdr_set_live_skip(self._h, code), "fdr_set_live_skip")
+
+    def set_pass_tail(self, mode):
+        """The end of the live-chunk pass: "auto" (default: the groups in descending cost) or "off" (ascending NL);
+        "order", "early", "early_group" force the order alone, or the order and the merge + re-rank of finished groups
+        under the pass's last launches (tests, measurements) -- same results, see include/fedrann_hip.h."""
+        code = {"auto": 0, "off": 1, "order": 2, "early": 3, "early_group": 4}[mode]
+        self._check(self._L.fdr_set_pass_tail(self._h, code), "fdr_set_pass_tail")
 
     def set_rerank_compact(self, mode):
         """Re-rank from compact rows at d <= 128: "auto" (default: on unless too many rows overflow their record),

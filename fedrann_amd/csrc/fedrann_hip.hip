@@ -1031,6 +1031,8 @@ struct fdr_ctx {
     int live_mode = FDR_LIVE_AUTO;  // fdr_set_live_chunks
     std::vector<unsigned> live_host;  // the live-chunk plan's read-back: the query blocks' masks
     int skip_mode = FDR_SKIP_AUTO;    // fdr_set_live_skip
+    int tail_mode = FDR_TAIL_AUTO;    // fdr_set_pass_tail
+    std::vector<hipEvent_t> tail_ev;  // "this queue has been given group g's last launch" (launch_rounds), made on demand
     std::vector<int> skip_host;       // ... and the lengths of the stage lists, [segment][mask value]
     int compact_mode = FDR_COMPACT_AUTO;  // fdr_set_rerank_compact
     KnnCallRecord last;  // what the fdr_last_* getters report
@@ -1150,6 +1152,7 @@ FDR_EXPORT int fdr_destroy(fdr_ctx *ctx) {
         }
     for (hipEvent_t e : ctx->aux_ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->tail_ev) (void)hipEventDestroy(e);
     delete ctx;
     return FDR_OK;
 }
@@ -1256,6 +1259,12 @@ FDR_EXPORT int fdr_set_dedup_mode(fdr_ctx *ctx, int mode) {
 FDR_EXPORT int fdr_set_live_chunks(fdr_ctx *ctx, int mode) {
     if (!ctx || mode < FDR_LIVE_AUTO || mode > FDR_LIVE_FORCE) return fail(FDR_E_ARG, "bad live-chunk mode");
     ctx->live_mode = mode;
+    return FDR_OK;
+}
+
+FDR_EXPORT int fdr_set_pass_tail(fdr_ctx *ctx, int mode) {
+    if (!ctx || mode < FDR_TAIL_AUTO || mode > FDR_TAIL_EARLY_GROUP) return fail(FDR_E_ARG, "bad pass-tail mode");
+    ctx->tail_mode = mode;
     return FDR_OK;
 }
 
@@ -1544,21 +1553,34 @@ static int no_kernel(int shape) {
 // caller's stream.  launch(stream, workgroups, first item, group) queues one.  Timed as one `kind` span over all launches
 // when they overlap on several queues (their own spans would count the same time twice), else a span per launch
 // (span_each) or one around them all.
-struct Rounds { int launches = 0, queues = 0; };
-template <class Launch>
+//
+// Work of a group alone (`trigger` != FDR_TAIL_TRIGGER_NONE; the live-chunk pass's merge and re-rank): early(stream,
+// group) queues it on ONE further stream, ctx->aux_stream[2], at the group's ready point (round_ready_points) -- behind
+// an event on every queue, i.e. behind that queue's last launch of the group -- and r.early[group] says so; the caller
+// runs what is left behind the join.  The span of the pass ends at the join of the pass's queues; the further stream
+// joins behind it.  Only with at most two queues for the pass: three streams in all.
+struct Rounds {
+    int launches = 0, queues = 0;
+    std::vector<char> early;  // [group]: its own work was queued in front of the join
+};
+template <class Launch, class Early>
 static int launch_rounds(fdr_ctx *ctx, const KnnPlan &p, const std::vector<long long> &items, int max_queues, int kind,
-                         bool span_each, hipStream_t st, Rounds &r, Launch launch) {
+                         bool span_each, hipStream_t st, Rounds &r, Launch launch, int trigger, Early early) {
     const int dealt = p.cohort > 0 ? std::max(1, std::min(p.queues, max_queues)) : 1;
     const std::vector<RoundLaunch> sched = round_schedule(items, p.cohort > 0 ? p.cohort : 0, dealt);
     const int nqueues = sched.size() > 1 ? dealt : 1;
+    const std::vector<int> ready = round_ready_points(sched, items.size(), nqueues, nqueues <= 2 ? trigger : FDR_TAIL_TRIGGER_NONE);
+    const bool tail = std::any_of(ready.begin(), ready.end(), [](int at) { return at >= 0; });
+    r.early.assign(items.size(), 0);
     hipStream_t qs[4] = {st, st, st, st};
-    if (nqueues > 1) {
+    if (nqueues > 1 || tail) {
         if (!ctx->aux_ev[0]) {
             for (hipStream_t &a : ctx->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&a, hipStreamNonBlocking));
             for (hipEvent_t &e : ctx->aux_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
         for (int q = 1; q < nqueues; ++q) qs[q] = ctx->aux_stream[q - 1];
     }
+    const hipStream_t ts = ctx->aux_stream[2];  // (the pass's own queues: the caller's and aux_stream[0])
     const bool one_span = nqueues > 1 || !span_each;
     int trc;
     if (one_span && (trc = timing_begin(ctx, kind, st))) return trc;
@@ -1566,7 +1588,25 @@ static int launch_rounds(fdr_ctx *ctx, const KnnPlan &p, const std::vector<long 
         HIP_TRY(hipEventRecord(ctx->aux_ev[0], st));
         for (int q = 1; q < nqueues; ++q) HIP_TRY(hipStreamWaitEvent(qs[q], ctx->aux_ev[0], 0));
     }
-    for (const RoundLaunch &l : sched) {
+    size_t ev_used = 0;
+    for (size_t i = 0; i < sched.size(); ++i) {
+        const RoundLaunch &l = sched[i];
+        bool waited = false;
+        for (size_t g = 0; tail && g < ready.size(); ++g) {
+            if (ready[g] != (int)i) continue;
+            for (int q = 0; q < nqueues && !waited; ++q) {  // behind what every queue has been given so far
+                if (ev_used == ctx->tail_ev.size()) {
+                    hipEvent_t e;
+                    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                    ctx->tail_ev.push_back(e);
+                }
+                HIP_TRY(hipEventRecord(ctx->tail_ev[ev_used], qs[q]));
+                HIP_TRY(hipStreamWaitEvent(ts, ctx->tail_ev[ev_used++], 0));
+            }
+            waited = true;
+            if ((trc = early(ts, (int)g))) return trc;
+            r.early[g] = 1;
+        }
         const hipStream_t ls = qs[l.queue];
         if (!one_span && (trc = timing_begin(ctx, kind, ls))) return trc;
         launch(ls, (unsigned)l.grid, l.base, l.group);
@@ -1579,7 +1619,18 @@ static int launch_rounds(fdr_ctx *ctx, const KnnPlan &p, const std::vector<long 
         HIP_TRY(hipEventRecord(ctx->aux_ev[q], qs[q]));
         HIP_TRY(hipStreamWaitEvent(st, ctx->aux_ev[q], 0));
     }
-    return one_span ? timing_end(ctx, kind, st) : FDR_OK;
+    if (one_span && (trc = timing_end(ctx, kind, st))) return trc;
+    if (ev_used > 0) {  // ... and, behind the pass's span, for the groups' early work
+        HIP_TRY(hipEventRecord(ctx->aux_ev[3], ts));
+        HIP_TRY(hipStreamWaitEvent(st, ctx->aux_ev[3], 0));
+    }
+    return FDR_OK;
+}
+template <class Launch>
+static int launch_rounds(fdr_ctx *ctx, const KnnPlan &p, const std::vector<long long> &items, int max_queues, int kind,
+                         bool span_each, hipStream_t st, Rounds &r, Launch launch) {
+    return launch_rounds(ctx, p, items, max_queues, kind, span_each, st, r, launch, FDR_TAIL_TRIGGER_NONE,
+                         [](hipStream_t, int) { return FDR_OK; });
 }
 
 // The argument checks of a k-NN call, before anything is routed or recorded.  (The workspace's SIZE is checked by the
@@ -1658,7 +1709,21 @@ struct PrefilterCall {
     // the stages, in the order launch_knn_prefilter runs them (a call takes one of the two passes)
     int setup(), pass_dense(Rounds &r), pass_live(Rounds &r);
     int certify(PrefilterCounts &n), range(PrefilterCounts &n), exact_rest(const PrefilterCounts &n);
+    // The queries certify() still has to merge and re-rank behind the join: all of them (one entry, perm == null), or
+    // the groups of the live-chunk pass whose work was not queued under the pass (pass_live).
+    std::vector<QuerySel> late;
+    QuerySel all_queries() const { return QuerySel{nullptr, nullptr, (int)a.nq, (int)a.nq}; }
+    int launch_merge(hipStream_t s, const QuerySel &sel), launch_rerank(hipStream_t s, const QuerySel &sel);
 };
+
+// What AUTO makes of fdr_set_pass_tail: each part is on only if it cleared the parent's run-to-run range on its own
+// (docs/experiments.md A-36).  The descending order did (0.92 ms a step against a range of 0.56); the early merge +
+// re-rank gained 0.33 ms more in six of six paired runs, which is inside that range: measured, kept behind
+// FDR_TAIL_EARLY, off in AUTO.
+#ifndef FDR_TAIL_AUTO_MODE
+#define FDR_TAIL_AUTO_MODE FDR_TAIL_ORDER
+#endif
+static int pass_tail_mode(const fdr_ctx *ctx) { return ctx->tail_mode == FDR_TAIL_AUTO ? FDR_TAIL_AUTO_MODE : ctx->tail_mode; }
 
 // Conversion and set-up, timed as "rerank": fp16 copies, zero bits, ordered and blocked copies, the keys' index bits.
 int PrefilterCall::setup() {
@@ -1735,6 +1800,7 @@ int PrefilterCall::setup() {
 
 // The dense candidate pass: rounds on up to four queues (one queue: every launch its own timed span).
 int PrefilterCall::pass_dense(Rounds &r) {
+    late.assign(1, all_queries());
     return launch_rounds(ctx, p, {(long long)p.nqb * p.nseg}, 4, FDR_KERNEL_KNN_PREFILTER, true, a.st, r,
                          [&](hipStream_t s, unsigned grid, int base, int) {
         hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh().nw), lds(), s, p1_q, (int)a.nq, p1_t, (int)a.nt, (int)a.t_base,
@@ -1771,11 +1837,24 @@ int PrefilterCall::pass_live(Rounds &r) {
     HIP_TRY(hipMemcpyAsync(L.live_order, lp.order.data(), (size_t)nqb * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));  // (pageable sources that end with this function)
     tr.pass_live = 1;
+    // The groups in issue order (fdr_set_pass_tail): the parent's ascending NL, or the dense group first and the
+    // cheapest items last; with the early re-rank, every group but the last is merged and re-ranked under the pass.
+    const int tail = pass_tail_mode(ctx);
+    const std::vector<int> issue = live_issue_order(lp, tail != FDR_TAIL_OFF);
+    const int trigger = tail == FDR_TAIL_EARLY ? FDR_TAIL_TRIGGER_LAST : tail == FDR_TAIL_EARLY_GROUP ? FDR_TAIL_TRIGGER_GROUP
+                                                                                                    : FDR_TAIL_TRIGGER_NONE;
     int dense_nq = 0;  // queries of the gathered dense group
     std::vector<long long> items;
-    for (const LiveGroup &g : lp.groups) {
+    std::vector<QuerySel> sels;    // [issued group]: its queries, for the merge and the re-rank
+    std::vector<int> sel_queries;  // ... and their number
+    for (size_t gi = 0; gi < issue.size(); ++gi) {
+        const LiveGroup &g = lp.groups[(size_t)issue[gi]];
+        tr.pass_group_order |= g.nl << (4 * (int)gi);
         items.push_back((long long)g.count * p.nseg);
+        const int last_block = lp.order[(size_t)(g.first + g.count - 1)];  // (ascending: only the last one can be short)
+        sel_queries.push_back((g.count - 1) * 256 + (int)std::min<int64_t>(256, a.nq - (int64_t)last_block * 256));
         if (g.nl != FDR_LIVE_DENSE) {
+            sels.push_back(QuerySel{L.live_order + g.first, ord.perm_q, g.count * 256, (int)a.nq});
             tr.pass_live_items[g.nl - FDR_LIVE_MIN_NL] = g.count * p.nseg;
             for (int sg = 0; sg < p.nseg; ++sg) {  // the stages its work items walk, of those the segments hold
                 const int len = std::min<int>((int)a.nt, p.segs.b[sg + 1]) - p.segs.b[sg];
@@ -1789,8 +1868,8 @@ int PrefilterCall::pass_live(Rounds &r) {
             continue;
         }
         tr.pass_live_dense_items = g.count * p.nseg;
-        const int last = lp.order[(size_t)(g.first + g.count - 1)];  // (ascending: only the last one can be short)
-        dense_nq = (g.count - 1) * 256 + (int)std::min<int64_t>(256, a.nq - (int64_t)last * 256);
+        dense_nq = sel_queries.back();
+        sels.push_back(QuerySel{nullptr, L.live_perm, dense_nq, dense_nq});
         hipLaunchKernelGGL(live_gather_dense_kernel, dim3((unsigned)g.count), dim3(256), 0, st, p1_q, ord.perm_q,
                            (const unsigned *)R.shared, (int)a.nq, (const int *)(L.live_order + g.first), L.live_hq,
                            L.live_perm, L.live_tau);
@@ -1799,9 +1878,9 @@ int PrefilterCall::pass_live(Rounds &r) {
         if (live_lds_bytes(nl) > 32768)
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kLiveKernels[nl - FDR_LIVE_MIN_NL]),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)live_lds_bytes(nl)));
-    return launch_rounds(ctx, p, items, 4, FDR_KERNEL_KNN_PREFILTER, false, st, r,
+    const int rc = launch_rounds(ctx, p, items, 4, FDR_KERNEL_KNN_PREFILTER, false, st, r,
                          [&](hipStream_t s, unsigned grid, int base, int group) {
-        const LiveGroup &g = lp.groups[(size_t)group];
+        const LiveGroup &g = lp.groups[(size_t)issue[(size_t)group]];
         if (g.nl == FDR_LIVE_DENSE)
             hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sh().nw), lds(), s, (const _Float16 *)L.live_hq, dense_nq, p1_t,
                                (int)a.nt, (int)a.t_base, p.segs, kp, p.nq_pad, R.partial, L.live_tau, ib, base, g.count,
@@ -1812,20 +1891,60 @@ int PrefilterCall::pass_live(Rounds &r) {
                                R.partial, R.shared, ib, base, g.count, (const int *)(L.live_order + g.first),
                                (const unsigned *)L.live_ids, ord, (const unsigned *)L.live_masks,
                                reinterpret_cast<const unsigned *>(L.live_lists), (const int *)L.live_lens);
+    }, trigger, [&](hipStream_t s, int group) {  // a complete group: its queries' lists are final (a span of its own)
+        int erc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, s);
+        if (erc || (erc = launch_merge(s, sels[(size_t)group])) || (erc = launch_rerank(s, sels[(size_t)group]))) return erc;
+        tr.rerank_early_queries += sel_queries[(size_t)group];
+        return timing_end(ctx, FDR_KERNEL_KNN_RERANK, s);
     });
+    if (rc) return rc;
+    if (trigger == FDR_TAIL_TRIGGER_NONE) {  // (one merge and one re-rank for everybody, as without the switch)
+        late.assign(1, all_queries());
+        return FDR_OK;
+    }
+    late.clear();
+    for (size_t i = 0; i < sels.size(); ++i)
+        if (!r.early[i]) late.push_back(sels[i]);
+    return FDR_OK;
 }
 
-// Key merge and capture, certificate + exact re-rank, zero answers; the 12-byte read-back that sizes the passes below.
+// The key merge of the queries `sel` on `s`: their segment lists -> L.cand.
+int PrefilterCall::launch_merge(hipStream_t s, const QuerySel &sel) {
+    const int64_t mq = p.nseg * L.kp <= 64 ? 4 * MERGE_QPW : 4;  // queries per workgroup of knn_merge_keys_kernel
+    hipLaunchKernelGGL(knn_merge_keys_kernel, dim3((unsigned)((sel.n + mq - 1) / mq)), dim3(256), 0, s,
+                       (const u64 *)R.partial, p.nseg, sel, p.nq_pad, L.kp, L.cand);
+    HIP_TRY(hipGetLastError());
+    return FDR_OK;
+}
+
+// Certificate + exact re-rank of the queries `sel` on `s`.  Every launch of a call appends to the same exact, zero and
+// range lists through the same counters (cleared once, in setup()).
+int PrefilterCall::launch_rerank(hipStream_t s, const QuerySel &sel) {
+    const float margin = 2.0f * prefilter_eps(ib) + 4.0e-7f;
+    // Beside the records the kernel's dense batches are short (the instance of RERANK_ROWS_COMPACT rows).  Whether the
+    // records are read is the kernel's own decision, from the long-row count their build left in counter[8] (knn_workspace.inc:
+    // RC_LONG_SHARE): no read-back in front of this launch.
+    const auto rerank = L.rc ? knn_rerank_kernel<RERANK_ROWS_COMPACT> : knn_rerank_kernel<RERANK_ROWS_DENSE>;
+    const int rerank_lds = L.rc ? RERANK_LDS_BYTES(RERANK_ROWS_COMPACT) : RERANK_LDS_BYTES(RERANK_ROWS_DENSE);
+    const int long_limit = ctx->compact_mode == FDR_COMPACT_FORCE ? 0x7fffffff : (int)(a.nt / RC_LONG_SHARE);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(rerank), hipFuncAttributeMaxDynamicSharedMemorySize, rerank_lds));
+    hipLaunchKernelGGL(rerank, dim3((unsigned)((sel.n + 3) / 4)), dim3(256), rerank_lds, s,
+                       (const u64 *)L.cand, L.kp, a.k, a.Qhat, a.qzero, a.That, (int)a.nq, dp, (int)a.t_base, margin,
+                       a.idx, a.dist, L.counter, L.flagged, L.rlist, L.theta, L.path, (const unsigned char *)L.rc, long_limit, sel);
+    HIP_TRY(hipGetLastError());
+    return FDR_OK;
+}
+
+// Key merge and capture, certificate + exact re-rank -- of the queries that are still `late` --, zero answers; the
+// 12-byte read-back that sizes the passes below.
 int PrefilterCall::certify(PrefilterCounts &n) {
     const hipStream_t st = a.st;
     const int kp = L.kp, k = a.k;
     const int64_t nq = a.nq;
     int trc;
     if ((trc = timing_begin(ctx, FDR_KERNEL_KNN_RERANK, st))) return trc;
-    const int64_t mq = p.nseg * kp <= 64 ? 4 * MERGE_QPW : 4;  // queries per workgroup of knn_merge_keys_kernel
-    hipLaunchKernelGGL(knn_merge_keys_kernel, dim3((unsigned)((nq + mq - 1) / mq)), dim3(256), 0, st,
-                       (const u64 *)R.partial, p.nseg, (int)nq, p.nq_pad, kp, L.cand);
-    HIP_TRY(hipGetLastError());
+    for (const QuerySel &sel : late)
+        if ((trc = launch_merge(st, sel))) return trc;
     if (ctx->cap.what & FDR_CAPTURE_CANDIDATES) {  // (test support: fdr_last_candidates)
         if ((trc = ctx->cap.cand.reserve((size_t)nq * kp))) return trc;
         HIP_TRY(ctx->cap.keep(ctx->cap.cand, 0, L.cand, (size_t)nq * kp, st));
@@ -1835,17 +1954,8 @@ int PrefilterCall::certify(PrefilterCounts &n) {
         ctx->cap.stream = st;
         ctx->cap.cand_valid = true;
     }
-    const float margin = 2.0f * prefilter_eps(ib) + 4.0e-7f;
-    // Beside the records the kernel's dense batches are short (the instance of RERANK_ROWS_COMPACT rows).  Whether the
-    // records are read is the kernel's own decision, from the long-row count their build left in counter[8] (knn_workspace.inc:
-    // RC_LONG_SHARE): no read-back in front of this launch.
-    const auto rerank = L.rc ? knn_rerank_kernel<RERANK_ROWS_COMPACT> : knn_rerank_kernel<RERANK_ROWS_DENSE>;
-    const int rerank_lds = L.rc ? RERANK_LDS_BYTES(RERANK_ROWS_COMPACT) : RERANK_LDS_BYTES(RERANK_ROWS_DENSE);
-    const int long_limit = ctx->compact_mode == FDR_COMPACT_FORCE ? 0x7fffffff : (int)(a.nt / RC_LONG_SHARE);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(rerank), hipFuncAttributeMaxDynamicSharedMemorySize, rerank_lds));
-    hipLaunchKernelGGL(rerank, dim3((unsigned)((nq + 3) / 4)), dim3(256), rerank_lds, st,
-                       (const u64 *)L.cand, kp, k, a.Qhat, a.qzero, a.That, (int)nq, dp, (int)a.t_base, margin,
-                       a.idx, a.dist, L.counter, L.flagged, L.rlist, L.theta, L.path, (const unsigned char *)L.rc, long_limit);
+    for (const QuerySel &sel : late)
+        if ((trc = launch_rerank(st, sel))) return trc;
     // all-zero queries share one closed-form answer (their number is only known on the device yet)
     hipLaunchKernelGGL(zero_answer_kernel, dim3(1), dim3(1024), 0, st, (const unsigned *)R.bits, (int)a.nt,
                        (int)a.t_base, k, L.zidx, L.zdist);
@@ -1858,6 +1968,7 @@ int PrefilterCall::certify(PrefilterCounts &n) {
     HIP_TRY(hipMemcpyAsync(counts, L.counter, sizeof counts, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     n = {counts[0], counts[1], counts[2]};
+    const int long_limit = ctx->compact_mode == FDR_COMPACT_FORCE ? 0x7fffffff : (int)(a.nt / RC_LONG_SHARE);  // (launch_rerank)
     ctx->last.trace.rerank_compact = L.rc && counts[8] <= long_limit;  // (the kernel's own test)
     ctx->last.trace.rerank_compact_entries = L.rc ? RC_ENTRIES : 0;
     ctx->last.trace.rerank_compact_long = counts[8];

@@ -580,6 +580,17 @@ static LivePlan live_plan(const unsigned *masks, int nqb, int nseg, long long mi
     return P;
 }
 
+// The order the pass issues a plan's groups in (indices into LivePlan::groups).  Ascending NL ends the pass on the
+// dense group, whose work items last longest: behind the last launches no later launch takes the freed slots, so the
+// chip drains for about one item time.  Descending -- the dense group first, NL = 6 down to the smallest -- ends it on
+// the cheapest items instead (fdr_set_pass_tail; docs/experiments.md A-36).  The groups share no bound words and no
+// lists, so the order changes no result.
+static std::vector<int> live_issue_order(const LivePlan &P, bool descending) {
+    std::vector<int> o(P.groups.size());
+    for (size_t i = 0; i < o.size(); ++i) o[i] = (int)(descending ? o.size() - 1 - i : i);
+    return o;
+}
+
 // ---- the launches of a pass: one list for every k-NN pass (fedrann_hip.hip: launch_rounds) ---------------------------
 // A pass is one or more groups of work items -- a plain pass: one group of nqb * nseg; the live-chunk pass: a group per
 // LiveGroup, count * nseg each -- and every group runs in launches of at most `per_launch` items (0: one launch per
@@ -597,4 +608,25 @@ static std::vector<RoundLaunch> round_schedule(const std::vector<long long> &ite
             S.push_back(RoundLaunch{(int)g, (int)(S.size() % (size_t)queues), (int)base, (int)std::min(per, n - base)});
     }
     return S;
+}
+
+// Work that depends on ONE group -- the merge and re-rank of its queries -- need not wait for the pass: it may be queued
+// on a further stream once the group's last launch has been issued, behind an event on every queue.  Returns, per group,
+// the index of the launch in front of which that happens, or -1: the group's work stays behind the join (always the
+// group issued last, and a group without items).
+//   FDR_TAIL_TRIGGER_GROUP: right behind the group's own last launch;
+//   FDR_TAIL_TRIGGER_LAST:  in front of the final launch of every queue (the last `queues` launches of the list), for
+//                           the groups that are complete by then: the work lands in the pass's tail, not all over it.
+enum { FDR_TAIL_TRIGGER_NONE = 0, FDR_TAIL_TRIGGER_LAST = 1, FDR_TAIL_TRIGGER_GROUP = 2 };
+static std::vector<int> round_ready_points(const std::vector<RoundLaunch> &S, size_t ngroups, int queues, int trigger) {
+    std::vector<int> at(ngroups, -1), last(ngroups, -1);
+    if (trigger == FDR_TAIL_TRIGGER_NONE || S.empty()) return at;
+    for (size_t i = 0; i < S.size(); ++i) last[(size_t)S[i].group] = (int)i;
+    const int cut = (int)S.size() - std::min<int>(queues, (int)S.size());
+    for (size_t g = 0; g < ngroups; ++g) {
+        if (last[g] < 0 || (int)g == S.back().group) continue;
+        if (trigger == FDR_TAIL_TRIGGER_GROUP) at[g] = last[g] + 1;
+        else if (last[g] < cut) at[g] = cut;
+    }
+    return at;
 }

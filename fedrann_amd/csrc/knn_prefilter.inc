@@ -749,6 +749,21 @@ __device__ __forceinline__ void wave_sort128(u64 &a, u64 &b, const int lane) {
 // are sorted with a 64-lane bitonic network, whose KP-th key is a tighter bound for the rest, and a
 // second sort of the KP best + the few remaining survivors finishes.  More than 128 survivors (wide
 // plateaus), more than 64 in the second sort, or no full list: KP rounds of a wave-wide minimum.
+// The queries a launch of the merge or the re-rank works on: all nq of the call (perm == null: item i is query i, n =
+// nq), or the `n` = 256 x blocks items of a list of 256-query blocks of the scan order -- item i is position
+// blocks[i / 256] * 256 + i % 256 (blocks == null: position i, the gathered dense group) and query perm[position];
+// positions from `limit` on hold no query (the short last block).  The live-chunk pass's groups are such lists
+// (PrefilterCall::group_queries), so that a finished group's queries are merged and re-ranked while later groups run.
+struct QuerySel {
+    const int *blocks, *perm;
+    int n, limit;
+};
+__device__ __forceinline__ int sel_query(const QuerySel &s, int i) {  // item i's query, -1: none
+    if (i >= s.n) return -1;
+    if (!s.perm) return i;
+    const int pos = s.blocks ? s.blocks[i >> 8] * 256 + (i & 255) : i;
+    return pos < s.limit ? s.perm[pos] : -1;
+}
 #define MERGE_QPW 4  // queries per wave when every key of a query has a lane (nseg * KP <= 64)
 #define MERGE_ADAPTIVE_FROM 8  // more lists per query than this: the adaptive bound (see knn_merge_keys_kernel)
 // the value lane 63 - l holds (a run reversed), for the bitonic merge of two ascending runs
@@ -763,7 +778,7 @@ __device__ __forceinline__ u64 lane_reverse64(u64 v, const int lane) {
     return r;
 }
 __global__ __launch_bounds__(256) void knn_merge_keys_kernel(const u64 *__restrict__ partial, int nseg,
-                                                             int nq, int nq_pad, int KP,
+                                                             QuerySel sel, int nq_pad, int KP,
                                                              u64 *__restrict__ cand) {
     __shared__ u64 stage[4][MERGE_CAP];
     static_assert(MERGE_CAP >= 256, "a wave's stage row doubles as its survivor buffer (256 keys)");
@@ -784,9 +799,12 @@ __global__ __launch_bounds__(256) void knn_merge_keys_kernel(const u64 *__restri
         const int sg = lane / KP;
         const int e = runs16 && (lane & 16) ? (lane & 16) + 15 - (lane & 15) : lane - sg * KP;
         u64 kv[MERGE_QPW];
+        int qs[MERGE_QPW];
+#pragma unroll
+        for (int t = 0; t < MERGE_QPW; ++t) qs[t] = sel_query(sel, q0 + t);
 #pragma unroll
         for (int t = 0; t < MERGE_QPW; ++t)
-            kv[t] = (lane < M && q0 + t < nq) ? partial[((size_t)sg * nq_pad + q0 + t) * KP + e] : KEY_INF;
+            kv[t] = (lane < M && qs[t] >= 0) ? partial[((size_t)sg * nq_pad + qs[t]) * KP + e] : KEY_INF;
         if (runs16) {
 #pragma unroll
             for (int t = 0; t < MERGE_QPW; ++t) kv[t] = wave_bitonic<32, 64>(kv[t], lane);
@@ -796,12 +814,12 @@ __global__ __launch_bounds__(256) void knn_merge_keys_kernel(const u64 *__restri
         }
 #pragma unroll
         for (int t = 0; t < MERGE_QPW; ++t)
-            if (lane < KP && q0 + t < nq) cand[(size_t)(q0 + t) * KP + lane] = kv[t];
+            if (lane < KP && qs[t] >= 0) cand[(size_t)qs[t] * KP + lane] = kv[t];
         return;
     }
     u64 *sv = stage[wave];
-    const int q = blockIdx.x * 4 + wave;
-    if (q >= nq) return;
+    const int q = sel_query(sel, blockIdx.x * 4 + wave);
+    if (q < 0) return;
     if (nseg > MERGE_ADAPTIVE_FROM) {
         // Many segments (a rank of config 5: 39-48 lists of 62 keys per query): the static bound below -- the smallest
         // maximum of a FULL list -- sits near the (nseg * KP)-th best key, a thousand keys survive it and every query
@@ -997,13 +1015,14 @@ __global__ __launch_bounds__(256) void knn_rerank_kernel(
     int *__restrict__ flagged, int *__restrict__ range_list, float *__restrict__ theta,
     unsigned char *__restrict__ path,  // path[q]: how query q's result is produced (FDR_PATH_*: fdr_last_query_paths)
     const unsigned char *__restrict__ rc,  // the targets' compact records, from row t_base on (null: dense route only)
-    int long_limit) {  // ... read only if their build counted at most so many long rows (counter[8]; knn_workspace.inc)
+    int long_limit,  // ... read only if their build counted at most so many long rows (counter[8]; knn_workspace.inc)
+    QuerySel sel) {  // the launch's queries, a wave each (several launches append to flagged / range_list alike)
     extern __shared__ float rerank_rows[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     float *rows = rerank_rows + wave * RERANK_WAVE_FLOATS(ROWS);
-    const int q = blockIdx.x * 4 + wave;
-    if (q >= nq) return;
+    const int q = __builtin_amdgcn_readfirstlane(sel_query(sel, blockIdx.x * 4 + wave));  // (wave-uniform)
+    if (q < 0) return;
     if (qzero[q]) {  // all-zero query: closed-form answer (zero_answer_kernel); listed from the back
         if (lane == 0) {
             flagged[nq - 1 - atomicAdd(counter + 1, 1)] = q;

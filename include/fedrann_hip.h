@@ -646,6 +646,22 @@ int fdr_set_live_chunks(fdr_ctx *ctx, int mode);
 #define FDR_SKIP_AUTO 0
 #define FDR_SKIP_OFF 1
 int fdr_set_live_skip(fdr_ctx *ctx, int mode);
+/* The end of the live-chunk pass (DESIGN.md sections 5 and 6; docs/experiments.md A-36).  The pass's groups share no
+ * bound words and no lists, and a query's candidate lists are complete as soon as its own group's last launch has ended,
+ * so neither the order of the groups nor the moment a group's queries are merged and re-ranked changes a result.
+ * AUTO (default): the groups in descending cost -- the dense group first, NL = 6 down to the cheapest -- so that the pass
+ * drains on its shortest work items.  The second part, the merge + re-rank of every group but the last on a further
+ * stream under the pass's final launches, gained less than the run-to-run range and is not part of AUTO.  OFF: ascending
+ * NL, and one merge + re-rank of all queries behind the join (the parity tests, A/B measurements).  The other values
+ * force a part whatever AUTO makes of it (the parity tests, A/B measurements): ORDER = the descending order alone;
+ * EARLY = that + the early work once only the final launch of every queue is outstanding; EARLY_GROUP = that + each
+ * group's work right behind the group's own last launch. */
+#define FDR_TAIL_AUTO 0
+#define FDR_TAIL_OFF 1
+#define FDR_TAIL_ORDER 2
+#define FDR_TAIL_EARLY 3
+#define FDR_TAIL_EARLY_GROUP 4
+int fdr_set_pass_tail(fdr_ctx *ctx, int mode);
 /* Compact re-rank (DESIGN.md sections 5 and 6): where the padded width is 128 (d <= 128) the prefilter mode keeps, beside the fp16 copies, one
  * fixed-size record per target row that lists the row's non-zero components in the order of the canonical chain, and
  * the certificate kernel re-ranks a candidate from its record; a row with more non-zeros than a record holds takes
@@ -726,6 +742,9 @@ typedef struct fdr_knn_trace {
     int64_t rerank_compact_long;    /* target rows with more non-zeros than a record holds (counted by the build) */
     int32_t rerank_compact;         /* 1: knn_rerank_kernel read the records (0: none built, or too many long rows) */
     int32_t rerank_compact_entries; /* non-zeros a record holds (0: no records were built) */
+    /* the end of the live-chunk pass (prefilter only; fdr_set_pass_tail) */
+    int32_t pass_group_order;       /* its groups in issue order, four bits each from the lowest: NL = 2 .. 6, 8 = the dense group */
+    int32_t rerank_early_queries;   /* queries merged and re-ranked under the pass, before the join (0: all behind it) */
 } fdr_knn_trace;
 int fdr_last_knn_trace(fdr_ctx *ctx, fdr_knn_trace *out);
 /* Prefilter mode only: number of query rows of the most recent k-NN call whose candidate set could
