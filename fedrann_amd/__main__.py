@@ -33,6 +33,10 @@ distances of --no-projection --no-projection-metric METRIC, bit for bit) and wri
 --radius R --radius-rescore METRIC [--radius-rescore-bound R2]: the candidates of the projected radius search, every
 pair scored exactly on the feature rows under METRIC (the rows go to the device once: fdr_rescore_rows_build), cut at
 R2 in that metric (default 1: every projected hit is kept) and written in the exact order (fdr_rescore_rows_radius).
+--refine METRIC [--refine-fan F] [--refine-rounds T] [--refine-reverse] (the default, projected mode, one GPU, after
+--rescore where that is given): the feature rows go to the device once (fdr_rescore_rows_build) and T rounds of
+refinement run on the lists: a read's candidates are its F nearest neighbours and theirs (fdr_graph_expand), scored
+exactly under METRIC and cut to the best k (fdr_rescore_rows_refine); round i's graph is round i - 1's rows.
 --symmetrize union|mutual (any of the one-GPU modes above): the graph the mode is about to write is symmetrised on the
 GPU first (fdr_graph_symmetrize: a pair under both reads when either lists the other, or only where each lists the
 other, at the smaller distance) and written once through fdr_overlaps_write_csr; the radius modes collect their row
@@ -170,6 +174,23 @@ def build_parser():
     g.add_argument("--radius-rescore-bound", type=float, default=None, metavar="R2",
                    help="With --radius-rescore: the bound in the exact metric, 0 <= R2 <= 1; by default 1, which keeps "
                         "every hit of the projected radius search.")
+    g.add_argument("--refine", choices=["cosine", "jaccard", "weighted_jaccard"], default=None,
+                   help="In the default, projected mode, after the search (and --rescore, whose metric must then be "
+                        "the same): refine every read's list among the neighbours of its neighbours.  The candidates "
+                        "of a read are its --refine-fan nearest entries and theirs (fdr_graph_expand), scored on the "
+                        "feature rows under this metric (the distances --no-projection --no-projection-metric "
+                        "reports, bit for bit) and cut to the best --nndescent-n-neighbors "
+                        "(fdr_rescore_rows_refine): the exact-metric route to candidates the projection did not "
+                        "name, without widening --rescore-candidates past 64.  One GPU; not with --radius or "
+                        "--no-projection.")
+    g.add_argument("--refine-fan", type=int, default=None, metavar="F",
+                   help="With --refine: entries of a list that are followed, 1 <= F <= %d; by default "
+                        "min(--nndescent-n-neighbors, %d).  A read has at most F + F^2 candidates a round." % (FDR_MAX_K, FDR_MAX_K))
+    g.add_argument("--refine-rounds", type=int, default=None, metavar="T",
+                   help="With --refine: rounds, each on the rows the round before it left; by default 1.")
+    g.add_argument("--refine-reverse", action="store_true", default=False,
+                   help="With --refine: each round first takes the union graph (fdr_graph_symmetrize), so that the "
+                        "reads that list a read are followed too (NN-descent's reverse neighbours).")
     g.add_argument("--symmetrize", choices=["union", "mutual"], default=None,
                    help="Symmetrise the neighbour graph on the GPU before overlaps.tsv is written "
                         "(fdr_graph_symmetrize): union lists a pair under both reads when either read lists the other, "
@@ -317,6 +338,35 @@ def check_rescore(args):
         raise SystemExit("--rescore-candidates must be in [--nndescent-n-neighbors = %d, %d], got %d"
                          % (k, _lib.FDR_MAX_K, kp))
     return kp
+
+
+def check_refine(args):
+    """--refine and its options against the other options, before any work.  Returns (fan or None, rounds); (None, 0)
+    without --refine."""
+    from . import _lib
+    if args.refine is None:
+        for flag, given in (("--refine-fan", args.refine_fan is not None), ("--refine-rounds", args.refine_rounds is not None),
+                            ("--refine-reverse", args.refine_reverse)):
+            if given:
+                raise SystemExit("%s needs --refine (without it nothing is refined)" % flag)
+        return None, 0
+    if args.no_projection:
+        raise SystemExit("--refine refines the projected search's lists: it does not run with --no-projection, whose "
+                         "lists are exact already")
+    if args.radius is not None:
+        raise SystemExit("--refine refines k-NN lists: it does not run with --radius")
+    if len(device_list(args.devices)) > 1:
+        raise SystemExit("--refine runs on one GPU: over --devices a rank holds only its own rows of the feature "
+                         "matrix, and a candidate may be any row")
+    if args.rescore is not None and args.rescore != args.refine:
+        raise SystemExit("--refine %s after --rescore %s: the two metrics must be the same (the refinement follows "
+                         "the re-scored distances)" % (args.refine, args.rescore))
+    if args.refine_fan is not None and not 1 <= args.refine_fan <= _lib.FDR_MAX_K:
+        raise SystemExit("--refine-fan must be in [1, %d], got %d" % (_lib.FDR_MAX_K, args.refine_fan))
+    rounds = 1 if args.refine_rounds is None else args.refine_rounds
+    if rounds < 1:
+        raise SystemExit("--refine-rounds must be at least 1, got %d" % rounds)
+    return args.refine_fan, rounds
 
 
 def check_radius_rescore(args):
@@ -574,7 +624,7 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                          kmer_counts=None, read_names_path=None, no_projection=False,
                          no_projection_metric="cosine", no_projection_radius=None, radius=None, rescore=None,
                          rescore_candidates=None, radius_rescore=None, radius_rescore_bound=None, symmetrize=None,
-                         components=None):
+                         components=None, refine=None, refine_fan=None, refine_rounds=1, refine_reverse=False):
     """Stages 2-4 of the reference pipeline (__main__.py:329-391) on one GPU.  The embeddings never leave
     HBM between the projection and the search (fdr_embed_knn), and only the features P has entries for
     cross PCIe (fdr_csr_compact; the saved feature_matrix.npz is the full matrix).  no_projection: stage 4
@@ -593,7 +643,10 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
     ("union" / "mutual"; None: the rows as searched): whichever of these modes ran, the graph it is about to write is
     symmetrised on the GPU first (fdr_graph_symmetrize) and written once through fdr_overlaps_write_csr.  components
     ((mode, max_distance); None: no components.tsv): the connected components of the rows as searched, before any
-    symmetrize, are found on the GPU (fdr_graph_components) and written to components.tsv beside overlaps.tsv."""
+    symmetrize, are found on the GPU (fdr_graph_components) and written to components.tsv beside overlaps.tsv.  refine
+    (projected k-NN mode, a sparse metric's name): the lists of the search, re-scored or not, go through refine_rounds
+    rounds of RescoreRows.refine on the feature rows held on the device, with refine_fan (None: min(k, FDR_MAX_K))
+    and refine_reverse, before they are written (refined_lists)."""
     from . import _lib
     from .feature_extraction import _projection_csr
     if kmer_searcher_output:
@@ -661,6 +714,11 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
         values = rescore_values(rescore)
         neighbor_matrix, distances = ctx.sparse_rescore(indptr, indices, values, n_features, candidates, k=k,
                                                         metric=rescore)
+        if refine is not None:
+            graph = refined_lists(ctx, (indptr, indices, values, n_features), refine, (neighbor_matrix, distances), k,
+                                  refine_fan, refine_rounds, refine_reverse)
+            _finish_ragged(output_dir, graph, read_names, strands, keep_intermediates, symmetrize, ctx, components)
+            return
         _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_intermediates, symmetrize, ctx, components)
         return
     if radius is not None and radius_rescore is not None:
@@ -678,6 +736,15 @@ def run_fedrann_pipeline(*, output_dir, embedding_dimension, nndescent_n_trees,
                                          symmetrize=symmetrize, ctx=ctx, components=components)
         logger.debug("wrote %d overlap rows of %d projected hits", rows, both.candidates)
         _cleanup(keep_intermediates)
+        return
+    if refine is not None:
+        k = nndescent_n_neighbors
+        logger.info("--- 4. Nearest Neighbors Search (projected, k = %d), refined on the feature rows ---", k)
+        lists = ctx.embed_knn(cip, cix, k)
+        del cip, cix
+        graph = refined_lists(ctx, (indptr, indices, rescore_values(refine), n_features), refine, lists, k, refine_fan,
+                              refine_rounds, refine_reverse)
+        _finish_ragged(output_dir, graph, read_names, strands, keep_intermediates, symmetrize, ctx, components)
         return
     del indptr, indices
     if radius is not None:
@@ -710,6 +777,40 @@ def _finish(output_dir, neighbor_matrix, distances, read_names, strands, keep_in
         rows = write_symmetrized(nbr_output_file, ctx, graph, symmetrize, read_names, strands)
     else:
         rows = write_overlaps(nbr_output_file, neighbor_matrix, distances, read_names, strands)
+    logger.debug("wrote %d overlap rows", rows)
+    _cleanup(keep_intermediates)
+
+
+def refined_lists(ctx, rows, metric, graph, k, fan=None, rounds=1, reverse=False):
+    """--refine: `rounds` rounds of RescoreRows.refine at k on the feature rows `rows` = (indptr, indices, values,
+    n_features) under `metric`, held on the device for all of them; round 1 starts from `graph` (the search's lists),
+    round i from round i - 1's rows.  Returns the last round's ragged (indptr, idx, dist)."""
+    indptr, indices, values, n_features = rows
+    with ctx.rescore_rows(indptr, indices, values, n_features, metric=metric) as held:
+        for i in range(rounds):
+            graph = held.refine(graph, k, fan=fan, reverse=reverse)
+            logger.info("--refine %s: round %d of %d left %d entries of %d rows", metric, i + 1, rounds,
+                        int(graph[0][-1]), graph[0].size - 1)
+    ctx.graph_free()
+    return graph
+
+
+def _finish_ragged(output_dir, graph, read_names, strands, keep_intermediates, symmetrize=None, ctx=None,
+                   components=None):
+    """_finish for a ragged (indptr, idx, dist), every row ascending by (distance bits, index): through
+    fdr_overlaps_write_csr."""
+    from . import _lib
+    nbr_output_file = join(output_dir, "overlaps.tsv")
+    logger.debug("Saving overlap table to %s", nbr_output_file)
+    if components is not None:
+        write_components(join(output_dir, "components.tsv"), ctx, graph, components[0], components[1], read_names,
+                         strands)
+    if symmetrize is not None:
+        rows = write_symmetrized(nbr_output_file, ctx, graph, symmetrize, read_names, strands)
+    else:
+        name_off, names = _lib.pack_names(read_names)
+        rows = _lib.overlaps_write_csr(nbr_output_file, *graph, name_off, names, np.asarray(strands, dtype=np.uint8),
+                                       n_threads=global_variables.threads if global_variables.threads > 1 else 0)
     logger.debug("wrote %d overlap rows", rows)
     _cleanup(keep_intermediates)
 
@@ -1051,6 +1152,7 @@ def main(argv=None):
     check_symmetrize(args)
     check_components(args)
     radius_rescore_bound = check_radius_rescore(args)
+    refine_fan, refine_rounds = check_refine(args)
     if args.no_projection_metric != "cosine" and not args.no_projection:
         raise SystemExit("--no-projection-metric %s needs --no-projection (the projected search is cosine only)"
                          % args.no_projection_metric)
@@ -1110,7 +1212,8 @@ def main(argv=None):
         no_projection_metric=args.no_projection_metric, no_projection_radius=args.no_projection_radius,
         radius=args.radius, rescore=args.rescore, rescore_candidates=args.rescore_candidates,
         radius_rescore=args.radius_rescore, radius_rescore_bound=radius_rescore_bound, symmetrize=args.symmetrize,
-        components=None if args.components is None else (args.components, args.components_distance))
+        components=None if args.components is None else (args.components, args.components_distance),
+        refine=args.refine, refine_fan=refine_fan, refine_rounds=refine_rounds, refine_reverse=args.refine_reverse)
 
 
 if __name__ == "__main__":

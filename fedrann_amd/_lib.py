@@ -33,6 +33,7 @@ SYMBOLS = (
     "fdr_rescore_rows_build", "fdr_rescore_rows_info", "fdr_rescore_rows_free", "fdr_rescore_rows_knn",
     "fdr_rescore_rows_radius", "fdr_rescore_rows_radius_fetch",
     "fdr_graph_symmetrize", "fdr_graph_symmetrize_fetch", "fdr_graph_free", "fdr_graph_components",
+    "fdr_graph_expand", "fdr_graph_expand_fetch", "fdr_rescore_rows_refine",
 )
 FDR_FAST_MAX_DIM = 512  # the reach of the fp16 passes, and so of the dense index (csrc/knn_plan.inc)
 FDR_MAX_K = 128
@@ -145,6 +146,9 @@ def load_library():
     L.fdr_graph_symmetrize_fetch.argtypes = [vp, i64, vp, vp]
     L.fdr_graph_free.argtypes = [vp]
     L.fdr_graph_components.argtypes = [vp, i32, i64, vp, vp, vp, ctypes.c_float, vp, vp, vp]
+    L.fdr_graph_expand.argtypes = [vp, i64, vp, vp, vp, i32, i64, i64, i64, vp]
+    L.fdr_graph_expand_fetch.argtypes = [vp, i64, vp]
+    L.fdr_rescore_rows_refine.argtypes = [vp, ctypes.c_float, i32, vp]
     L.fdr_sparse_rescore.argtypes = [vp, i32, i64, i64, vp, vp, vp, i64, i64, i32, vp, i32, vp, vp]
     L.fdr_rescore_rows_build.argtypes = [vp, i32, i64, i64, vp, vp, vp]
     L.fdr_rescore_rows_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i64),
@@ -683,6 +687,35 @@ def check_graph_symmetrize(graph, mode="union", max_entries=1 << 27):
     if not 1 <= n <= np.iinfo(np.int32).max or idx.size > np.iinfo(np.int32).max:
         raise ValueError("need 1 <= n < 2^31 rows and fewer than 2^31 entries (got %d and %d)" % (n, idx.size))
     return code, n, indptr, idx, dist
+
+
+def check_graph_expand(graph, fan, lo=0, hi=None, max_entries=1 << 27):
+    """The argument checks of Context.graph_expand (fdr_graph_expand repeats those of the indptr and the limits); needs
+    no GPU.  graph as check_graph_symmetrize takes it; 1 <= fan <= FDR_MAX_K; 0 <= lo <= hi <= n (hi None: n); 1 <=
+    max_entries < 2^31.  All ValueError.  What the rows hold (indices in [0, n), distances >= 0 and not NaN) is checked
+    on the device, over the whole graph.  Returns (n, indptr, idx, dist, fan, lo, hi)."""
+    from . import graph as _graph
+    _, n, indptr, idx, dist = check_graph_symmetrize(graph, "union", max_entries)
+    indptr, idx, dist, n, fan, lo, hi = _graph.check_expand(indptr, idx, dist, fan, lo, hi)
+    return n, indptr, idx, dist, fan, lo, hi
+
+
+def expand_pieces(bound, max_entries):
+    """Cut rows whose expansions hold at most `bound` (int64 [nq]) entries into consecutive pieces that fit max_entries
+    by those bounds: [(a, b), ...] covering [0, nq); None when one row's bound alone exceeds it.  radius_pieces without
+    its walk over the rows.  Needs no GPU."""
+    nq = int(bound.size)
+    if nq == 0 or int(bound.sum()) <= max_entries:
+        return [(0, nq)]
+    if int(bound.max()) > max_entries:
+        return None
+    ends = np.cumsum(bound)
+    pieces, a, done = [], 0, 0
+    while a < nq:
+        b = int(np.searchsorted(ends, done + max_entries, side="right"))
+        pieces.append((a, b))
+        a, done = b, int(ends[b - 1])
+    return pieces
 
 
 def check_graph_components(graph, mode="union", max_distance=None):
@@ -1232,8 +1265,32 @@ class Context:
                                                  ctypes.addressof(found)), "fdr_graph_components")
         return labels, sizes[:found.value].copy()
 
+    def _graph_expand_held(self, n, indptr, idx, dist, fan, lo, hi, max_entries):
+        """fdr_graph_expand on checked arguments: the result's row pointer; the indices stay held on the device."""
+        out_ip = np.empty(hi - lo + 1, dtype=np.int64)
+        self._check(self._L.fdr_graph_expand(self._h, n, _ptr(indptr), _ptr(idx), _ptr(dist), fan, lo, hi - lo,
+                                             int(max_entries), _ptr(out_ip)), "fdr_graph_expand")
+        return out_ip
+
+    def graph_expand(self, graph, fan, lo=0, hi=None, max_entries=1 << 27):
+        """The distinct rows within two hops of the rows [lo, hi) of a neighbour graph (graph as graph_symmetrize takes
+        it) along its `fan` nearest entries: row r names every s among its first `fan` entries by (distance bits,
+        index), and every s != r among the first `fan` entries of those.  Returns (indptr int64 [hi - lo + 1], idx
+        int32), every row ascending by index: graph.expand_rows bit for bit, computed on the GPU (fdr_graph_expand, then
+        fdr_graph_expand_fetch).  The argument checks (check_graph_expand) are ValueErrors before the library is called;
+        an index outside [0, n) and a negative or NaN distance anywhere in the graph, and a result of more than
+        max_entries entries, are refused by the library (FedrannHipError).  An index twice in a row takes two places
+        of the fan and comes out once.  The expansion stays held in the context (RescoreRows.refine scores it there)
+        until the next graph_expand or graph_free; everything else the context holds stays as it is."""
+        n, indptr, idx, dist, fan, lo, hi = check_graph_expand(graph, fan, lo, hi, max_entries)
+        out_ip = self._graph_expand_held(n, indptr, idx, dist, fan, lo, hi, max_entries)
+        out_idx = np.empty(int(out_ip[-1]), dtype=np.int32)
+        self._check(self._L.fdr_graph_expand_fetch(self._h, int(out_ip[-1]), _ptr(out_idx)), "fdr_graph_expand_fetch")
+        return out_ip, out_idx
+
     def graph_free(self):
-        """Free the device memory of graph_symmetrize and graph_components (it grows with the largest graph seen):
+        """Free the device memory of graph_symmetrize, graph_components and graph_expand, a held expansion
+        included (it grows with the largest graph seen):
         fdr_graph_free."""
         self._check(self._L.fdr_graph_free(self._h), "fdr_graph_free")
 
@@ -1671,6 +1728,60 @@ class RescoreRows(_HeldIndex):
         if len(outs) == 1:
             return outs[0]
         out_ip = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum(np.concatenate([np.diff(o[0]) for o in outs]), out=out_ip[1:])
+        return out_ip, np.concatenate([o[1] for o in outs]), np.concatenate([o[2] for o in outs])
+
+    def refine(self, graph, k, fan=None, radius=1.0, reverse=False, block_rows=None, max_entries=1 << 27):
+        """One refinement step of the neighbour lists `graph` (as Context.graph_symmetrize takes it, on the set's n
+        rows): every row's candidates are its `fan` nearest entries and the `fan` nearest of each of those
+        (Context.graph_expand), scored exactly on the held rows, cut by `radius` (0 <= radius <= 1; 1 keeps all) and to
+        the k best.  Returns the ragged (indptr int64 [n + 1], idx int32, dist float32) over all rows, every row
+        ascending by (distance bits, index) and of at most k entries: what radius(*graph_expand(graph, fan), radius)
+        gives, each row cut to k.  The candidates never leave the device (fdr_graph_expand, fdr_rescore_rows_refine,
+        fdr_rescore_rows_radius_fetch per block of rows).  fan: min(k, FDR_MAX_K) by default.  reverse=True first
+        takes Context.graph_symmetrize(graph, "union"), so a row's listers are candidates too (NN-descent's reverse
+        neighbours; a hub is bounded by the fan cut).  The rows go in consecutive blocks: of block_rows rows, or, by
+        default, as many as keep fan-cut length * (1 + fan), an upper bound of a row's candidates that needs the row
+        pointer alone, within max_entries in sum (one row above it is a ValueError).  A row's own index is a
+        candidate exactly when the row lists itself inside its fan."""
+        from . import graph as _graph
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) < 2 ** 31:
+            raise ValueError("k must be an integer in [1, 2^31), got %r" % (k,))
+        if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+            raise ValueError("radius must be a number, got %r" % (radius,))
+        r = np.float32(radius)
+        if not (r >= 0 and r <= 1):
+            raise ValueError("need 0 <= radius <= 1, got %r" % (radius,))
+        r = r + np.float32(0)  # (-0.0 is 0)
+        _check_block_rows(block_rows)
+        fan = min(int(k), FDR_MAX_K) if fan is None else fan
+        n, indptr, idx, dist, fan, _, _ = check_graph_expand(graph, fan, 0, None, max_entries)
+        if n != self.n:
+            raise ValueError("the graph has %d rows, the re-score rows are %d" % (n, self.n))
+        self._live("RescoreRows.refine")
+        c = self._ctx
+        if reverse:
+            indptr, idx, dist = c.graph_symmetrize((indptr, idx, dist), "union", max_entries=2 ** 31 - 1)
+        if block_rows is None:
+            pieces = expand_pieces(_graph.expand_bound(indptr, fan), int(max_entries))
+            if pieces is None:
+                raise ValueError("one row alone may have more than max_entries = %d candidates at fan = %d"
+                                 % (int(max_entries), fan))
+        else:
+            pieces = [(a, min(n, a + int(block_rows))) for a in range(0, n, int(block_rows))]
+        outs = []
+        for a, b in pieces:
+            c._graph_expand_held(n, indptr, idx, dist, fan, a, b, max_entries)
+            ip = np.full(b - a + 1, -1, dtype=np.int64)
+            c._check(c._L.fdr_rescore_rows_refine(c._h, r, int(min(int(k), 2 ** 31 - 1)), _ptr(ip)),
+                     "fdr_rescore_rows_refine")
+            total = int(ip[-1])
+            out_idx, out_dist = np.empty(total, dtype=np.int32), np.empty(total, dtype=np.float32)
+            c._check(c._L.fdr_rescore_rows_radius_fetch(c._h, total, _ptr(out_idx), _ptr(out_dist)), self._fetch)
+            outs.append((ip, out_idx, out_dist))
+        if len(outs) == 1:
+            return outs[0]
+        out_ip = np.zeros(n + 1, dtype=np.int64)
         np.cumsum(np.concatenate([np.diff(o[0]) for o in outs]), out=out_ip[1:])
         return out_ip, np.concatenate([o[1] for o in outs]), np.concatenate([o[2] for o in outs])
 

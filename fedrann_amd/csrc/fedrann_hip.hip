@@ -831,6 +831,33 @@ struct GraphCompScratch {
     void release() { each([](auto &...a) { release_all(a...); }); }
 };
 
+// fdr_graph_expand (graph_expand.inc): the distinct rows within two hops of a block of rows.  The graph itself goes
+// through GraphSymScratch's input arrays, as fdr_graph_components' does.  The held result is `out` with its row pointer
+// on the device (`off`) and on the host (h_off: fdr_rescore_rows_refine lists its work items from it), kept until the
+// next fdr_graph_expand or fdr_graph_free, whatever fdr_graph_symmetrize and fdr_graph_components do in between.
+struct GraphExpandScratch {
+    DevArray<long long> bound, boff;  // [nq + 1] the rows' upper bounds (a 0 behind them); their exclusive scan
+    DevArray<unsigned> cand;          // [bound entries + 1] the one- and two-hop indices as gathered; then the run heads
+    DevArray<unsigned> sorted;        // [bound entries] every segment ascending
+    DevArray<unsigned> pos;           // [bound entries + 1] the run heads' exclusive scan: an entry's place in `out`
+    DevArray<long long> off;          // [nq + 1] HELD: the result's row pointer
+    DevArray<int> out;                // [held] HELD: the result's indices
+    DevArray<u64> flags;              // [1] stores that fell outside their segment (an internal error)
+    std::vector<long long> h_off;     // [nq + 1] HELD: `off` on the host
+    long long held = -1;              // the held result's entries (-1: none)
+    long long n = 0, q_lo = 0, nq = 0;  // the held result's graph and rows
+    template <class F>
+    auto each(F f) { return f(bound, boff, cand, sorted, pos, off, out, flags); }
+    size_t bytes() { return each([](auto &...a) { return (a.bytes() + ...); }); }
+    void drop() { held = -1; }
+    void release() {
+        each([](auto &...a) { release_all(a...); });
+        std::vector<long long>().swap(h_off);
+        held = -1;
+        n = q_lo = nq = 0;
+    }
+};
+
 // The re-score calls (sparse_rescore.inc).  RsCsr: a CSR as uploaded and what the row pass X1 makes of its rows.
 // RsLists: rectangular candidate lists, the re-scored rows before they are copied out, and the record of a refused
 // call.  fdr_sparse_rescore owns one of each (SparseRescoreScratch), valid within one call, freed with the context;
@@ -1024,6 +1051,7 @@ struct fdr_ctx {
     RescoreRowSet rrs;     // the held re-score rows and their calls (sparse_rescore.inc): kept until fdr_rescore_rows_free
     GraphSymScratch gs;    // a graph's symmetrised rows and their call (graph_symmetrize.inc): kept until fdr_graph_free
     GraphCompScratch gc;   // a graph's union-find and labels (graph_components.inc): kept until fdr_graph_free
+    GraphExpandScratch ge; // a block of rows' two-hop candidates and their call (graph_expand.inc): kept until fdr_graph_free
     // timing: when enabled, every launch of kernel kind i gets its own hipEvent pair on the launch
     // stream; fdr_timing_read() sums the elapsed times of all launches since the last read
     int knn_mode = FDR_MODE_AUTO;
@@ -2582,6 +2610,7 @@ FDR_EXPORT int fdr_embed_knn(fdr_ctx *ctx, int64_t n_rows, const int64_t *a_indp
 #include "radius_merge.inc"  // M1: the exact merge of the ranks' ragged rows of a target-sharded sparse radius search
 #include "sparse_rescore.inc"  // X1 / X2: candidate lists re-scored by exact distance on the sparse rows (fdr_sparse_rescore)
 #include "graph_symmetrize.inc"  // G1 .. G4: union, mutual and transposed rows of a neighbour graph (fdr_graph_symmetrize)
+#include "graph_expand.inc"  // E1 .. E6: the distinct rows within two hops of a block of rows (fdr_graph_expand)
 #include "graph_components.inc"  // C0 .. C3: connected components of a neighbour graph, cut at a distance (fdr_graph_components)
 #include "kmer_search.inc"
 #include "kmer_output_loader.inc"

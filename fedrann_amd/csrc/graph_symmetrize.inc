@@ -362,5 +362,6 @@ FDR_EXPORT int fdr_graph_free(fdr_ctx *ctx) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->gs.release();
     ctx->gc.release();
+    ctx->ge.release();
     return FDR_OK;
 }

@@ -579,12 +579,71 @@ FDR_EXPORT int fdr_rescore_rows_knn(fdr_ctx *ctx, int64_t q_lo, int64_t nq, int3
     return rs_lists_end(s.lists, st, who, s.n, 0, q_lo, k_in, cand_idx, n_out, idx_out, dist_out);
 }
 
+// X3 over the work items of the candidate rows (d_indptr, d_cand), which lie on the device
 template <int METRIC>
-static void rs_x3_launch(RescoreRowSet &s, hipStream_t st, size_t n_items, int64_t q_lo, unsigned rbits) {
+static void rs_x3_launch(RescoreRowSet &s, hipStream_t st, size_t n_items, int64_t q_lo, unsigned rbits,
+                         const long long *d_indptr, const int *d_cand) {
     hipLaunchKernelGGL((sparse_rescore_ragged_kernel<METRIC>), dim3((unsigned)n_items), dim3(64), 0, st, (long long)s.n,
                        (long long)q_lo, rbits, rs_rows_of(s.csr, METRIC, s.has_values), (const int2 *)s.items.ptr(),
-                       (const long long *)s.cand_indptr.ptr(), (const int *)s.lists.cand.ptr(), s.lists.cnt.ptr(),
-                       s.rr.keys.ptr(), reinterpret_cast<unsigned long long *>(s.rr.count.ptr()));
+                       d_indptr, d_cand, s.lists.cnt.ptr(), s.rr.keys.ptr(),
+                       reinterpret_cast<unsigned long long *>(s.rr.count.ptr()));
+}
+
+// count[r] <- min(count[r], k_top) for the nq rows
+__global__ __launch_bounds__(256) void rs_clamp_kernel(long long nq, long long k_top, long long *__restrict__ count) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r < nq && count[r] > k_top) count[r] = k_top;
+}
+
+// What fdr_rescore_rows_radius and fdr_rescore_rows_refine share once the candidate rows (d_indptr [nq + 1], d_cand,
+// `total` > 0 candidates) lie on the device and s.h_items lists their batches; the caller has made `radius` a
+// non-negative float in [0, 1] and reserved nothing.  X3; the refusal record into *refused (not ~0: the call is over,
+// FDR_OK, nothing written, and the caller words the error); the hit counts, clamped to k_top where k_top > 0; their
+// scan into indptr_out; the sort; the split; the result held.
+static int rs_ragged_run(RescoreRowSet &s, const RadiusCall &call, float radius, int64_t q_lo, int64_t total,
+                         const long long *d_indptr, const int *d_cand, int64_t k_top, u64 *refused) {
+    int rc;
+    RadiusResult &rr = s.rr;
+    const hipStream_t st = call.st;
+    const int64_t nq = call.nq;
+    const size_t n_items = s.h_items.size();  // (at most total / FDR_MAX_K + nq: below 2^31)
+    if ((rc = radius_reserve(rr, call))) return rc;
+    if ((rc = s.items.reserve(n_items))) return rc;
+    if ((rc = s.lists.cnt.reserve(RS_CNT_WORDS))) return rc;
+    if ((rc = rr.keys.reserve((size_t)total))) return rc;
+    if ((rc = rr.sorted.reserve((size_t)total))) return rc;
+    HIP_TRY(upload(s.items, s.h_items.data(), n_items, st));
+    HIP_TRY(hipMemsetAsync(s.lists.cnt.ptr() + RS_CNT_REFUSAL, 0xff, 8, st));
+    const unsigned rbits = __builtin_bit_cast(unsigned, radius);
+    if (s.metric == FDR_METRIC_JACCARD) rs_x3_launch<FDR_METRIC_JACCARD>(s, st, n_items, q_lo, rbits, d_indptr, d_cand);
+    else if (s.metric == FDR_METRIC_WEIGHTED_JACCARD)
+        rs_x3_launch<FDR_METRIC_WEIGHTED_JACCARD>(s, st, n_items, q_lo, rbits, d_indptr, d_cand);
+    else rs_x3_launch<FDR_METRIC_COSINE>(s, st, n_items, q_lo, rbits, d_indptr, d_cand);
+    HIP_TRY(hipGetLastError());
+    *refused = ~0ull;
+    HIP_TRY(hipMemcpyAsync(refused, s.lists.cnt.ptr() + RS_CNT_REFUSAL, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (*refused != ~0ull) return FDR_OK;  // (nothing has been written to indptr_out)
+    if (k_top > 0) {
+        hipLaunchKernelGGL(rs_clamp_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, (long long)nq,
+                           (long long)k_top, rr.count.ptr());
+        HIP_TRY(hipGetLastError());
+    }
+    rc = radius_offsets(rr, s.tmp, call, "hits", "hit counts", nullptr);
+    const long long hits = rr.counted;
+    if (rc || hits == 0) return rc;  // (no hit: the empty result is held)
+    auto sort = [&](void *tmp, size_t &bytes) {  // (a key lies below 2^62: distance bits <= those of 1.0f)
+        return rocprim::segmented_radix_sort_keys(tmp, bytes, rr.keys.ptr(), rr.sorted.ptr(), (unsigned)total, (unsigned)nq,
+                                                  d_indptr, d_indptr + 1, 0, 63, st);
+    };
+    if ((rc = rocprim_run(s.tmp, "rocprim::segmented_radix_sort_keys", sort))) return rc;
+    hipLaunchKernelGGL(radius_split_kernel<true>, dim3((unsigned)((hits + 255) / 256)), dim3(256), 0, st, hits,
+                       (const u64 *)rr.sorted.ptr(), rr.idx(), reinterpret_cast<float *>(rr.idx() + hits), (long long)nq,
+                       (const long long *)rr.off.ptr(), d_indptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    rr.held = hits;
+    return FDR_OK;
 }
 
 FDR_EXPORT int fdr_rescore_rows_radius(fdr_ctx *ctx, float radius, int64_t q_lo, int64_t nq, const int64_t *cand_indptr,
@@ -623,48 +682,67 @@ FDR_EXPORT int fdr_rescore_rows_radius(fdr_ctx *ctx, float radius, int64_t q_lo,
         return FDR_OK;
     }
     if (!cand_idx) return fail(FDR_E_ARG, "%s: null pointer", who);
-    const size_t n_items = s.h_items.size();  // (at most total / FDR_MAX_K + nq: below 2^31)
     const hipStream_t st = ctx->stream;
     const RadiusCall call = {st, who, nq, INT64_MAX, indptr_out};  // (no cap: the caller supplied the candidates)
-    if ((rc = radius_reserve(rr, call))) return rc;
     if ((rc = s.cand_indptr.reserve((size_t)nq + 1))) return rc;
-    if ((rc = s.items.reserve(n_items))) return rc;
     if ((rc = s.lists.cand.reserve((size_t)total))) return rc;
-    if ((rc = s.lists.cnt.reserve(RS_CNT_WORDS))) return rc;
-    if ((rc = rr.keys.reserve((size_t)total))) return rc;
-    if ((rc = rr.sorted.reserve((size_t)total))) return rc;
     static_assert(sizeof(long long) == sizeof(int64_t), "cand_indptr is the sort's segment offsets");
     HIP_TRY(hipMemcpyAsync(s.cand_indptr.ptr(), cand_indptr, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(upload(s.items, s.h_items.data(), n_items, st));
     HIP_TRY(hipMemcpyAsync(s.lists.cand.ptr(), cand_idx, (size_t)total * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(s.lists.cnt.ptr() + RS_CNT_REFUSAL, 0xff, 8, st));
-    const unsigned rbits = __builtin_bit_cast(unsigned, radius);
-    if (s.metric == FDR_METRIC_JACCARD) rs_x3_launch<FDR_METRIC_JACCARD>(s, st, n_items, q_lo, rbits);
-    else if (s.metric == FDR_METRIC_WEIGHTED_JACCARD) rs_x3_launch<FDR_METRIC_WEIGHTED_JACCARD>(s, st, n_items, q_lo, rbits);
-    else rs_x3_launch<FDR_METRIC_COSINE>(s, st, n_items, q_lo, rbits);
-    HIP_TRY(hipGetLastError());
     u64 refused = ~0ull;
-    HIP_TRY(hipMemcpyAsync(&refused, s.lists.cnt.ptr() + RS_CNT_REFUSAL, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = rs_ragged_run(s, call, radius, q_lo, total, s.cand_indptr.ptr(), s.lists.cand.ptr(), 0, &refused))) return rc;
     if (refused != ~0ull) {  // (nothing has been written to indptr_out)
         const long long row = (long long)(refused >> 32), pos = (long long)(refused & 0xffffffffull);
         return fail(FDR_E_ARG, "%s: query %lld, position %lld: the candidate (%d) is no row in [0, %lld)", who,
                     (long long)q_lo + row, pos, cand_idx[cand_indptr[row] + pos], s.n);
     }
-    rc = radius_offsets(rr, s.tmp, call, "hits", "hit counts", nullptr);
-    const long long hits = rr.counted;
-    if (rc || hits == 0) return rc;  // (no hit: the empty result is held)
-    auto sort = [&](void *tmp, size_t &bytes) {  // (a key lies below 2^62: distance bits <= those of 1.0f)
-        return rocprim::segmented_radix_sort_keys(tmp, bytes, rr.keys.ptr(), rr.sorted.ptr(), (unsigned)total, (unsigned)nq,
-                                                  s.cand_indptr.ptr(), s.cand_indptr.ptr() + 1, 0, 63, st);
-    };
-    if ((rc = rocprim_run(s.tmp, "rocprim::segmented_radix_sort_keys", sort))) return rc;
-    hipLaunchKernelGGL(radius_split_kernel<true>, dim3((unsigned)((hits + 255) / 256)), dim3(256), 0, st, hits,
-                       (const u64 *)rr.sorted.ptr(), rr.idx(), reinterpret_cast<float *>(rr.idx() + hits), (long long)nq,
-                       (const long long *)rr.off.ptr(), (const long long *)s.cand_indptr.ptr());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    rr.held = hits;
+    return FDR_OK;
+}
+
+// The held expansion (fdr_graph_expand, graph_expand.inc) scored on the held rows, straight from device memory: X3 on
+// work items listed from the expansion's host-side row pointer, the hit counts clamped to k_top ahead of the scan, and
+// from there fdr_rescore_rows_radius' sort and split unchanged: a row's result is the first min(hits, k_top) keys of
+// its sorted segment.  The expansion stays held.
+FDR_EXPORT int fdr_rescore_rows_refine(fdr_ctx *ctx, float radius, int32_t k_top, int64_t *indptr_out) {
+    static const char who[] = "rescore_rows_refine";
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    RescoreRowSet &s = ctx->rrs;
+    if (!s.valid) return fail(FDR_E_STATE, "%s: the context holds no re-score rows", who);
+    RadiusResult &rr = s.rr;
+    rr.drop();
+    const GraphExpandScratch &ge = ctx->ge;
+    if (ge.held < 0)
+        return fail(FDR_E_STATE, "%s: the context holds no expansion (fdr_graph_expand makes one; the next "
+                    "fdr_graph_expand and fdr_graph_free drop it)", who);
+    if (k_top < 1) return fail(FDR_E_ARG, "%s: k_top (%d) must be in [1, 2^31)", who, k_top);
+    if (!(radius >= 0.0f && radius <= 1.0f))  // (a NaN is not in range)
+        return fail(FDR_E_ARG, "%s: the radius must be in [0, 1], got %g", who, (double)radius);
+    if (radius == 0.0f) radius = 0.0f;  // (-0 is 0, as in fdr_rescore_rows_radius)
+    if (ge.n != s.n)
+        return fail(FDR_E_ARG, "%s: the expansion is of a graph on %lld rows, the re-score rows are %lld", who, ge.n, s.n);
+    if (!indptr_out) return fail(FDR_E_ARG, "%s: null indptr pointer", who);
+    const int64_t nq = ge.nq, total = ge.held;
+    if (nq == 0) return radius_none(rr, indptr_out);
+    if (total == 0) {  // (no candidate, no hit: the indptr alone)
+        for (int64_t r = 0; r <= nq; ++r) indptr_out[r] = 0;
+        rr.held = 0;
+        return FDR_OK;
+    }
+    s.h_items.clear();
+    try {  // (no exception leaves the C entry point)
+        for (int64_t r = 0; r < nq; ++r) {
+            const int64_t len = ge.h_off[r + 1] - ge.h_off[r];
+            for (int64_t b = 0; b * FDR_MAX_K < len; ++b) s.h_items.push_back(make_int2((int)r, (int)b));
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(FDR_E_NOMEM, "%s: out of host memory for the work items", who);
+    }
+    const RadiusCall call = {ctx->stream, who, nq, INT64_MAX, indptr_out};  // (no cap: fdr_graph_expand's held)
+    u64 refused = ~0ull;
+    if ((rc = rs_ragged_run(s, call, radius, ge.q_lo, total, ge.off.ptr(), ge.out.ptr(), k_top, &refused))) return rc;
+    if (refused != ~0ull)  // (fdr_graph_expand has checked every index)
+        return fail(FDR_E_HIP, "internal: %s: the held expansion names a row outside [0, %lld)", who, s.n);
     return FDR_OK;
 }
 

@@ -27,6 +27,13 @@ different distances.  label[r] in [0, C) numbers the components in ascending ord
 are a function of the edge set alone; size[c], int64, is the number of rows of component c.  A graph is refused for
 exactly what symmetrize_rows refuses, in both modes and in the same words; transpose is refused as a mode (its
 components are union's).
+
+Expansion (expand_rows: the statement fdr_graph_expand, csrc/graph_expand.inc, is held to).  N_f(x) is the first
+min(fan, len(x)) entries of row x in ascending order of key = distance bits << 32 | index.  Row r of the result holds s
+iff s is in N_f(r), or s != r and s is in N_f(t) for some t in N_f(r): the rows within two hops along the fan, the
+row's own index exactly when the row lists itself inside its fan.  Every row is strictly ascending by index and holds
+every index once.  Refused, over the whole graph and in the words above: an index outside [0, n); distance bits above
+0x7f800000.  An index listed twice in a row is not refused: it takes two places of the fan cut and comes out once.
 """
 import numpy as np
 
@@ -158,3 +165,74 @@ def component_labels(indptr, idx, dist, mode="union", max_distance=None):
     number[np.argsort(first)] = np.arange(first.size, dtype=np.int32)
     labels = number[found]
     return labels, np.bincount(labels, minlength=first.size).astype(np.int64)
+
+
+FDR_MAX_K = 128  # include/fedrann_hip.h
+
+
+def check_expand(indptr, idx, dist, fan, lo=0, hi=None):
+    """The argument checks expand_rows and _lib.check_graph_expand share (ValueError): the ragged graph, at least one
+    row, 1 <= fan <= FDR_MAX_K, [lo, hi) a range of the rows (hi None: n).  Returns (indptr, idx, dist, n, fan, lo, hi)."""
+    indptr, idx, dist = as_ragged((indptr, idx, dist))
+    n = indptr.size - 1
+    if n < 1:
+        raise ValueError("a graph has at least one row")
+    for name, v in (("fan", fan), ("lo", lo)) + ((("hi", hi),) if hi is not None else ()):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    fan, lo, hi = int(fan), int(lo), n if hi is None else int(hi)
+    if not 1 <= fan <= FDR_MAX_K:
+        raise ValueError("need 1 <= fan <= %d, got %d" % (FDR_MAX_K, fan))
+    if not 0 <= lo <= hi <= n:
+        raise ValueError("the rows [%d, %d) are no range of the n = %d rows" % (lo, hi, n))
+    return indptr, idx, dist, n, fan, lo, hi
+
+
+def expand_bound(indptr, fan):
+    """int64 [n]: fan-cut length times (1 + fan), an upper bound of what row r gathers before duplicates go that needs
+    the row pointer alone (the exact bound, |N_f(r)| + the sum of |N_f(t)| over t in N_f(r), needs the sorted rows)."""
+    return np.minimum(np.diff(np.asarray(indptr, np.int64)), int(fan)) * (1 + int(fan))
+
+
+def expand_rows(indptr, idx, dist, fan, lo=0, hi=None, piece_entries=1 << 24):
+    """The rows within two hops of the rows [lo, hi) of the ragged graph (indptr, idx, dist) along a fan of `fan`, see
+    the module's docstring: (indptr int64 [hi - lo + 1], idx int32), every row ascending by index, a function of the
+    input alone.  The whole graph is checked, whatever the range.  The rows are walked in pieces whose gathered entries
+    stay near piece_entries."""
+    indptr, idx, dist, n, fan, lo, hi = check_expand(indptr, idx, dist, fan, lo, hi)
+    lens = np.diff(indptr)
+    rows = np.repeat(np.arange(n, dtype=np.int64), lens)
+    t = idx.astype(np.int64)
+    bits = dist.view(np.uint32)
+    records = np.concatenate([rows[(t < 0) | (t >= n)] * 4, rows[bits > MAX_BITS] * 4 + 1])
+    if records.size:
+        worst = int(records.min())
+        raise ValueError("row %d: %s" % (worst // 4, RULES[worst % 4]))
+    # ---- the fan cut: every row by key, its first `fan` entries ----
+    order = np.lexsort((t, bits, rows))
+    keep = (np.arange(t.size, dtype=np.int64) - indptr[rows]) < fan  # (rows[order] == rows: the sort keeps the segments)
+    ft = t[order][keep]
+    flen = np.minimum(lens, fan)
+    fptr = np.zeros(n + 1, np.int64)
+    np.cumsum(flen, out=fptr[1:])
+    counts = np.zeros(hi - lo, np.int64)
+    parts = []
+    bound = expand_bound(indptr, fan)[lo:hi]
+    a = lo
+    while a < hi:
+        b = a + max(1, int(np.searchsorted(np.cumsum(bound[a - lo:]), piece_entries, side="right")))
+        b = min(b, hi)
+        one_r = np.repeat(np.arange(a, b, dtype=np.int64), flen[a:b])
+        one_t = ft[fptr[a]:fptr[b]]
+        reps = flen[one_t]
+        two_r = np.repeat(one_r, reps)
+        first = np.repeat(fptr[one_t] - (np.cumsum(reps) - reps), reps)  # N_f(t)'s start less the entry's place
+        two_s = ft[first + np.arange(two_r.size, dtype=np.int64)]
+        far = two_s != two_r
+        code = np.unique(np.concatenate([one_r * n + one_t, two_r[far] * n + two_s[far]]))
+        counts[a - lo:b - lo] = np.bincount(code // n - a, minlength=b - a)
+        parts.append((code % n).astype(np.int32))
+        a = b
+    out = np.zeros(hi - lo + 1, np.int64)
+    np.cumsum(counts, out=out[1:])
+    return out, np.concatenate(parts) if parts else np.zeros(0, np.int32)

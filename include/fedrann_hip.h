@@ -452,6 +452,41 @@ int fdr_graph_components(fdr_ctx *ctx, int32_t mode /* FDR_GRAPH_UNION | FDR_GRA
                          int32_t *label_out /* [n] */, int64_t *size_out /* [n] or NULL */,
                          int64_t *n_components_out);
 
+/* ---- expand a neighbour graph by one hop: the distinct rows within two hops  (the candidate generator of a list
+ *      refinement.  The reference's default search is NN-descent, nearest_neighbors.py:39-55, which improves a list by
+ *      looking among the neighbours of its neighbours; this call names those, fdr_rescore_rows_refine scores them) ----
+ * The graph is fdr_graph_symmetrize's: n rows, indptr int64 [n + 1], idx int32 and dist float32 [indptr[n]], rows in any
+ * order.  N_f(x) is the first min(fan, len(x)) entries of row x in ascending order of key = (uint64)distance bits << 32 |
+ * (uint32)index.  Row r of the result, for q_lo <= r < q_lo + nq, holds s iff
+ *   s is in N_f(r), or
+ *   s != r and s is in N_f(t) for some t in N_f(r);
+ * each row strictly ascending by index, every index once, at most fan + fan^2 entries: fedrann_amd.graph.expand_rows bit
+ * for bit, a function of the input alone (two runs give the same bytes).  A row's own index stays exactly when the row
+ * lists itself inside its fan, so whatever convention the search had survives.
+ * fdr_graph_expand counts: indptr_out int64 [nq + 1] takes the exact prefix sums, and the indices stay on the device,
+ * beside the held symmetrised graph and independent of it, until the next fdr_graph_expand or fdr_graph_free;
+ * fdr_graph_expand_fetch copies them out, idx_out int32 [entries], entries == indptr_out[nq] (another value: FDR_E_ARG;
+ * nothing held: FDR_E_STATE; 0 entries need no pointer).  Host pointers; both calls synchronise.
+ * Checked on the host (FDR_E_ARG): 1 <= fan <= FDR_MAX_K; 1 <= n < 2^31; [q_lo, q_lo + nq) is a range of the rows (nq == 0
+ * is FDR_OK and holds an empty result); 1 <= max_entries < 2^31; the indptr starts at 0, never decreases and totals
+ * below 2^31; null pointers (idx / dist may be null for a graph without entries); the block's upper bound, the sum over
+ * its rows r of |N_f(r)| + the sum over t in N_f(r) of |N_f(t)|, is below 2^31 (it is formed on the device in 64 bits
+ * and compared on the host before indptr_out is written; the message says to take fewer rows a call).  Checked on the
+ * device before anything is written to indptr_out (FDR_E_ARG, in fdr_graph_symmetrize's words, the smallest (row, rule)
+ * named), over the WHOLE graph, because any row can be some t: an index outside [0, n); distance bits above 0x7f800000.
+ * NOT refused: an index listed twice in one row.  It takes two places of the fan cut and comes out once.  A result of
+ * more than max_entries entries is refused (FDR_E_ARG) with indptr_out holding the counts.  After any refusal nothing
+ * is held.
+ * The call touches neither the sparse index, the dense index, the re-score rows, their held radius results, the held
+ * symmetrised graph nor fdr_last_knn_trace.  Device memory: 24 bytes per input entry (shared with
+ * fdr_graph_symmetrize's input), 12 per entry of the upper bound, 4 per result entry, 8 per row of the graph and 24 per
+ * row of the block, and rocprim's temporary storage; the buffers belong to the context, only grow and are freed by
+ * fdr_graph_free and fdr_destroy.  Cost: one segmented sort of the input rows by key, one of the bound's 32-bit indices
+ * by row, two scans; DESIGN.md section 5 (X4). */
+int fdr_graph_expand(fdr_ctx *ctx, int64_t n, const int64_t *indptr, const int32_t *idx, const float *dist, int32_t fan,
+                     int64_t q_lo, int64_t nq, int64_t max_entries, int64_t *indptr_out /* [nq + 1] */);
+int fdr_graph_expand_fetch(fdr_ctx *ctx, int64_t entries, int32_t *idx_out);
+
 /* ---- re-score candidate lists by exact distance on the sparse rows  (the second stage of an approximate search:
  *      NNDescent_ava.get_neighbors on the embeddings names the neighbours, nearest_neighbors.py:39-55, the boundary this
  *      library replaces; their distances there are the projection's, and this call puts the feature rows' own in their
@@ -518,7 +553,7 @@ int fdr_sparse_rescore(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_featur
  * (distance bits, index).  indptr_out int64 [nq + 1]: the exact prefix sums, indptr_out[0] = 0.  The result is held and
  * fdr_rescore_rows_radius_fetch copies it out: idx_out int32 [hits], dist_out float32 [hits]; `hits` must equal the
  * total (FDR_E_ARG otherwise); without a held result FDR_E_STATE; a fetch leaves it held, and the next
- * fdr_rescore_rows_* call other than _info, _knn and _radius_fetch drops it.  So:
+ * fdr_rescore_rows_* call other than _info, _knn and _radius_fetch drops it (_refine holds its own in its place).  So:
  *   - radius domain: 0 <= radius <= 1.  NaN, a negative radius and one above 1 are FDR_E_ARG; -0.0f is 0;
  *   - radius == 1 keeps every candidate (a distance lies in [0, 1]): the plain ragged re-score, indptr_out = cand_indptr;
  *   - below 1 a pair at exactly 1.0f is no hit, the radius searches' rule;
@@ -538,7 +573,18 @@ int fdr_sparse_rescore(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_featur
  * 40 waves; the keys land in the candidates' places, one segmented sort orders each row, and the hits, the first keys
  * of each sorted row, are compacted.  Cost: per pair the candidate's stored entries are read once per tile of the
  * query, as in fdr_sparse_rescore, without its upload; DESIGN.md section 5 (X3).  Not here: several devices, device
- * pointers. */
+ * pointers.
+ * fdr_rescore_rows_refine scores the context's HELD expansion (fdr_graph_expand) on the held rows, straight from device
+ * memory: the candidates never pass through host memory.  With the expansion's q_lo, nq and rows, row r of the result is
+ * what fdr_rescore_rows_radius(radius, q_lo, nq, the expansion) would hold, cut to its first k_top entries: the same
+ * kernel on work items listed from the expansion's host-side row pointer, the hit counts clamped to k_top ahead of their
+ * scan, the sort and the split unchanged.  indptr_out int64 [nq + 1]; the result is held and fetched with
+ * fdr_rescore_rows_radius_fetch under the rules above; the expansion stays held.  radius == 1 and k_top >= fan + fan^2
+ * is the plain ragged re-score of the expansion.  Refused: k_top outside [1, 2^31) and a radius outside [0, 1]
+ * (FDR_E_ARG; -0.0f is 0); no row set, or no held expansion (FDR_E_STATE); an expansion of a graph whose n differs from
+ * the rows' n (FDR_E_ARG); a null indptr_out.  Device memory and cost: fdr_rescore_rows_radius' without the candidates'
+ * upload (16 bytes per candidate of the expansion, 24 per row, 8 per FDR_MAX_K candidates of a row); DESIGN.md section
+ * 5 (X4).  Not here: NN-descent's new / old flags, sampling, several devices, device pointers. */
 int fdr_rescore_rows_build(fdr_ctx *ctx, int32_t metric, int64_t n, int64_t n_features, const int64_t *indptr,
                            const int32_t *indices, const float *values);
 int fdr_rescore_rows_info(fdr_ctx *ctx, int32_t *metric, int64_t *n, int64_t *stored, size_t *device_bytes);
@@ -548,6 +594,7 @@ int fdr_rescore_rows_knn(fdr_ctx *ctx, int64_t q_lo, int64_t nq, int32_t k_in, c
 int fdr_rescore_rows_radius(fdr_ctx *ctx, float radius, int64_t q_lo, int64_t nq, const int64_t *cand_indptr /* [nq + 1] */,
                             const int32_t *cand_idx, int64_t *indptr_out /* [nq + 1] */);
 int fdr_rescore_rows_radius_fetch(fdr_ctx *ctx, int64_t hits, int32_t *idx_out, float *dist_out);
+int fdr_rescore_rows_refine(fdr_ctx *ctx, float radius, int32_t k_top, int64_t *indptr_out /* [nq + 1] */);
 
 /* ---- device-resident API (multi-GPU host, bench.py) ----------------------------------------
  * All pointers are device pointers; work is enqueued on `stream` (a hipStream_t). */
