@@ -3,6 +3,8 @@ sets, incl. the reference's treatment of invalid characters, short and empty rea
 import numpy as np
 import pytest
 
+import _kmer_count_model as M
+from _kmer_inputs import revcomp
 from fedrann_amd import _lib
 from fedrann_amd import feature_extraction as fx
 from fedrann_amd import kmer_search as ks
@@ -99,6 +101,36 @@ def test_kmer_searcher_drop_in_writes_reference_files(ctx, oracle, tmp_path):
     assert np.array_equal(ix2[ip2[0]:ip2[1]], ix[ip[0]:ip[1]])
     freq = np.fromfile(str(tmp_path / "out" / "kmer_frequency.bin"), dtype="<u8").reshape(-1, 2)
     assert int(freq[:, 1].sum()) == ix.size
+
+
+@pytest.mark.parametrize("k", [15, 31])
+def test_kmer_search_beyond_one_trip_of_the_grid_stride_loop(ctx, oracle, k):
+    """The read set of the count's grid-stride test (_kmer_count_model: read boundaries and invalid bytes at the chunk
+    and stretch edges), tiled until some workgroup of ks_search_kernel takes a second chunk: min(chunks, CUs * 8)
+    workgroups of 4096 characters.  The base's total is odd, so every copy lies differently in the chunks.  The library
+    comes from the base; the expected CSR is the base's, repeated."""
+    need = ctx.device_info()["cus"] * 8 * M.CHUNK + 3 * M.CHUNK
+    base_seqs, base_off = M.grid_stride_base(k)
+    reads = M.to_reads(base_seqs, base_off)
+    fwd = []
+    for r in reads[::3]:
+        for w in (r[:k], r[-k:], r[len(r) // 2:len(r) // 2 + k]):
+            if len(w) == k and not w.translate(None, b"ACGT"):
+                fwd.append(w)
+    text = b"\n".join(fwd + [revcomp(w) for w in fwd]) + b"\n" + b"A" * k + b"\n"  # (+ what an empty read looks up)
+    codes = ks.load_kmer_library(text, k)
+    assert np.array_equal(codes, oracle.kmer_library(text, k)) and codes.size > 300
+    wp, wx = oracle.kmer_search(reads, codes, k)
+    assert wx.size > len(reads) // 4  # the library really is hit
+    times = M.times_to_exceed(int(base_off[-1]), need)
+    seqs, off, e = M.tiled(base_seqs, base_off, times)
+    print("grid-stride search: k = %d, %d CUs, %d copies of %d characters = %d characters (> %d)"
+          % (k, ctx.device_info()["cus"], times, e["base_total"], int(off[-1]), need))
+    assert int(off[-1]) > need and int(off[-1]) == seqs.size and e["copy_shifts"] == min(16, times)
+    ip, ix = ctx.kmer_search(seqs, off, codes, k)
+    want_ip = np.concatenate([np.zeros(1, dtype=np.int64)] + [wp[1:] + np.int64(t) * wx.size for t in range(times)])
+    assert np.array_equal(ip, want_ip), "row pointers differ"
+    assert np.array_equal(ix, np.tile(wx, times)), "library indices differ"
 
 
 @pytest.mark.parametrize("k,min_count", [(15, 2), (5, 1), (31, 1), (21, 3)])

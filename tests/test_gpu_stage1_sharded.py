@@ -44,6 +44,22 @@ def _runs(rng, W, n, lo=0, hi=1 << 40, empty=(), same=False, disjoint=False, big
     return runs
 
 
+def _runs_of(rng, lens, pool=None, ones=False):
+    """Runs of exactly these lengths: from one pool of codes (they overlap heavily), or, pool=None, from ranges of their
+    own, the later run the lower range."""
+    runs = []
+    for r, n in enumerate(lens):
+        if pool is None:
+            lo = (len(lens) - r) << 20
+            c = lo + rng.choice(3 * n + 1, size=n, replace=False)
+        else:
+            c = rng.choice(pool, size=n, replace=False)
+        c = np.sort(c.astype(np.uint64))
+        assert c.size == n and np.unique(c).size == n
+        runs.append((c, np.ones(n, dtype=np.uint64) if ones else rng.integers(1, 6, size=n, dtype=np.uint64)))
+    return runs
+
+
 def _want(runs, min_count):
     c = np.concatenate([r[0] for r in runs])
     n = np.concatenate([r[1] for r in runs])
@@ -103,6 +119,55 @@ def test_merge_large_sizes_not_multiple_of_a_tile(ctx):
     assert _check(ctx, runs, 3) > 0
 
 
+STRIDE_EDGE_LENS = (1, 1023, 1024, 1025, 2048, 2049, 0, 4096, 4097)  # (len - 1) // KM_STRIDE samples: 0 0 0 1 1 2 - 3 4
+
+
+@pytest.mark.parametrize("min_count", [1, 2])
+def test_merge_run_lengths_at_the_sample_stride(ctx, min_count):
+    rng = np.random.default_rng(21)
+    pool = np.unique(rng.integers(0, 1 << 40, size=5000, dtype=np.uint64))[:4500]
+    assert pool.size == 4500
+    kept = _check(ctx, _runs_of(rng, STRIDE_EDGE_LENS, pool=pool), min_count)
+    assert 0 < kept <= 4500
+    kept = _check(ctx, _runs_of(rng, STRIDE_EDGE_LENS), min_count)  # disjoint: nothing sums
+    assert kept == sum(STRIDE_EDGE_LENS) if min_count == 1 else 0 < kept < sum(STRIDE_EDGE_LENS)
+
+
+W_MAX = 256  # KM_MAX_RUNS: what km_tile_kernel's per-run arrays and its serial prefix are sized for
+
+
+def test_merge_of_256_random_runs(ctx):
+    rng = np.random.default_rng(22)
+    runs = _runs(rng, W_MAX, 300, hi=2000)
+    assert len(runs) == W_MAX and 200 < min(r[0].size for r in runs)
+    tot = _want(runs, 1)[1]
+    for min_count in (1, 2, int(np.median(tot))):
+        assert _check(ctx, runs, min_count) > 0
+    z = np.zeros(0, dtype=np.uint64)
+    with pytest.raises(_lib.FedrannHipError, match="1 .. 256 runs"):
+        ctx.kmer_count_merge(np.zeros(W_MAX + 2, dtype=np.int64), z, z, 1)  # (257 runs)
+
+
+@pytest.mark.parametrize("min_count,kept", [(1, 3000), (256, 3000), (257, 0)])
+def test_merge_of_256_identical_runs(ctx, min_count, kept):
+    """Every code tied 256 ways, each copy counting 1: the totals are 256.  Tiles of 256 x ~1500 codes, beyond
+    KM_CACHE, so the searches read global memory."""
+    rng = np.random.default_rng(23)
+    (codes, ones), = _runs_of(rng, [3000], ones=True)
+    assert _check(ctx, [(codes, ones)] * W_MAX, min_count) == kept
+
+
+@pytest.mark.parametrize("at", [0, 137, 255])
+def test_merge_of_255_empty_runs_and_a_real_one(ctx, at):
+    rng = np.random.default_rng(24 + at)
+    lens = [0] * W_MAX
+    lens[at] = 5000
+    runs = _runs_of(rng, lens)
+    assert _check(ctx, runs, 1) == 5000
+    assert 0 < _check(ctx, runs, 3) < 5000
+    assert _check(ctx, runs, 6) == 0
+
+
 def test_merge_of_nothing_and_bad_arguments(ctx):
     z = np.zeros(0, dtype=np.uint64)
     gc, gn = ctx.kmer_count_merge(np.zeros(4, dtype=np.int64), z, z, 1)
@@ -129,6 +194,51 @@ def test_export_cuts_the_unthresholded_table(ctx):
     wc, wn = ctx.kmer_count_finish(1)
     assert np.array_equal(hc, wc) and np.array_equal(counts.cpu().numpy().view(np.uint64), wn)
     assert off.tolist() == [0] + np.searchsorted(wc, spl.view(np.uint64)).tolist() + [n]
+
+
+def test_export_splitters_at_and_beyond_the_codes(ctx):
+    """km_parts_kernel: splitters below, above and equal to codes, repeated ones, one part, and more than 256 parts
+    (its second workgroup).  The table's last entry is the "no k-mer here" marker, which is not exported."""
+    s = synth_sequences(200, genome_len=20_000, mean_len=600, k=15, n_rate=2e-3, seed=4)
+    st = torch.cuda.current_stream().cuda_stream
+    ctx.kmer_count_begin(15)
+    ctx.kmer_count_add(s["seqs"], s["seq_off"])
+    n = int(ctx.kmer_count_export_dev(0, 1, stream=st)[-1])
+    codes = torch.empty(n, dtype=torch.int64, device="cuda")
+    counts = torch.empty(n, dtype=torch.int64, device="cuda")
+    assert ctx.kmer_count_export_dev(0, 1, codes.data_ptr(), counts.data_ptr(), stream=st).tolist() == [0, n]
+    hc = codes.cpu().numpy().view(np.uint64)
+    assert n > 1000 and hc[0] > 1 and np.all(hc[1:] > hc[:-1])
+    rng = np.random.default_rng(1)
+    many = np.sort(np.concatenate([rng.integers(0, int(hc[-1]) + 1000, size=279, dtype=np.uint64),
+                                   hc[rng.integers(0, n, size=20)]]))
+    first, mid, last, ones = int(hc[0]), int(hc[n // 2]), int(hc[-1]), (1 << 64) - 1
+    sets = {
+        "below the first code": [0],
+        "just below the first code": [first - 1],
+        "above the last code": [last + 1],
+        "the marker's value": [ones],
+        "the first, a middle and the last code": [first, mid, last],
+        "just above a code": [int(hc[7]) + 1],
+        "three equal splitters": [mid, mid, mid],
+        "below and above": [0, 0, last + 1, ones],
+        "299 sorted random splitters": many.tolist(),
+    }
+    assert many.size == 299
+    for name, spl in sets.items():
+        spl = np.array(spl, dtype=np.uint64)
+        spl_t = torch.from_numpy(spl.view(np.int64)).cuda()
+        off = ctx.kmer_count_export_dev(spl_t.data_ptr(), spl.size + 1, stream=st)
+        assert off.tolist() == [0] + np.searchsorted(hc, spl, "left").tolist() + [n], name
+    assert ctx.kmer_count_export_dev(0, 1, stream=st).tolist() == [0, n]  # one part
+    c2 = torch.zeros(n, dtype=torch.int64, device="cuda")
+    n2 = torch.zeros(n, dtype=torch.int64, device="cuda")
+    spl_t = torch.from_numpy(many.view(np.int64)).cuda()
+    ctx.kmer_count_export_dev(spl_t.data_ptr(), 300, c2.data_ptr(), n2.data_ptr(), stream=st)
+    wc, wn = ctx.kmer_count_finish(1)
+    assert wc.size == n
+    for c, m in ((codes, counts), (c2, n2)):
+        assert np.array_equal(c.cpu().numpy().view(np.uint64), wc) and np.array_equal(m.cpu().numpy().view(np.uint64), wn)
 
 
 # ---- the CLI: sharded stage 1 against the one-GPU run ----------------------------------------------------------------
